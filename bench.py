@@ -6,16 +6,18 @@ invalid_reassignment -> rapid_consensus; src/assemble.cpp:71-150) over one batch
 (otg_assemble_submit ran before the timed region), INCLUDING the hand-over of the allele records to the host:
 otg_assemble_collect at N=1, the RCCL gather to rank 0 + its one device-to-host copy at N>1.
 
-`value` is BASELINE configs[1] (10 000 regions x 1-5 kb, 30x ONT per GPU; weak scaling over identical per-GPU shards at every N).  At N = 1 the
-line also carries, under `config`:
+`value` is BASELINE configs[1] (10 000 regions x 1-5 kb, 30x ONT per GPU; weak scaling over identical per-GPU shards at every N).  A plain
+run does only what `value` needs: generate the inputs, warm up, time --steps steps, print the line (with --dump-outputs DIR, first write what
+the last timed step returned to DIR/<name>.npy).  With --full the line also carries the secondary measurements; at N = 1, under `config`:
   host_to_host   the same batch from host memory to records in host memory (SURVEY §8d's kernel-path metric: submit + run + collect);
   legs           configs[2] (the same with -r and soft-clipped divergent flanks), configs[4] (north_star's shape: 1-10 kb regions, the
                  12 500-region shard one GPU owns of the 100 000-region 8-GPU job) and configs[3] (otter genotype's allele clustering,
                  5 000 regions x 101 alleles), each with value / ms_per_step / stage_ms / roofline (/ cpu_baseline); and
                  configs[1]_adaptive: the timed workload again with both aligners under wfadaptive(10, 50, 1) (otg_params.heuristic — the mode
                  the reference's binary runs in if its WFA2-lib build defaults to it; `cpu_baseline.adaptive` is the oracle in that mode);
-  e2e            BED + BAM -> SAM text through the library's dispatcher on 10 000 loci of configs[1]'s shape.
---config N makes another configuration the timed one; --no-legs / --e2e-regions 0 / --no-cpu-baseline switch the extras off.
+  e2e            BED + BAM -> SAM text through the library's dispatcher on 10 000 loci of configs[1]'s shape;
+and `cpu_baseline` beside `value` (N > 1: the configs[4] leg).
+--config N makes another configuration the timed one; under --full, --no-legs / --e2e-regions 0 / --no-cpu-baseline switch single extras off.
 
 `python bench.py --gpus N` without a launcher starts the N ranks itself: the parent never imports torch or touches the
 GPU, it starts N fresh child processes (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set before anything is imported) and
@@ -56,6 +58,10 @@ def parse_args():
     ap.add_argument("--leg-steps", type=int, default=3)
     ap.add_argument("--e2e-regions", type=int, default=10000, help="regions of the file-to-text leg (BED + BAM -> SAM text through otg_assemble_files); 0: skip")
     ap.add_argument("--vcf-regions", type=int, default=5000, help="regions of the file-to-VCF leg (50-sample allele BAM + BED + FASTA -> VCF through otg_genotype_files; configs[3]'s size); 0: skip")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements: host-to-host passes, cpu_baseline, the legs of the other configs, the file-to-text and file-to-VCF legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step to DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     return ap.parse_args()
 
 
@@ -355,6 +361,82 @@ def stage_ms(st):
     return {k: round(float(st[k]), 2) for k in ("ms_realign", "ms_edit", "ms_cluster", "ms_reassign", "ms_affine", "ms_poa", "ms_total")}
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_BUDGET = 64 << 20      # bytes of all .npy payloads together
+DUMP_REGIONS = 20000        # more regions than this: the records of a fixed, seeded sample of them
+DUMP_SEQ_REGIONS = 256      # regions whose allele sequences are written byte for byte (every allele also gets a CRC-32 of its sequence)
+
+
+def _region_sample(n, k, seed):
+    import numpy as np
+    return np.arange(n) if n <= k else np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def _spans(first, count):
+    """indices first[i] .. first[i] + count[i] - 1 of every i, concatenated"""
+    import numpy as np
+    first = np.asarray(first, dtype=np.int64); count = np.asarray(count, dtype=np.int64)
+    return np.repeat(first - np.cumsum(count) + count, count) + np.arange(int(count.sum()), dtype=np.int64)
+
+
+def _write_dump(path, arrays):
+    """arrays: ordered (name, array); integers and float32 fields as float64 (exact), sequence bytes as float32; the last array is cut to the budget"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET
+    for name, a in arrays:
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.uint8 else np.float64)
+        if a.nbytes > left:
+            a = a[:left // a.itemsize]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+
+
+def dump_assemble(path, res, batch_regions=None):
+    """What the caller of the timed assemble path holds after its last step: per region the result record, per allele the record and its sequence,
+    per read the cluster label (N = 1; the gathered records at N > 1 carry no labels)."""
+    import zlib
+    import numpy as np
+    regions, alleles, seqs = res["regions"], res["alleles"], res["seqs"]
+    n = len(regions)
+    sel = _region_sample(n, DUMP_REGIONS, 1)
+    out = []
+    if len(sel) < n:
+        out.append(("region_index", sel))
+        alleles = alleles[_spans(regions["first_allele"][sel], regions["n_alleles"][sel])]
+    for f in regions.dtype.names:
+        out.append(("regions_" + f, regions[f][sel]))
+    for f in alleles.dtype.names:
+        out.append(("alleles_" + f, alleles[f]))
+    out.append(("alleles_seq_crc32", np.array([zlib.crc32(seqs[int(a["seq_off"]):int(a["seq_off"]) + int(a["seq_len"])].tobytes()) for a in alleles], dtype=np.int64)))
+    if "labels" in res:
+        lab = res["labels"]
+        if len(sel) < n and batch_regions is not None:
+            lab = lab[_spans(batch_regions["first_read"][sel], batch_regions["n_reads"][sel])]
+        out.append(("labels", lab))
+    ss = _region_sample(n, DUMP_SEQ_REGIONS, 2)
+    sa = res["alleles"][_spans(regions["first_allele"][ss], regions["n_alleles"][ss])]
+    out.append(("seq_sample_regions", ss))
+    out.append(("seq_sample_lens", sa["seq_len"]))
+    parts = [seqs[int(a["seq_off"]):int(a["seq_off"]) + int(a["seq_len"])] for a in sa]
+    out.append(("seq_sample", np.concatenate(parts) if parts else np.zeros(0, np.uint8)))
+    _write_dump(path, out)
+
+
+def dump_genotype(path, res, first_allele, n_alleles):
+    """otg_genotype_cluster_batch's outputs: per allele gt / gt_l / gt_k / hsd / reps, per region n_gt"""
+    gt, gl, gk, hsd, ngt, reps = res
+    n = len(n_alleles)
+    sel = _region_sample(n, DUMP_REGIONS // 4, 1)
+    out = []
+    if len(sel) < n:
+        out.append(("region_index", sel))
+        idx = _spans(first_allele[sel], n_alleles[sel])
+        gt, gl, gk, hsd, reps, ngt = gt[idx], gl[idx], gk[idx], hsd[idx], reps[idx], ngt[sel]
+    out += [("gt", gt), ("gt_l", gl), ("gt_k", gk), ("hsd", hsd), ("reps", reps), ("n_gt", ngt)]
+    _write_dump(path, out)
+
+
 # ------------------------------------------------------------------------------------------------ one rank
 def run_rank(args):
     rank = int(os.environ.get("RANK", "0"))
@@ -386,18 +468,18 @@ def run_rank(args):
     # same bytes whatever the world size)
     batch = synth.config_batch(cfg, n_regions, first_chunk=rank * (n_regions // synth.CHUNK) if world > 1 else 0, workers=workers)
     legs_in = {}
-    want_legs = world == 1 and not args.no_legs and args.config is None and args.regions is None
+    want_legs = args.full and world == 1 and not args.no_legs and args.config is None and args.regions is None
     if want_legs:
         legs_in[2] = synth.config_batch(2, workers=workers)
         legs_in[4] = synth.config_batch(4, synth.CONFIGS[4]["n_regions"] // 8, workers=workers)
         legs_in[3] = synth.config_batch(3, workers=workers)
     # N > 1: north_star's own shape rides along — configs[4], the 100 000-region job of 1-10 kb loci, 12 500 regions per GPU (rank r's contiguous shard)
-    want_leg4_multi = world > 1 and not args.no_legs and args.config is None and args.regions is None
+    want_leg4_multi = args.full and world > 1 and not args.no_legs and args.config is None and args.regions is None
     if want_leg4_multi:
         n4 = reh_regions if reh_regions else synth.CONFIGS[4]["n_regions"] // 8
         legs_in[4] = synth.config_batch(4, n4, first_chunk=rank * (n4 // synth.CHUNK), workers=workers)
     gen_s = time.perf_counter() - t_gen
-    fixture = start_fixture(args.e2e_regions) if (args.e2e_regions > 0 and world == 1) else None
+    fixture = start_fixture(args.e2e_regions) if (args.full and args.e2e_regions > 0 and world == 1) else None
     gt_fixture = start_gt_fixture(args.vcf_regions) if (args.vcf_regions > 0 and want_legs) else None
 
     import torch
@@ -424,7 +506,7 @@ def run_rank(args):
             torch.cuda.synchronize()
 
     # ---- configs[3]: otter genotype's allele clustering (operator-level entry: host buffers in, host buffers out)
-    def genotype_run(gb, steps, warmup):
+    def genotype_run(gb, steps, warmup, dump_dir=None):
         P = abi.default_params()
         ga = (gb["arena"], gb["seq_off"], gb["seq_len"], np.ascontiguousarray(gb["first_allele"][:-1]), gb["n_alleles"])
         for _ in range(warmup):
@@ -435,6 +517,8 @@ def run_rank(args):
             res = ctx.genotype_cluster_batch(P, *ga)
             kms.append(ctx.last_kernel_ms())
         dt = time.perf_counter() - t0
+        if dump_dir:
+            dump_genotype(dump_dir, res, ga[3], ga[4])
         nreg = len(gb["n_alleles"])
         nbytes = int(gb["seq_len"].astype(np.int64).sum()) + 65 * 8 * len(gb["seq_len"])        # allele bytes + one 65-bin usage vector per allele
         k = float(np.mean(kms))
@@ -456,12 +540,12 @@ def run_rank(args):
         return {"value": round(n / dt, 2), "unit": "regions/s", "cores": 1, "kind": "port", "sample": "first %d regions, 1 thread, oracle anallele_cluster, %.1f s" % (n, dt)}
 
     if cfg == 3:          # --config 3: the genotype leg as the timed workload
-        out3, P3, ga3 = genotype_run(batch, args.steps, args.warmup)
+        out3, P3, ga3 = genotype_run(batch, args.steps, args.warmup, args.dump_outputs if rank == 0 else None)
         line = {"metric": "regions/sec (otter genotype allele clustering) on synthetic allele sets", "value": out3["value"], "unit": "regions/s", "n_gpus": world,
                 "steps": args.steps, "warmup": args.warmup, "ms_per_step": out3["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                 "dtype": "f64", "data": "synthetic", "config": dict(workload=synth.config_workload(3, n_regions, world), **{k: v for k, v in out3.items() if k not in ("roofline", "value", "unit", "ms_per_step", "steps")}),
                 "roofline": out3["roofline"]}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = genotype_cpu(P3, ga3)
         if rank == 0:
             print(json.dumps(line), flush=True)
@@ -488,11 +572,13 @@ def run_rank(args):
                 if rank == 0:
                     info["records"] = len(g["alleles"])
                     info["gather_bytes"] = int(g["alleles"].nbytes + g["seqs"].nbytes + g["regions"].nbytes)
+                    info["result"] = g
             else:
                 t0 = time.perf_counter()
                 res = ctx.assemble_collect()       # allele records + sequences + region results to host memory
                 info["collect_ms"] = (time.perf_counter() - t0) * 1000.0
                 info["records"] = len(res["alleles"])
+                info["result"] = res
 
         for _ in range(warmup):
             step()
@@ -513,7 +599,10 @@ def run_rank(args):
             h2h = (time.perf_counter() - t1) / h2h_passes
         return {"dt": dt, "kstats": kstats, "info": info, "submit_ms": submit_ms, "h2h_s": h2h, "params": params}
 
-    r = assemble_run(cfg, batch, args.steps, args.warmup, min(3, max(1, args.steps)), args.heuristic)
+    r = assemble_run(cfg, batch, args.steps, args.warmup, min(3, max(1, args.steps)) if args.full else 0, args.heuristic)
+    if args.dump_outputs and rank == 0:
+        dump_assemble(args.dump_outputs, r["info"]["result"], batch["regions"])
+    r["info"].pop("result", None)
     st = r["kstats"][-1]
     regions_ok = int(st["n_regions_ok"])
     dt = r["dt"]
@@ -561,18 +650,19 @@ def run_rank(args):
                    "wavefront_cells": int(st["edit_cells"]) + int(st["affine_cells"]),
                    "exp_variant": "glibc-fma" if ctx.exp_variant else "glibc-nofma",
                    "h2d_submit_ms": round(r["submit_ms"], 2), "input_bytes": int(batch["arena"].size + batch["reads"].nbytes + batch["regions"].nbytes),
-                   "allele_records": info.get("records"), "synthetic_input_generation_s": round(gen_s, 1),
-                   "host_to_host": {"regions_per_s": round(regions_ok / r["h2h_s"], 2), "ms": round(r["h2h_s"] * 1000.0, 2),
-                                    "what": "SURVEY 8(d): otg_assemble_submit (H2D) + run + collect (D2H), mean of %d passes" % min(3, max(1, args.steps))}},
+                   "allele_records": info.get("records"), "synthetic_input_generation_s": round(gen_s, 1)},
         "roofline": roofline(r["kstats"], cfg, n_regions, adaptive=args.heuristic != "none"),
     }
+    if r["h2h_s"] is not None:
+        out["config"]["host_to_host"] = {"regions_per_s": round(regions_ok / r["h2h_s"], 2), "ms": round(r["h2h_s"] * 1000.0, 2),
+                                         "what": "SURVEY 8(d): otg_assemble_submit (H2D) + run + collect (D2H), mean of %d passes" % min(3, max(1, args.steps))}
     if leg4_multi is not None:
         out["config"]["legs"] = {"configs[4]": leg4_multi}
     if world > 1:
         out["config"]["gather"] = {"path": "device buffers -> RCCL gather -> one D2H on rank 0", "bytes": info.get("gather_bytes"), "ms_last_step": round(info.get("gather_ms", 0.0), 2)}
     else:
         out["config"]["collect_ms_last_step"] = round(info.get("collect_ms", 0.0), 2)
-    if not args.no_cpu_baseline and world == 1:        # rank 0 at N=1 only
+    if args.full and not args.no_cpu_baseline and world == 1:        # rank 0 at N=1 only
         try:
             pa = abi.default_params(realign=r["params"].realign, heuristic=abi.OTG_HEURISTIC_WFADAPTIVE)
             out["cpu_baseline"] = cpu_baseline(batch, r["params"], args.cpu_seconds, nth, adaptive_params=pa if args.heuristic == "none" else None)

@@ -113,7 +113,7 @@ for k, c in agg.items():
     kernels[k] = derive(c, n)
     for name, v in c.items():
         groups[g][name] += v
-# launches of each chain inside the profiled process (bench.py --steps 1 --warmup 0 = the timed step + the host-to-host pass): counted on a kernel
+# launches of each chain inside the profiled process (bench.py --steps 1 --warmup 0 = the timed step, + the host-to-host pass under --full): counted on a kernel
 # that runs exactly once per chain launch
 def n_of(name, default):
     for k in kernels:

@@ -114,7 +114,7 @@ def test_bench_multi_rank_control_flow_rehearsal(gpu):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     gpu.trim()
     env = dict(os.environ, OTG_BENCH_REHEARSAL="1", OTG_BENCH_REHEARSAL_REGIONS="250")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--leg-steps", "1"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--leg-steps", "1", "--full"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
