@@ -132,6 +132,20 @@ int otg_edit_distance_batch(otg_ctx* ctx,
                             const otg_align_task* tasks, uint32_t n_tasks,
                             int32_t* scores_out, uint64_t* cells_out);
 
+/* Replaces WFAlignerEdit(Alignment, MemoryMed)::alignEnd2End + getAlignmentScore() + getAlignmentCigar()
+ * (src/compare.cpp:59-61,95).  End-to-end only: a task with endsfree != 0 is OTG_ERR_ARG, and so is a context whose heuristic is
+ * OTG_HEURISTIC_WFADAPTIVE (exact alignment only).  scores_out[i] = unit-cost edit distance.  Op strings as otg_affine_align_batch
+ * (M X I D, one char per column, I consumes text, D consumes pattern; bytes compared raw), the tie-break of WFA2-lib's edit piggy-back
+ * (DESIGN.md §3).  cigar_arena == NULL: only cigar_len_out (= alignment columns) is produced, cigar_off_out may be NULL.
+ * *cigar_bytes_used = total length; OTG_ERR_CAPACITY when cigar_capacity is smaller.                                              */
+int otg_edit_align_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_bytes,
+                         const otg_align_task* tasks, uint32_t n_tasks, int32_t* scores_out,
+                         uint64_t* cigar_off_out, uint32_t* cigar_len_out,
+                         uint8_t* cigar_arena, uint64_t cigar_capacity, uint64_t* cigar_bytes_used);
+/* HIP-event times (ms) of the latest otg_edit_align_batch on this context: the score chain and the provenance pass (which includes
+ * the backtrace and the unpack).  Measurement hook; the reference has no counterpart. */
+int otg_edit_align_last_ms(otg_ctx* ctx, double* score_ms, double* prov_ms);
+
 /* Replaces WFAlignerGapAffine(x,o,e, Alignment, MemoryMed)::alignEnd2End/alignEndsFree +
  * getAlignmentCigar() (src/assemble.cpp:50, src/analignments.cpp:25,31,37,268-280).
  * scores_out[i] = gap-affine penalty (>= 0; WFA2 reports its negative).  The op string of task i
@@ -498,6 +512,62 @@ typedef struct otg_genotype_job {
   uint32_t    reserved;
 } otg_genotype_job;
 int otg_genotype_files(const otg_genotype_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
+/* ---------------------------------------------------------------------------------------------
+ * `otter compare` (src/compare.cpp, src/command_compare.cpp): truth alleles against assembled alleles per BED region.
+ * ------------------------------------------------------------------------------------------- */
+/* The allele records of each region as compare() reads them (src/compare.cpp:26-48,104-105), with its own sample map: sample0 (the truth
+ * BAM's first @RG) -> 0, then sample1 (the query BAM's first @RG) -> 1; one key (-> 1) when the names are equal.  An allele whose read group
+ * is not in the map is the reference's exit(1): OTG_ERR_ARG.  truth != 0 (local_parse_analleles): only records whose name starts with the
+ * chromosome are looked at, and each of them appends its `sp:A` value to `spannings` (u or absent -1, b 0, l 1, r 2, n 3, anything else
+ * nothing) whether or not its `ta` tag selects it — so spannings[i] need not belong to allele i, as in the reference.  first_spanning has
+ * n_regions + 1 entries (in-out counter *n_spannings).  The query side (truth == 0) is parse_analleles.  Regions whose query fails add
+ * "WARNING: query failed at region chr:start-end\n" to `warn` (nullable; in-out *warn_len).  Otherwise as otg_ingest_alleles. */
+int otg_ingest_compare_alleles(otg_bam* bam, const char* sample0, const char* sample1, int32_t truth, const otg_bed* beds, const char* chr_arena,
+                               uint32_t n_regions, int32_t threads, uint8_t* arena, uint64_t arena_capacity, uint64_t* arena_used,
+                               otg_allele* alleles, uint32_t alleles_capacity, uint32_t* n_alleles, uint32_t* first_allele,
+                               int32_t* spannings, uint32_t spannings_capacity, uint32_t* n_spannings, uint32_t* first_spanning,
+                               char* warn, uint64_t warn_capacity, uint64_t* warn_len);
+typedef struct otg_compare_counts {
+  uint64_t n_compared;           /* regions that printed their two lines                             */
+  uint64_t skip_many_truth;      /* > 2 truth alleles                                                 */
+  uint64_t skip_one_truth;       /* 1 truth allele                                                    */
+  uint64_t skip_no_truth;        /* 0 truth alleles                                                   */
+  uint64_t skip_no_query;        /* 0 query alleles                                                   */
+} otg_compare_counts;
+/* The region logic of compare() (src/compare.cpp:106-146) on ingested alleles: host code.  Region r has truth alleles
+ * truth[truth_first[r] .. truth_first[r+1]), spanning values spannings[span_first[r] ..), query alleles likewise.  A region with exactly two
+ * truth alleles and at least one query allele has 2 x max(n_query, 2) pairs (the single query allele is duplicated), truth-major, at
+ * pair_first[r] ..: pair_edit / pair_ops = edit distance and alignment columns of truth i against query j aligned end-to-end with the longer
+ * one as the pattern (ties: the query) — otg_edit_align_batch.  Pairs the reference does not align (equal alleles, "N" / "NDNNN") take their
+ * fixed values here, whatever the arrays hold.  Every other region is skipped with the reference's warning line (no timestamp) in `warn`.
+ * Output lines: region, truth length, query length, spanning, edit, ops (the two doubles as ostream prints them: %g).  A spanning index past
+ * the values the region pushed prints -1 (the reference reads outside its vector there).  Same buffer protocol as otg_emit_alleles for both
+ * buffers (warn nullable). */
+int otg_compare_emit(const otg_bed* beds, const char* chr_arena, uint32_t n_regions,
+                     const uint32_t* truth_first, const otg_allele* truth, const uint8_t* truth_seqs,
+                     const uint32_t* span_first, const int32_t* spannings,
+                     const uint32_t* query_first, const otg_allele* query, const uint8_t* query_seqs,
+                     const uint64_t* pair_first, const double* pair_edit, const double* pair_ops,
+                     char* out, uint64_t out_capacity, uint64_t* out_len,
+                     char* warn, uint64_t warn_capacity, uint64_t* warn_len, otg_compare_counts* counts);
+/* `otter compare` from files to text in one call — compare() (src/compare.cpp:68-150): BED regions in bounded batches through the two ingests
+ * (host threads), the edit alignments of all pairs of a batch on the device (otg_edit_align_batch, exact), and otg_compare_emit; text in BED
+ * order (the reference's threads interleave theirs).  The ingest of the next batch overlaps the device work and the emit of the current one.
+ * warn (nullable) receives the reference's warning lines without the timestamp.  stats: n_regions_ok = compared regions, n_regions_skipped
+ * the rest, n_alleles = truth + query alleles, n_reads = aligned pairs. */
+typedef struct otg_compare_job {
+  const char* truth_bam_path;    /* first positional <BAM>: the truth alleles                        */
+  const char* query_bam_path;    /* second positional <BAM>: the assembled alleles                   */
+  const char* bed_path;          /* -b                                                               */
+  int32_t     threads;           /* -t: host threads of the ingest                                   */
+  int32_t     device;            /* HIP device ordinal                                               */
+  uint32_t    batch_regions;     /* regions per batch, 0 = 1024                                      */
+  uint32_t    reserved;
+  otg_write_fn warn;             /* nullable                                                         */
+  void*       warn_user;
+} otg_compare_job;
+int otg_compare_files(const otg_compare_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
+
 /* The dispatcher keeps its per-device contexts (and their HBM workspaces) for the next job of the process; this frees them. */
 void otg_assemble_files_release(void);
 

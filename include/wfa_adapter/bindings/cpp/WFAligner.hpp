@@ -86,7 +86,13 @@ class WFAligner {
     t.pattern_begin_free = pbf; t.pattern_end_free = pef; t.text_begin_free = tbf; t.text_end_free = tef; t.endsfree = endsfree; t._pad = 0;
     int32_t sc = 0;
     int rc;
-    if (!affine()) {
+    if (!affine() && scope_ == Alignment && !endsfree) {
+      // WFAlignerEdit(Alignment): score and op string of the edit piggy-back (src/compare.cpp:59-61,95); ends-free keeps the score path
+      uint64_t off = 0, used = 0; uint32_t len = 0;
+      ops_.resize(pattern.size() + text.size() + 64);
+      rc = otg_edit_align_batch(ctx_, (const uint8_t*)arena_.data(), arena_.size(), &t, 1, &sc, &off, &len, (uint8_t*)&ops_[0], ops_.size(), &used);
+      if (rc == OTG_OK) { score_ = sc; cigar_.assign(ops_.data() + off, len); }
+    } else if (!affine()) {
       rc = otg_edit_distance_batch(ctx_, (const uint8_t*)arena_.data(), arena_.size(), &t, 1, &sc, nullptr);
       if (rc == OTG_OK) score_ = sc;                       // edit distance: reported positive
     } else {

@@ -19,6 +19,7 @@ EXPORTS = [
     "otg_ingest_regions_named", "otg_emit_reads", "otg_parse_bed_file", "otg_fasta_open", "otg_fasta_close", "otg_fasta_n_seqs",
     "otg_fasta_seq", "otg_fasta_fetch", "otg_fasta_region_flanks",
     "otg_bam_sample_index", "otg_bam_sample", "otg_ingest_alleles", "otg_emit_vcf_header", "otg_emit_vcf_lines", "otg_emit_genotype_lengths", "otg_assemble_files", "otg_assemble_files_release", "otg_assemble_batch_plan", "otg_genotype_files", "otg_wgat",
+    "otg_edit_align_batch", "otg_edit_align_last_ms", "otg_ingest_compare_alleles", "otg_compare_emit", "otg_compare_files",
     "otg_comm_unique_id", "otg_comm_create", "otg_comm_destroy", "otg_gather_sizes", "otg_gather_records",
 ]
 
@@ -109,6 +110,33 @@ class Context:
                                              abi.ptr(scores), abi.ptr(cells))
         self._check(rc, "otg_edit_distance_batch")
         return (scores, cells) if want_cells else scores
+
+    def edit_align_batch(self, arena, tasks, want_cigars=True):
+        """otg_edit_align_batch: end-to-end unit-cost alignments with op strings -> (scores, list of op strings); want_cigars=False
+        asks for the column counts only -> (scores, lengths)."""
+        n = len(tasks)
+        scores = np.zeros(n, dtype=np.int32)
+        off = np.zeros(n, dtype=np.uint64)
+        ln = np.zeros(n, dtype=np.uint32)
+        used = C.c_uint64(0)
+        if want_cigars:
+            cap = int(tasks["pattern_len"].astype(np.int64).sum() + tasks["text_len"].astype(np.int64).sum()) + 64
+            out = np.zeros(cap, dtype=np.uint8)
+        else:
+            cap, out = 0, None
+        rc = self._L.otg_edit_align_batch(self._h, abi.ptr(arena), C.c_uint64(arena.size), abi.ptr(tasks), C.c_uint32(n), abi.ptr(scores),
+                                          abi.ptr(off) if want_cigars else None, abi.ptr(ln), abi.ptr(out) if want_cigars else None,
+                                          C.c_uint64(cap), C.byref(used))
+        self._check(rc, "otg_edit_align_batch")
+        if not want_cigars:
+            return scores, ln
+        return scores, [out[int(off[i]):int(off[i]) + int(ln[i])].tobytes() for i in range(n)]
+
+    def edit_align_last_ms(self):
+        """(score chain ms, provenance pass ms) of the latest edit_align_batch (HIP events)."""
+        a, b = C.c_double(0), C.c_double(0)
+        self._check(self._L.otg_edit_align_last_ms(self._h, C.byref(a), C.byref(b)), "otg_edit_align_last_ms")
+        return a.value, b.value
 
     def affine_align_batch(self, arena, tasks, x=4, o=6, e=2, want_cells=False):
         n = len(tasks)
@@ -390,6 +418,34 @@ class Bam:
                 raise OtterGpuError("otg_ingest_alleles failed (%d): %s" % (rc, (self._L.otg_last_error(None) or b"").decode()))
             return {"alleles": np.ascontiguousarray(alleles[:na.value]), "first_allele": first, "arena": np.ascontiguousarray(arena[:used.value + 64])}
 
+    def ingest_compare(self, regions, sample0, sample1, truth, threads=1):
+        """otg_ingest_compare_alleles: the allele records of each region as `otter compare` reads them (sample map {sample0: 0, sample1: 1};
+        truth=True: local_parse_analleles, with the spanning values) -> {"alleles", "first_allele", "arena", "spannings", "first_spanning", "warn"}."""
+        beds, carena = regions if isinstance(regions, tuple) else abi.make_beds(regions)
+        fsz = os.path.getsize(self._path)
+        cap_n, cap_a, cap_s, cap_w = max(1024, fsz // 32), max(1 << 20, 8 * fsz), max(1024, fsz // 32), 1 << 16
+        first = np.zeros(len(beds) + 1, dtype=np.uint32)
+        sfirst = np.zeros(len(beds) + 1, dtype=np.uint32)
+        while True:
+            alleles = np.zeros(cap_n, dtype=abi.allele_dt)
+            arena = np.zeros(cap_a, dtype=np.uint8)
+            sp = np.zeros(cap_s, dtype=np.int32)
+            warn = np.zeros(cap_w, dtype=np.uint8)
+            used, na, ns, wl = C.c_uint64(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+            rc = self._L.otg_ingest_compare_alleles(self._h, C.c_char_p(sample0.encode()), C.c_char_p(sample1.encode()), C.c_int32(int(truth)),
+                                                    abi.ptr(beds), abi.ptr(carena, C.c_char_p), C.c_uint32(len(beds)), C.c_int32(threads),
+                                                    abi.ptr(arena), C.c_uint64(cap_a), C.byref(used), abi.ptr(alleles), C.c_uint32(cap_n), C.byref(na),
+                                                    abi.ptr(first), abi.ptr(sp), C.c_uint32(cap_s), C.byref(ns), abi.ptr(sfirst),
+                                                    abi.ptr(warn, C.c_char_p), C.c_uint64(cap_w), C.byref(wl))
+            if rc == abi.OTG_ERR_CAPACITY:
+                cap_n, cap_a, cap_s, cap_w = max(cap_n, na.value + 16), max(cap_a, used.value + 4096), max(cap_s, ns.value + 16), max(cap_w, wl.value + 64)
+                continue
+            if rc != 0:
+                raise OtterGpuError("otg_ingest_compare_alleles failed (%d): %s" % (rc, (self._L.otg_last_error(None) or b"").decode()))
+            return {"alleles": np.ascontiguousarray(alleles[:na.value]), "first_allele": first, "arena": np.ascontiguousarray(arena[:used.value + 64]),
+                    "spannings": np.ascontiguousarray(sp[:ns.value]) if truth else np.zeros(0, np.int32),
+                    "first_spanning": sfirst if truth else np.zeros(len(beds) + 1, np.uint32), "warn": warn[:wl.value].tobytes()}
+
     def ingest(self, regions, offset_l=0, offset_r=0, mapq=0, nonprimary=False, omit_nonspanning=False, read_quality=0.0, threads=1,
                names=False):
         """regions: list of (chr, start, end), or the (beds, chr_arena) pair of parse_bed_file -> batch dict {"arena", "reads",
@@ -670,3 +726,58 @@ def wgat(bam, regions, read_group="", fasta=False, offset_l=1, offset_r=0):
     if rc != 0:
         raise OtterGpuError("otg_wgat failed (%d): %s" % (rc, _err(L)))
     return b"".join(chunks), int(nrec.value)
+
+
+def compare_emit(regions, truth, query, pair_first, pair_edit, pair_ops):
+    """otg_compare_emit: the region logic of `otter compare` on ingested alleles (dicts of Bam.ingest_compare) and per-pair (edit, ops)
+    -> (text bytes, warning bytes, counts dict)."""
+    L = load()
+    beds, carena = regions if isinstance(regions, tuple) else abi.make_beds(regions)
+    pair_first = np.ascontiguousarray(pair_first, dtype=np.uint64)
+    pe = np.ascontiguousarray(pair_edit, dtype=np.float64)
+    po = np.ascontiguousarray(pair_ops, dtype=np.float64)
+    if pe.size == 0:
+        pe, po = np.zeros(1), np.zeros(1)
+    sp = truth["spannings"] if truth["spannings"].size else np.zeros(1, np.int32)
+    cnt = abi.CompareCounts()
+    need, wneed = C.c_uint64(0), C.c_uint64(0)
+    args = lambda out, cap, w, wcap: (abi.ptr(beds), abi.ptr(carena, C.c_char_p), C.c_uint32(len(beds)),
+                                      abi.ptr(truth["first_allele"]), abi.ptr(truth["alleles"]), abi.ptr(truth["arena"]),
+                                      abi.ptr(truth["first_spanning"]), abi.ptr(sp),
+                                      abi.ptr(query["first_allele"]), abi.ptr(query["alleles"]), abi.ptr(query["arena"]),
+                                      abi.ptr(pair_first), abi.ptr(pe), abi.ptr(po), out, C.c_uint64(cap), C.byref(need), w, C.c_uint64(wcap),
+                                      C.byref(wneed), C.byref(cnt))
+    rc = L.otg_compare_emit(*args(None, 0, None, 0))
+    if rc not in (0, abi.OTG_ERR_CAPACITY):
+        raise OtterGpuError("otg_compare_emit failed (%d): %s" % (rc, (L.otg_last_error(None) or b"").decode()))
+    out = C.create_string_buffer(need.value + 1)
+    w = C.create_string_buffer(wneed.value + 1)
+    rc = L.otg_compare_emit(*args(out, need.value, w, wneed.value))
+    if rc != 0:
+        raise OtterGpuError("otg_compare_emit failed (%d): %s" % (rc, (L.otg_last_error(None) or b"").decode()))
+    return out.raw[:need.value], w.raw[:wneed.value], {k: getattr(cnt, k) for k, _ in abi.CompareCounts._fields_}
+
+
+def compare_files(truth_bam, query_bam, bed, threads=1, device=0, batch_regions=0):
+    """otg_compare_files: `otter compare` from files to text.  Returns (text bytes, warning bytes, stats dict)."""
+    L = load()
+    job = abi.CompareJob()
+    job.truth_bam_path = truth_bam.encode(); job.query_bam_path = query_bam.encode(); job.bed_path = bed.encode()
+    job.threads = threads; job.device = device; job.batch_regions = batch_regions
+    chunks, warns = [], []
+
+    def sink(_user, data, n):
+        chunks.append(C.string_at(data, n))
+        return 0
+
+    def wsink(_user, data, n):
+        warns.append(C.string_at(data, n))
+        return 0
+    cb, wcb = abi.WRITE_FN(sink), abi.WRITE_FN(wsink)
+    job.warn = C.cast(wcb, C.c_void_p)
+    st = abi.JobStats()
+    L.otg_compare_files.argtypes = [C.POINTER(abi.CompareJob), abi.WRITE_FN, C.c_void_p, C.POINTER(abi.JobStats)]
+    rc = L.otg_compare_files(C.byref(job), cb, None, C.byref(st))
+    if rc != 0:
+        raise OtterGpuError("otg_compare_files failed (%d): %s" % (rc, (L.otg_last_error(None) or b"").decode()))
+    return b"".join(chunks), b"".join(warns), {k: getattr(st, k) for k, _ in abi.JobStats._fields_}

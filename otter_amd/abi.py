@@ -170,6 +170,17 @@ class GenotypeJob(C.Structure):
                 ("threads", C.c_int32), ("device", C.c_int32), ("batch_regions", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class CompareJob(C.Structure):
+    """otg_compare_job (include/otter_gpu.h)."""
+    _fields_ = [("truth_bam_path", C.c_char_p), ("query_bam_path", C.c_char_p), ("bed_path", C.c_char_p), ("threads", C.c_int32),
+                ("device", C.c_int32), ("batch_regions", C.c_uint32), ("reserved", C.c_uint32), ("warn", C.c_void_p), ("warn_user", C.c_void_p)]
+
+
+class CompareCounts(C.Structure):
+    """otg_compare_counts (include/otter_gpu.h)."""
+    _fields_ = [(k, C.c_uint64) for k in ("n_compared", "skip_many_truth", "skip_one_truth", "skip_no_truth", "skip_no_query")]
+
+
 class JobStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_regions", "n_regions_ok", "n_regions_skipped", "n_reads", "n_alleles", "input_bytes", "output_bytes")] + \
                [("n_devices", C.c_uint32), ("reserved", C.c_uint32)] + [(k, C.c_double) for k in ("ms_total", "ms_ingest", "ms_hot_path", "ms_emit")]

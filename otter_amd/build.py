@@ -7,7 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libotter_gpu.so")
-SOURCES = ["otg_api.hip", "wfa_edit.hip", "myers_edit.hip", "wfa_affine.hip", "wfa_affine_reg.hip", "wfa_adaptive.hip", "cluster.hip", "poa.hip", "pipeline.hip", "emit.hip", "ingest.hip", "bedfa.hip", "dispatch.hip", "gather.hip"]
+SOURCES = ["otg_api.hip", "wfa_edit.hip", "edit_align.hip", "myers_edit.hip", "wfa_affine.hip", "wfa_affine_reg.hip", "wfa_adaptive.hip", "cluster.hip", "poa.hip", "pipeline.hip", "emit.hip", "compare.hip", "ingest.hip", "bedfa.hip", "dispatch.hip", "gather.hip"]
 # -ffp-contract=off: the reference's clustering decisions are FP64 comparisons made without FMA
 # contraction; fused operations are written explicitly where glibc uses them.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
@@ -31,15 +31,17 @@ def needs_build():
 
 TOOL_SRC = os.path.join(HERE, "..", "tools", "otter_assemble.cpp")
 TOOL = os.path.join(HERE, "..", "tools", "otter_assemble")
+TOOLS = [(TOOL_SRC, TOOL), (os.path.join(HERE, "..", "tools", "otter_compare.cpp"), os.path.join(HERE, "..", "tools", "otter_compare"))]
 
 
 def build_tool(force=False):
-    """the command-line host of the dispatcher (plain C++ over the C-ABI); rebuilt when its source or the library is newer"""
-    if not os.path.exists(TOOL_SRC) or not os.path.exists(LIB):
-        return
-    if not force and os.path.exists(TOOL) and os.path.getmtime(TOOL) > max(os.path.getmtime(TOOL_SRC), os.path.getmtime(LIB), os.path.getmtime(os.path.join(HERE, "..", "include", "otter_gpu.h"))):
-        return
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-o", TOOL, TOOL_SRC, "-L" + HERE, "-lotter_gpu", "-Wl,-rpath," + HERE, "-Wl,-rpath,/opt/rocm/lib"])
+    """the command-line hosts of the dispatcher (plain C++ over the C-ABI); each rebuilt when its source or the library is newer"""
+    for src, exe in TOOLS:
+        if not os.path.exists(src) or not os.path.exists(LIB):
+            continue
+        if not force and os.path.exists(exe) and os.path.getmtime(exe) > max(os.path.getmtime(src), os.path.getmtime(LIB), os.path.getmtime(os.path.join(HERE, "..", "include", "otter_gpu.h"))):
+            continue
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-o", exe, src, "-L" + HERE, "-lotter_gpu", "-Wl,-rpath," + HERE, "-Wl,-rpath,/opt/rocm/lib"])
 
 
 def build(force=False, verbose=False, jobs=4):

@@ -12,6 +12,7 @@
 // Memory is bounded by the batch size, not by the BED file; output order is the BED order whatever the number of devices or batches
 // (the reference's order with -t 1; with -t > 1 the reference prints in completion order).
 #include "otg_common.hpp"
+#include "otg_compare.hpp"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -470,6 +471,151 @@ int otg_assemble_files(const otg_assemble_job* job, otg_write_fn write, void* us
 // ---- `otter genotype` from files to text in one call: genotype() / genotype_process() (src/genotype.cpp:69-192).  Regions in bounded
 // batches: allele ingest (host threads) -> anallele_cluster on the device -> VCF lines (or, without a reference, the two-length table),
 // text in BED order.  The reference's worker loop does the same region by region on a thread pool and prints under a mutex.
+// `otter compare` from files to text — compare() (src/compare.cpp:68-150).  Two batches in flight: while the pairs of one are aligned on the
+// device and emitted, the next one is ingested (both BAMs) on a host thread.
+int otg_compare_files(const otg_compare_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
+{
+  if (!job || !write || !job->truth_bam_path || !job->query_bam_path || !job->bed_path)
+    return otg_fail(nullptr, OTG_ERR_ARG, "otg_compare_files: NULL job, writer, BAM or BED path");
+  const auto t_all = Clock::now();
+  otg_job_stats st{};
+  std::vector<otg_bed> beds; std::vector<char> chr_arena;
+  {
+    uint32_t n = 0, skipped = 0; uint64_t cu = 0;
+    int rc = otg_parse_bed_file(job->bed_path, nullptr, 0, &n, nullptr, 0, &cu, &skipped);
+    if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) return rc;
+    beds.resize((size_t)n + 1); chr_arena.resize((size_t)cu + 16);
+    rc = otg_parse_bed_file(job->bed_path, beds.data(), (uint32_t)beds.size(), &n, chr_arena.data(), chr_arena.size(), &cu, &skipped);
+    if (rc != OTG_OK) return rc;
+    beds.resize(n);
+    st.n_regions = n;
+  }
+  otg_bam* bt = nullptr; otg_bam* bq = nullptr; otg_ctx* ctx = nullptr;
+  int rc = otg_bam_open(job->truth_bam_path, &bt);
+  if (rc != OTG_OK) return rc;
+  rc = otg_bam_open(job->query_bam_path, &bq);
+  if (rc != OTG_OK) { otg_bam_close(bt); return rc; }
+  auto cleanup = [&] { if (ctx) pool_release(job->device, ctx); otg_bam_close(bq); otg_bam_close(bt); };
+  // sample2index (src/compare.cpp:77-88): the first read group of each BAM (SampleIndex::init)
+  std::string s0, s1;
+  for (int side = 0; side < 2; ++side) {
+    otg_bam* b = side ? bq : bt;
+    rc = otg_bam_sample_index(b, nullptr, nullptr, nullptr);
+    if (rc != OTG_OK) { cleanup(); return rc; }
+    (side ? s1 : s0) = otg_bam_sample(b, 0);
+  }
+  if (!(ctx = pool_acquire(job->device))) { cleanup(); return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_compare_files: %s", last_err().c_str()); }
+  const uint32_t per = job->batch_regions ? job->batch_regions : 1024u;
+  const int threads = job->threads > 0 ? job->threads : 1;
+  struct Side {
+    std::vector<uint8_t> arena; std::vector<otg_allele> alleles; std::vector<uint32_t> first;
+    std::vector<int32_t> sp; std::vector<uint32_t> sp_first; std::string warn;
+    uint32_t na = 0, ns = 0; uint64_t used = 0;
+  };
+  struct CmpBatch { Side side[2]; uint32_t f = 0, n = 0; int rc = OTG_OK; double ms = 0; std::string err; };
+  CmpBatch bufs[2];
+  auto ingest_into = [&](CmpBatch& B, uint32_t f) {
+    B.f = f; B.n = std::min<uint32_t>(per, (uint32_t)beds.size() - f);
+    const auto t0 = Clock::now();
+    B.rc = OTG_OK;
+    for (int side = 0; side < 2 && B.rc == OTG_OK; ++side) {
+      Side& S = B.side[side];
+      S.first.assign((size_t)B.n + 1, 0); S.sp_first.assign((size_t)B.n + 1, 0);
+      size_t cap_al = std::max<size_t>(S.alleles.size(), (size_t)B.n * 16 + 64), cap_ar = std::max<size_t>(S.arena.size(), (size_t)B.n * 16 * 1024 + 4096);
+      size_t cap_sp = std::max<size_t>(S.sp.size(), (size_t)B.n * 16 + 64), cap_w = std::max<size_t>(S.warn.size(), (size_t)B.n * 96 + 64);
+      for (int attempt = 0; attempt < 4; ++attempt) {
+        S.alleles.resize(cap_al); S.arena.resize(cap_ar); S.sp.resize(cap_sp); S.warn.resize(cap_w);
+        S.na = 0; S.used = 0; S.ns = 0; uint64_t wl = 0;
+        B.rc = otg_ingest_compare_alleles(side ? bq : bt, s0.c_str(), s1.c_str(), side ? 0 : 1, beds.data() + f, chr_arena.data(), B.n, threads,
+                                          S.arena.data(), S.arena.size(), &S.used, S.alleles.data(), (uint32_t)S.alleles.size(), &S.na, S.first.data(),
+                                          S.sp.data(), (uint32_t)S.sp.size(), &S.ns, S.sp_first.data(), &S.warn[0], S.warn.size(), &wl);
+        if (B.rc != OTG_ERR_CAPACITY) { S.warn.resize(B.rc == OTG_OK ? wl : 0); break; }
+        cap_al = (size_t)S.na + 64; cap_ar = (size_t)S.used + 4096; cap_sp = (size_t)S.ns + 64; cap_w = (size_t)wl + 64;
+      }
+      if (B.rc != OTG_OK) B.err = last_err();
+    }
+    B.ms = ms_since(t0);
+  };
+  std::vector<otg_align_task> tasks; std::vector<uint8_t> seqs; std::vector<uint64_t> pair_first;
+  std::vector<double> pedit, pops; std::vector<int64_t> pair_task;
+  std::vector<int32_t> scores; std::vector<uint32_t> clen;
+  std::string text, wtext;
+  const uint32_t n_beds = (uint32_t)beds.size();
+  auto emit_warn = [&](const std::string& w) { return w.empty() || !job->warn || job->warn(job->warn_user, w.data(), w.size()) == 0; };
+  if (n_beds) ingest_into(bufs[0], 0);
+  for (uint32_t f = 0, idx = 0; f < n_beds; f += per, ++idx) {
+    CmpBatch& B = bufs[idx & 1];
+    if (B.rc != OTG_OK) { rc = B.rc; const std::string e = B.err; cleanup(); return otg_fail(nullptr, rc, "otg_compare_files: %s", e.c_str()); }
+    std::thread next;
+    if (f + per < n_beds) next = std::thread([&, f, idx] { ingest_into(bufs[(idx + 1) & 1], f + per); });
+    struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{next};
+    auto join_next = [&] { if (next.joinable()) next.join(); };
+    const Side& T = B.side[0]; const Side& Q = B.side[1];
+    const uint32_t n = B.n;
+    st.ms_ingest += B.ms; st.n_alleles += T.na + Q.na; st.input_bytes += T.used + Q.used;
+    auto t0 = Clock::now();
+    // the pairs of every compared region (get_distances, src/compare.cpp:52-63): pattern = the longer allele, ties -> the query
+    tasks.clear(); seqs.clear(); pair_first.assign((size_t)n + 1, 0); pair_task.clear();
+    auto add_seq = [&](const uint8_t* p, uint32_t l) { const uint64_t o = seqs.size(); seqs.insert(seqs.end(), p, p + l); return o; };
+    for (uint32_t r = 0; r < n; ++r) {
+      pair_first[r] = pair_task.size();
+      const uint32_t nt = T.first[r + 1] - T.first[r], nq0 = Q.first[r + 1] - Q.first[r];
+      if (!otg_compare_n_pairs(nt, nq0)) continue;
+      const uint32_t nq = nq0 == 1 ? 2 : nq0;
+      for (uint32_t i = 0; i < nt; ++i) {
+        const otg_allele& ta = T.alleles[T.first[r] + i];
+        for (uint32_t j = 0; j < nq; ++j) {
+          const otg_allele& qa = Q.alleles[Q.first[r] + (nq0 == 1 ? 0 : j)];
+          double e, o;
+          if (otg_compare_special(T.arena.data() + ta.seq_off, ta.seq_len, Q.arena.data() + qa.seq_off, qa.seq_len, &e, &o)) { pair_task.push_back(-1); continue; }
+          otg_align_task t; memset(&t, 0, sizeof(t));
+          const bool tp = ta.seq_len > qa.seq_len;
+          const otg_allele& pa = tp ? ta : qa; const otg_allele& xa = tp ? qa : ta;
+          t.pattern_off = add_seq((tp ? T : Q).arena.data() + pa.seq_off, pa.seq_len); t.pattern_len = pa.seq_len;
+          t.text_off = add_seq((tp ? Q : T).arena.data() + xa.seq_off, xa.seq_len); t.text_len = xa.seq_len;
+          pair_task.push_back((int64_t)tasks.size());
+          tasks.push_back(t);
+        }
+      }
+    }
+    pair_first[n] = pair_task.size();
+    seqs.resize(seqs.size() + 64, 0);
+    scores.assign(tasks.size(), 0); clen.assign(tasks.size(), 0);
+    if (!tasks.empty()) {
+      uint64_t used = 0;
+      rc = otg_edit_align_batch(ctx, seqs.data(), seqs.size(), tasks.data(), (uint32_t)tasks.size(), scores.data(), nullptr, clen.data(), nullptr, 0, &used);
+      if (rc != OTG_OK) { const std::string e = otg_last_error(ctx) ? otg_last_error(ctx) : ""; join_next(); cleanup(); return otg_fail(nullptr, rc, "otg_compare_files: %s", e.c_str()); }
+    }
+    pedit.assign(pair_task.size(), 0.0); pops.assign(pair_task.size(), 0.0);
+    for (size_t p = 0; p < pair_task.size(); ++p)
+      if (pair_task[p] >= 0) { pedit[p] = (double)scores[(size_t)pair_task[p]]; pops[p] = (double)clen[(size_t)pair_task[p]]; }
+    st.n_reads += tasks.size();
+    st.ms_hot_path += ms_since(t0);
+    t0 = Clock::now();
+    uint64_t need = 0, wneed = 0;
+    otg_compare_counts cc{};
+    rc = otg_compare_emit(beds.data() + f, chr_arena.data(), n, T.first.data(), T.alleles.data(), T.arena.data(), T.sp_first.data(), T.sp.data(),
+                          Q.first.data(), Q.alleles.data(), Q.arena.data(), pair_first.data(), pedit.data(), pops.data(), nullptr, 0, &need, nullptr, 0, &wneed, &cc);
+    if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) { join_next(); cleanup(); return rc; }
+    text.resize(need); wtext.resize(wneed);
+    rc = otg_compare_emit(beds.data() + f, chr_arena.data(), n, T.first.data(), T.alleles.data(), T.arena.data(), T.sp_first.data(), T.sp.data(),
+                          Q.first.data(), Q.alleles.data(), Q.arena.data(), pair_first.data(), pedit.data(), pops.data(), need ? &text[0] : nullptr, need, &need,
+                          wneed ? &wtext[0] : nullptr, wneed, &wneed, &cc);
+    if (rc != OTG_OK) { join_next(); cleanup(); return rc; }
+    st.ms_emit += ms_since(t0);
+    st.n_regions_ok += cc.n_compared;
+    st.n_regions_skipped += cc.skip_many_truth + cc.skip_one_truth + cc.skip_no_truth + cc.skip_no_query;
+    if (!emit_warn(T.warn) || !emit_warn(Q.warn) || !emit_warn(wtext)) { join_next(); cleanup(); return otg_fail(nullptr, OTG_ERR_ARG, "otg_compare_files: the warning writer failed"); }
+    if (!text.empty() && write(user, text.data(), text.size()) != 0) { join_next(); cleanup(); return otg_fail(nullptr, OTG_ERR_ARG, "otg_compare_files: the writer failed"); }
+    st.output_bytes += text.size();
+    join_next();
+  }
+  cleanup();
+  st.ms_total = ms_since(t_all); st.n_devices = 1;
+  if (stats) *stats = st;
+  return OTG_OK;
+}
+
 int otg_genotype_files(const otg_genotype_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
 {
   if (!job || !write || !job->bam_path || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "otg_genotype_files: NULL job, writer, BAM or BED path");

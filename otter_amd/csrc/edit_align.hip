@@ -1,0 +1,296 @@
+// edit_align.hip — batched unit-cost wavefront aligner WITH op strings (gfx950).
+//
+// Replaces wfa::WFAlignerEdit(Alignment, MemoryMed)::alignEnd2End + getAlignmentScore() + getAlignmentCigar()
+// (reference: src/compare.cpp:59-61,95).  End-to-end only.
+//
+// Three steps per batch:
+//   1. the exact score s of every pair from the existing score chain (otg_launch_edit: wavefront + bit-parallel tiers);
+//   2. a provenance pass restricted to the diamond |k - kend| <= s - t of score t: ONE wave64 per alignment, lanes =
+//      diagonals, the wavefront of furthest-reaching offsets updated in place (LDS tier, or a global-row tier for wide
+//      ones), 2 bits of provenance per (score, diagonal) cell written to an HBM arena sized exactly from the known scores
+//      (two 64-bit ballots per 64-diagonal chunk);
+//   3. lane 0 of the same wave walks the provenance back from (s, kend), storing the s edit operations in forward order;
+//      the whole wave then unpacks them the way WFA2-lib's pcigar_unpack_linear does: a maximal match run, then per
+//      operation the operation and a maximal match run (wavefront_pcigar.c:151).
+// Provenance rule = wavefront_compute_edit_idm_piggyback (wavefront_compute_edit.c:143-190): candidates ins (k-1, +1),
+// del (k+1), misms (k, +1); max; three sequential tests ins, del, misms, the last equal one wins; then the cell is nulled
+// when h > tlen or v > plen.
+#include "otg_common.hpp"
+#include <algorithm>
+#include <cstdlib>
+
+namespace {
+
+using lds_i32 = __attribute__((address_space(3))) int32_t;
+
+constexpr uint8_t OP_INS = 1, OP_DEL = 2, OP_MISMS = 3;
+
+// diagonal range of score t inside the diamond (end-to-end: the score-t wavefront spans [-t, t] clamped to the matrix)
+__host__ __device__ __forceinline__ void diamond_range(int t, int s, int kend, int pl, int tl, int* lo, int* hi)
+{
+  int a = -t, b = t;
+  if (a < kend - (s - t)) a = kend - (s - t);
+  if (b > kend + (s - t)) b = kend + (s - t);
+  if (a < -pl) a = -pl;
+  if (b > tl) b = tl;
+  *lo = a; *hi = b;
+}
+
+__host__ __device__ __forceinline__ uint64_t prov_row_bytes(int lo, int hi)
+{
+  return hi >= lo ? (uint64_t)((hi - lo + 64) / 64) * 16u : 0u;
+}
+
+struct AlignJob {
+  uint64_t prov_off;      // into the provenance arena (bytes, 16-aligned)
+  uint64_t ops_off;       // into the op buffer (s bytes)
+  uint64_t cig_off;       // into the device cigar arena (ignored when no cigar is produced)
+};
+
+// stat[ti] = s on success; -2: the end cell was not reached or the backtrace left the diamond; -3: the unpacked string does not end at (plen, tlen)
+template <int CAP, int WPB, bool GLOBAL_WF>
+__global__ __launch_bounds__(WPB * 64) void edit_align_kernel(
+    const uint8_t* __restrict__ arena, const otg_align_task* __restrict__ tasks, const int32_t* __restrict__ scores,
+    const uint32_t* __restrict__ todo, uint32_t n_todo, const AlignJob* __restrict__ jobs,
+    uint8_t* __restrict__ prov, uint8_t* __restrict__ ops, uint8_t* __restrict__ cig, uint32_t* __restrict__ cig_len,
+    int32_t* __restrict__ stat, uint32_t* __restrict__ ticket, int32_t* gws, int gcap)
+{
+  extern __shared__ __attribute__((aligned(16))) int32_t smem[];
+  const int lane = threadIdx.x & 63;
+  const int wib = threadIdx.x >> 6;
+  volatile int32_t* gwf = GLOBAL_WF ? (volatile int32_t*)(gws + (size_t)(blockIdx.x * WPB + wib) * (size_t)gcap) : nullptr;
+  volatile lds_i32* lwf = (volatile lds_i32*)smem + wib * CAP;
+  auto wf_rd = [&](int j) -> int { if constexpr (GLOBAL_WF) return gwf[j]; else return lwf[j]; };
+  auto wf_wr = [&](int j, int v) { if constexpr (GLOBAL_WF) gwf[j] = v; else lwf[j] = v; };
+
+  for (;;) {
+    const uint32_t tk = otg_wave_atomic_add(ticket, 1u);
+    if (tk >= n_todo) break;
+    const uint32_t ti = todo[tk];
+    const otg_align_task t = tasks[ti];
+    const AlignJob jb = jobs[ti];
+    const uint8_t* P = arena + t.pattern_off;
+    const uint8_t* T = arena + t.text_off;
+    const int pl = (int)t.pattern_len, tl = (int)t.text_len;
+    const int kend = tl - pl;
+    const int s = scores[ti];
+    // the union of the diamond ranges is [ceil((kend - s) / 2), floor((kend + s) / 2)] clamped: the host sized CAP / gcap from it
+    int kmin = kend - s; kmin = kmin >= 0 ? kmin / 2 : -((-kmin) / 2);
+    if (kmin < -pl) kmin = -pl;
+    const int kbase = kmin - 1;                   // one spare slot below, one above: reads of k +- 1 stay inside
+    uint8_t* const prow0 = prov + jb.prov_off;
+    uint64_t row = 0;
+    int lo_prev = 0, hi_prev = 0;
+    bool ok = true;
+    for (int sc = 0; sc <= s; ++sc) {
+      int lo, hi;
+      diamond_range(sc, s, kend, pl, tl, &lo, &hi);
+      // left neighbour of the first chunk: the diamond of score sc - 1 is wider, so (sc - 1, lo - 1) can be a live cell
+      int carry = (sc > 0 && lo - 1 >= lo_prev && lo - 1 <= hi_prev) ? wf_rd(lo - 1 - kbase) : OTG_NULL_OFF;
+      for (int c = lo; c <= hi; c += 64) {
+        const int k = c + lane;
+        const int j = k - kbase;
+        const bool in = k <= hi;
+        int mx;
+        uint32_t op = 0;
+        if (sc == 0) {
+          mx = 0;
+        } else {
+          const int o = (in && k >= lo_prev && k <= hi_prev) ? wf_rd(j) : OTG_NULL_OFF;
+          const int r = (in && k + 1 >= lo_prev && k + 1 <= hi_prev) ? wf_rd(j + 1) : OTG_NULL_OFF;
+          int l = __shfl_up(o, 1);
+          if (lane == 0) l = carry;
+          carry = __shfl(o, 63);
+          const int ins = l + 1, del = r, misms = o + 1;
+          mx = ins > del ? ins : del;
+          mx = misms > mx ? misms : mx;
+          if (mx == ins) op = OP_INS;
+          if (mx == del) op = OP_DEL;
+          if (mx == misms) op = OP_MISMS;
+        }
+        int h = mx, v = mx - k;
+        const bool valid = in && mx >= 0 && v >= 0 && h <= tl && v <= pl;
+        if (valid && v < pl && h < tl) {
+          const int rem = pl - v < tl - h ? pl - v : tl - h;
+          int m = otg_match64(P, T, v, h, rem);
+          v += m; h += m;
+          while (m == 64 && v < pl && h < tl) {
+            const int rem2 = pl - v < tl - h ? pl - v : tl - h;
+            m = otg_match64(P, T, v, h, rem2);
+            v += m; h += m;
+          }
+        }
+        if (in) wf_wr(j, valid ? h : OTG_NULL_OFF);
+        if (sc > 0) {
+          const unsigned long long b0 = __ballot(in && (op & 1u));
+          const unsigned long long b1 = __ballot(in && (op & 2u));
+          uint64_t* dst = (uint64_t*)(prow0 + row + (uint64_t)((c - lo) >> 6) * 16u);
+          if (lane == 0) dst[0] = b0;
+          if (lane == 1) dst[1] = b1;
+        }
+      }
+      if (sc > 0) row += prov_row_bytes(lo, hi);
+      lo_prev = lo; hi_prev = hi;
+    }
+    // the end cell must have been reached at score s (else the score chain and this pass disagree)
+    if (kend < lo_prev || kend > hi_prev || wf_rd(kend - kbase) < tl) ok = false;
+    // ---- backtrace (lane 0): ops in forward order
+    uint8_t* const opv = ops + jb.ops_off;
+    uint32_t n_ins = 0;
+    if (ok && lane == 0) {
+      int k = kend;
+      uint64_t r_end = row;
+      for (int sc = s; sc >= 1; --sc) {
+        int lo, hi;
+        diamond_range(sc, s, kend, pl, tl, &lo, &hi);
+        const uint64_t rb = prov_row_bytes(lo, hi);
+        r_end -= rb;
+        if (k < lo || k > hi) { n_ins = 0xFFFFFFFFu; break; }
+        const int idx = k - lo;
+        const uint64_t* src = (const uint64_t*)(prow0 + r_end + (uint64_t)(idx >> 6) * 16u);
+        const uint32_t bit = (uint32_t)(idx & 63);
+        const uint32_t op = (uint32_t)((src[0] >> bit) & 1u) | ((uint32_t)((src[1] >> bit) & 1u) << 1);
+        opv[sc - 1] = (uint8_t)op;
+        if (op == OP_INS) { ++n_ins; k -= 1; }
+        else if (op == OP_DEL) k += 1;
+        else if (op != OP_MISMS) { n_ins = 0xFFFFFFFFu; break; }
+      }
+      if (k != 0 && n_ins != 0xFFFFFFFFu) n_ins = 0xFFFFFFFFu;
+    }
+    __threadfence_block();                        // lane 0's op stores before the whole wave reads them back
+    n_ins = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_ins);
+    if (n_ins == 0xFFFFFFFFu) ok = false;
+    if (!ok) {
+      if (lane == 0) stat[ti] = -2;
+      continue;
+    }
+    // ---- unpack (whole wave): maximal match run, then per op the op and a maximal match run
+    if (cig) {
+      uint8_t* out = cig + jb.cig_off;
+      int v = 0, h = 0;
+      uint32_t pos = 0;
+      for (int q = 0; q <= s; ++q) {
+        if (q > 0) {
+          const uint32_t op = opv[q - 1];
+          const uint8_t ch = op == OP_INS ? 'I' : op == OP_DEL ? 'D' : 'X';
+          if (lane == 0) out[pos] = ch;
+          ++pos;
+          if (op == OP_INS) ++h; else if (op == OP_DEL) ++v; else { ++v; ++h; }
+        }
+        const int rem = pl - v < tl - h ? pl - v : tl - h;
+        const int m = rem > 0 ? otg_wave_match(P, T, v, h, rem, lane) : 0;
+        for (int i = lane; i < m; i += 64) out[pos + (uint32_t)i] = 'M';
+        pos += (uint32_t)m; v += m; h += m;
+      }
+      if (v != pl || h != tl) { if (lane == 0) stat[ti] = -3; continue; }
+    }
+    if (lane == 0) { cig_len[ti] = (uint32_t)pl + n_ins; stat[ti] = s; }
+  }
+}
+
+} // namespace
+
+// Host side of otg_edit_align_batch: scores first (the existing chain), then the provenance pass in chunks bounded by a memory budget.
+// d_arena / d_tasks resident (arena padded by >= 64 readable bytes); h_tasks the same tasks on the host.  Fills scores_out, len_out and,
+// when d_cig_base is non-null, the op strings at d_cig_base + cig_slot[i] (cig_slot: n_tasks entries, host).
+int otg_launch_edit_align(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* d_tasks, const otg_align_task* h_tasks, uint32_t n_tasks,
+                          int32_t* scores_out, uint32_t* len_out, uint8_t* d_cig_base, const uint64_t* cig_slot, double* score_ms, double* prov_ms)
+{
+  if (n_tasks == 0) return OTG_OK;
+  int32_t* d_scores = (int32_t*)otg_slot(ctx, SLOT_SCORES, (size_t)n_tasks * sizeof(int32_t));
+  uint64_t* d_cells = (uint64_t*)otg_slot(ctx, SLOT_CELLS, (size_t)n_tasks * sizeof(uint64_t));
+  if (!d_scores || !d_cells) return OTG_ERR_HIP;
+  HIP_TRY(ctx, hipMemsetAsync(d_scores, 0xff, (size_t)n_tasks * sizeof(int32_t), ctx->stream));
+  float sms = 0;
+  int rc = otg_launch_edit(ctx, d_arena, d_tasks, n_tasks, d_scores, d_cells, score_ms ? &sms : nullptr, nullptr);
+  if (rc) return rc;
+  if (score_ms) *score_ms = sms;
+  HIP_TRY(ctx, hipMemcpyAsync(scores_out, d_scores, (size_t)n_tasks * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  for (uint32_t i = 0; i < n_tasks; ++i)
+    if (scores_out[i] < 0) return otg_fail(ctx, OTG_ERR_FATAL, "edit task %u did not terminate", i);
+
+  // per task: provenance bytes (exact, the same row sizes the kernel walks), op bytes, wavefront width
+  std::vector<AlignJob> jobs(n_tasks);
+  std::vector<uint64_t> pbytes(n_tasks);
+  std::vector<int> width(n_tasks);
+  for (uint32_t i = 0; i < n_tasks; ++i) {
+    const int pl = (int)h_tasks[i].pattern_len, tl = (int)h_tasks[i].text_len, s = scores_out[i], kend = tl - pl;
+    uint64_t b = 0;
+    for (int sc = 1; sc <= s; ++sc) { int lo, hi; diamond_range(sc, s, kend, pl, tl, &lo, &hi); b += prov_row_bytes(lo, hi); }
+    pbytes[i] = b;
+    int kmin = kend - s; kmin = kmin >= 0 ? kmin / 2 : -((-kmin) / 2); if (kmin < -pl) kmin = -pl;
+    int kmax = kend + s; kmax = kmax >= 0 ? kmax / 2 : -((-kmax + 1) / 2); if (kmax > tl) kmax = tl;
+    width[i] = kmax - kmin + 3;
+    jobs[i].cig_off = cig_slot ? cig_slot[i] : 0;
+  }
+  // chunks: consecutive tasks while the provenance + op bytes stay within the budget (a single larger task gets a chunk of its own)
+  static const uint64_t budget = getenv("OTG_EDIT_ALIGN_BUDGET_MB") ? (uint64_t)atoll(getenv("OTG_EDIT_ALIGN_BUDGET_MB")) << 20 : (uint64_t)2 << 30;
+  constexpr int CAP = 2048, WPB = 4;
+  float ms_total = 0;
+  uint32_t c0 = 0;
+  while (c0 < n_tasks) {
+    uint32_t c1 = c0;
+    uint64_t pb = 0, ob = 0;
+    int gmax = 0;
+    while (c1 < n_tasks) {
+      const uint64_t add_p = pbytes[c1], add_o = ((uint64_t)scores_out[c1] + 15) & ~15ull;
+      if (c1 > c0 && pb + ob + add_p + add_o > budget) break;
+      jobs[c1].prov_off = pb; jobs[c1].ops_off = ob;
+      pb += add_p; ob += add_o;
+      if (width[c1] > CAP) gmax = std::max(gmax, width[c1]);
+      ++c1;
+    }
+    const uint32_t n = c1 - c0;
+    std::vector<uint32_t> lds_list, glb_list;
+    for (uint32_t i = c0; i < c1; ++i) (width[i] <= CAP ? lds_list : glb_list).push_back(i);
+    uint8_t* d_prov = (uint8_t*)otg_slot(ctx, SLOT_BT_POOL, pb + 64);
+    uint8_t* d_ops = (uint8_t*)otg_slot(ctx, SLOT_REVOPS, ob + 64);
+    AlignJob* d_jobs = (AlignJob*)otg_slot(ctx, SLOT_AUX1, (size_t)n_tasks * sizeof(AlignJob));
+    uint32_t* d_todo = (uint32_t*)otg_slot(ctx, SLOT_AUX2, ((size_t)n + 16) * sizeof(uint32_t));
+    uint32_t* d_len = (uint32_t*)otg_slot(ctx, SLOT_CIG_LEN, (size_t)n_tasks * sizeof(uint32_t));
+    int32_t* d_stat = (int32_t*)otg_slot(ctx, SLOT_AUX3, (size_t)n_tasks * sizeof(int32_t));
+    if (!d_prov || !d_ops || !d_jobs || !d_todo || !d_len || !d_stat) return OTG_ERR_HIP;
+    uint32_t* d_tick = d_todo + n;            // two ticket counters after the todo list
+    std::vector<uint32_t> todo(lds_list);
+    todo.insert(todo.end(), glb_list.begin(), glb_list.end());
+    HIP_TRY(ctx, hipMemcpyAsync(d_jobs + c0, jobs.data() + c0, (size_t)n * sizeof(AlignJob), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_todo, todo.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(d_tick, 0, 16 * sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(d_stat + c0, 0xff, (size_t)n * sizeof(int32_t), ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    if (!lds_list.empty()) {
+      const uint32_t want = ((uint32_t)lds_list.size() + WPB - 1) / WPB;
+      const uint32_t grid = std::min<uint32_t>((uint32_t)ctx->n_cu * 4, want);
+      hipLaunchKernelGGL((edit_align_kernel<CAP, WPB, false>), dim3(grid), dim3(WPB * 64), (size_t)CAP * WPB * sizeof(int32_t), ctx->stream,
+                         d_arena, d_tasks, d_scores, d_todo, (uint32_t)lds_list.size(), d_jobs, d_prov, d_ops, d_cig_base, d_len, d_stat, d_tick,
+                         (int32_t*)nullptr, 0);
+    }
+    if (!glb_list.empty()) {
+      constexpr int GW = 4;
+      const uint32_t want = ((uint32_t)glb_list.size() + GW - 1) / GW;
+      const uint32_t grid = std::min<uint32_t>((uint32_t)ctx->n_cu, want);
+      const int gcap = gmax + 64;
+      int32_t* ws = (int32_t*)otg_slot(ctx, SLOT_WF_WS, (size_t)grid * GW * (size_t)gcap * sizeof(int32_t));
+      if (!ws) return OTG_ERR_HIP;
+      hipLaunchKernelGGL((edit_align_kernel<0, GW, true>), dim3(grid), dim3(GW * 64), 0, ctx->stream,
+                         d_arena, d_tasks, d_scores, d_todo + lds_list.size(), (uint32_t)glb_list.size(), d_jobs, d_prov, d_ops, d_cig_base, d_len,
+                         d_stat, d_tick + 1, ws, gcap);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    std::vector<int32_t> stat(n);
+    HIP_TRY(ctx, hipMemcpyAsync(len_out + c0, d_len + c0, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(stat.data(), d_stat + c0, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    ms_total += ms;
+    for (uint32_t i = 0; i < n; ++i)
+      if (stat[i] != scores_out[c0 + i])
+        return otg_fail(ctx, OTG_ERR_FATAL, "edit alignment task %u: provenance pass failed (code %d, score %d)", c0 + i, stat[i], scores_out[c0 + i]);
+    c0 = c1;
+  }
+  if (prov_ms) *prov_ms = ms_total;
+  return OTG_OK;
+}

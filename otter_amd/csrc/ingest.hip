@@ -576,9 +576,21 @@ static int parse_sample_index(otg_bam* b, std::string& err)
 
 // parse_analleles / parse_anallele (src/anseqs.cpp:462-524) for a slice of regions, plus the reference allele genotype_process appends
 // (src/genotype.cpp:92-101).  alleles[].region = region index, alleles[].label = sample index.
+// `otter compare` (src/compare.cpp:26-48,104-105): its own two-sample map instead of the BAM's, and on the truth side only records whose
+// name starts with the chromosome, each of which pushes its `sp:A` value (before the `ta` test of parse_anallele rejects it or not).
+struct CompareSide {
+  const std::unordered_map<std::string, int>* sample2index;
+  bool truth;
+  std::vector<int32_t>* spannings;
+  uint32_t* sp_per_region;
+  std::vector<std::string>* warnings;
+};
+
 static int alleles_slice(const otg_bam* b, const char* path, const otg_bed* beds, const char* chr_arena, uint32_t g0, uint32_t g1,
-                         const otg_fasta* fa, std::vector<otg_allele>& alleles, std::vector<uint8_t>& arena, uint32_t* n_per_region, std::string& err)
+                         const otg_fasta* fa, std::vector<otg_allele>& alleles, std::vector<uint8_t>& arena, uint32_t* n_per_region, std::string& err,
+                         const CompareSide* cmp = nullptr)
 {
+  const std::unordered_map<std::string, int>& s2i = cmp ? *cmp->sample2index : b->sample2index;
   static const char nt16[] = "=ACMGRSVTWYHKDBN";
   otg_bam local;
   if (!local.fp.open(path)) { err = "cannot reopen BAM"; return OTG_ERR_ARG; }
@@ -588,7 +600,9 @@ static int alleles_slice(const otg_bam* b, const char* path, const otg_bed* beds
   const int refindex = (int)b->index2sample.size();
   for (uint32_t g = g0; g < g1 && rc_out == OTG_OK; ++g) {
     const size_t first = alleles.size();
+    const size_t sp_first = cmp && cmp->truth ? cmp->spannings->size() : 0;
     n_per_region[g] = 0;
+    if (cmp && cmp->truth) cmp->sp_per_region[g] = 0;
     const std::string chr(chr_arena + beds[g].chr_off, beds[g].chr_len);
     const std::string target = chr + ":" + std::to_string((uint32_t)beds[g].start) + "-" + std::to_string((uint32_t)beds[g].end);   // toScString
     auto it = b->name2id.find(chr);
@@ -597,17 +611,29 @@ static int alleles_slice(const otg_bam* b, const char* path, const otg_bed* beds
     const long long s0 = (long long)(uint32_t)beds[g].start, e0 = (long long)(uint32_t)beds[g].end;
     long long qbeg = s0 - 1; if (qbeg < 0) qbeg = 0;
     const long long qend = e0;
-    if (it == b->name2id.end() || s0 > 2147483647LL || e0 > 2147483647LL || qbeg > qend) continue;
+    if (it == b->name2id.end() || s0 > 2147483647LL || e0 > 2147483647LL || qbeg > qend) {
+      if (cmp && cmp->warnings) cmp->warnings->push_back("WARNING: query failed at region " + target);     // bam_itr_querys returned NULL
+      continue;
+    }
     int cb_rc = OTG_OK;
     const int sc_rc = scan_region(b, local, it->second, qbeg, qend, bins, chunks, err, [&](const Rec& r) {
       if (cb_rc != OTG_OK) return;
+      int32_t sp_push = INT32_MIN;
+      if (cmp && cmp->truth) {
+        // local_parse_analleles (src/compare.cpp:32-43): name prefix test, then the spanning value pushed whatever parse_anallele does
+        if (!(r.l_name >= chr.size() && memcmp(r.name, chr.data(), chr.size()) == 0)) return;
+        char sp = 'u';
+        if (const uint8_t* spa = aux_get(r, 's', 'p')) sp = spa[0] == 'A' ? (char)spa[1] : (char)0;     // bam_aux2A of another type is 0
+        if (sp == 'u') sp_push = -1; else if (sp == 'b') sp_push = 0; else if (sp == 'l') sp_push = 1; else if (sp == 'r') sp_push = 2; else if (sp == 'n') sp_push = 3;
+      }
+      struct SpPush { int32_t v; const CompareSide* c; ~SpPush() { if (v != INT32_MIN) c->spannings->push_back(v); } } sp_guard{sp_push, cmp};
       const uint8_t* a = aux_get(r, 't', 'a');
       std::string parsed = aux2str(a);
       if (parsed != target) return;
       a = aux_get(r, 'R', 'G');
       const std::string sample = aux2str(a);
-      auto si = b->sample2index.find(sample);
-      if (si == b->sample2index.end()) { err = "unrecognized sample name (read group): " + sample; cb_rc = OTG_ERR_ARG; return; }
+      auto si = s2i.find(sample);
+      if (si == s2i.end()) { err = "unrecognized sample name (read group): " + sample; cb_rc = OTG_ERR_ARG; return; }
       otg_allele o;
       memset(&o, 0, sizeof(o));
       o.tcov = 1; o.acov = 1; o.scov = 1; o.ps = -1; o.hp = -1; o.se = 0.0f; o.ic = 1;
@@ -647,6 +673,7 @@ static int alleles_slice(const otg_bam* b, const char* path, const otg_bed* beds
       alleles.push_back(o);
     }
     n_per_region[g] = (uint32_t)(alleles.size() - first);
+    if (cmp && cmp->truth) cmp->sp_per_region[g] = (uint32_t)(cmp->spannings->size() - sp_first);
   }
   local.fp.close();
   return rc_out;
@@ -779,6 +806,68 @@ int otg_ingest_alleles(otg_bam* b, const otg_bed* beds, const char* chr_arena, u
   for (uint32_t g = 0; g < n_regions; ++g) { first_allele[g] = acc; acc += per[g]; }
   first_allele[n_regions] = acc;
   *arena_used = used; *n_alleles = na;
+  return overflow ? OTG_ERR_CAPACITY : OTG_OK;
+}
+
+int otg_ingest_compare_alleles(otg_bam* b, const char* sample0, const char* sample1, int32_t truth, const otg_bed* beds, const char* chr_arena,
+                               uint32_t n_regions, int32_t threads, uint8_t* arena, uint64_t arena_capacity, uint64_t* arena_used,
+                               otg_allele* alleles, uint32_t alleles_capacity, uint32_t* n_alleles, uint32_t* first_allele,
+                               int32_t* spannings, uint32_t spannings_capacity, uint32_t* n_spannings, uint32_t* first_spanning,
+                               char* warn, uint64_t warn_capacity, uint64_t* warn_len)
+{
+  if (!b || !sample0 || !sample1 || (n_regions && (!beds || !first_allele)) || !arena_used || !n_alleles || (truth && (!n_spannings || (n_regions && !first_spanning))))
+    return otg_fail(nullptr, OTG_ERR_ARG, "otg_ingest_compare_alleles: null argument");
+  // sample2index of compare() (src/compare.cpp:77-88): truth's first read group -> 0, then query's -> 1 (one key when they are equal)
+  std::unordered_map<std::string, int> s2i;
+  s2i[sample0] = 0;
+  s2i[sample1] = 1;
+  uint32_t T = threads > 1 ? (uint32_t)threads : 1u;
+  if (T > n_regions) T = n_regions ? n_regions : 1;
+  std::vector<std::vector<otg_allele>> R(T);
+  std::vector<std::vector<uint8_t>> A(T);
+  std::vector<std::vector<int32_t>> S(T);
+  std::vector<std::vector<std::string>> W(T);
+  std::vector<uint32_t> per(n_regions, 0u), sp_per(n_regions, 0u);
+  std::vector<int> rcs(T, OTG_OK);
+  std::vector<std::string> errs(T);
+  auto work = [&](uint32_t t) {
+    const uint32_t g0 = (uint32_t)((uint64_t)n_regions * t / T), g1 = (uint32_t)((uint64_t)n_regions * (t + 1) / T);
+    const CompareSide cs{&s2i, truth != 0, &S[t], sp_per.data(), &W[t]};
+    try { rcs[t] = alleles_slice(b, b->path.c_str(), beds, chr_arena, g0, g1, nullptr, R[t], A[t], per.data(), errs[t], &cs); }
+    catch (const std::exception& e) { rcs[t] = OTG_ERR_ARG; errs[t] = std::string("exception while reading the BAM: ") + e.what(); }
+  };
+  if (T == 1) work(0);
+  else {
+    std::vector<std::thread> th;
+    for (uint32_t t = 0; t < T; ++t) th.emplace_back(work, t);
+    for (auto& x : th) x.join();
+  }
+  for (uint32_t t = 0; t < T; ++t) if (rcs[t] != OTG_OK) return otg_fail(nullptr, rcs[t], "otg_ingest_compare_alleles: %s", errs[t].c_str());
+  uint64_t used = *arena_used; uint32_t na = *n_alleles; uint32_t ns = truth ? *n_spannings : 0; uint64_t wl = warn_len ? *warn_len : 0;
+  bool overflow = false;
+  for (uint32_t t = 0; t < T; ++t) {
+    uint64_t wbytes = 0;
+    for (auto& w : W[t]) wbytes += w.size() + 1;
+    const bool fits = (uint64_t)na + R[t].size() <= alleles_capacity && used + A[t].size() + 64 <= arena_capacity && alleles && arena &&
+                      (!truth || ((uint64_t)ns + S[t].size() <= spannings_capacity && (spannings || S[t].empty()))) &&
+                      (!warn_len || wbytes == 0 || (warn && wl + wbytes <= warn_capacity));
+    if (fits && !overflow) {
+      for (size_t i = 0; i < R[t].size(); ++i) { alleles[na + i] = R[t][i]; alleles[na + i].seq_off += used; }
+      if (!A[t].empty()) memcpy(arena + used, A[t].data(), A[t].size());
+      if (truth && !S[t].empty()) memcpy(spannings + ns, S[t].data(), S[t].size() * sizeof(int32_t));
+      if (warn_len) { uint64_t p = wl; for (auto& w : W[t]) { memcpy(warn + p, w.data(), w.size()); warn[p + w.size()] = '\n'; p += w.size() + 1; } }
+    } else overflow = true;
+    na += (uint32_t)R[t].size(); used += A[t].size(); ns += (uint32_t)S[t].size(); wl += wbytes;
+  }
+  uint32_t acc = *n_alleles, sacc = truth ? *n_spannings : 0;
+  for (uint32_t g = 0; g < n_regions; ++g) {
+    first_allele[g] = acc; acc += per[g];
+    if (truth) { first_spanning[g] = sacc; sacc += sp_per[g]; }
+  }
+  first_allele[n_regions] = acc;
+  if (truth) { first_spanning[n_regions] = sacc; *n_spannings = ns; }
+  *arena_used = used; *n_alleles = na;
+  if (warn_len) *warn_len = wl;
   return overflow ? OTG_ERR_CAPACITY : OTG_OK;
 }
 

@@ -205,6 +205,63 @@ int otg_edit_distance_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t are
   return OTG_OK;
 }
 
+int otg_edit_align_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_bytes, const otg_align_task* tasks, uint32_t n_tasks,
+                         int32_t* scores_out, uint64_t* cigar_off_out, uint32_t* cigar_len_out,
+                         uint8_t* cigar_arena, uint64_t cigar_capacity, uint64_t* cigar_bytes_used)
+{
+  if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_edit_align_batch: no context (no HIP device?)");
+  if (cigar_bytes_used) *cigar_bytes_used = 0;
+  if (n_tasks == 0) return OTG_OK;
+  if (!seq_arena || !tasks || !scores_out || !cigar_len_out || (cigar_arena && !cigar_off_out))
+    return otg_fail(ctx, OTG_ERR_ARG, "otg_edit_align_batch: NULL argument");
+  if (ctx->heur_strategy != OTG_HEURISTIC_NONE)
+    return otg_fail(ctx, OTG_ERR_ARG, "otg_edit_align_batch: exact alignment only; the context's heuristic is WFadaptive (its traceback is not implemented)");
+  for (uint32_t i = 0; i < n_tasks; ++i)
+    if (tasks[i].endsfree) return otg_fail(ctx, OTG_ERR_ARG, "otg_edit_align_batch: task %u is ends-free; only end-to-end alignment is supported", i);
+  int rc = check_tasks(ctx, tasks, n_tasks, arena_bytes);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // device op-string slots: task i has at most pattern_len + text_len columns
+  std::vector<uint64_t> slot(n_tasks + 1);
+  slot[0] = 0;
+  for (uint32_t i = 0; i < n_tasks; ++i) slot[i + 1] = slot[i] + (cigar_arena ? (((uint64_t)tasks[i].pattern_len + tasks[i].text_len + 15) & ~15ull) : 0);
+  uint8_t* d_arena = (uint8_t*)otg_slot(ctx, SLOT_ARENA, arena_bytes + 64);
+  otg_align_task* d_tasks = (otg_align_task*)otg_slot(ctx, SLOT_TASKS, (size_t)n_tasks * sizeof(otg_align_task));
+  uint8_t* d_cig = cigar_arena ? (uint8_t*)otg_slot(ctx, SLOT_CIG_ARENA, slot[n_tasks] + 64) : nullptr;
+  if (!d_arena || !d_tasks || (cigar_arena && !d_cig)) return OTG_ERR_HIP;
+  HIP_TRY(ctx, hipMemsetAsync(d_arena + arena_bytes, 0, 64, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_arena, seq_arena, arena_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_tasks, tasks, (size_t)n_tasks * sizeof(otg_align_task), hipMemcpyHostToDevice, ctx->stream));
+  ctx->max_seq_len = max_len_of(tasks, n_tasks);
+  double sms = 0, pms = 0;
+  rc = otg_launch_edit_align(ctx, d_arena, d_tasks, tasks, n_tasks, scores_out, cigar_len_out, d_cig, slot.data(), &sms, &pms);
+  if (rc) return rc;
+  ctx->last_score_ms = sms; ctx->last_prov_ms = pms;
+  uint64_t pos = 0;
+  for (uint32_t i = 0; i < n_tasks; ++i) pos += cigar_len_out[i];
+  if (cigar_bytes_used) *cigar_bytes_used = pos;
+  if (!cigar_arena) return OTG_OK;
+  if (pos > cigar_capacity) return otg_fail(ctx, OTG_ERR_CAPACITY, "cigar_capacity %llu too small, %llu needed", (unsigned long long)cigar_capacity, (unsigned long long)pos);
+  std::vector<uint8_t> h_cig(slot[n_tasks] + 1);
+  HIP_TRY(ctx, hipMemcpyAsync(h_cig.data(), d_cig, slot[n_tasks], hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  pos = 0;
+  for (uint32_t i = 0; i < n_tasks; ++i) {
+    cigar_off_out[i] = pos;
+    memcpy(cigar_arena + pos, h_cig.data() + slot[i], cigar_len_out[i]);
+    pos += cigar_len_out[i];
+  }
+  return OTG_OK;
+}
+
+int otg_edit_align_last_ms(otg_ctx* ctx, double* score_ms, double* prov_ms)
+{
+  if (!ctx) return otg_fail(nullptr, OTG_ERR_ARG, "otg_edit_align_last_ms: NULL context");
+  if (score_ms) *score_ms = ctx->last_score_ms;
+  if (prov_ms) *prov_ms = ctx->last_prov_ms;
+  return OTG_OK;
+}
+
 int otg_affine_align_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_bytes,
                            const otg_align_task* tasks, uint32_t n_tasks,
                            int32_t mismatch, int32_t gap_open, int32_t gap_ext,

@@ -39,6 +39,7 @@ struct otg_ctx {
   uint32_t* edit_hist = nullptr;                  // pinned: [kind][16] = tier input counts of the last pass
   hipEvent_t edit_hist_ev[2] = {nullptr, nullptr};
   uint32_t edit_hist_mask[2] = {0u, 0u};          // the mask that pass ran with (0: no history)
+  double last_score_ms = 0.0, last_prov_ms = 0.0;  // HIP-event times of the two device passes of the latest otg_edit_align_batch (otg_edit_align_last_ms)
   double last_kernel_ms = 0.0;                    // HIP-event time of the kernels of the latest operator-level call that reports one (otg_last_kernel_ms)
   unsigned long long* affine_visited = nullptr;   // device counter: (score, diagonal) cells the exact gap-affine tiers visited (wfa_affine.hip)
   // aligner heuristic of the L1 calls and of the running pipeline (otg_set_heuristic / otg_params.heuristic; wfa_adaptive.hip)
@@ -200,6 +201,10 @@ __device__ __forceinline__ int otg_wave_match(const uint8_t* P, const uint8_t* T
 // wfa_edit.hip
 int otg_launch_edit(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* d_tasks, uint32_t n_tasks,
                     int32_t* d_scores, uint64_t* d_cells, float* kernel_ms, uint64_t* launches);
+
+// edit_align.hip: scores (the chain above), then the diamond provenance pass and the op strings (host arrays in, host arrays out)
+int otg_launch_edit_align(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* d_tasks, const otg_align_task* h_tasks, uint32_t n_tasks,
+                          int32_t* scores_out, uint32_t* len_out, uint8_t* d_cig_base, const uint64_t* cig_slot, double* score_ms, double* prov_ms);
 
 // bit-parallel edit tiers (myers_edit.hip), narrowest first: <blocks per lane, lanes per pair> = <1,8> <2,8> <3,8> <2,16> <3,16> <2,32> <2,64> <4,64>
 constexpr int OTG_MYERS_TIERS = 8;
