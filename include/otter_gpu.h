@@ -214,6 +214,22 @@ int otg_genotype_cluster_batch(otg_ctx* ctx, const otg_params* params,
  * what a roofline figure divides by; host copies excluded.  The reference has no counterpart (measurement hook).        */
 int otg_last_kernel_ms(otg_ctx* ctx, double* ms);
 
+/* Replaces seq2kcounts + KUSAGE + KUSAGE::hsdiv + get_gc_content for each allele of `otter vcf2mat` (src/anseqs.cpp:111-121,135-166,
+ * 186,203-208; src/vcf2mat.cpp:38-46,66-72).  Allele i is seq_arena[seq_off[i] .. + seq_len[i]).  1 <= k <= OTG_KMER_MAX (OTG_ERR_ARG
+ * otherwise).  Each of the L-k+1 windows is counted once: bin = base-4 code (A/a=0 C/c=1 G/g=2 T/t=3, first base most significant) when all k
+ * bytes are ACGTacgt, else bin 4^k.  usage_out: n rows of 4^k+1 doubles, row-major, value = count / total (total = L-k+1 as an int; 0/0 = NaN
+ * when L < k); gc_out[i] = (C/c/G/g bytes) / L (NaN when L = 0); hsd_out[i] = e^(-sum v log v) over the bins with v > 0 in ascending order
+ * (1 when there is none).  Counts, values and GC are exact; hsd carries the device's log/pow.  A NULL output is left in HBM
+ * (otg_kmer_usage_device_results).  A batch whose rows (and, for k >= 8, u32 histograms) exceed the 4 GiB workspace is OTG_ERR_CAPACITY. */
+int otg_kmer_usage_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_bytes, const uint64_t* seq_off, const uint32_t* seq_len,
+                         uint32_t n, int32_t k, double* usage_out, double* gc_out, double* hsd_out);
+/* Device pointers of the latest otg_kmer_usage_batch of this context (n and k as passed to it): usage rows, gc, hsd.  Valid until the next
+ * otg_kmer_usage_batch on this context or otg_destroy.  The reference has no counterpart. */
+int otg_kmer_usage_device_results(otg_ctx* ctx, uint32_t n, int32_t k, const double** usage, const double** gc, const double** hsd);
+/* HIP-event times (ms) of the latest otg_kmer_usage_batch on this context: counting (k <= 7: counting and epilogue in one kernel) and the
+ * epilogue passes of k >= 8.  Measurement hook; the reference has no counterpart. */
+int otg_kmer_usage_last_ms(otg_ctx* ctx, double* count_ms, double* epilogue_ms);
+
 /* ================================================================= L3: region-batch pipeline
  * SoA image of std::vector<ANREAD> (src/anseqs.hpp:56-76) for a batch of regions.               */
 typedef struct otg_read {
@@ -567,6 +583,51 @@ typedef struct otg_compare_job {
   void*       warn_user;
 } otg_compare_job;
 int otg_compare_files(const otg_compare_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
+
+/* ---------------------------------------------------------------------------------------------
+ * `otter vcf2mat` (src/vcf2mat.cpp, src/command_vcf2mat.cpp): one row of k-mer usage per allele of a VCF.
+ * ------------------------------------------------------------------------------------------- */
+#define OTG_KMER_MAX 12          /* largest supported k (the reference accepts 32)      */
+typedef struct otg_vcf otg_vcf;
+typedef struct otg_vcf_record {
+  uint64_t region_off;           /* the ID column (vcf2mat's region string) in the region arena      */
+  uint32_t region_len;
+  uint32_t first_allele;         /* index of allele 0 (REF) in the batch's allele arrays             */
+  uint32_t n_alleles;            /* REF + the ALT alleles                                            */
+  uint32_t reserved;
+} otg_vcf_record;
+/* Replaces GZIPiter (src/angzipiter.hpp) on a VCF: plain text, gzip or BGZF through zlib's gz* reader. */
+int  otg_vcf_open(const char* path, otg_vcf** out);
+void otg_vcf_close(otg_vcf* v);
+/* Replaces the line loop and parse_alleles of vcf2mat (src/vcf2mat.cpp:16-36,57-65): the next records of the file, in file order, as many as
+ * fit the capacities.  Lines starting with '#' are skipped; a line is split on '\t' with std::getline semantics (a trailing empty field is
+ * dropped); column 3 is the region, column 4 (REF) allele 0, column 5 (ALT) adds nothing when it is ".", the allele "N" when it is exactly
+ * "<DEL>", else its ','-separated fields (getline semantics again).  A line with fewer than 4 columns gives no record.  Unlike the reference, a
+ * last line without '\n' is read and lines may be longer than 1 MB.  Alleles are packed in seq_arena at seq_off[i], length seq_len[i]; region
+ * strings in region_arena.  *n_records == 0 at the end of the file.  OTG_ERR_CAPACITY when even the next record does not fit: the counters
+ * then hold what it alone needs, and it is returned by the next call.  *bytes_in (nullable) += the text bytes consumed. */
+int  otg_vcf_read_alleles(otg_vcf* v, otg_vcf_record* records, uint32_t records_capacity, uint32_t* n_records,
+                          char* region_arena, uint64_t region_capacity, uint64_t* region_used,
+                          uint64_t* seq_off, uint32_t* seq_len, uint32_t alleles_capacity, uint32_t* n_alleles,
+                          uint8_t* seq_arena, uint64_t arena_capacity, uint64_t* arena_used, uint64_t* bytes_in);
+/* Replaces the output of vcf2mat (src/vcf2mat.cpp:66-72): per allele a of record r, the row
+ * region \t i \t gc[a] \t seq_len[a] \t hsd[a] (\t usage[a][b] for the 4^k+1 bins) \n, with a = records[r].first_allele + i.  Doubles as
+ * std::cout prints them (%g); every NaN prints "-nan", as the reference's 0/0 does on x86-64.  Same buffer protocol as otg_emit_alleles. */
+int  otg_vcf2mat_emit(const otg_vcf_record* records, uint32_t n_records, const char* region_arena, const uint32_t* seq_len, int32_t k,
+                      const double* usage, const double* gc, const double* hsd, char* out, uint64_t out_capacity, uint64_t* out_len);
+/* `otter vcf2mat` from a file to text in one call (src/vcf2mat.cpp:48-77): the BED is parsed and filters nothing; records in bounded batches
+ * (sized by the bytes of a row, so that k = 12 fits), otg_kmer_usage_batch on the device, the rows formatted by `threads` host threads and
+ * written in file order.  Reading the next batch overlaps the device pass and the emit of the current one.  stats: n_regions = records,
+ * n_alleles, input_bytes = VCF text bytes, output_bytes, ms_ingest = reading, ms_hot_path = device, ms_emit = formatting. */
+typedef struct otg_vcf2mat_job {
+  const char* vcf_path;          /* positional <VCF[.GZ]>                                            */
+  const char* bed_path;          /* -b: required, parsed, unused (as in the reference)               */
+  int32_t     k;                 /* -k: 1..OTG_KMER_MAX                                               */
+  int32_t     threads;           /* -t: host threads of the emit                                     */
+  int32_t     device;            /* HIP device ordinal                                               */
+  uint32_t    batch_alleles;     /* alleles per batch, 0 = sized from k                              */
+} otg_vcf2mat_job;
+int otg_vcf2mat_files(const otg_vcf2mat_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
 
 /* The dispatcher keeps its per-device contexts (and their HBM workspaces) for the next job of the process; this frees them. */
 void otg_assemble_files_release(void);

@@ -20,6 +20,8 @@ EXPORTS = [
     "otg_fasta_seq", "otg_fasta_fetch", "otg_fasta_region_flanks",
     "otg_bam_sample_index", "otg_bam_sample", "otg_ingest_alleles", "otg_emit_vcf_header", "otg_emit_vcf_lines", "otg_emit_genotype_lengths", "otg_assemble_files", "otg_assemble_files_release", "otg_assemble_batch_plan", "otg_genotype_files", "otg_wgat",
     "otg_edit_align_batch", "otg_edit_align_last_ms", "otg_ingest_compare_alleles", "otg_compare_emit", "otg_compare_files",
+    "otg_kmer_usage_batch", "otg_kmer_usage_device_results", "otg_kmer_usage_last_ms", "otg_vcf_open", "otg_vcf_close", "otg_vcf_read_alleles",
+    "otg_vcf2mat_emit", "otg_vcf2mat_files",
     "otg_comm_unique_id", "otg_comm_create", "otg_comm_destroy", "otg_gather_sizes", "otg_gather_records",
 ]
 
@@ -136,6 +138,52 @@ class Context:
         """(score chain ms, provenance pass ms) of the latest edit_align_batch (HIP events)."""
         a, b = C.c_double(0), C.c_double(0)
         self._check(self._L.otg_edit_align_last_ms(self._h, C.byref(a), C.byref(b)), "otg_edit_align_last_ms")
+        return a.value, b.value
+
+    def kmer_usage_batch(self, arena, seq_off, seq_len, k=3, device_tensor=False):
+        """otg_kmer_usage_batch: per allele the 4^k+1 k-mer frequencies of vcf2mat, its GC fraction and Hill-Shannon diversity ->
+        (usage [n, 4^k+1] float64, gc [n], hsd [n]) as numpy arrays, or with device_tensor=True as float64 torch tensors on this context's
+        device that wrap the results in HBM without a copy (valid until the next kmer_usage_batch on this context)."""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+        ln = np.ascontiguousarray(seq_len, dtype=np.uint32)
+        n, bins = len(ln), 4 ** int(k) + 1
+        if device_tensor:
+            rc = self._L.otg_kmer_usage_batch(self._h, abi.ptr(arena), C.c_uint64(arena.size), abi.ptr(off), abi.ptr(ln), C.c_uint32(n),
+                                              C.c_int32(k), None, None, None)
+            self._check(rc, "otg_kmer_usage_batch")
+            return self._kmer_device_results(n, k)
+        usage = np.zeros((n, bins), dtype=np.float64)
+        gc = np.zeros(n, dtype=np.float64)
+        hsd = np.zeros(n, dtype=np.float64)
+        rc = self._L.otg_kmer_usage_batch(self._h, abi.ptr(arena), C.c_uint64(arena.size), abi.ptr(off), abi.ptr(ln), C.c_uint32(n), C.c_int32(k),
+                                          abi.ptr(usage), abi.ptr(gc), abi.ptr(hsd))
+        self._check(rc, "otg_kmer_usage_batch")
+        return usage, gc, hsd
+
+    def _kmer_device_results(self, n, k):
+        import torch
+        pu, pg, ph = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._check(self._L.otg_kmer_usage_device_results(self._h, C.c_uint32(n), C.c_int32(k), C.byref(pu), C.byref(pg), C.byref(ph)),
+                    "otg_kmer_usage_device_results")
+        dev = torch.device("cuda", self.device)
+        bins = 4 ** int(k) + 1
+
+        class _Span:          # __cuda_array_interface__ carrier: torch.as_tensor wraps it without copying
+            def __init__(self, ptr, shape):
+                self.__cuda_array_interface__ = {"shape": shape, "typestr": "<f8", "data": (int(ptr), False), "version": 2, "strides": None}
+
+        def wrap(ptr, shape):
+            if n == 0:
+                return torch.zeros(shape, dtype=torch.float64, device=dev)
+            return torch.as_tensor(_Span(ptr, shape), device=dev)
+
+        return wrap(pu.value, (n, bins)), wrap(pg.value, (n,)), wrap(ph.value, (n,))
+
+    def kmer_usage_last_ms(self):
+        """(counting ms, epilogue ms) of the latest kmer_usage_batch (HIP events; k <= 7 counts and finishes in one kernel)."""
+        a, b = C.c_double(0), C.c_double(0)
+        self._check(self._L.otg_kmer_usage_last_ms(self._h, C.byref(a), C.byref(b)), "otg_kmer_usage_last_ms")
         return a.value, b.value
 
     def affine_align_batch(self, arena, tasks, x=4, o=6, e=2, want_cells=False):
@@ -781,3 +829,92 @@ def compare_files(truth_bam, query_bam, bed, threads=1, device=0, batch_regions=
     if rc != 0:
         raise OtterGpuError("otg_compare_files failed (%d): %s" % (rc, (L.otg_last_error(None) or b"").decode()))
     return b"".join(chunks), b"".join(warns), {k: getattr(st, k) for k, _ in abi.JobStats._fields_}
+
+
+def vcf_read_alleles(path, max_alleles=1 << 16, max_bytes=64 << 20):
+    """otg_vcf_read_alleles over a whole VCF (batches of at most max_alleles alleles / max_bytes sequence bytes) ->
+    {"records": vcf_record_dt array, "regions": bytes, "seq_off", "seq_len", "arena": uint8 array, "bytes_in", "batches"}; the records of
+    later batches are rebased onto the concatenated arrays."""
+    L = load()
+    L.otg_vcf_open.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+    L.otg_vcf_close.argtypes = [C.c_void_p]
+    h = C.c_void_p()
+    if L.otg_vcf_open(path.encode(), C.byref(h)) != 0:
+        raise OtterGpuError("otg_vcf_open failed: %s" % _err(L))
+    recs, regs, offs, lens, arenas = [], [], [], [], []
+    base_r, base_a, base_s, batches = 0, 0, 0, 0
+    bytes_in = C.c_uint64(0)
+    cap_r, cap_a, cap_s, cap_g = max_alleles, max_alleles, max_bytes, 1 << 20
+    try:
+        while True:
+            rec = np.zeros(cap_r, dtype=abi.vcf_record_dt)
+            reg = np.zeros(cap_g, dtype=np.uint8)
+            off = np.zeros(cap_a, dtype=np.uint64)
+            ln = np.zeros(cap_a, dtype=np.uint32)
+            ar = np.zeros(cap_s, dtype=np.uint8)
+            nr, ru, na, au = C.c_uint32(0), C.c_uint64(0), C.c_uint32(0), C.c_uint64(0)
+            rc = L.otg_vcf_read_alleles(h, abi.ptr(rec), C.c_uint32(cap_r), C.byref(nr), abi.ptr(reg), C.c_uint64(cap_g), C.byref(ru),
+                                        abi.ptr(off), abi.ptr(ln), C.c_uint32(cap_a), C.byref(na), abi.ptr(ar), C.c_uint64(cap_s), C.byref(au),
+                                        C.byref(bytes_in))
+            if rc == abi.OTG_ERR_CAPACITY:
+                cap_a, cap_r = max(cap_a, na.value), max(cap_r, 1)
+                cap_g, cap_s = max(cap_g, ru.value), max(cap_s, au.value)
+                continue
+            if rc != 0:
+                raise OtterGpuError("otg_vcf_read_alleles failed (%d): %s" % (rc, _err(L)))
+            if nr.value == 0:
+                break
+            batches += 1
+            r = rec[:nr.value].copy()
+            r["region_off"] += base_r
+            r["first_allele"] += base_a
+            recs.append(r); regs.append(reg[:ru.value].tobytes())
+            offs.append(off[:na.value] + np.uint64(base_s)); lens.append(ln[:na.value].copy()); arenas.append(ar[:au.value].copy())
+            base_r += ru.value; base_a += na.value; base_s += au.value
+    finally:
+        L.otg_vcf_close(h)
+    cat = lambda xs, dt: np.concatenate(xs) if xs else np.zeros(0, dtype=dt)
+    return {"records": cat(recs, abi.vcf_record_dt), "regions": b"".join(regs), "seq_off": cat(offs, np.uint64), "seq_len": cat(lens, np.uint32),
+            "arena": cat(arenas, np.uint8), "bytes_in": int(bytes_in.value), "batches": batches}
+
+
+def vcf2mat_emit(records, regions, seq_len, k, usage, gc, hsd):
+    """otg_vcf2mat_emit: the rows of vcf2mat for the records (vcf_record_dt) and per-allele values -> text bytes."""
+    L = load()
+    records = np.ascontiguousarray(records, dtype=abi.vcf_record_dt)
+    seq_len = np.ascontiguousarray(seq_len, dtype=np.uint32)
+    usage = np.ascontiguousarray(usage, dtype=np.float64)
+    gc = np.ascontiguousarray(gc, dtype=np.float64)
+    hsd = np.ascontiguousarray(hsd, dtype=np.float64)
+    reg = np.frombuffer(regions + b"\0", dtype=np.uint8)
+    need = C.c_uint64(0)
+    args = lambda out, cap: (abi.ptr(records), C.c_uint32(len(records)), abi.ptr(reg), abi.ptr(seq_len), C.c_int32(k), abi.ptr(usage),
+                             abi.ptr(gc), abi.ptr(hsd), out, C.c_uint64(cap), C.byref(need))
+    rc = L.otg_vcf2mat_emit(*args(None, 0))
+    if rc not in (0, abi.OTG_ERR_CAPACITY):
+        raise OtterGpuError("otg_vcf2mat_emit failed (%d): %s" % (rc, _err(L)))
+    out = C.create_string_buffer(need.value + 1)
+    rc = L.otg_vcf2mat_emit(*args(out, need.value))
+    if rc != 0:
+        raise OtterGpuError("otg_vcf2mat_emit failed (%d): %s" % (rc, _err(L)))
+    return out.raw[:need.value]
+
+
+def vcf2mat_files(vcf, bed, k=3, threads=1, device=0, batch_alleles=0):
+    """otg_vcf2mat_files: `otter vcf2mat` from a VCF (plain, gzip or BGZF) to text.  Returns (text bytes, stats dict)."""
+    L = load()
+    job = abi.Vcf2matJob()
+    job.vcf_path = vcf.encode(); job.bed_path = bed.encode()
+    job.k = k; job.threads = threads; job.device = device; job.batch_alleles = batch_alleles
+    chunks = []
+
+    def sink(_user, data, n):
+        chunks.append(C.string_at(data, n))
+        return 0
+    cb = abi.WRITE_FN(sink)
+    st = abi.JobStats()
+    L.otg_vcf2mat_files.argtypes = [C.POINTER(abi.Vcf2matJob), abi.WRITE_FN, C.c_void_p, C.POINTER(abi.JobStats)]
+    rc = L.otg_vcf2mat_files(C.byref(job), cb, None, C.byref(st))
+    if rc != 0:
+        raise OtterGpuError("otg_vcf2mat_files failed (%d): %s" % (rc, _err(L)))
+    return b"".join(chunks), {k_: getattr(st, k_) for k_, _ in abi.JobStats._fields_}

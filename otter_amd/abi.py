@@ -181,6 +181,19 @@ class CompareCounts(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_compared", "skip_many_truth", "skip_one_truth", "skip_no_truth", "skip_no_query")]
 
 
+class Vcf2matJob(C.Structure):
+    """otg_vcf2mat_job (include/otter_gpu.h)."""
+    _fields_ = [("vcf_path", C.c_char_p), ("bed_path", C.c_char_p), ("k", C.c_int32), ("threads", C.c_int32), ("device", C.c_int32),
+                ("batch_alleles", C.c_uint32)]
+
+
+# otg_vcf_record (include/otter_gpu.h)
+vcf_record_dt = np.dtype([("region_off", np.uint64), ("region_len", np.uint32), ("first_allele", np.uint32), ("n_alleles", np.uint32),
+                          ("reserved", np.uint32)])
+assert vcf_record_dt.itemsize == 24
+KMER_MAX = 12
+
+
 class JobStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_regions", "n_regions_ok", "n_regions_skipped", "n_reads", "n_alleles", "input_bytes", "output_bytes")] + \
                [("n_devices", C.c_uint32), ("reserved", C.c_uint32)] + [(k, C.c_double) for k in ("ms_total", "ms_ingest", "ms_hot_path", "ms_emit")]

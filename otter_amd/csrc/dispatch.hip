@@ -13,6 +13,7 @@
 // (the reference's order with -t 1; with -t > 1 the reference prints in completion order).
 #include "otg_common.hpp"
 #include "otg_compare.hpp"
+#include "otg_vcf2mat.hpp"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -612,6 +613,107 @@ int otg_compare_files(const otg_compare_job* job, otg_write_fn write, void* user
   }
   cleanup();
   st.ms_total = ms_since(t_all); st.n_devices = 1;
+  if (stats) *stats = st;
+  return OTG_OK;
+}
+
+// `otter vcf2mat` from a file to text — vcf2mat() (src/vcf2mat.cpp:48-77).  Two batches in flight: while the alleles of one are counted on
+// the device and its rows formatted by the host threads, the next one is read on a host thread.  Batches are bounded by alleles and by the
+// bytes of their rows (a row is 4^k+1 doubles: 134 MB at k = 12).
+int otg_vcf2mat_files(const otg_vcf2mat_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
+{
+  if (!job || !write || !job->vcf_path || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "otg_vcf2mat_files: NULL job, writer, VCF or BED path");
+  const int k = job->k;
+  if (k < 1 || k > OTG_KMER_MAX) return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--kmer-size' (%d). Needs to be 1 <= x <= %d.", k, OTG_KMER_MAX);
+  const auto t_all = Clock::now();
+  otg_job_stats st{};
+  {
+    // parse_bed_file (src/vcf2mat.cpp:50-51): required, filters nothing
+    uint32_t n = 0, skipped = 0; uint64_t cu = 0;
+    int rc = otg_parse_bed_file(job->bed_path, nullptr, 0, &n, nullptr, 0, &cu, &skipped);
+    if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) return rc;
+    std::vector<otg_bed> beds((size_t)n + 1); std::vector<char> chr((size_t)cu + 16);
+    rc = otg_parse_bed_file(job->bed_path, beds.data(), (uint32_t)beds.size(), &n, chr.data(), chr.size(), &cu, &skipped);
+    if (rc != OTG_OK) return rc;
+  }
+  otg_vcf* vcf = nullptr;
+  int rc = otg_vcf_open(job->vcf_path, &vcf);
+  if (rc != OTG_OK) return rc;
+  otg_ctx* ctx = pool_acquire(job->device);
+  if (!ctx) { otg_vcf_close(vcf); return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_vcf2mat_files: %s", last_err().c_str()); }
+  auto cleanup = [&] { pool_release(job->device, ctx); otg_vcf_close(vcf); };
+  const uint64_t bins = (1ull << (2 * k)) + 1;
+  // alleles per batch: at most 1 GiB of rows on the host and what the device workspace of otg_kmer_usage_batch holds (k >= 8: + u32 histograms)
+  const uint64_t dev_row = bins * 8 + (k >= 8 ? bins * 4 : 0);
+  uint64_t per = job->batch_alleles ? job->batch_alleles : std::min<uint64_t>(65536, std::max<uint64_t>(1, (1ull << 30) / (bins * 8)));
+  per = std::max<uint64_t>(1, std::min<uint64_t>({per, (4ull << 30) / dev_row, 1ull << 24}));
+  const int threads = job->threads > 0 ? job->threads : 1;
+  struct VBatch {
+    std::vector<otg_vcf_record> rec; std::vector<char> regions; std::vector<uint64_t> off; std::vector<uint32_t> len; std::vector<uint8_t> seqs;
+    uint32_t nr = 0, na = 0; uint64_t ru = 0, au = 0, bytes = 0; int rc = OTG_OK; double ms = 0; std::string err;
+  };
+  VBatch bufs[2];
+  for (auto& B : bufs) { B.rec.resize(per); B.off.resize(per); B.len.resize(per); B.regions.resize(1 << 20); B.seqs.resize(64ull << 20); }
+  auto read_into = [&](VBatch& B) {
+    const auto t0 = Clock::now();
+    B.bytes = 0;
+    for (;;) {
+      B.rc = otg_vcf_read_alleles(vcf, B.rec.data(), (uint32_t)B.rec.size(), &B.nr, B.regions.data(), B.regions.size(), &B.ru, B.off.data(), B.len.data(),
+                                  (uint32_t)B.off.size(), &B.na, B.seqs.data(), B.seqs.size(), &B.au, &B.bytes);
+      if (B.rc != OTG_ERR_CAPACITY) break;
+      // one record larger than the buffers: grow them to hold it (its alleles may exceed `per`; the device call then reports the workspace)
+      if (B.na > B.off.size()) { B.off.resize(B.na); B.len.resize(B.na); }
+      if (B.ru > B.regions.size()) B.regions.resize(B.ru);
+      if (B.au > B.seqs.size()) B.seqs.resize(B.au);
+    }
+    if (B.rc != OTG_OK) { B.err = last_err(); B.nr = 0; }
+    B.ms = ms_since(t0);
+  };
+  std::vector<double> usage, gc, hsd;
+  std::vector<std::string> parts((size_t)threads);
+  read_into(bufs[0]);
+  for (uint32_t idx = 0;; ++idx) {
+    VBatch& B = bufs[idx & 1];
+    st.ms_ingest += B.ms; st.input_bytes += B.bytes;
+    if (B.rc != OTG_OK) { rc = B.rc; const std::string e = B.err; cleanup(); return otg_fail(nullptr, rc, "otg_vcf2mat_files: %s", e.c_str()); }
+    if (B.nr == 0) break;
+    std::thread next([&, idx] { read_into(bufs[(idx + 1) & 1]); });
+    struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{next};
+    auto join_next = [&] { if (next.joinable()) next.join(); };
+    st.n_regions += B.nr; st.n_alleles += B.na;
+    auto t0 = Clock::now();
+    usage.resize((size_t)B.na * bins); gc.resize(B.na); hsd.resize(B.na);
+    rc = otg_kmer_usage_batch(ctx, B.seqs.data(), B.au, B.off.data(), B.len.data(), B.na, k, usage.data(), gc.data(), hsd.data());
+    if (rc != OTG_OK) { const std::string e = otg_last_error(ctx) ? otg_last_error(ctx) : ""; join_next(); cleanup(); return otg_fail(nullptr, rc, "otg_vcf2mat_files: %s", e.c_str()); }
+    st.ms_hot_path += ms_since(t0);
+    t0 = Clock::now();
+    // the rows of contiguous record ranges with about equal allele counts, one range per thread, written in file order
+    std::vector<uint32_t> cut((size_t)threads + 1, B.nr);
+    cut[0] = 0;
+    for (uint32_t r = 0, t = 1; r < B.nr && t < (uint32_t)threads; ++r)
+      if ((uint64_t)B.rec[r].first_allele * threads >= (uint64_t)B.na * t) cut[t++] = r;
+    for (int t = 1; t <= threads; ++t) cut[t] = std::max(cut[t], cut[t - 1]);
+    {
+      std::vector<std::thread> pool;
+      for (int t = 0; t < threads; ++t) {
+        parts[t].clear();
+        if (cut[t + 1] > cut[t])
+          pool.emplace_back([&, t] { otg_vcf2mat_rows(parts[t], B.rec.data() + cut[t], cut[t + 1] - cut[t], B.regions.data(), B.len.data(), k,
+                                                      usage.data(), gc.data(), hsd.data()); });
+      }
+      for (auto& th : pool) th.join();
+    }
+    st.ms_emit += ms_since(t0);
+    for (int t = 0; t < threads; ++t) {
+      if (!parts[t].empty() && write(user, parts[t].data(), parts[t].size()) != 0) {
+        join_next(); cleanup(); return otg_fail(nullptr, OTG_ERR_ARG, "otg_vcf2mat_files: the writer failed");
+      }
+      st.output_bytes += parts[t].size();
+    }
+    join_next();
+  }
+  cleanup();
+  st.ms_total = ms_since(t_all); st.n_devices = 1; st.n_regions_ok = st.n_regions;
   if (stats) *stats = st;
   return OTG_OK;
 }

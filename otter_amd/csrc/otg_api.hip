@@ -135,6 +135,7 @@ void otg_destroy(otg_ctx* ctx)
   for (int i = 0; i < 2; ++i) if (ctx->edit_hist_ev[i]) (void)hipEventDestroy(ctx->edit_hist_ev[i]);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
+  if (ctx->ev2) (void)hipEventDestroy(ctx->ev2);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }

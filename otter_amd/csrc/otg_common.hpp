@@ -40,6 +40,8 @@ struct otg_ctx {
   hipEvent_t edit_hist_ev[2] = {nullptr, nullptr};
   uint32_t edit_hist_mask[2] = {0u, 0u};          // the mask that pass ran with (0: no history)
   double last_score_ms = 0.0, last_prov_ms = 0.0;  // HIP-event times of the two device passes of the latest otg_edit_align_batch (otg_edit_align_last_ms)
+  double last_kmer_count_ms = 0.0, last_kmer_epi_ms = 0.0;  // HIP-event times of the latest otg_kmer_usage_batch (otg_kmer_usage_last_ms)
+  hipEvent_t ev2 = nullptr;                       // third timing event, created on first use (kmer_usage.hip)
   double last_kernel_ms = 0.0;                    // HIP-event time of the kernels of the latest operator-level call that reports one (otg_last_kernel_ms)
   unsigned long long* affine_visited = nullptr;   // device counter: (score, diagonal) cells the exact gap-affine tiers visited (wfa_affine.hip)
   // aligner heuristic of the L1 calls and of the running pipeline (otg_set_heuristic / otg_params.heuristic; wfa_adaptive.hip)
@@ -70,6 +72,7 @@ enum {
   SLOT_P0, SLOT_P1, SLOT_P2, SLOT_P3, SLOT_P4, SLOT_P5, SLOT_P6, SLOT_P7, SLOT_P8, SLOT_P9,
   SLOT_P10, SLOT_P11, SLOT_P12, SLOT_P13, SLOT_P14, SLOT_P15, SLOT_P16, SLOT_P17, SLOT_P18, SLOT_P19,
   SLOT_P20, SLOT_P21, SLOT_P22, SLOT_P23, SLOT_P24, SLOT_P25, SLOT_P26, SLOT_P27, SLOT_P28, SLOT_P29,
+  SLOT_KMER_SEQ, SLOT_KMER_META, SLOT_KMER_HIST, SLOT_KMER_OUT,     // otg_kmer_usage_batch (kmer_usage.hip); OUT stays valid for the device results
   SLOT_COUNT
 };
 
