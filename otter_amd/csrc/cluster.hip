@@ -13,15 +13,32 @@
 // the same comparisons on the same bits.
 #include "otg_common.hpp"
 #include <cmath>
+#include <type_traits>
 
 #define OTG_EXP_TAB_QUAL __device__ __constant__ const
 #include "exp_table.inc"
 
 namespace {
 
-constexpr int NMAX = 256;      // max valid reads per region handled on chip (reference default max_cov = 200)
+constexpr int NMAX = (int)OTG_CLUSTER_NMAX;   // max valid reads (alleles) per region whose per-read scratch lives in LDS (reference default max_cov = 200)
 constexpr int GMAX = 512;      // max KDE grid points
 constexpr int DLDS = 2016;     // dist working copy kept in LDS when n <= 64
+
+// A per-read scratch array: on chip for the narrow kernels (regions of up to NMAX reads / alleles), a view into the workgroup's own slab
+// in HBM for the wide ones (regions above NMAX, or every region under OTG_CLUSTER_WIDE).  The code that uses the scratch is the same.
+template <class T, int N, bool WIDE> using arr_t = std::conditional_t<WIDE, T*, T[N]>;
+
+// The wide kernels' slab, one per workgroup, carved by thread 0: every array 16-byte aligned.  The host sizes a workgroup's slab by running
+// the same carve on a null base (`base == nullptr`: offsets only), so the size follows the arrays carve() takes.
+struct SlabCarver {
+  char* base; size_t off;
+  template <class T> __host__ __device__ T* take(size_t count)
+  {
+    T* q = base ? (T*)(base + off) : nullptr;
+    off += (count * sizeof(T) + 15) & ~(size_t)15;
+    return q;
+  }
+};
 
 __device__ __constant__ double c_grid[GMAX];
 
@@ -176,23 +193,38 @@ __device__ bool std_sort_emul(int* f, int n, const MaxCmp& cmp)
 // then the loop continues on [first,cut)); partitions are disjoint, so processing order does not change
 // the result.
 
-struct Lds {
+template <bool WIDE>
+struct LdsT {
+  template <class T, int N> using arr = arr_t<T, N, WIDE>;
   double dens[GMAX];
   double sums[GMAX];
-  double members[NMAX];
-  double zdist[NMAX];
-  double height[NMAX];
-  double dwork[DLDS];
+  arr<double, NMAX> members;
+  arr<double, NMAX> zdist;
+  arr<double, NMAX> height;
+  double dwork[WIDE ? 1 : DLDS];
   int maxi[GMAX / 2 + 2], mini[GMAX / 2 + 2];
   double maxv[GMAX / 2 + 2], minv[GMAX / 2 + 2];
   int sorted[GMAX / 2 + 2];
-  int nn_chain[NMAX], succ[NMAX + 1], pred[NMAX + 1];
-  int z1[NMAX], z2[NMAX], zrank[NMAX];
-  int parent[2 * NMAX];
-  int merge[2 * NMAX];
-  int labels[NMAX], labels2[NMAX];
-  int ct_up[NMAX + 1], ct_own[NMAX], ct_first[NMAX + 1], ct_lab[NMAX + 1];     // cutree_wave scratch
-  int cnt[NMAX], maxsz[NMAX], req[NMAX], remap[NMAX];
+  arr<int, NMAX> nn_chain; int succ[WIDE ? 1 : NMAX + 1]; arr<int, NMAX + 1> pred;
+  arr<int, NMAX> z1, z2, zrank;
+  arr<int, 2 * NMAX> parent;
+  arr<int, 2 * NMAX> merge;
+  arr<int, NMAX> labels; int labels2[WIDE ? 1 : NMAX];
+  arr<int, NMAX + 1> ct_up; arr<int, NMAX> ct_own; arr<int, NMAX + 1> ct_first, ct_lab;     // cutree_wave scratch
+  arr<int, NMAX> cnt, maxsz, req, remap;
+  // wide: points the per-read arrays into `slab` at capacity `cap`; returns the bytes taken
+  __host__ __device__ size_t carve(char* slab, int cap)
+  {
+    SlabCarver c{slab, 0};
+    if constexpr (WIDE) {
+      members = c.take<double>(cap); zdist = c.take<double>(cap); height = c.take<double>(cap);
+      nn_chain = c.take<int>(cap + 1); pred = c.take<int>(cap + 1); z1 = c.take<int>(cap + 1); z2 = c.take<int>(cap + 1); zrank = c.take<int>(cap + 1);
+      parent = c.take<int>(2 * cap + 1); merge = c.take<int>(2 * cap + 1); labels = c.take<int>(cap + 1);
+      ct_up = c.take<int>(cap + 1); ct_own = c.take<int>(cap + 1); ct_first = c.take<int>(cap + 1); ct_lab = c.take<int>(cap + 1);
+      cnt = c.take<int>(cap + 1); maxsz = c.take<int>(cap + 1); req = c.take<int>(cap + 1); remap = c.take<int>(cap + 1);
+    }
+    return c.off;
+  }
   double total;
   int n_max, n_min, err;
   int do_hclust;
@@ -390,18 +422,32 @@ __device__ void hclust_to_merge(int n, double* D, S& L, int tid)
   __syncthreads();
 }
 
-template <bool FMA>
+// WIDE = false: regions of at most n_split (<= NMAX) valid reads, scratch in LDS; WIDE = true: the regions of `wide_idx` above n_split,
+// per-read scratch in this workgroup's slab of `slab_stride` bytes (capacity `cap` reads).  Each instantiation leaves the other's regions
+// untouched.
+template <bool FMA, bool WIDE>
 __global__ __launch_bounds__(256) void cluster_kernel(
     ClusterArgs A, const double* __restrict__ dist, const uint64_t* __restrict__ dist_off,
     const uint32_t* __restrict__ read_len, const uint64_t* __restrict__ len_off, const uint32_t* __restrict__ n_valid,
-    uint32_t n_regions, double* __restrict__ gwork,
+    uint32_t n_regions, double* __restrict__ gwork, int n_split, const uint32_t* __restrict__ wide_idx, uint32_t n_wide,
+    char* __restrict__ slab, size_t slab_stride, int cap,
     int32_t* __restrict__ labels_out, int32_t* __restrict__ ic_out, int32_t* __restrict__ fc_out,
     double* __restrict__ bounds_out, int32_t* __restrict__ err_out)
 {
-  __shared__ Lds L;
+  __shared__ LdsT<WIDE> L;
   const int tid = threadIdx.x;
-  for (uint32_t r = blockIdx.x; r < n_regions; r += gridDim.x) {
+  if constexpr (WIDE) {
+    if (tid == 0) L.carve(slab + (size_t)blockIdx.x * slab_stride, cap);
+    __syncthreads();
+  }
+  for (uint32_t it = blockIdx.x; it < (WIDE ? n_wide : n_regions); it += gridDim.x) {
+    const uint32_t r = WIDE ? wide_idx[it] : it;          // the wide kernel walks the list of regions that may exceed n_split
     const int n = (int)n_valid[r];
+    if (WIDE ? n <= n_split : n > n_split) continue;
+    if (WIDE && n > cap) {      // the launcher sizes the slab from an upper bound of every region's n: not reached
+      if (tid == 0) { ic_out[r] = 0; fc_out[r] = 0; if (err_out) err_out[r] = 10; }
+      continue;
+    }
     const double* dv = dist + dist_off[r];
     const uint32_t* lens = read_len + len_off[r];
     int32_t* lab = labels_out + len_off[r];
@@ -412,11 +458,10 @@ __global__ __launch_bounds__(256) void cluster_kernel(
     }
     __syncthreads();
     // ---- trivial cases (src/otterclust.cpp:121-156)
-    if (n <= 2 || A.max_alleles == 1 || n > NMAX) {
+    if (n <= 2 || A.max_alleles == 1) {
       if (tid == 0) {
         int ic = 0, fc = 0;
-        if (n > NMAX) { L.err = 10; }
-        else if (n == 1) { lab[0] = 0; ic = fc = 1; }
+        if (n == 1) { lab[0] = 0; ic = fc = 1; }
         else if (n == 2) {
           lab[0] = 0; lab[1] = 0; ic = fc = 1;
           if (A.max_alleles != 1 && !(dv[0] <= A.max_error)) { lab[1] = 1; ic = fc = 2; }
@@ -529,7 +574,7 @@ __global__ __launch_bounds__(256) void cluster_kernel(
       continue;
     }
     // ---- hclust_fast(AVERAGE) on a working copy (:181-182)
-    double* D = (npairs <= (size_t)DLDS) ? L.dwork : gwork + dist_off[r];
+    double* D = (!WIDE && npairs <= (size_t)DLDS) ? L.dwork : gwork + dist_off[r];
     for (size_t q = tid; q < npairs; q += blockDim.x) D[q] = dv[q];
     __syncthreads();
     hclust_to_merge(n, D, L, tid);
@@ -612,24 +657,49 @@ __global__ __launch_bounds__(256) void cluster_kernel(
 //   5. genotypes = first appearances of (gt_l, gt_k): one thread per allele looks for an earlier allele with its pair, ballot + prefix
 //      count numbers the first appearances; medoids: one thread per allele sums its row over its genotype (ascending, as the reference),
 //      one thread per genotype takes the first strict minimum.
+// Regions of more than NMAX alleles (or every region under OTG_CLUSTER_WIDE) run the same code on the WIDE instantiation: the per-allele
+// arrays are views into the workgroup's slab in HBM, both matrices are clustered in place in HBM (g_work / g_dk).
 constexpr int GT_DLDS = 5152;      // 102 alleles: BASELINE configs[3] has 101
-struct HcScratch {
-  double members[NMAX], zdist[NMAX], height[NMAX];
-  int nn_chain[NMAX], pred[NMAX + 1];
-  int z1[NMAX], z2[NMAX], zrank[NMAX];
-  int parent[2 * NMAX], merge[2 * NMAX];
-  int labels[NMAX];
-  int ct_up[NMAX + 1], ct_own[NMAX], ct_first[NMAX + 1], ct_lab[NMAX + 1];
+template <bool WIDE>
+struct HcScratchT {
+  template <class T, int N> using arr = arr_t<T, N, WIDE>;
+  arr<double, NMAX> members, zdist, height;
+  arr<int, NMAX> nn_chain; arr<int, NMAX + 1> pred;
+  arr<int, NMAX> z1, z2, zrank;
+  arr<int, 2 * NMAX> parent, merge;
+  arr<int, NMAX> labels;
+  arr<int, NMAX + 1> ct_up; arr<int, NMAX> ct_own; arr<int, NMAX + 1> ct_first, ct_lab;
   int cut_k;
 };
-struct GLds {
-  union {
+template <bool WIDE>
+struct GLdsT {
+  template <class T, int N> using arr = arr_t<T, N, WIDE>;
+  union Narrow {
     uint16_t hist[4][65 * 64];      // phase 1: per wave, [bin][lane]
-    HcScratch hc;                   // phase 4
-  } u;
-  int lab_l[NMAX], lab_k[NMAX], gtlab[NMAX], firstof[NMAX], nfirst[8];
-  double rowsum[NMAX];
-  double dmat[GT_DLDS];             // working copy of a condensed matrix while the NN-chain runs on it (regions of up to 102 alleles)
+    HcScratchT<false> hc;           // phase 4
+  };
+  struct Wide {                     // the scratch's slab pointers must outlive phase 1
+    uint16_t hist[4][65 * 64];
+    HcScratchT<true> hc;
+  };
+  std::conditional_t<WIDE, Wide, Narrow> u;
+  arr<int, NMAX> lab_l, lab_k, gtlab, firstof; int nfirst[8];
+  arr<double, NMAX> rowsum;
+  double dmat[WIDE ? 1 : GT_DLDS];  // working copy of a condensed matrix while the NN-chain runs on it (regions of up to 102 alleles)
+  // wide: points the per-allele arrays into `slab` at capacity `cap`; returns the bytes taken
+  __host__ __device__ size_t carve(char* slab, int cap)
+  {
+    SlabCarver c{slab, 0};
+    if constexpr (WIDE) {
+      HcScratchT<true>& S = u.hc;
+      S.members = c.take<double>(cap); S.zdist = c.take<double>(cap); S.height = c.take<double>(cap); rowsum = c.take<double>(cap);
+      S.nn_chain = c.take<int>(cap + 1); S.pred = c.take<int>(cap + 1); S.z1 = c.take<int>(cap + 1); S.z2 = c.take<int>(cap + 1);
+      S.zrank = c.take<int>(cap + 1); S.parent = c.take<int>(2 * cap + 1); S.merge = c.take<int>(2 * cap + 1); S.labels = c.take<int>(cap + 1);
+      S.ct_up = c.take<int>(cap + 1); S.ct_own = c.take<int>(cap + 1); S.ct_first = c.take<int>(cap + 1); S.ct_lab = c.take<int>(cap + 1);
+      lab_l = c.take<int>(cap + 1); lab_k = c.take<int>(cap + 1); gtlab = c.take<int>(cap + 1); firstof = c.take<int>(cap + 1);
+    }
+    return c.off;
+  }
 };
 
 // union-find relabel of the NN-chain output into R's merge matrix (generate_R_dendrogram<false>, fastcluster_R_dm.hpp:68-115), one thread
@@ -661,26 +731,36 @@ __device__ void dendrogram_relabel(int n, S& L)
   }
 }
 
+// WIDE = false: regions of at most a_split (<= NMAX) alleles; WIDE = true: the regions of `wide_idx` above a_split, scratch in this
+// workgroup's slab
+template <bool WIDE>
 __global__ __launch_bounds__(256) void genotype_kernel(
     double max_error_l, double max_error_c, const uint8_t* __restrict__ arena, const uint64_t* __restrict__ seq_off,
     const uint32_t* __restrict__ seq_len, const uint32_t* __restrict__ first_allele, const uint32_t* __restrict__ n_alleles,
     uint32_t n_regions, const uint64_t* __restrict__ pair_off, double* __restrict__ g_dl, double* __restrict__ g_dk,
     double* __restrict__ g_work, double* __restrict__ g_kvec, double* __restrict__ g_vnorm,
+    int a_split, const uint32_t* __restrict__ wide_idx, uint32_t n_wide, char* __restrict__ slab, size_t slab_stride, int cap,
     int32_t* __restrict__ gt, int32_t* __restrict__ gt_l, int32_t* __restrict__ gt_k, double* __restrict__ hsd,
     int32_t* __restrict__ n_gt, int32_t* __restrict__ reps, int32_t* __restrict__ err_out)
 {
-  __shared__ GLds L;
+  __shared__ GLdsT<WIDE> L;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  for (uint32_t r = blockIdx.x; r < n_regions; r += gridDim.x) {
+  if constexpr (WIDE) {
+    if (tid == 0) L.carve(slab + (size_t)blockIdx.x * slab_stride, cap);
+    __syncthreads();
+  }
+  for (uint32_t it = blockIdx.x; it < (WIDE ? n_wide : n_regions); it += gridDim.x) {
+    const uint32_t r = WIDE ? wide_idx[it] : it;
     const int A = (int)n_alleles[r];
     const uint32_t f = first_allele[r];
+    if (WIDE ? A <= a_split : A > a_split) continue;
     __syncthreads();
     if (A == 0) { if (tid == 0) { n_gt[r] = 0; err_out[r] = 0; } continue; }
-    if (A > NMAX) { if (tid == 0) { n_gt[r] = 0; err_out[r] = 10; } continue; }
+    if (WIDE && A > cap) { if (tid == 0) { n_gt[r] = 0; err_out[r] = 10; } continue; }     // the launcher sizes the slab from the largest A: not reached
     double* dl = g_dl + pair_off[r]; double* dk = g_dk + pair_off[r]; double* wk = g_work + pair_off[r];
     double* kv = g_kvec + (size_t)f * 65; double* vn = g_vnorm + f;
     const size_t npairs = (size_t)A * (A - 1) / 2;
-    const bool in_lds = npairs <= (size_t)GT_DLDS;
+    const bool in_lds = !WIDE && npairs <= (size_t)GT_DLDS;
     // ---- 1. 3-mer counts (seq2kcounts, src/anseqs.cpp:149-166): 64 bins + one bin for 3-mers holding a byte outside ACGT (either case)
     {
       uint16_t* H = &L.u.hist[wv][0];
@@ -689,6 +769,16 @@ __global__ __launch_bounds__(256) void genotype_kernel(
         wave_sync();
         const uint8_t* s = arena + seq_off[f + a];
         const int n = (int)seq_len[f + a];
+        // a lane adds at most 16 per tile to one 16-bit cell: the columns are folded into 32-bit registers every 4095 tiles (4095 * 16 < 2^16)
+        // and at the end.  Column sums: lane q walks the 64 columns of bin q starting at its own index (rotated: distinct banks across the lanes)
+        uint32_t c0 = 0, c64 = 0;
+        auto fold = [&]() {
+          wave_sync();
+          for (int j = 0; j < 64; ++j) c0 += H[lane * 64 + ((j + lane) & 63)];
+          c64 += H[64 * 64 + lane];
+          wave_sync();
+        };
+        int tiles = 0;
         // tiles of 1024 bases: a lane takes 16 consecutive positions + the two bases after them from ONE 16-byte load and one 2-byte load
         // (the arena ends in 64 bytes of slack), i.e. 16 three-mers per round trip instead of one
         for (int t0 = 0; t0 + 3 <= n; t0 += 1024) {
@@ -712,13 +802,15 @@ __global__ __launch_bounds__(256) void genotype_kernel(
               }
             }
           }
+          if (++tiles == 4095) {
+            fold();
+            for (int q = lane; q < 65 * 32; q += 64) ((uint32_t*)H)[q] = 0u;
+            wave_sync();
+            tiles = 0;
+          }
         }
-        wave_sync();
-        // column sums: lane q walks the 64 columns of bin q starting at its own index (rotated: distinct banks across the lanes)
+        fold();
         {
-          uint32_t c0 = 0, c64 = 0;
-          for (int j = 0; j < 64; ++j) c0 += H[lane * 64 + ((j + lane) & 63)];
-          c64 = H[64 * 64 + lane];
 #pragma unroll
           for (int off = 32; off > 0; off >>= 1) c64 += __shfl_xor(c64, off);
           double* v = kv + (size_t)a * 65;
@@ -771,7 +863,7 @@ __global__ __launch_bounds__(256) void genotype_kernel(
     // every nearest-neighbour scan and update at LDS latency), rank sort of the merges by all threads, union-find relabel by one thread, tree
     // cut by wave 0
     auto cluster_one = [&](double* D, double cut, int* labels_out) {
-      HcScratch& S = L.u.hc;
+      auto& S = L.u.hc;
       if (wv == 0) nn_chain_average(A, D, S, lane);
       __syncthreads();
       for (int i = tid; i < A - 1; i += blockDim.x) {        // stable sort by height = rank by (distance, position) (fastcluster_R_dm.hpp:74)
@@ -793,11 +885,11 @@ __global__ __launch_bounds__(256) void genotype_kernel(
       for (int a2 = tid; a2 < A; a2 += blockDim.x) labels_out[a2] = S.labels[a2];
       __syncthreads();
     };
-    cluster_one(in_lds ? L.dmat : wk, max_error_l, L.lab_l);
+    cluster_one(in_lds ? &L.dmat[0] : wk, max_error_l, &L.lab_l[0]);
     if (in_lds) { for (size_t q = tid; q < npairs; q += blockDim.x) L.dmat[q] = dk[q]; __syncthreads(); }
-    cluster_one(in_lds ? L.dmat : dk, max_error_c, L.lab_k);
+    cluster_one(in_lds ? &L.dmat[0] : dk, max_error_c, &L.lab_k[0]);
     // ---- 5. genotypes: distinct (gt_l, gt_k) pairs numbered by first appearance (:500-516)
-    const int* lab_l = L.lab_l; const int* lab_k = L.lab_k;
+    const int* lab_l = &L.lab_l[0]; const int* lab_k = &L.lab_k[0];
     for (int a = tid; a < A; a += blockDim.x) {
       gt_l[f + a] = lab_l[a]; gt_k[f + a] = lab_k[a];
       int fo = a;
@@ -805,17 +897,21 @@ __global__ __launch_bounds__(256) void genotype_kernel(
       L.firstof[a] = fo;
     }
     __syncthreads();
-    {   // number the first appearances in index order: per 64-chunk ballot + prefix count, chunk totals through LDS
-      const bool isf = tid < A && L.firstof[tid < A ? tid : 0] == tid;
+    int ng = 0;
+    // number the first appearances in index order, 256 alleles per round: per-wave ballot + prefix count, wave totals through LDS,
+    // running base across the rounds
+    for (int a0 = 0; a0 < A; a0 += blockDim.x) {
+      const int a = a0 + tid;
+      const bool isf = a < A && L.firstof[a < A ? a : 0] == a;
       const unsigned long long fm = __ballot(isf);
       if (lane == 0) L.nfirst[wv] = __builtin_popcountll(fm);
       __syncthreads();
-      int base = 0;
+      int base = ng;
       for (int w = 0; w < wv; ++w) base += L.nfirst[w];
-      if (isf) L.gtlab[tid] = base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(fm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fm, 0u));
+      if (isf) L.gtlab[a] = base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(fm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fm, 0u));
+      ng += L.nfirst[0] + L.nfirst[1] + L.nfirst[2] + L.nfirst[3];
       __syncthreads();
     }
-    const int ng = L.nfirst[0] + L.nfirst[1] + L.nfirst[2] + L.nfirst[3];
     for (int a = tid; a < A; a += blockDim.x) { const int g2 = L.gtlab[L.firstof[a]]; gt[f + a] = g2; reps[f + a] = -1; }
     __syncthreads();
     // medoid of every genotype under the length matrix (:517-524): row sums over the genotype in ascending order, first strict minimum
@@ -842,10 +938,47 @@ __global__ __launch_bounds__(256) void genotype_kernel(
 
 } // namespace
 
+// OTG_CLUSTER_WIDE (read once per process): every region through the wide kernels, whatever its size
+static bool cluster_force_wide()
+{
+  static const bool on = [] { const char* e = getenv("OTG_CLUSTER_WIDE"); return e && *e && strcmp(e, "0") != 0; }();
+  return on;
+}
+
+// Routing shared by both launchers: the narrow kernel takes the regions of at most `n_split` reads / alleles, the wide one the regions the
+// caller lists in `h_wide` (those whose size may exceed NMAX; every region under OTG_CLUSTER_WIDE), dealt to its workgroups from a compact
+// list.  `n_max` bounds every region's size.  Fills `w`: the wide grid (0: no wide launch), the list on the device and the slab after it, one
+// stretch of `stride` bytes per workgroup at capacity `cap` reads / alleles (`slab_size(cap)`: the bytes the kernel's carve() takes).
+struct WideRoute { int n_split; uint32_t grid, n_wide; int cap; size_t stride; const uint32_t* idx; char* slab; };
+static int wide_route(otg_ctx* ctx, int slot, uint32_t n_regions, uint32_t n_max, const uint32_t* h_wide, uint32_t n_wide,
+                      size_t (*slab_size)(int), WideRoute& w)
+{
+  const bool force = cluster_force_wide();
+  std::vector<uint32_t> all;
+  if (force) { all.resize(n_regions); for (uint32_t r = 0; r < n_regions; ++r) all[r] = r; h_wide = all.data(); n_wide = n_regions; }
+  w.n_split = force ? -1 : NMAX;
+  w.n_wide = n_wide;
+  const uint32_t gmax = (uint32_t)ctx->n_cu * 8;
+  w.grid = n_wide < gmax ? n_wide : gmax;
+  w.cap = (int)std::max<uint32_t>(n_max, 1);
+  w.stride = (slab_size(w.cap) + 255) & ~(size_t)255;
+  w.idx = nullptr; w.slab = nullptr;
+  if (!w.grid) return OTG_OK;
+  const size_t idx_bytes = ((size_t)n_wide * 4 + 255) & ~(size_t)255;
+  char* base = (char*)otg_slot(ctx, slot, idx_bytes + (size_t)w.grid * w.stride);
+  if (!base) return OTG_ERR_HIP;
+  w.idx = (const uint32_t*)base; w.slab = base + idx_bytes;
+  HIP_TRY(ctx, hipMemcpyAsync(base, h_wide, (size_t)n_wide * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));       // the host list need not outlive the call
+  return OTG_OK;
+}
+static size_t cluster_slab_size(int cap) { static LdsT<true> probe; return probe.carve(nullptr, cap); }
+static size_t genotype_slab_size(int cap) { static GLdsT<true> probe; return probe.carve(nullptr, cap); }
+
 int otg_launch_cluster(otg_ctx* ctx, const otg_params* P, const double* d_dist, const uint64_t* d_dist_off,
                        const uint32_t* d_read_len, const uint64_t* d_len_off, const uint32_t* d_n_valid,
-                       uint32_t n_regions, int32_t* d_labels, int32_t* d_ic, int32_t* d_fc, double* d_bounds,
-                       int32_t* d_err)
+                       uint32_t n_regions, uint32_t n_max, const uint32_t* h_wide, uint32_t n_wide, int32_t* d_labels, int32_t* d_ic,
+                       int32_t* d_fc, double* d_bounds, int32_t* d_err)
 {
   if (n_regions == 0) return OTG_OK;
   ClusterArgs A;
@@ -879,20 +1012,23 @@ int otg_launch_cluster(otg_ctx* ctx, const otg_params* P, const double* d_dist, 
   // (size unknown here -> callers guarantee SLOT_AUX9 holds at least as many doubles as d_dist)
   double* gwork = (double*)ctx->pool[SLOT_AUX9].p;
   if (!gwork) return otg_fail(ctx, OTG_ERR_ARG, "cluster workspace (SLOT_AUX9) not allocated");
+  WideRoute w;
+  if (int rc = wide_route(ctx, SLOT_P25, n_regions, n_max, h_wide, n_wide, cluster_slab_size, w)) return rc;
   uint32_t grid_dim = n_regions < (uint32_t)ctx->n_cu * 8 ? n_regions : (uint32_t)ctx->n_cu * 8;
-  if (A.exp_fma)
-    hipLaunchKernelGGL((cluster_kernel<true>), dim3(grid_dim), dim3(256), 0, ctx->stream, A, d_dist, d_dist_off, d_read_len, d_len_off,
-                       d_n_valid, n_regions, gwork, d_labels, d_ic, d_fc, d_bounds, d_err);
-  else
-    hipLaunchKernelGGL((cluster_kernel<false>), dim3(grid_dim), dim3(256), 0, ctx->stream, A, d_dist, d_dist_off, d_read_len, d_len_off,
-                       d_n_valid, n_regions, gwork, d_labels, d_ic, d_fc, d_bounds, d_err);
+  auto launch = [&](auto kernel, uint32_t grid, char* slab) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, ctx->stream, A, d_dist, d_dist_off, d_read_len, d_len_off,
+                       d_n_valid, n_regions, gwork, w.n_split, w.idx, w.n_wide, slab, w.stride, w.cap, d_labels, d_ic, d_fc, d_bounds, d_err);
+  };
+  if (w.n_split >= 0) { if (A.exp_fma) launch(cluster_kernel<true, false>, grid_dim, nullptr); else launch(cluster_kernel<false, false>, grid_dim, nullptr); }
+  if (w.grid) { if (A.exp_fma) launch(cluster_kernel<true, true>, w.grid, w.slab); else launch(cluster_kernel<false, true>, w.grid, w.slab); }
   HIP_TRY(ctx, hipGetLastError());
   return OTG_OK;
 }
 
 int otg_launch_genotype(otg_ctx* ctx, const otg_params* P, const uint8_t* d_arena, const uint64_t* d_seq_off,
                         const uint32_t* d_seq_len, const uint32_t* d_first, const uint32_t* d_n, uint32_t n_regions,
-                        const uint64_t* d_pair_off, uint64_t n_pairs_total, uint64_t n_alleles_total,
+                        const uint64_t* d_pair_off, uint64_t n_pairs_total, uint64_t n_alleles_total, uint32_t a_max,
+                        const uint32_t* h_wide, uint32_t n_wide,
                         int32_t* d_gt, int32_t* d_gtl, int32_t* d_gtk, double* d_hsd, int32_t* d_ngt, int32_t* d_reps,
                         int32_t* d_err)
 {
@@ -903,9 +1039,16 @@ int otg_launch_genotype(otg_ctx* ctx, const otg_params* P, const uint8_t* d_aren
   double* g_kv = (double*)otg_slot(ctx, SLOT_P23, (n_alleles_total + 1) * 65 * 8);
   double* g_vn = (double*)otg_slot(ctx, SLOT_P24, (n_alleles_total + 1) * 8);
   if (!g_dl || !g_dk || !g_wk || !g_kv || !g_vn) return OTG_ERR_HIP;
+  WideRoute w;
+  if (int rc = wide_route(ctx, SLOT_P26, n_regions, a_max, h_wide, n_wide, genotype_slab_size, w)) return rc;
   uint32_t grid_dim = n_regions < (uint32_t)ctx->n_cu * 8 ? n_regions : (uint32_t)ctx->n_cu * 8;
-  hipLaunchKernelGGL(genotype_kernel, dim3(grid_dim), dim3(256), 0, ctx->stream, P->gt_max_error, P->gt_max_cosdis, d_arena, d_seq_off,
-                     d_seq_len, d_first, d_n, n_regions, d_pair_off, g_dl, g_dk, g_wk, g_kv, g_vn, d_gt, d_gtl, d_gtk, d_hsd, d_ngt, d_reps, d_err);
+  auto launch = [&](auto kernel, uint32_t grid, char* slab) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, ctx->stream, P->gt_max_error, P->gt_max_cosdis, d_arena, d_seq_off,
+                       d_seq_len, d_first, d_n, n_regions, d_pair_off, g_dl, g_dk, g_wk, g_kv, g_vn, w.n_split, w.idx, w.n_wide, slab, w.stride, w.cap,
+                       d_gt, d_gtl, d_gtk, d_hsd, d_ngt, d_reps, d_err);
+  };
+  if (w.n_split >= 0) launch(genotype_kernel<false>, grid_dim, nullptr);
+  if (w.grid) launch(genotype_kernel<true>, w.grid, w.slab);
   HIP_TRY(ctx, hipGetLastError());
   return OTG_OK;
 }

@@ -333,8 +333,12 @@ int otg_cluster_batch(otg_ctx* ctx, const otg_params* params,
     return otg_fail(ctx, OTG_ERR_ARG, "otg_cluster_batch: NULL argument");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   uint64_t n_dist = 0, n_len = 0;
+  uint32_t n_max = 0;
+  std::vector<uint32_t> wide;          // regions above the LDS scratch of the clustering kernel
   for (uint32_t r = 0; r < n_regions; ++r) {
     uint64_t n = n_valid[r];
+    n_max = std::max<uint32_t>(n_max, n_valid[r]);
+    if (n_valid[r] > OTG_CLUSTER_NMAX) wide.push_back(r);
     n_dist = std::max<uint64_t>(n_dist, dist_off[r] + n * (n ? n - 1 : 0) / 2);
     n_len = std::max<uint64_t>(n_len, len_off[r] + n);
   }
@@ -357,7 +361,7 @@ int otg_cluster_batch(otg_ctx* ctx, const otg_params* params,
   HIP_TRY(ctx, hipMemcpyAsync(d_loff, len_off, (size_t)n_regions * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_nv, n_valid, (size_t)n_regions * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(d_lab, 0xff, (n_len + 1) * sizeof(int32_t), ctx->stream));
-  int rc = otg_launch_cluster(ctx, params, d_dist, d_doff, d_len, d_loff, d_nv, n_regions, d_lab, d_ic, d_fc, d_bounds, d_err);
+  int rc = otg_launch_cluster(ctx, params, d_dist, d_doff, d_len, d_loff, d_nv, n_regions, n_max, wide.data(), (uint32_t)wide.size(), d_lab, d_ic, d_fc, d_bounds, d_err);
   if (rc) return rc;
   std::vector<int32_t> h_err(n_regions);
   HIP_TRY(ctx, hipMemcpyAsync(labels_out, d_lab, n_len * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -370,7 +374,7 @@ int otg_cluster_batch(otg_ctx* ctx, const otg_params* params,
     if (h_err[r])
       return otg_fail(ctx, h_err[r] == 10 ? OTG_ERR_CAPACITY : OTG_ERR_FATAL,
                       "region %u: clustering failed with code %d (1-4: the reference exit(1)s here, src/otterclust.cpp:39-109; "
-                      "5: std::sort emulation depth; 10: more than 256 valid reads)", r, h_err[r]);
+                      "5: std::sort emulation depth; 10: more valid reads than the clustering workspace was sized for)", r, h_err[r]);
   return OTG_OK;
 }
 
@@ -441,9 +445,13 @@ int otg_genotype_cluster_batch(otg_ctx* ctx, const otg_params* params, const uin
     return otg_fail(ctx, OTG_ERR_ARG, "otg_genotype_cluster_batch: NULL argument");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   uint64_t na = 0;
+  uint32_t a_max = 0;
+  std::vector<uint32_t> wide;          // regions above the LDS scratch of the genotype kernel
   std::vector<uint64_t> pair_off(n_regions + 1, 0);
   for (uint32_t r = 0; r < n_regions; ++r) {
     na = std::max<uint64_t>(na, (uint64_t)first_allele[r] + n_alleles[r]);
+    a_max = std::max<uint32_t>(a_max, n_alleles[r]);
+    if (n_alleles[r] > OTG_CLUSTER_NMAX) wide.push_back(r);
     uint64_t A = n_alleles[r];
     pair_off[r + 1] = pair_off[r] + A * (A ? A - 1 : 0) / 2;
   }
@@ -467,7 +475,7 @@ int otg_genotype_cluster_batch(otg_ctx* ctx, const otg_params* params, const uin
   HIP_TRY(ctx, hipMemcpyAsync(d_poff, pair_off.data(), (size_t)(n_regions + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(d_gt, 0xff, (na + 1) * 4 * 4, ctx->stream));
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  int rc = otg_launch_genotype(ctx, params, d_arena, d_off, d_len, d_first, d_n, n_regions, d_poff, pair_off[n_regions], na,
+  int rc = otg_launch_genotype(ctx, params, d_arena, d_off, d_len, d_first, d_n, n_regions, d_poff, pair_off[n_regions], na, a_max, wide.data(), (uint32_t)wide.size(),
                                d_gt, d_gtl, d_gtk, d_hsd, d_ngt, d_reps, d_err);
   if (rc) return rc;
   HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
@@ -481,7 +489,8 @@ int otg_genotype_cluster_batch(otg_ctx* ctx, const otg_params* params, const uin
   HIP_TRY(ctx, hipMemcpyAsync(h_err.data(), d_err, (size_t)n_regions * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   { float ms = 0; HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1)); ctx->last_kernel_ms = ms; }
-  for (uint32_t r = 0; r < n_regions; ++r) if (h_err[r]) return otg_fail(ctx, OTG_ERR_CAPACITY, "region %u: more than 256 alleles", r);
+  for (uint32_t r = 0; r < n_regions; ++r)
+    if (h_err[r]) return otg_fail(ctx, OTG_ERR_CAPACITY, "region %u: %u alleles, more than the clustering workspace was sized for", r, n_alleles[r]);
   return OTG_OK;
 }
 

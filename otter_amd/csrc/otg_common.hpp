@@ -65,6 +65,9 @@ void* otg_slot(otg_ctx* ctx, int slot, size_t bytes);
 
 // words of SLOT_COUNTERS every aligner chain asks for (one size: the slot is never re-allocated between two chains of a batch)
 constexpr size_t OTG_COUNTER_WORDS = 160;
+// cluster.hip: regions of up to this many valid reads (assemble) / alleles (genotype) keep their clustering scratch in LDS; the callers of
+// otg_launch_cluster / otg_launch_genotype list the regions above it, which run on the wide kernels
+constexpr uint32_t OTG_CLUSTER_NMAX = 256;
 enum {
   SLOT_ARENA = 0, SLOT_TASKS, SLOT_SCORES, SLOT_CELLS, SLOT_COUNTERS, SLOT_WF_WS, SLOT_CIG_OFF, SLOT_CIG_LEN,
   SLOT_CIG_ARENA, SLOT_BT_POOL, SLOT_ROWTAB, SLOT_REVOPS, SLOT_TASKSTATE, SLOT_TODO, SLOT_AUX0, SLOT_AUX1,
@@ -242,8 +245,8 @@ int otg_launch_affine_adaptive_todo(otg_ctx* ctx, const uint8_t* d_arena, const 
 // cluster.hip
 int otg_launch_cluster(otg_ctx* ctx, const otg_params* P, const double* d_dist, const uint64_t* d_dist_off,
                        const uint32_t* d_read_len, const uint64_t* d_len_off, const uint32_t* d_n_valid,
-                       uint32_t n_regions, int32_t* d_labels, int32_t* d_ic, int32_t* d_fc, double* d_bounds,
-                       int32_t* d_err);
+                       uint32_t n_regions, uint32_t n_max, const uint32_t* h_wide, uint32_t n_wide, int32_t* d_labels, int32_t* d_ic,
+                       int32_t* d_fc, double* d_bounds, int32_t* d_err);
 
 // poa.hip
 int otg_launch_poa(otg_ctx* ctx, const uint8_t* d_seq_arena, const uint8_t* d_cig_arena,
@@ -254,6 +257,7 @@ int otg_launch_poa(otg_ctx* ctx, const uint8_t* d_seq_arena, const uint8_t* d_ci
 // cluster.hip (genotype_kernel)
 int otg_launch_genotype(otg_ctx* ctx, const otg_params* P, const uint8_t* d_arena, const uint64_t* d_seq_off,
                         const uint32_t* d_seq_len, const uint32_t* d_first, const uint32_t* d_n, uint32_t n_regions,
-                        const uint64_t* d_pair_off, uint64_t n_pairs_total, uint64_t n_alleles_total,
+                        const uint64_t* d_pair_off, uint64_t n_pairs_total, uint64_t n_alleles_total, uint32_t a_max,
+                        const uint32_t* h_wide, uint32_t n_wide,
                         int32_t* d_gt, int32_t* d_gtl, int32_t* d_gtk, double* d_hsd, int32_t* d_ngt, int32_t* d_reps,
                         int32_t* d_err);

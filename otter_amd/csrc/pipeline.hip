@@ -39,6 +39,8 @@ struct Pipeline {
   std::vector<otg_region> h_regions;
   std::vector<uint64_t> h_dist_off, h_re_off, h_cig_off;
   uint64_t n_pair_slots = 0, n_re_slots = 0, cig_bytes = 0;
+  uint32_t cl_nmax = 0;                   // upper bound of the valid reads of a clustered region (its read count)
+  std::vector<uint32_t> cl_wide;          // regions whose read count exceeds the LDS scratch of the clustering kernel
   std::vector<DevBuf> buf;
   otg_run_stats stats;
   uint32_t out_alleles = 0;
@@ -649,6 +651,7 @@ int otg_assemble_submit(otg_ctx* ctx, const otg_params* params, const uint8_t* s
   if (!ctx->pipe) { ctx->pipe = new Pipeline(); ctx->pipe->buf.resize(B_COUNT); }
   Pipeline* pl = ctx->pipe;
   pl->P = *params; pl->n_reads = n_reads; pl->n_regions = n_regions; pl->arena_bytes = arena_bytes; pl->ran = false;
+  pl->cl_nmax = 0; pl->cl_wide.clear();
   pl->h_reads.assign(reads, reads + n_reads);
   pl->h_regions.assign(regions, regions + n_regions);
   std::vector<uint32_t> read_region(n_reads, 0xffffffffu);   // reads outside every region are ignored
@@ -671,6 +674,12 @@ int otg_assemble_submit(otg_ctx* ctx, const otg_params* params, const uint8_t* s
     }
     region_maxlen[r] = ml; maxlen = std::max(maxlen, ml);
     const bool big = (int)g.n_reads > params->max_cov;
+    if (!big) {
+      // one region's V(V-1)/2 distance and V^2 reassignment slots must stay below 2^32 whatever the batch
+      if (n >= 65536) return otg_fail(ctx, OTG_ERR_CAPACITY, "region %u: %llu reads, more than the 65 535 one region can hold (V^2 slots below 2^32)", r, (unsigned long long)n);
+      pl->cl_nmax = std::max<uint32_t>(pl->cl_nmax, g.n_reads);
+      if (g.n_reads > OTG_CLUSTER_NMAX) pl->cl_wide.push_back(r);
+    }
     pl->h_dist_off[r + 1] = pl->h_dist_off[r] + (big ? 0 : n * (n ? n - 1 : 0) / 2);
     pl->h_re_off[r + 1] = pl->h_re_off[r] + (big ? 0 : n * n);
   }
@@ -850,7 +859,7 @@ static int assemble_run_body(otg_ctx* ctx, bool realign_only)
   {
     Timer t(ctx);
     rc = otg_launch_cluster(ctx, &P, d_dist, (const uint64_t*)B(B_DIST_OFF), d_vlen, (const uint64_t*)B(B_FIRST_READ64), d_nvalid, NG,
-                            (int32_t*)B(B_CLLAB), (int32_t*)B(B_IC), (int32_t*)B(B_FC), (double*)B(B_BOUNDS), (int32_t*)B(B_CLERR));
+                            pl->cl_nmax, pl->cl_wide.data(), (uint32_t)pl->cl_wide.size(), (int32_t*)B(B_CLLAB), (int32_t*)B(B_IC), (int32_t*)B(B_FC), (double*)B(B_BOUNDS), (int32_t*)B(B_CLERR));
     if (rc) return rc;
     hipLaunchKernelGGL(K_scatter_labels, dim3(gr_reads), dim3(TB), 0, st, d_rr, d_regions, d_vpos, (const int32_t*)B(B_CLLAB), NR, d_labels);
     pl->stats.ms_cluster = t.ms();

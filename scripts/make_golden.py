@@ -13,6 +13,48 @@ import oracle_lib as O  # noqa: E402
 from helpers import cluster_cases, random_poa_specs, build_poa_batch  # noqa: E402
 
 assert O.ref() is not None, "oracle/_ref not built (needs /root/reference)"
+
+
+def large_n_inputs():
+    """G2b inputs: tie-heavy condensed matrices at n = 257 and 600, quantised (distance = code / 10**q) so the fixture stays small."""
+    from helpers import tie_heavy_matrix
+    rl = np.random.default_rng(20261016)
+    out_ = []
+    for n, q in ((257, 3), (600, 2)):
+        codes = np.round(tie_heavy_matrix(rl, n) * 10 ** q).astype(np.uint16)
+        out_.append((n, q, codes))
+    return out_
+
+
+def large_n_distances(codes, q):
+    return codes.astype(np.float64) / 10 ** q
+
+
+def write_large_n():
+    """G2b: hclust_fast(AVERAGE) / cutree_k / cutree_cdist / get_medoid / KDE::f of the reference above 256 observations
+    (tests/golden/hclust_large_ref.npz)."""
+    rec = {}
+    for i, (n, q, codes) in enumerate(large_n_inputs()):
+        d = large_n_distances(codes, q)
+        merge, height = O.hclust_average(n, d, which="ref")
+        cd = float(np.median(d))
+        rec["n%d" % i] = np.array([n]); rec["q%d" % i] = np.array([q]); rec["codes%d" % i] = codes
+        rec["merge%d" % i] = merge; rec["height%d" % i] = height
+        for k in (2, 3, 4):
+            rec["cut_k%d_%d" % (k, i)] = O.cutree_k(n, merge, k, which="ref").astype(np.int16)
+        rec["cd%d" % i] = np.array([cd])
+        rec["cut_c_%d" % i] = O.cutree_cdist(n, merge, height, cd, which="ref").astype(np.int16)
+        rec["medoid%d" % i] = np.array([O.medoid(n, d, np.arange(0, n, 2, dtype=np.uint32), which="ref")])
+        xs = np.array([0.0, 0.05, 0.1275, 0.3, 0.6])
+        rec["xs%d" % i] = xs
+        rec["f%d" % i] = np.array([O.kde_f(0.01, d, float(x), which="ref") for x in xs])
+    rec["n_cases"] = np.array([len(large_n_inputs())])
+    np.savez_compressed(os.path.join(ROOT, "tests", "golden", "hclust_large_ref.npz"), **rec)
+
+
+if "--large-n" in sys.argv:         # only the G2b fixture
+    write_large_n()
+    sys.exit(0)
 rng = np.random.default_rng(20241008)
 out = os.path.join(ROOT, "tests", "golden")
 
@@ -104,3 +146,5 @@ for i, kw in enumerate(OPTS):
     rec["reads%d" % i] = b["reads"]; rec["arena%d" % i] = np.ascontiguousarray(b["arena"]); rec["n_reads%d" % i] = b["regions"]["n_reads"]
 np.savez_compressed(os.path.join(out, "ingest_ref.npz"), **rec)
 print("ingest_small.bam", os.path.getsize(os.path.join(out, "ingest_small.bam")), "bytes;", {k: len(v) for k, v in rec.items() if k.startswith("reads")})
+
+write_large_n()

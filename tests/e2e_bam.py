@@ -50,7 +50,8 @@ def _sam_cigar(ops):
 
 
 def make_dataset(tmpdir, n_regions=8, seed=61, err=0.01, depth=12):
-    """Writes ref.fa, reads.sam (sorted), regions (list of (chr, start, end)); returns paths + regions."""
+    """Writes ref.fa, reads.sam (sorted), regions (list of (chr, start, end)); returns paths + regions.
+    depth: records written per region, one number for all regions or a list with one per region."""
     rng = np.random.default_rng(seed)
     chrom = "chrT"
     ref = bytearray(_rand(rng, 3000))
@@ -68,7 +69,7 @@ def make_dataset(tmpdir, n_regions=8, seed=61, err=0.01, depth=12):
     pairs, meta = [], []
     for r, ((c, start, end), (motif, ncopy)) in enumerate(zip(regions, tracts)):
         alleles = [ncopy + int(rng.integers(-6, 7)), ncopy + int(rng.integers(-25, 26))]
-        for i in range(depth):
+        for i in range(depth[r] if isinstance(depth, (list, tuple)) else depth):
             a = alleles[i % 2]
             fl, fr = int(rng.integers(300, 1200)), int(rng.integers(300, 1200))
             w0, w1 = start - fl, end + fr

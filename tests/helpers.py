@@ -171,3 +171,66 @@ def random_poa_specs(rng, oracle, n_graphs, lmin, lmax, err=0.07, partial=True):
         c, t = consensus_weights(n + 1)
         specs.append((rep, [(reads[i], cigs[i], flags[i][0], flags[i][1]) for i in range(n)], c, t))
     return specs
+
+
+def deep_batch(rng, specs, err="hifi", haps=False):
+    """Regions of chosen depth for the size thresholds of the clustering stage.  specs: list of (n_spanning, n_partial, allele_lengths):
+    `n_spanning` reads span the locus (the valid reads under ignore_haps), `n_partial` more span one side only (left for reassignment);
+    the reads are drawn evenly from one tandem-repeat allele per entry of `allele_lengths` (copy-number variants of one motif).
+    haps=True tags every read with phase set 1 and haplotype = its allele + 1.  Returns a synth-style batch dict(arena, reads, regions)."""
+    rate, split = synth.ERR[err]
+    chunks, reads, regions = [], [], []
+    pos = 0
+    for n_span, n_part, lens in specs:
+        m = int(rng.integers(2, 7))
+        motif = rng.integers(0, 4, m, dtype=np.uint8)
+        while np.all(motif == motif[0]):
+            motif = rng.integers(0, 4, m, dtype=np.uint8)
+        lead = rng.integers(0, 4, 1, dtype=np.uint8)
+        alleles = [np.concatenate([lead, np.tile(motif, max(1, (L - 1) // m))]) for L in lens]
+        first = len(reads)
+        which = rng.permutation(np.arange(n_span + n_part) % len(alleles))
+        for i in range(n_span + n_part):
+            tmpl = alleles[int(which[i])]
+            spl = spr = 1
+            if i >= n_span:                                   # one-sided read: a prefix or a suffix of the allele
+                cut = int(rng.integers(max(1, int(0.3 * tmpl.size)), max(2, int(0.9 * tmpl.size))))
+                if rng.random() < 0.5:
+                    tmpl, spr = tmpl[:cut], 0
+                else:
+                    tmpl, spl = tmpl[tmpl.size - cut:], 0
+            seq = synth._mutate(rng, tmpl, rate, split)
+            if seq.size == 0:
+                seq = np.zeros(1, dtype=np.uint8)
+            b = _ACGT[seq]
+            chunks.append(b)
+            ps, hp = (1, int(which[i]) + 1) if haps else (-1, -1)
+            reads.append((pos, b.size, spl, spr, 0, ps, hp, 0, b.size))
+            pos += b.size
+        regions.append((first, n_span + n_part, 0, 0, 0, 0))
+    arena = np.concatenate(chunks + [np.zeros(64, dtype=np.uint8)])
+    return {"arena": arena, "reads": np.array(reads, dtype=abi.read_dt), "regions": np.array(regions, dtype=abi.region_dt)}
+
+
+def tie_heavy_matrix(rng, n, quantum=None):
+    """A condensed distance matrix of k <= 4 groups plus noise, optionally rounded to `quantum` decimals (many equal minima)."""
+    k = int(rng.integers(1, 5))
+    g = rng.integers(0, k, n)
+    cen = np.sort(rng.uniform(0.0, 0.6, k))
+    full = np.abs(cen[g][:, None] - cen[g][None, :]) + 0.05 + rng.random((n, n)) * 0.04
+    if quantum is not None:
+        full = np.round(full, quantum)
+    return np.ascontiguousarray(full[np.triu_indices(n, 1)])
+
+
+def genotype_region_alleles(rng, n_alleles, len_range=(200, 600), pop_alleles=4, err=0.003):
+    """One `otter genotype` region: n_alleles sample alleles drawn from `pop_alleles` copy-number variants of one motif, with
+    consensus-level errors (a few carry an N run).  Returns a list of byte strings."""
+    pop = [tr_seq(rng, int(rng.integers(len_range[0], len_range[1] + 1))) for _ in range(pop_alleles)]
+    out = []
+    for a in range(n_alleles):
+        s = mutate(rng, pop[int(rng.integers(0, pop_alleles))], err)
+        if a % 37 == 11:
+            s = s[:10] + b"NN" + s[10:]
+        out.append(s or b"A")
+    return out

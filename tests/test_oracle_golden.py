@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 from otter_amd import abi
-from helpers import pair_tasks, cluster_cases, random_poa_specs, build_poa_batch
+from helpers import pair_tasks, cluster_cases, random_poa_specs, build_poa_batch, tie_heavy_matrix
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -24,6 +24,23 @@ def test_hclust_cutree_medoid_golden(oracle):
         assert np.array_equal(oracle.cutree_k(n, merge, 3), g["cut_k3_%d" % i])
         assert np.array_equal(oracle.cutree_cdist(n, merge, height, float(g["cd%d" % i][0])), g["cut_c_%d" % i])
         assert oracle.medoid(n, d, np.arange(0, n, 2, dtype=np.uint32)) == int(g["medoid%d" % i][0])
+
+
+def test_hclust_large_n_golden(oracle):
+    """n = 257 and 600 (above the GPU kernels' on-chip scratch), tie-heavy quantised distances: the reference's merges, heights, cuts,
+    medoid and KDE densities (scripts/make_golden.py, G2b)."""
+    g = np.load(os.path.join(GOLD, "hclust_large_ref.npz"))
+    for i in range(int(g["n_cases"][0])):
+        n, q = int(g["n%d" % i][0]), int(g["q%d" % i][0])
+        d = g["codes%d" % i].astype(np.float64) / 10 ** q
+        merge, height = oracle.hclust_average(n, d)
+        assert np.array_equal(merge, g["merge%d" % i]) and np.array_equal(height, g["height%d" % i])
+        for k in (2, 3, 4):
+            assert np.array_equal(oracle.cutree_k(n, merge, k), g["cut_k%d_%d" % (k, i)])
+        assert np.array_equal(oracle.cutree_cdist(n, merge, height, float(g["cd%d" % i][0])), g["cut_c_%d" % i])
+        assert oracle.medoid(n, d, np.arange(0, n, 2, dtype=np.uint32)) == int(g["medoid%d" % i][0])
+        f = np.array([oracle.kde_f(0.01, d, float(x)) for x in g["xs%d" % i]])
+        assert np.allclose(f, g["f%d" % i], rtol=1e-15, atol=0)      # libm exp() may differ in the last ulp between hosts
 
 
 def test_kde_golden(oracle):
@@ -81,6 +98,29 @@ def test_live_against_reference_build(oracle):
     specs = random_poa_specs(rng, oracle, 60, 3, 200, err=0.1)
     sarena, carena, members, graphs = build_poa_batch(specs)
     assert oracle.poa_consensus_batch(sarena, carena, members, graphs) == oracle.poa_consensus_batch(sarena, carena, members, graphs, which="ref")
+
+
+@pytest.mark.parametrize("n", [64, 65, 128, 200, 256, 257, 600])
+def test_live_large_n_against_reference_build(oracle, n):
+    """The oracle's clustering pieces against the reference's own build at the GPU kernels' size thresholds (LDS working copy up to 64,
+    on-chip scratch up to 256), on tie-heavy matrices quantised to 2 and 3 decimals and unquantised."""
+    if oracle.ref() is None:
+        pytest.skip("oracle/_ref not built (reference sources not mounted)")
+    rng = np.random.default_rng(1000 + n)
+    for quantum in (2, 3, None):
+        d = tie_heavy_matrix(rng, n, quantum)
+        m1, h1 = oracle.hclust_average(n, d)
+        m2, h2 = oracle.hclust_average(n, d, which="ref")
+        assert np.array_equal(m1, m2) and np.array_equal(h1, h2)
+        for k in (1, 2, 3, 4, n):
+            assert np.array_equal(oracle.cutree_k(n, m1, k), oracle.cutree_k(n, m2, k, which="ref"))
+        for cd in (float(np.median(d)), 0.0525, 0.2):
+            assert np.array_equal(oracle.cutree_cdist(n, m1, h1, cd), oracle.cutree_cdist(n, m2, h2, cd, which="ref"))
+        for ind in (np.arange(0, n, 2), np.arange(n), rng.choice(n, max(2, n // 3), replace=False)):
+            ind = np.sort(ind).astype(np.uint32)
+            assert oracle.medoid(n, d, ind) == oracle.medoid(n, d, ind, which="ref")
+        for h, x in ((0.01, 0.1275), (0.015, 0.05), (0.01, 0.3)):
+            assert oracle.kde_f(h, d, x) == oracle.kde_f(h, d, x, which="ref")
 
 
 def test_pipeline_invariants(oracle):
