@@ -629,6 +629,67 @@ typedef struct otg_vcf2mat_job {
 } otg_vcf2mat_job;
 int otg_vcf2mat_files(const otg_vcf2mat_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
 
+/* ---------------------------------------------------------------------------------------------
+ * Cohort: sample BAMs to one joint VCF, the alleles staying in HBM between `otter assemble` and `otter genotype`.  The reference's workflow
+ * writes the allele records of every sample as SAM text (src/assemble.cpp:143-149), merges the per-sample BAMs outside otter and reads them
+ * back (parse_analleles, src/anseqs.cpp:462-524; genotype_process, src/genotype.cpp:80-157).  Here, for one batch of regions:
+ *   otg_cohort_begin     opens a staging area for n_regions regions and n_samples samples on ctx;
+ *   otg_cohort_stage     after otg_assemble_run on src_ctx (ctx itself or another context on the same device) over the SAME n_regions regions:
+ *                        copies that run's allele records and bytes device to device as sample `sample` (each sample once, any order);
+ *                        src_ctx may run its next batch as soon as the call returns;
+ *   otg_cohort_regroup   all samples staged: uploads the reference alleles (region r: ref_arena + ref_off[r], ref_len[r] bytes — what
+ *                        genotype_process fetches, bases [start - offset_l, end + offset_r - 1], src/genotype.cpp:93-101) and regroups on the
+ *                        device into the inputs of anallele_cluster: region-major; inside a region sample-major in sample order, the alleles of
+ *                        a sample in label order, the reference allele last with sample index n_samples.  A region in which no sample has an
+ *                        allele has no alleles at all (src/genotype.cpp:90); a zero-length allele becomes "N" (src/anseqs.cpp:505-507);
+ *   otg_cohort_genotype  anallele_cluster on the regrouped buffers (the kernels of otg_genotype_cluster_batch; gt_max_error, gt_max_cosdis);
+ *   otg_cohort_collect   D2H; every output is nullable.  first_allele_out has n_regions + 1 entries; alleles_out are the records in regrouped
+ *                        order as otg_ingest_alleles would deliver them (.seq_off into seq_out, .region = batch-local region, .label = sample
+ *                        index); sample_out / seq_off_out / seq_len_out are the arrays the kernels read; gt .. reps as
+ *                        otg_genotype_cluster_batch returns them (they need otg_cohort_genotype, the others only otg_cohort_regroup).
+ *                        Sizes: otg_cohort_result_sizes; OTG_ERR_CAPACITY when a capacity is smaller;
+ *   otg_cohort_end       closes the batch; the staging buffers stay with the context for the next one.
+ * ------------------------------------------------------------------------------------------- */
+int otg_cohort_begin(otg_ctx* ctx, uint32_t n_regions, uint32_t n_samples);
+int otg_cohort_stage(otg_ctx* ctx, otg_ctx* src_ctx, uint32_t sample);
+int otg_cohort_regroup(otg_ctx* ctx, const uint8_t* ref_arena, uint64_t ref_bytes, const uint64_t* ref_off, const uint32_t* ref_len);
+int otg_cohort_genotype(otg_ctx* ctx, const otg_params* params);
+int otg_cohort_result_sizes(otg_ctx* ctx, uint32_t* n_alleles, uint64_t* seq_bytes);
+int otg_cohort_collect(otg_ctx* ctx, uint32_t* first_allele_out, otg_allele* alleles_out, uint32_t allele_capacity, int32_t* sample_out,
+                       uint64_t* seq_off_out, uint32_t* seq_len_out, uint8_t* seq_out, uint64_t seq_capacity,
+                       int32_t* gt_out, int32_t* gt_l_out, int32_t* gt_k_out, double* hsd_out, int32_t* n_gt_out, int32_t* reps_out);
+int otg_cohort_end(otg_ctx* ctx);
+
+/* Sample BAMs + BED + reference FASTA to one joint VCF in one call: per batch of regions and per sample, read ingest on host threads ->
+ * otg_assemble_submit / run -> otg_cohort_stage; then otg_cohort_regroup / genotype / collect and the VCF text (otg_emit_vcf_header with the
+ * contigs of the FIRST BAM and one column per sample name, otg_emit_vcf_lines), in BED order.  The ingest of a sample overlaps the device run of
+ * the previous one (two contexts per device, as in otg_assemble_files); BED sharding over devices[] and the batch plan as otg_assemble_files.
+ * The text equals what otg_genotype_files prints for the merged allele BAM of the per-sample otg_assemble_files runs with read_group =
+ * sample_names[s].  OTG_ERR_ARG, with the offending item in otg_last_error(NULL): no samples, an empty or repeated sample name, no FASTA, a BAM
+ * whose targets differ from the first BAM's, two BED records with the same chr:start-end (the file round trip would hand each of them the alleles
+ * of both; this path identifies regions by index).
+ * allele_write (nullable): receives per sample the SAM text otg_assemble_files would have written for it (header first, records in BED order);
+ * when NULL no SAM text is formatted and the allele records are never copied to the host.
+ * stats: n_reads = reads ingested over all samples, n_alleles = staged alleles (reference alleles excluded), n_regions_ok = regions with a VCF
+ * line, ms_ingest / ms_hot_path / ms_emit = busy times summed over their threads. */
+typedef int (*otg_cohort_allele_write_fn)(void* user, uint32_t sample, const char* data, uint64_t len);
+typedef struct otg_cohort_job {
+  uint32_t    n_samples;
+  uint32_t    batch_regions;     /* regions per batch; 0 = the plan of otg_assemble_files                                   */
+  const char* const* bam_paths;  /* n_samples reads BAMs (index <BAM>.bai)                                                 */
+  const char* const* sample_names; /* the -R of each assemble = the VCF column names: unique, non-empty                    */
+  const char* bed_path;          /* -b                                                                                     */
+  const char* fasta_path;        /* -r: required (local re-alignment flanks AND the reference alleles)                     */
+  otg_params  params;            /* assemble heuristics and gt_max_error / gt_max_cosdis (realign is set by the library)   */
+  otg_ingest_opts ingest;        /* one --offset pair for the whole cohort (one `OF:` header line carries it); .threads = host ingest threads */
+  int32_t     n_devices;         /* 0: device 0 only                                                                       */
+  int32_t     reserved;
+  const int32_t* devices;        /* HIP device ordinals, one contiguous BED shard each                                     */
+  otg_cohort_allele_write_fn allele_write;   /* nullable                                                                   */
+  void*       allele_user;
+} otg_cohort_job;
+int otg_cohort_files(const otg_cohort_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
+
 /* The dispatcher keeps its per-device contexts (and their HBM workspaces) for the next job of the process; this frees them. */
 void otg_assemble_files_release(void);
 

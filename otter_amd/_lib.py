@@ -22,6 +22,8 @@ EXPORTS = [
     "otg_edit_align_batch", "otg_edit_align_last_ms", "otg_ingest_compare_alleles", "otg_compare_emit", "otg_compare_files",
     "otg_kmer_usage_batch", "otg_kmer_usage_device_results", "otg_kmer_usage_last_ms", "otg_vcf_open", "otg_vcf_close", "otg_vcf_read_alleles",
     "otg_vcf2mat_emit", "otg_vcf2mat_files",
+    "otg_cohort_begin", "otg_cohort_stage", "otg_cohort_regroup", "otg_cohort_genotype", "otg_cohort_result_sizes", "otg_cohort_collect",
+    "otg_cohort_end", "otg_cohort_files",
     "otg_comm_unique_id", "otg_comm_create", "otg_comm_destroy", "otg_gather_sizes", "otg_gather_records",
 ]
 
@@ -320,6 +322,53 @@ class Context:
         self.assemble_submit(params, batch, region_range)
         self.assemble_run()
         return self.assemble_collect()
+
+
+    # ------------------------------------------------------------------ cohort (assemble -> genotype without leaving the device)
+    def cohort_begin(self, n_regions, n_samples):
+        """otg_cohort_begin: opens the staging area of one batch of n_regions regions for n_samples samples."""
+        self._check(self._L.otg_cohort_begin(self._h, C.c_uint32(n_regions), C.c_uint32(n_samples)), "otg_cohort_begin")
+        self._cohort_regions = int(n_regions)
+
+    def cohort_stage(self, sample, src=None):
+        """otg_cohort_stage: the results of the latest assemble_run of `src` (default: this context) become sample `sample` of the batch."""
+        self._check(self._L.otg_cohort_stage(self._h, (src or self)._h, C.c_uint32(sample)), "otg_cohort_stage")
+
+    def cohort_regroup(self, ref_arena, ref_off, ref_len):
+        """otg_cohort_regroup: uploads the reference allele of every region (bytes ref_arena[ref_off[r] : ref_off[r] + ref_len[r]]) and regroups
+        the staged alleles on the device into the inputs of anallele_cluster."""
+        ref_arena = np.ascontiguousarray(ref_arena, dtype=np.uint8)
+        ref_off = np.ascontiguousarray(ref_off, dtype=np.uint64)
+        ref_len = np.ascontiguousarray(ref_len, dtype=np.uint32)
+        self._check(self._L.otg_cohort_regroup(self._h, abi.ptr(ref_arena), C.c_uint64(ref_arena.size), abi.ptr(ref_off), abi.ptr(ref_len)), "otg_cohort_regroup")
+
+    def cohort_genotype(self, params, ref_arena=None, ref_off=None, ref_len=None):
+        """otg_cohort_genotype (after cohort_regroup when the reference alleles are given): anallele_cluster on the regrouped buffers."""
+        if ref_off is not None:
+            self.cohort_regroup(ref_arena, ref_off, ref_len)
+        self._check(self._L.otg_cohort_genotype(self._h, C.byref(params)), "otg_cohort_genotype")
+
+    def cohort_collect(self, clustered=True):
+        """otg_cohort_collect -> {"first_allele" [n_regions + 1], "n_alleles", "alleles" (allele_dt, .label = sample index), "sample", "seq_off",
+        "seq_len", "arena" (+ 64 slack bytes)} and, with clustered=True, "gt", "gt_l", "gt_k", "hsd", "n_gt", "reps"."""
+        na, sb = C.c_uint32(0), C.c_uint64(0)
+        self._check(self._L.otg_cohort_result_sizes(self._h, C.byref(na), C.byref(sb)), "otg_cohort_result_sizes")
+        n, B = na.value, self._cohort_regions
+        res = {"first_allele": np.zeros(B + 1, dtype=np.uint32), "alleles": np.zeros(n, dtype=abi.allele_dt), "sample": np.zeros(n, dtype=np.int32),
+               "seq_off": np.zeros(n, dtype=np.uint64), "seq_len": np.zeros(n, dtype=np.uint32), "arena": np.zeros(sb.value + 64, dtype=np.uint8)}
+        if clustered:
+            res.update({"gt": np.zeros(n, dtype=np.int32), "gt_l": np.zeros(n, dtype=np.int32), "gt_k": np.zeros(n, dtype=np.int32), "hsd": np.zeros(n),
+                        "n_gt": np.zeros(B, dtype=np.int32), "reps": np.zeros(n, dtype=np.int32)})
+        g = lambda k: abi.ptr(res[k]) if k in res else None
+        rc = self._L.otg_cohort_collect(self._h, g("first_allele"), g("alleles"), C.c_uint32(n), g("sample"), g("seq_off"), g("seq_len"), g("arena"),
+                                        C.c_uint64(sb.value), g("gt"), g("gt_l"), g("gt_k"), g("hsd"), g("n_gt"), g("reps"))
+        self._check(rc, "otg_cohort_collect")
+        res["n_alleles"] = np.diff(res["first_allele"].astype(np.int64)).astype(np.uint32)
+        res["seq_bytes"] = int(sb.value)
+        return res
+
+    def cohort_end(self):
+        self._check(self._L.otg_cohort_end(self._h), "otg_cohort_end")
 
 
 class Comm:
@@ -751,6 +800,47 @@ def genotype_files(bam, bed, fasta=None, params=None, threads=1, device=0, batch
     if rc != 0:
         raise OtterGpuError("otg_genotype_files failed (%d): %s" % (rc, (L.otg_last_error(None) or b"").decode()))
     return b"".join(chunks), {k: getattr(st, k) for k, _ in abi.JobStats._fields_}
+
+
+def cohort_files(bams, names, bed, fasta, params=None, batch_regions=0, devices=None, offset_l=1, offset_r=0, mapq=0, nonprimary=False,
+                 omit_nonspanning=False, read_quality=0.0, threads=1, alleles=False):
+    """otg_cohort_files: sample BAMs + BED + reference FASTA to one joint VCF, the alleles staying on the device between `otter assemble` and
+    `otter genotype`.  Returns (VCF bytes, stats dict), and with alleles=True also the list of per-sample SAM texts (what assemble_files returns
+    for each sample with read_group = its name)."""
+    L = load()
+    job = abi.CohortJob()
+    n = len(bams)
+    pb = (C.c_char_p * max(1, n))(*[b.encode() for b in bams])
+    pn = (C.c_char_p * max(1, n))(*[x.encode() for x in names])
+    job.n_samples = n; job.batch_regions = batch_regions
+    job.bam_paths = pb; job.sample_names = pn
+    job.bed_path = bed.encode(); job.fasta_path = fasta.encode() if fasta else None
+    job.params = params if params is not None else abi.default_params()
+    job.ingest = abi.IngestOpts(offset_l, offset_r, mapq, int(nonprimary), int(omit_nonspanning), threads, read_quality)
+    devs = (C.c_int32 * len(devices))(*devices) if devices else None
+    job.n_devices = len(devices) if devices else 0
+    job.devices = devs
+    chunks, sams = [], [[] for _ in range(n)]
+
+    def sink(_user, data, ln):
+        chunks.append(C.string_at(data, ln))
+        return 0
+
+    def asink(_user, sample, data, ln):
+        sams[sample].append(C.string_at(data, ln))
+        return 0
+    cb, acb = abi.WRITE_FN(sink), abi.ALLELE_WRITE_FN(asink)
+    if alleles:
+        job.allele_write = C.cast(acb, C.c_void_p)
+    st = abi.JobStats()
+    L.otg_cohort_files.argtypes = [C.POINTER(abi.CohortJob), abi.WRITE_FN, C.c_void_p, C.POINTER(abi.JobStats)]
+    rc = L.otg_cohort_files(C.byref(job), cb, None, C.byref(st))
+    if rc != 0:
+        raise OtterGpuError("otg_cohort_files failed (%d): %s" % (rc, (L.otg_last_error(None) or b"").decode()))
+    stats = {k: getattr(st, k) for k, _ in abi.JobStats._fields_}
+    if alleles:
+        return b"".join(chunks), stats, [b"".join(x) for x in sams]
+    return b"".join(chunks), stats
 
 
 def assemble_files_release():

@@ -200,3 +200,12 @@ class JobStats(C.Structure):
 
 
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_char), C.c_uint64)
+ALLELE_WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_char), C.c_uint64)
+
+
+class CohortJob(C.Structure):
+    """otg_cohort_job (include/otter_gpu.h)."""
+    _fields_ = [("n_samples", C.c_uint32), ("batch_regions", C.c_uint32), ("bam_paths", C.POINTER(C.c_char_p)), ("sample_names", C.POINTER(C.c_char_p)),
+                ("bed_path", C.c_char_p), ("fasta_path", C.c_char_p), ("params", otg_params), ("ingest", IngestOpts),
+                ("n_devices", C.c_int32), ("reserved", C.c_int32), ("devices", C.POINTER(C.c_int32)),
+                ("allele_write", C.c_void_p), ("allele_user", C.c_void_p)]

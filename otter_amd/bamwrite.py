@@ -276,3 +276,101 @@ def make_genotype_fixture(dirname, n_regions, n_samples=50, len_range=(1000, 500
         for i in range(0, len(rb), 60):
             f.write(rb[i:i + 60] + "\n")
     return {"bam": bam, "bed": bed, "fasta": fa, "regions": regions, "n_records": len(recs), "n_samples": n_samples}
+
+
+def _noisy(rng, seq, rate):
+    """Sequencing errors on `seq` (uint8 ACGT codes as bytes) with the per-op code array that describes them (0 = M, 1 = I, 2 = D): every
+    reference base contributes its inserted bases (0-3) and then itself or nothing."""
+    ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
+    n = len(seq)
+    if n == 0:
+        return seq.copy(), np.zeros(0, dtype=np.uint8)
+    kind = rng.random(n)
+    sub = kind < rate * 0.45
+    ins = (kind >= rate * 0.45) & (kind < rate * 0.72)
+    keep = ~((kind >= rate * 0.72) & (kind < rate))
+    s2 = seq.copy()
+    s2[sub] = ACGT[rng.integers(0, 4, int(sub.sum()))]
+    ilen = np.zeros(n, dtype=np.int64)
+    ilen[ins] = rng.integers(1, 4, int(ins.sum()))
+    end = np.cumsum(ilen + keep)
+    out = ACGT[rng.integers(0, 4, int(end[-1]))]
+    out[(end - 1)[keep]] = s2[keep]
+    oend = np.cumsum(ilen + 1)
+    codes = np.ones(int(oend[-1]), dtype=np.uint8)
+    codes[oend - 1] = np.where(keep, 0, 2)
+    return out, codes
+
+
+def _rle(codes):
+    """(lengths, BAM op codes) of a per-op code array."""
+    if codes.size == 0:
+        return np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint8)
+    starts = np.concatenate(([0], np.flatnonzero(np.diff(codes)) + 1))
+    return np.diff(np.concatenate((starts, [codes.size]))).astype(np.uint32), codes[starts]
+
+
+def make_cohort_fixture(dirname, n_regions, n_samples, depth=12, len_range=(300, 900), seed=23, rate=0.01, flank=1200, pool=3, frac_empty=0.05):
+    """A cohort for otter_amd.cohort_files: ONE reference (ref.fa) and BED (regions.bed, sorted by position, no two regions with the same
+    start) and per sample a reads BAM (<name>.bam + .bai).  Every tandem-repeat locus has a small pool of `pool` repeat counts (the reference
+    allele's and copy-number variants of it); each sample's two alleles are drawn from that pool, so samples share alleles and the genotype
+    clusters of a region have more than one member.  About frac_empty of the (sample, locus) pairs have no reads at all.
+    Returns dict(bams, names, bed, fasta, regions)."""
+    import os
+    rng = np.random.default_rng(seed)
+    ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
+    names = ["s%02d" % i for i in range(n_samples)]
+    ref_parts, regions, loci = [], [], []
+    pos = 0
+    for r in range(n_regions):
+        motif = ACGT[rng.integers(0, 4, int(rng.integers(2, 7)))]
+        L = int(rng.integers(len_range[0], len_range[1]))
+        tr = np.tile(motif, L // len(motif) + 1)[:L]
+        fl, fr = ACGT[rng.integers(0, 4, flank)], ACGT[rng.integers(0, 4, flank)]
+        start = pos + flank
+        ref_parts += [fl, tr, fr]
+        regions.append(("chrC", start, start + L))
+        max_del = max(1, min(40, (L // 2) // len(motif)))
+        deltas = [0]
+        while len(deltas) < pool:
+            d = int(rng.integers(-max_del, 41)) * len(motif)
+            if d not in deltas:
+                deltas.append(d)
+        loci.append((motif, tr, fl, fr, start, L, deltas))
+        pos += flank + L + flank
+    ref = np.concatenate(ref_parts)
+    bams = []
+    for s in range(n_samples):
+        recs = []
+        for r, (motif, tr, fl, fr, start, L, deltas) in enumerate(loci):
+            pick = [deltas[int(i)] for i in rng.integers(0, len(deltas), 2)]
+            if rng.random() < frac_empty:
+                continue
+            for d in range(depth):
+                dl = pick[d % 2]
+                lf, rf = int(rng.integers(200, 900)), int(rng.integers(200, 900))
+                body = tr if dl >= 0 else tr[:L + dl]
+                left, c_l = _noisy(rng, fl[flank - lf:], rate)
+                mid, c_m = _noisy(rng, body, rate)
+                right, c_r = _noisy(rng, fr[:rf], rate)
+                extra, c_x = np.zeros(0, np.uint8), np.zeros(0, np.uint8)
+                if dl > 0:
+                    extra = np.tile(motif, dl // len(motif))
+                    c_x = np.full(len(extra), 1, dtype=np.uint8)
+                elif dl < 0:
+                    c_x = np.full(-dl, 2, dtype=np.uint8)
+                recs.append((0, start - lf, "%s_r%d_%d" % (names[s], r, d), 0, 60, _rle(np.concatenate([c_l, c_m, c_x, c_r])), np.concatenate([left, mid, extra, right]), b""))
+        recs.sort(key=lambda x: x[1])
+        path = os.path.join(dirname, names[s] + ".bam")
+        write_bam(path, [("chrC", int(ref.size))], recs)
+        bams.append(path)
+    bed, fa = os.path.join(dirname, "regions.bed"), os.path.join(dirname, "ref.fa")
+    with open(bed, "w") as f:
+        for c, s_, e in regions:
+            f.write("%s\t%d\t%d\n" % (c, s_, e))
+    with open(fa, "w") as f:
+        f.write(">chrC\n")
+        rb = ref.tobytes().decode()
+        for i in range(0, len(rb), 60):
+            f.write(rb[i:i + 60] + "\n")
+    return {"bams": bams, "names": names, "bed": bed, "fasta": fa, "regions": regions}

@@ -7,7 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libotter_gpu.so")
-SOURCES = ["otg_api.hip", "wfa_edit.hip", "edit_align.hip", "myers_edit.hip", "wfa_affine.hip", "wfa_affine_reg.hip", "wfa_adaptive.hip", "cluster.hip", "poa.hip", "pipeline.hip", "emit.hip", "compare.hip", "kmer_usage.hip", "vcf2mat.hip", "ingest.hip", "bedfa.hip", "dispatch.hip", "gather.hip"]
+SOURCES = ["otg_api.hip", "wfa_edit.hip", "edit_align.hip", "myers_edit.hip", "wfa_affine.hip", "wfa_affine_reg.hip", "wfa_adaptive.hip", "cluster.hip", "poa.hip", "pipeline.hip", "emit.hip", "compare.hip", "kmer_usage.hip", "vcf2mat.hip", "ingest.hip", "bedfa.hip", "dispatch.hip", "gather.hip", "cohort.hip"]
 # -ffp-contract=off: the reference's clustering decisions are FP64 comparisons made without FMA
 # contraction; fused operations are written explicitly where glibc uses them.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
@@ -32,7 +32,8 @@ def needs_build():
 TOOL_SRC = os.path.join(HERE, "..", "tools", "otter_assemble.cpp")
 TOOL = os.path.join(HERE, "..", "tools", "otter_assemble")
 TOOLS = [(TOOL_SRC, TOOL), (os.path.join(HERE, "..", "tools", "otter_compare.cpp"), os.path.join(HERE, "..", "tools", "otter_compare")),
-         (os.path.join(HERE, "..", "tools", "otter_vcf2mat.cpp"), os.path.join(HERE, "..", "tools", "otter_vcf2mat"))]
+         (os.path.join(HERE, "..", "tools", "otter_vcf2mat.cpp"), os.path.join(HERE, "..", "tools", "otter_vcf2mat")),
+         (os.path.join(HERE, "..", "tools", "otter_cohort.cpp"), os.path.join(HERE, "..", "tools", "otter_cohort"))]
 
 
 def build_tool(force=False):

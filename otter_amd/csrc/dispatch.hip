@@ -374,6 +374,247 @@ void shard_worker(Job& J, int device, uint32_t a, uint32_t bnd, int ingest_threa
   for (int t = 0; t < n_gpu_threads; ++t) { J.st.ms_hot_path += ms_gpu[t]; J.st.ms_emit += ms_emit[t]; }
 }
 
+
+// ---- the cohort dispatcher (otg_cohort_files): per device shard, per batch, per sample: ingest -> hot path -> otg_cohort_stage; the thread that
+// stages the last sample of a batch regroups, clusters, collects and formats it.
+struct CohortText { std::string vcf; std::vector<std::string> sam; };
+struct CohortOut {
+  std::mutex m;
+  std::condition_variable cv;
+  std::map<uint32_t, CohortText> ready;     // batch index -> texts
+  uint32_t n_batches = 0, next = 0;
+  size_t cap = 3;
+};
+struct CohortRef {                           // reference alleles of one batch (genotype_process, src/genotype.cpp:93-101), fetched once
+  std::vector<uint8_t> arena; std::vector<uint64_t> off; std::vector<uint32_t> len;
+};
+struct CohortItem { BatchPtr b; uint32_t sample = 0; std::shared_ptr<CohortRef> ref; };
+struct CohortSlot {                          // one batch being staged on a device: a light context of its own (a stream and the staging buffers)
+  otg_ctx* ctx = nullptr;
+  std::mutex m;
+  std::condition_variable cv;
+  int64_t batch = -1;                        // the batch it is open for (-1: free)
+  int64_t next = 0;                          // the batch that may open it next (slots alternate: next += 2)
+  uint32_t staged = 0;
+  std::vector<std::string> sam;
+};
+struct CohortShared {
+  const otg_cohort_job* j = nullptr;
+  Job M;                                     // BED, FASTA, job status and statistics
+  std::vector<std::unique_ptr<Job>> S;       // per sample: what ingest_batch reads (BAM handle, its otg_assemble_job)
+  std::vector<otg_assemble_job> aj;
+  otg_params P;
+  uint32_t n_samples = 0;
+};
+
+int fetch_reference_alleles(const CohortShared& C, uint32_t first, uint32_t n, CohortRef& R)
+{
+  R.arena.clear(); R.off.assign(n, 0); R.len.assign(n, 0);
+  std::vector<char> buf;
+  for (uint32_t g = 0; g < n; ++g) {
+    const otg_bed& bd = C.M.beds[first + g];
+    const int fb = (int)(uint32_t)bd.start - C.j->ingest.offset_l, fe = (int)(uint32_t)bd.end + C.j->ingest.offset_r - 1;
+    uint64_t need = 0;
+    buf.resize((size_t)(fe >= fb ? (long long)fe - fb + 2 : 2) + 16);
+    if (otg_fasta_fetch(C.M.fasta, C.M.chr_arena.data() + bd.chr_off, bd.chr_len, fb, fe, buf.data(), buf.size(), &need) != OTG_OK) {
+      buf.resize((size_t)need + 16);
+      if (otg_fasta_fetch(C.M.fasta, C.M.chr_arena.data() + bd.chr_off, bd.chr_len, fb, fe, buf.data(), buf.size(), &need) != OTG_OK) return OTG_ERR_ARG;
+    }
+    R.off[g] = R.arena.size(); R.len[g] = (uint32_t)need;
+    R.arena.insert(R.arena.end(), (const uint8_t*)buf.data(), (const uint8_t*)buf.data() + need);
+  }
+  R.arena.resize(R.arena.size() + 64, 0);
+  return OTG_OK;
+}
+
+// regroup + cluster + collect + VCF lines of one fully staged batch
+int cohort_finish_batch(CohortShared& C, otg_ctx* cctx, const Batch& b, const CohortRef& ref, int threads, std::string& text, double* ms_gpu, double* ms_emit, uint32_t* n_ok)
+{
+  auto t0 = Clock::now();
+  int rc = otg_cohort_regroup(cctx, ref.arena.data(), ref.arena.size(), ref.off.data(), ref.len.data());
+  if (rc == OTG_OK) rc = otg_cohort_genotype(cctx, &C.P);
+  uint32_t na = 0; uint64_t sb = 0;
+  if (rc == OTG_OK) rc = otg_cohort_result_sizes(cctx, &na, &sb);
+  if (rc != OTG_OK) return rc;
+  const uint32_t n = b.n;
+  std::vector<uint32_t> first((size_t)n + 1); std::vector<otg_allele> alleles((size_t)na + 1); std::vector<uint8_t> seqs((size_t)sb + 64);
+  std::vector<int32_t> gt((size_t)na + 1), reps((size_t)na + 1), ngt((size_t)n + 1); std::vector<double> hsd((size_t)na + 1);
+  rc = otg_cohort_collect(cctx, first.data(), alleles.data(), na, nullptr, nullptr, nullptr, seqs.data(), sb, gt.data(), nullptr, nullptr, hsd.data(), ngt.data(), reps.data());
+  if (rc != OTG_OK) return rc;
+  *ms_gpu += ms_since(t0);
+  t0 = Clock::now();
+  // VCF lines: slices of the batch's regions on host threads, as otg_genotype_files formats them
+  const uint32_t nslice = (uint32_t)std::max(1, std::min<int>(threads, (int)((n + 31) / 32)));
+  std::vector<std::string> parts(nslice);
+  std::vector<int> prc(nslice, OTG_OK);
+  auto emit_slice = [&](uint32_t sidx) {
+    const uint32_t a = (uint32_t)((uint64_t)n * sidx / nslice), e = (uint32_t)((uint64_t)n * (sidx + 1) / nslice);
+    std::string& out = parts[sidx];
+    uint64_t bytes = (uint64_t)(e - a) * (512 + 80ull * (C.n_samples + 1));
+    for (uint32_t i = first[a]; i < first[e]; ++i) bytes += alleles[i].seq_len + 8;
+    out.resize(bytes);
+    uint64_t len = 0;
+    int r2 = otg_emit_vcf_lines(C.M.beds.data() + b.first + a, C.M.chr_arena.data(), e - a, first.data() + a, alleles.data(), seqs.data(), C.n_samples, gt.data(), hsd.data(),
+                                ngt.data() + a, reps.data(), C.j->ingest.offset_l, C.j->ingest.offset_r, bytes ? &out[0] : nullptr, bytes, &len);
+    if (r2 == OTG_ERR_CAPACITY) {
+      out.resize(len);
+      r2 = otg_emit_vcf_lines(C.M.beds.data() + b.first + a, C.M.chr_arena.data(), e - a, first.data() + a, alleles.data(), seqs.data(), C.n_samples, gt.data(), hsd.data(),
+                              ngt.data() + a, reps.data(), C.j->ingest.offset_l, C.j->ingest.offset_r, len ? &out[0] : nullptr, len, &len);
+    }
+    prc[sidx] = r2;
+    out.resize(r2 == OTG_OK ? len : 0);
+  };
+  if (nslice == 1) emit_slice(0);
+  else {
+    std::vector<std::thread> th;
+    for (uint32_t sidx = 0; sidx < nslice; ++sidx) th.emplace_back(emit_slice, sidx);
+    for (auto& t : th) t.join();
+  }
+  text.clear();
+  for (uint32_t sidx = 0; sidx < nslice; ++sidx) { if (prc[sidx] != OTG_OK) return prc[sidx]; text += parts[sidx]; }
+  for (uint32_t r = 0; r < n; ++r) if (first[r + 1] > first[r]) ++*n_ok;
+  *ms_emit += ms_since(t0);
+  return OTG_OK;
+}
+
+void cohort_shard_worker(CohortShared& C, int device, uint32_t a, uint32_t bnd, int ingest_threads, CohortOut& out)
+{
+  if (a >= bnd) return;
+  Job& M = C.M;
+  const uint32_t S = C.n_samples;
+  const bool want_sam = C.j->allele_write != nullptr;
+  const std::vector<std::pair<uint32_t, uint32_t>> plan = batch_plan(a, bnd, C.j->batch_regions);
+  const int n_gpu_threads = dispatch_contexts();
+  BoundedQueue<CohortItem> q_in((size_t)n_gpu_threads);
+  BatchPool& recycled = g_batches;
+  { std::lock_guard<std::mutex> lk(out.m); out.cap = (size_t)n_gpu_threads + 1; }
+  CohortSlot slots[2];
+  for (int i = 0; i < 2; ++i) {
+    slots[i].next = i;
+    if (otg_create(device, &slots[i].ctx) != OTG_OK) { M.fail(OTG_ERR_NO_DEVICE, "otg_create: " + last_err()); for (int k = 0; k < i; ++k) otg_destroy(slots[k].ctx); return; }
+  }
+  double ms_ingest = 0, ms_gpu[4] = {0, 0, 0, 0}, ms_emit[4] = {0, 0, 0, 0};
+  std::thread ingest([&] {
+    try {
+      for (uint32_t idx = 0; idx < (uint32_t)plan.size() && M.rc.load() == OTG_OK; ++idx) {
+        auto ref = std::make_shared<CohortRef>();
+        const auto tr = Clock::now();
+        if (fetch_reference_alleles(C, plan[idx].first, plan[idx].second, *ref) != OTG_OK) { M.fail(OTG_ERR_ARG, "cannot fetch the reference alleles: " + last_err()); break; }
+        ms_ingest += ms_since(tr);
+        bool stop = false;
+        for (uint32_t s = 0; s < S && M.rc.load() == OTG_OK; ++s) {
+          CohortItem it;
+          it.b = recycled.get(); it.sample = s; it.ref = ref;
+          it.b->index = idx; it.b->first = plan[idx].first; it.b->n = plan[idx].second;
+          const auto t0 = Clock::now();
+          const int rc = ingest_batch(*C.S[s], *it.b, ingest_threads);
+          ms_ingest += ms_since(t0);
+          trace("ingest", idx, it.b->n, t0);
+          if (rc != OTG_OK) { M.fail(rc, std::string("ingest of ") + C.j->bam_paths[s] + ": " + last_err()); stop = true; break; }
+          { std::lock_guard<std::mutex> lk(M.st_m); M.st.n_reads += it.b->n_reads; M.st.input_bytes += it.b->arena_used; }
+          if (!q_in.push(std::move(it))) { stop = true; break; }
+        }
+        if (stop) break;
+      }
+    } catch (const std::exception& e) { M.fail(OTG_ERR_ARG, std::string("ingest: ") + e.what()); }
+    q_in.finish();
+  });
+  auto gpu_thread = [&](int slot_idx) {
+    otg_ctx* ctx = pool_acquire(device);
+    if (!ctx) { M.fail(OTG_ERR_NO_DEVICE, "otg_create: " + last_err()); q_in.abort(); return; }
+    std::vector<otg_region_result> rr; std::vector<otg_allele> al; std::vector<uint8_t> seqs;
+    auto fail_ctx = [&](int rc, const char* what, otg_ctx* c) { M.fail(rc, std::string(what) + ": " + (c && otg_last_error(c) && otg_last_error(c)[0] ? std::string(otg_last_error(c)) : last_err())); q_in.abort(); };
+    try {
+      CohortItem it;
+      while (M.rc.load() == OTG_OK && q_in.pop(it)) {
+        Batch& b = *it.b;
+        const uint32_t idx = b.index, s = it.sample;
+        auto t0 = Clock::now();
+        int rc = otg_assemble_submit(ctx, &C.P, b.arena.data(), b.arena_used, b.reads.data(), b.n_reads, b.regions.data(), b.n);
+        if (rc == OTG_OK) rc = otg_assemble_run(ctx);
+        uint32_t na = 0; uint64_t sb = 0;
+        if (rc == OTG_OK) rc = otg_assemble_result_sizes(ctx, &na, &sb);
+        if (rc != OTG_OK) { fail_ctx(rc, "hot path", ctx); break; }
+        trace("run", idx, b.n, t0);
+        ms_gpu[slot_idx] += ms_since(t0);
+        std::string sam;
+        if (want_sam) {
+          // the records `otter assemble -R <name>` prints for this sample and batch (otg_assemble_files' text)
+          t0 = Clock::now();
+          rr.resize(b.n); al.resize((size_t)na + 1); seqs.resize((size_t)sb + 64);
+          rc = otg_assemble_collect(ctx, rr.data(), al.data(), (uint32_t)al.size(), seqs.data(), seqs.size(), nullptr);
+          if (rc != OTG_OK) { fail_ctx(rc, "collect", ctx); break; }
+          ms_gpu[slot_idx] += ms_since(t0);
+          t0 = Clock::now();
+          uint64_t need = 0;
+          rc = otg_emit_alleles(M.beds.data() + b.first, M.chr_arena.data(), b.n, rr.data(), al.data(), seqs.data(), C.j->sample_names[s], 0, nullptr, 0, &need);
+          if (rc == OTG_OK || rc == OTG_ERR_CAPACITY) {
+            sam.resize(need);
+            rc = otg_emit_alleles(M.beds.data() + b.first, M.chr_arena.data(), b.n, rr.data(), al.data(), seqs.data(), C.j->sample_names[s], 0, sam.empty() ? nullptr : &sam[0], sam.size(), &need);
+          }
+          if (rc != OTG_OK) { fail_ctx(rc, "emit", nullptr); break; }
+          ms_emit[slot_idx] += ms_since(t0);
+        }
+        // stage into the batch's slot; the thread that brings the last sample finishes the batch
+        CohortSlot& sl = slots[idx & 1u];
+        CohortText done;
+        bool finished = false;
+        {
+          std::unique_lock<std::mutex> lk(sl.m);
+          while (!(sl.batch == (int64_t)idx || (sl.batch < 0 && sl.next == (int64_t)idx) || M.rc.load() != OTG_OK)) sl.cv.wait_for(lk, std::chrono::milliseconds(50));
+          if (M.rc.load() != OTG_OK) break;
+          t0 = Clock::now();
+          if (sl.batch < 0) {
+            rc = otg_cohort_begin(sl.ctx, b.n, S);
+            if (rc != OTG_OK) { fail_ctx(rc, "cohort", sl.ctx); break; }
+            sl.batch = idx; sl.staged = 0; sl.sam.assign(want_sam ? S : 0, std::string());
+          }
+          rc = otg_cohort_stage(sl.ctx, ctx, s);
+          if (rc != OTG_OK) { fail_ctx(rc, "stage", sl.ctx); break; }
+          trace("stage", idx, b.n, t0);
+          ms_gpu[slot_idx] += ms_since(t0);
+          if (want_sam) sl.sam[s] = std::move(sam);
+          { std::lock_guard<std::mutex> lk2(M.st_m); M.st.n_alleles += na; }
+          if (++sl.staged == S) {
+            uint32_t n_ok = 0;
+            t0 = Clock::now();
+            rc = cohort_finish_batch(C, sl.ctx, b, *it.ref, ingest_threads, done.vcf, &ms_gpu[slot_idx], &ms_emit[slot_idx], &n_ok);
+            if (rc != OTG_OK) { fail_ctx(rc, "genotype", sl.ctx); break; }
+            trace("genotype", idx, b.n, t0);
+            (void)otg_cohort_end(sl.ctx);
+            done.sam = std::move(sl.sam);
+            sl.sam.clear();
+            { std::lock_guard<std::mutex> lk2(M.st_m); M.st.n_regions_ok += n_ok; }
+            sl.batch = -1; sl.next += 2;
+            finished = true;
+          }
+        }
+        sl.cv.notify_all();
+        recycled.put(std::move(it.b));
+        it.ref.reset();
+        if (finished) {
+          std::unique_lock<std::mutex> lk(out.m);
+          while (!(out.ready.size() < out.cap || idx == out.next || M.rc.load() != OTG_OK)) out.cv.wait_for(lk, std::chrono::milliseconds(50));
+          out.ready.emplace(idx, std::move(done));
+          lk.unlock();
+          out.cv.notify_all();
+        }
+      }
+    } catch (const std::exception& e) { M.fail(OTG_ERR_ARG, std::string("hot path: ") + e.what()); }
+    if (M.rc.load() != OTG_OK) { q_in.abort(); for (auto& sl : slots) sl.cv.notify_all(); }
+    pool_release(device, ctx);
+  };
+  std::vector<std::thread> gts;
+  for (int t = 0; t < n_gpu_threads; ++t) gts.emplace_back(gpu_thread, t);
+  ingest.join();
+  for (auto& t : gts) t.join();
+  out.cv.notify_all();
+  for (auto& sl : slots) otg_destroy(sl.ctx);
+  std::lock_guard<std::mutex> lk(M.st_m);
+  M.st.ms_ingest += ms_ingest;
+  for (int t = 0; t < n_gpu_threads; ++t) { M.st.ms_hot_path += ms_gpu[t]; M.st.ms_emit += ms_emit[t]; }
+}
+
 } // namespace
 
 extern "C" {
@@ -866,6 +1107,150 @@ int otg_genotype_files(const otg_genotype_job* job, otg_write_fn write, void* us
   cleanup();
   st.ms_total = ms_since(t_all); st.n_devices = 1;
   if (stats) *stats = st;
+  return OTG_OK;
+}
+
+// ---- sample BAMs to one joint VCF: `otter assemble` per sample and `otter genotype` on their alleles, which stay on the device in between
+// (cohort.hip).  Shards, batch plan and the BED-order writer as otg_assemble_files.
+int otg_cohort_files(const otg_cohort_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
+{
+  if (!job || !write || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: NULL job, writer or BED path");
+  if (job->n_samples == 0 || !job->bam_paths || !job->sample_names) return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: zero samples (n_samples = %u)", job->n_samples);
+  if (!job->fasta_path || !job->fasta_path[0]) return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: no reference FASTA (fasta_path): the joint VCF needs the reference alleles");
+  if (job->n_devices < 0 || (job->n_devices > 0 && !job->devices)) return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: bad device list");
+  const uint32_t S = job->n_samples;
+  {
+    std::map<std::string, uint32_t> seen;
+    for (uint32_t s = 0; s < S; ++s) {
+      if (!job->bam_paths[s] || !job->bam_paths[s][0]) return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: sample %u has no BAM path", s);
+      if (!job->sample_names[s] || !job->sample_names[s][0]) return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: sample %u (%s) has an empty name", s, job->bam_paths[s]);
+      auto ins = seen.emplace(job->sample_names[s], s);
+      if (!ins.second) return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: sample name '%s' is given twice (samples %u and %u)", job->sample_names[s], ins.first->second, s);
+    }
+  }
+  const auto t_all = Clock::now();
+  g_trace_t0 = t_all;
+  CohortShared C;
+  C.j = job; C.n_samples = S;
+  C.P = job->params; C.P.realign = 1;
+  Job& M = C.M;
+  {
+    uint32_t n = 0, skipped = 0; uint64_t cu = 0;
+    int rc = otg_parse_bed_file(job->bed_path, nullptr, 0, &n, nullptr, 0, &cu, &skipped);
+    if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) return rc;
+    M.beds.resize((size_t)n + 1); M.chr_arena.resize((size_t)cu + 16);
+    rc = otg_parse_bed_file(job->bed_path, M.beds.data(), (uint32_t)M.beds.size(), &n, M.chr_arena.data(), M.chr_arena.size(), &cu, &skipped);
+    if (rc != OTG_OK) return rc;
+    M.beds.resize(n);
+    M.st.n_regions = n;
+    // regions are identified by index here, by their chr:start-end string in the file round trip: the same string twice would differ
+    std::map<std::string, uint32_t> seen;
+    for (uint32_t r = 0; r < n; ++r) {
+      const otg_bed& b = M.beds[r];
+      std::string key(M.chr_arena.data() + b.chr_off, b.chr_len);
+      key += ":" + std::to_string((uint32_t)b.start) + "-" + std::to_string((uint32_t)b.end);
+      auto ins = seen.emplace(key, r);
+      if (!ins.second) return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: BED records %u and %u of %s are the same region %s", ins.first->second + 1, r + 1, job->bed_path, key.c_str());
+    }
+  }
+  auto cleanup = [&] { for (auto& sj : C.S) if (sj && sj->bam) otg_bam_close(sj->bam); if (M.fasta) otg_fasta_close(M.fasta); };
+  int rc = otg_fasta_open(job->fasta_path, &M.fasta);
+  if (rc != OTG_OK) return rc;
+  C.aj.resize(S);
+  for (uint32_t s = 0; s < S; ++s) {
+    C.S.emplace_back(new Job());
+    Job& J = *C.S.back();
+    otg_assemble_job& a = C.aj[s];
+    memset(&a, 0, sizeof(a));
+    a.bam_path = job->bam_paths[s]; a.bed_path = job->bed_path; a.fasta_path = job->fasta_path; a.read_group = job->sample_names[s];
+    a.params = C.P; a.ingest = job->ingest; a.batch_regions = job->batch_regions;
+    J.j = &a; J.beds = M.beds; J.chr_arena = M.chr_arena; J.fasta = M.fasta;
+    rc = otg_bam_open(job->bam_paths[s], &J.bam);
+    if (rc != OTG_OK) { cleanup(); return rc; }
+    if (s > 0) {
+      otg_bam* b0 = C.S[0]->bam;
+      bool same = otg_bam_n_targets(J.bam) == otg_bam_n_targets(b0);
+      for (uint32_t i = 0; same && i < otg_bam_n_targets(b0); ++i) {
+        uint64_t l0 = 0, l1 = 0;
+        const char* n0 = otg_bam_target(b0, i, &l0); const char* n1 = otg_bam_target(J.bam, i, &l1);
+        same = l0 == l1 && strcmp(n0, n1) == 0;
+      }
+      if (!same) { cleanup(); return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: the targets of %s differ from those of the first BAM %s", job->bam_paths[s], job->bam_paths[0]); }
+    }
+  }
+  // headers: the VCF header with the first BAM's contigs and the samples' names; per sample the SAM header of its allele records
+  {
+    otg_bam* b0 = C.S[0]->bam;
+    otg_bam_set_samples(b0, job->sample_names, S, job->ingest.offset_l, job->ingest.offset_r);
+    uint64_t need = 0;
+    rc = otg_emit_vcf_header(b0, nullptr, 0, &need);
+    if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) { cleanup(); return rc; }
+    std::string hdr(need, '\0');
+    rc = otg_emit_vcf_header(b0, need ? &hdr[0] : nullptr, need, &need);
+    if (rc != OTG_OK) { cleanup(); return rc; }
+    if (write(user, hdr.data(), hdr.size()) != 0) { cleanup(); return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: the writer failed"); }
+    M.st.output_bytes += hdr.size();
+    if (job->allele_write) {
+      const uint32_t nt = otg_bam_n_targets(b0);
+      std::string names; std::vector<uint64_t> off(nt), len(nt); std::vector<uint32_t> nl(nt);
+      for (uint32_t i = 0; i < nt; ++i) { uint64_t l = 0; const char* nm = otg_bam_target(b0, i, &l); off[i] = names.size(); nl[i] = (uint32_t)strlen(nm); len[i] = l; names += nm; }
+      for (uint32_t s = 0; s < S; ++s) {
+        rc = otg_emit_sam_header(names.data(), off.data(), nl.data(), len.data(), nt, job->sample_names[s], job->ingest.offset_l, job->ingest.offset_r, nullptr, 0, &need);
+        if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) { cleanup(); return rc; }
+        std::string sh(need, '\0');
+        rc = otg_emit_sam_header(names.data(), off.data(), nl.data(), len.data(), nt, job->sample_names[s], job->ingest.offset_l, job->ingest.offset_r, need ? &sh[0] : nullptr, need, &need);
+        if (rc != OTG_OK) { cleanup(); return rc; }
+        if (job->allele_write(job->allele_user, s, sh.data(), sh.size()) != 0) { cleanup(); return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: the allele writer failed"); }
+      }
+    }
+  }
+  std::vector<int> devs;
+  if (job->n_devices > 0) devs.assign(job->devices, job->devices + job->n_devices); else devs.push_back(0);
+  const uint32_t R = (uint32_t)M.beds.size(), W = (uint32_t)devs.size();
+  const uint32_t block = R / W;
+  const int threads_total = job->ingest.threads > 0 ? job->ingest.threads : 1;
+  const int threads_per = std::max(1, threads_total / (int)W);
+  std::vector<std::unique_ptr<CohortOut>> outs;
+  std::vector<std::thread> workers;
+  std::vector<std::pair<uint32_t, uint32_t>> bounds;
+  for (uint32_t w = 0; w < W; ++w) {
+    const uint32_t a = block == 0 ? std::min(w, R) : w * block;
+    const uint32_t b = block == 0 ? std::min(w + 1, R) : (w == W - 1 ? R : a + block);
+    bounds.emplace_back(a, b);
+    outs.emplace_back(new CohortOut());
+    outs.back()->n_batches = (uint32_t)batch_plan(a, b, job->batch_regions).size();
+  }
+  for (uint32_t w = 0; w < W; ++w) workers.emplace_back(cohort_shard_worker, std::ref(C), devs[w], bounds[w].first, bounds[w].second, threads_per, std::ref(*outs[w]));
+  for (uint32_t w = 0; w < W; ++w) {
+    CohortOut& o = *outs[w];
+    for (uint32_t k = 0; k < o.n_batches; ++k) {
+      CohortText text;
+      {
+        std::unique_lock<std::mutex> lk(o.m);
+        while (!o.ready.count(k) && M.rc.load() == OTG_OK) o.cv.wait_for(lk, std::chrono::milliseconds(50));
+        if (!o.ready.count(k)) break;
+        text = std::move(o.ready[k]);
+        o.ready.erase(k);
+        o.next = k + 1;
+      }
+      o.cv.notify_all();
+      if (!text.vcf.empty() && write(user, text.vcf.data(), text.vcf.size()) != 0) { M.fail(OTG_ERR_ARG, "the writer failed"); break; }
+      M.st.output_bytes += text.vcf.size();
+      for (uint32_t s = 0; s < (uint32_t)text.sam.size(); ++s)
+        if (!text.sam[s].empty() && job->allele_write(job->allele_user, s, text.sam[s].data(), text.sam[s].size()) != 0) { M.fail(OTG_ERR_ARG, "the allele writer failed"); break; }
+      if (M.rc.load() != OTG_OK) break;
+    }
+    if (M.rc.load() != OTG_OK) break;
+  }
+  for (auto& o : outs) o->cv.notify_all();
+  for (auto& t : workers) t.join();
+  cleanup();
+  pool_trim(devs);
+  trace("job", 0, R, t_all);
+  M.st.ms_total = ms_since(t_all);
+  M.st.n_devices = W;
+  if (stats) *stats = M.st;
+  if (M.rc.load() != OTG_OK) return otg_fail(nullptr, M.rc.load(), "otg_cohort_files: %s", M.err.c_str());
   return OTG_OK;
 }
 

@@ -757,6 +757,20 @@ int otg_bam_sample_index(otg_bam* b, uint32_t* n_samples, int32_t* offset_l, int
   return OTG_OK;
 }
 
+} // extern "C"
+
+// The cohort path (dispatch.hip) has no allele BAM: the sample list and offsets its VCF header and lines need come from the job.
+void otg_bam_set_samples(otg_bam* b, const char* const* names, uint32_t n, int32_t offset_l, int32_t offset_r)
+{
+  b->index2sample.assign(names, names + n);
+  b->sample2index.clear();
+  for (uint32_t i = 0; i < n; ++i) b->sample2index[b->index2sample[i]] = (int)i;
+  b->offset_l = offset_l; b->offset_r = offset_r;
+  b->samples_parsed = true;
+}
+
+extern "C" {
+
 const char* otg_bam_sample(const otg_bam* b, uint32_t i)
 {
   if (!b || !b->samples_parsed || i >= b->index2sample.size()) return nullptr;

@@ -128,6 +128,7 @@ void otg_destroy(otg_ctx* ctx)
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
   otg_pipeline_free(ctx);
+  otg_cohort_free(ctx);
   for (auto& b : ctx->pool) if (b.p) (void)hipFree(b.p);
   for (int i = 0; i < 5; ++i) { if (ctx->tier_stream[i]) (void)hipStreamDestroy(ctx->tier_stream[i]); if (ctx->ev_join[i]) (void)hipEventDestroy(ctx->ev_join[i]); }
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
@@ -433,6 +434,33 @@ int otg_poa_consensus_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t are
   return OTG_OK;
 }
 
+} // extern "C"
+
+// The launch part of anallele_cluster on device-resident inputs: what otg_genotype_cluster_batch runs behind its uploads and the cohort path
+// (cohort.hip) runs on its regrouped buffers.  h_n_alleles is the host copy of d_n (wide routing).  d_gt holds 4 x (na + 1) int32 (gt, gt_l,
+// gt_k, reps), d_ngt 2 x n_regions (n_gt, then the per-region error flags).  ctx->ev0 / ev1 are recorded around the kernels; no synchronisation.
+int otg_genotype_resident(otg_ctx* ctx, const otg_params* params, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len,
+                          const uint32_t* d_first, const uint32_t* d_n, const uint32_t* h_n_alleles, uint32_t n_regions, const uint64_t* d_poff,
+                          uint64_t n_pairs, uint64_t na, int32_t* d_gt, double* d_hsd, int32_t* d_ngt)
+{
+  uint32_t a_max = 0;
+  std::vector<uint32_t> wide;          // regions above the LDS scratch of the genotype kernel
+  for (uint32_t r = 0; r < n_regions; ++r) {
+    a_max = std::max<uint32_t>(a_max, h_n_alleles[r]);
+    if (h_n_alleles[r] > OTG_CLUSTER_NMAX) wide.push_back(r);
+  }
+  int32_t *d_gtl = d_gt + (na + 1), *d_gtk = d_gtl + (na + 1), *d_reps = d_gtk + (na + 1), *d_err = d_ngt + n_regions;
+  HIP_TRY(ctx, hipMemsetAsync(d_gt, 0xff, (na + 1) * 4 * 4, ctx->stream));
+  HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  int rc = otg_launch_genotype(ctx, params, d_arena, d_off, d_len, d_first, d_n, n_regions, d_poff, n_pairs, na, a_max, wide.data(), (uint32_t)wide.size(),
+                               d_gt, d_gtl, d_gtk, d_hsd, d_ngt, d_reps, d_err);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  return OTG_OK;
+}
+
+extern "C" {
+
 int otg_genotype_cluster_batch(otg_ctx* ctx, const otg_params* params, const uint8_t* seq_arena, uint64_t arena_bytes,
                                const uint64_t* seq_off, const uint32_t* seq_len,
                                const uint32_t* first_allele, const uint32_t* n_alleles, uint32_t n_regions,
@@ -445,13 +473,9 @@ int otg_genotype_cluster_batch(otg_ctx* ctx, const otg_params* params, const uin
     return otg_fail(ctx, OTG_ERR_ARG, "otg_genotype_cluster_batch: NULL argument");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   uint64_t na = 0;
-  uint32_t a_max = 0;
-  std::vector<uint32_t> wide;          // regions above the LDS scratch of the genotype kernel
   std::vector<uint64_t> pair_off(n_regions + 1, 0);
   for (uint32_t r = 0; r < n_regions; ++r) {
     na = std::max<uint64_t>(na, (uint64_t)first_allele[r] + n_alleles[r]);
-    a_max = std::max<uint32_t>(a_max, n_alleles[r]);
-    if (n_alleles[r] > OTG_CLUSTER_NMAX) wide.push_back(r);
     uint64_t A = n_alleles[r];
     pair_off[r + 1] = pair_off[r] + A * (A ? A - 1 : 0) / 2;
   }
@@ -473,12 +497,8 @@ int otg_genotype_cluster_batch(otg_ctx* ctx, const otg_params* params, const uin
   HIP_TRY(ctx, hipMemcpyAsync(d_first, first_allele, (size_t)n_regions * 4, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_n, n_alleles, (size_t)n_regions * 4, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_poff, pair_off.data(), (size_t)(n_regions + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(d_gt, 0xff, (na + 1) * 4 * 4, ctx->stream));
-  HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  int rc = otg_launch_genotype(ctx, params, d_arena, d_off, d_len, d_first, d_n, n_regions, d_poff, pair_off[n_regions], na, a_max, wide.data(), (uint32_t)wide.size(),
-                               d_gt, d_gtl, d_gtk, d_hsd, d_ngt, d_reps, d_err);
+  int rc = otg_genotype_resident(ctx, params, d_arena, d_off, d_len, d_first, d_n, n_alleles, n_regions, d_poff, pair_off[n_regions], na, d_gt, d_hsd, d_ngt);
   if (rc) return rc;
-  HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   std::vector<int32_t> h_err(n_regions);
   HIP_TRY(ctx, hipMemcpyAsync(gt_out, d_gt, na * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(gt_l_out, d_gtl, na * 4, hipMemcpyDeviceToHost, ctx->stream));

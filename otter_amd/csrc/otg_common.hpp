@@ -46,6 +46,8 @@ struct otg_ctx {
   unsigned long long* affine_visited = nullptr;   // device counter: (score, diagonal) cells the exact gap-affine tiers visited (wfa_affine.hip)
   // aligner heuristic of the L1 calls and of the running pipeline (otg_set_heuristic / otg_params.heuristic; wfa_adaptive.hip)
   int heur_strategy = OTG_HEURISTIC_NONE, heur_min_wf_len = 10, heur_max_dist = 50, heur_steps = 1;
+  // cohort staging area of otg_cohort_begin .. otg_cohort_end (cohort.hip); created on first use
+  struct Cohort* cohort = nullptr;
 };
 
 extern thread_local std::string g_otg_err;
@@ -80,6 +82,10 @@ enum {
 };
 
 void otg_pipeline_free(otg_ctx* ctx);
+int64_t otg_pipeline_run_regions(otg_ctx* ctx);
+void otg_cohort_free(otg_ctx* ctx);
+// ingest.hip: gives a BAM handle the sample list of a cohort job (what otg_bam_sample_index reads from an allele BAM's header)
+void otg_bam_set_samples(otg_bam* b, const char* const* names, uint32_t n, int32_t offset_l, int32_t offset_r);
 
 // Contexts that share a device (the dispatcher runs 2-4 per GPU) size their multi-gigabyte workspaces from hipMemGetInfo; two of them doing so
 // at the same moment would both claim the same free bytes.  Every "measure free memory, then allocate" section holds this lock.
@@ -253,6 +259,11 @@ int otg_launch_poa(otg_ctx* ctx, const uint8_t* d_seq_arena, const uint8_t* d_ci
                    const otg_poa_member* d_members, uint32_t n_members, const otg_poa_graph* d_graphs,
                    const otg_poa_graph* h_graphs, uint32_t n_graphs, uint32_t* d_out_len,
                    std::vector<uint64_t>& node_off);
+
+// otg_api.hip: anallele_cluster on device-resident inputs (memset of the outputs, ev0, the kernels below, ev1); see its definition
+int otg_genotype_resident(otg_ctx* ctx, const otg_params* params, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len,
+                          const uint32_t* d_first, const uint32_t* d_n, const uint32_t* h_n_alleles, uint32_t n_regions, const uint64_t* d_poff,
+                          uint64_t n_pairs, uint64_t na, int32_t* d_gt, double* d_hsd, int32_t* d_ngt);
 
 // cluster.hip (genotype_kernel)
 int otg_launch_genotype(otg_ctx* ctx, const otg_params* P, const uint8_t* d_arena, const uint64_t* d_seq_off,

@@ -80,6 +80,9 @@ void otg_pipeline_free(otg_ctx* ctx)
   ctx->pipe = nullptr;
 }
 
+// regions of the latest completed run (cohort.hip checks a staged run against its batch); -1 without one
+int64_t otg_pipeline_run_regions(otg_ctx* ctx) { return (ctx && ctx->pipe && ctx->pipe->ran) ? (int64_t)ctx->pipe->n_regions : -1; }
+
 namespace {
 
 __device__ __forceinline__ size_t didx(int N, int r, int c) { return (size_t)((((long long)(2 * N - 3 - r)) * r) >> 1) + c - 1; }
