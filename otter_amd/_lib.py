@@ -737,11 +737,35 @@ def genotype_blocks(blk):
             np.ascontiguousarray(first[:-1], dtype=np.uint32), np.ascontiguousarray(np.diff(first.astype(np.int64)), dtype=np.uint32))
 
 
+def _run_files_job(fn_name, job, job_type, callbacks=None, sink=None):
+    """One otg_*_files entry point: collects what it writes and returns (text bytes, stats dict); OtterGpuError with the library's last
+    error when it fails.  callbacks: {job field: (callback type, Python callable)} for the further writers a job struct carries (set on
+    the job and kept alive here).  sink: a writer to use in place of the collecting one.  tests/dispatch_exits_child.py gets its refusing
+    writers in by wrapping this function (looked up as a module global by the five public functions) and passing `sink` / replacing the
+    callables in `callbacks` by field name: a change of this signature or of that layout has to be made there too."""
+    L = load()
+    chunks = []
+
+    def collect(_user, data, n):
+        chunks.append(C.string_at(data, n))
+        return 0
+    cb = abi.WRITE_FN(sink or collect)
+    alive = [fn_type(fn) for fn_type, fn in (callbacks or {}).values()]
+    for field, c in zip(callbacks or {}, alive):
+        setattr(job, field, C.cast(c, C.c_void_p))
+    st = abi.JobStats()
+    fn = getattr(L, fn_name)
+    fn.argtypes = [C.POINTER(job_type), abi.WRITE_FN, C.c_void_p, C.POINTER(abi.JobStats)]
+    rc = fn(C.byref(job), cb, None, C.byref(st))
+    if rc != 0:
+        raise OtterGpuError("%s failed (%d): %s" % (fn_name, rc, _err(L)))
+    return b"".join(chunks), {k: getattr(st, k) for k, _ in abi.JobStats._fields_}
+
+
 def assemble_files(bam, bed, fasta=None, read_group="", is_fasta=False, reads_only=False, params=None, batch_regions=0, devices=None,
                    offset_l=1, offset_r=0, mapq=0, nonprimary=False, omit_nonspanning=False, read_quality=0.0, threads=1):
     """otg_assemble_files: `otter assemble` from files to record text (the library's dispatcher, include/otter_gpu.h).
     Returns (text bytes, stats dict)."""
-    L = load()
     job = abi.AssembleJob()
     job.bam_path = bam.encode(); job.bed_path = bed.encode(); job.fasta_path = fasta.encode() if fasta else None
     job.read_group = read_group.encode(); job.is_fasta = int(is_fasta); job.reads_only = int(reads_only)
@@ -751,18 +775,7 @@ def assemble_files(bam, bed, fasta=None, read_group="", is_fasta=False, reads_on
     devs = (C.c_int32 * len(devices))(*devices) if devices else None
     job.n_devices = len(devices) if devices else 0
     job.devices = devs
-    chunks = []
-
-    def sink(_user, data, n):
-        chunks.append(C.string_at(data, n))
-        return 0
-    cb = abi.WRITE_FN(sink)
-    st = abi.JobStats()
-    L.otg_assemble_files.argtypes = [C.POINTER(abi.AssembleJob), abi.WRITE_FN, C.c_void_p, C.POINTER(abi.JobStats)]
-    rc = L.otg_assemble_files(C.byref(job), cb, None, C.byref(st))
-    if rc != 0:
-        raise OtterGpuError("otg_assemble_files failed (%d): %s" % (rc, (L.otg_last_error(None) or b"").decode()))
-    return b"".join(chunks), {k: getattr(st, k) for k, _ in abi.JobStats._fields_}
+    return _run_files_job("otg_assemble_files", job, abi.AssembleJob)
 
 
 def assemble_batch_plan(n_regions, batch_regions=0):
@@ -783,23 +796,11 @@ def assemble_batch_plan(n_regions, batch_regions=0):
 def genotype_files(bam, bed, fasta=None, params=None, threads=1, device=0, batch_regions=0):
     """otg_genotype_files: `otter genotype` from files to text (VCF with a reference FASTA, the two-length table without).
     Returns (text bytes, stats dict)."""
-    L = load()
     job = abi.GenotypeJob()
     job.bam_path = bam.encode(); job.bed_path = bed.encode(); job.fasta_path = fasta.encode() if fasta else None
     job.params = params if params is not None else abi.default_params()
     job.threads = threads; job.device = device; job.batch_regions = batch_regions
-    chunks = []
-
-    def sink(_user, data, n):
-        chunks.append(C.string_at(data, n))
-        return 0
-    cb = abi.WRITE_FN(sink)
-    st = abi.JobStats()
-    L.otg_genotype_files.argtypes = [C.POINTER(abi.GenotypeJob), abi.WRITE_FN, C.c_void_p, C.POINTER(abi.JobStats)]
-    rc = L.otg_genotype_files(C.byref(job), cb, None, C.byref(st))
-    if rc != 0:
-        raise OtterGpuError("otg_genotype_files failed (%d): %s" % (rc, (L.otg_last_error(None) or b"").decode()))
-    return b"".join(chunks), {k: getattr(st, k) for k, _ in abi.JobStats._fields_}
+    return _run_files_job("otg_genotype_files", job, abi.GenotypeJob)
 
 
 def cohort_files(bams, names, bed, fasta, params=None, batch_regions=0, devices=None, offset_l=1, offset_r=0, mapq=0, nonprimary=False,
@@ -807,7 +808,6 @@ def cohort_files(bams, names, bed, fasta, params=None, batch_regions=0, devices=
     """otg_cohort_files: sample BAMs + BED + reference FASTA to one joint VCF, the alleles staying on the device between `otter assemble` and
     `otter genotype`.  Returns (VCF bytes, stats dict), and with alleles=True also the list of per-sample SAM texts (what assemble_files returns
     for each sample with read_group = its name)."""
-    L = load()
     job = abi.CohortJob()
     n = len(bams)
     pb = (C.c_char_p * max(1, n))(*[b.encode() for b in bams])
@@ -820,27 +820,15 @@ def cohort_files(bams, names, bed, fasta, params=None, batch_regions=0, devices=
     devs = (C.c_int32 * len(devices))(*devices) if devices else None
     job.n_devices = len(devices) if devices else 0
     job.devices = devs
-    chunks, sams = [], [[] for _ in range(n)]
-
-    def sink(_user, data, ln):
-        chunks.append(C.string_at(data, ln))
-        return 0
+    sams = [[] for _ in range(n)]
 
     def asink(_user, sample, data, ln):
         sams[sample].append(C.string_at(data, ln))
         return 0
-    cb, acb = abi.WRITE_FN(sink), abi.ALLELE_WRITE_FN(asink)
+    text, stats = _run_files_job("otg_cohort_files", job, abi.CohortJob, {"allele_write": (abi.ALLELE_WRITE_FN, asink)} if alleles else None)
     if alleles:
-        job.allele_write = C.cast(acb, C.c_void_p)
-    st = abi.JobStats()
-    L.otg_cohort_files.argtypes = [C.POINTER(abi.CohortJob), abi.WRITE_FN, C.c_void_p, C.POINTER(abi.JobStats)]
-    rc = L.otg_cohort_files(C.byref(job), cb, None, C.byref(st))
-    if rc != 0:
-        raise OtterGpuError("otg_cohort_files failed (%d): %s" % (rc, (L.otg_last_error(None) or b"").decode()))
-    stats = {k: getattr(st, k) for k, _ in abi.JobStats._fields_}
-    if alleles:
-        return b"".join(chunks), stats, [b"".join(x) for x in sams]
-    return b"".join(chunks), stats
+        return text, stats, [b"".join(x) for x in sams]
+    return text, stats
 
 
 def assemble_files_release():
@@ -898,27 +886,16 @@ def compare_emit(regions, truth, query, pair_first, pair_edit, pair_ops):
 
 def compare_files(truth_bam, query_bam, bed, threads=1, device=0, batch_regions=0):
     """otg_compare_files: `otter compare` from files to text.  Returns (text bytes, warning bytes, stats dict)."""
-    L = load()
     job = abi.CompareJob()
     job.truth_bam_path = truth_bam.encode(); job.query_bam_path = query_bam.encode(); job.bed_path = bed.encode()
     job.threads = threads; job.device = device; job.batch_regions = batch_regions
-    chunks, warns = [], []
-
-    def sink(_user, data, n):
-        chunks.append(C.string_at(data, n))
-        return 0
+    warns = []
 
     def wsink(_user, data, n):
         warns.append(C.string_at(data, n))
         return 0
-    cb, wcb = abi.WRITE_FN(sink), abi.WRITE_FN(wsink)
-    job.warn = C.cast(wcb, C.c_void_p)
-    st = abi.JobStats()
-    L.otg_compare_files.argtypes = [C.POINTER(abi.CompareJob), abi.WRITE_FN, C.c_void_p, C.POINTER(abi.JobStats)]
-    rc = L.otg_compare_files(C.byref(job), cb, None, C.byref(st))
-    if rc != 0:
-        raise OtterGpuError("otg_compare_files failed (%d): %s" % (rc, (L.otg_last_error(None) or b"").decode()))
-    return b"".join(chunks), b"".join(warns), {k: getattr(st, k) for k, _ in abi.JobStats._fields_}
+    text, stats = _run_files_job("otg_compare_files", job, abi.CompareJob, {"warn": (abi.WRITE_FN, wsink)})
+    return text, b"".join(warns), stats
 
 
 def vcf_read_alleles(path, max_alleles=1 << 16, max_bytes=64 << 20):
@@ -992,19 +969,7 @@ def vcf2mat_emit(records, regions, seq_len, k, usage, gc, hsd):
 
 def vcf2mat_files(vcf, bed, k=3, threads=1, device=0, batch_alleles=0):
     """otg_vcf2mat_files: `otter vcf2mat` from a VCF (plain, gzip or BGZF) to text.  Returns (text bytes, stats dict)."""
-    L = load()
     job = abi.Vcf2matJob()
     job.vcf_path = vcf.encode(); job.bed_path = bed.encode()
     job.k = k; job.threads = threads; job.device = device; job.batch_alleles = batch_alleles
-    chunks = []
-
-    def sink(_user, data, n):
-        chunks.append(C.string_at(data, n))
-        return 0
-    cb = abi.WRITE_FN(sink)
-    st = abi.JobStats()
-    L.otg_vcf2mat_files.argtypes = [C.POINTER(abi.Vcf2matJob), abi.WRITE_FN, C.c_void_p, C.POINTER(abi.JobStats)]
-    rc = L.otg_vcf2mat_files(C.byref(job), cb, None, C.byref(st))
-    if rc != 0:
-        raise OtterGpuError("otg_vcf2mat_files failed (%d): %s" % (rc, _err(L)))
-    return b"".join(chunks), {k_: getattr(st, k_) for k_, _ in abi.JobStats._fields_}
+    return _run_files_job("otg_vcf2mat_files", job, abi.Vcf2matJob)

@@ -13,6 +13,7 @@
 // (the reference's order with -t 1; with -t > 1 the reference prints in completion order).
 #include "otg_common.hpp"
 #include "otg_compare.hpp"
+#include "otg_dispatch_queue.hpp"
 #include "otg_vcf2mat.hpp"
 #include <algorithm>
 #include <atomic>
@@ -20,7 +21,6 @@
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -39,6 +39,7 @@ template <class T> struct HostBuf {
   HostBuf& operator=(const HostBuf&) = delete;
   ~HostBuf() { free(p); }
   T* data() { return p; }
+  const T* data() const { return p; }
   size_t size() const { return n; }
   // at least `want` elements; the first `keep` stay what they were, the rest is undefined
   void resize(size_t want, size_t keep = 0) {
@@ -64,37 +65,6 @@ struct Batch {
   std::string text;                     // emitted records
 };
 
-template <class T>
-class BoundedQueue {
- public:
-  explicit BoundedQueue(size_t cap) : cap_(cap) {}
-  bool push(T v) {
-    std::unique_lock<std::mutex> lk(m_);
-    cv_space_.wait(lk, [&] { return q_.size() < cap_ || closed_; });
-    if (closed_) return false;
-    q_.push_back(std::move(v));
-    cv_item_.notify_one();
-    return true;
-  }
-  bool pop(T& out) {
-    std::unique_lock<std::mutex> lk(m_);
-    cv_item_.wait(lk, [&] { return !q_.empty() || done_ || closed_; });
-    if (closed_ || q_.empty()) return false;
-    out = std::move(q_.front());
-    q_.pop_front();
-    cv_space_.notify_one();
-    return true;
-  }
-  void finish() { std::lock_guard<std::mutex> lk(m_); done_ = true; cv_item_.notify_all(); }           // no more items will come
-  void abort() { std::lock_guard<std::mutex> lk(m_); closed_ = true; cv_item_.notify_all(); cv_space_.notify_all(); }
- private:
-  std::mutex m_;
-  std::condition_variable cv_item_, cv_space_;
-  std::deque<T> q_;
-  size_t cap_;
-  bool done_ = false, closed_ = false;
-};
-
 using BatchPtr = std::unique_ptr<Batch>;
 using Clock = std::chrono::steady_clock;
 double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
@@ -107,12 +77,8 @@ void trace(const char* what, uint32_t batch, uint32_t n, Clock::time_point from)
   fprintf(stderr, "[otg trace] %-8s batch %3u (%5u regions) %9.2f -> %9.2f ms\n", what, batch, n, std::chrono::duration<double, std::milli>(from - g_trace_t0).count(), ms_since(g_trace_t0));
 }
 
+// What the threads of one job share: its status — the first failure wins, everybody else sees rc != OTG_OK and stops — and its statistics.
 struct Job {
-  const otg_assemble_job* j = nullptr;
-  std::vector<otg_bed> beds;
-  std::vector<char> chr_arena;
-  otg_bam* bam = nullptr;
-  otg_fasta* fasta = nullptr;
   std::atomic<int> rc{OTG_OK};
   std::mutex err_m;
   std::string err;
@@ -124,6 +90,9 @@ struct Job {
     if (rc.compare_exchange_strong(expected, code)) { std::lock_guard<std::mutex> lk(err_m); err = what; }
   }
 };
+
+std::string last_err() { const char* e = otg_last_error(nullptr); return e ? std::string(e) : std::string(); }
+std::string ctx_err(otg_ctx* ctx) { const char* e = otg_last_error(ctx); return e ? std::string(e) : std::string(); }
 
 // Contexts survive the job: a fresh context pays for its first launches (page mapping of newly allocated workspaces, ~0.2-1 s), so a process
 // that runs several jobs — or bench.py's repeated file-to-text leg — keeps them in a pool; otg_assemble_files_release() empties it.
@@ -148,7 +117,7 @@ int dispatch_contexts()
 }
 // End of a job: the pool keeps what ONE shard per device needs for the next job and destroys the rest — contexts hold multi-gigabyte aligner
 // workspaces, and a caller that creates its own otg_ctx afterwards is budgeted against what is left of the device.
-void pool_trim(const std::vector<int>& devs)
+void pool_trim()
 {
   std::lock_guard<std::mutex> lk(g_pool_m);
   const int keep = dispatch_contexts();
@@ -158,42 +127,124 @@ void pool_trim(const std::vector<int>& devs)
     if (++seen[p.first] <= keep) kept.push_back(p);
     else otg_destroy(p.second);
   }
-  (void)devs;
   g_pool.swap(kept);
 }
 
-std::string last_err() { const char* e = otg_last_error(nullptr); return e ? std::string(e) : std::string(); }
+// Owners: a file handle closes, a pooled context goes back to the pool, when its owner leaves scope — on every path out of an entry point.
+// An entry point declares them BEFORE its batch buffers and its TwoInFlight, so that the prefetch thread, which reads the handles, is joined
+// first and the handles are closed after.
+struct BamClose { void operator()(otg_bam* b) const { otg_bam_close(b); } };
+struct FastaClose { void operator()(otg_fasta* f) const { otg_fasta_close(f); } };
+struct VcfClose { void operator()(otg_vcf* v) const { otg_vcf_close(v); } };
+struct PoolReturn { int device; void operator()(otg_ctx* c) const { pool_release(device, c); } };
+using BamPtr = std::unique_ptr<otg_bam, BamClose>;
+using FastaPtr = std::unique_ptr<otg_fasta, FastaClose>;
+using VcfPtr = std::unique_ptr<otg_vcf, VcfClose>;
+using PooledCtx = std::unique_ptr<otg_ctx, PoolReturn>;
+// open(path, &raw) of the C interface into an owner; the owner stays empty when the call fails
+template <class Ptr, class Open> int open_into(Ptr& out, Open open, const char* path)
+{
+  typename Ptr::pointer raw = nullptr;
+  const int rc = open(path, &raw);
+  out.reset(raw);
+  return rc;
+}
+int open_bam(const char* path, BamPtr& out) { return open_into(out, otg_bam_open, path); }
+int open_fasta(const char* path, FastaPtr& out) { return open_into(out, otg_fasta_open, path); }
+int open_vcf(const char* path, VcfPtr& out) { return open_into(out, otg_vcf_open, path); }
+PooledCtx acquire_ctx(int device) { return PooledCtx(pool_acquire(device), PoolReturn{device}); }
+
+// The regions of a job: the BED records and the arena their chromosome names point into.
+struct Bed { std::vector<otg_bed> beds; std::vector<char> chr_arena; };
+int load_bed(const char* path, Bed& B)
+{
+  // size protocol: the first call reports the needed sizes
+  uint32_t n = 0, skipped = 0; uint64_t cu = 0;
+  int rc = otg_parse_bed_file(path, nullptr, 0, &n, nullptr, 0, &cu, &skipped);
+  if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) return rc;
+  B.beds.resize((size_t)n + 1); B.chr_arena.resize((size_t)cu + 16);
+  rc = otg_parse_bed_file(path, B.beds.data(), (uint32_t)B.beds.size(), &n, B.chr_arena.data(), B.chr_arena.size(), &cu, &skipped);
+  if (rc != OTG_OK) return rc;
+  B.beds.resize(n);
+  return OTG_OK;
+}
+
+// The size protocol of the emitters: call(buf, cap, &need) with no buffer reports the size (OTG_ERR_CAPACITY from that call is not an
+// error), `out` takes that size, and the second call fills it.
+template <class Call> int sized_text(std::string& out, Call call)
+{
+  uint64_t need = 0;
+  int rc = call((char*)nullptr, (uint64_t)0, &need);
+  if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) return rc;
+  out.resize(need);
+  return call(need ? &out[0] : nullptr, need, &need);
+}
+
+// SAM header of the allele records of one read group (src/assemble.cpp:167-177), its @SQ lines from the BAM's targets
+int sam_header_text(otg_bam* bam, const char* read_group, int32_t offset_l, int32_t offset_r, std::string& out)
+{
+  const uint32_t nt = otg_bam_n_targets(bam);
+  std::string names; std::vector<uint64_t> off(nt), len(nt); std::vector<uint32_t> nl(nt);
+  for (uint32_t i = 0; i < nt; ++i) { uint64_t l = 0; const char* nm = otg_bam_target(bam, i, &l); off[i] = names.size(); nl[i] = (uint32_t)strlen(nm); len[i] = l; names += nm; }
+  return sized_text(out, [&](char* buf, uint64_t cap, uint64_t* need) {
+    return otg_emit_sam_header(names.data(), off.data(), nl.data(), len.data(), nt, read_group, offset_l, offset_r, buf, cap, need);
+  });
+}
+
+// Two batches in flight: while the caller works on current(), prefetch() fills the other buffer on a thread of its own; advance() waits
+// for it and makes it current.  The destructor joins the thread, so an entry point may return at any point of its loop.
+template <class B>
+class TwoInFlight {
+ public:
+  TwoInFlight() = default;
+  TwoInFlight(const TwoInFlight&) = delete;
+  ~TwoInFlight() { join(); }
+  B& current() { return bufs_[idx_ & 1]; }
+  B& other() { return bufs_[(idx_ + 1) & 1]; }
+  B* begin() { return bufs_; }
+  B* end() { return bufs_ + 2; }
+  template <class Fill> void prefetch(Fill fill) {
+    join();
+    B* o = &other();
+    next_ = std::thread([fill, o] { fill(*o); });
+  }
+  void advance() { join(); ++idx_; }
+ private:
+  void join() { if (next_.joinable()) next_.join(); }
+  B bufs_[2];
+  uint32_t idx_ = 0;
+  std::thread next_;
+};
 
 // ---- stage 1: one batch of regions from the BAM (and the FASTA flanks with -r), buffers grown on OTG_ERR_CAPACITY
-int ingest_batch(Job& J, Batch& b, int threads)
+int ingest_batch(otg_bam* bam, otg_fasta* fasta, const Bed& bed, const otg_ingest_opts& opts, bool reads_only, int flank, Batch& b, int threads)
 {
-  const otg_assemble_job& j = *J.j;
-  otg_ingest_opts o = j.ingest;
+  otg_ingest_opts o = opts;
   o.threads = threads;
+  const otg_bed* beds = bed.beds.data() + b.first;
+  const char* chr = bed.chr_arena.data();
   b.regions.assign(b.n, otg_region{});
   size_t cap_reads = std::max<size_t>(b.reads.size(), (size_t)b.n * 48 + 256), cap_arena = std::max<size_t>(b.arena.size(), (size_t)b.n * 48 * 4096 + 4096);
-  size_t cap_names = std::max<size_t>(b.names.size(), j.reads_only ? (size_t)b.n * 48 * 48 : 0);
+  size_t cap_names = std::max<size_t>(b.names.size(), reads_only ? (size_t)b.n * 48 * 48 : 0);
   for (int attempt = 0; attempt < 4; ++attempt) {
     b.reads.resize(cap_reads); b.arena.resize(cap_arena);
-    if (j.reads_only) { b.meta.resize(cap_reads); b.names.resize(cap_names); }
+    if (reads_only) { b.meta.resize(cap_reads); b.names.resize(cap_names); }
     uint64_t used = 0, nused = 0; uint32_t nr = 0;
-    const int rc = j.reads_only
-        ? otg_ingest_regions_named(J.bam, J.beds.data() + b.first, J.chr_arena.data(), b.n, &o, b.arena.data(), b.arena.size(), &used, b.reads.data(),
-                                   (uint32_t)b.reads.size(), &nr, b.regions.data(), b.meta.data(), b.names.data(), b.names.size(), &nused)
-        : otg_ingest_regions(J.bam, J.beds.data() + b.first, J.chr_arena.data(), b.n, &o, b.arena.data(), b.arena.size(), &used, b.reads.data(),
-                             (uint32_t)b.reads.size(), &nr, b.regions.data());
+    const int rc = reads_only
+        ? otg_ingest_regions_named(bam, beds, chr, b.n, &o, b.arena.data(), b.arena.size(), &used, b.reads.data(), (uint32_t)b.reads.size(), &nr, b.regions.data(),
+                                   b.meta.data(), b.names.data(), b.names.size(), &nused)
+        : otg_ingest_regions(bam, beds, chr, b.n, &o, b.arena.data(), b.arena.size(), &used, b.reads.data(), (uint32_t)b.reads.size(), &nr, b.regions.data());
     if (rc == OTG_ERR_CAPACITY) {      // the counters hold the needed totals
-      cap_reads = (size_t)nr + 256; cap_arena = (size_t)used + 4096 + (J.fasta ? (size_t)b.n * 2 * ((size_t)j.params.flank + 8) : 0); cap_names = (size_t)nused + 256;
+      cap_reads = (size_t)nr + 256; cap_arena = (size_t)used + 4096 + (fasta ? (size_t)b.n * 2 * ((size_t)flank + 8) : 0); cap_names = (size_t)nused + 256;
       continue;
     }
     if (rc != OTG_OK) return rc;
     b.arena_used = used; b.n_reads = nr;
-    if (J.fasta) {
-      const size_t need = used + (size_t)b.n * 2 * ((size_t)j.params.flank + 8) + 128;
+    if (fasta) {
+      const size_t need = used + (size_t)b.n * 2 * ((size_t)flank + 8) + 128;
       if (b.arena.size() < need) b.arena.resize(need, (size_t)used);
       uint64_t u2 = used;
-      const int rf = otg_fasta_region_flanks(J.fasta, J.beds.data() + b.first, J.chr_arena.data(), b.n, o.offset_l, o.offset_r, j.params.flank, b.arena.data(), b.arena.size(),
-                                             &u2, b.regions.data());
+      const int rf = otg_fasta_region_flanks(fasta, beds, chr, b.n, o.offset_l, o.offset_r, flank, b.arena.data(), b.arena.size(), &u2, b.regions.data());
       if (rf != OTG_OK) return rf;
       b.arena_used = u2;
     }
@@ -202,18 +253,55 @@ int ingest_batch(Job& J, Batch& b, int threads)
   return OTG_ERR_CAPACITY;
 }
 
-// ---- stage 2 + 3 of one batch on one context: hot path, then the record text
-int run_batch(Job& J, otg_ctx* ctx, Batch& b, std::vector<otg_region_result>& rr, std::vector<otg_allele>& al, std::vector<uint8_t>& seqs, double* ms_gpu, double* ms_emit)
+// ---- stage 2 of one batch on one context: submit -> run -> result sizes, then (where the records are wanted on the host) collect
+int hot_path_on(otg_ctx* ctx, const otg_params& P, const Batch& b, uint32_t* n_alleles, uint64_t* seq_bytes)
 {
-  const otg_assemble_job& j = *J.j;
+  auto t0 = Clock::now();
+  int rc = otg_assemble_submit(ctx, &P, b.arena.data(), b.arena_used, b.reads.data(), b.n_reads, b.regions.data(), b.n);
+  trace("submit", b.index, b.n, t0);
+  t0 = Clock::now();
+  if (rc == OTG_OK) rc = otg_assemble_run(ctx);
+  trace("run", b.index, b.n, t0);
+  if (rc == OTG_OK) rc = otg_assemble_result_sizes(ctx, n_alleles, seq_bytes);
+  return rc;
+}
+int collect_on(otg_ctx* ctx, const Batch& b, uint32_t n_alleles, uint64_t seq_bytes, std::vector<otg_region_result>& rr, std::vector<otg_allele>& al, std::vector<uint8_t>& seqs)
+{
+  const auto t0 = Clock::now();
+  rr.resize(b.n); al.resize((size_t)n_alleles + 1); seqs.resize((size_t)seq_bytes + 64);
+  const int rc = otg_assemble_collect(ctx, rr.data(), al.data(), (uint32_t)al.size(), seqs.data(), seqs.size(), nullptr);
+  if (rc == OTG_OK) trace("collect", b.index, b.n, t0);
+  return rc;
+}
+// ---- stage 3: the allele records of a collected batch, as `otter assemble -R <read_group>` prints them
+int alleles_text(const Bed& bed, const Batch& b, const std::vector<otg_region_result>& rr, const std::vector<otg_allele>& al, const std::vector<uint8_t>& seqs, const char* read_group,
+                 int is_fasta, std::string& out)
+{
+  return sized_text(out, [&](char* buf, uint64_t cap, uint64_t* need) {
+    return otg_emit_alleles(bed.beds.data() + b.first, bed.chr_arena.data(), b.n, rr.data(), al.data(), seqs.data(), read_group, is_fasta, buf, cap, need);
+  });
+}
+
+// What otg_assemble_files' threads share besides the Job: the caller's options and the open inputs.
+struct AssembleShared {
+  const otg_assemble_job* j = nullptr;
+  Job J;
+  Bed bed;
+  BamPtr bam;
+  FastaPtr fasta;
+};
+
+// ---- stage 2 + 3 of one batch on one context: hot path, then the record text
+int run_batch(AssembleShared& A, otg_ctx* ctx, Batch& b, std::vector<otg_region_result>& rr, std::vector<otg_allele>& al, std::vector<uint8_t>& seqs, double* ms_gpu, double* ms_emit)
+{
+  const otg_assemble_job& j = *A.j;
   otg_params P = j.params;
-  P.realign = J.fasta ? 1 : 0;
+  P.realign = A.fasta ? 1 : 0;
   const char* rg = j.read_group ? j.read_group : "";
   auto t0 = Clock::now();
-  uint64_t need = 0;
   if (j.reads_only) {
     // --reads-only: the reads of each region; with -r they are printed after local_realignment trimmed them (src/assemble.cpp:72-89)
-    if (J.fasta && b.n_reads) {
+    if (A.fasta && b.n_reads) {
       int rc = otg_assemble_submit(ctx, &P, b.arena.data(), b.arena_used, b.reads.data(), b.n_reads, b.regions.data(), b.n);
       if (rc == OTG_OK) rc = otg_assemble_realign(ctx);
       if (rc == OTG_OK) rc = otg_assemble_collect_reads(ctx, b.reads.data(), b.n_reads);
@@ -221,53 +309,29 @@ int run_batch(Job& J, otg_ctx* ctx, Batch& b, std::vector<otg_region_result>& rr
     }
     *ms_gpu += ms_since(t0);
     t0 = Clock::now();
-    int rc = otg_emit_reads(J.beds.data() + b.first, J.chr_arena.data(), b.n, b.regions.data(), b.reads.data(), b.arena.data(), b.meta.data(), b.names.data(), rg, j.is_fasta,
-                            P.max_cov, nullptr, 0, &need);
-    if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) return rc;
-    b.text.resize(need);
-    rc = otg_emit_reads(J.beds.data() + b.first, J.chr_arena.data(), b.n, b.regions.data(), b.reads.data(), b.arena.data(), b.meta.data(), b.names.data(), rg, j.is_fasta,
-                        P.max_cov, b.text.empty() ? nullptr : &b.text[0], b.text.size(), &need);
+    const int rc = sized_text(b.text, [&](char* buf, uint64_t cap, uint64_t* need) {
+      return otg_emit_reads(A.bed.beds.data() + b.first, A.bed.chr_arena.data(), b.n, b.regions.data(), b.reads.data(), b.arena.data(), b.meta.data(), b.names.data(), rg, j.is_fasta,
+                            P.max_cov, buf, cap, need);
+    });
     *ms_emit += ms_since(t0);
     return rc;
   }
-  int rc = otg_assemble_submit(ctx, &P, b.arena.data(), b.arena_used, b.reads.data(), b.n_reads, b.regions.data(), b.n);
-  trace("submit", b.index, b.n, t0);
-  auto t1 = Clock::now();
-  if (rc == OTG_OK) rc = otg_assemble_run(ctx);
-  trace("run", b.index, b.n, t1);
-  t1 = Clock::now();
   uint32_t na = 0; uint64_t sb = 0;
-  if (rc == OTG_OK) rc = otg_assemble_result_sizes(ctx, &na, &sb);
+  int rc = hot_path_on(ctx, P, b, &na, &sb);
+  if (rc == OTG_OK) rc = collect_on(ctx, b, na, sb, rr, al, seqs);
   if (rc != OTG_OK) return rc;
-  rr.resize(b.n); al.resize((size_t)na + 1); seqs.resize((size_t)sb + 64);
-  rc = otg_assemble_collect(ctx, rr.data(), al.data(), (uint32_t)al.size(), seqs.data(), seqs.size(), nullptr);
-  if (rc != OTG_OK) return rc;
-  trace("collect", b.index, b.n, t1);
   *ms_gpu += ms_since(t0);
   t0 = Clock::now();
-  rc = otg_emit_alleles(J.beds.data() + b.first, J.chr_arena.data(), b.n, rr.data(), al.data(), seqs.data(), rg, j.is_fasta, nullptr, 0, &need);
-  if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) return rc;
-  b.text.resize(need);
-  rc = otg_emit_alleles(J.beds.data() + b.first, J.chr_arena.data(), b.n, rr.data(), al.data(), seqs.data(), rg, j.is_fasta, b.text.empty() ? nullptr : &b.text[0], b.text.size(), &need);
+  rc = alleles_text(A.bed, b, rr, al, seqs, rg, j.is_fasta, b.text);
   *ms_emit += ms_since(t0);
   trace("emit", b.index, b.n, t0);
   {
-    std::lock_guard<std::mutex> lk(J.st_m);
-    J.st.n_alleles += na;
-    for (uint32_t r = 0; r < b.n; ++r) { if (rr[r].n_alleles) ++J.st.n_regions_ok; if (rr[r].status == OTG_REGION_SKIP_MAXCOV) ++J.st.n_regions_skipped; }
+    std::lock_guard<std::mutex> lk(A.J.st_m);
+    A.J.st.n_alleles += na;
+    for (uint32_t r = 0; r < b.n; ++r) { if (rr[r].n_alleles) ++A.J.st.n_regions_ok; if (rr[r].status == OTG_REGION_SKIP_MAXCOV) ++A.J.st.n_regions_skipped; }
   }
   return rc;
 }
-
-// ---- one device's shard [a, b): ingest thread -> two hot-path threads -> ordered text
-struct ShardOut {
-  std::mutex m;
-  std::condition_variable cv;
-  std::map<uint32_t, std::string> ready;    // batch index -> text
-  uint32_t n_batches = 0;
-  uint32_t next = 0;                        // the batch the writer takes next
-  size_t cap = 3;                           // finished batches a shard may hold back (the writer drains the shards one after the other)
-};
 
 // Batch objects cycle between the ingest thread and the hot-path threads of a shard: their vectors keep the capacity of the batches they
 // have carried (no 400 MB zero-fill per batch; at most 2 x contexts + 2 objects exist per shard).
@@ -312,16 +376,56 @@ std::vector<std::pair<uint32_t, uint32_t>> batch_plan(uint32_t a, uint32_t b, ui
 // mapping them again at the start of the next costs tens of milliseconds per object); otg_assemble_files_release() frees them.
 BatchPool g_batches;
 
-void shard_worker(Job& J, int device, uint32_t a, uint32_t bnd, int ingest_threads, ShardOut& out)
+// ---- the devices of a job and the BED-order writer over their shards
+// static contiguous split over the workers (BS::thread_pool::parallelize_loop: block = total / workers, the last takes the remainder)
+std::pair<uint32_t, uint32_t> shard_bounds(uint32_t R, uint32_t W, uint32_t w)
+{
+  const uint32_t block = R / W;
+  if (block == 0) return {std::min(w, R), std::min(w + 1, R)};
+  return {w * block, w == W - 1 ? R : (w + 1) * block};
+}
+
+// One worker thread per device on its shard of the R regions, and on the calling thread the writer: shards in order, batches in order.
+// worker(device, a, b, ingest threads, out) delivers the batches of [a, b) to `out`; write_step(batch, payload) hands one to the caller's
+// callbacks and returns false (after J.fail) when they refuse it.  Returns the number of devices.
+template <class T, class Worker, class WriteStep>
+uint32_t run_shards(Job& J, const int32_t* devices, int32_t n_devices, uint32_t R, uint32_t batch_regions, int threads_total, Worker worker, WriteStep write_step)
+{
+  std::vector<int> devs;
+  if (n_devices > 0) devs.assign(devices, devices + n_devices); else devs.push_back(0);
+  const uint32_t W = (uint32_t)devs.size();
+  const int threads_per = std::max(1, std::max(1, threads_total) / (int)W);
+  std::vector<std::unique_ptr<OrderedOutput<T>>> outs;
+  std::vector<std::thread> workers;
+  for (uint32_t w = 0; w < W; ++w) {
+    const std::pair<uint32_t, uint32_t> s = shard_bounds(R, W, w);
+    outs.emplace_back(new OrderedOutput<T>(J.rc, (uint32_t)batch_plan(s.first, s.second, batch_regions).size()));
+    workers.emplace_back(worker, devs[w], s.first, s.second, threads_per, std::ref(*outs[w]));
+  }
+  for (uint32_t w = 0; w < W && J.rc.load() == OTG_OK; ++w) {
+    T payload;
+    for (uint32_t k = 0; k < outs[w]->n_batches() && J.rc.load() == OTG_OK; ++k)
+      if (!outs[w]->take(k, payload) || !write_step(k, payload)) break;
+  }
+  for (auto& o : outs) o->wake();
+  for (auto& t : workers) t.join();
+  pool_trim();
+  return W;
+}
+
+// ---- one device's shard [a, b): ingest thread -> two hot-path threads -> ordered text
+void shard_worker(AssembleShared& A, int device, uint32_t a, uint32_t bnd, int ingest_threads, OrderedOutput<std::string>& out)
 {
   if (a >= bnd) return;                 // more devices than regions: nothing to do here (and no context to create)
-  const std::vector<std::pair<uint32_t, uint32_t>> plan = batch_plan(a, bnd, J.j->batch_regions);
+  Job& J = A.J;
+  const otg_assemble_job& j = *A.j;
+  const std::vector<std::pair<uint32_t, uint32_t>> plan = batch_plan(a, bnd, j.batch_regions);
   // hot-path threads (one context each) per device: a batch of a few hundred regions cannot fill the device — its stages wait for their
   // longest alignment / graph — so several batches are in flight; OTG_DISPATCH_CONTEXTS overrides (1..4)
   const int n_gpu_threads = dispatch_contexts();
   BoundedQueue<BatchPtr> q_in((size_t)n_gpu_threads);
   BatchPool& recycled = g_batches;
-  { std::lock_guard<std::mutex> lk(out.m); out.cap = (size_t)n_gpu_threads + 1; }
+  out.set_cap((size_t)n_gpu_threads + 1);
   double ms_ingest = 0, ms_gpu[4] = {0, 0, 0, 0}, ms_emit[4] = {0, 0, 0, 0};
   std::thread ingest([&] {
     try {
@@ -329,7 +433,7 @@ void shard_worker(Job& J, int device, uint32_t a, uint32_t bnd, int ingest_threa
         BatchPtr b = recycled.get();
         b->index = idx; b->first = plan[idx].first; b->n = plan[idx].second;
         const auto t0 = Clock::now();
-        const int rc = ingest_batch(J, *b, ingest_threads);
+        const int rc = ingest_batch(A.bam.get(), A.fasta.get(), A.bed, j.ingest, j.reads_only != 0, j.params.flank, *b, ingest_threads);
         ms_ingest += ms_since(t0);
         trace("ingest", idx, b->n, t0);
         if (rc != OTG_OK) { J.fail(rc, "ingest: " + last_err()); break; }
@@ -340,51 +444,77 @@ void shard_worker(Job& J, int device, uint32_t a, uint32_t bnd, int ingest_threa
     q_in.finish();
   });
   auto gpu_thread = [&](int slot) {
-    otg_ctx* ctx = nullptr;
-    const bool need_gpu = !J.j->reads_only || J.fasta;
-    if (need_gpu && !(ctx = pool_acquire(device))) { J.fail(OTG_ERR_NO_DEVICE, "otg_create: " + last_err()); q_in.abort(); return; }
+    PooledCtx ctx(nullptr, PoolReturn{device});
+    const bool need_gpu = !j.reads_only || A.fasta;
+    if (need_gpu && !(ctx = acquire_ctx(device))) { J.fail(OTG_ERR_NO_DEVICE, "otg_create: " + last_err()); q_in.abort(); return; }
     std::vector<otg_region_result> rr; std::vector<otg_allele> al; std::vector<uint8_t> seqs;
     try {
       BatchPtr b;
       while (J.rc.load() == OTG_OK && q_in.pop(b)) {
-        const int rc = run_batch(J, ctx, *b, rr, al, seqs, &ms_gpu[slot], &ms_emit[slot]);
-        if (rc != OTG_OK) { J.fail(rc, "hot path: " + (ctx && otg_last_error(ctx) ? std::string(otg_last_error(ctx)) : last_err())); q_in.abort(); break; }
-        {
-          // Back-pressure: the writer drains the shards strictly in order, so a shard it has not reached yet may hold back `cap` finished
-          // batches and no more (host memory stays bounded by the batch size, not by the shard).  The batch the writer wants next always
-          // gets in — the threads of a shard finish out of order, and that batch may be the last one to arrive.
-          std::unique_lock<std::mutex> lk(out.m);
-          while (!(out.ready.size() < out.cap || b->index == out.next || J.rc.load() != OTG_OK)) out.cv.wait_for(lk, std::chrono::milliseconds(50));
-          out.ready.emplace(b->index, std::move(b->text));
-        }
-        out.cv.notify_all();
+        const int rc = run_batch(A, ctx.get(), *b, rr, al, seqs, &ms_gpu[slot], &ms_emit[slot]);
+        if (rc != OTG_OK) { J.fail(rc, "hot path: " + (ctx && otg_last_error(ctx.get()) ? ctx_err(ctx.get()) : last_err())); q_in.abort(); break; }
+        out.deliver(b->index, std::move(b->text));
         recycled.put(std::move(b));
       }
     } catch (const std::exception& e) { J.fail(OTG_ERR_ARG, std::string("hot path: ") + e.what()); }
     if (J.rc.load() != OTG_OK) q_in.abort();               // whatever stopped the job: release the ingest thread
-    if (ctx) pool_release(device, ctx);
   };
   std::vector<std::thread> gts;
   for (int t = 0; t < n_gpu_threads; ++t) gts.emplace_back(gpu_thread, t);
   ingest.join();
   for (auto& t : gts) t.join();
-  out.cv.notify_all();
+  out.wake();
   std::lock_guard<std::mutex> lk(J.st_m);
   J.st.ms_ingest += ms_ingest;
   for (int t = 0; t < n_gpu_threads; ++t) { J.st.ms_hot_path += ms_gpu[t]; J.st.ms_emit += ms_emit[t]; }
 }
 
+// ---- the VCF lines of a batch (output_vcf_line, src/genotype.cpp:43-78, is a pure function of its region): contiguous slices of its n
+// regions, starting at BED record `first_bed`, formatted on up to `threads` host threads into `parts` and concatenated in order into `text`.
+// `first` (n + 1 entries), `n_gt` are the batch's; alleles, seqs, gt, hsd, reps are indexed by what `first` holds.  On failure *err is the
+// failing slice's error text, which only the slice's own thread can read.
+int emit_vcf_sliced(const Bed& bed, uint32_t first_bed, uint32_t n, const uint32_t* first, const otg_allele* alleles, const uint8_t* seqs, uint32_t n_samples, const int32_t* gt,
+                    const double* hsd, const int32_t* n_gt, const int32_t* reps, int32_t offset_l, int32_t offset_r, int threads, std::vector<std::string>& parts, std::string& text,
+                    std::string* err)
+{
+  const uint32_t nslice = (uint32_t)std::max(1, std::min<int>(threads, (int)((n + 31) / 32)));
+  parts.assign(nslice, std::string());
+  std::vector<int> prc(nslice, OTG_OK);
+  std::vector<std::string> perr(nslice);
+  auto emit_slice = [&](uint32_t sidx) {
+    const uint32_t a = (uint32_t)((uint64_t)n * sidx / nslice), e = (uint32_t)((uint64_t)n * (sidx + 1) / nslice);
+    std::string& out = parts[sidx];
+    uint64_t bytes = (uint64_t)(e - a) * (512 + 80ull * (n_samples + 1));
+    for (uint32_t i = first[a]; i < first[e]; ++i) bytes += alleles[i].seq_len + 8;          // every allele sequence could be an ALT
+    uint64_t len = 0;
+    int rc = OTG_ERR_CAPACITY;
+    // (the estimate above is an upper bound: the second round, with the size the first one reported, is a safety net)
+    for (int round = 0; round < 2 && rc == OTG_ERR_CAPACITY; ++round, bytes = len) {
+      out.resize(bytes);
+      rc = otg_emit_vcf_lines(bed.beds.data() + first_bed + a, bed.chr_arena.data(), e - a, first + a, alleles, seqs, n_samples, gt, hsd, n_gt + a, reps, offset_l, offset_r,
+                              bytes ? &out[0] : nullptr, bytes, &len);
+    }
+    if (rc != OTG_OK) perr[sidx] = last_err();
+    prc[sidx] = rc;
+    out.resize(rc == OTG_OK ? len : 0);
+  };
+  if (nslice == 1) emit_slice(0);
+  else {
+    std::vector<std::thread> th;
+    for (uint32_t sidx = 0; sidx < nslice; ++sidx) th.emplace_back(emit_slice, sidx);
+    for (auto& t : th) t.join();
+  }
+  text.clear();
+  for (uint32_t sidx = 0; sidx < nslice; ++sidx) {
+    if (prc[sidx] != OTG_OK) { if (err) *err = perr[sidx]; return prc[sidx]; }
+    text += parts[sidx];
+  }
+  return OTG_OK;
+}
 
 // ---- the cohort dispatcher (otg_cohort_files): per device shard, per batch, per sample: ingest -> hot path -> otg_cohort_stage; the thread that
 // stages the last sample of a batch regroups, clusters, collects and formats it.
 struct CohortText { std::string vcf; std::vector<std::string> sam; };
-struct CohortOut {
-  std::mutex m;
-  std::condition_variable cv;
-  std::map<uint32_t, CohortText> ready;     // batch index -> texts
-  uint32_t n_batches = 0, next = 0;
-  size_t cap = 3;
-};
 struct CohortRef {                           // reference alleles of one batch (genotype_process, src/genotype.cpp:93-101), fetched once
   std::vector<uint8_t> arena; std::vector<uint64_t> off; std::vector<uint32_t> len;
 };
@@ -400,9 +530,10 @@ struct CohortSlot {                          // one batch being staged on a devi
 };
 struct CohortShared {
   const otg_cohort_job* j = nullptr;
-  Job M;                                     // BED, FASTA, job status and statistics
-  std::vector<std::unique_ptr<Job>> S;       // per sample: what ingest_batch reads (BAM handle, its otg_assemble_job)
-  std::vector<otg_assemble_job> aj;
+  Job M;                                     // job status and statistics
+  Bed bed;
+  FastaPtr fasta;
+  std::vector<BamPtr> bams;                  // one per sample
   otg_params P;
   uint32_t n_samples = 0;
 };
@@ -412,13 +543,13 @@ int fetch_reference_alleles(const CohortShared& C, uint32_t first, uint32_t n, C
   R.arena.clear(); R.off.assign(n, 0); R.len.assign(n, 0);
   std::vector<char> buf;
   for (uint32_t g = 0; g < n; ++g) {
-    const otg_bed& bd = C.M.beds[first + g];
+    const otg_bed& bd = C.bed.beds[first + g];
     const int fb = (int)(uint32_t)bd.start - C.j->ingest.offset_l, fe = (int)(uint32_t)bd.end + C.j->ingest.offset_r - 1;
     uint64_t need = 0;
     buf.resize((size_t)(fe >= fb ? (long long)fe - fb + 2 : 2) + 16);
-    if (otg_fasta_fetch(C.M.fasta, C.M.chr_arena.data() + bd.chr_off, bd.chr_len, fb, fe, buf.data(), buf.size(), &need) != OTG_OK) {
+    if (otg_fasta_fetch(C.fasta.get(), C.bed.chr_arena.data() + bd.chr_off, bd.chr_len, fb, fe, buf.data(), buf.size(), &need) != OTG_OK) {
       buf.resize((size_t)need + 16);
-      if (otg_fasta_fetch(C.M.fasta, C.M.chr_arena.data() + bd.chr_off, bd.chr_len, fb, fe, buf.data(), buf.size(), &need) != OTG_OK) return OTG_ERR_ARG;
+      if (otg_fasta_fetch(C.fasta.get(), C.bed.chr_arena.data() + bd.chr_off, bd.chr_len, fb, fe, buf.data(), buf.size(), &need) != OTG_OK) return OTG_ERR_ARG;
     }
     R.off[g] = R.arena.size(); R.len[g] = (uint32_t)need;
     R.arena.insert(R.arena.end(), (const uint8_t*)buf.data(), (const uint8_t*)buf.data() + need);
@@ -443,41 +574,16 @@ int cohort_finish_batch(CohortShared& C, otg_ctx* cctx, const Batch& b, const Co
   if (rc != OTG_OK) return rc;
   *ms_gpu += ms_since(t0);
   t0 = Clock::now();
-  // VCF lines: slices of the batch's regions on host threads, as otg_genotype_files formats them
-  const uint32_t nslice = (uint32_t)std::max(1, std::min<int>(threads, (int)((n + 31) / 32)));
-  std::vector<std::string> parts(nslice);
-  std::vector<int> prc(nslice, OTG_OK);
-  auto emit_slice = [&](uint32_t sidx) {
-    const uint32_t a = (uint32_t)((uint64_t)n * sidx / nslice), e = (uint32_t)((uint64_t)n * (sidx + 1) / nslice);
-    std::string& out = parts[sidx];
-    uint64_t bytes = (uint64_t)(e - a) * (512 + 80ull * (C.n_samples + 1));
-    for (uint32_t i = first[a]; i < first[e]; ++i) bytes += alleles[i].seq_len + 8;
-    out.resize(bytes);
-    uint64_t len = 0;
-    int r2 = otg_emit_vcf_lines(C.M.beds.data() + b.first + a, C.M.chr_arena.data(), e - a, first.data() + a, alleles.data(), seqs.data(), C.n_samples, gt.data(), hsd.data(),
-                                ngt.data() + a, reps.data(), C.j->ingest.offset_l, C.j->ingest.offset_r, bytes ? &out[0] : nullptr, bytes, &len);
-    if (r2 == OTG_ERR_CAPACITY) {
-      out.resize(len);
-      r2 = otg_emit_vcf_lines(C.M.beds.data() + b.first + a, C.M.chr_arena.data(), e - a, first.data() + a, alleles.data(), seqs.data(), C.n_samples, gt.data(), hsd.data(),
-                              ngt.data() + a, reps.data(), C.j->ingest.offset_l, C.j->ingest.offset_r, len ? &out[0] : nullptr, len, &len);
-    }
-    prc[sidx] = r2;
-    out.resize(r2 == OTG_OK ? len : 0);
-  };
-  if (nslice == 1) emit_slice(0);
-  else {
-    std::vector<std::thread> th;
-    for (uint32_t sidx = 0; sidx < nslice; ++sidx) th.emplace_back(emit_slice, sidx);
-    for (auto& t : th) t.join();
-  }
-  text.clear();
-  for (uint32_t sidx = 0; sidx < nslice; ++sidx) { if (prc[sidx] != OTG_OK) return prc[sidx]; text += parts[sidx]; }
+  std::vector<std::string> parts;
+  rc = emit_vcf_sliced(C.bed, b.first, n, first.data(), alleles.data(), seqs.data(), C.n_samples, gt.data(), hsd.data(), ngt.data(), reps.data(), C.j->ingest.offset_l,
+                       C.j->ingest.offset_r, threads, parts, text, nullptr);
+  if (rc != OTG_OK) return rc;
   for (uint32_t r = 0; r < n; ++r) if (first[r + 1] > first[r]) ++*n_ok;
   *ms_emit += ms_since(t0);
   return OTG_OK;
 }
 
-void cohort_shard_worker(CohortShared& C, int device, uint32_t a, uint32_t bnd, int ingest_threads, CohortOut& out)
+void cohort_shard_worker(CohortShared& C, int device, uint32_t a, uint32_t bnd, int ingest_threads, OrderedOutput<CohortText>& out)
 {
   if (a >= bnd) return;
   Job& M = C.M;
@@ -487,7 +593,7 @@ void cohort_shard_worker(CohortShared& C, int device, uint32_t a, uint32_t bnd, 
   const int n_gpu_threads = dispatch_contexts();
   BoundedQueue<CohortItem> q_in((size_t)n_gpu_threads);
   BatchPool& recycled = g_batches;
-  { std::lock_guard<std::mutex> lk(out.m); out.cap = (size_t)n_gpu_threads + 1; }
+  out.set_cap((size_t)n_gpu_threads + 1);
   CohortSlot slots[2];
   for (int i = 0; i < 2; ++i) {
     slots[i].next = i;
@@ -507,7 +613,7 @@ void cohort_shard_worker(CohortShared& C, int device, uint32_t a, uint32_t bnd, 
           it.b = recycled.get(); it.sample = s; it.ref = ref;
           it.b->index = idx; it.b->first = plan[idx].first; it.b->n = plan[idx].second;
           const auto t0 = Clock::now();
-          const int rc = ingest_batch(*C.S[s], *it.b, ingest_threads);
+          const int rc = ingest_batch(C.bams[s].get(), C.fasta.get(), C.bed, C.j->ingest, false, C.P.flank, *it.b, ingest_threads);
           ms_ingest += ms_since(t0);
           trace("ingest", idx, it.b->n, t0);
           if (rc != OTG_OK) { M.fail(rc, std::string("ingest of ") + C.j->bam_paths[s] + ": " + last_err()); stop = true; break; }
@@ -520,38 +626,30 @@ void cohort_shard_worker(CohortShared& C, int device, uint32_t a, uint32_t bnd, 
     q_in.finish();
   });
   auto gpu_thread = [&](int slot_idx) {
-    otg_ctx* ctx = pool_acquire(device);
+    const PooledCtx pooled = acquire_ctx(device);
+    otg_ctx* ctx = pooled.get();
     if (!ctx) { M.fail(OTG_ERR_NO_DEVICE, "otg_create: " + last_err()); q_in.abort(); return; }
     std::vector<otg_region_result> rr; std::vector<otg_allele> al; std::vector<uint8_t> seqs;
-    auto fail_ctx = [&](int rc, const char* what, otg_ctx* c) { M.fail(rc, std::string(what) + ": " + (c && otg_last_error(c) && otg_last_error(c)[0] ? std::string(otg_last_error(c)) : last_err())); q_in.abort(); };
+    auto fail_ctx = [&](int rc, const char* what, otg_ctx* c) { M.fail(rc, std::string(what) + ": " + (c && otg_last_error(c) && otg_last_error(c)[0] ? ctx_err(c) : last_err())); q_in.abort(); };
     try {
       CohortItem it;
       while (M.rc.load() == OTG_OK && q_in.pop(it)) {
         Batch& b = *it.b;
         const uint32_t idx = b.index, s = it.sample;
         auto t0 = Clock::now();
-        int rc = otg_assemble_submit(ctx, &C.P, b.arena.data(), b.arena_used, b.reads.data(), b.n_reads, b.regions.data(), b.n);
-        if (rc == OTG_OK) rc = otg_assemble_run(ctx);
         uint32_t na = 0; uint64_t sb = 0;
-        if (rc == OTG_OK) rc = otg_assemble_result_sizes(ctx, &na, &sb);
+        int rc = hot_path_on(ctx, C.P, b, &na, &sb);
         if (rc != OTG_OK) { fail_ctx(rc, "hot path", ctx); break; }
-        trace("run", idx, b.n, t0);
         ms_gpu[slot_idx] += ms_since(t0);
         std::string sam;
         if (want_sam) {
           // the records `otter assemble -R <name>` prints for this sample and batch (otg_assemble_files' text)
           t0 = Clock::now();
-          rr.resize(b.n); al.resize((size_t)na + 1); seqs.resize((size_t)sb + 64);
-          rc = otg_assemble_collect(ctx, rr.data(), al.data(), (uint32_t)al.size(), seqs.data(), seqs.size(), nullptr);
+          rc = collect_on(ctx, b, na, sb, rr, al, seqs);
           if (rc != OTG_OK) { fail_ctx(rc, "collect", ctx); break; }
           ms_gpu[slot_idx] += ms_since(t0);
           t0 = Clock::now();
-          uint64_t need = 0;
-          rc = otg_emit_alleles(M.beds.data() + b.first, M.chr_arena.data(), b.n, rr.data(), al.data(), seqs.data(), C.j->sample_names[s], 0, nullptr, 0, &need);
-          if (rc == OTG_OK || rc == OTG_ERR_CAPACITY) {
-            sam.resize(need);
-            rc = otg_emit_alleles(M.beds.data() + b.first, M.chr_arena.data(), b.n, rr.data(), al.data(), seqs.data(), C.j->sample_names[s], 0, sam.empty() ? nullptr : &sam[0], sam.size(), &need);
-          }
+          rc = alleles_text(C.bed, b, rr, al, seqs, C.j->sample_names[s], 0, sam);
           if (rc != OTG_OK) { fail_ctx(rc, "emit", nullptr); break; }
           ms_emit[slot_idx] += ms_since(t0);
         }
@@ -592,23 +690,16 @@ void cohort_shard_worker(CohortShared& C, int device, uint32_t a, uint32_t bnd, 
         sl.cv.notify_all();
         recycled.put(std::move(it.b));
         it.ref.reset();
-        if (finished) {
-          std::unique_lock<std::mutex> lk(out.m);
-          while (!(out.ready.size() < out.cap || idx == out.next || M.rc.load() != OTG_OK)) out.cv.wait_for(lk, std::chrono::milliseconds(50));
-          out.ready.emplace(idx, std::move(done));
-          lk.unlock();
-          out.cv.notify_all();
-        }
+        if (finished) out.deliver(idx, std::move(done));
       }
     } catch (const std::exception& e) { M.fail(OTG_ERR_ARG, std::string("hot path: ") + e.what()); }
     if (M.rc.load() != OTG_OK) { q_in.abort(); for (auto& sl : slots) sl.cv.notify_all(); }
-    pool_release(device, ctx);
   };
   std::vector<std::thread> gts;
   for (int t = 0; t < n_gpu_threads; ++t) gts.emplace_back(gpu_thread, t);
   ingest.join();
   for (auto& t : gts) t.join();
-  out.cv.notify_all();
+  out.wake();
   for (auto& sl : slots) otg_destroy(sl.ctx);
   std::lock_guard<std::mutex> lk(M.st_m);
   M.st.ms_ingest += ms_ingest;
@@ -625,94 +716,44 @@ int otg_assemble_files(const otg_assemble_job* job, otg_write_fn write, void* us
   if (job->n_devices < 0 || (job->n_devices > 0 && !job->devices)) return otg_fail(nullptr, OTG_ERR_ARG, "otg_assemble_files: bad device list");
   const auto t_all = Clock::now();
   g_trace_t0 = t_all;
-  Job J;
-  J.j = job;
-  // BED file (size protocol: first call reports the needed sizes)
-  {
-    uint32_t n = 0, skipped = 0; uint64_t cu = 0;
-    int rc = otg_parse_bed_file(job->bed_path, nullptr, 0, &n, nullptr, 0, &cu, &skipped);
-    if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) return rc;
-    J.beds.resize((size_t)n + 1); J.chr_arena.resize((size_t)cu + 16);
-    rc = otg_parse_bed_file(job->bed_path, J.beds.data(), (uint32_t)J.beds.size(), &n, J.chr_arena.data(), J.chr_arena.size(), &cu, &skipped);
-    if (rc != OTG_OK) return rc;
-    J.beds.resize(n);
-    J.st.n_regions = n;
-  }
-  int rc = otg_bam_open(job->bam_path, &J.bam);
+  AssembleShared A;
+  A.j = job;
+  Job& J = A.J;
+  int rc = load_bed(job->bed_path, A.bed);
+  if (rc != OTG_OK) return rc;
+  const uint32_t R = (uint32_t)A.bed.beds.size();
+  J.st.n_regions = R;
+  rc = open_bam(job->bam_path, A.bam);
   if (rc != OTG_OK) return rc;
   if (job->fasta_path && job->fasta_path[0]) {
-    rc = otg_fasta_open(job->fasta_path, &J.fasta);
-    if (rc != OTG_OK) { otg_bam_close(J.bam); return rc; }
+    rc = open_fasta(job->fasta_path, A.fasta);
+    if (rc != OTG_OK) return rc;
   }
-  auto cleanup = [&] { if (J.fasta) otg_fasta_close(J.fasta); otg_bam_close(J.bam); };
-  // SAM header (src/assemble.cpp:167-177); FASTA output has none
+  // SAM header; FASTA output has none
   if (!job->is_fasta) {
-    const uint32_t nt = otg_bam_n_targets(J.bam);
-    std::string names; std::vector<uint64_t> off(nt), len(nt); std::vector<uint32_t> nl(nt);
-    for (uint32_t i = 0; i < nt; ++i) { uint64_t l = 0; const char* nm = otg_bam_target(J.bam, i, &l); off[i] = names.size(); nl[i] = (uint32_t)strlen(nm); len[i] = l; names += nm; }
-    uint64_t need = 0;
-    rc = otg_emit_sam_header(names.data(), off.data(), nl.data(), len.data(), nt, job->read_group ? job->read_group : "", job->ingest.offset_l, job->ingest.offset_r, nullptr, 0, &need);
-    if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) { cleanup(); return rc; }
-    std::string hdr(need, '\0');
-    rc = otg_emit_sam_header(names.data(), off.data(), nl.data(), len.data(), nt, job->read_group ? job->read_group : "", job->ingest.offset_l, job->ingest.offset_r, need ? &hdr[0] : nullptr, need, &need);
-    if (rc != OTG_OK) { cleanup(); return rc; }
-    if (write(user, hdr.data(), hdr.size()) != 0) { cleanup(); return otg_fail(nullptr, OTG_ERR_ARG, "otg_assemble_files: the writer failed"); }
+    std::string hdr;
+    rc = sam_header_text(A.bam.get(), job->read_group ? job->read_group : "", job->ingest.offset_l, job->ingest.offset_r, hdr);
+    if (rc != OTG_OK) return rc;
+    if (write(user, hdr.data(), hdr.size()) != 0) return otg_fail(nullptr, OTG_ERR_ARG, "otg_assemble_files: the writer failed");
     J.st.output_bytes += hdr.size();
   }
-  // static contiguous split over the devices (BS::thread_pool::parallelize_loop: block = total / workers, the last takes the remainder)
-  std::vector<int> devs;
-  if (job->n_devices > 0) devs.assign(job->devices, job->devices + job->n_devices); else devs.push_back(0);
-  const uint32_t R = (uint32_t)J.beds.size(), W = (uint32_t)devs.size();
-  const uint32_t block = R / W;
-  const int threads_total = job->ingest.threads > 0 ? job->ingest.threads : 1;
-  const int threads_per = std::max(1, threads_total / (int)W);
-  std::vector<std::unique_ptr<ShardOut>> outs;
-  std::vector<std::thread> workers;
-  std::vector<std::pair<uint32_t, uint32_t>> bounds;
-  for (uint32_t w = 0; w < W; ++w) {
-    const uint32_t a = block == 0 ? std::min(w, R) : w * block;
-    const uint32_t b = block == 0 ? std::min(w + 1, R) : (w == W - 1 ? R : a + block);
-    bounds.emplace_back(a, b);
-    outs.emplace_back(new ShardOut());
-    outs.back()->n_batches = (uint32_t)batch_plan(a, b, job->batch_regions).size();
-  }
-  for (uint32_t w = 0; w < W; ++w) workers.emplace_back(shard_worker, std::ref(J), devs[w], bounds[w].first, bounds[w].second, threads_per, std::ref(*outs[w]));
-  // the writer: shards in order, batches in order
-  for (uint32_t w = 0; w < W; ++w) {
-    ShardOut& o = *outs[w];
-    for (uint32_t k = 0; k < o.n_batches; ++k) {
-      std::string text;
-      {
-        std::unique_lock<std::mutex> lk(o.m);
-        o.cv.wait_for(lk, std::chrono::milliseconds(50), [&] { return o.ready.count(k) || J.rc.load() != OTG_OK; });
-        while (!o.ready.count(k) && J.rc.load() == OTG_OK) o.cv.wait_for(lk, std::chrono::milliseconds(50));
-        if (!o.ready.count(k)) break;
-        text = std::move(o.ready[k]);
-        o.ready.erase(k);
-        o.next = k + 1;
-      }
-      o.cv.notify_all();                    // room for the shard's hot-path threads
-      const auto tw = Clock::now();
-      if (!text.empty() && write(user, text.data(), text.size()) != 0) { J.fail(OTG_ERR_ARG, "the writer failed"); break; }
-      trace("write", k, (uint32_t)(text.size() >> 10), tw);
-      J.st.output_bytes += text.size();
-    }
-    if (J.rc.load() != OTG_OK) break;
-  }
-  for (auto& t : workers) t.join();
-  cleanup();
-  pool_trim(devs);
+  J.st.n_devices = run_shards<std::string>(
+      J, job->devices, job->n_devices, R, job->batch_regions, job->ingest.threads,
+      [&](int device, uint32_t a, uint32_t b, int threads, OrderedOutput<std::string>& out) { shard_worker(A, device, a, b, threads, out); },
+      [&](uint32_t k, const std::string& text) {
+        const auto tw = Clock::now();
+        if (!text.empty() && write(user, text.data(), text.size()) != 0) { J.fail(OTG_ERR_ARG, "the writer failed"); return false; }
+        trace("write", k, (uint32_t)(text.size() >> 10), tw);
+        J.st.output_bytes += text.size();
+        return true;
+      });
   trace("job", 0, R, t_all);
   J.st.ms_total = ms_since(t_all);
-  J.st.n_devices = W;
   if (stats) *stats = J.st;
   if (J.rc.load() != OTG_OK) return otg_fail(nullptr, J.rc.load(), "otg_assemble_files: %s", J.err.c_str());
   return OTG_OK;
 }
 
-// ---- `otter genotype` from files to text in one call: genotype() / genotype_process() (src/genotype.cpp:69-192).  Regions in bounded
-// batches: allele ingest (host threads) -> anallele_cluster on the device -> VCF lines (or, without a reference, the two-length table),
-// text in BED order.  The reference's worker loop does the same region by region on a thread pool and prints under a mutex.
 // `otter compare` from files to text — compare() (src/compare.cpp:68-150).  Two batches in flight: while the pairs of one are aligned on the
 // device and emitted, the next one is ingested (both BAMs) on a host thread.
 int otg_compare_files(const otg_compare_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
@@ -721,32 +762,26 @@ int otg_compare_files(const otg_compare_job* job, otg_write_fn write, void* user
     return otg_fail(nullptr, OTG_ERR_ARG, "otg_compare_files: NULL job, writer, BAM or BED path");
   const auto t_all = Clock::now();
   otg_job_stats st{};
-  std::vector<otg_bed> beds; std::vector<char> chr_arena;
-  {
-    uint32_t n = 0, skipped = 0; uint64_t cu = 0;
-    int rc = otg_parse_bed_file(job->bed_path, nullptr, 0, &n, nullptr, 0, &cu, &skipped);
-    if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) return rc;
-    beds.resize((size_t)n + 1); chr_arena.resize((size_t)cu + 16);
-    rc = otg_parse_bed_file(job->bed_path, beds.data(), (uint32_t)beds.size(), &n, chr_arena.data(), chr_arena.size(), &cu, &skipped);
-    if (rc != OTG_OK) return rc;
-    beds.resize(n);
-    st.n_regions = n;
-  }
-  otg_bam* bt = nullptr; otg_bam* bq = nullptr; otg_ctx* ctx = nullptr;
-  int rc = otg_bam_open(job->truth_bam_path, &bt);
+  Bed bed;
+  int rc = load_bed(job->bed_path, bed);
   if (rc != OTG_OK) return rc;
-  rc = otg_bam_open(job->query_bam_path, &bq);
-  if (rc != OTG_OK) { otg_bam_close(bt); return rc; }
-  auto cleanup = [&] { if (ctx) pool_release(job->device, ctx); otg_bam_close(bq); otg_bam_close(bt); };
+  const std::vector<otg_bed>& beds = bed.beds; const std::vector<char>& chr_arena = bed.chr_arena;
+  st.n_regions = (uint32_t)beds.size();
+  BamPtr bt, bq;
+  rc = open_bam(job->truth_bam_path, bt);
+  if (rc != OTG_OK) return rc;
+  rc = open_bam(job->query_bam_path, bq);
+  if (rc != OTG_OK) return rc;
   // sample2index (src/compare.cpp:77-88): the first read group of each BAM (SampleIndex::init)
   std::string s0, s1;
   for (int side = 0; side < 2; ++side) {
-    otg_bam* b = side ? bq : bt;
+    otg_bam* b = side ? bq.get() : bt.get();
     rc = otg_bam_sample_index(b, nullptr, nullptr, nullptr);
-    if (rc != OTG_OK) { cleanup(); return rc; }
+    if (rc != OTG_OK) return rc;
     (side ? s1 : s0) = otg_bam_sample(b, 0);
   }
-  if (!(ctx = pool_acquire(job->device))) { cleanup(); return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_compare_files: %s", last_err().c_str()); }
+  const PooledCtx ctx = acquire_ctx(job->device);
+  if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_compare_files: %s", last_err().c_str());
   const uint32_t per = job->batch_regions ? job->batch_regions : 1024u;
   const int threads = job->threads > 0 ? job->threads : 1;
   struct Side {
@@ -755,7 +790,6 @@ int otg_compare_files(const otg_compare_job* job, otg_write_fn write, void* user
     uint32_t na = 0, ns = 0; uint64_t used = 0;
   };
   struct CmpBatch { Side side[2]; uint32_t f = 0, n = 0; int rc = OTG_OK; double ms = 0; std::string err; };
-  CmpBatch bufs[2];
   auto ingest_into = [&](CmpBatch& B, uint32_t f) {
     B.f = f; B.n = std::min<uint32_t>(per, (uint32_t)beds.size() - f);
     const auto t0 = Clock::now();
@@ -768,7 +802,7 @@ int otg_compare_files(const otg_compare_job* job, otg_write_fn write, void* user
       for (int attempt = 0; attempt < 4; ++attempt) {
         S.alleles.resize(cap_al); S.arena.resize(cap_ar); S.sp.resize(cap_sp); S.warn.resize(cap_w);
         S.na = 0; S.used = 0; S.ns = 0; uint64_t wl = 0;
-        B.rc = otg_ingest_compare_alleles(side ? bq : bt, s0.c_str(), s1.c_str(), side ? 0 : 1, beds.data() + f, chr_arena.data(), B.n, threads,
+        B.rc = otg_ingest_compare_alleles(side ? bq.get() : bt.get(), s0.c_str(), s1.c_str(), side ? 0 : 1, beds.data() + f, chr_arena.data(), B.n, threads,
                                           S.arena.data(), S.arena.size(), &S.used, S.alleles.data(), (uint32_t)S.alleles.size(), &S.na, S.first.data(),
                                           S.sp.data(), (uint32_t)S.sp.size(), &S.ns, S.sp_first.data(), &S.warn[0], S.warn.size(), &wl);
         if (B.rc != OTG_ERR_CAPACITY) { S.warn.resize(B.rc == OTG_OK ? wl : 0); break; }
@@ -784,14 +818,12 @@ int otg_compare_files(const otg_compare_job* job, otg_write_fn write, void* user
   std::string text, wtext;
   const uint32_t n_beds = (uint32_t)beds.size();
   auto emit_warn = [&](const std::string& w) { return w.empty() || !job->warn || job->warn(job->warn_user, w.data(), w.size()) == 0; };
-  if (n_beds) ingest_into(bufs[0], 0);
-  for (uint32_t f = 0, idx = 0; f < n_beds; f += per, ++idx) {
-    CmpBatch& B = bufs[idx & 1];
-    if (B.rc != OTG_OK) { rc = B.rc; const std::string e = B.err; cleanup(); return otg_fail(nullptr, rc, "otg_compare_files: %s", e.c_str()); }
-    std::thread next;
-    if (f + per < n_beds) next = std::thread([&, f, idx] { ingest_into(bufs[(idx + 1) & 1], f + per); });
-    struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{next};
-    auto join_next = [&] { if (next.joinable()) next.join(); };
+  TwoInFlight<CmpBatch> flight;
+  if (n_beds) ingest_into(flight.current(), 0);
+  for (uint32_t f = 0; f < n_beds; f += per, flight.advance()) {
+    const CmpBatch& B = flight.current();
+    if (B.rc != OTG_OK) return otg_fail(nullptr, B.rc, "otg_compare_files: %s", B.err.c_str());
+    if (f + per < n_beds) flight.prefetch([&, f](CmpBatch& N) { ingest_into(N, f + per); });
     const Side& T = B.side[0]; const Side& Q = B.side[1];
     const uint32_t n = B.n;
     st.ms_ingest += B.ms; st.n_alleles += T.na + Q.na; st.input_bytes += T.used + Q.used;
@@ -825,8 +857,8 @@ int otg_compare_files(const otg_compare_job* job, otg_write_fn write, void* user
     scores.assign(tasks.size(), 0); clen.assign(tasks.size(), 0);
     if (!tasks.empty()) {
       uint64_t used = 0;
-      rc = otg_edit_align_batch(ctx, seqs.data(), seqs.size(), tasks.data(), (uint32_t)tasks.size(), scores.data(), nullptr, clen.data(), nullptr, 0, &used);
-      if (rc != OTG_OK) { const std::string e = otg_last_error(ctx) ? otg_last_error(ctx) : ""; join_next(); cleanup(); return otg_fail(nullptr, rc, "otg_compare_files: %s", e.c_str()); }
+      rc = otg_edit_align_batch(ctx.get(), seqs.data(), seqs.size(), tasks.data(), (uint32_t)tasks.size(), scores.data(), nullptr, clen.data(), nullptr, 0, &used);
+      if (rc != OTG_OK) return otg_fail(nullptr, rc, "otg_compare_files: %s", ctx_err(ctx.get()).c_str());
     }
     pedit.assign(pair_task.size(), 0.0); pops.assign(pair_task.size(), 0.0);
     for (size_t p = 0; p < pair_task.size(); ++p)
@@ -834,25 +866,22 @@ int otg_compare_files(const otg_compare_job* job, otg_write_fn write, void* user
     st.n_reads += tasks.size();
     st.ms_hot_path += ms_since(t0);
     t0 = Clock::now();
-    uint64_t need = 0, wneed = 0;
+    uint64_t wneed = 0;
     otg_compare_counts cc{};
-    rc = otg_compare_emit(beds.data() + f, chr_arena.data(), n, T.first.data(), T.alleles.data(), T.arena.data(), T.sp_first.data(), T.sp.data(),
-                          Q.first.data(), Q.alleles.data(), Q.arena.data(), pair_first.data(), pedit.data(), pops.data(), nullptr, 0, &need, nullptr, 0, &wneed, &cc);
-    if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) { join_next(); cleanup(); return rc; }
-    text.resize(need); wtext.resize(wneed);
-    rc = otg_compare_emit(beds.data() + f, chr_arena.data(), n, T.first.data(), T.alleles.data(), T.arena.data(), T.sp_first.data(), T.sp.data(),
-                          Q.first.data(), Q.alleles.data(), Q.arena.data(), pair_first.data(), pedit.data(), pops.data(), need ? &text[0] : nullptr, need, &need,
-                          wneed ? &wtext[0] : nullptr, wneed, &wneed, &cc);
-    if (rc != OTG_OK) { join_next(); cleanup(); return rc; }
+    rc = sized_text(text, [&](char* buf, uint64_t cap, uint64_t* need) {
+      wtext.resize(wneed);                  // the warnings go by the same protocol: empty on the sizing call, then the size that call reported
+      return otg_compare_emit(beds.data() + f, chr_arena.data(), n, T.first.data(), T.alleles.data(), T.arena.data(), T.sp_first.data(), T.sp.data(),
+                              Q.first.data(), Q.alleles.data(), Q.arena.data(), pair_first.data(), pedit.data(), pops.data(), buf, cap, need,
+                              wneed ? &wtext[0] : nullptr, wneed, &wneed, &cc);
+    });
+    if (rc != OTG_OK) return rc;
     st.ms_emit += ms_since(t0);
     st.n_regions_ok += cc.n_compared;
     st.n_regions_skipped += cc.skip_many_truth + cc.skip_one_truth + cc.skip_no_truth + cc.skip_no_query;
-    if (!emit_warn(T.warn) || !emit_warn(Q.warn) || !emit_warn(wtext)) { join_next(); cleanup(); return otg_fail(nullptr, OTG_ERR_ARG, "otg_compare_files: the warning writer failed"); }
-    if (!text.empty() && write(user, text.data(), text.size()) != 0) { join_next(); cleanup(); return otg_fail(nullptr, OTG_ERR_ARG, "otg_compare_files: the writer failed"); }
+    if (!emit_warn(T.warn) || !emit_warn(Q.warn) || !emit_warn(wtext)) return otg_fail(nullptr, OTG_ERR_ARG, "otg_compare_files: the warning writer failed");
+    if (!text.empty() && write(user, text.data(), text.size()) != 0) return otg_fail(nullptr, OTG_ERR_ARG, "otg_compare_files: the writer failed");
     st.output_bytes += text.size();
-    join_next();
   }
-  cleanup();
   st.ms_total = ms_since(t_all); st.n_devices = 1;
   if (stats) *stats = st;
   return OTG_OK;
@@ -870,19 +899,15 @@ int otg_vcf2mat_files(const otg_vcf2mat_job* job, otg_write_fn write, void* user
   otg_job_stats st{};
   {
     // parse_bed_file (src/vcf2mat.cpp:50-51): required, filters nothing
-    uint32_t n = 0, skipped = 0; uint64_t cu = 0;
-    int rc = otg_parse_bed_file(job->bed_path, nullptr, 0, &n, nullptr, 0, &cu, &skipped);
-    if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) return rc;
-    std::vector<otg_bed> beds((size_t)n + 1); std::vector<char> chr((size_t)cu + 16);
-    rc = otg_parse_bed_file(job->bed_path, beds.data(), (uint32_t)beds.size(), &n, chr.data(), chr.size(), &cu, &skipped);
-    if (rc != OTG_OK) return rc;
+    Bed bed;
+    const int rb = load_bed(job->bed_path, bed);
+    if (rb != OTG_OK) return rb;
   }
-  otg_vcf* vcf = nullptr;
-  int rc = otg_vcf_open(job->vcf_path, &vcf);
+  VcfPtr vcf;
+  int rc = open_vcf(job->vcf_path, vcf);
   if (rc != OTG_OK) return rc;
-  otg_ctx* ctx = pool_acquire(job->device);
-  if (!ctx) { otg_vcf_close(vcf); return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_vcf2mat_files: %s", last_err().c_str()); }
-  auto cleanup = [&] { pool_release(job->device, ctx); otg_vcf_close(vcf); };
+  const PooledCtx ctx = acquire_ctx(job->device);
+  if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_vcf2mat_files: %s", last_err().c_str());
   const uint64_t bins = (1ull << (2 * k)) + 1;
   // alleles per batch: at most 1 GiB of rows on the host and what the device workspace of otg_kmer_usage_batch holds (k >= 8: + u32 histograms)
   const uint64_t dev_row = bins * 8 + (k >= 8 ? bins * 4 : 0);
@@ -893,13 +918,11 @@ int otg_vcf2mat_files(const otg_vcf2mat_job* job, otg_write_fn write, void* user
     std::vector<otg_vcf_record> rec; std::vector<char> regions; std::vector<uint64_t> off; std::vector<uint32_t> len; std::vector<uint8_t> seqs;
     uint32_t nr = 0, na = 0; uint64_t ru = 0, au = 0, bytes = 0; int rc = OTG_OK; double ms = 0; std::string err;
   };
-  VBatch bufs[2];
-  for (auto& B : bufs) { B.rec.resize(per); B.off.resize(per); B.len.resize(per); B.regions.resize(1 << 20); B.seqs.resize(64ull << 20); }
   auto read_into = [&](VBatch& B) {
     const auto t0 = Clock::now();
     B.bytes = 0;
     for (;;) {
-      B.rc = otg_vcf_read_alleles(vcf, B.rec.data(), (uint32_t)B.rec.size(), &B.nr, B.regions.data(), B.regions.size(), &B.ru, B.off.data(), B.len.data(),
+      B.rc = otg_vcf_read_alleles(vcf.get(), B.rec.data(), (uint32_t)B.rec.size(), &B.nr, B.regions.data(), B.regions.size(), &B.ru, B.off.data(), B.len.data(),
                                   (uint32_t)B.off.size(), &B.na, B.seqs.data(), B.seqs.size(), &B.au, &B.bytes);
       if (B.rc != OTG_ERR_CAPACITY) break;
       // one record larger than the buffers: grow them to hold it (its alleles may exceed `per`; the device call then reports the workspace)
@@ -912,20 +935,20 @@ int otg_vcf2mat_files(const otg_vcf2mat_job* job, otg_write_fn write, void* user
   };
   std::vector<double> usage, gc, hsd;
   std::vector<std::string> parts((size_t)threads);
-  read_into(bufs[0]);
-  for (uint32_t idx = 0;; ++idx) {
-    VBatch& B = bufs[idx & 1];
+  TwoInFlight<VBatch> flight;
+  for (VBatch& B : flight) { B.rec.resize(per); B.off.resize(per); B.len.resize(per); B.regions.resize(1 << 20); B.seqs.resize(64ull << 20); }
+  read_into(flight.current());
+  for (;; flight.advance()) {
+    VBatch& B = flight.current();
     st.ms_ingest += B.ms; st.input_bytes += B.bytes;
-    if (B.rc != OTG_OK) { rc = B.rc; const std::string e = B.err; cleanup(); return otg_fail(nullptr, rc, "otg_vcf2mat_files: %s", e.c_str()); }
+    if (B.rc != OTG_OK) return otg_fail(nullptr, B.rc, "otg_vcf2mat_files: %s", B.err.c_str());
     if (B.nr == 0) break;
-    std::thread next([&, idx] { read_into(bufs[(idx + 1) & 1]); });
-    struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{next};
-    auto join_next = [&] { if (next.joinable()) next.join(); };
+    flight.prefetch(read_into);
     st.n_regions += B.nr; st.n_alleles += B.na;
     auto t0 = Clock::now();
     usage.resize((size_t)B.na * bins); gc.resize(B.na); hsd.resize(B.na);
-    rc = otg_kmer_usage_batch(ctx, B.seqs.data(), B.au, B.off.data(), B.len.data(), B.na, k, usage.data(), gc.data(), hsd.data());
-    if (rc != OTG_OK) { const std::string e = otg_last_error(ctx) ? otg_last_error(ctx) : ""; join_next(); cleanup(); return otg_fail(nullptr, rc, "otg_vcf2mat_files: %s", e.c_str()); }
+    rc = otg_kmer_usage_batch(ctx.get(), B.seqs.data(), B.au, B.off.data(), B.len.data(), B.na, k, usage.data(), gc.data(), hsd.data());
+    if (rc != OTG_OK) return otg_fail(nullptr, rc, "otg_vcf2mat_files: %s", ctx_err(ctx.get()).c_str());
     st.ms_hot_path += ms_since(t0);
     t0 = Clock::now();
     // the rows of contiguous record ranges with about equal allele counts, one range per thread, written in file order
@@ -946,54 +969,44 @@ int otg_vcf2mat_files(const otg_vcf2mat_job* job, otg_write_fn write, void* user
     }
     st.ms_emit += ms_since(t0);
     for (int t = 0; t < threads; ++t) {
-      if (!parts[t].empty() && write(user, parts[t].data(), parts[t].size()) != 0) {
-        join_next(); cleanup(); return otg_fail(nullptr, OTG_ERR_ARG, "otg_vcf2mat_files: the writer failed");
-      }
+      if (!parts[t].empty() && write(user, parts[t].data(), parts[t].size()) != 0) return otg_fail(nullptr, OTG_ERR_ARG, "otg_vcf2mat_files: the writer failed");
       st.output_bytes += parts[t].size();
     }
-    join_next();
   }
-  cleanup();
   st.ms_total = ms_since(t_all); st.n_devices = 1; st.n_regions_ok = st.n_regions;
   if (stats) *stats = st;
   return OTG_OK;
 }
 
+// ---- `otter genotype` from files to text in one call: genotype() / genotype_process() (src/genotype.cpp:69-192).  Regions in bounded
+// batches: allele ingest (host threads) -> anallele_cluster on the device -> VCF lines (or, without a reference, the two-length table),
+// text in BED order.  The reference's worker loop does the same region by region on a thread pool and prints under a mutex.
 int otg_genotype_files(const otg_genotype_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
 {
   if (!job || !write || !job->bam_path || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "otg_genotype_files: NULL job, writer, BAM or BED path");
   const auto t_all = Clock::now();
   otg_job_stats st{};
-  std::vector<otg_bed> beds; std::vector<char> chr_arena;
-  {
-    uint32_t n = 0, skipped = 0; uint64_t cu = 0;
-    int rc = otg_parse_bed_file(job->bed_path, nullptr, 0, &n, nullptr, 0, &cu, &skipped);
-    if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) return rc;
-    beds.resize((size_t)n + 1); chr_arena.resize((size_t)cu + 16);
-    rc = otg_parse_bed_file(job->bed_path, beds.data(), (uint32_t)beds.size(), &n, chr_arena.data(), chr_arena.size(), &cu, &skipped);
-    if (rc != OTG_OK) return rc;
-    beds.resize(n);
-    st.n_regions = n;
-  }
-  otg_bam* bam = nullptr; otg_fasta* fasta = nullptr; otg_ctx* ctx = nullptr;
-  int rc = otg_bam_open(job->bam_path, &bam);
+  Bed bed;
+  int rc = load_bed(job->bed_path, bed);
   if (rc != OTG_OK) return rc;
-  auto cleanup = [&] { if (ctx) pool_release(job->device, ctx); if (fasta) otg_fasta_close(fasta); otg_bam_close(bam); };
+  const std::vector<otg_bed>& beds = bed.beds; const std::vector<char>& chr_arena = bed.chr_arena;
+  st.n_regions = (uint32_t)beds.size();
+  BamPtr bam; FastaPtr fasta;
+  PooledCtx ctx(nullptr, PoolReturn{job->device});
+  rc = open_bam(job->bam_path, bam);
+  if (rc != OTG_OK) return rc;
   uint32_t n_samples = 0; int32_t ol = 0, orr = 0;
-  rc = otg_bam_sample_index(bam, &n_samples, &ol, &orr);                      // SampleIndex::init (src/anbamdb.cpp:42-63)
-  if (rc != OTG_OK) { cleanup(); return rc; }
+  rc = otg_bam_sample_index(bam.get(), &n_samples, &ol, &orr);                // SampleIndex::init (src/anbamdb.cpp:42-63)
+  if (rc != OTG_OK) return rc;
   const bool with_ref = job->fasta_path && job->fasta_path[0];
   if (with_ref) {
-    rc = otg_fasta_open(job->fasta_path, &fasta);
-    if (rc != OTG_OK) { cleanup(); return rc; }
-    if (!(ctx = pool_acquire(job->device))) { cleanup(); return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_genotype_files: %s", last_err().c_str()); }
-    uint64_t need = 0;
-    rc = otg_emit_vcf_header(bam, nullptr, 0, &need);                        // output_vcf_header (src/genotype.cpp:16-40)
-    if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) { cleanup(); return rc; }
-    std::string hdr(need, '\0');
-    rc = otg_emit_vcf_header(bam, need ? &hdr[0] : nullptr, need, &need);
-    if (rc != OTG_OK) { cleanup(); return rc; }
-    if (write(user, hdr.data(), hdr.size()) != 0) { cleanup(); return otg_fail(nullptr, OTG_ERR_ARG, "otg_genotype_files: the writer failed"); }
+    rc = open_fasta(job->fasta_path, fasta);
+    if (rc != OTG_OK) return rc;
+    if (!(ctx = acquire_ctx(job->device))) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_genotype_files: %s", last_err().c_str());
+    std::string hdr;
+    rc = sized_text(hdr, [&](char* buf, uint64_t cap, uint64_t* need) { return otg_emit_vcf_header(bam.get(), buf, cap, need); });   // output_vcf_header (src/genotype.cpp:16-40)
+    if (rc != OTG_OK) return rc;
+    if (write(user, hdr.data(), hdr.size()) != 0) return otg_fail(nullptr, OTG_ERR_ARG, "otg_genotype_files: the writer failed");
     st.output_bytes += hdr.size();
   }
   const uint32_t per = job->batch_regions ? job->batch_regions : 1024u;
@@ -1005,7 +1018,6 @@ int otg_genotype_files(const otg_genotype_job* job, otg_write_fn write, void* us
     std::vector<uint8_t> arena; std::vector<otg_allele> alleles; std::vector<uint32_t> first;
     uint32_t f = 0, n = 0, na = 0; uint64_t used = 0; int rc = OTG_OK; double ms = 0; std::string err;
   };
-  GtBatch bufs[2];
   auto ingest_into = [&](GtBatch& B, uint32_t f) {
     B.f = f; B.n = std::min<uint32_t>(per, (uint32_t)beds.size() - f);
     B.first.assign((size_t)B.n + 1, 0);
@@ -1014,7 +1026,7 @@ int otg_genotype_files(const otg_genotype_job* job, otg_write_fn write, void* us
     for (int attempt = 0; attempt < 4; ++attempt) {
       B.alleles.resize(cap_al); B.arena.resize(cap_ar);
       B.na = 0; B.used = 0;
-      B.rc = otg_ingest_alleles(bam, beds.data() + f, chr_arena.data(), B.n, threads, fasta, B.arena.data(), B.arena.size(), &B.used, B.alleles.data(), (uint32_t)B.alleles.size(), &B.na, B.first.data());
+      B.rc = otg_ingest_alleles(bam.get(), beds.data() + f, chr_arena.data(), B.n, threads, fasta.get(), B.arena.data(), B.arena.size(), &B.used, B.alleles.data(), (uint32_t)B.alleles.size(), &B.na, B.first.data());
       if (B.rc != OTG_ERR_CAPACITY) break;
       cap_al = (size_t)B.na + 64; cap_ar = (size_t)B.used + 4096;
     }
@@ -1026,19 +1038,16 @@ int otg_genotype_files(const otg_genotype_job* job, otg_write_fn write, void* us
   std::string text;
   std::vector<std::string> parts;
   const uint32_t n_beds = (uint32_t)beds.size();
-  if (n_beds) ingest_into(bufs[0], 0);
-  for (uint32_t f = 0, idx = 0; f < n_beds; f += per, ++idx) {
-    GtBatch& B = bufs[idx & 1];
-    if (B.rc != OTG_OK) { rc = B.rc; const std::string e = B.err; cleanup(); return otg_fail(nullptr, rc, "otg_genotype_files: %s", e.c_str()); }
-    std::thread next;
-    const bool overlap = with_ref && f + per < n_beds;            // (the two-length table without -r reads the BAM handle's sample list while it formats: kept in sequence)
-    if (overlap) next = std::thread([&, f, idx] { ingest_into(bufs[(idx + 1) & 1], f + per); });
-    auto join_next = [&] { if (next.joinable()) next.join(); };       // before every return: the ingest thread writes into bufs[] and reads the handles cleanup() closes
-    struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{next};
+  TwoInFlight<GtBatch> flight;
+  if (n_beds) ingest_into(flight.current(), 0);
+  for (uint32_t f = 0; f < n_beds; f += per, flight.advance()) {
+    GtBatch& B = flight.current();
+    if (B.rc != OTG_OK) return otg_fail(nullptr, B.rc, "otg_genotype_files: %s", B.err.c_str());
+    const bool more = f + per < n_beds;
+    if (more && with_ref) flight.prefetch([&, f](GtBatch& N) { ingest_into(N, f + per); });
     const uint32_t n = B.n, na = B.na; const uint64_t used = B.used;
     std::vector<uint32_t>& first = B.first; std::vector<otg_allele>& alleles = B.alleles; std::vector<uint8_t>& arena = B.arena;
     st.ms_ingest += B.ms; st.n_reads += na; st.input_bytes += used;
-    uint64_t need = 0;
     auto t0 = Clock::now();
     if (with_ref) {
       seq_off.resize(na); seq_len.resize(na); n_al.resize(n);
@@ -1047,64 +1056,29 @@ int otg_genotype_files(const otg_genotype_job* job, otg_write_fn write, void* us
       gt.resize((size_t)na + 1); gtl.resize((size_t)na + 1); gtk.resize((size_t)na + 1); reps.resize((size_t)na + 1); hsd.resize((size_t)na + 1); ngt.resize((size_t)n + 1);
       if (arena.size() < used + 64) arena.resize(used + 64);
       if (na) {
-        rc = otg_genotype_cluster_batch(ctx, &job->params, arena.data(), used + 64, seq_off.data(), seq_len.data(), first.data(), n_al.data(), n,
+        rc = otg_genotype_cluster_batch(ctx.get(), &job->params, arena.data(), used + 64, seq_off.data(), seq_len.data(), first.data(), n_al.data(), n,
                                         gt.data(), gtl.data(), gtk.data(), hsd.data(), ngt.data(), reps.data());      // anallele_cluster (src/genotype.cpp:138)
-        if (rc != OTG_OK) { const std::string e = otg_last_error(ctx) ? otg_last_error(ctx) : ""; join_next(); cleanup(); return otg_fail(nullptr, rc, "otg_genotype_files: %s", e.c_str()); }
+        if (rc != OTG_OK) return otg_fail(nullptr, rc, "otg_genotype_files: %s", ctx_err(ctx.get()).c_str());
       } else std::fill(ngt.begin(), ngt.end(), 0);
       st.ms_hot_path += ms_since(t0);
       t0 = Clock::now();
-      // VCF lines: slices of the batch's regions on host threads (output_vcf_line, src/genotype.cpp:43-78, is a pure function of its region)
-      const uint32_t nslice = (uint32_t)std::max(1, std::min<int>(threads, (int)((n + 31) / 32)));
-      parts.assign(nslice, std::string());
-      std::vector<int> prc(nslice, OTG_OK);
-      std::vector<std::string> perr(nslice);
-      auto emit_slice = [&](uint32_t sidx) {
-        const uint32_t a = (uint32_t)((uint64_t)n * sidx / nslice), e = (uint32_t)((uint64_t)n * (sidx + 1) / nslice);
-        std::string& out = parts[sidx];
-        uint64_t bytes = 0;
-        for (uint32_t r = a; r < e; ++r) bytes += 512 + 80ull * (n_samples + 1);
-        for (uint32_t i = first[a]; i < first[e]; ++i) bytes += alleles[i].seq_len + 8;          // every allele sequence could be an ALT
-        out.resize(bytes);
-        uint64_t len = 0;
-        int r2 = otg_emit_vcf_lines(beds.data() + f + a, chr_arena.data(), e - a, first.data() + a, alleles.data(), arena.data(), n_samples, gt.data(), hsd.data(), ngt.data() + a,
-                                    reps.data(), ol, orr, bytes ? &out[0] : nullptr, bytes, &len);
-        if (r2 == OTG_ERR_CAPACITY) {         // (the estimate above is an upper bound; kept as a safety net)
-          out.resize(len);
-          r2 = otg_emit_vcf_lines(beds.data() + f + a, chr_arena.data(), e - a, first.data() + a, alleles.data(), arena.data(), n_samples, gt.data(), hsd.data(), ngt.data() + a,
-                                  reps.data(), ol, orr, len ? &out[0] : nullptr, len, &len);
-        }
-        if (r2 != OTG_OK) perr[sidx] = last_err();
-        prc[sidx] = r2;
-        out.resize(r2 == OTG_OK ? len : 0);
-      };
-      if (nslice == 1) emit_slice(0);
-      else {
-        std::vector<std::thread> th;
-        for (uint32_t sidx = 0; sidx < nslice; ++sidx) th.emplace_back(emit_slice, sidx);
-        for (auto& t : th) t.join();
-      }
-      text.clear();
-      for (uint32_t sidx = 0; sidx < nslice; ++sidx) {
-        if (prc[sidx] != OTG_OK) { rc = prc[sidx]; const std::string e = perr[sidx]; join_next(); cleanup(); return otg_fail(nullptr, rc, "otg_genotype_files: %s", e.c_str()); }
-        text += parts[sidx];
-      }
-      rc = OTG_OK;
+      std::string err;
+      rc = emit_vcf_sliced(bed, f, n, first.data(), alleles.data(), arena.data(), n_samples, gt.data(), hsd.data(), ngt.data(), reps.data(), ol, orr, threads, parts, text, &err);
+      if (rc != OTG_OK) return otg_fail(nullptr, rc, "otg_genotype_files: %s", err.c_str());
     } else {
-      rc = otg_emit_genotype_lengths(bam, beds.data() + f, chr_arena.data(), n, first.data(), alleles.data(), n_samples, nullptr, 0, &need);   // src/genotype.cpp:112-121
-      if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) { cleanup(); return rc; }
-      text.resize(need);
-      rc = otg_emit_genotype_lengths(bam, beds.data() + f, chr_arena.data(), n, first.data(), alleles.data(), n_samples, need ? &text[0] : nullptr, need, &need);
+      rc = sized_text(text, [&](char* buf, uint64_t cap, uint64_t* need) {                                                     // src/genotype.cpp:112-121
+        return otg_emit_genotype_lengths(bam.get(), beds.data() + f, chr_arena.data(), n, first.data(), alleles.data(), n_samples, buf, cap, need);
+      });
+      if (rc != OTG_OK) return rc;
     }
-    if (rc != OTG_OK) { join_next(); cleanup(); return rc; }
     st.ms_emit += ms_since(t0);
     for (uint32_t r = 0; r < n; ++r) { if (first[r + 1] > first[r]) ++st.n_regions_ok; }
     st.n_alleles += na;
-    if (!text.empty() && write(user, text.data(), text.size()) != 0) { join_next(); cleanup(); return otg_fail(nullptr, OTG_ERR_ARG, "otg_genotype_files: the writer failed"); }
+    if (!text.empty() && write(user, text.data(), text.size()) != 0) return otg_fail(nullptr, OTG_ERR_ARG, "otg_genotype_files: the writer failed");
     st.output_bytes += text.size();
-    if (next.joinable()) next.join();
-    if (!overlap && f + per < n_beds) ingest_into(bufs[(idx + 1) & 1], f + per);
+    // (the two-length table without -r reads the BAM handle's sample list while it formats: there the next batch is ingested in sequence)
+    if (more && !with_ref) ingest_into(flight.other(), f + per);
   }
-  cleanup();
   st.ms_total = ms_since(t_all); st.n_devices = 1;
   if (stats) *stats = st;
   return OTG_OK;
@@ -1134,121 +1108,65 @@ int otg_cohort_files(const otg_cohort_job* job, otg_write_fn write, void* user, 
   C.j = job; C.n_samples = S;
   C.P = job->params; C.P.realign = 1;
   Job& M = C.M;
+  int rc = load_bed(job->bed_path, C.bed);
+  if (rc != OTG_OK) return rc;
+  const uint32_t R = (uint32_t)C.bed.beds.size();
+  M.st.n_regions = R;
   {
-    uint32_t n = 0, skipped = 0; uint64_t cu = 0;
-    int rc = otg_parse_bed_file(job->bed_path, nullptr, 0, &n, nullptr, 0, &cu, &skipped);
-    if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) return rc;
-    M.beds.resize((size_t)n + 1); M.chr_arena.resize((size_t)cu + 16);
-    rc = otg_parse_bed_file(job->bed_path, M.beds.data(), (uint32_t)M.beds.size(), &n, M.chr_arena.data(), M.chr_arena.size(), &cu, &skipped);
-    if (rc != OTG_OK) return rc;
-    M.beds.resize(n);
-    M.st.n_regions = n;
     // regions are identified by index here, by their chr:start-end string in the file round trip: the same string twice would differ
     std::map<std::string, uint32_t> seen;
-    for (uint32_t r = 0; r < n; ++r) {
-      const otg_bed& b = M.beds[r];
-      std::string key(M.chr_arena.data() + b.chr_off, b.chr_len);
+    for (uint32_t r = 0; r < R; ++r) {
+      const otg_bed& b = C.bed.beds[r];
+      std::string key(C.bed.chr_arena.data() + b.chr_off, b.chr_len);
       key += ":" + std::to_string((uint32_t)b.start) + "-" + std::to_string((uint32_t)b.end);
       auto ins = seen.emplace(key, r);
       if (!ins.second) return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: BED records %u and %u of %s are the same region %s", ins.first->second + 1, r + 1, job->bed_path, key.c_str());
     }
   }
-  auto cleanup = [&] { for (auto& sj : C.S) if (sj && sj->bam) otg_bam_close(sj->bam); if (M.fasta) otg_fasta_close(M.fasta); };
-  int rc = otg_fasta_open(job->fasta_path, &M.fasta);
+  rc = open_fasta(job->fasta_path, C.fasta);
   if (rc != OTG_OK) return rc;
-  C.aj.resize(S);
+  C.bams.resize(S);
   for (uint32_t s = 0; s < S; ++s) {
-    C.S.emplace_back(new Job());
-    Job& J = *C.S.back();
-    otg_assemble_job& a = C.aj[s];
-    memset(&a, 0, sizeof(a));
-    a.bam_path = job->bam_paths[s]; a.bed_path = job->bed_path; a.fasta_path = job->fasta_path; a.read_group = job->sample_names[s];
-    a.params = C.P; a.ingest = job->ingest; a.batch_regions = job->batch_regions;
-    J.j = &a; J.beds = M.beds; J.chr_arena = M.chr_arena; J.fasta = M.fasta;
-    rc = otg_bam_open(job->bam_paths[s], &J.bam);
-    if (rc != OTG_OK) { cleanup(); return rc; }
+    rc = open_bam(job->bam_paths[s], C.bams[s]);
+    if (rc != OTG_OK) return rc;
     if (s > 0) {
-      otg_bam* b0 = C.S[0]->bam;
-      bool same = otg_bam_n_targets(J.bam) == otg_bam_n_targets(b0);
+      otg_bam* b0 = C.bams[0].get(); otg_bam* bs = C.bams[s].get();
+      bool same = otg_bam_n_targets(bs) == otg_bam_n_targets(b0);
       for (uint32_t i = 0; same && i < otg_bam_n_targets(b0); ++i) {
         uint64_t l0 = 0, l1 = 0;
-        const char* n0 = otg_bam_target(b0, i, &l0); const char* n1 = otg_bam_target(J.bam, i, &l1);
+        const char* n0 = otg_bam_target(b0, i, &l0); const char* n1 = otg_bam_target(bs, i, &l1);
         same = l0 == l1 && strcmp(n0, n1) == 0;
       }
-      if (!same) { cleanup(); return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: the targets of %s differ from those of the first BAM %s", job->bam_paths[s], job->bam_paths[0]); }
+      if (!same) return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: the targets of %s differ from those of the first BAM %s", job->bam_paths[s], job->bam_paths[0]);
     }
   }
   // headers: the VCF header with the first BAM's contigs and the samples' names; per sample the SAM header of its allele records
   {
-    otg_bam* b0 = C.S[0]->bam;
+    otg_bam* b0 = C.bams[0].get();
     otg_bam_set_samples(b0, job->sample_names, S, job->ingest.offset_l, job->ingest.offset_r);
-    uint64_t need = 0;
-    rc = otg_emit_vcf_header(b0, nullptr, 0, &need);
-    if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) { cleanup(); return rc; }
-    std::string hdr(need, '\0');
-    rc = otg_emit_vcf_header(b0, need ? &hdr[0] : nullptr, need, &need);
-    if (rc != OTG_OK) { cleanup(); return rc; }
-    if (write(user, hdr.data(), hdr.size()) != 0) { cleanup(); return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: the writer failed"); }
+    std::string hdr;
+    rc = sized_text(hdr, [&](char* buf, uint64_t cap, uint64_t* need) { return otg_emit_vcf_header(b0, buf, cap, need); });
+    if (rc != OTG_OK) return rc;
+    if (write(user, hdr.data(), hdr.size()) != 0) return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: the writer failed");
     M.st.output_bytes += hdr.size();
-    if (job->allele_write) {
-      const uint32_t nt = otg_bam_n_targets(b0);
-      std::string names; std::vector<uint64_t> off(nt), len(nt); std::vector<uint32_t> nl(nt);
-      for (uint32_t i = 0; i < nt; ++i) { uint64_t l = 0; const char* nm = otg_bam_target(b0, i, &l); off[i] = names.size(); nl[i] = (uint32_t)strlen(nm); len[i] = l; names += nm; }
-      for (uint32_t s = 0; s < S; ++s) {
-        rc = otg_emit_sam_header(names.data(), off.data(), nl.data(), len.data(), nt, job->sample_names[s], job->ingest.offset_l, job->ingest.offset_r, nullptr, 0, &need);
-        if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) { cleanup(); return rc; }
-        std::string sh(need, '\0');
-        rc = otg_emit_sam_header(names.data(), off.data(), nl.data(), len.data(), nt, job->sample_names[s], job->ingest.offset_l, job->ingest.offset_r, need ? &sh[0] : nullptr, need, &need);
-        if (rc != OTG_OK) { cleanup(); return rc; }
-        if (job->allele_write(job->allele_user, s, sh.data(), sh.size()) != 0) { cleanup(); return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: the allele writer failed"); }
-      }
+    for (uint32_t s = 0; job->allele_write && s < S; ++s) {
+      rc = sam_header_text(b0, job->sample_names[s], job->ingest.offset_l, job->ingest.offset_r, hdr);
+      if (rc != OTG_OK) return rc;
+      if (job->allele_write(job->allele_user, s, hdr.data(), hdr.size()) != 0) return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: the allele writer failed");
     }
   }
-  std::vector<int> devs;
-  if (job->n_devices > 0) devs.assign(job->devices, job->devices + job->n_devices); else devs.push_back(0);
-  const uint32_t R = (uint32_t)M.beds.size(), W = (uint32_t)devs.size();
-  const uint32_t block = R / W;
-  const int threads_total = job->ingest.threads > 0 ? job->ingest.threads : 1;
-  const int threads_per = std::max(1, threads_total / (int)W);
-  std::vector<std::unique_ptr<CohortOut>> outs;
-  std::vector<std::thread> workers;
-  std::vector<std::pair<uint32_t, uint32_t>> bounds;
-  for (uint32_t w = 0; w < W; ++w) {
-    const uint32_t a = block == 0 ? std::min(w, R) : w * block;
-    const uint32_t b = block == 0 ? std::min(w + 1, R) : (w == W - 1 ? R : a + block);
-    bounds.emplace_back(a, b);
-    outs.emplace_back(new CohortOut());
-    outs.back()->n_batches = (uint32_t)batch_plan(a, b, job->batch_regions).size();
-  }
-  for (uint32_t w = 0; w < W; ++w) workers.emplace_back(cohort_shard_worker, std::ref(C), devs[w], bounds[w].first, bounds[w].second, threads_per, std::ref(*outs[w]));
-  for (uint32_t w = 0; w < W; ++w) {
-    CohortOut& o = *outs[w];
-    for (uint32_t k = 0; k < o.n_batches; ++k) {
-      CohortText text;
-      {
-        std::unique_lock<std::mutex> lk(o.m);
-        while (!o.ready.count(k) && M.rc.load() == OTG_OK) o.cv.wait_for(lk, std::chrono::milliseconds(50));
-        if (!o.ready.count(k)) break;
-        text = std::move(o.ready[k]);
-        o.ready.erase(k);
-        o.next = k + 1;
-      }
-      o.cv.notify_all();
-      if (!text.vcf.empty() && write(user, text.vcf.data(), text.vcf.size()) != 0) { M.fail(OTG_ERR_ARG, "the writer failed"); break; }
-      M.st.output_bytes += text.vcf.size();
-      for (uint32_t s = 0; s < (uint32_t)text.sam.size(); ++s)
-        if (!text.sam[s].empty() && job->allele_write(job->allele_user, s, text.sam[s].data(), text.sam[s].size()) != 0) { M.fail(OTG_ERR_ARG, "the allele writer failed"); break; }
-      if (M.rc.load() != OTG_OK) break;
-    }
-    if (M.rc.load() != OTG_OK) break;
-  }
-  for (auto& o : outs) o->cv.notify_all();
-  for (auto& t : workers) t.join();
-  cleanup();
-  pool_trim(devs);
+  M.st.n_devices = run_shards<CohortText>(
+      M, job->devices, job->n_devices, R, job->batch_regions, job->ingest.threads,
+      [&](int device, uint32_t a, uint32_t b, int threads, OrderedOutput<CohortText>& out) { cohort_shard_worker(C, device, a, b, threads, out); },
+      [&](uint32_t, const CohortText& text) {
+        if (!text.vcf.empty() && write(user, text.vcf.data(), text.vcf.size()) != 0) { M.fail(OTG_ERR_ARG, "the writer failed"); return false; }
+        M.st.output_bytes += text.vcf.size();
+        for (uint32_t s = 0; s < (uint32_t)text.sam.size(); ++s)
+          if (!text.sam[s].empty() && job->allele_write(job->allele_user, s, text.sam[s].data(), text.sam[s].size()) != 0) { M.fail(OTG_ERR_ARG, "the allele writer failed"); return false; }
+        return true;
+      });
   trace("job", 0, R, t_all);
   M.st.ms_total = ms_since(t_all);
-  M.st.n_devices = W;
   if (stats) *stats = M.st;
   if (M.rc.load() != OTG_OK) return otg_fail(nullptr, M.rc.load(), "otg_cohort_files: %s", M.err.c_str());
   return OTG_OK;
