@@ -690,6 +690,48 @@ typedef struct otg_cohort_job {
 } otg_cohort_job;
 int otg_cohort_files(const otg_cohort_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
 
+/* ---------------------------------------------------------------------------------------------
+ * Indexed allele BAMs from the product's own SAM text.  Every writer above emits SAM text and every reader wants a
+ * coordinate-sorted BAM with its `.bai`; the reference's workflow goes through `samtools view -bh | samtools sort`, `samtools index` and
+ * `samtools merge -pco` in between.  Host code (zlib + threads), no device work.
+ *   otg_bam_sink_open    starts <bam_path>.  opts (NULL: all 0 / level -1): sort = 0 takes records in (target, position) order, unmapped last,
+ *                        and streams them out with bounded memory (an out-of-order record is refused); sort = 1 holds every record in memory
+ *                        as BAM bytes and stable-sorts them at close (ties keep input order).  threads: host threads that deflate the BGZF
+ *                        blocks (<= 1: one); level: zlib's, -1 = its default.  The file bytes depend on neither threads nor on how the
+ *                        text was cut into pieces;
+ *   otg_bam_sink_write   has the otg_write_fn signature with user = the sink: pass it as `write` to otg_assemble_files (allele and
+ *                        --reads-only SAM output) and otg_wgat, or call it from an otg_cohort_allele_write_fn with one sink per sample.
+ *                        SAM text in arbitrary pieces (a piece may end inside a line): header lines first, then records with the eleven
+ *                        mandatory fields and tags of type A, i, f, Z.  Records are byte for byte what sam_parse1 (src/sam.c:504-668) makes
+ *                        of the line: integer tags take the smallest of c C s S i I, POS 0 and a `*` CIGAR make the record unmapped the way
+ *                        it does.  The header text is `@HD VN:1.6 SO:coordinate` followed by the input's header lines (its own @HD dropped);
+ *                        the targets are the @SQ lines.  Refused (OTG_ERR_ARG, line number and reason in otg_bam_sink_error): a header line
+ *                        after the first record, fewer than eleven fields, a malformed number or CIGAR, a tag of another type, an RNAME that
+ *                        is no @SQ, SEQ / QUAL / CIGAR lengths that disagree, more than 65535 CIGAR operations, a record that ends past
+ *                        2^29 (BAI cannot index it), an out-of-order record with sort = 0.  After a refusal every later write fails with the same code
+ *                        (OTG_ERR_FATAL when the file could not be written);
+ *   otg_bam_sink_close   finishes <bam_path> (the BGZF EOF block last), writes <bam_path>.bai (binning index + 16-kb linear index, every chunk
+ *                        begin the virtual offset of a record start) and frees the sink; after a refusal it behaves like otg_bam_sink_abort
+ *                        and returns the error (its text stays in otg_last_error(NULL)).  *n_records (nullable) = records written;
+ *   otg_bam_sink_abort   removes what was written and frees the sink;
+ *   otg_bam_sink_error   the text of the sink's refusal ("" when there is none).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct otg_bam_sink otg_bam_sink;
+typedef struct otg_bam_sink_opts { int32_t sort, threads, level, reserved; } otg_bam_sink_opts;
+int  otg_bam_sink_open(const char* bam_path, const otg_bam_sink_opts* opts, otg_bam_sink** out);
+int  otg_bam_sink_write(void* sink, const char* data, uint64_t len);
+int  otg_bam_sink_close(otg_bam_sink* sink, uint64_t* n_records);
+void otg_bam_sink_abort(otg_bam_sink* sink);
+const char* otg_bam_sink_error(const otg_bam_sink* sink);
+/* The `samtools merge -pco` step: coordinate-sorted BAMs with identical target lists (per-sample allele BAMs) into one BAM + BAI.  Header:
+ * the @HD line above, the first input's @SQ lines, then every other header line of the inputs in input order, a line already present
+ * verbatim dropped.  Records are copied unchanged in a k-way merge by (target, position): ties go to the earlier input and keep file order
+ * within an input.  OTG_ERR_ARG with the offending file in otg_last_error(NULL): two @RG lines with the same ID (a sample given twice), two
+ * @PG ID:otter lines whose OF: differ, different target lists, an unsorted, damaged or truncated input (a file
+ * that does not end with the BGZF EOF block included); a refused merge leaves no <out_path> and no <out_path>.bai, stale ones included.  Every
+ * input stays open during the merge: n is bounded by the process's limit on open files.  *n_records (nullable) = records written. */
+int  otg_bam_merge(const char* const* bam_paths, uint32_t n, const char* out_path, int32_t threads, int32_t level, uint64_t* n_records);
+
 /* The dispatcher keeps its per-device contexts (and their HBM workspaces) for the next job of the process; this frees them. */
 void otg_assemble_files_release(void);
 

@@ -24,6 +24,7 @@ EXPORTS = [
     "otg_vcf2mat_emit", "otg_vcf2mat_files",
     "otg_cohort_begin", "otg_cohort_stage", "otg_cohort_regroup", "otg_cohort_genotype", "otg_cohort_result_sizes", "otg_cohort_collect",
     "otg_cohort_end", "otg_cohort_files",
+    "otg_bam_sink_open", "otg_bam_sink_write", "otg_bam_sink_close", "otg_bam_sink_abort", "otg_bam_sink_error", "otg_bam_merge",
     "otg_comm_unique_id", "otg_comm_create", "otg_comm_destroy", "otg_gather_sizes", "otg_gather_records",
 ]
 
@@ -737,6 +738,111 @@ def genotype_blocks(blk):
             np.ascontiguousarray(first[:-1], dtype=np.uint32), np.ascontiguousarray(np.diff(first.astype(np.int64)), dtype=np.uint32))
 
 
+class BamSink:
+    """otg_bam_sink: SAM text in (write(), in arbitrary pieces), coordinate-sorted BAM + BAI out at close().  sort=False takes the text in
+    coordinate order and streams it; sort=True holds the records in memory and sorts them at close.  As a context manager it closes on a
+    clean exit and removes what it wrote when the block raises.  `writer` is a callable with the otg_write_fn signature for the `sink`
+    parameter of _run_files_job."""
+
+    def __init__(self, path, sort=False, threads=1, level=-1):
+        L = load()
+        L.otg_bam_sink_open.argtypes = [C.c_char_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.otg_bam_sink_write.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.otg_bam_sink_close.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.otg_bam_sink_abort.argtypes = [C.c_void_p]
+        L.otg_bam_sink_abort.restype = None
+        L.otg_bam_sink_error.argtypes = [C.c_void_p]
+        L.otg_bam_sink_error.restype = C.c_char_p
+        opts = (C.c_int32 * 4)(int(bool(sort)), int(threads), int(level), 0)
+        h = C.c_void_p()
+        rc = L.otg_bam_sink_open(path.encode(), opts, C.byref(h))
+        if rc != 0:
+            raise OtterGpuError("otg_bam_sink_open failed (%d): %s" % (rc, _err(L)))
+        self._h, self._L, self.path, self.n_records = h, L, path, None
+
+    @property
+    def error(self):
+        """the text of the sink's refusal ("" when there is none)"""
+        return (self._L.otg_bam_sink_error(self._h) or b"").decode(errors="replace") if self._h else ""
+
+    def writer(self, _user, data, n):
+        return self._L.otg_bam_sink_write(self._h, data, n)
+
+    def write(self, data):
+        data = bytes(data)
+        rc = self._L.otg_bam_sink_write(self._h, data, len(data))
+        if rc != 0:
+            raise OtterGpuError("otg_bam_sink_write failed (%d): %s" % (rc, self.error))
+
+    def close(self):
+        """finishes the BAM and its index -> the number of records; after a refusal removes both and raises"""
+        if not self._h:
+            return self.n_records
+        n = C.c_uint64(0)
+        h, self._h = self._h, None
+        rc = self._L.otg_bam_sink_close(h, C.byref(n))
+        if rc != 0:
+            raise OtterGpuError("otg_bam_sink_close failed (%d): %s" % (rc, _err(self._L)))
+        self.n_records = int(n.value)
+        return self.n_records
+
+    def abort(self):
+        if self._h:
+            h, self._h = self._h, None
+            self._L.otg_bam_sink_abort(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, *a):
+        if exc_type is None:
+            self.close()
+        else:
+            self.abort()
+
+    def __del__(self):
+        try:
+            self.abort()
+        except Exception:
+            pass
+
+
+def merge_bams(paths, out, threads=1, level=-1):
+    """otg_bam_merge: coordinate-sorted BAMs with the same targets (per-sample allele BAMs) -> one BAM + BAI; returns the number of records."""
+    L = load()
+    L.otg_bam_merge.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
+    arr = (C.c_char_p * max(1, len(paths)))(*[p.encode() for p in paths])
+    n = C.c_uint64(0)
+    rc = L.otg_bam_merge(arr, len(paths), out.encode(), int(threads), int(level), C.byref(n))
+    if rc != 0:
+        raise OtterGpuError("otg_bam_merge failed (%d): %s" % (rc, _err(L)))
+    return int(n.value)
+
+
+def _into_sinks(sinks, run):
+    """run() with the BamSinks open: closes them when it returns, removes their files when it raises (the sink's own refusal, which the
+    dispatcher only sees as a failed writer, is appended to the error)."""
+    try:
+        out = run()
+    except OtterGpuError as e:
+        why = "; ".join(x.error for x in sinks if x.error)
+        for x in sinks:
+            x.abort()
+        raise OtterGpuError("%s%s" % (e, " [" + why + "]" if why else "")) from None
+    except BaseException:
+        for x in sinks:
+            x.abort()
+        raise
+    for i, x in enumerate(sinks):
+        try:
+            x.close()
+        except BaseException:
+            for y in sinks[i + 1:]:
+                y.abort()
+            raise
+    return out
+
+
 def _run_files_job(fn_name, job, job_type, callbacks=None, sink=None):
     """One otg_*_files entry point: collects what it writes and returns (text bytes, stats dict); OtterGpuError with the library's last
     error when it fails.  callbacks: {job field: (callback type, Python callable)} for the further writers a job struct carries (set on
@@ -763,9 +869,12 @@ def _run_files_job(fn_name, job, job_type, callbacks=None, sink=None):
 
 
 def assemble_files(bam, bed, fasta=None, read_group="", is_fasta=False, reads_only=False, params=None, batch_regions=0, devices=None,
-                   offset_l=1, offset_r=0, mapq=0, nonprimary=False, omit_nonspanning=False, read_quality=0.0, threads=1):
+                   offset_l=1, offset_r=0, mapq=0, nonprimary=False, omit_nonspanning=False, read_quality=0.0, threads=1, *, bam_out=None, sort=False, bam_threads=None):
     """otg_assemble_files: `otter assemble` from files to record text (the library's dispatcher, include/otter_gpu.h).
-    Returns (text bytes, stats dict)."""
+    Returns (text bytes, stats dict).  bam_out: the SAM records go into that BAM (+ .bai) through a BamSink instead (text bytes = b"");
+    sort=True for a BED that is not in coordinate order; bam_threads: the sink's deflate threads (default: `threads`)."""
+    if bam_out is not None and is_fasta:
+        raise OtterGpuError("assemble_files: bam_out takes SAM records, not is_fasta")
     job = abi.AssembleJob()
     job.bam_path = bam.encode(); job.bed_path = bed.encode(); job.fasta_path = fasta.encode() if fasta else None
     job.read_group = read_group.encode(); job.is_fasta = int(is_fasta); job.reads_only = int(reads_only)
@@ -775,7 +884,10 @@ def assemble_files(bam, bed, fasta=None, read_group="", is_fasta=False, reads_on
     devs = (C.c_int32 * len(devices))(*devices) if devices else None
     job.n_devices = len(devices) if devices else 0
     job.devices = devs
-    return _run_files_job("otg_assemble_files", job, abi.AssembleJob)
+    if bam_out is None:
+        return _run_files_job("otg_assemble_files", job, abi.AssembleJob)
+    bs = BamSink(bam_out, sort=sort, threads=threads if bam_threads is None else bam_threads)
+    return _into_sinks([bs], lambda: _run_files_job("otg_assemble_files", job, abi.AssembleJob, None, bs.writer))
 
 
 def assemble_batch_plan(n_regions, batch_regions=0):
@@ -804,10 +916,12 @@ def genotype_files(bam, bed, fasta=None, params=None, threads=1, device=0, batch
 
 
 def cohort_files(bams, names, bed, fasta, params=None, batch_regions=0, devices=None, offset_l=1, offset_r=0, mapq=0, nonprimary=False,
-                 omit_nonspanning=False, read_quality=0.0, threads=1, alleles=False):
+                 omit_nonspanning=False, read_quality=0.0, threads=1, alleles=False, *, alleles_bam=None):
     """otg_cohort_files: sample BAMs + BED + reference FASTA to one joint VCF, the alleles staying on the device between `otter assemble` and
     `otter genotype`.  Returns (VCF bytes, stats dict), and with alleles=True also the list of per-sample SAM texts (what assemble_files returns
-    for each sample with read_group = its name)."""
+    for each sample with read_group = its name).  alleles_bam: a list of paths, one per sample: the same records as BAM + BAI files."""
+    if alleles_bam is not None and len(alleles_bam) != len(bams):
+        raise OtterGpuError("cohort_files: alleles_bam has %d paths for %d samples" % (len(alleles_bam), len(bams)))
     job = abi.CohortJob()
     n = len(bams)
     pb = (C.c_char_p * max(1, n))(*[b.encode() for b in bams])
@@ -822,10 +936,14 @@ def cohort_files(bams, names, bed, fasta, params=None, batch_regions=0, devices=
     job.devices = devs
     sams = [[] for _ in range(n)]
 
+    sinks = [BamSink(p, threads=threads) for p in alleles_bam] if alleles_bam is not None else []
+
     def asink(_user, sample, data, ln):
-        sams[sample].append(C.string_at(data, ln))
-        return 0
-    text, stats = _run_files_job("otg_cohort_files", job, abi.CohortJob, {"allele_write": (abi.ALLELE_WRITE_FN, asink)} if alleles else None)
+        if alleles:
+            sams[sample].append(C.string_at(data, ln))
+        return sinks[sample].writer(None, data, ln) if sinks else 0
+    text, stats = _into_sinks(sinks, lambda: _run_files_job("otg_cohort_files", job, abi.CohortJob,
+                                                            {"allele_write": (abi.ALLELE_WRITE_FN, asink)} if alleles or sinks else None))
     if alleles:
         return text, stats, [b"".join(x) for x in sams]
     return text, stats
@@ -836,21 +954,30 @@ def assemble_files_release():
     load().otg_assemble_files_release()
 
 
-def wgat(bam, regions, read_group="", fasta=False, offset_l=1, offset_r=0):
-    """otg_wgat: `otter wgat` on an open Bam handle; regions = list of (chr, start, end) or the (beds, chr_arena) pair.  Returns the text."""
+def wgat(bam, regions, read_group="", fasta=False, offset_l=1, offset_r=0, *, bam_out=None):
+    """otg_wgat: `otter wgat` on an open Bam handle; regions = list of (chr, start, end) or the (beds, chr_arena) pair.  Returns the text and
+    the number of records.  bam_out: the SAM records go into that BAM (+ .bai) instead, sorted by the sink (text = b"")."""
     L = load()
     beds, carena = regions if isinstance(regions, tuple) else abi.make_beds(regions)
     chunks = []
+    if bam_out is not None and fasta:
+        raise OtterGpuError("wgat: bam_out takes SAM records, not fasta")
+    bs = BamSink(bam_out, sort=True) if bam_out is not None else None
 
     def sink(_user, data, n):
         chunks.append(C.string_at(data, n))
         return 0
-    cb = abi.WRITE_FN(sink)
+    cb = abi.WRITE_FN(bs.writer if bs else sink)
     nrec = C.c_uint64(0)
     L.otg_wgat.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint32, C.c_char_p, C.c_int, C.c_int32, C.c_int32, abi.WRITE_FN, C.c_void_p, C.POINTER(C.c_uint64)]
     rc = L.otg_wgat(bam._h, abi.ptr(beds), abi.ptr(carena, C.c_char_p), C.c_uint32(len(beds)), read_group.encode(), int(fasta), offset_l, offset_r, cb, None, C.byref(nrec))
     if rc != 0:
-        raise OtterGpuError("otg_wgat failed (%d): %s" % (rc, _err(L)))
+        why = bs.error if bs else ""
+        if bs:
+            bs.abort()
+        raise OtterGpuError("otg_wgat failed (%d): %s%s" % (rc, _err(L), " [" + why + "]" if why else ""))
+    if bs:
+        bs.close()
     return b"".join(chunks), int(nrec.value)
 
 

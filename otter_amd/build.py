@@ -8,6 +8,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libotter_gpu.so")
 SOURCES = ["otg_api.hip", "wfa_edit.hip", "edit_align.hip", "myers_edit.hip", "wfa_affine.hip", "wfa_affine_reg.hip", "wfa_adaptive.hip", "cluster.hip", "poa.hip", "pipeline.hip", "emit.hip", "compare.hip", "kmer_usage.hip", "vcf2mat.hip", "ingest.hip", "bedfa.hip", "dispatch.hip", "gather.hip", "cohort.hip"]
+# host-only sources (no device code; each also builds alone, without the rest of the library): the BAM + BAI writer and merge
+HOST_SOURCES = ["bam_sink.cpp"]
 # -ffp-contract=off: the reference's clustering decisions are FP64 comparisons made without FMA
 # contraction; fused operations are written explicitly where glibc uses them.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
@@ -33,7 +35,8 @@ TOOL_SRC = os.path.join(HERE, "..", "tools", "otter_assemble.cpp")
 TOOL = os.path.join(HERE, "..", "tools", "otter_assemble")
 TOOLS = [(TOOL_SRC, TOOL), (os.path.join(HERE, "..", "tools", "otter_compare.cpp"), os.path.join(HERE, "..", "tools", "otter_compare")),
          (os.path.join(HERE, "..", "tools", "otter_vcf2mat.cpp"), os.path.join(HERE, "..", "tools", "otter_vcf2mat")),
-         (os.path.join(HERE, "..", "tools", "otter_cohort.cpp"), os.path.join(HERE, "..", "tools", "otter_cohort"))]
+         (os.path.join(HERE, "..", "tools", "otter_cohort.cpp"), os.path.join(HERE, "..", "tools", "otter_cohort")),
+         (os.path.join(HERE, "..", "tools", "otter_merge.cpp"), os.path.join(HERE, "..", "tools", "otter_merge"))]
 
 
 def build_tool(force=False):
@@ -54,14 +57,14 @@ def build(force=False, verbose=False, jobs=4):
     objs = []
     procs = []
     os.makedirs(os.path.join(CSRC, "build"), exist_ok=True)
-    for src in SOURCES:
+    for src in SOURCES + HOST_SOURCES:
         path = os.path.join(CSRC, src)
-        obj = os.path.join(CSRC, "build", src.replace(".hip", ".o"))
+        obj = os.path.join(CSRC, "build", os.path.splitext(src)[0] + ".o")
         objs.append(obj)
         headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".inc"))] + [os.path.join(HERE, "..", "include", "otter_gpu.h")]
         if (not force) and os.path.exists(obj) and os.path.getmtime(obj) > max([os.path.getmtime(path)] + [os.path.getmtime(h) for h in headers]):
             continue
-        cmd = [cc] + FLAGS + os.environ.get("OTG_EXTRA_HIPCC_FLAGS", "").split() + ["-c", path, "-o", obj]      # (measurement builds: -DOTG_REG_TIMING, ...)
+        cmd = [cc] + (FLAGS if src in SOURCES else FLAGS[1:]) + os.environ.get("OTG_EXTRA_HIPCC_FLAGS", "").split() + ["-c", path, "-o", obj]      # (measurement builds: -DOTG_REG_TIMING, ...)
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))

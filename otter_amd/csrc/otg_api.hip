@@ -18,6 +18,9 @@ int otg_fail(otg_ctx* ctx, int code, const char* fmt, ...)
   return code;
 }
 
+// bam_sink.cpp is built without the rest of the library in stand-alone programs; inside the library its refusals reach otg_last_error(NULL) here
+extern "C" void otg_set_global_error(const char* msg) { g_otg_err = msg ? msg : ""; }
+
 std::mutex& otg_device_mutex(int device)
 {
   static std::mutex m[64];

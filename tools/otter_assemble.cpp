@@ -3,7 +3,9 @@
 // SAM or FASTA records on stdout, in BED order.
 //   otter_assemble -b regions.bed -R sample [-r ref.fa] [--fasta] [--reads-only] [--haps] [-p] [-l] [-o L[,R]] [-a N] [-m Q] [-q RQ] [-c COV]
 //                  [-F f] [-A len,f] [-e err] [-h bw[,len,bw]] [-f flank] [-s sim] [-t threads] [--batch N] [--gpus 0,1,..]
-//                  [--wfa-heuristic none|wfadaptive[:min_wavefront_length,max_distance_threshold,steps]] <BAM>
+//                  [--wfa-heuristic none|wfadaptive[:min_wavefront_length,max_distance_threshold,steps]] [--bam OUT.bam [--sort]] <BAM>
+// --bam writes the SAM records as an indexed BAM (OUT.bam + OUT.bam.bai, otg_bam_sink) and nothing to stdout; --sort for a BED that is not in
+// coordinate order (the records are then held in memory).  Together with --fasta it is a usage error.
 // The last option has no counterpart in the reference: its aligners run whatever WFA2-lib's default heuristic is (src/assemble.cpp:49-50 never
 // calls setHeuristic*); here the default is exact alignment and `wfadaptive` (= 10,50,1) reproduces a WFA2-lib whose default is the adaptive one.
 #include <cstdio>
@@ -27,7 +29,8 @@ int main(int argc, char** argv)
   otg_assemble_job job; memset(&job, 0, sizeof job);
   otg_params_default(&job.params);
   job.ingest.offset_l = 1; job.ingest.offset_r = 0; job.ingest.threads = 1;       // --offset 1,0 and -t 1: the reference's defaults
-  std::string bed, rg, ref, bam;
+  std::string bed, rg, ref, bam, bam_out;
+  bool sort_out = false;
   std::vector<int32_t> devs;
   bool have_rg = false;
   for (int i = 1; i < argc; ++i) {
@@ -37,6 +40,8 @@ int main(int argc, char** argv)
     else if (a == "-R" || a == "--sample-name") { rg = val(); have_rg = true; }
     else if (a == "-r" || a == "--reference") ref = val();
     else if (a == "--fasta") job.is_fasta = 1;
+    else if (a == "--bam") bam_out = val();
+    else if (a == "--sort") sort_out = true;
     else if (a == "--haps") job.params.ignore_haps = 0;
     else if (a == "--reads-only") job.reads_only = 1;
     else if (a == "-p" || a == "--non-primary") job.ingest.nonprimary = 1;
@@ -69,11 +74,24 @@ int main(int argc, char** argv)
     else bam = a;
   }
   if (bam.empty() || bed.empty() || !have_rg) { fprintf(stderr, "usage: otter_assemble -b <BED> -R <sample> [options] <BAM>   ('--bed' and '--sample-name' are required)\n"); return 1; }
+  if (!bam_out.empty() && job.is_fasta) { fprintf(stderr, "usage: --bam takes SAM records: it cannot be combined with --fasta\n"); return 1; }
+  if (sort_out && bam_out.empty()) { fprintf(stderr, "usage: --sort needs --bam\n"); return 1; }
   job.bam_path = bam.c_str(); job.bed_path = bed.c_str(); job.fasta_path = ref.empty() ? nullptr : ref.c_str(); job.read_group = rg.c_str();
   job.n_devices = (int32_t)devs.size(); job.devices = devs.empty() ? nullptr : devs.data();
   otg_job_stats st;
-  const int rc = otg_assemble_files(&job, write_stdout, nullptr, &st);
+  otg_bam_sink* sink = nullptr;
+  if (!bam_out.empty()) {
+    otg_bam_sink_opts so; memset(&so, 0, sizeof so);
+    so.sort = sort_out ? 1 : 0; so.threads = job.ingest.threads; so.level = -1;
+    if (otg_bam_sink_open(bam_out.c_str(), &so, &sink) != OTG_OK) { fprintf(stderr, "[ERROR] %s\n", otg_last_error(nullptr)); return 1; }
+  }
+  int rc = sink ? otg_assemble_files(&job, otg_bam_sink_write, sink, &st) : otg_assemble_files(&job, write_stdout, nullptr, &st);
   fflush(stdout);
+  if (sink) {
+    const std::string job_err = rc != OTG_OK ? otg_last_error(nullptr) : "", why = otg_bam_sink_error(sink);
+    if (rc != OTG_OK) { otg_bam_sink_abort(sink); fprintf(stderr, "[ERROR] otter_assemble failed (%d): %s%s%s\n", rc, job_err.c_str(), why.empty() ? "" : ": ", why.c_str()); return 1; }
+    rc = otg_bam_sink_close(sink, nullptr);
+  }
   if (rc != OTG_OK) { fprintf(stderr, "[ERROR] otter_assemble failed (%d): %s\n", rc, otg_last_error(nullptr)); return 1; }
   fprintf(stderr, "otter_assemble: %llu regions (%llu with alleles), %llu reads, %llu alleles, %.1f MB out; %.3f s wall = %.0f regions/s on %u GPU(s); stage busy ms: ingest %.0f, hot path %.0f, emit %.0f\n",
           (unsigned long long)st.n_regions, (unsigned long long)st.n_regions_ok, (unsigned long long)st.n_reads, (unsigned long long)st.n_alleles, st.output_bytes / 1e6,

@@ -2,9 +2,9 @@
 // `otter genotype` over their alleles in one pass (otg_cohort_files), the alleles never leaving the device in between.  Host C++ only.
 //   otter_cohort -b regions.bed -r ref.fa [the assemble options of otter_assemble: --haps -p -l -o L[,R] -a N -m Q -q RQ -c COV -F f -A len,f -e err
 //                -h bw[,len,bw] -f flank -s sim -t threads --batch N --gpus 0,1,.. --wfa-heuristic ..] [-E gt-max-error] [-S gt-max-cosdis]
-//                [--alleles-prefix P] NAME=reads.bam ...
+//                [--alleles-prefix P [--alleles-bam]] NAME=reads.bam ...
 // The VCF goes to stdout.  NAME is the sample's `-R` and its VCF column.  --alleles-prefix P also writes the allele records of every sample, as
-// `otter assemble -R NAME` prints them, to P<NAME>.sam.
+// `otter assemble -R NAME` prints them, to P<NAME>.sam; with --alleles-bam to P<NAME>.bam + P<NAME>.bam.bai instead (otg_bam_sink).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -17,6 +17,11 @@ static int write_sample(void* user, uint32_t sample, const char* data, uint64_t 
 {
   FILE* f = (*(std::vector<FILE*>*)user)[sample];
   return fwrite(data, 1, (size_t)len, f) == (size_t)len ? 0 : 1;
+}
+
+static int write_sample_bam(void* user, uint32_t sample, const char* data, uint64_t len)
+{
+  return otg_bam_sink_write((*(std::vector<otg_bam_sink*>*)user)[sample], data, len);
 }
 
 static std::vector<std::string> split(const std::string& s, char c)
@@ -36,6 +41,7 @@ int main(int argc, char** argv)
   std::string bed, ref, prefix;
   std::vector<std::string> names, bams;
   std::vector<int32_t> devs;
+  bool alleles_bam = false;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     auto val = [&]() -> std::string { if (i + 1 >= argc) { fprintf(stderr, "[ERROR] %s needs a value\n", a.c_str()); exit(1); } return argv[++i]; };
@@ -44,6 +50,7 @@ int main(int argc, char** argv)
     else if (a == "-E" || a == "--gt-max-error") job.params.gt_max_error = atof(val().c_str());
     else if (a == "-S" || a == "--gt-max-cosdis") job.params.gt_max_cosdis = atof(val().c_str());
     else if (a == "--alleles-prefix") prefix = val();
+    else if (a == "--alleles-bam") alleles_bam = true;
     else if (a == "--haps") job.params.ignore_haps = 0;
     else if (a == "-p" || a == "--non-primary") job.ingest.nonprimary = 1;
     else if (a == "-l" || a == "--omit-nonspanning") job.ingest.omit_nonspanning = 1;
@@ -84,8 +91,23 @@ int main(int argc, char** argv)
   job.n_samples = (uint32_t)bams.size(); job.bam_paths = pb.data(); job.sample_names = pn.data();
   job.bed_path = bed.c_str(); job.fasta_path = ref.c_str();
   job.n_devices = (int32_t)devs.size(); job.devices = devs.empty() ? nullptr : devs.data();
+  if (alleles_bam && prefix.empty()) { fprintf(stderr, "usage: --alleles-bam needs --alleles-prefix\n"); return 1; }
   std::vector<FILE*> files;
-  if (!prefix.empty()) {
+  std::vector<otg_bam_sink*> sinks;
+  if (alleles_bam) {
+    otg_bam_sink_opts so; memset(&so, 0, sizeof so);
+    so.threads = job.ingest.threads; so.level = -1;
+    for (size_t s = 0; s < bams.size(); ++s) {
+      otg_bam_sink* k = nullptr;
+      if (otg_bam_sink_open((prefix + names[s] + ".bam").c_str(), &so, &k) != OTG_OK) {
+        fprintf(stderr, "[ERROR] %s\n", otg_last_error(nullptr));
+        for (otg_bam_sink* x : sinks) otg_bam_sink_abort(x);
+        return 1;
+      }
+      sinks.push_back(k);
+    }
+    job.allele_write = write_sample_bam; job.allele_user = &sinks;
+  } else if (!prefix.empty()) {
     for (size_t s = 0; s < bams.size(); ++s) {
       const std::string path = prefix + names[s] + ".sam";
       FILE* f = fopen(path.c_str(), "wb");
@@ -95,9 +117,19 @@ int main(int argc, char** argv)
     job.allele_write = write_sample; job.allele_user = &files;
   }
   otg_job_stats st;
-  const int rc = otg_cohort_files(&job, write_stdout, nullptr, &st);
+  int rc = otg_cohort_files(&job, write_stdout, nullptr, &st);
   fflush(stdout);
   for (FILE* f : files) fclose(f);
+  if (rc != OTG_OK) {
+    const std::string job_err = otg_last_error(nullptr);
+    std::string why;
+    for (otg_bam_sink* x : sinks) { if (why.empty()) why = otg_bam_sink_error(x); otg_bam_sink_abort(x); }
+    fprintf(stderr, "[ERROR] otter_cohort failed (%d): %s%s%s\n", rc, job_err.c_str(), why.empty() ? "" : ": ", why.c_str());
+    return 1;
+  }
+  for (size_t s = 0; s < sinks.size(); ++s) {
+    if (rc == OTG_OK) rc = otg_bam_sink_close(sinks[s], nullptr); else otg_bam_sink_abort(sinks[s]);
+  }
   if (rc != OTG_OK) { fprintf(stderr, "[ERROR] otter_cohort failed (%d): %s\n", rc, otg_last_error(nullptr)); return 1; }
   fprintf(stderr, "otter_cohort: %u samples, %llu regions (%llu with a VCF line), %llu reads, %llu alleles, %.1f MB out; %.3f s wall on %u GPU(s); stage busy ms: ingest %.0f, hot path %.0f, emit %.0f\n",
           job.n_samples, (unsigned long long)st.n_regions, (unsigned long long)st.n_regions_ok, (unsigned long long)st.n_reads, (unsigned long long)st.n_alleles, st.output_bytes / 1e6,
