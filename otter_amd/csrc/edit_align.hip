@@ -15,7 +15,7 @@
 // Provenance rule = wavefront_compute_edit_idm_piggyback (wavefront_compute_edit.c:143-190): candidates ins (k-1, +1),
 // del (k+1), misms (k, +1); max; three sequential tests ins, del, misms, the last equal one wins; then the cell is nulled
 // when h > tlen or v > plen.
-#include "otg_common.hpp"
+#include "otg_chain.hpp"
 #include <algorithm>
 #include <cstdlib>
 
@@ -225,7 +225,7 @@ int otg_launch_edit_align(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_
     jobs[i].cig_off = cig_slot ? cig_slot[i] : 0;
   }
   // chunks: consecutive tasks while the provenance + op bytes stay within the budget (a single larger task gets a chunk of its own)
-  static const uint64_t budget = getenv("OTG_EDIT_ALIGN_BUDGET_MB") ? (uint64_t)atoll(getenv("OTG_EDIT_ALIGN_BUDGET_MB")) << 20 : (uint64_t)2 << 30;
+  static const uint64_t budget = (uint64_t)otg_env_int("OTG_EDIT_ALIGN_BUDGET_MB", 2048) << 20;
   constexpr int CAP = 2048, WPB = 4;
   float ms_total = 0;
   uint32_t c0 = 0;
@@ -283,9 +283,7 @@ int otg_launch_edit_align(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_
     HIP_TRY(ctx, hipMemcpyAsync(len_out + c0, d_len + c0, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(stat.data(), d_stat + c0, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    float ms = 0;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    ms_total += ms;
+    if (int rc = otg_timer_add(ctx, &ms_total, nullptr)) return rc;
     for (uint32_t i = 0; i < n; ++i)
       if (stat[i] != scores_out[c0 + i])
         return otg_fail(ctx, OTG_ERR_FATAL, "edit alignment task %u: provenance pass failed (code %d, score %d)", c0 + i, stat[i], scores_out[c0 + i]);

@@ -43,7 +43,6 @@ struct otg_ctx {
   double last_kmer_count_ms = 0.0, last_kmer_epi_ms = 0.0;  // HIP-event times of the latest otg_kmer_usage_batch (otg_kmer_usage_last_ms)
   hipEvent_t ev2 = nullptr;                       // third timing event, created on first use (kmer_usage.hip)
   double last_kernel_ms = 0.0;                    // HIP-event time of the kernels of the latest operator-level call that reports one (otg_last_kernel_ms)
-  unsigned long long* affine_visited = nullptr;   // device counter: (score, diagonal) cells the exact gap-affine tiers visited (wfa_affine.hip)
   // aligner heuristic of the L1 calls and of the running pipeline (otg_set_heuristic / otg_params.heuristic; wfa_adaptive.hip)
   int heur_strategy = OTG_HEURISTIC_NONE, heur_min_wf_len = 10, heur_max_dist = 50, heur_steps = 1;
   // cohort staging area of otg_cohort_begin .. otg_cohort_end (cohort.hip); created on first use
@@ -65,13 +64,11 @@ int otg_fail(otg_ctx* ctx, int code, const char* fmt, ...);
 // Grow-only device allocation slot; returns nullptr on failure (error recorded).
 void* otg_slot(otg_ctx* ctx, int slot, size_t bytes);
 
-// words of SLOT_COUNTERS every aligner chain asks for (one size: the slot is never re-allocated between two chains of a batch)
-constexpr size_t OTG_COUNTER_WORDS = 160;
 // cluster.hip: regions of up to this many valid reads (assemble) / alleles (genotype) keep their clustering scratch in LDS; the callers of
 // otg_launch_cluster / otg_launch_genotype list the regions above it, which run on the wide kernels
 constexpr uint32_t OTG_CLUSTER_NMAX = 256;
 enum {
-  SLOT_ARENA = 0, SLOT_TASKS, SLOT_SCORES, SLOT_CELLS, SLOT_COUNTERS, SLOT_WF_WS, SLOT_CIG_OFF, SLOT_CIG_LEN,
+  SLOT_ARENA = 0, SLOT_TASKS, SLOT_SCORES, SLOT_CELLS, SLOT_COUNTERS /* OtgCounters, otg_chain.hpp */, SLOT_WF_WS, SLOT_CIG_OFF, SLOT_CIG_LEN,
   SLOT_CIG_ARENA, SLOT_BT_POOL, SLOT_ROWTAB, SLOT_REVOPS, SLOT_TASKSTATE, SLOT_TODO, SLOT_AUX0, SLOT_AUX1,
   SLOT_AUX2, SLOT_AUX3, SLOT_AUX4, SLOT_AUX5, SLOT_AUX6, SLOT_AUX7, SLOT_AUX8, SLOT_AUX9,
   SLOT_P0, SLOT_P1, SLOT_P2, SLOT_P3, SLOT_P4, SLOT_P5, SLOT_P6, SLOT_P7, SLOT_P8, SLOT_P9,
@@ -220,6 +217,8 @@ int otg_launch_edit_align(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_
 
 // bit-parallel edit tiers (myers_edit.hip), narrowest first: <blocks per lane, lanes per pair> = <1,8> <2,8> <3,8> <2,16> <3,16> <2,32> <2,64> <4,64>
 constexpr int OTG_MYERS_TIERS = 8;
+// register-resident gap-affine tiers (wfa_affine_reg.hpp)
+constexpr int OTG_REG_TIERS = 5;
 int otg_launch_myers(otg_ctx* ctx, int tier, const uint8_t* d_arena, const otg_align_task* d_tasks, const uint32_t* d_todo,
                      const uint32_t* d_n_todo, uint32_t n_tasks, int32_t* d_scores, uint64_t* d_cells,
                      uint32_t* ticket, uint32_t* n_overflow, uint32_t* overflow_list);

@@ -12,7 +12,7 @@
 // submit time (pairs: n(n-1)/2 per region; reassignment: n^2 per region; op strings: one slot per read),
 // the aligners consume compacted todo lists whose length stays on the device.  The host only reads back a
 // handful of scalars (POA layout totals, output sizes).
-#include "otg_common.hpp"
+#include "otg_chain.hpp"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -629,7 +629,7 @@ __global__ void K_fill_f64(double* p, size_t n, double v)
 
 static void dbg(otg_ctx* ctx, const char* what)
 {
-  if (!getenv("OTG_DEBUG")) return;
+  if (!otg_env_set("OTG_DEBUG")) return;
   hipError_t e = hipStreamSynchronize(ctx->stream);
   hipError_t e2 = hipGetLastError();
   fprintf(stderr, "[otg] %s: %s / %s\n", what, hipGetErrorString(e), hipGetErrorString(e2));
@@ -816,7 +816,7 @@ static int assemble_run_body(otg_ctx* ctx, bool realign_only)
   HIP_TRY(ctx, hipMemcpyAsync(d_reads, pl->h_reads.data(), (size_t)NR * sizeof(otg_read), hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, 64 * 8, st));
   HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, 64 * 8, st));
-  if (ctx->affine_visited) HIP_TRY(ctx, hipMemsetAsync(ctx->affine_visited, 0, 8, st));
+  if (unsigned long long* visited = otg_affine_visited(ctx)) HIP_TRY(ctx, hipMemsetAsync(visited, 0, 8, st));
   const int TB = 256;
   const uint32_t gr_reads = (NR + TB - 1) / TB, gr_regions = (NG + TB - 1) / TB;
   const uint32_t gr_blocks = std::min<uint32_t>(NG, (uint32_t)ctx->n_cu * 16);
@@ -871,7 +871,7 @@ static int assemble_run_body(otg_ctx* ctx, bool realign_only)
   // ------------------------------------------------------------------ invalid_reassignment
   {
     Timer t(ctx);
-    static const bool no_rev = getenv("OTG_NO_REASSIGN_REV") != nullptr;
+    static const bool no_rev = otg_env_set("OTG_NO_REASSIGN_REV");
     // (under the adaptive heuristic an alignment and its mirror image are different computations: no reversed copies there)
     const uint64_t rev_base = (no_rev || ctx->heur_strategy != OTG_HEURISTIC_NONE) ? 0 : pl->rev_base;
     if (rev_base) hipLaunchKernelGGL(K_reverse_reads, dim3(std::min<uint32_t>((NR + 3) / 4, (uint32_t)ctx->n_cu * 32)), dim3(256), 0, st, d_arena, d_reads, d_regions, d_rr, NR,
@@ -962,7 +962,7 @@ static int assemble_run_body(otg_ctx* ctx, bool realign_only)
   pl->stats.edit_cells = hs[0]; pl->stats.edit_seq_bytes = hs[1]; pl->stats.edit_tasks = hs[2];
   pl->stats.affine_cells = hs[4]; pl->stats.affine_seq_bytes = hs[5]; pl->stats.affine_tasks = hs[6];
   pl->stats.n_regions = NG;
-  if (ctx->affine_visited) { unsigned long long v = 0; HIP_TRY(ctx, hipMemcpy(&v, ctx->affine_visited, 8, hipMemcpyDeviceToHost)); pl->stats.affine_visited_cells = v; }
+  if (const unsigned long long* visited = otg_affine_visited(ctx)) { unsigned long long v = 0; HIP_TRY(ctx, hipMemcpy(&v, visited, 8, hipMemcpyDeviceToHost)); pl->stats.affine_visited_cells = v; }
   pl->stats.allele_bytes = pl->out_seq_bytes + 40ull * pl->out_alleles;
   pl->stats.algorithmic_bytes = pl->stats.edit_seq_bytes + 4 * pl->stats.edit_cells + pl->stats.affine_seq_bytes + 4 * pl->stats.affine_cells +
                                 (pl->stats.affine_cells + 1) / 2 + pl->stats.allele_bytes;

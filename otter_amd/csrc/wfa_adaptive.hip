@@ -31,6 +31,7 @@
 //               alignment and the 4 096 one with eight (wfa_affine_adaptive_mw_kernel: chunks dealt to the waves, one LDS barrier per score) ->
 //               byte probes 1 024 -> int32 rings in HBM.
 #include "wfa_affine_common.hpp"
+#include "otg_chain.hpp"
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
@@ -1782,40 +1783,28 @@ __global__ __launch_bounds__(NW * 64) void wfa_affine_adaptive_mw_kernel(
   }
 }
 
-int gcd3(int a, int b, int c)
-{
-  auto g2 = [](int x, int y) { while (y) { int t = x % y; x = y; y = t; } return x; };
-  return g2(g2(a, b), c);
-}
-
 } // namespace
 
 // ---------------------------------------------------------------------------------------------------
 // Launch chains.  Same contracts as otg_launch_edit_todo / otg_launch_affine_todo (which hand over to these when the context's heuristic is
-// wfadaptive).  Counters: SLOT_COUNTERS words 108..129 (free of the exact chains' words).
+// wfadaptive).  Counters: the adaptive_edit / adaptive_affine groups of SLOT_COUNTERS.
 int otg_launch_edit_adaptive_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* d_tasks, const uint32_t* d_todo,
                                   const uint32_t* d_n_todo, uint32_t n_tasks, int32_t* d_scores, uint64_t* d_cells,
                                   float* kernel_ms, uint64_t* launches)
 {
   if (n_tasks == 0) return OTG_OK;
-  if (ctx->pool[SLOT_COUNTERS].cap < OTG_COUNTER_WORDS * sizeof(uint32_t)) ctx->affine_visited = nullptr;      // (it points into this slot; the exact chain sets it up again)
-  uint32_t* cnt = (uint32_t*)otg_slot(ctx, SLOT_COUNTERS, OTG_COUNTER_WORDS * sizeof(uint32_t));
+  OtgCounters::AdaptiveEdit* const c = otg_counters(ctx, &OtgCounters::adaptive_edit);
   uint32_t* lists = (uint32_t*)otg_slot(ctx, SLOT_TODO, 5 * (size_t)n_tasks * sizeof(uint32_t));
-  if (!cnt || !lists) return OTG_ERR_HIP;
-  uint32_t* c = cnt + 108;                    // c[0..3] tickets of the first four tiers, c[4..7] lengths of their overflow lists, c[8..9] the last tier's
-  uint32_t* c16 = cnt + 128;                  // ticket and overflow length of the packed 16384-diagonal tier
-  HIP_TRY(ctx, hipMemsetAsync(c, 0, 10 * sizeof(uint32_t), ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(c16, 0, 2 * sizeof(uint32_t), ctx->stream));
+  if (!c || !lists) return OTG_ERR_HIP;
   const Heur H{ctx->heur_min_wf_len, ctx->heur_max_dist, ctx->heur_steps < 1 ? 1 : ctx->heur_steps};
   const uint32_t ncu = (uint32_t)ctx->n_cu;
   // test switch, bit t = tier t runs: 1 packed 1024, 2 packed 4096, 4 bytes 2048, 8 bytes 16384, 16 packed 16384 (eight waves per pair, behind the packed
   // 4096 one: what outgrew that went through the byte-probe tiers before); the HBM tier always runs
-  static const int only = getenv("OTG_ADAPTIVE_EDIT_TIERS") ? atoi(getenv("OTG_ADAPTIVE_EDIT_TIERS")) : 31;
+  static const int only = otg_env_int("OTG_ADAPTIVE_EDIT_TIERS", 31);
   if (kernel_ms) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  const uint32_t* in = d_todo; const uint32_t* in_n = d_n_todo; uint32_t in_imm = n_tasks;
+  OtgTodo in{d_todo, d_n_todo, n_tasks};
   uint32_t* l0 = lists; uint32_t* l1 = lists + n_tasks; uint32_t* l2 = lists + 2 * (size_t)n_tasks;
-  uint32_t* l3 = lists + 3 * (size_t)n_tasks;
-  uint32_t* l4 = lists + 4 * (size_t)n_tasks;
+  uint32_t* l3 = lists + 3 * (size_t)n_tasks; uint32_t* l4 = lists + 4 * (size_t)n_tasks;
   // words of LDS per wave for the packed pair: two reads of the batch's longest length (at most 32 KB: 2 x 32766 bases is what 16-bit offsets hold anyway)
   const int seqw = (int)std::min<size_t>(2 * (((size_t)ctx->max_seq_len + 15) / 16 + 3) + 2, 8192);
   // SLOT_WF_WS serves the first tier (a global row of 16-bit offsets per wave, for pairs that START wider than the window) and the last one (int32
@@ -1826,15 +1815,15 @@ int otg_launch_edit_adaptive_todo(otg_ctx* ctx, const uint8_t* d_arena, const ot
   const uint32_t grid0 = std::min<uint32_t>(ncu * per_cu0, (n_tasks + WPB0 - 1) / WPB0);
   const int gcap0 = (int)std::min<size_t>((2 * (size_t)ctx->max_seq_len + 128) & ~(size_t)1, 65664);      // (the tier takes pairs of two sequences below 32 767 bases: pl + tl + 72 never needs more)
   const int gcapL = (int)(2 * (size_t)ctx->max_seq_len + 4);
-  static const bool wide_start = getenv("OTG_ADAPTIVE_NO_WIDE_START") == nullptr;
+  static const bool wide_start = !otg_env_set("OTG_ADAPTIVE_NO_WIDE_START");
   const size_t need0 = (only & 1) && wide_start ? (size_t)grid0 * WPB0 * (size_t)gcap0 * sizeof(int16_t) : 0;
   const size_t needL = (size_t)ncu * WPBL * (size_t)gcapL * sizeof(int32_t);
   uint8_t* wsp = (uint8_t*)otg_slot(ctx, SLOT_WF_WS, std::max(need0, needL));
   if (!wsp) return OTG_ERR_HIP;
   if (only & 1) {       // fast tier: window of 1024 diagonals (3 KB of LDS per wave) + the packed pair
-    hipLaunchKernelGGL((wfa_edit_adaptive_lds_kernel<1024, 512, WPB0>), dim3(grid0), dim3(WPB0 * 64), dyn0, ctx->stream, d_arena, d_tasks, in, in_n, in_imm,
-                       d_scores, d_cells, c + 0, c + 4, l0, H, seqw, need0 ? (int16_t*)wsp : (int16_t*)nullptr, gcap0);
-    in = l0; in_n = c + 4; in_imm = 0;
+    hipLaunchKernelGGL((wfa_edit_adaptive_lds_kernel<1024, 512, WPB0>), dim3(grid0), dim3(WPB0 * 64), dyn0, ctx->stream, d_arena, d_tasks, in.list, in.n, in.imm,
+                       d_scores, d_cells, &c->packed1024.ticket, &c->packed1024.overflow, l0, H, seqw, need0 ? (int16_t*)wsp : (int16_t*)nullptr, gcap0);
+    in.next(l0, &c->packed1024.overflow);
   }
   if (only & 2) {       // 4096 diagonals, one wave per pair: 10 KB per wave + the packed pair.  (Measured and not kept: this window on the multi-wave kernel below —
                         // the reassignment pass sends it 437 000 pairs on the 1-10 kb shard, work enough for one wave each: 4 waves per pair 388 ms, 2 waves 363, one 322)
@@ -1842,55 +1831,47 @@ int otg_launch_edit_adaptive_todo(otg_ctx* ctx, const uint8_t* d_arena, const ot
     const size_t dyn = (size_t)WPB * seqw * 4;
     const uint32_t per_cu = std::max<uint32_t>(1, std::min<uint32_t>(8, (uint32_t)((160 * 1024) / (WPB * 10240 + dyn))));
     const uint32_t grid = std::min<uint32_t>(ncu * per_cu, (n_tasks + WPB - 1) / WPB);
-    hipLaunchKernelGGL((wfa_edit_adaptive_lds_kernel<4096, 1024, WPB>), dim3(grid), dim3(WPB * 64), dyn, ctx->stream, d_arena, d_tasks, in, in_n, in_imm,
-                       d_scores, d_cells, c + 1, c + 5, l1, H, seqw, (int16_t*)nullptr, 0);
-    in = l1; in_n = c + 5; in_imm = 0;
+    hipLaunchKernelGGL((wfa_edit_adaptive_lds_kernel<4096, 1024, WPB>), dim3(grid), dim3(WPB * 64), dyn, ctx->stream, d_arena, d_tasks, in.list, in.n, in.imm,
+                       d_scores, d_cells, &c->packed4096.ticket, &c->packed4096.overflow, l1, H, seqw, (int16_t*)nullptr, 0);
+    in.next(l1, &c->packed4096.overflow);
   }
   if (only & 16) {                       // 16384 diagonals, eight waves per pair: two rows of 32 KB, two blocks per CU
     constexpr int NW = 8;
     const size_t dyn = (size_t)seqw * 4;
     const uint32_t per_cu = std::max<uint32_t>(1, std::min<uint32_t>(2, (uint32_t)((160 * 1024) / (2 * 16384 * 2 + NW * 256 * 2 + 256 + dyn))));
     const uint32_t grid = std::min<uint32_t>(ncu * per_cu, n_tasks);
-    hipLaunchKernelGGL((wfa_edit_adaptive_mw_kernel<16384, 256, NW>), dim3(grid), dim3(NW * 64), dyn, ctx->stream, d_arena, d_tasks, in, in_n, in_imm,
-                       d_scores, d_cells, c16 + 0, c16 + 1, l4, H, seqw);
-    in = l4; in_n = c16 + 1; in_imm = 0;
+    hipLaunchKernelGGL((wfa_edit_adaptive_mw_kernel<16384, 256, NW>), dim3(grid), dim3(NW * 64), dyn, ctx->stream, d_arena, d_tasks, in.list, in.n, in.imm,
+                       d_scores, d_cells, &c->packed16384.ticket, &c->packed16384.overflow, l4, H, seqw);
+    in.next(l4, &c->packed16384.overflow);
   }
   if (only & 4) {       // byte probes (pairs with bytes outside ACGT, pairs too long to pack), 2048 diagonals
     constexpr int WPB = 2;
     const uint32_t grid = std::min<uint32_t>(ncu * 6, (n_tasks + WPB - 1) / WPB);
-    hipLaunchKernelGGL((wfa_edit_adaptive_kernel<2048, 2048, WPB>), dim3(grid), dim3(WPB * 64), 0, ctx->stream, d_arena, d_tasks, in, in_n, in_imm,
-                       d_scores, d_cells, c + 2, c + 6, l2, H, (int32_t*)nullptr, 0);
-    in = l2; in_n = c + 6; in_imm = 0;
+    hipLaunchKernelGGL((wfa_edit_adaptive_kernel<2048, 2048, WPB>), dim3(grid), dim3(WPB * 64), 0, ctx->stream, d_arena, d_tasks, in.list, in.n, in.imm,
+                       d_scores, d_cells, &c->bytes2048.ticket, &c->bytes2048.overflow, l2, H, (int32_t*)nullptr, 0);
+    in.next(l2, &c->bytes2048.overflow);
   }
   if (only & 8) {       // 16384 diagonals: 40 KB per wave
     constexpr int WPB = 1;
     const uint32_t grid = std::min<uint32_t>(ncu * 3, n_tasks);
-    hipLaunchKernelGGL((wfa_edit_adaptive_kernel<16384, 2048, WPB>), dim3(grid), dim3(WPB * 64), 0, ctx->stream, d_arena, d_tasks, in, in_n, in_imm,
-                       d_scores, d_cells, c + 3, c + 7, l3, H, (int32_t*)nullptr, 0);
-    in = l3; in_n = c + 7; in_imm = 0;
+    hipLaunchKernelGGL((wfa_edit_adaptive_kernel<16384, 2048, WPB>), dim3(grid), dim3(WPB * 64), 0, ctx->stream, d_arena, d_tasks, in.list, in.n, in.imm,
+                       d_scores, d_cells, &c->bytes16384.ticket, &c->bytes16384.overflow, l3, H, (int32_t*)nullptr, 0);
+    in.next(l3, &c->bytes16384.overflow);
   }
   {                     // int32 wavefront in HBM, sized for the longest pair of the batch
-    hipLaunchKernelGGL((wfa_edit_adaptive_kernel<0, 2048, WPBL>), dim3(ncu), dim3(WPBL * 64), 0, ctx->stream, d_arena, d_tasks, in, in_n, in_imm,
-                       d_scores, d_cells, c + 8, c + 9, (uint32_t*)nullptr, H, (int32_t*)wsp, gcapL);
+    hipLaunchKernelGGL((wfa_edit_adaptive_kernel<0, 2048, WPBL>), dim3(ncu), dim3(WPBL * 64), 0, ctx->stream, d_arena, d_tasks, in.list, in.n, in.imm,
+                       d_scores, d_cells, &c->last.ticket, &c->last.overflow, (uint32_t*)nullptr, H, (int32_t*)wsp, gcapL);
   }
   if (kernel_ms) HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   HIP_TRY(ctx, hipGetLastError());
-  if (getenv("OTG_DEBUG")) {
+  if (otg_env_set("OTG_DEBUG")) {
     hipError_t er = hipStreamSynchronize(ctx->stream);
-    uint32_t h[10], h16[2];
-    (void)hipMemcpy(h, c, sizeof(h), hipMemcpyDeviceToHost);
-    (void)hipMemcpy(h16, c16, sizeof(h16), hipMemcpyDeviceToHost);
+    OtgCounters::AdaptiveEdit h;
+    (void)hipMemcpy(&h, c, sizeof(h), hipMemcpyDeviceToHost);
     fprintf(stderr, "[otg] edit, wfadaptive(%d,%d,%d): %s; the packed 1024-diagonal tier passes on %u pairs, the packed 4096 one %u, the packed 16384 one %u, the byte-probe 2048 one %u, the 16384 one %u\n",
-            H.min_wf_len, H.max_dist, H.steps, hipGetErrorString(er), h[4], h[5], h16[1], h[6], h[7]);
+            H.min_wf_len, H.max_dist, H.steps, hipGetErrorString(er), h.packed1024.overflow, h.packed4096.overflow, h.packed16384.overflow, h.bytes2048.overflow, h.bytes16384.overflow);
   }
-  if (kernel_ms) {
-    HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
-    float ms = 0;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    *kernel_ms += ms;
-    if (launches) *launches += 1;
-  }
-  return OTG_OK;
+  return otg_timer_add(ctx, kernel_ms, launches);
 }
 
 int otg_launch_affine_adaptive_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* d_tasks, const uint32_t* d_todo,
@@ -1899,40 +1880,21 @@ int otg_launch_affine_adaptive_todo(otg_ctx* ctx, const uint8_t* d_arena, const 
                                     float* kernel_ms, uint64_t* launches)
 {
   if (n_tasks == 0) return OTG_OK;
-  if (x <= 0 || e <= 0 || o < 0) return otg_fail(ctx, OTG_ERR_ARG, "affine penalties must satisfy x>0, o>=0, e>0");
-  const int g = gcd3(x, o + e, e);
-  const int xs = x / g, oes = (o + e) / g, es = e / g;
-  if (std::max(xs, oes) + 1 > 64 || es + 1 > 64) return otg_fail(ctx, OTG_ERR_ARG, "affine penalties too large after gcd reduction");
-  if (ctx->pool[SLOT_COUNTERS].cap < OTG_COUNTER_WORDS * sizeof(uint32_t)) ctx->affine_visited = nullptr;
-  uint32_t* cnt = (uint32_t*)otg_slot(ctx, SLOT_COUNTERS, OTG_COUNTER_WORDS * sizeof(uint32_t));
+  int g, xs, oes, es;
+  if (int rc = affine_penalties(ctx, x, o, e, &g, &xs, &oes, &es)) return rc;
+  OtgCounters::AdaptiveAffine* const c = otg_counters(ctx, &OtgCounters::adaptive_affine);
   uint32_t* lists = (uint32_t*)otg_slot(ctx, SLOT_TODO, 2 * (size_t)n_tasks * sizeof(uint32_t));
-  if (!cnt || !lists) return OTG_ERR_HIP;
-  uint32_t* c = cnt + 120;                    // c[0..2] tickets, c[3..4] lengths of the overflow lists, c[6..7] the byte tier's pair, c[-2..-1] the 4096 window's
-  HIP_TRY(ctx, hipMemsetAsync(c - 2, 0, 10 * sizeof(uint32_t), ctx->stream));
+  if (!c || !lists) return OTG_ERR_HIP;
   const Heur H{ctx->heur_min_wf_len, ctx->heur_max_dist, ctx->heur_steps < 1 ? 1 : ctx->heur_steps};
   const uint32_t ncu = (uint32_t)ctx->n_cu;
   const size_t maxlen = ((size_t)ctx->max_seq_len + 4095) & ~(size_t)4095;
   // bit t = tier t runs: 1 packed 256, 2 packed 1024, 4 bytes 1024, 8 packed 4096; 16 = the 1024 window as ONE wave per alignment (the tier as first
   // built) instead of four; the int32 tier always runs
-  static const int only = getenv("OTG_ADAPTIVE_AFFINE_TIERS") ? atoi(getenv("OTG_ADAPTIVE_AFFINE_TIERS")) : 15;
+  static const int only = otg_env_int("OTG_ADAPTIVE_AFFINE_TIERS", 15);
 
-  AffWs ws;
-  ws.capa = (int)(2 * maxlen + 16) & ~1;
-  ws.rm = std::max(xs, oes) + 1;
-  ws.ri = es + 1;
-  ws.nrows = (int)(2 * (size_t)oes + (size_t)es * 2 * maxlen + 16);
-  ws.rev_cap = 4 * maxlen + 64;
-  ws.dbg = 0; ws.visited = nullptr;
+  const AffWs ws = aff_ws_common(maxlen, xs, oes, es);      // (dbg 0, no visited-cell counter)
   // LDS tiers: no rings in HBM, only row table + reversed op list + provenance slab
-  auto lds_ws = [&](size_t slab) {
-    AffWs w = ws;
-    w.off_rowtab = 0;
-    w.off_rev = ((size_t)w.nrows * sizeof(int64_t) + 255) & ~(size_t)255;
-    w.off_slab = (w.off_rev + w.rev_cap + 255) & ~(size_t)255;
-    w.slab_bytes = slab & ~(size_t)255;
-    w.stride = w.off_slab + w.slab_bytes;
-    return w;
-  };
+  auto lds_ws = [&](size_t slab) { AffWs w = ws; aff_ws_layout(w, false); aff_ws_slab(w, slab); return w; };
   constexpr int WPB0 = 4, WPB1 = 1, WPB2 = 4;
   const int seqw = (int)std::min<size_t>(2 * (((size_t)ctx->max_seq_len + 15) / 16 + 3) + 2, 8192);      // LDS words per wave for the packed pair
   // provenance: a row per score, as wide as the wavefront.  Mean width under the cut ~100 diagonals, scores ~0.4 per base
@@ -1948,13 +1910,7 @@ int otg_launch_affine_adaptive_todo(otg_ctx* ctx, const uint8_t* d_arena, const 
   constexpr int NW1 = 4, NW3 = 8, QMW = 256;
   uint32_t grid0 = std::min<uint32_t>(ncu * pc0, (n_tasks + WPB0 - 1) / WPB0), grid1 = std::min<uint32_t>(ncu * pc1, n_tasks), grid2 = 8;
   uint32_t grid3 = std::min<uint32_t>(ncu, n_tasks);
-  AffWs w2 = ws;
-  {
-    const size_t ring_bytes = (size_t)(ws.rm + 2 * ws.ri) * ws.capa * sizeof(int32_t);
-    w2.off_rowtab = (ring_bytes + 255) & ~(size_t)255;
-    w2.off_rev = (w2.off_rowtab + (size_t)ws.nrows * sizeof(int64_t) + 255) & ~(size_t)255;
-    w2.off_slab = (w2.off_rev + ws.rev_cap + 255) & ~(size_t)255;
-  }
+  AffWs w2 = ws; aff_ws_layout(w2, true);
   {
     std::lock_guard<std::mutex> alloc_lock(otg_device_mutex(ctx->device));
     size_t free_b = 0, total_b = 0;
@@ -1966,58 +1922,52 @@ int otg_launch_affine_adaptive_todo(otg_ctx* ctx, const uint8_t* d_arena, const 
     // the generic tier: the worst case of the longest pair of the batch (every diagonal at every score), as far as the budget goes
     size_t slab2 = std::min<size_t>((size_t)2 * maxlen * (size_t)ws.nrows, budget / (grid2 * WPB2));
     if (slab2 > w2.off_slab + 256) slab2 -= w2.off_slab + 256;
-    w2.slab_bytes = slab2 & ~(size_t)255; w2.stride = w2.off_slab + w2.slab_bytes;
+    aff_ws_slab(w2, slab2);
     const size_t need = std::max(std::max(std::max(w0.stride * grid0 * WPB0, w1.stride * grid1 * WPB1), w2.stride * (size_t)grid2 * WPB2), w3.stride * grid3);
     uint8_t* wsp = (uint8_t*)otg_slot(ctx, SLOT_WF_WS, need);
     if (!wsp) return OTG_ERR_HIP;
     w0.base = w1.base = w2.base = w3.base = wsp;
   }
   if (kernel_ms) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  const uint32_t* in = d_todo; const uint32_t* in_n = d_n_todo; uint32_t in_imm = n_tasks;
+  OtgTodo in{d_todo, d_n_todo, n_tasks};
   uint32_t* l0 = lists; uint32_t* l1 = lists + n_tasks;
   const bool std_pen = xs == 2 && oes == 4 && es == 1;
   if ((only & 1) && std_pen) {      // fast tier, 256 diagonals
-    hipLaunchKernelGGL((wfa_affine_adaptive_lds_kernel<256, 256, WPB0, true>), dim3(grid0), dim3(WPB0 * 64), (size_t)WPB0 * seqw * 4, ctx->stream, d_arena, d_tasks, in, in_n, in_imm,
-                       g, d_scores, d_cig_off, d_cig_len, d_cig_arena, d_cells, c + 0, c + 3, l0, w0, H, seqw);
-    in = l0; in_n = c + 3; in_imm = 0;
+    hipLaunchKernelGGL((wfa_affine_adaptive_lds_kernel<256, 256, WPB0, true>), dim3(grid0), dim3(WPB0 * 64), (size_t)WPB0 * seqw * 4, ctx->stream, d_arena, d_tasks, in.list, in.n, in.imm,
+                       g, d_scores, d_cig_off, d_cig_len, d_cig_arena, d_cells, &c->win256.ticket, &c->win256.overflow, l0, w0, H, seqw);
+    in.next(l0, &c->win256.overflow);
   }
   if ((only & 2) && std_pen) {      // 1024 diagonals, four waves per alignment (bit 16: one)
     if (only & 16)
-      hipLaunchKernelGGL((wfa_affine_adaptive_lds_kernel<1024, 1024, WPB1, false>), dim3(grid1), dim3(WPB1 * 64), (size_t)WPB1 * seqw * 4, ctx->stream, d_arena, d_tasks, in, in_n, in_imm,
-                         g, d_scores, d_cig_off, d_cig_len, d_cig_arena, d_cells, c + 1, c + 4, l1, w1, H, seqw);
+      hipLaunchKernelGGL((wfa_affine_adaptive_lds_kernel<1024, 1024, WPB1, false>), dim3(grid1), dim3(WPB1 * 64), (size_t)WPB1 * seqw * 4, ctx->stream, d_arena, d_tasks, in.list, in.n, in.imm,
+                         g, d_scores, d_cig_off, d_cig_len, d_cig_arena, d_cells, &c->win1024.ticket, &c->win1024.overflow, l1, w1, H, seqw);
     else
-      hipLaunchKernelGGL((wfa_affine_adaptive_mw_kernel<1024, QMW, NW1>), dim3(grid1), dim3(NW1 * 64), (size_t)seqw * 4, ctx->stream, d_arena, d_tasks, in, in_n, in_imm,
-                         g, d_scores, d_cig_off, d_cig_len, d_cig_arena, d_cells, c + 1, c + 4, l1, w1, H, seqw);
-    in = l1; in_n = c + 4; in_imm = 0;
+      hipLaunchKernelGGL((wfa_affine_adaptive_mw_kernel<1024, QMW, NW1>), dim3(grid1), dim3(NW1 * 64), (size_t)seqw * 4, ctx->stream, d_arena, d_tasks, in.list, in.n, in.imm,
+                         g, d_scores, d_cig_off, d_cig_len, d_cig_arena, d_cells, &c->win1024.ticket, &c->win1024.overflow, l1, w1, H, seqw);
+    in.next(l1, &c->win1024.overflow);
   }
   if ((only & 8) && std_pen) {      // 4096 diagonals, eight waves per alignment, one block per CU
-    uint32_t* lout = in == l0 ? l1 : l0;
-    hipLaunchKernelGGL((wfa_affine_adaptive_mw_kernel<4096, QMW, NW3>), dim3(grid3), dim3(NW3 * 64), (size_t)seqw * 4, ctx->stream, d_arena, d_tasks, in, in_n, in_imm,
-                       g, d_scores, d_cig_off, d_cig_len, d_cig_arena, d_cells, c - 2, c - 1, lout, w3, H, seqw);
-    in = lout; in_n = c - 1; in_imm = 0;
+    uint32_t* lout = in.list == l0 ? l1 : l0;
+    hipLaunchKernelGGL((wfa_affine_adaptive_mw_kernel<4096, QMW, NW3>), dim3(grid3), dim3(NW3 * 64), (size_t)seqw * 4, ctx->stream, d_arena, d_tasks, in.list, in.n, in.imm,
+                       g, d_scores, d_cig_off, d_cig_len, d_cig_arena, d_cells, &c->win4096.ticket, &c->win4096.overflow, lout, w3, H, seqw);
+    in.next(lout, &c->win4096.overflow);
   }
   if ((only & 4) && std_pen) {      // byte probes, 1024 diagonals: pairs with bytes outside ACGT or too long to pack
-    hipLaunchKernelGGL((wfa_affine_adaptive_kernel<1024, 1024, WPB1, 8>), dim3(grid1), dim3(WPB1 * 64), 0, ctx->stream, d_arena, d_tasks, in, in_n, in_imm,
-                       xs, oes, es, g, d_scores, d_cig_off, d_cig_len, d_cig_arena, d_cells, c + 6, c + 7, in == l0 ? l1 : l0, w1, H, 0);
-    in = in == l0 ? l1 : l0; in_n = c + 7; in_imm = 0;
+    uint32_t* lout = in.list == l0 ? l1 : l0;
+    hipLaunchKernelGGL((wfa_affine_adaptive_kernel<1024, 1024, WPB1, 8>), dim3(grid1), dim3(WPB1 * 64), 0, ctx->stream, d_arena, d_tasks, in.list, in.n, in.imm,
+                       xs, oes, es, g, d_scores, d_cig_off, d_cig_len, d_cig_arena, d_cells, &c->bytes1024.ticket, &c->bytes1024.overflow, lout, w1, H, 0);
+    in.next(lout, &c->bytes1024.overflow);
   }
-  hipLaunchKernelGGL((wfa_affine_adaptive_kernel<0, 2048, WPB2, 64>), dim3(grid2), dim3(WPB2 * 64), 0, ctx->stream, d_arena, d_tasks, in, in_n, in_imm,
-                     xs, oes, es, g, d_scores, d_cig_off, d_cig_len, d_cig_arena, d_cells, c + 2, c + 5, (uint32_t*)nullptr, w2, H, 0);
+  hipLaunchKernelGGL((wfa_affine_adaptive_kernel<0, 2048, WPB2, 64>), dim3(grid2), dim3(WPB2 * 64), 0, ctx->stream, d_arena, d_tasks, in.list, in.n, in.imm,
+                     xs, oes, es, g, d_scores, d_cig_off, d_cig_len, d_cig_arena, d_cells, &c->last.ticket, &c->last.overflow, (uint32_t*)nullptr, w2, H, 0);
   if (kernel_ms) HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   HIP_TRY(ctx, hipGetLastError());
-  if (getenv("OTG_DEBUG")) {
+  if (otg_env_set("OTG_DEBUG")) {
     hipError_t er = hipStreamSynchronize(ctx->stream);
-    uint32_t h[10];
-    (void)hipMemcpy(h, c - 2, sizeof(h), hipMemcpyDeviceToHost);
+    OtgCounters::AdaptiveAffine h;
+    (void)hipMemcpy(&h, c, sizeof(h), hipMemcpyDeviceToHost);
     fprintf(stderr, "[otg] affine, wfadaptive(%d,%d,%d): %s; the 256-diagonal window passes on %u alignments, the 1024 one %u, the 4096 one %u, the byte probes %u; %u / %u / %u alignments in flight, %.2f / %.2f / %.2f MB each\n",
-            H.min_wf_len, H.max_dist, H.steps, hipGetErrorString(er), h[5], h[6], h[1], h[9], grid0 * WPB0, grid1 * WPB1, grid3, (double)w0.stride / 1e6, (double)w1.stride / 1e6, (double)w3.stride / 1e6);
+            H.min_wf_len, H.max_dist, H.steps, hipGetErrorString(er), h.win256.overflow, h.win1024.overflow, h.win4096.overflow, h.bytes1024.overflow, grid0 * WPB0, grid1 * WPB1, grid3, (double)w0.stride / 1e6, (double)w1.stride / 1e6, (double)w3.stride / 1e6);
   }
-  if (kernel_ms) {
-    HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
-    float ms = 0;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    *kernel_ms += ms;
-    if (launches) *launches += 1;
-  }
-  return OTG_OK;
+  return otg_timer_add(ctx, kernel_ms, launches);
 }

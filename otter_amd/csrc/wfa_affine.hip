@@ -16,6 +16,7 @@
 // (wfa_affine_common.hpp).  An alignment a tier cannot finish is queued on the device for the next one.
 #include "wfa_affine_common.hpp"
 #include "wfa_affine_reg.hpp"
+#include "otg_chain.hpp"
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
@@ -737,12 +738,6 @@ __global__ __launch_bounds__(NW * 64) void wfa_affine_kernel_v3(
   }
 }
 
-int gcd3(int a, int b, int c)
-{
-  auto g2 = [](int x, int y) { while (y) { int t = x % y; x = y; y = t; } return x; };
-  return g2(g2(a, b), c);
-}
-
 // ---- counting sort of the alignment list by (tier, score bound), largest bound first inside a tier: the exact pass of an alignment costs
 // ~ bound^2, and the persistent tier kernels hand alignments out in list order, so the longest run first and the tail of each kernel is
 // short ones.  Which tier takes an alignment follows from its score bound and shape alone — the same window arithmetic as the kernels
@@ -853,42 +848,27 @@ int otg_launch_affine_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align
   if (ctx->heur_strategy == OTG_HEURISTIC_WFADAPTIVE)
     return otg_launch_affine_adaptive_todo(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, x, o, e, d_scores, d_cig_off, d_cig_len, d_cig_arena, d_cells,
                                            kernel_ms, launches);
-  if (x <= 0 || e <= 0 || o < 0) return otg_fail(ctx, OTG_ERR_ARG, "affine penalties must satisfy x>0, o>=0, e>0");
-  const int g = gcd3(x, o + e, e);
-  const int xs = x / g, oes = (o + e) / g, es = e / g;
-  if (std::max(xs, oes) + 1 > 64 || es + 1 > 64) return otg_fail(ctx, OTG_ERR_ARG, "affine penalties too large after gcd reduction");
-  const bool fresh_cnt = ctx->pool[SLOT_COUNTERS].cap < OTG_COUNTER_WORDS * sizeof(uint32_t);
-  uint32_t* cnt = (uint32_t*)otg_slot(ctx, SLOT_COUNTERS, OTG_COUNTER_WORDS * sizeof(uint32_t));
+  int g, xs, oes, es;
+  if (int rc = affine_penalties(ctx, x, o, e, &g, &xs, &oes, &es)) return rc;
+  // zeroed: segment bounds, tickets and overflow counters; the visited-cell counter behind them accumulates over the launches of a run
+  OtgCounters::ExactAffine* const cnt = otg_counters(ctx, &OtgCounters::exact_affine, offsetof(OtgCounters::ExactAffine, visited));
   uint32_t* todo = (uint32_t*)otg_slot(ctx, SLOT_TODO, 4 * (size_t)n_tasks * sizeof(uint32_t));
   if (!cnt || !todo) return OTG_ERR_HIP;
-  HIP_TRY(ctx, hipMemsetAsync(cnt + 8, 0, 8 * sizeof(uint32_t), ctx->stream));        // tickets / overflow counters of the tiers behind the register tiers
-  HIP_TRY(ctx, hipMemsetAsync(cnt + 64, 0, 16 * sizeof(uint32_t), ctx->stream));      // register tiers: segment bounds, overflow count, tickets
-  // visited-cell counter of the exact tiers (accumulates over the launches of a run; otg_assemble_run zeroes it)
-  if (fresh_cnt || !ctx->affine_visited) { ctx->affine_visited = (unsigned long long*)(cnt + 96); HIP_TRY(ctx, hipMemsetAsync(cnt + 96, 0, 8, ctx->stream)); }
 
   // workspace sizes must not follow the batch: every change of size is a hipFree + hipMalloc of gigabytes, and batches of one job differ in
   // their longest read and their task count — the longest read is rounded up to 4 kb steps and the grids are sized for a full device
   const size_t maxlen = ((size_t)ctx->max_seq_len + 4095) & ~(size_t)4095;
-  AffWs ws;
-  ws.capa = (int)(2 * maxlen + 16) & ~1;
-  ws.rm = std::max(xs, oes) + 1;
-  ws.ri = es + 1;
-  ws.nrows = (int)(2 * (size_t)oes + (size_t)es * 2 * maxlen + 16);
-  ws.rev_cap = 4 * maxlen + 64;
-  ws.dbg = getenv("OTG_DEBUG") != nullptr ? 1 : 0;
-  ws.visited = ctx->affine_visited;
-  size_t ring_bytes = (size_t)(ws.rm + 2 * ws.ri) * ws.capa * sizeof(int32_t);
-  ws.off_rowtab = (ring_bytes + 255) & ~(size_t)255;
-  ws.off_rev = (ws.off_rowtab + (size_t)ws.nrows * sizeof(int64_t) + 255) & ~(size_t)255;
-  ws.off_slab = (ws.off_rev + ws.rev_cap + 255) & ~(size_t)255;
+  AffWs ws = aff_ws_common(maxlen, xs, oes, es);
+  ws.dbg = otg_env_set("OTG_DEBUG") ? 1 : 0; ws.visited = &cnt->visited;
+  aff_ws_layout(ws, true);
 
-  static const bool no_v3 = getenv("OTG_NO_AFFINE_V3") != nullptr;            // generic kernel only (test switch)
-  static const bool no_bound = getenv("OTG_NO_AFFINE_BOUND") != nullptr;      // no score bound: the HBM-row tiers without pruning (test switch)
+  static const bool no_v3 = otg_env_set("OTG_NO_AFFINE_V3");            // generic kernel only (test switch)
+  static const bool no_bound = otg_env_set("OTG_NO_AFFINE_BOUND");      // no score bound: the HBM-row tiers without pruning (test switch)
   // register tiers that run (bit mask, test switch OTG_AFFINE_REG: 1 / 2 / 4 = the one-wave tiers of 1024 / 1536 / 2048 diagonals, 8 = the four-wave
   // tier of 4096, 16 = the eight-wave tier of 8192 — that one only when the batch can need it: its slabs are the largest)
-  static const int reg_mask_env = getenv("OTG_AFFINE_REG") ? atoi(getenv("OTG_AFFINE_REG")) : 31;
+  static const int reg_mask_env = otg_env_int("OTG_AFFINE_REG", 31);
   // measurement switch: which instantiation a window runs on, one digit per tier (wfa_affine_reg.hip; 0 = default)
-  static const int shape_env = getenv("OTG_REG_SHAPE") ? atoi(getenv("OTG_REG_SHAPE")) : 0;
+  static const int shape_env = otg_env_int("OTG_REG_SHAPE", 0);
   const int shape[OTG_REG_TIERS] = {(shape_env / 10000) % 10, (shape_env / 1000) % 10, (shape_env / 100) % 10, (shape_env / 10) % 10, shape_env % 10};
   const bool bounded = !no_v3 && es == 1 && xs == 2 && oes == 4 && !no_bound;
   int reg_mask = !bounded ? 0 : (maxlen <= 4096 ? (reg_mask_env & ~16) : reg_mask_env) & 31;
@@ -920,16 +900,16 @@ int otg_launch_affine_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align
     // tier A: HBM rows, LDS window of 4096 diagonals; tier B: 12288 diagonals (the longest reads of a 1-10 kb job without a usable bound)
     wavesA = ncu * 2; size_t slabA = diamond_slab(4096);
     fit(wavesA, slabA);
-    wsA.slab_bytes = slabA & ~(size_t)255; wsA.stride = wsA.off_slab + wsA.slab_bytes;
+    aff_ws_slab(wsA, slabA);
     wavesB = maxlen > 8192 ? ncu : ncu / 2; size_t slabB = diamond_slab(12288);
     fit(wavesB, slabB);
-    wsB.slab_bytes = slabB & ~(size_t)255; wsB.stride = wsB.off_slab + wsB.slab_bytes;
+    aff_ws_slab(wsB, slabB);
     // tier C: generic kernel (global int32 rings), a few waves with the largest useful slabs
     size_t slabC = std::min<size_t>((size_t)2 * maxlen * (size_t)(ws.nrows), budget / (gridC * WPB));
-    static const size_t slab_cap_env = getenv("OTG_AFFINE_LAST_SLAB_MB") ? (size_t)atoi(getenv("OTG_AFFINE_LAST_SLAB_MB")) << 20 : 0;      // test switch: a last-resort tier that runs out
+    static const size_t slab_cap_env = (size_t)otg_env_int("OTG_AFFINE_LAST_SLAB_MB", 0) << 20;      // test switch: a last-resort tier that runs out
     if (slab_cap_env) slabC = std::min(slabC, slab_cap_env);
     if (slabC > ws.off_slab + 256) slabC -= ws.off_slab + 256;
-    wsC.slab_bytes = slabC & ~(size_t)255; wsC.stride = wsC.off_slab + wsC.slab_bytes;
+    aff_ws_slab(wsC, slabC);
     const size_t need = std::max(std::max(wsA.stride * wavesA, wsB.stride * wavesB), wsC.stride * (size_t)gridC * WPB);
     uint8_t* wsp = (uint8_t*)otg_slot(ctx, SLOT_WF_WS, need);
     if (!wsp) return OTG_ERR_HIP;
@@ -945,12 +925,10 @@ int otg_launch_affine_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align
         AffWs w = ws;
         const size_t cap = (size_t)OTG_REG_CAP[t];
         w.nrows = OTG_REG_CAP[t] + 64;
-        w.off_rowtab = 0;
-        w.off_rev = ((size_t)w.nrows * sizeof(int64_t) + 255) & ~(size_t)255;
-        w.off_slab = (w.off_rev + ws.rev_cap + 255) & ~(size_t)255;
-        w.slab_bytes = (cap * cap * 7 / 8 + (1 << 16)) & ~(size_t)255;
-        if (t == 4) w.slab_bytes = std::min<size_t>(w.slab_bytes, ((size_t)(0.2 * (double)maxlen * (double)maxlen) + (1 << 20)) & ~(size_t)255);
-        w.stride = w.off_slab + w.slab_bytes;
+        aff_ws_layout(w, false);                     // no rings in HBM
+        size_t slab = cap * cap * 7 / 8 + (1 << 16);
+        if (t == 4) slab = std::min<size_t>(slab, (size_t)(0.2 * (double)maxlen * (double)maxlen) + (1 << 20));
+        aff_ws_slab(w, slab);
         wr[t] = w;
         int apb = 1, bpc = 1;
         otg_affine_reg_geometry(t, shape[t], &apb, &bpc);
@@ -986,20 +964,18 @@ int otg_launch_affine_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align
   uint32_t* sorted = todo + 2 * (size_t)n_tasks;        // the counting sort's output: one segment per register tier + the rest
   uint32_t* ovf_r = todo + 3 * (size_t)n_tasks;         // the rest + what the register tiers give up: the input of tier A
   if (kernel_ms) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  const uint32_t* cur = d_todo; const uint32_t* cur_n = d_n_todo; uint32_t cur_imm = n_tasks;
+  OtgTodo cur{d_todo, d_n_todo, n_tasks};
   if (!no_v3 && es == 1) {
     int32_t* d_bound = nullptr;
     if (bounded) {
       d_bound = (int32_t*)otg_slot(ctx, SLOT_BT_POOL, (size_t)n_tasks * sizeof(int32_t));
       if (!d_bound) return OTG_ERR_HIP;
       const uint32_t gridU = std::min<uint32_t>(ncu * 8, (n_tasks + 3) / 4);
-      hipLaunchKernelGGL((wfa_affine_bound1_kernel<2, 4>), dim3(gridU), dim3(256), 0, ctx->stream, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_bound, cnt + 14);
+      hipLaunchKernelGGL((wfa_affine_bound1_kernel<2, 4>), dim3(gridU), dim3(256), 0, ctx->stream, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_bound, &cnt->bound_ticket);
     }
-    const uint32_t* inA = d_todo; const uint32_t* inA_n = d_n_todo; uint32_t inA_imm = n_tasks;
     if (d_bound && reg_mask) {
       uint32_t* hist = (uint32_t*)otg_slot(ctx, SLOT_ROWTAB, TSORT_BUCKETS * sizeof(uint32_t));
-      uint32_t* seg = cnt + 64;               // seg[0 .. OTG_REG_TIERS + 1]
-      uint32_t* n_ovf = cnt + 71;
+      uint32_t* seg = cnt->seg; uint32_t* n_ovf = &cnt->reg_overflow;
       if (!hist) return OTG_ERR_HIP;
       HIP_TRY(ctx, hipMemsetAsync(hist, 0, TSORT_BUCKETS * sizeof(uint32_t), ctx->stream));
       const uint32_t sg = std::min<uint32_t>((n_tasks + 2047) / 2048, ncu * 2);
@@ -1011,7 +987,7 @@ int otg_launch_affine_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align
       // Small batches: the tiers next to each other on side streams (disjoint lists, workspaces and tickets; what they give up goes to one list
       // through an atomic counter) — each tier alone would leave most of the device idle and still last as long as its longest alignment.
       // Large batches: one after the other (side by side the tiers' blocks share CUs and the chain takes 12 % longer, measured).
-      static const int conc_env = getenv("OTG_AFFINE_CONCURRENT") ? atoi(getenv("OTG_AFFINE_CONCURRENT")) : -1;
+      static const int conc_env = otg_env_int("OTG_AFFINE_CONCURRENT", -1);
       const bool concurrent = conc_env >= 0 ? conc_env != 0 : n_tasks <= 50000u;      // measured: 6 250 alignments 44 -> 30 ms, 25 000: 67 -> 59 ms, 100 000: 194 -> 201 ms
       hipStream_t main_stream = ctx->stream;
       if (concurrent) {
@@ -1051,45 +1027,47 @@ int otg_launch_affine_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align
       } else {
         for (int t = 0; t < OTG_REG_TIERS; ++t) side_of[t] = blocks[t] ? -1 : -2;
       }
+      // ctx->stream points at a side stream only around a tier's launch; after a failure the side streams already used are waited for
       bool side_used[2] = {false, false};
-      for (int q = 0; q < OTG_REG_TIERS; ++q) {
-        const int t = order[q];
-        if (side_of[t] == -2) continue;
-        if (side_of[t] >= 0) {
-          ctx->stream = ctx->tier_stream[side_of[t]];
-          if (!side_used[side_of[t]]) { HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_fork, 0)); side_used[side_of[t]] = true; }
-        }
-        const int rc = otg_launch_affine_reg_tier(ctx, t, shape[t], blocks[t], d_arena, d_tasks, sorted, seg + t, g, d_scores, d_cig_off, d_cig_len, d_cig_arena, d_cells,
-                                                  cnt + 72 + t, n_ovf, ovf_r, wr[t], d_bound, ctx->affine_visited);
+      int rc = OTG_OK; hipError_t he = hipSuccess;
+      for (int q = 0; q < OTG_REG_TIERS && !rc; ++q) {
+        const int t = order[q], sd = side_of[t];
+        if (sd == -2) continue;
+        if (sd >= 0 && !side_used[sd] && (he = hipStreamWaitEvent(ctx->tier_stream[sd], ctx->ev_fork, 0)) != hipSuccess) break;
+        if (sd >= 0) { side_used[sd] = true; ctx->stream = ctx->tier_stream[sd]; }
+        rc = otg_launch_affine_reg_tier(ctx, t, shape[t], blocks[t], d_arena, d_tasks, sorted, seg + t, g, d_scores, d_cig_off, d_cig_len, d_cig_arena, d_cells,
+                                        &cnt->reg_ticket[t], n_ovf, ovf_r, wr[t], d_bound, &cnt->visited);
         ctx->stream = main_stream;
-        if (rc) return rc;
       }
       for (int sd = 0; sd < 2; ++sd) if (side_used[sd]) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_join[sd], ctx->tier_stream[sd]));
-        HIP_TRY(ctx, hipStreamWaitEvent(main_stream, ctx->ev_join[sd], 0));
+        if (!rc && he == hipSuccess && (he = hipEventRecord(ctx->ev_join[sd], ctx->tier_stream[sd])) == hipSuccess) he = hipStreamWaitEvent(main_stream, ctx->ev_join[sd], 0);
+        if (rc || he != hipSuccess) (void)hipStreamSynchronize(ctx->tier_stream[sd]);
       }
-      inA = ovf_r; inA_n = n_ovf; inA_imm = 0;
+      HIP_TRY(ctx, he);
+      if (rc) return rc;
+      cur.next(ovf_r, n_ovf);
     }
     hipLaunchKernelGGL((wfa_affine_kernel_v3<4096, 512, NWA>), dim3(wavesA), dim3(NWA * 64), 0, ctx->stream, d_arena, d_tasks,
-                       inA, inA_n, inA_imm, xs, oes, es, g, d_scores, d_cig_off, d_cig_len,
-                       d_cig_arena, d_cells, cnt + 8, cnt + 9, listA, wsA, (const int32_t*)d_bound);
+                       cur.list, cur.n, cur.imm, xs, oes, es, g, d_scores, d_cig_off, d_cig_len,
+                       d_cig_arena, d_cells, &cnt->a.ticket, &cnt->a.overflow, listA, wsA, (const int32_t*)d_bound);
+    cur.next(listA, &cnt->a.overflow);
     hipLaunchKernelGGL((wfa_affine_kernel_v3<12288, 512, NWA>), dim3(wavesB), dim3(NWA * 64), 0, ctx->stream, d_arena, d_tasks,
-                       (const uint32_t*)listA, (const uint32_t*)(cnt + 9), 0u, xs, oes, es, g, d_scores, d_cig_off, d_cig_len,
-                       d_cig_arena, d_cells, cnt + 10, cnt + 11, listB, wsB, (const int32_t*)d_bound);
-    cur = listB; cur_n = cnt + 11; cur_imm = 0;
+                       cur.list, cur.n, cur.imm, xs, oes, es, g, d_scores, d_cig_off, d_cig_len,
+                       d_cig_arena, d_cells, &cnt->b.ticket, &cnt->b.overflow, listB, wsB, (const int32_t*)d_bound);
+    cur.next(listB, &cnt->b.overflow);
   }
   hipLaunchKernelGGL((wfa_affine_kernel<WPB>), dim3(gridC), dim3(WPB * 64), 0, ctx->stream, d_arena, d_tasks,
-                     cur, cur_n, cur_imm, xs, oes, es, g, d_scores, d_cig_off, d_cig_len,
-                     d_cig_arena, d_cells, cnt + 12, cnt + 13, (uint32_t*)nullptr, wsC);
+                     cur.list, cur.n, cur.imm, xs, oes, es, g, d_scores, d_cig_off, d_cig_len,
+                     d_cig_arena, d_cells, &cnt->c.ticket, &cnt->c.overflow, (uint32_t*)nullptr, wsC);
   if (kernel_ms) HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));      // after the LAST tier of the chain
   HIP_TRY(ctx, hipGetLastError());
   if (ws.dbg) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    uint32_t h[16], h5[8];
-    HIP_TRY(ctx, hipMemcpy(h, cnt, sizeof(h), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(h5, cnt + 64, sizeof(h5), hipMemcpyDeviceToHost));
+    OtgCounters::ExactAffine h;
+    HIP_TRY(ctx, hipMemcpy(&h, cnt, sizeof(h), hipMemcpyDeviceToHost));
     fprintf(stderr, "[otg] affine: register tiers take %u / %u / %u / %u / %u alignments, %u go to the HBM-row tiers (of which given up by a register tier: %u); tier A gives up %u, tier B %u\n",
-            h5[1] - h5[0], h5[2] - h5[1], h5[3] - h5[2], h5[4] - h5[3], h5[5] - h5[4], h5[7], h5[7] - (h5[6] - h5[5]), h[9], h[11]);
+            h.seg[1] - h.seg[0], h.seg[2] - h.seg[1], h.seg[3] - h.seg[2], h.seg[4] - h.seg[3], h.seg[5] - h.seg[4], h.reg_overflow,
+            h.reg_overflow - (h.seg[6] - h.seg[5]), h.a.overflow, h.b.overflow);
     const int32_t* dbg_bound = (const int32_t*)ctx->pool[SLOT_BT_POOL].p;
     if (dbg_bound && bounded) {
       // How loose is the bound?  The exact tiers visit the diamond of the bound U (~U^2 / 2 cells); the diamond of the final score s would do.
@@ -1116,8 +1094,8 @@ int otg_launch_affine_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align
                         (unsigned long long)n_ok, 100.0 * hist[0] / n_ok, 100.0 * hist[1] / n_ok, 100.0 * hist[2] / n_ok, 100.0 * hist[3] / n_ok, 100.0 * hist[4] / n_ok, 100.0 * hist[5] / n_ok,
                         100.0 * (su2 - ss2) / su2);
     }
-    if (h5[7] && dbg_bound && bounded && reg_mask) {        // who left a register tier (the first few): lengths, free ends, bound
-      const uint32_t nshow = std::min<uint32_t>(h5[7], 24u);
+    if (h.reg_overflow && dbg_bound && bounded && reg_mask) {        // who left a register tier (the first few): lengths, free ends, bound
+      const uint32_t nshow = std::min<uint32_t>(h.reg_overflow, 24u);
       std::vector<uint32_t> ids(nshow);
       HIP_TRY(ctx, hipMemcpy(ids.data(), todo + 3 * (size_t)n_tasks, nshow * sizeof(uint32_t), hipMemcpyDeviceToHost));
       for (uint32_t i = 0; i < nshow; ++i) {
@@ -1130,19 +1108,11 @@ int otg_launch_affine_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align
       }
     }
 #ifdef OTG_REG_TIMING
-    unsigned long long tm[7];
-    HIP_TRY(ctx, hipMemcpy(tm, cnt + 100, sizeof(tm), hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemsetAsync(cnt + 100, 0, sizeof(tm), ctx->stream));
+    const unsigned long long* tm = h.reg_timing;
+    HIP_TRY(ctx, hipMemsetAsync(cnt->reg_timing, 0, sizeof(h.reg_timing), ctx->stream));
     if (tm[5]) fprintf(stderr, "[otg] register tiers, clock ticks per wave and score: preamble %.0f sweep %.0f (%.2f slot visits) drain+fold %.0f exports %.0f barrier %.0f; %llu wave-scores\n",
                        (double)tm[0] / tm[5], (double)tm[1] / tm[5], (double)tm[6] / tm[5], (double)tm[2] / tm[5], (double)tm[3] / tm[5], (double)tm[4] / tm[5], tm[5]);
 #endif
   }
-  if (kernel_ms) {
-    HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
-    float ms = 0;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    *kernel_ms += ms;
-    if (launches) *launches += 1;
-  }
-  return OTG_OK;
+  return otg_timer_add(ctx, kernel_ms, launches);
 }

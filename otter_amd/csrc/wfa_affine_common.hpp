@@ -193,4 +193,33 @@ __device__ __forceinline__ bool affine_window(const otg_align_task& t, int U, in
   return hi0 >= lo0;
 }
 
+// ---- host side shared by the launch chains (wfa_affine.hip, wfa_adaptive.hip)
+// The penalties in units of their gcd: g, mismatch, gap open + extension, gap extension.  The rings hold max(xs, oes) + 1 and es + 1 rows, 64 at most.
+inline int affine_penalties(otg_ctx* ctx, int x, int o, int e, int* g, int* xs, int* oes, int* es)
+{
+  if (x <= 0 || e <= 0 || o < 0) return otg_fail(ctx, OTG_ERR_ARG, "affine penalties must satisfy x>0, o>=0, e>0");
+  auto g2 = [](int a, int b) { while (b) { int t = a % b; a = b; b = t; } return a; };
+  *g = g2(g2(x, o + e), e);
+  *xs = x / *g; *oes = (o + e) / *g; *es = e / *g;
+  if ((*xs > *oes ? *xs : *oes) + 1 > 64 || *es + 1 > 64) return otg_fail(ctx, OTG_ERR_ARG, "affine penalties too large after gcd reduction");
+  return OTG_OK;
+}
+// The fields every tier's workspace shares, for reads of up to maxlen bases (base, offsets, slab and stride: aff_ws_layout / aff_ws_slab).
+inline AffWs aff_ws_common(size_t maxlen, int xs, int oes, int es)
+{
+  AffWs w{};
+  w.capa = (int)(2 * maxlen + 16) & ~1; w.rm = (xs > oes ? xs : oes) + 1; w.ri = es + 1;
+  w.nrows = (int)(2 * (size_t)oes + (size_t)es * 2 * maxlen + 16); w.rev_cap = 4 * maxlen + 64;
+  return w;
+}
+// One alignment's workspace: [the M / I / D rings, for the tiers that keep them in HBM] row table (w.nrows entries) | reversed op list | slab.
+inline void aff_ws_layout(AffWs& w, bool rings)
+{
+  const size_t ring_bytes = rings ? (size_t)(w.rm + 2 * w.ri) * w.capa * sizeof(int32_t) : 0;
+  w.off_rowtab = (ring_bytes + 255) & ~(size_t)255;
+  w.off_rev = (w.off_rowtab + (size_t)w.nrows * sizeof(int64_t) + 255) & ~(size_t)255;
+  w.off_slab = (w.off_rev + w.rev_cap + 255) & ~(size_t)255;
+}
+inline void aff_ws_slab(AffWs& w, size_t slab) { w.slab_bytes = slab & ~(size_t)255; w.stride = w.off_slab + w.slab_bytes; }
+
 } // namespace otg_affine

@@ -4,7 +4,6 @@
 #pragma once
 #include "wfa_affine_common.hpp"
 
-constexpr int OTG_REG_TIERS = 5;
 // diagonals of window / bytes of packed sequence pair a tier admits (the counting sort in wfa_affine.hip and the kernels use the same figures)
 constexpr int OTG_REG_CAP[OTG_REG_TIERS] = {1024, 1536, 2048, 4096, 8192};
 constexpr int OTG_REG_SEQB[OTG_REG_TIERS] = {4096, 4608, 6144, 8192, 12288};

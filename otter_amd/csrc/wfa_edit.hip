@@ -16,7 +16,7 @@
 // Recurrence: M[s][k] = max(M[s-1][k-1]+1, M[s-1][k]+1, M[s-1][k+1]), nulled
 // when h>tlen or v>plen; k = h - v, offset = h.  End2end stops when M[s][tlen-plen] == tlen; ends-free
 // when any diagonal reaches a permitted boundary (score only: which diagonal does not matter).
-#include "otg_common.hpp"
+#include "otg_chain.hpp"
 #include <algorithm>
 #include <cstdlib>
 
@@ -561,7 +561,7 @@ __global__ __launch_bounds__(256) void K_sort_scatter(const uint32_t* __restrict
 } // namespace
 
 // Enqueue the tier chain: wavefront tier 1 (LDS, score-capped) -> bit-parallel tiers 0..4 -> wavefront tier 2 -> global.  Requires: d_arena padded with >= 8 readable bytes after the last
-// sequence byte.  Uses SLOT_COUNTERS (64 u32), SLOT_TODO ((OTG_MYERS_TIERS + 4) * n_tasks u32), SLOT_WF_WS (last tier only).
+// sequence byte.  Uses SLOT_COUNTERS (its exact_edit group), SLOT_TODO ((OTG_MYERS_TIERS + 4) * n_tasks u32), SLOT_WF_WS (last tier only).
 int otg_launch_edit(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* d_tasks, uint32_t n_tasks,
                     int32_t* d_scores, uint64_t* d_cells, float* kernel_ms, uint64_t* launches)
 {
@@ -573,30 +573,26 @@ int otg_launch_edit(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* 
 int otg_launch_edit_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* d_tasks, const uint32_t* d_todo,
                          const uint32_t* d_n_todo, uint32_t n_tasks, int32_t* d_scores, uint64_t* d_cells,
                          float* kernel_ms, uint64_t* launches)
-
 {
   if (n_tasks == 0) return OTG_OK;
   if (ctx->heur_strategy == OTG_HEURISTIC_WFADAPTIVE)
     return otg_launch_edit_adaptive_todo(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, kernel_ms, launches);
-  uint32_t* cnt = (uint32_t*)otg_slot(ctx, SLOT_COUNTERS, 64 * sizeof(uint32_t));
+  OtgCounters::ExactEdit* const cnt = otg_counters(ctx, &OtgCounters::exact_edit);
   constexpr int NT = OTG_MYERS_TIERS;
   uint32_t* todo = (uint32_t*)otg_slot(ctx, SLOT_TODO, (size_t)(NT + 4) * n_tasks * sizeof(uint32_t));
   if (!cnt || !todo) return OTG_ERR_HIP;
-  HIP_TRY(ctx, hipMemsetAsync(cnt, 0, 8 * sizeof(uint32_t), ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(cnt + 16, 0, 16 * sizeof(uint32_t), ctx->stream));
   // lists[t] (t = 0..NT-1) feed the bit-parallel tiers, lists[NT] the wide wavefront tier, listG its overflow.  The
   // first kernel routes every pair it cannot finish to the tier matching its estimated distance; a tier that is too
-  // narrow appends the pair to the next list.  cnt[32 + t] = length of lists[t].
+  // narrow appends the pair to the next list.  rc[t] = length of lists[t].
   uint32_t* const lists = todo;
   uint32_t* listG = todo + (size_t)(NT + 1) * n_tasks;
-  uint32_t* const rc = cnt + 32;
-  HIP_TRY(ctx, hipMemsetAsync(rc, 0, 16 * sizeof(uint32_t), ctx->stream));      // rc[0 .. NT], then (cnt + 44 ..) the counters of the sampling router
+  uint32_t* const rc = cnt->routes.len;
   // The two three-block tiers pay where their lists are long (a pair pays for the band of its tier: <3,8> and <3,16> take what would run on tiers
   // 1.45 x as costly — edit stage 723 -> 664 ms on the 1-10 kb shard, the reassignment pass of a batch with clipped reads likewise) and cost a
   // launch each — sort + a kernel that lasts as long as its longest pair, ~2 ms — where they are short (a batch of 1 000 regions, the reassignment
   // pass of fully spanning reads).  The batches of a job are alike, so each kind of pass decides from what its previous pass saw: an optional tier
   // that ran stays while it got 20 000 pairs, one that did not run comes in when the tier above it got 40 000.  No history: by the task slots.
-  static const int tiers_env = getenv("OTG_EDIT_TIERS") ? atoi(getenv("OTG_EDIT_TIERS")) : 0;      // test switch: the tiers that run, as a bit mask (tier 0 and the last always do)
+  static const int tiers_env = otg_env_int("OTG_EDIT_TIERS", 0);      // test switch: the tiers that run, as a bit mask (tier 0 and the last always do)
   const int kind = ctx->edit_pass_kind & 1;
   uint32_t tier_mask = (n_tasks >= 2000000u && kind == 0) ? 0xFFu : 0xEBu;
   if (ctx->edit_hist && ctx->edit_hist_mask[kind] && hipEventQuery(ctx->edit_hist_ev[kind]) == hipSuccess) {
@@ -608,11 +604,11 @@ int otg_launch_edit_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_t
   }
   (void)hipGetLastError();
   if (tiers_env) tier_mask = ((uint32_t)tiers_env & 0xFFu) | 0x81u;
-  static const bool no_myers = getenv("OTG_NO_MYERS") != nullptr;
-  static const bool no_route = getenv("OTG_NO_EDIT_ROUTE") != nullptr;
+  static const bool no_myers = otg_env_set("OTG_NO_MYERS");
+  static const bool no_route = otg_env_set("OTG_NO_EDIT_ROUTE");
   // a tier that turns out too narrow costs about half of going one tier up straight away, so the cheapest choice sits a little below
   // the median estimate (measured at config 1: 0.85-0.92 flat optimum; OTG_EDIT_ROUTE_MARGIN overrides, in percent)
-  static const float route_margin = getenv("OTG_EDIT_ROUTE_MARGIN") ? (float)atoi(getenv("OTG_EDIT_ROUTE_MARGIN")) / 100.0f : 0.88f;
+  static const float route_margin = (float)otg_env_int("OTG_EDIT_ROUTE_MARGIN", 88) / 100.0f;
   if (kernel_ms) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   {
     // with the bit-parallel tiers behind it this pass only has to hold wavefronts of ~2 x cap diagonals: 1024 diagonals
@@ -623,31 +619,30 @@ int otg_launch_edit_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_t
       constexpr int CAP = 2048;                                // 2 x 2048 x u16 = 8 KB per wave -> 20 waves / CU
       uint32_t grid = std::min<uint32_t>((uint32_t)ctx->n_cu * 5, want);
       hipLaunchKernelGGL((wfa_edit_kernel_v2<CAP, WPB>), dim3(grid), dim3(WPB * 64), (size_t)CAP * 2 * WPB * sizeof(uint16_t), ctx->stream, d_arena, d_tasks,
-                         d_todo, d_n_todo, n_tasks, d_scores, d_cells, cnt + 0, rc + NT, lists + (size_t)NT * n_tasks, 0.0f,
+                         d_todo, d_n_todo, n_tasks, d_scores, d_cells, &cnt->wf_ticket, rc + NT, lists + (size_t)NT * n_tasks, 0.0f,
                          (uint32_t*)nullptr, lists, n_tasks, route_margin, tier_mask);
     } else {
       constexpr int CAP = 1024;
       uint32_t grid = std::min<uint32_t>((uint32_t)ctx->n_cu * 8, want);
-      const uint32_t* in = d_todo; const uint32_t* in_n = d_n_todo; uint32_t in_imm = n_tasks;
-      static const bool no_sample = getenv("OTG_NO_EDIT_SAMPLE") != nullptr;
+      OtgTodo in{d_todo, d_n_todo, n_tasks};
+      static const bool no_sample = otg_env_set("OTG_NO_EDIT_SAMPLE");
       if (!no_route && !no_sample) {
         // tier choice from two 64-base samples per pair (one pair per lane); only what it leaves goes through the wavefront pass
         uint32_t* wf_list = todo + (size_t)(NT + 3) * n_tasks;
         const uint32_t rg = std::min<uint32_t>((n_tasks + 255) / 256, (uint32_t)ctx->n_cu * 16);
         hipLaunchKernelGGL(edit_route_kernel, dim3(rg), dim3(256), 0, ctx->stream, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, 1.0f, rc, lists,
-                           n_tasks, route_margin, cnt + 44, wf_list, tier_mask);
-        in = wf_list; in_n = cnt + 44; in_imm = 0;
+                           n_tasks, route_margin, &cnt->routes.wf_len, wf_list, tier_mask);
+        in.next(wf_list, &cnt->routes.wf_len);
       }
       hipLaunchKernelGGL((wfa_edit_kernel_v2<CAP, WPB>), dim3(grid), dim3(WPB * 64), (size_t)CAP * 2 * WPB * sizeof(uint16_t), ctx->stream, d_arena, d_tasks,
-                         in, in_n, in_imm, d_scores, d_cells, cnt + 0, rc + 0, lists, 1.0f,
+                         in.list, in.n, in.imm, d_scores, d_cells, &cnt->wf_ticket, rc + 0, lists, 1.0f,
                          no_route ? (uint32_t*)nullptr : rc, lists, n_tasks, route_margin, tier_mask);
     }
   }
-  uint32_t dbg_routed[16] = {0};
-  if (getenv("OTG_DEBUG")) { (void)hipStreamSynchronize(ctx->stream); (void)hipMemcpy(dbg_routed, rc, sizeof(dbg_routed), hipMemcpyDeviceToHost); }      // what the routers sent where, before any tier passed pairs on
+  OtgCounters::ExactEdit::Routes dbg_routed{};
+  if (otg_env_set("OTG_DEBUG")) { (void)hipStreamSynchronize(ctx->stream); (void)hipMemcpy(&dbg_routed, &cnt->routes, sizeof(dbg_routed), hipMemcpyDeviceToHost); }      // what the routers sent where, before any tier passed pairs on
   if (!no_myers) {
-    uint32_t* const tick[NT] = {cnt + 2, cnt + 4, cnt + 6, cnt + 20, cnt + 22, cnt + 24, cnt + 26, cnt + 28};
-    static const bool no_sort = getenv("OTG_NO_EDIT_SORT") != nullptr;
+    static const bool no_sort = otg_env_set("OTG_NO_EDIT_SORT");
     uint32_t* sorted = todo + (size_t)(NT + 2) * n_tasks;
     uint32_t* hist = (uint32_t*)otg_slot(ctx, SLOT_ROWTAB, NT * SORT_BUCKETS * sizeof(uint32_t));
     if (!hist) return OTG_ERR_HIP;
@@ -666,17 +661,16 @@ int otg_launch_edit_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_t
         in = sorted;
       }
       const int rc_ = otg_launch_myers(ctx, tier, d_arena, d_tasks, in, rc + tier, n_tasks, d_scores, d_cells,
-                                       tick[tier], rc + next, lists + (size_t)next * n_tasks);
+                                       &cnt->tier_ticket[tier], rc + next, lists + (size_t)next * n_tasks);
       if (rc_) return rc_;
     }
   }
-  const uint32_t* cur = lists + (size_t)NT * n_tasks; const uint32_t* cur_n = rc + NT;
   {
     constexpr int CAP = 8192, WPB = 1;                         // 32 KB per wave -> 5 waves / CU, scores up to ~4000
     const size_t lds = (size_t)CAP * 2 * WPB * sizeof(uint16_t);
     uint32_t grid = (uint32_t)ctx->n_cu * 5;
     hipLaunchKernelGGL((wfa_edit_kernel_v2<CAP, WPB>), dim3(grid), dim3(WPB * 64), lds, ctx->stream, d_arena, d_tasks,
-                       cur, cur_n, 0u, d_scores, d_cells, cnt + 16, cnt + 17, listG, 0.0f, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, 1.0f, 0u);
+                       (const uint32_t*)(lists + (size_t)NT * n_tasks), (const uint32_t*)(rc + NT), 0u, d_scores, d_cells, &cnt->wide.ticket, &cnt->wide.overflow, listG, 0.0f, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, 1.0f, 0u);
   }
   {
     // last tier: global-memory wavefront sized for the longest possible pair; only reached by huge inputs
@@ -686,7 +680,7 @@ int otg_launch_edit_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_t
     int32_t* ws = (int32_t*)otg_slot(ctx, SLOT_WF_WS, (size_t)grid * WPB * (size_t)gcap * sizeof(int32_t));
     if (!ws) return OTG_ERR_HIP;
     hipLaunchKernelGGL((wfa_edit_kernel<0, WPB, true>), dim3(grid), dim3(WPB * 64), 0, ctx->stream, d_arena, d_tasks,
-                       (const uint32_t*)listG, (const uint32_t*)(cnt + 17), 0u, d_scores, d_cells, cnt + 18, cnt + 19,
+                       (const uint32_t*)listG, (const uint32_t*)&cnt->wide.overflow, 0u, d_scores, d_cells, &cnt->last.ticket, &cnt->last.overflow,
                        (uint32_t*)nullptr, ws, gcap);
   }
   if (kernel_ms) HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));      // after the LAST tier of the chain
@@ -695,26 +689,20 @@ int otg_launch_edit_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_t
       HIP_TRY(ctx, hipHostMalloc((void**)&ctx->edit_hist, 32 * sizeof(uint32_t), hipHostMallocDefault));
       for (int i = 0; i < 2; ++i) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->edit_hist_ev[i], hipEventDisableTiming));
     }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->edit_hist + 16 * kind, rc, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->edit_hist + 16 * kind, &cnt->routes, sizeof(cnt->routes), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->edit_hist_ev[kind], ctx->stream));
     ctx->edit_hist_mask[kind] = tier_mask;
   }
   HIP_TRY(ctx, hipGetLastError());
-  if (getenv("OTG_DEBUG")) {
+  if (otg_env_set("OTG_DEBUG")) {
     hipError_t er = hipStreamSynchronize(ctx->stream);
-    uint32_t h[48];
-    (void)hipMemcpy(h, cnt, sizeof(h), hipMemcpyDeviceToHost);
+    OtgCounters::ExactEdit h;
+    (void)hipMemcpy(&h, cnt, sizeof(h), hipMemcpyDeviceToHost);
+    const uint32_t* hl = h.routes.len;
     fprintf(stderr, "[otg] edit (tiers %02x): %s; wavefront pass input %u; inputs of the bit-parallel tiers 0..7: %u %u %u %u %u %u %u %u, wide wavefront tier %u, its overflow %u\n",
-            tier_mask, hipGetErrorString(er), h[44], h[32], h[33], h[34], h[35], h[36], h[37], h[38], h[39], h[40], h[17]);
+            tier_mask, hipGetErrorString(er), h.routes.wf_len, hl[0], hl[1], hl[2], hl[3], hl[4], hl[5], hl[6], hl[7], hl[NT], h.wide.overflow);
     fprintf(stderr, "[otg] edit:   of which routed there directly: %u %u %u %u %u %u %u %u (the rest came up from the tier below: its band was too narrow)\n",
-            dbg_routed[0], dbg_routed[1], dbg_routed[2], dbg_routed[3], dbg_routed[4], dbg_routed[5], dbg_routed[6], dbg_routed[7]);
+            dbg_routed.len[0], dbg_routed.len[1], dbg_routed.len[2], dbg_routed.len[3], dbg_routed.len[4], dbg_routed.len[5], dbg_routed.len[6], dbg_routed.len[7]);
   }
-  if (kernel_ms) {
-    HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
-    float ms = 0;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    *kernel_ms += ms;
-    if (launches) *launches += 1;
-  }
-  return OTG_OK;
+  return otg_timer_add(ctx, kernel_ms, launches);
 }
