@@ -161,6 +161,32 @@ int otg_affine_align_batch(otg_ctx* ctx,
                            uint8_t* cigar_arena, uint64_t cigar_capacity, uint64_t* cigar_bytes_used,
                            uint64_t* cells_out);
 
+/* Which tier of the exact gap-affine chain was given each alignment of the latest otg_affine_align_batch on this context, and which one
+ * finished it.  Test and measurement hook, read-only; the reference has no counterpart.  Valid directly behind that call
+ * with the same n_tasks; OTG_ERR_ARG (with a message) when the last tier chain launched on the context was another one (edit distance,
+ * an adaptive chain, a region pipeline's launch on a list of slots), when that launch failed or had another task count, after otg_trim,
+ * or when the context's heuristic is OTG_HEURISTIC_WFADAPTIVE.  Waits for the stream and copies the chain's counters, lists and bounds back.
+ * Per task:
+ *   bound_out     the score bound U of the bound pass in units of gcd(x, o+e, e) (INT32_MAX: the pass found none), -1 when the
+ *                 launch ran without a bound pass;
+ *   routed_out    the tier the counting sort assigned: 0..4 = the register tiers of 1024 / 1536 / 2048 / 4096 / 8192 diagonals,
+ *                 5 = none, straight to tier A (every task when the register tiers did not run);
+ *   finished_out  the tier that wrote the result: 0..4 a register tier, 5 = HBM-row tier A, 6 = tier B, 7 = the generic kernel,
+ *                 -2 = the generic kernel gave up too (the task's score is negative).
+ * counts_out / lists_out, both NULL or both given, receive the same launch's raw lists from the same snapshot.  counts_out[OTG_AFFINE_N_COUNTS]:
+ * [0..6] the counting sort's segment bounds (register tier t owns sorted[counts[t] .. counts[t+1]), [5]..[6] is what no register tier
+ * takes), [7] length of tier A's input (that rest, then what the register tiers gave up, appended), [8] what tier A gave up, [9] what
+ * tier B gave up.  lists_out[4 * n_tasks]: tier A's give-ups | tier B's give-ups | the sort's output | tier A's input, each in a stride
+ * of n_tasks; only the lengths above are meaningful.  Lists a launch did not write (no register tiers, no HBM-row tiers) have length 0.
+ * Returns the mask of register tiers that ran (bit t = tier t; >= 0), or a negative error code. */
+#define OTG_AFFINE_TIER_NONE  5
+#define OTG_AFFINE_FIN_A      5
+#define OTG_AFFINE_FIN_B      6
+#define OTG_AFFINE_FIN_C      7
+#define OTG_AFFINE_N_COUNTS   10
+int otg_affine_last_routing(otg_ctx* ctx, uint32_t n_tasks, int32_t* bound_out, int8_t* routed_out, int8_t* finished_out,
+                            uint32_t* counts_out, uint32_t* lists_out);
+
 /* ================================================================= L2: per-region operators */
 
 /* Replaces otter_hclust (src/otterclust.cpp:118-320) incl. otter_find_clustering_dist (:20-116),

@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(HERE, "libotter_gpu.so")
 
 EXPORTS = [
     "otg_params_default", "otg_create", "otg_destroy", "otg_trim", "otg_last_error", "otg_device_count", "otg_exp_variant", "otg_set_heuristic",
-    "otg_edit_distance_batch", "otg_affine_align_batch", "otg_cluster_batch", "otg_poa_consensus_batch",
+    "otg_edit_distance_batch", "otg_affine_align_batch", "otg_affine_last_routing", "otg_cluster_batch", "otg_poa_consensus_batch",
     "otg_genotype_cluster_batch", "otg_last_kernel_ms", "otg_assemble_submit", "otg_assemble_run", "otg_assemble_result_sizes",
     "otg_assemble_collect", "otg_assemble_device_results", "otg_assemble_stats", "otg_assemble_realign", "otg_assemble_collect_reads",
     "otg_emit_alleles", "otg_emit_sam_header",
@@ -204,6 +204,24 @@ class Context:
         self._check(rc, "otg_affine_align_batch")
         cigs = [out[int(off[i]):int(off[i]) + int(ln[i])].tobytes() for i in range(n)]
         return (scores, cigs, cells) if want_cells else (scores, cigs)
+
+    def affine_last_routing(self, n_tasks):
+        """otg_affine_last_routing for the affine_align_batch just made on this context (same n_tasks): which tier the counting sort gave
+        each alignment and which tier finished it.  Returns a dict: `bound`, `routed`, `finished` (one entry per task; abi.AFFINE_*),
+        `mask` (the register tiers that ran), `seg` (the sort's 7 segment bounds), and the chain's lists cut to their lengths: `sorted`,
+        `tier_a_input`, `tier_a_gave_up`, `tier_b_gave_up`."""
+        n = int(n_tasks)
+        bound = np.zeros(n, dtype=np.int32)
+        routed = np.zeros(n, dtype=np.int8)
+        finished = np.zeros(n, dtype=np.int8)
+        counts = np.zeros(abi.AFFINE_N_COUNTS, dtype=np.uint32)
+        lists = np.zeros((4, max(n, 1)), dtype=np.uint32)
+        mask = self._L.otg_affine_last_routing(self._h, C.c_uint32(n), abi.ptr(bound), abi.ptr(routed), abi.ptr(finished), abi.ptr(counts), abi.ptr(lists))
+        if mask < 0:
+            self._check(mask, "otg_affine_last_routing")
+        return {"bound": bound, "routed": routed, "finished": finished, "mask": int(mask), "seg": counts[:7].astype(np.int64),
+                "tier_a_gave_up": lists[0, :int(counts[8])].copy(), "tier_b_gave_up": lists[1, :int(counts[9])].copy(),
+                "sorted": lists[2, :int(counts[6])].copy(), "tier_a_input": lists[3, :int(counts[7])].copy()}
 
     # ------------------------------------------------------------------ L2
     def cluster_batch(self, params, dist, dist_off, read_len, len_off, n_valid):

@@ -33,6 +33,16 @@ class otg_params(C.Structure):
 OTG_HEURISTIC_NONE = 0
 OTG_HEURISTIC_WFADAPTIVE = 1
 
+# otg_affine_last_routing: routed 0..4 = a register tier, AFFINE_TIER_NONE = straight to tier A; finished 0..4, AFFINE_FIN_A / _B / _C,
+# AFFINE_FIN_NOBODY = the generic kernel gave up too.  AFFINE_N_COUNTS = length of its counts_out.
+AFFINE_REG_TIERS = 5
+AFFINE_TIER_NONE = 5
+AFFINE_FIN_A = 5
+AFFINE_FIN_B = 6
+AFFINE_FIN_C = 7
+AFFINE_FIN_NOBODY = -2
+AFFINE_N_COUNTS = 10
+
 
 def default_params(**kw):
     """Reference CLI defaults (src/command_assemble.cpp:34-45, src/command_genotype.cpp:25-27)."""

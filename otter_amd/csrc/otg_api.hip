@@ -154,6 +154,7 @@ int otg_trim(otg_ctx* ctx)
     DevBuf& b = ctx->pool[slot];
     if (b.p) { HIP_TRY(ctx, hipFree(b.p)); b.p = nullptr; b.cap = 0; }
   }
+  ctx->last_chain = -1;      // the score bounds went with SLOT_BT_POOL: otg_affine_last_routing has nothing to read until the next launch
   return OTG_OK;
 }
 

@@ -36,6 +36,7 @@ G* otg_counters(otg_ctx* ctx, G OtgCounters::*group, size_t bytes = sizeof(G))
   const bool fresh = !ctx->pool[SLOT_COUNTERS].p;
   OtgCounters* c = (OtgCounters*)otg_slot(ctx, SLOT_COUNTERS, sizeof(OtgCounters));
   if (!c) return nullptr;
+  ctx->last_chain = (int)((const char*)&(c->*group) - (const char*)c);      // the chain that runs now owns what the accessors of the last launch read
   const hipError_t e = fresh ? hipMemsetAsync(c, 0, sizeof(OtgCounters), ctx->stream) : hipMemsetAsync(&(c->*group), 0, bytes, ctx->stream);
   if (e != hipSuccess) { otg_fail(ctx, OTG_ERR_HIP, "zeroing the chain counters failed"); return nullptr; }
   return &(c->*group);

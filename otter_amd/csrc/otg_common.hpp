@@ -45,6 +45,18 @@ struct otg_ctx {
   double last_kernel_ms = 0.0;                    // HIP-event time of the kernels of the latest operator-level call that reports one (otg_last_kernel_ms)
   // aligner heuristic of the L1 calls and of the running pipeline (otg_set_heuristic / otg_params.heuristic; wfa_adaptive.hip)
   int heur_strategy = OTG_HEURISTIC_NONE, heur_min_wf_len = 10, heur_max_dist = 50, heur_steps = 1;
+  // What the latest tier chain on this context left behind, for otg_affine_last_routing: which chain it was (the byte offset of its group in
+  // OtgCounters, set by otg_counters; -1: none yet) and, recorded by otg_launch_affine_todo once a launch is enqueued whole (n_tasks = 0 until then), the shape of the exact gap-affine launch whose
+  // counters, lists (SLOT_TODO) and bounds (SLOT_BT_POOL) are still on the device.
+  int last_chain = -1;
+  struct AffineLast {
+    uint32_t n_tasks = 0;
+    bool hbm_tiers = false;         // tiers A and B ran (false: the generic kernel alone)
+    bool bounded = false;           // the score-bound pass ran
+    bool sublist = false;           // the launch worked on a list of task slots, not on all of them
+    int reg_mask = 0;               // register tiers that ran (0: no sort either)
+    const void* scores_at = nullptr;   // where the launch wrote its scores; compared with SLOT_SCORES before that slot is read, never dereferenced
+  } affine_last;
   // cohort staging area of otg_cohort_begin .. otg_cohort_end (cohort.hip); created on first use
   struct Cohort* cohort = nullptr;
 };

@@ -13,7 +13,8 @@
 //      cannot take or give up: bytes outside ACGT, no bound, windows beyond 8192 diagonals, a full match-run queue;
 //   5. the generic kernel (any penalties, any lengths; int32 rings in HBM).
 // Every tier writes one provenance byte per kept (score, diagonal) cell into a per-alignment slab and shares the backtrace
-// (wfa_affine_common.hpp).  An alignment a tier cannot finish is queued on the device for the next one.
+// (wfa_affine_common.hpp).  An alignment a tier cannot finish is queued on the device for the next one.  Who was given what and who finished it
+// can be read back after a launch: otg_affine_last_routing at the end of this file (host code; include/otter_gpu.h).
 #include "wfa_affine_common.hpp"
 #include "wfa_affine_reg.hpp"
 #include "otg_chain.hpp"
@@ -845,6 +846,7 @@ int otg_launch_affine_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align
                            float* kernel_ms, uint64_t* launches)
 {
   if (n_tasks == 0) return OTG_OK;
+  ctx->affine_last = {};                     // otg_affine_last_routing describes this launch once it is enqueued whole, and none until then
   if (ctx->heur_strategy == OTG_HEURISTIC_WFADAPTIVE)
     return otg_launch_affine_adaptive_todo(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, x, o, e, d_scores, d_cig_off, d_cig_len, d_cig_arena, d_cells,
                                            kernel_ms, launches);
@@ -1061,6 +1063,9 @@ int otg_launch_affine_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align
                      d_cig_arena, d_cells, &cnt->c.ticket, &cnt->c.overflow, (uint32_t*)nullptr, wsC);
   if (kernel_ms) HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));      // after the LAST tier of the chain
   HIP_TRY(ctx, hipGetLastError());
+  // what otg_affine_last_routing needs to read this launch's counters, lists and bounds back
+  ctx->affine_last.n_tasks = n_tasks; ctx->affine_last.hbm_tiers = !no_v3 && es == 1; ctx->affine_last.bounded = bounded;
+  ctx->affine_last.sublist = d_todo != nullptr; ctx->affine_last.reg_mask = reg_mask; ctx->affine_last.scores_at = d_scores;
   if (ws.dbg) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     OtgCounters::ExactAffine h;
@@ -1115,4 +1120,65 @@ int otg_launch_affine_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align
 #endif
   }
   return otg_timer_add(ctx, kernel_ms, launches);
+}
+
+// ---- which tier the sort gave every alignment of the latest launch, and which tier finished it (include/otter_gpu.h).  Host code only: the
+// launch zeroes its counters and rewrites its lists, so what is on the device behind a launch describes that launch and no earlier one.
+extern "C" int otg_affine_last_routing(otg_ctx* ctx, uint32_t n_tasks, int32_t* bound_out, int8_t* routed_out, int8_t* finished_out,
+                                       uint32_t* counts_out, uint32_t* lists_out)
+{
+  const char* const who = "otg_affine_last_routing";
+  if (!ctx) return otg_fail(nullptr, OTG_ERR_ARG, "%s: NULL context", who);
+  if (!bound_out || !routed_out || !finished_out || !counts_out != !lists_out) return otg_fail(ctx, OTG_ERR_ARG, "%s: NULL argument", who);
+  const otg_ctx::AffineLast& L = ctx->affine_last;
+  if (ctx->heur_strategy != OTG_HEURISTIC_NONE) return otg_fail(ctx, OTG_ERR_ARG, "%s: the context's heuristic is WFadaptive; only the exact gap-affine chain is accounted for", who);
+  if (ctx->last_chain != (int)offsetof(OtgCounters, exact_affine) || !ctx->pool[SLOT_COUNTERS].p || !ctx->pool[SLOT_TODO].p)
+    return otg_fail(ctx, OTG_ERR_ARG, "%s: the last tier chain launched on this context was not the exact gap-affine chain", who);
+  if (n_tasks == 0 || n_tasks != L.n_tasks) return otg_fail(ctx, OTG_ERR_ARG, "%s: the last gap-affine launch had %u tasks, not %u", who, L.n_tasks, n_tasks);
+  if (L.sublist) return otg_fail(ctx, OTG_ERR_ARG, "%s: the last gap-affine launch worked on a list of task slots (the region pipeline's), not on a whole batch", who);
+  if (ctx->pool[SLOT_TODO].cap < 4 * (size_t)n_tasks * sizeof(uint32_t) || (L.bounded && ctx->pool[SLOT_BT_POOL].cap < (size_t)n_tasks * sizeof(int32_t)))
+    return otg_fail(ctx, OTG_ERR_ARG, "%s: the workspaces of the last gap-affine launch have been released", who);
+  // the scores are read from the context's own slot, and only while it is the buffer the launch wrote (otg_affine_align_batch's; a caller's buffer, or a slot that has moved since, is not followed)
+  if (!L.scores_at || L.scores_at != ctx->pool[SLOT_SCORES].p || ctx->pool[SLOT_SCORES].cap < (size_t)n_tasks * sizeof(int32_t))
+    return otg_fail(ctx, OTG_ERR_ARG, "%s: the scores of the last gap-affine launch are not in the context's score buffer (any more)", who);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));        // the side streams of the register tiers join the main stream in front of tier A
+  OtgCounters::ExactAffine c;
+  HIP_TRY(ctx, hipMemcpy(&c, &((const OtgCounters*)ctx->pool[SLOT_COUNTERS].p)->exact_affine, sizeof(c), hipMemcpyDeviceToHost));
+  std::vector<uint32_t> lists(4 * (size_t)n_tasks);      // what tier A gave up | what tier B gave up | the sort's output | the input of tier A
+  HIP_TRY(ctx, hipMemcpy(lists.data(), ctx->pool[SLOT_TODO].p, lists.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  std::vector<int32_t> sc(n_tasks);
+  HIP_TRY(ctx, hipMemcpy(sc.data(), ctx->pool[SLOT_SCORES].p, (size_t)n_tasks * sizeof(int32_t), hipMemcpyDeviceToHost));
+  // lists that this launch did not write hold whatever an earlier one left: their lengths count as zero
+  if (!L.hbm_tiers) c.a.overflow = c.b.overflow = 0;
+  if (!L.reg_mask) { for (uint32_t& x : c.seg) x = 0; c.reg_overflow = 0; }
+  const uint32_t rest = c.seg[OTG_REG_TIERS + 1] - c.seg[OTG_REG_TIERS];      // the sort's last segment: alignments no register tier takes
+  bool sane = c.a.overflow <= n_tasks && c.b.overflow <= n_tasks && c.reg_overflow <= n_tasks && c.seg[OTG_REG_TIERS + 1] <= n_tasks;
+  for (int t = 0; t <= OTG_REG_TIERS; ++t) sane = sane && c.seg[t] <= c.seg[t + 1];
+  if (!sane) return otg_fail(ctx, OTG_ERR_FATAL, "%s: the chain's counters are inconsistent (segment end %u, register tiers hand on %u, tier A %u, tier B %u of %u tasks)", who,
+                             c.seg[OTG_REG_TIERS + 1], c.reg_overflow, c.a.overflow, c.b.overflow, n_tasks);
+  const uint32_t len[4] = {c.a.overflow, c.b.overflow, c.seg[OTG_REG_TIERS + 1], c.reg_overflow};
+  for (int l = 0; l < 4; ++l) for (uint32_t i = 0; i < len[l]; ++i)
+    if (lists[(size_t)l * n_tasks + i] >= n_tasks) return otg_fail(ctx, OTG_ERR_FATAL, "%s: list %d holds task %u of %u at position %u", who, l, lists[(size_t)l * n_tasks + i], n_tasks, i);
+  const uint32_t *listA = lists.data(), *listB = listA + n_tasks, *sorted = listB + n_tasks, *ovf_r = sorted + n_tasks;
+  if (L.bounded) HIP_TRY(ctx, hipMemcpy(bound_out, ctx->pool[SLOT_BT_POOL].p, (size_t)n_tasks * sizeof(int32_t), hipMemcpyDeviceToHost));
+  else for (uint32_t i = 0; i < n_tasks; ++i) bound_out[i] = -1;
+  constexpr int8_t NONE = OTG_REG_TIERS, FIN_A = OTG_REG_TIERS, FIN_B = OTG_REG_TIERS + 1, FIN_C = OTG_REG_TIERS + 2;
+  if (L.reg_mask) {
+    // -1 stays where the sort lost a task: the caller sees it
+    for (uint32_t i = 0; i < n_tasks; ++i) { routed_out[i] = -1; finished_out[i] = -1; }
+    for (int t = 0; t <= OTG_REG_TIERS; ++t) for (uint32_t i = c.seg[t]; i < c.seg[t + 1]; ++i) { routed_out[sorted[i]] = (int8_t)t; finished_out[sorted[i]] = (int8_t)t; }
+    for (uint32_t i = rest; i < c.reg_overflow; ++i) finished_out[ovf_r[i]] = FIN_A;      // appended by the register tiers behind the rest segment
+  } else {
+    for (uint32_t i = 0; i < n_tasks; ++i) { routed_out[i] = NONE; finished_out[i] = L.hbm_tiers ? FIN_A : FIN_C; }
+  }
+  for (uint32_t i = 0; i < c.a.overflow; ++i) finished_out[listA[i]] = FIN_B;
+  for (uint32_t i = 0; i < c.b.overflow; ++i) finished_out[listB[i]] = FIN_C;
+  for (uint32_t i = 0; i < n_tasks; ++i) if (finished_out[i] == FIN_C && sc[i] < 0) finished_out[i] = -2;      // the generic kernel has no list: it leaves a negative score
+  if (counts_out) {
+    for (int t = 0; t < OTG_REG_TIERS + 2; ++t) counts_out[t] = c.seg[t];
+    counts_out[OTG_REG_TIERS + 2] = c.reg_overflow; counts_out[OTG_REG_TIERS + 3] = c.a.overflow; counts_out[OTG_REG_TIERS + 4] = c.b.overflow;
+    memcpy(lists_out, lists.data(), lists.size() * sizeof(uint32_t));
+  }
+  return L.reg_mask;
 }

@@ -57,6 +57,22 @@ def test_default_params_match_reference_cli():
     assert (p.max_error, p.bandwidth_short, p.bandwidth_long, p.min_sim) == (0.01, 0.01, 0.015, 0.9)
 
 
+def test_affine_routing_entry():
+    """otg_affine_last_routing: exported, its tier codes mirrored in abi.py, and a call without a context or without
+    output arrays is OTG_ERR_ARG with a message, not a crash."""
+    txt = open(HEADER).read()
+    defs = dict(re.findall(r"#define\s+(OTG_AFFINE_[A-Z_]+)\s+(-?\d+)", txt))
+    assert {k: int(v) for k, v in defs.items()} == {"OTG_AFFINE_TIER_NONE": abi.AFFINE_TIER_NONE, "OTG_AFFINE_FIN_A": abi.AFFINE_FIN_A, "OTG_AFFINE_FIN_B": abi.AFFINE_FIN_B,
+                                                    "OTG_AFFINE_FIN_C": abi.AFFINE_FIN_C, "OTG_AFFINE_N_COUNTS": abi.AFFINE_N_COUNTS}
+    assert abi.AFFINE_TIER_NONE == abi.AFFINE_REG_TIERS == 5 and abi.AFFINE_N_COUNTS == abi.AFFINE_REG_TIERS + 5
+    lib = otter_amd.load()
+    assert "otg_affine_last_routing" in otter_amd.EXPORTS
+    b, r, f = np.zeros(4, np.int32), np.zeros(4, np.int8), np.zeros(4, np.int8)
+    assert lib.otg_affine_last_routing(None, C.c_uint32(4), abi.ptr(b), abi.ptr(r), abi.ptr(f), None, None) == abi.OTG_ERR_ARG
+    assert b"NULL context" in lib.otg_last_error(None)
+    assert lib.otg_affine_last_routing(None, C.c_uint32(4), None, None, None, None, None) == abi.OTG_ERR_ARG
+
+
 def test_no_silent_cpu_fallback():
     if otter_amd.device_count() > 0:
         pytest.skip("a GPU is present")

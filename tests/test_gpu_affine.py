@@ -138,9 +138,12 @@ def test_affine_non_acgt_bytes(gpu, oracle):
 
 
 def test_affine_lds_tier_admission_sweep(gpu, oracle):
-    """Alignments whose score bound sits right at the admission limit of each tier (LDS tiers: windows of 1024 / 1472 / 2048 / 4096
+    """Alignments whose optimal score sits right at the window sizes of the tiers (LDS tiers: windows of 1024 / 1472 / 2048 / 4096
     diagonals; register tiers: 1024 / 1536 / 2048 / 4096 / 8192): one long gap (reduced score = gap length + 3) or two gaps in opposite directions, early and late
-    in the sequence.  Whether such an alignment is admitted to a tier or passed on, op string and score must match."""
+    in the sequence.  Whichever tier such an alignment ends up on, op string and score must match.  (The tiers admit by the score BOUND, and across
+    a gap of G bases the bound pass gives about 2 G, or none beyond pattern + text + 64 scores: these pairs run a tier or two above the window their
+    optimum names, most of the larger ones on the HBM-row tiers.  The admission limits themselves, wanted window = capacity - 1 and = capacity, are
+    swept by test_gpu_affine_routing.py::test_routing_window_edge.)"""
     rng = np.random.default_rng(27)
     pairs = []
     L = 900

@@ -19,10 +19,14 @@ AFFINE_ALL_BUT_ADMISSION = ["tests/test_gpu_affine.py::" + t for t in (
     "test_affine_small_mixed", "test_affine_other_penalties", "test_affine_long_ont", "test_affine_cigar_valid_full_size", "test_affine_bounded_tandem_repeats",
     "test_affine_non_acgt_bytes", "test_affine_packed_sequence_capacity_sweep", "test_affine_probe_boundaries", "test_affine_wide_free_begin")]
 
+# which tier finishes what (test_gpu_affine_routing.py): every instantiation of a register window, and every way of launching the tiers, must finish what it
+# admits; without the register tiers the accounting must say so
+ROUTING = "tests/test_gpu_affine_routing.py"
+
 CASES = [
     ("OTG_NO_AFFINE_BOUND", ["tests/test_gpu_affine.py"]),                               # no score bound: everything on the HBM-row tiers, un-pruned
-    ("OTG_AFFINE_REG=0", ["tests/test_gpu_affine.py"]),                                  # bound + HBM-row tiers only (what the register tiers fall back to)
-    ("OTG_AFFINE_REG=25", AFFINE_ALL_BUT_ADMISSION + ["tests/test_gpu_poa.py"]),        # register tiers 1024 / 4096 / 8192 only: the 1536 / 2048 windows on the multi-wave tier
+    ("OTG_AFFINE_REG=0", ["tests/test_gpu_affine.py", ROUTING]),                              # bound + HBM-row tiers only (what the register tiers fall back to)
+    ("OTG_AFFINE_REG=25", AFFINE_ALL_BUT_ADMISSION + ["tests/test_gpu_poa.py", ROUTING]),      # register tiers 1024 / 4096 / 8192 only: the 1536 / 2048 windows on the multi-wave tier
     ("OTG_NO_AFFINE_V3", AFFINE_CORE),                                                   # generic kernel only
     ("OTG_NO_MYERS", ["tests/test_gpu_edit.py::test_edit_small_mixed", "tests/test_gpu_edit.py::test_edit_long_ont"]),
     ("OTG_NO_EDIT_ROUTE OTG_NO_EDIT_SORT", ["tests/test_gpu_edit.py"]),
@@ -33,10 +37,10 @@ CASES = [
     ("OTG_POA_PIECE_MB=1", ["tests/test_gpu_poa.py", "tests/test_gpu_pipeline.py::test_ont_kb"]),         # graph images in many small pieces that reuse the work arrays
     ("OTG_NO_REASSIGN_REV", ["tests/test_gpu_pipeline.py::test_haps_mode", "tests/test_gpu_pipeline.py::test_ont_kb"]),
     ("OTG_CLUSTER_WIDE=1", ["tests/test_gpu_cluster.py", "tests/test_gpu_genotype.py", "tests/test_gpu_pipeline.py::test_edge_regions"]),   # every region on the wide clustering kernels (HBM scratch)
-    ("OTG_REG_SHAPE=11210", AFFINE_CORE),                                                # the other instantiation of every register window: <2,4>, <1,12> at 4 waves, <1,16>, <8,4>
-    ("OTG_REG_SHAPE=2200", AFFINE_CORE),                                                 # <2,6> for the 1536 window, <1,16> without spills for the 2048 one
-    ("OTG_AFFINE_CONCURRENT=1", AFFINE_CORE),                                            # register tiers side by side on three streams whatever the batch size
-    ("OTG_AFFINE_CONCURRENT=0", ["tests/test_gpu_affine.py::test_affine_small_mixed", "tests/test_gpu_pipeline.py::test_ont_kb"]),   # ... and one after the other on a small batch
+    ("OTG_REG_SHAPE=11210", AFFINE_CORE + [ROUTING]),                                      # the other instantiation of every register window: <2,4>, <1,12> at 4 waves, <1,16>, <8,4>
+    ("OTG_REG_SHAPE=2200", AFFINE_CORE + [ROUTING]),                                      # <2,6> for the 1536 window, <1,16> without spills for the 2048 one
+    ("OTG_AFFINE_CONCURRENT=1", AFFINE_CORE + [ROUTING]),                                 # register tiers side by side on three streams whatever the batch size
+    ("OTG_AFFINE_CONCURRENT=0", ["tests/test_gpu_affine.py::test_affine_small_mixed", "tests/test_gpu_pipeline.py::test_ont_kb", ROUTING]),   # ... and one after the other on a small batch
     # the adaptive mode's tier chains (wfa_adaptive.hip): byte-probe tiers only; the wide packed tier first; the 1024-diagonal LDS tier / the int32 tier alone for the gap-affine aligner
     ("OTG_ADAPTIVE_EDIT_TIERS=12", ["tests/test_gpu_adaptive.py::test_adaptive_edit_small", "tests/test_gpu_adaptive.py::test_adaptive_edit_long", "tests/test_gpu_adaptive.py::test_adaptive_edit_wide_and_huge"]),
     ("OTG_ADAPTIVE_NO_WIDE_START", ["tests/test_gpu_adaptive.py::test_adaptive_edit_small", "tests/test_gpu_adaptive.py::test_adaptive_edit_wide_and_huge", "tests/test_gpu_adaptive.py::test_adaptive_pipeline_hifi_and_haps"]),
