@@ -20,7 +20,10 @@
 // Pattern match masks (A, C, G, T + at most one further byte value occurring in the pattern, e.g. N) are built
 // once per pair into an L2-resident scratch and fetched when a lane moves to its next superblock; richer
 // alphabets, text-side free ends and patterns > 16384 bytes go to the wavefront kernel.
+// The column step of a block (myers_step.hpp) works on 32-bit halves with three-input bit operations: what a vector instruction costs on
+// gfx950 depends on its class, and the tiers are bound by vector issue.
 #include "otg_common.hpp"
+#include "myers_step.hpp"
 #include <cstdlib>
 
 namespace {
@@ -71,7 +74,9 @@ __global__ __launch_bounds__(WPB * 64) void myers_edit_kernel(
   // per-step fetch `row(symbol of this column)` is one conflict-free ds_read_b64 instead of a select tree.
   // sym: 0..3 = A C T G (code (byte >> 1) & 3), 4 = the one extra byte value of the pattern, 5 = anything else (zero).
   __shared__ u64 s_eq[6 * BPL][NT];
-  // byte -> row index (sym * BPL) per lane group; text bytes are translated when a lane loads its next 8 columns
+  // byte -> row index (sym * BPL) * 8 per lane group; text bytes are translated when a lane loads its next 8 columns.  The entry sits
+  // in bits 8..15 of a 16-bit field of the translated text, where it IS the byte offset of the row in s_eq (row * NT * 8 = row * 8 << 8).
+  static_assert(NT * sizeof(u64) == (8u << 8) && 5 * BPL * 8 < 256, "a row's byte offset must be its 8-bit map entry shifted by 8");
   __shared__ uint8_t s_lut[WPB * G][256];
   const int lane = threadIdx.x & 63;
   const int wib = threadIdx.x >> 6;
@@ -83,13 +88,14 @@ __global__ __launch_bounds__(WPB * 64) void myers_edit_kernel(
   using lds_u8 = __attribute__((address_space(3))) uint8_t;
   volatile lds_u64* EQ = (volatile lds_u64*)&s_eq[0][0] + threadIdx.x;          // this thread's column; row r at EQ[r * NT]
   volatile lds_u8* LUT = (volatile lds_u8*)&s_lut[wib * G + grp][0];
+  const uint32_t eq_addr = (uint32_t)(uintptr_t)(lds_u64*)&s_eq[0][0] + threadIdx.x * (uint32_t)sizeof(u64);     // LDS byte address of this thread's column
   {
     // static part of the tables: zero rows, ACGT entries of the byte map (the extra symbol is patched per pair)
 #pragma unroll
     for (int q = 0; q < BPL; ++q) EQ[(5 * BPL + q) * NT] = 0ull;
     for (int c = gl; c < 256; c += GL) {
       const uint32_t code = ((uint32_t)c >> 1) & 3u;
-      LUT[c] = (uint8_t)(((uint32_t)c == ((0x47544341u >> (8 * code)) & 0xffu) ? code : 5u) * BPL);
+      LUT[c] = (uint8_t)(((uint32_t)c == ((0x47544341u >> (8 * code)) & 0xffu) ? code : 5u) * BPL * 8);
     }
   }
   int lut_other = -1;                    // byte currently mapped to row 4 in this group's map
@@ -167,8 +173,8 @@ __global__ __launch_bounds__(WPB * 64) void myers_edit_kernel(
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     if (other != lut_other) {            // group-uniform
       if (gl == 0) {
-        if (lut_other >= 0) LUT[lut_other] = (uint8_t)(5 * BPL);
-        if (other >= 0) LUT[other] = (uint8_t)(4 * BPL);
+        if (lut_other >= 0) LUT[lut_other] = (uint8_t)(5 * BPL * 8);
+        if (other >= 0) LUT[other] = (uint8_t)(4 * BPL * 8);
       }
       lut_other = other;
     }
@@ -177,31 +183,34 @@ __global__ __launch_bounds__(WPB * 64) void myers_edit_kernel(
     int B = gl;                         // current superblock of this lane
     if (!unsupported) while (B < nsb && SB * B + SB - 1 + KL < 0) B += GL;      // (KL < 0: the band starts below diagonal 0, the superblocks above it never enter it)
     bool inited = false;
-    u64 Pv[BPL], Mv[BPL];
+    uint32_t PvL[BPL], PvH[BPL], MvL[BPL], MvH[BPL];     // vertical deltas of the lane's blocks, as 32-bit halves (myers_step.hpp)
 #pragma unroll
-    for (int q = 0; q < BPL; ++q) { Pv[q] = ~0ull; Mv[q] = 0; }
+    for (int q = 0; q < BPL; ++q) { PvL[q] = PvH[q] = ~0u; MvL[q] = MvH[q] = 0; }
     int score = 0, hout = 0;
     int best = 0x3fffffff;
     const int i_lo = m - pef;           // the answer is min over rows i in [i_lo, m] of D[i][n]
     if (i_lo <= 0) best = n;            // D[0][n] = n
     const int t_end = unsupported ? -1 : n - 1 + nsb - 1;
     // per-superblock time window (recomputed only when the lane moves to its next superblock)
-    int t_start, t_stop, t_hin_stop, t_last; bool exact_init;
+    // with u = t - t_start: in the band <=> (uint32_t)u < t_len, one unsigned compare; past it <=> u >= t_len as signed numbers
+    // (no window: t_len = 0 and t_start = INT_MAX, so u stays negative).  ends_sweep: the window's last column is the text's last one.
+    int t_start, t_len, t_hin_stop; bool ends_sweep, exact_init;
     auto setup = [&]() {
       int jlo = SB * B - KU; if (jlo < 0) jlo = 0;
       int jhi = SB * B + SB - 1 + KL; if (jhi > n - 1) jhi = n - 1;
       exact_init = (jlo == 0);
       if (!unsupported && B < nsb && jlo <= jhi) {
-        t_start = jlo + B; t_stop = jhi + B;
+        t_start = jlo + B; t_len = jhi - jlo + 1;
         int jh = SB * B - 1 + KL; if (jh > jhi) jh = jhi;
         t_hin_stop = B > 0 ? jh + B : -1;              // block above still inside the band
-        t_last = (jhi == n - 1) ? n - 1 + B : -1;
-      } else { t_start = 0x7fffffff; t_stop = 0x7ffffffe; t_hin_stop = -1; t_last = -1; }
+        ends_sweep = (jhi == n - 1);
+      } else { t_start = 0x7fffffff; t_len = 0; t_hin_stop = -1; ends_sweep = false; }
     };
     setup();
-    // text bytes: one unaligned 8-byte load per 8 steps and lane (prefetched 4 steps ahead); byte (t & 7) of c8
+    // text bytes: one unaligned 8-byte load per 8 steps and lane (prefetched 4 steps ahead); byte (t & 7) of it
     // is column (t & ~7) - B + (t & 7) = t - B
-    auto load_group = [&](int tg) -> u64 {              // tg = first step of the group; returns 8 row indices
+    struct Txt { uint32_t w[4]; };                      // 8 row offsets: step 2i in bits 0..15 of w[i], step 2i + 1 in bits 16..31
+    auto load_group = [&](int tg) -> Txt {              // tg = first step of the group
       int a = tg - B;
       if (a > n - 1) a = n - 1;
       u64 x;
@@ -210,10 +219,30 @@ __global__ __launch_bounds__(WPB * 64) void myers_edit_kernel(
       uint32_t r[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) r[i] = LUT[(uint32_t)(x >> (8 * i)) & 0xffu];
-      const uint32_t lo = r[0] | (r[1] << 8) | (r[2] << 16) | (r[3] << 24), hi = r[4] | (r[5] << 8) | (r[6] << 16) | (r[7] << 24);
-      return (u64)lo | ((u64)hi << 32);
+      Txt c;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) c.w[i] = __builtin_amdgcn_perm(r[2 * i + 1], r[2 * i], 0x040c000cu);       // (r[2i] << 8) | (r[2i+1] << 24)
+      return c;
     };
-    u64 c8 = load_group(0), c8n = 0;
+    Txt c8 = load_group(0), c8n = {{0, 0, 0, 0}};
+    // D[i][n] of the rows of the lane's superblock that may end the alignment; called once the window's last column is done, if ends_sweep:
+    // where the lane leaves the superblock, or after the sweep
+    auto harvest = [&]() {
+      const int row_top = SB * B;                     // rows row_top+1 .. row_top+SB
+      if (row_top + SB >= i_lo && row_top < m) {
+        int sc = score;
+#pragma unroll
+        for (int q = BPL - 1; q >= 0; --q) {
+          const u64 pv = (u64)PvH[q] << 32 | PvL[q], mv = (u64)MvH[q] << 32 | MvL[q];
+#pragma unroll 1
+          for (int r = 63; r >= 0; --r) {
+            const int i = row_top + 64 * q + r + 1;
+            if (i <= m && i >= i_lo && i >= 1 && sc < best) best = sc;
+            sc -= (int)((pv >> r) & 1ull) - (int)((mv >> r) & 1ull);
+          }
+        }
+      }
+    };
     // the wave runs until its longest pair is done
     int t_end_w = t_end;
     for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_xor(t_end_w, off); t_end_w = o > t_end_w ? o : t_end_w; }
@@ -224,7 +253,8 @@ __global__ __launch_bounds__(WPB * 64) void myers_edit_kernel(
       const int up_score = group_ror1<GL>(score, lane);
       const int up_hout = group_ror1<GL>(hout, lane);
       bool switched = false;
-      if (t > t_stop) {                 // this superblock left the band: move to the next one owned by the lane
+      if (t - t_start >= t_len) {       // this superblock left the band: move to the next one owned by the lane
+        if (ends_sweep) harvest();
         B += GL; inited = false; setup();
         c8 = load_group(t - ph);
         if (ph >= 4) c8n = load_group(t - ph + 8);
@@ -232,7 +262,7 @@ __global__ __launch_bounds__(WPB * 64) void myers_edit_kernel(
       }
       if (ph == 4) c8n = load_group(t + 4);
       else if (ph == 0 && t > 0 && !switched) c8 = c8n;     // (after a switch c8 is already this group's text; c8n still belongs to the old superblock)
-      if (t >= t_start && t <= t_stop) {
+      if ((uint32_t)(t - t_start) < (uint32_t)t_len) {
         if (!inited) {
 #pragma unroll
           for (int q = 0; q < BPL; ++q) {
@@ -240,62 +270,37 @@ __global__ __launch_bounds__(WPB * 64) void myers_edit_kernel(
             const bool have = b < nblk;
 #pragma unroll
             for (int y = 0; y < 5; ++y) EQ[(y * BPL + q) * NT] = have ? peq[b * 5 + (y == 2 ? 3 : y == 3 ? 2 : y)] : 0ull;   // rows A C T G X <- scratch A C G T X
-            Mv[q] = 0;
+            MvL[q] = MvH[q] = 0;
+            u64 pv0 = ~0ull;
             if (exact_init) {
               // true first column: D[i][0] = max(0, i - pbf)  ->  vertical delta +1 for rows i > pbf
               const int r0 = b << 6;                       // row i = r0 + bit + 1
               const int z = pbf - r0;                      // bits [0, z) are 0
-              Pv[q] = z <= 0 ? ~0ull : (z >= 64 ? 0ull : (~0ull << z));
-            } else Pv[q] = ~0ull;
+              pv0 = z <= 0 ? ~0ull : (z >= 64 ? 0ull : (~0ull << z));
+            }
+            PvL[q] = (uint32_t)pv0; PvH[q] = (uint32_t)(pv0 >> 32);
           }
           if (exact_init) { const int rows = SB * (B + 1); score = rows > pbf ? rows - pbf : 0; }
           else score = (up_score - up_hout) + SB;
           inited = true;
         }
-        const uint32_t row = (uint32_t)(c8 >> (8 * ph)) & 0xffu;               // sym * BPL of this column's text byte
+        // LDS address of the mask row of this column's text byte, in this thread's column
+        const uint32_t rowa = ((ph & 1) ? c8.w[ph >> 1] >> 16 : c8.w[ph >> 1] & 0xff00u) + eq_addr;
         int hin = t <= t_hin_stop ? up_hout : 1;
 #pragma unroll
         for (int q = 0; q < BPL; ++q) {
-          u64 Eq = EQ[(row + q) * NT];
-          const u64 pv = Pv[q], mv = Mv[q];
-          const u64 hneg = hin < 0 ? 1ull : 0ull;
-          const u64 Xv = Eq | mv;
-          Eq |= hneg;
-          const u64 Xh = (((Eq & pv) + pv) ^ pv) | Eq;
-          u64 Ph = mv | ~(Xh | pv);
-          u64 Mh = pv & Xh;
-          const int ho = (int)(Ph >> 63) - (int)(Mh >> 63);
-          Ph = (Ph << 1) | (hin > 0 ? 1ull : 0ull);
-          Mh = (Mh << 1) | hneg;
-          Pv[q] = Mh | ~(Xv | Ph);
-          Mv[q] = Ph & Xv;
-          hin = ho;
+          const u64 Eq = *(volatile lds_u64*)(uintptr_t)(rowa + (uint32_t)(q * NT * sizeof(u64)));
+          hin = otg_myers::block_step(PvL[q], PvH[q], MvL[q], MvH[q], (uint32_t)Eq, (uint32_t)(Eq >> 32), hin);
         }
         hout = hin;
         score += hout;
-        if (t == t_last) {
-          // last column: collect D[i][n] for the rows of this superblock that may end the alignment
-          const int row_top = SB * B;                     // rows row_top+1 .. row_top+SB
-          if (row_top + SB >= i_lo && row_top < m) {
-            int sc = score;
-#pragma unroll
-            for (int q = BPL - 1; q >= 0; --q) {
-              const u64 pv = Pv[q], mv = Mv[q];
-#pragma unroll 1
-              for (int r = 63; r >= 0; --r) {
-                const int i = row_top + 64 * q + r + 1;
-                if (i <= m && i >= i_lo && i >= 1 && sc < best) best = sc;
-                sc -= (int)((pv >> r) & 1ull) - (int)((mv >> r) & 1ull);
-              }
-            }
-          }
-        }
       }
     };
     for (int t8 = 0; t8 <= t_end_w; t8 += 8) {
       step(t8 + 0, 0); step(t8 + 1, 1); step(t8 + 2, 2); step(t8 + 3, 3);
       step(t8 + 4, 4); step(t8 + 5, 5); step(t8 + 6, 6); step(t8 + 7, 7);
     }
+    if (ends_sweep) harvest();          // the lane's last superblock ended with the sweep
     for (int off = GL / 2; off > 0; off >>= 1) { const int o = __shfl_xor(best, off, GL); best = o < best ? o : best; }
     const bool ok = !unsupported && best <= K;
     u64 w = 0;
@@ -344,7 +349,7 @@ int launch_one(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* d_tas
 // One tier of the bit-parallel engine: tasks from (d_todo, d_n_todo) (or all n_tasks when d_todo is null);
 // tasks it cannot finish exactly are appended to overflow_list / n_overflow.
 // tier (OTG_MYERS_TIERS of them): 0 = 8-lane groups x 1 block per lane (8 pairs / wave); then 8 / 16 / 32 / 64-lane groups x 2 blocks per lane
-//       (two blocks share the per-column overhead of a lane: ~19 % fewer instructions per row than one block per lane), with a three-block step
+//       (two blocks share the per-column overhead of a lane: ~14 % fewer SIMD cycles per row than one block per lane), with a three-block step
 //       between the 8- and 16-lane and between the 16- and 32-lane ones (<3,8> = 1352 rows at 0.7 x the cost of <2,16>, <3,16> = 2896 rows at
 //       0.7 x the cost of <2,32>: a pair pays for the band of its tier, not for its own); last = whole wave x 4 blocks per lane.
 int otg_launch_myers(otg_ctx* ctx, int tier, const uint8_t* d_arena, const otg_align_task* d_tasks, const uint32_t* d_todo,
