@@ -686,6 +686,29 @@ int otg_cohort_collect(otg_ctx* ctx, uint32_t* first_allele_out, otg_allele* all
                        int32_t* gt_out, int32_t* gt_l_out, int32_t* gt_k_out, double* hsd_out, int32_t* n_gt_out, int32_t* reps_out);
 int otg_cohort_end(otg_ctx* ctx);
 
+/* The k-mer usage matrix of the joint alleles (`otter vcf2mat` on the VCF of this batch, src/vcf2mat.cpp:23-46,66-72) without the VCF in
+ * between: after otg_cohort_genotype the alleles of every VCF line are selected on the device and the k-mer tiers of otg_kmer_usage_batch read
+ * them in the regrouped arena, in place.
+ *   otg_kmer_cohort_rows   builds the row list of the open, clustered batch (OTG_ERR_ARG "has not been clustered" before otg_cohort_genotype).
+ *                          A region with alleles contributes n_gt rows, the alleles of its VCF line in column order: row 0 its reference
+ *                          allele (the REF column), row i >= 1 the representative of ALT i (src/genotype.cpp:149-153).  A zero-length allele is
+ *                          the row of "N", as vcf2mat reads a lone <DEL> back (beside other ALT alleles vcf2mat counts the text "<DEL>" itself:
+ *                          otg_cohort_files substitutes that row in its matrix text, these building blocks do not).  *n_rows = the rows of the batch; row_first_out (n_regions + 1):
+ *                          the first row of every region; row_allele_out (n_rows): the row's allele, an index into the arrays of
+ *                          otg_cohort_collect; sample_gt_out (n_regions x n_samples x 2): the two GT numbers the VCF prints for a sample, -1 -1
+ *                          where it prints ./. and in regions without alleles.  Every output is nullable; the list is built once per
+ *                          otg_cohort_genotype, so a first call may ask for *n_rows alone.
+ *   otg_kmer_cohort_usage  rows [row_begin, row_begin + n) through the tiers of otg_kmer_usage_batch (builds the row list when it has not been
+ *                          built): usage_out n x (4^k + 1), gc_out n, hsd_out n; nullable, NULL leaves them in HBM for
+ *                          otg_kmer_usage_device_results(ctx, n, k, ..) and otg_kmer_usage_last_ms.  k outside 1..OTG_KMER_MAX and a range past
+ *                          *n_rows are OTG_ERR_ARG; rows beyond the 4 GiB workspace (about 21 at k = 12) are OTG_ERR_CAPACITY before anything is
+ *                          allocated: the caller walks the row list in ranges.
+ *   otg_kmer_cohort_device_rows  device pointers of the row list (valid until the next otg_cohort_regroup or otg_destroy): row_first
+ *                          (n_regions + 1), row_allele (n_rows), sample_gt (n_regions x n_samples x 2).  Every output is nullable. */
+int otg_kmer_cohort_rows(otg_ctx* ctx, uint32_t* n_rows, uint32_t* row_first_out, uint32_t* row_allele_out, int32_t* sample_gt_out);
+int otg_kmer_cohort_usage(otg_ctx* ctx, int32_t k, uint32_t row_begin, uint32_t n, double* usage_out, double* gc_out, double* hsd_out);
+int otg_kmer_cohort_device_rows(otg_ctx* ctx, uint32_t* n_rows, const uint32_t** row_first, const uint32_t** row_allele, const int32_t** sample_gt);
+
 /* Sample BAMs + BED + reference FASTA to one joint VCF in one call: per batch of regions and per sample, read ingest on host threads ->
  * otg_assemble_submit / run -> otg_cohort_stage; then otg_cohort_regroup / genotype / collect and the VCF text (otg_emit_vcf_header with the
  * contigs of the FIRST BAM and one column per sample name, otg_emit_vcf_lines), in BED order.  The ingest of a sample overlaps the device run of
@@ -696,8 +719,12 @@ int otg_cohort_end(otg_ctx* ctx);
  * of both; this path identifies regions by index).
  * allele_write (nullable): receives per sample the SAM text otg_assemble_files would have written for it (header first, records in BED order);
  * when NULL no SAM text is formatted and the allele records are never copied to the host.
+ * matrix_write (nullable; matrix_user, matrix_k): receives the k-mer usage matrix of the joint alleles, the text otg_vcf2mat_files prints for
+ * the VCF of this call at k = matrix_k (rows in BED order, the region string = the ID column chr:start-end), from otg_kmer_cohort_rows /
+ * otg_kmer_cohort_usage on the batch while it is still in HBM.  matrix_k outside 1..OTG_KMER_MAX with a writer set is OTG_ERR_ARG with vcf2mat's
+ * message.  With matrix_write NULL no k-mer work is done.
  * stats: n_reads = reads ingested over all samples, n_alleles = staged alleles (reference alleles excluded), n_regions_ok = regions with a VCF
- * line, ms_ingest / ms_hot_path / ms_emit = busy times summed over their threads. */
+ * line, ms_ingest / ms_hot_path / ms_emit = busy times summed over their threads; output_bytes = the VCF text (the matrix is not counted). */
 typedef int (*otg_cohort_allele_write_fn)(void* user, uint32_t sample, const char* data, uint64_t len);
 typedef struct otg_cohort_job {
   uint32_t    n_samples;
@@ -713,6 +740,10 @@ typedef struct otg_cohort_job {
   const int32_t* devices;        /* HIP device ordinals, one contiguous BED shard each                                     */
   otg_cohort_allele_write_fn allele_write;   /* nullable                                                                   */
   void*       allele_user;
+  otg_write_fn matrix_write;     /* nullable: the k-mer usage matrix of the joint alleles                                   */
+  void*       matrix_user;
+  int32_t     matrix_k;          /* 1..OTG_KMER_MAX when matrix_write is set                                               */
+  int32_t     reserved2;
 } otg_cohort_job;
 int otg_cohort_files(const otg_cohort_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
 

@@ -23,7 +23,7 @@ EXPORTS = [
     "otg_kmer_usage_batch", "otg_kmer_usage_device_results", "otg_kmer_usage_last_ms", "otg_vcf_open", "otg_vcf_close", "otg_vcf_read_alleles",
     "otg_vcf2mat_emit", "otg_vcf2mat_files",
     "otg_cohort_begin", "otg_cohort_stage", "otg_cohort_regroup", "otg_cohort_genotype", "otg_cohort_result_sizes", "otg_cohort_collect",
-    "otg_cohort_end", "otg_cohort_files",
+    "otg_cohort_end", "otg_cohort_files", "otg_kmer_cohort_rows", "otg_kmer_cohort_usage", "otg_kmer_cohort_device_rows",
     "otg_bam_sink_open", "otg_bam_sink_write", "otg_bam_sink_close", "otg_bam_sink_abort", "otg_bam_sink_error", "otg_bam_merge",
     "otg_comm_unique_id", "otg_comm_create", "otg_comm_destroy", "otg_gather_sizes", "otg_gather_records",
 ]
@@ -71,6 +71,7 @@ class Context:
         self._h = h
         self._L = L
         self.device = int(device)
+        self._cohort_regions = self._cohort_samples = 0          # of the open cohort batch (cohort_begin)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -169,19 +170,21 @@ class Context:
         pu, pg, ph = C.c_void_p(), C.c_void_p(), C.c_void_p()
         self._check(self._L.otg_kmer_usage_device_results(self._h, C.c_uint32(n), C.c_int32(k), C.byref(pu), C.byref(pg), C.byref(ph)),
                     "otg_kmer_usage_device_results")
-        dev = torch.device("cuda", self.device)
         bins = 4 ** int(k) + 1
+        return self._wrap_device(pu.value, (n, bins), "<f8"), self._wrap_device(pg.value, (n,), "<f8"), self._wrap_device(ph.value, (n,), "<f8")
+
+    def _wrap_device(self, ptr, shape, typestr):
+        """a torch tensor on this context's device over `shape` elements of `typestr` at the device address ptr, without a copy"""
+        import torch
+        dev = torch.device("cuda", self.device)
 
         class _Span:          # __cuda_array_interface__ carrier: torch.as_tensor wraps it without copying
             def __init__(self, ptr, shape):
-                self.__cuda_array_interface__ = {"shape": shape, "typestr": "<f8", "data": (int(ptr), False), "version": 2, "strides": None}
+                self.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (int(ptr), False), "version": 2, "strides": None}
 
-        def wrap(ptr, shape):
-            if n == 0:
-                return torch.zeros(shape, dtype=torch.float64, device=dev)
-            return torch.as_tensor(_Span(ptr, shape), device=dev)
-
-        return wrap(pu.value, (n, bins)), wrap(pg.value, (n,)), wrap(ph.value, (n,))
+        if 0 in shape:
+            return torch.zeros(shape, dtype={"<f8": torch.float64, "<i4": torch.int32}[typestr], device=dev)
+        return torch.as_tensor(_Span(ptr, shape), device=dev)
 
     def kmer_usage_last_ms(self):
         """(counting ms, epilogue ms) of the latest kmer_usage_batch (HIP events; k <= 7 counts and finishes in one kernel)."""
@@ -347,7 +350,7 @@ class Context:
     def cohort_begin(self, n_regions, n_samples):
         """otg_cohort_begin: opens the staging area of one batch of n_regions regions for n_samples samples."""
         self._check(self._L.otg_cohort_begin(self._h, C.c_uint32(n_regions), C.c_uint32(n_samples)), "otg_cohort_begin")
-        self._cohort_regions = int(n_regions)
+        self._cohort_regions, self._cohort_samples = int(n_regions), int(n_samples)
 
     def cohort_stage(self, sample, src=None):
         """otg_cohort_stage: the results of the latest assemble_run of `src` (default: this context) become sample `sample` of the batch."""
@@ -385,6 +388,43 @@ class Context:
         res["n_alleles"] = np.diff(res["first_allele"].astype(np.int64)).astype(np.uint32)
         res["seq_bytes"] = int(sb.value)
         return res
+
+    def cohort_kmer_rows(self, device_tensor=False):
+        """otg_kmer_cohort_rows (after cohort_genotype): the rows of the batch's k-mer usage matrix, the alleles of every VCF line in column
+        order -> {"n_rows", "row_first" [n_regions + 1], "row_allele" [n_rows] (indices into cohort_collect's arrays), "sample_gt"
+        [n_regions, n_samples, 2] (the GT numbers the VCF prints, -1 -1 for ./.)}: uint32 / uint32 / int32 numpy arrays, or with
+        device_tensor=True int32 torch tensors that wrap the lists in HBM (valid until the next cohort_regroup)."""
+        B, S = self._cohort_regions, self._cohort_samples
+        n = C.c_uint32(0)
+        if device_tensor:
+            pf, pa, pg = C.c_void_p(), C.c_void_p(), C.c_void_p()
+            self._check(self._L.otg_kmer_cohort_device_rows(self._h, C.byref(n), C.byref(pf), C.byref(pa), C.byref(pg)), "otg_kmer_cohort_device_rows")
+            return {"n_rows": n.value, "row_first": self._wrap_device(pf.value, (B + 1,), "<i4"), "row_allele": self._wrap_device(pa.value, (n.value,), "<i4"),
+                    "sample_gt": self._wrap_device(pg.value, (B, S, 2), "<i4")}
+        self._check(self._L.otg_kmer_cohort_rows(self._h, C.byref(n), None, None, None), "otg_kmer_cohort_rows")
+        res = {"n_rows": n.value, "row_first": np.zeros(B + 1, dtype=np.uint32), "row_allele": np.zeros(n.value, dtype=np.uint32),
+               "sample_gt": np.zeros((B, S, 2), dtype=np.int32)}
+        self._check(self._L.otg_kmer_cohort_rows(self._h, C.byref(n), abi.ptr(res["row_first"]), abi.ptr(res["row_allele"]), abi.ptr(res["sample_gt"])),
+                    "otg_kmer_cohort_rows")
+        return res
+
+    def cohort_kmer_usage(self, k, row_begin=0, n=None, device_tensor=False):
+        """otg_kmer_cohort_usage: rows [row_begin, row_begin + n) of the row list (n=None: to the end) through the k-mer tiers, read in the
+        cohort arena in place -> (usage [n, 4^k+1], gc [n], hsd [n]) as numpy arrays, or with device_tensor=True as float64 torch tensors
+        wrapping HBM (valid until the next k-mer call on this context), as kmer_usage_batch returns them."""
+        if n is None:
+            total = C.c_uint32(0)
+            self._check(self._L.otg_kmer_cohort_rows(self._h, C.byref(total), None, None, None), "otg_kmer_cohort_rows")
+            n = max(0, total.value - int(row_begin))
+        n, k = int(n), int(k)
+        if device_tensor:
+            self._check(self._L.otg_kmer_cohort_usage(self._h, C.c_int32(k), C.c_uint32(row_begin), C.c_uint32(n), None, None, None), "otg_kmer_cohort_usage")
+            return self._kmer_device_results(n, k)
+        bins = 4 ** k + 1 if 1 <= k <= abi.KMER_MAX else 1
+        usage, gc, hsd = np.zeros((n, bins), dtype=np.float64), np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64)
+        self._check(self._L.otg_kmer_cohort_usage(self._h, C.c_int32(k), C.c_uint32(row_begin), C.c_uint32(n), abi.ptr(usage), abi.ptr(gc), abi.ptr(hsd)),
+                    "otg_kmer_cohort_usage")
+        return usage, gc, hsd
 
     def cohort_end(self):
         self._check(self._L.otg_cohort_end(self._h), "otg_cohort_end")
@@ -934,10 +974,12 @@ def genotype_files(bam, bed, fasta=None, params=None, threads=1, device=0, batch
 
 
 def cohort_files(bams, names, bed, fasta, params=None, batch_regions=0, devices=None, offset_l=1, offset_r=0, mapq=0, nonprimary=False,
-                 omit_nonspanning=False, read_quality=0.0, threads=1, alleles=False, *, alleles_bam=None):
+                 omit_nonspanning=False, read_quality=0.0, threads=1, alleles=False, *, alleles_bam=None, matrix_k=None):
     """otg_cohort_files: sample BAMs + BED + reference FASTA to one joint VCF, the alleles staying on the device between `otter assemble` and
     `otter genotype`.  Returns (VCF bytes, stats dict), and with alleles=True also the list of per-sample SAM texts (what assemble_files returns
-    for each sample with read_group = its name).  alleles_bam: a list of paths, one per sample: the same records as BAM + BAI files."""
+    for each sample with read_group = its name).  alleles_bam: a list of paths, one per sample: the same records as BAM + BAI files.
+    matrix_k: also the k-mer usage matrix of the joint alleles at that k (the text vcf2mat_files returns for the VCF), computed while the
+    alleles are in HBM and appended to the returned tuple as its last element."""
     if alleles_bam is not None and len(alleles_bam) != len(bams):
         raise OtterGpuError("cohort_files: alleles_bam has %d paths for %d samples" % (len(alleles_bam), len(bams)))
     job = abi.CohortJob()
@@ -960,11 +1002,20 @@ def cohort_files(bams, names, bed, fasta, params=None, batch_regions=0, devices=
         if alleles:
             sams[sample].append(C.string_at(data, ln))
         return sinks[sample].writer(None, data, ln) if sinks else 0
-    text, stats = _into_sinks(sinks, lambda: _run_files_job("otg_cohort_files", job, abi.CohortJob,
-                                                            {"allele_write": (abi.ALLELE_WRITE_FN, asink)} if alleles or sinks else None))
-    if alleles:
-        return text, stats, [b"".join(x) for x in sams]
-    return text, stats
+    mat = []
+
+    def msink(_user, data, ln):
+        mat.append(C.string_at(data, ln))
+        return 0
+    callbacks = {}
+    if alleles or sinks:
+        callbacks["allele_write"] = (abi.ALLELE_WRITE_FN, asink)
+    if matrix_k is not None:
+        job.matrix_k = int(matrix_k)
+        callbacks["matrix_write"] = (abi.WRITE_FN, msink)
+    text, stats = _into_sinks(sinks, lambda: _run_files_job("otg_cohort_files", job, abi.CohortJob, callbacks or None))
+    out = (text, stats) + (([b"".join(x) for x in sams],) if alleles else ())
+    return out + ((b"".join(mat),) if matrix_k is not None else ())
 
 
 def assemble_files_release():

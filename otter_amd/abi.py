@@ -218,4 +218,5 @@ class CohortJob(C.Structure):
     _fields_ = [("n_samples", C.c_uint32), ("batch_regions", C.c_uint32), ("bam_paths", C.POINTER(C.c_char_p)), ("sample_names", C.POINTER(C.c_char_p)),
                 ("bed_path", C.c_char_p), ("fasta_path", C.c_char_p), ("params", otg_params), ("ingest", IngestOpts),
                 ("n_devices", C.c_int32), ("reserved", C.c_int32), ("devices", C.POINTER(C.c_int32)),
-                ("allele_write", C.c_void_p), ("allele_user", C.c_void_p)]
+                ("allele_write", C.c_void_p), ("allele_user", C.c_void_p),
+                ("matrix_write", C.c_void_p), ("matrix_user", C.c_void_p), ("matrix_k", C.c_int32), ("reserved2", C.c_int32)]

@@ -10,8 +10,11 @@
 //            allele last with sample index S (OTTER_INTREF, src/genotype.cpp:186-188); a region without sample alleles has no reference
 //            allele either (src/genotype.cpp:90); a zero-length allele becomes "N" (src/anseqs.cpp:505-507);
 //   cluster  otg_genotype_resident (the launch part of otg_genotype_cluster_batch) on those buffers;
-//   collect  D2H of the results, the allele records and the regrouped bytes for the VCF text.
+//   collect  D2H of the results, the allele records and the regrouped bytes for the VCF text;
+//   rows     after the clustering, the alleles of every VCF line in column order (the rows of `otter vcf2mat` on that VCF) and the GT numbers of
+//            every sample, selected on the device; the k-mer tiers (kmer_usage.hip) read those rows in the regrouped arena, in place.
 #include "otg_common.hpp"
+#include "otg_scan.hpp"
 #include <algorithm>
 
 struct Cohort {
@@ -22,12 +25,15 @@ struct Cohort {
   DevBuf stg_al, stg_seq, cnt, sfirst;               // staging: records, bytes, S x B counts, S x B index of the first staged record
   DevBuf ref_seq, ref_off, ref_len;                  // reference alleles of the batch
   DevBuf n_al, first, pairs, pair_off, src_of, seq_len, seq_off, smp, meta, arena, gt, hsd, ngt;
+  DevBuf row_first, row_allele, row_off, row_len, sample_gt;   // the row list of otg_kmer_cohort_rows
+  bool rows_built = false;
+  uint32_t n_rows = 0;
   std::vector<uint32_t> h_first, h_n_al;
   std::vector<uint64_t> h_pair_off;
   uint32_t na = 0;
   uint64_t seq_bytes = 0;
-  DevBuf* all[20] = {&stg_al, &stg_seq, &cnt, &sfirst, &ref_seq, &ref_off, &ref_len, &n_al, &first, &pairs, &pair_off, &src_of, &seq_len, &seq_off,
-                     &smp, &meta, &arena, &gt, &hsd, &ngt};
+  DevBuf* all[25] = {&stg_al, &stg_seq, &cnt, &sfirst, &ref_seq, &ref_off, &ref_len, &n_al, &first, &pairs, &pair_off, &src_of, &seq_len, &seq_off,
+                     &smp, &meta, &arena, &gt, &hsd, &ngt, &row_first, &row_allele, &row_off, &row_len, &sample_gt};
 };
 
 void otg_cohort_free(otg_ctx* ctx)
@@ -91,47 +97,7 @@ __global__ void cohort_region_counts_kernel(const uint32_t* __restrict__ cnt, ui
   pairs[r] = (uint64_t)A * (A ? A - 1u : 0u) / 2u;
 }
 
-// ---- regroup 2 / 4: exclusive scan of n values into n + 1 (out[n] = the total).  One block; every thread owns ITEMS consecutive values of a
-// tile, the thread sums are scanned in LDS.  The tables are a few thousand regions / some ten thousand alleles: one block is enough.
-template <class Tin, class Tout>
-__global__ void __launch_bounds__(1024) cohort_scan_kernel(const Tin* __restrict__ in, uint32_t n, Tout* __restrict__ out)
-{
-  constexpr uint32_t ITEMS = 8, T = 1024;
-  __shared__ Tout part[T];
-  __shared__ Tout carry_s;
-  const uint32_t t = threadIdx.x;
-  if (t == 0) carry_s = 0;
-  __syncthreads();
-  for (uint32_t base = 0; base < n; base += ITEMS * T) {
-    Tout v[ITEMS];
-    Tout sum = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < ITEMS; ++k) {
-      const uint32_t i = base + t * ITEMS + k;
-      v[k] = i < n ? (Tout)in[i] : (Tout)0;
-      sum += v[k];
-    }
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t d = 1; d < T; d <<= 1) {
-      const Tout add = t >= d ? part[t - d] : (Tout)0;
-      __syncthreads();
-      part[t] += add;
-      __syncthreads();
-    }
-    Tout run = carry_s + part[t] - sum;
-#pragma unroll
-    for (uint32_t k = 0; k < ITEMS; ++k) {
-      const uint32_t i = base + t * ITEMS + k;
-      if (i < n) out[i] = run;
-      run += v[k];
-    }
-    __syncthreads();
-    if (t == T - 1) carry_s += part[t];
-    __syncthreads();
-  }
-  if (t == 0) out[n] = carry_s;
-}
+// ---- regroup 2 / 4: exclusive scans of the counts (otg_scan_kernel, otg_scan.hpp)
 
 // ---- regroup 3: the place of every allele in its region (sample-major, reference last): source record, output length, sample index
 __global__ void cohort_place_kernel(const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ sfirst, uint32_t B, uint32_t S,
@@ -196,11 +162,93 @@ __global__ void __launch_bounds__(256) cohort_gather_kernel(const uint32_t* __re
   if (lane < tail) d[(size_t)nvec * 16u + lane] = s[(size_t)nvec * 16u + lane];
 }
 
+// ---- rows 1: the rows of a region = the alleles of its VCF line: n_gt where it has alleles (scanned into row_first)
+struct CohortRowCount {
+  const uint32_t* n_al; const int32_t* ngt;
+  __device__ __forceinline__ uint32_t operator()(uint32_t r) const
+  {
+    const uint32_t na = n_al[r];
+    const int32_t g = ngt[r];
+    return na == 0 || g <= 0 ? 0u : ((uint32_t)g < na ? (uint32_t)g : na);        // (there are never more clusters than alleles)
+  }
+};
+
+// ---- rows 2: one thread per allele a, the i-th of its region r (meta[a].region).  With i < rows of r it writes row row_first[r] + i of the VCF
+// line's column order (src/genotype.cpp:149-153, emit.hip): row 0 the reference allele — the last of the region, not reps[0] —, row i >= 1 the
+// representative reps[i - 1] (i <= ref_gt) or reps[i].  As a sample's allele it writes the sample's GT numbers: inside a region the alleles are
+// sample-major, so the first of a sample is the one whose predecessor has another sample (or that opens the region), its last the one whose
+// successor has another sample (the reference allele, smp == S, closes every region): no atomics.
+__global__ void __launch_bounds__(256) cohort_rows_kernel(const otg_allele* __restrict__ meta, const int32_t* __restrict__ smp, uint32_t na, uint32_t B, uint32_t S,
+                                                          const uint32_t* __restrict__ first, const uint32_t* __restrict__ n_al, const int32_t* __restrict__ gt,
+                                                          const int32_t* __restrict__ reps, const uint32_t* __restrict__ row_first,
+                                                          const uint64_t* __restrict__ seq_off, const uint32_t* __restrict__ seq_len,
+                                                          uint32_t* __restrict__ row_allele, uint64_t* __restrict__ row_off, uint32_t* __restrict__ row_len,
+                                                          int32_t* __restrict__ sample_gt)
+{
+  const uint32_t a = blockIdx.x * blockDim.x + threadIdx.x;
+  if (a >= na) return;
+  const uint32_t r = meta[a].region;
+  if (r >= B) return;
+  const uint32_t a0 = first[r], n = n_al[r];
+  if (a < a0 || a - a0 >= n) return;
+  const uint32_t i = a - a0, ref_i = n - 1u;
+  const int32_t ref_gt = gt[a0 + ref_i];
+  const uint32_t rows = row_first[r + 1] - row_first[r];
+  if (i < rows) {
+    uint32_t pick = ref_i;
+    if (i > 0) {
+      const int32_t rep = reps[a0 + ((int32_t)i <= ref_gt ? i - 1u : i)];
+      pick = rep >= 0 && (uint32_t)rep < n ? (uint32_t)rep : ref_i;
+    }
+    const uint32_t row = row_first[r] + i, al = a0 + pick;
+    row_allele[row] = al; row_off[row] = seq_off[al]; row_len[row] = seq_len[al];
+  }
+  const int32_t s = smp[a];
+  if (s < 0 || (uint32_t)s >= S) return;                                  // the reference allele is nobody's genotype
+  const int32_t g = gt[a];
+  const int32_t g2 = g == ref_gt ? 0 : (g < ref_gt ? g + 1 : g);
+  int32_t* out = sample_gt + ((size_t)r * S + (uint32_t)s) * 2u;
+  if (i == 0 || smp[a - 1] != s) out[0] = g2;
+  if (i + 1 >= n || smp[a + 1] != s) out[1] = g2;
+}
+
 Cohort* cohort_of(otg_ctx* ctx, const char* who)
 {
   if (!ctx) { otg_fail(nullptr, OTG_ERR_NO_DEVICE, "%s: no context (no HIP device?)", who); return nullptr; }
   if (!ctx->cohort || !ctx->cohort->open) { otg_fail(ctx, OTG_ERR_ARG, "%s: no cohort batch is open on this context (otg_cohort_begin)", who); return nullptr; }
   return ctx->cohort;
+}
+
+// builds the row list once per clustering
+int cohort_build_rows(otg_ctx* ctx, Cohort& c, const char* who)
+{
+  if (!c.clustered) return otg_fail(ctx, OTG_ERR_ARG, "%s: the batch has not been clustered (otg_cohort_genotype)", who);
+  if (c.rows_built) return OTG_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const uint32_t B = c.B, na = c.na;
+  const size_t cells = (size_t)B * c.S * 2;
+  int rc = OTG_OK;
+  if ((rc = grow(ctx, c.row_first, ((size_t)B + 1) * 4)) || (rc = grow(ctx, c.row_allele, ((size_t)na + 1) * 4)) || (rc = grow(ctx, c.row_off, ((size_t)na + 1) * 8)) ||
+      (rc = grow(ctx, c.row_len, ((size_t)na + 1) * 4)) || (rc = grow(ctx, c.sample_gt, cells * 4)))
+    return rc;
+  hipStream_t st = ctx->stream;
+  c.n_rows = 0;
+  HIP_TRY(ctx, hipMemsetAsync(c.row_first.p, 0, ((size_t)B + 1) * 4, st));
+  if (cells) HIP_TRY(ctx, hipMemsetAsync(c.sample_gt.p, 0xff, cells * 4, st));          // -1: ./. and the regions without alleles
+  if (B && na) {
+    hipLaunchKernelGGL((otg_scan_kernel<uint32_t, uint32_t, CohortRowCount>), dim3(1), dim3(1024), 0, st, CohortRowCount{(const uint32_t*)c.n_al.p, (const int32_t*)c.ngt.p}, B,
+                       (uint32_t*)c.row_first.p, (uint32_t*)nullptr);
+    const int32_t* d_gt = (const int32_t*)c.gt.p;
+    hipLaunchKernelGGL(cohort_rows_kernel, dim3((na + 255) / 256), dim3(256), 0, st, (const otg_allele*)c.meta.p, (const int32_t*)c.smp.p, na, B, c.S, (const uint32_t*)c.first.p,
+                       (const uint32_t*)c.n_al.p, d_gt, d_gt + 3 * ((size_t)na + 1), (const uint32_t*)c.row_first.p, (const uint64_t*)c.seq_off.p, (const uint32_t*)c.seq_len.p,
+                       (uint32_t*)c.row_allele.p, (uint64_t*)c.row_off.p, (uint32_t*)c.row_len.p, (int32_t*)c.sample_gt.p);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(&c.n_rows, (const uint32_t*)c.row_first.p + B, 4, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  if (c.n_rows > na) return otg_fail(ctx, OTG_ERR_FATAL, "%s: %u rows of %u alleles", who, c.n_rows, na);
+  c.rows_built = true;
+  return OTG_OK;
 }
 
 } // namespace
@@ -218,7 +266,7 @@ int otg_cohort_begin(otg_ctx* ctx, uint32_t n_regions, uint32_t n_samples)
   c.B = n_regions; c.S = n_samples;
   c.staged.assign(n_samples, 0);
   c.n_staged = 0; c.staged_bytes = 0; c.na = 0; c.seq_bytes = 0;
-  c.regrouped = c.clustered = false;
+  c.regrouped = c.clustered = c.rows_built = false;
   const size_t cells = (size_t)n_regions * n_samples;
   if (int rc = grow(ctx, c.cnt, cells * 4)) return rc;
   if (int rc = grow(ctx, c.sfirst, cells * 4)) return rc;
@@ -276,7 +324,7 @@ int otg_cohort_regroup(otg_ctx* ctx, const uint8_t* ref_arena, uint64_t ref_byte
     ref_total += ref_len[r];
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  c.regrouped = c.clustered = false;
+  c.regrouped = c.clustered = c.rows_built = false;
   const uint32_t B = c.B;
   c.h_first.assign((size_t)B + 1, 0); c.h_n_al.assign(B, 0); c.h_pair_off.assign((size_t)B + 1, 0);
   c.na = 0; c.seq_bytes = 0;
@@ -295,13 +343,15 @@ int otg_cohort_regroup(otg_ctx* ctx, const uint8_t* ref_arena, uint64_t ref_byte
   if (ref_bytes) HIP_TRY(ctx, hipMemcpyAsync(c.ref_seq.p, ref_arena, ref_bytes, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(c.ref_off.p, ref_off, (size_t)B * 8, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(c.ref_len.p, ref_len, (size_t)B * 4, hipMemcpyHostToDevice, st));
+  // Invariant: the regrouped arena ends in 128 zeroed bytes.  The k-mer tiers (kmer_usage.hip, ku_segment) read up to 32 bytes past an allele's
+  // last window, the clustering up to 64; past the last allele those reads stay inside this allocation and see zeros.
   HIP_TRY(ctx, hipMemsetAsync(c.arena.p, 0, bytes_cap + 128, st));
   HIP_TRY(ctx, hipMemsetAsync(c.seq_len.p, 0, (na_cap + 1) * 4, st));
   HIP_TRY(ctx, hipMemsetAsync(c.src_of.p, 0, (na_cap + 1) * 4, st));
   const dim3 gB((B + 255) / 256), b256(256);
   hipLaunchKernelGGL(cohort_region_counts_kernel, gB, b256, 0, st, (const uint32_t*)c.cnt.p, B, c.S, (uint32_t*)c.n_al.p, (uint64_t*)c.pairs.p);
-  hipLaunchKernelGGL((cohort_scan_kernel<uint32_t, uint32_t>), dim3(1), dim3(1024), 0, st, (const uint32_t*)c.n_al.p, B, (uint32_t*)c.first.p);
-  hipLaunchKernelGGL((cohort_scan_kernel<uint64_t, uint64_t>), dim3(1), dim3(1024), 0, st, (const uint64_t*)c.pairs.p, B, (uint64_t*)c.pair_off.p);
+  hipLaunchKernelGGL((otg_scan_kernel<uint32_t, uint32_t, OtgScanPtr<uint32_t>>), dim3(1), dim3(1024), 0, st, OtgScanPtr<uint32_t>{(const uint32_t*)c.n_al.p}, B, (uint32_t*)c.first.p, (uint32_t*)nullptr);
+  hipLaunchKernelGGL((otg_scan_kernel<uint64_t, uint64_t, OtgScanPtr<uint64_t>>), dim3(1), dim3(1024), 0, st, OtgScanPtr<uint64_t>{(const uint64_t*)c.pairs.p}, B, (uint64_t*)c.pair_off.p, (uint64_t*)nullptr);
   hipLaunchKernelGGL(cohort_place_kernel, gB, b256, 0, st, (const uint32_t*)c.cnt.p, (const uint32_t*)c.sfirst.p, B, c.S, (const uint32_t*)c.first.p,
                      (const uint32_t*)c.n_al.p, (const otg_allele*)c.stg_al.p, (uint32_t)c.n_staged, (const uint32_t*)c.ref_len.p, (uint32_t)na_cap,
                      (uint32_t*)c.src_of.p, (uint32_t*)c.seq_len.p, (int32_t*)c.smp.p);
@@ -313,7 +363,7 @@ int otg_cohort_regroup(otg_ctx* ctx, const uint8_t* ref_arena, uint64_t ref_byte
   const uint32_t na = c.h_first[B];
   if (na > na_cap) return otg_fail(ctx, OTG_ERR_CAPACITY, "otg_cohort_regroup: %u alleles regrouped, %llu staged", na, (unsigned long long)na_cap);
   for (uint32_t r = 0; r < B; ++r) c.h_n_al[r] = c.h_first[r + 1] - c.h_first[r];
-  hipLaunchKernelGGL((cohort_scan_kernel<uint32_t, uint64_t>), dim3(1), dim3(1024), 0, st, (const uint32_t*)c.seq_len.p, na, (uint64_t*)c.seq_off.p);
+  hipLaunchKernelGGL((otg_scan_kernel<uint64_t, uint64_t, OtgScanPtr<uint32_t>>), dim3(1), dim3(1024), 0, st, OtgScanPtr<uint32_t>{(const uint32_t*)c.seq_len.p}, na, (uint64_t*)c.seq_off.p, (uint64_t*)nullptr);
   if (na)
     hipLaunchKernelGGL(cohort_gather_kernel, dim3((na + 3) / 4), dim3(256), 0, st, (const uint32_t*)c.src_of.p, (const uint32_t*)c.seq_len.p, (const uint64_t*)c.seq_off.p,
                        (const int32_t*)c.smp.p, na, (const otg_allele*)c.stg_al.p, (const uint8_t*)c.stg_seq.p, (const uint8_t*)c.ref_seq.p, (const uint64_t*)c.ref_off.p,
@@ -336,7 +386,7 @@ int otg_cohort_genotype(otg_ctx* ctx, const otg_params* params)
   if (!params) return otg_fail(ctx, OTG_ERR_ARG, "otg_cohort_genotype: NULL argument");
   if (!c.regrouped) return otg_fail(ctx, OTG_ERR_ARG, "otg_cohort_genotype: the batch has not been regrouped (otg_cohort_regroup)");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  c.clustered = false;
+  c.clustered = c.rows_built = false;
   const uint32_t B = c.B;
   const uint64_t na = c.na;
   int rc = OTG_OK;
@@ -403,10 +453,53 @@ int otg_cohort_collect(otg_ctx* ctx, uint32_t* first_allele_out, otg_allele* all
   return OTG_OK;
 }
 
+int otg_kmer_cohort_rows(otg_ctx* ctx, uint32_t* n_rows, uint32_t* row_first_out, uint32_t* row_allele_out, int32_t* sample_gt_out)
+{
+  Cohort* cp = cohort_of(ctx, "otg_kmer_cohort_rows");
+  if (!cp) return ctx ? OTG_ERR_ARG : OTG_ERR_NO_DEVICE;
+  Cohort& c = *cp;
+  if (int rc = cohort_build_rows(ctx, c, "otg_kmer_cohort_rows")) return rc;
+  if (n_rows) *n_rows = c.n_rows;
+  hipStream_t st = ctx->stream;
+  const size_t cells = (size_t)c.B * c.S * 2;
+  if (row_first_out) HIP_TRY(ctx, hipMemcpyAsync(row_first_out, c.row_first.p, ((size_t)c.B + 1) * 4, hipMemcpyDeviceToHost, st));
+  if (row_allele_out && c.n_rows) HIP_TRY(ctx, hipMemcpyAsync(row_allele_out, c.row_allele.p, (size_t)c.n_rows * 4, hipMemcpyDeviceToHost, st));
+  if (sample_gt_out && cells) HIP_TRY(ctx, hipMemcpyAsync(sample_gt_out, c.sample_gt.p, cells * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return OTG_OK;
+}
+
+int otg_kmer_cohort_device_rows(otg_ctx* ctx, uint32_t* n_rows, const uint32_t** row_first, const uint32_t** row_allele, const int32_t** sample_gt)
+{
+  Cohort* cp = cohort_of(ctx, "otg_kmer_cohort_device_rows");
+  if (!cp) return ctx ? OTG_ERR_ARG : OTG_ERR_NO_DEVICE;
+  Cohort& c = *cp;
+  if (int rc = cohort_build_rows(ctx, c, "otg_kmer_cohort_device_rows")) return rc;
+  if (n_rows) *n_rows = c.n_rows;
+  if (row_first) *row_first = (const uint32_t*)c.row_first.p;
+  if (row_allele) *row_allele = (const uint32_t*)c.row_allele.p;
+  if (sample_gt) *sample_gt = (const int32_t*)c.sample_gt.p;
+  return OTG_OK;
+}
+
+int otg_kmer_cohort_usage(otg_ctx* ctx, int32_t k, uint32_t row_begin, uint32_t n, double* usage_out, double* gc_out, double* hsd_out)
+{
+  Cohort* cp = cohort_of(ctx, "otg_kmer_cohort_usage");
+  if (!cp) return ctx ? OTG_ERR_ARG : OTG_ERR_NO_DEVICE;
+  Cohort& c = *cp;
+  if (!c.clustered) return otg_fail(ctx, OTG_ERR_ARG, "otg_kmer_cohort_usage: the batch has not been clustered (otg_cohort_genotype)");
+  if (k < 1 || k > OTG_KMER_MAX) return otg_fail(ctx, OTG_ERR_ARG, "otg_kmer_cohort_usage: k = %d outside 1..%d", k, OTG_KMER_MAX);
+  if (int rc = cohort_build_rows(ctx, c, "otg_kmer_cohort_usage")) return rc;
+  if ((uint64_t)row_begin + n > c.n_rows) return otg_fail(ctx, OTG_ERR_ARG, "otg_kmer_cohort_usage: rows %u .. %llu of %u", row_begin, (unsigned long long)row_begin + n, c.n_rows);
+  if (int rc = otg_kmer_usage_fits(ctx, "otg_kmer_cohort_usage", n, k)) return rc;
+  return otg_kmer_usage_resident(ctx, "otg_kmer_cohort_usage", (const uint8_t*)c.arena.p, (const uint64_t*)c.row_off.p + row_begin, (const uint32_t*)c.row_len.p + row_begin,
+                                 nullptr, n, k, usage_out, gc_out, hsd_out);
+}
+
 int otg_cohort_end(otg_ctx* ctx)
 {
   if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_cohort_end: no context");
-  if (ctx->cohort) { ctx->cohort->open = false; ctx->cohort->regrouped = ctx->cohort->clustered = false; }      // the buffers stay for the next batch (otg_destroy frees them)
+  if (ctx->cohort) { ctx->cohort->open = false; ctx->cohort->regrouped = ctx->cohort->clustered = ctx->cohort->rows_built = false; }      // the buffers stay for the next batch (otg_destroy frees them)
   return OTG_OK;
 }
 

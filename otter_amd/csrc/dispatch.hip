@@ -15,6 +15,7 @@
 #include "otg_compare.hpp"
 #include "otg_dispatch_queue.hpp"
 #include "otg_vcf2mat.hpp"
+#include <cmath>
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -514,7 +515,7 @@ int emit_vcf_sliced(const Bed& bed, uint32_t first_bed, uint32_t n, const uint32
 
 // ---- the cohort dispatcher (otg_cohort_files): per device shard, per batch, per sample: ingest -> hot path -> otg_cohort_stage; the thread that
 // stages the last sample of a batch regroups, clusters, collects and formats it.
-struct CohortText { std::string vcf; std::vector<std::string> sam; };
+struct CohortText { std::string vcf, mat; std::vector<std::string> sam; };
 struct CohortRef {                           // reference alleles of one batch (genotype_process, src/genotype.cpp:93-101), fetched once
   std::vector<uint8_t> arena; std::vector<uint64_t> off; std::vector<uint32_t> len;
 };
@@ -558,9 +559,104 @@ int fetch_reference_alleles(const CohortShared& C, uint32_t first, uint32_t n, C
   return OTG_OK;
 }
 
-// regroup + cluster + collect + VCF lines of one fully staged batch
-int cohort_finish_batch(CohortShared& C, otg_ctx* cctx, const Batch& b, const CohortRef& ref, int threads, std::string& text, double* ms_gpu, double* ms_emit, uint32_t* n_ok)
+// Device bytes the k-mer workspace of a cohort slot context may take per range of matrix rows (usage rows, gc, hsd, tier L histograms); the
+// host holds two thirds of that as the rows' doubles.  Every range costs two launches and a synchronisation, so the cap wants to be large
+// next to a batch's rows at the common k (a row is 520 B at k = 3, 8 KiB at k = 5) and small next to the device: 256 MiB is half a million
+// rows at k = 3 and leaves a batch in one range up to k = 7.  Above that the ranges shrink to single rows (k = 11: 48 MiB a row; k = 12 takes
+// 192 MiB for its one row).  DESIGN.md §4.
+constexpr uint64_t COHORT_MATRIX_WORKSPACE = 256ull << 20;
+
+// the matrix rows of a clustered batch (otg_kmer_cohort_rows / otg_kmer_cohort_usage), formatted as vcf2mat prints them for the batch's VCF lines
+int cohort_matrix_text(CohortShared& C, otg_ctx* cctx, const Batch& b, const uint32_t* first, const otg_allele* alleles, const uint8_t* seqs, uint32_t na, int threads,
+                       std::string& text, double* ms_gpu, double* ms_emit)
 {
+  auto t0 = Clock::now();
+  const int k = C.j->matrix_k;
+  const uint32_t n = b.n;
+  uint32_t n_rows = 0;
+  std::vector<uint32_t> row_first((size_t)n + 1), row_allele((size_t)na + 1);
+  int rc = otg_kmer_cohort_rows(cctx, &n_rows, row_first.data(), row_allele.data(), nullptr);
+  if (rc != OTG_OK) return rc;
+  *ms_gpu += ms_since(t0);
+  text.clear();
+  if (n_rows == 0) return OTG_OK;
+  // the region strings: the ID column of the VCF line, chr:start-end
+  std::string names; std::vector<uint64_t> name_off((size_t)n + 1, 0);
+  for (uint32_t r = 0; r < n; ++r) {
+    name_off[r] = names.size();
+    if (first[r + 1] == first[r]) continue;
+    const otg_bed& bd = C.bed.beds[b.first + r];
+    names.append(C.bed.chr_arena.data() + bd.chr_off, bd.chr_len);
+    names += ':'; names += std::to_string((uint32_t)bd.start); names += '-'; names += std::to_string((uint32_t)bd.end);
+  }
+  name_off[n] = names.size();
+  const uint64_t bins = (1ull << (2 * k)) + 1;
+  const uint64_t row_bytes = bins * 8 + 16 + (k >= 8 ? bins * 4 : 0);
+  const uint32_t per = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(COHORT_MATRIX_WORKSPACE / row_bytes, 1u << 20));
+  std::vector<double> usage, gc, hsd;
+  std::vector<uint32_t> len;
+  std::vector<otg_vcf_record> rec;
+  std::vector<std::string> parts;
+  uint32_t r = 0;                                                  // the region of row `lo`
+  for (uint32_t lo = 0; lo < n_rows; lo += per) {
+    const uint32_t m = std::min(per, n_rows - lo);
+    t0 = Clock::now();
+    usage.resize((size_t)m * bins); gc.resize(m); hsd.resize(m); len.resize(m);
+    rc = otg_kmer_cohort_usage(cctx, k, lo, m, usage.data(), gc.data(), hsd.data());
+    if (rc != OTG_OK) return rc;
+    *ms_gpu += ms_since(t0);
+    t0 = Clock::now();
+    for (uint32_t i = 0; i < m; ++i) len[i] = alleles[row_allele[lo + i]].seq_len;
+    // the records of the range: its part of every region it meets; the first may continue a region begun in the range before
+    while (row_first[r + 1] <= lo) ++r;
+    // The VCF prints an ALT allele that is the one byte N — a zero-length allele — as <DEL> (otg_emit_vcf_lines), and vcf2mat reads <DEL> back
+    // as N only where it is the whole ALT column: beside other ALT alleles parse_alleles keeps the five characters (src/vcf2mat.cpp:30-33).
+    // The row of that text: length 5, no C or G, every window in the non-ACGT bin (k <= 5) or no window at all (0 / 0), one term of diversity 1.
+    for (uint32_t q = r; q < n && row_first[q] < lo + m; ++q) {
+      if (row_first[q + 1] - row_first[q] < 3) continue;
+      for (uint32_t row = std::max(row_first[q] + 1, lo); row < std::min(row_first[q + 1], lo + m); ++row) {
+        const otg_allele& al = alleles[row_allele[row]];
+        if (al.seq_len != 1 || seqs[al.seq_off] != 'N') continue;
+        const uint32_t i = row - lo;
+        len[i] = 5; gc[i] = 0.0; hsd[i] = 1.0;
+        double* u = usage.data() + (size_t)i * bins;
+        std::fill(u, u + bins, k <= 5 ? 0.0 : std::nan(""));
+        if (k <= 5) u[bins - 1] = 1.0;
+      }
+    }
+    const uint32_t index0 = lo - row_first[r];
+    rec.clear();
+    for (uint32_t q = r; q < n && row_first[q] < lo + m; ++q) {
+      const uint32_t a0 = std::max(row_first[q], lo), a1 = std::min(row_first[q + 1], lo + m);
+      if (a1 <= a0) continue;
+      otg_vcf_record R;
+      R.region_off = name_off[q]; R.region_len = (uint32_t)(name_off[q + 1] - name_off[q]); R.first_allele = a0 - lo; R.n_alleles = a1 - a0; R.reserved = 0;
+      rec.push_back(R);
+    }
+    // contiguous record ranges, one per thread, appended in order
+    const uint32_t nrec = (uint32_t)rec.size(), nt = (uint32_t)std::max(1, std::min<int>(threads, (int)nrec));
+    parts.assign(nt, std::string());
+    auto rows_of = [&](uint32_t t) {
+      const uint32_t c0 = (uint32_t)((uint64_t)nrec * t / nt), c1 = (uint32_t)((uint64_t)nrec * (t + 1) / nt);
+      if (c1 > c0) otg_vcf2mat_rows(parts[t], rec.data() + c0, c1 - c0, names.data(), len.data(), k, usage.data(), gc.data(), hsd.data(), c0 == 0 ? index0 : 0u);
+    };
+    if (nt == 1) rows_of(0);
+    else {
+      std::vector<std::thread> th;
+      for (uint32_t t = 0; t < nt; ++t) th.emplace_back(rows_of, t);
+      for (auto& t : th) t.join();
+    }
+    for (const std::string& p : parts) text += p;
+    *ms_emit += ms_since(t0);
+  }
+  return OTG_OK;
+}
+
+// regroup + cluster + collect + VCF lines (+ matrix rows) of one fully staged batch
+int cohort_finish_batch(CohortShared& C, otg_ctx* cctx, const Batch& b, const CohortRef& ref, int threads, std::string& text, std::string& matrix, double* ms_gpu, double* ms_emit, uint32_t* n_ok,
+                        const char** step)
+{
+  *step = "genotype";
   auto t0 = Clock::now();
   int rc = otg_cohort_regroup(cctx, ref.arena.data(), ref.arena.size(), ref.off.data(), ref.len.data());
   if (rc == OTG_OK) rc = otg_cohort_genotype(cctx, &C.P);
@@ -580,6 +676,8 @@ int cohort_finish_batch(CohortShared& C, otg_ctx* cctx, const Batch& b, const Co
   if (rc != OTG_OK) return rc;
   for (uint32_t r = 0; r < n; ++r) if (first[r + 1] > first[r]) ++*n_ok;
   *ms_emit += ms_since(t0);
+  *step = "matrix";
+  if (C.j->matrix_write) return cohort_matrix_text(C, cctx, b, first.data(), alleles.data(), seqs.data(), na, threads, matrix, ms_gpu, ms_emit);
   return OTG_OK;
 }
 
@@ -676,8 +774,9 @@ void cohort_shard_worker(CohortShared& C, int device, uint32_t a, uint32_t bnd, 
           if (++sl.staged == S) {
             uint32_t n_ok = 0;
             t0 = Clock::now();
-            rc = cohort_finish_batch(C, sl.ctx, b, *it.ref, ingest_threads, done.vcf, &ms_gpu[slot_idx], &ms_emit[slot_idx], &n_ok);
-            if (rc != OTG_OK) { fail_ctx(rc, "genotype", sl.ctx); break; }
+            const char* step = nullptr;
+            rc = cohort_finish_batch(C, sl.ctx, b, *it.ref, ingest_threads, done.vcf, done.mat, &ms_gpu[slot_idx], &ms_emit[slot_idx], &n_ok, &step);
+            if (rc != OTG_OK) { fail_ctx(rc, step, sl.ctx); break; }
             trace("genotype", idx, b.n, t0);
             (void)otg_cohort_end(sl.ctx);
             done.sam = std::move(sl.sam);
@@ -1092,6 +1191,8 @@ int otg_cohort_files(const otg_cohort_job* job, otg_write_fn write, void* user, 
   if (job->n_samples == 0 || !job->bam_paths || !job->sample_names) return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: zero samples (n_samples = %u)", job->n_samples);
   if (!job->fasta_path || !job->fasta_path[0]) return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: no reference FASTA (fasta_path): the joint VCF needs the reference alleles");
   if (job->n_devices < 0 || (job->n_devices > 0 && !job->devices)) return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: bad device list");
+  if (job->matrix_write && (job->matrix_k < 1 || job->matrix_k > OTG_KMER_MAX))
+    return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--kmer-size' (%d). Needs to be 1 <= x <= %d.", job->matrix_k, OTG_KMER_MAX);
   const uint32_t S = job->n_samples;
   {
     std::map<std::string, uint32_t> seen;
@@ -1161,6 +1262,7 @@ int otg_cohort_files(const otg_cohort_job* job, otg_write_fn write, void* user, 
       [&](uint32_t, const CohortText& text) {
         if (!text.vcf.empty() && write(user, text.vcf.data(), text.vcf.size()) != 0) { M.fail(OTG_ERR_ARG, "the writer failed"); return false; }
         M.st.output_bytes += text.vcf.size();
+        if (!text.mat.empty() && job->matrix_write(job->matrix_user, text.mat.data(), text.mat.size()) != 0) { M.fail(OTG_ERR_ARG, "the matrix writer failed"); return false; }
         for (uint32_t s = 0; s < (uint32_t)text.sam.size(); ++s)
           if (!text.sam[s].empty() && job->allele_write(job->allele_user, s, text.sam[s].data(), text.sam[s].size()) != 0) { M.fail(OTG_ERR_ARG, "the allele writer failed"); return false; }
         return true;

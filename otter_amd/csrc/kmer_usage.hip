@@ -15,6 +15,7 @@
 // Epilogue: value = count / total in double (0/0 when total == 0, as the reference), GC = (C/c/G/g bytes) / L, and the diversity summed by one
 // wave in ascending bin order with the lanes' terms added one at a time (ballot over the nonzero bins, which are the only terms).
 #include "otg_common.hpp"
+#include "otg_scan.hpp"
 #include <algorithm>
 #include <vector>
 
@@ -283,62 +284,64 @@ using LaunchFn = void (*)(otg_ctx*, const uint8_t*, const uint64_t*, const uint3
 const LaunchFn kLaunch[13] = {nullptr, launch_tier<1>, launch_tier<2>, launch_tier<3>, launch_tier<4>, launch_tier<5>, launch_tier<6>,
                               launch_tier<7>, launch_tier<8>, launch_tier<9>, launch_tier<10>, launch_tier<11>, launch_tier<12>};
 
+// the prefix of tier L on the device: workgroups per row from the resident lengths
+struct KuChunks {
+  const uint32_t* len;
+  __device__ __forceinline__ uint32_t operator()(uint32_t i) const { return (len[i] + KU_CHUNK_L - 1) / KU_CHUNK_L; }
+};
+
 } // namespace
 
-extern "C" int otg_kmer_usage_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_bytes, const uint64_t* seq_off, const uint32_t* seq_len,
-                                    uint32_t n, int32_t k, double* usage_out, double* gc_out, double* hsd_out)
+int otg_kmer_usage_fits(otg_ctx* ctx, const char* who, uint32_t n, int32_t k)
 {
-  if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_kmer_usage_batch: no context (no HIP device?)");
-  if (k < 1 || k > OTG_KMER_MAX) return otg_fail(ctx, OTG_ERR_ARG, "otg_kmer_usage_batch: k = %d outside 1..%d", k, OTG_KMER_MAX);
-  if (n && (!seq_off || !seq_len || (arena_bytes && !seq_arena))) return otg_fail(ctx, OTG_ERR_ARG, "otg_kmer_usage_batch: NULL argument");
-  for (uint32_t i = 0; i < n; ++i)
-    if (seq_off[i] > arena_bytes || seq_len[i] > arena_bytes - seq_off[i])
-      return otg_fail(ctx, OTG_ERR_ARG, "otg_kmer_usage_batch: allele %u (offset %llu, length %u) lies outside the %llu-byte arena", i,
-                      (unsigned long long)seq_off[i], seq_len[i], (unsigned long long)arena_bytes);
   const uint64_t bins = (1ull << (2 * k)) + 1;
-  const bool tier_l = k >= 8;
-  const uint64_t row_bytes = bins * sizeof(double) + (tier_l ? bins * sizeof(uint32_t) : 0);
+  const uint64_t row_bytes = bins * sizeof(double) + (k >= 8 ? bins * sizeof(uint32_t) : 0);
   if ((uint64_t)n * row_bytes > KU_WORKSPACE)
-    return otg_fail(ctx, OTG_ERR_CAPACITY, "otg_kmer_usage_batch: %u alleles at k = %d need %llu device bytes, the workspace holds %llu (at most %llu alleles)",
-                    n, k, (unsigned long long)(n * row_bytes), (unsigned long long)KU_WORKSPACE, (unsigned long long)(KU_WORKSPACE / row_bytes));
+    return otg_fail(ctx, OTG_ERR_CAPACITY, "%s: %u alleles at k = %d need %llu device bytes, the workspace holds %llu (at most %llu alleles)",
+                    who, n, k, (unsigned long long)(n * row_bytes), (unsigned long long)KU_WORKSPACE, (unsigned long long)(KU_WORKSPACE / row_bytes));
+  return OTG_OK;
+}
+
+// The launch part of otg_kmer_usage_batch on device-resident rows: row i is d_arena[d_off[i] .. + d_len[i]), and the tiers read up to 32 bytes
+// past a row's last window, so the arena must extend that far past every row.  h_blk (nullable, read for k >= 8 only) is the workgroup prefix
+// of tier L (n + 1 entries) where the caller has the lengths on the host; without it the prefix is scanned on the device and only its total
+// read back.  The results land in SLOT_KMER_OUT (otg_kmer_usage_device_results); the caller has checked otg_kmer_usage_fits.
+int otg_kmer_usage_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, const uint32_t* h_blk,
+                            uint32_t n, int32_t k, double* usage_out, double* gc_out, double* hsd_out)
+{
   ctx->last_kmer_count_ms = ctx->last_kmer_epi_ms = 0.0;
   if (n == 0) return OTG_OK;
+  const uint64_t bins = (1ull << (2 * k)) + 1;
+  const bool tier_l = k >= 8;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (!ctx->ev2) HIP_TRY(ctx, hipEventCreate(&ctx->ev2));
-  // metadata: seq_off (u64) | seq_len (u32) | gc counts (u32) | tier L workgroup prefix (u32, n + 1)
-  std::vector<uint32_t> blk(tier_l ? n + 1 : 0);
-  uint32_t n_blk = 0;
-  if (tier_l) {
-    uint64_t acc = 0;
-    for (uint32_t i = 0; i < n; ++i) { blk[i] = (uint32_t)acc; acc += (seq_len[i] + KU_CHUNK_L - 1) / KU_CHUNK_L; }
-    if (acc > 0x7fffffffull) return otg_fail(ctx, OTG_ERR_CAPACITY, "otg_kmer_usage_batch: the batch needs %llu workgroups", (unsigned long long)acc);
-    blk[n] = n_blk = (uint32_t)acc;
-  }
-  const size_t meta_bytes = (size_t)n * 8 + (size_t)n * 4 * 2 + (tier_l ? (size_t)(n + 1) * 4 : 0);
-  uint8_t* d_arena = (uint8_t*)otg_slot(ctx, SLOT_KMER_SEQ, arena_bytes + 64);
-  uint8_t* d_meta = (uint8_t*)otg_slot(ctx, SLOT_KMER_META, meta_bytes);
+  // tier L: gc counts (u32) | workgroup prefix (u32, n + 1) | their u64 total
+  uint64_t acc = tier_l && h_blk ? h_blk[n] : 0;
+  const size_t blk_words = ((size_t)2 * n + 2) & ~(size_t)1;              // the total behind them is 8-byte aligned
   const size_t usage_bytes = (size_t)n * bins * sizeof(double);
   uint8_t* d_out = (uint8_t*)otg_slot(ctx, SLOT_KMER_OUT, usage_bytes + (size_t)n * 2 * sizeof(double));   // usage rows | gc | hsd
   uint32_t* d_hist = tier_l ? (uint32_t*)otg_slot(ctx, SLOT_KMER_HIST, (size_t)n * bins * sizeof(uint32_t)) : nullptr;
-  if (!d_arena || !d_meta || !d_out || (tier_l && !d_hist)) return OTG_ERR_HIP;
-  uint64_t* d_off = (uint64_t*)d_meta;
-  uint32_t* d_len = (uint32_t*)(d_meta + (size_t)n * 8);
-  uint32_t* d_gc = d_len + n;
+  uint32_t* d_gc = tier_l ? (uint32_t*)otg_slot(ctx, SLOT_KMER_BLK, blk_words * 4 + 8) : nullptr;
+  if (!d_out || (tier_l && (!d_hist || !d_gc))) return OTG_ERR_HIP;
   uint32_t* d_blk = tier_l ? d_gc + n : nullptr;
   double* d_usage = (double*)d_out;
   double* d_gcv = (double*)(d_out + usage_bytes);
   double* d_hsd = d_gcv + n;
-  HIP_TRY(ctx, hipMemsetAsync(d_arena + arena_bytes, 0, 64, ctx->stream));
-  if (arena_bytes) HIP_TRY(ctx, hipMemcpyAsync(d_arena, seq_arena, arena_bytes, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_off, seq_off, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_len, seq_len, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
   if (tier_l) {
-    HIP_TRY(ctx, hipMemcpyAsync(d_blk, blk.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (h_blk) HIP_TRY(ctx, hipMemcpyAsync(d_blk, h_blk, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    else {
+      uint64_t* d_total = (uint64_t*)(d_gc + blk_words);
+      hipLaunchKernelGGL((otg_scan_kernel<uint64_t, uint32_t, KuChunks>), dim3(1), dim3(1024), 0, ctx->stream, KuChunks{d_len}, n, d_blk, d_total);
+      HIP_TRY(ctx, hipGetLastError());
+      HIP_TRY(ctx, hipMemcpyAsync(&acc, d_total, 8, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      if (acc > 0x7fffffffull) return otg_fail(ctx, OTG_ERR_CAPACITY, "%s: the batch needs %llu workgroups", who, (unsigned long long)acc);
+    }
     HIP_TRY(ctx, hipMemsetAsync(d_gc, 0, (size_t)n * 4, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(d_hist, 0, (size_t)n * bins * sizeof(uint32_t), ctx->stream));
   }
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  kLaunch[k](ctx, d_arena, d_off, d_len, d_blk, n, n_blk, d_usage, d_hist, d_gc, d_gcv, d_hsd);
+  kLaunch[k](ctx, d_arena, d_off, d_len, d_blk, n, (uint32_t)acc, d_usage, d_hist, d_gc, d_gcv, d_hsd);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
   if (usage_out) HIP_TRY(ctx, hipMemcpyAsync(usage_out, d_usage, usage_bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -350,6 +353,41 @@ extern "C" int otg_kmer_usage_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint
   HIP_TRY(ctx, hipEventElapsedTime(&e_ms, ctx->ev1, ctx->ev2));
   ctx->last_kmer_count_ms = c_ms; ctx->last_kmer_epi_ms = e_ms;
   return OTG_OK;
+}
+
+extern "C" int otg_kmer_usage_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_bytes, const uint64_t* seq_off, const uint32_t* seq_len,
+                                    uint32_t n, int32_t k, double* usage_out, double* gc_out, double* hsd_out)
+{
+  if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_kmer_usage_batch: no context (no HIP device?)");
+  if (k < 1 || k > OTG_KMER_MAX) return otg_fail(ctx, OTG_ERR_ARG, "otg_kmer_usage_batch: k = %d outside 1..%d", k, OTG_KMER_MAX);
+  if (n && (!seq_off || !seq_len || (arena_bytes && !seq_arena))) return otg_fail(ctx, OTG_ERR_ARG, "otg_kmer_usage_batch: NULL argument");
+  for (uint32_t i = 0; i < n; ++i)
+    if (seq_off[i] > arena_bytes || seq_len[i] > arena_bytes - seq_off[i])
+      return otg_fail(ctx, OTG_ERR_ARG, "otg_kmer_usage_batch: allele %u (offset %llu, length %u) lies outside the %llu-byte arena", i,
+                      (unsigned long long)seq_off[i], seq_len[i], (unsigned long long)arena_bytes);
+  if (int rc = otg_kmer_usage_fits(ctx, "otg_kmer_usage_batch", n, k)) return rc;
+  ctx->last_kmer_count_ms = ctx->last_kmer_epi_ms = 0.0;
+  if (n == 0) return OTG_OK;
+  // tier L: the workgroup prefix from the host lengths, refused before anything is allocated
+  std::vector<uint32_t> blk(k >= 8 ? n + 1 : 0);
+  if (k >= 8) {
+    uint64_t acc = 0;
+    for (uint32_t i = 0; i < n; ++i) { blk[i] = (uint32_t)acc; acc += (seq_len[i] + KU_CHUNK_L - 1) / KU_CHUNK_L; }
+    if (acc > 0x7fffffffull) return otg_fail(ctx, OTG_ERR_CAPACITY, "otg_kmer_usage_batch: the batch needs %llu workgroups", (unsigned long long)acc);
+    blk[n] = (uint32_t)acc;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // the rows: the arena and seq_off (u64) | seq_len (u32)
+  uint8_t* d_arena = (uint8_t*)otg_slot(ctx, SLOT_KMER_SEQ, arena_bytes + 64);
+  uint8_t* d_meta = (uint8_t*)otg_slot(ctx, SLOT_KMER_META, (size_t)n * 12);
+  if (!d_arena || !d_meta) return OTG_ERR_HIP;
+  uint64_t* d_off = (uint64_t*)d_meta;
+  uint32_t* d_len = (uint32_t*)(d_meta + (size_t)n * 8);
+  HIP_TRY(ctx, hipMemsetAsync(d_arena + arena_bytes, 0, 64, ctx->stream));
+  if (arena_bytes) HIP_TRY(ctx, hipMemcpyAsync(d_arena, seq_arena, arena_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_off, seq_off, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_len, seq_len, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+  return otg_kmer_usage_resident(ctx, "otg_kmer_usage_batch", d_arena, d_off, d_len, k >= 8 ? blk.data() : nullptr, n, k, usage_out, gc_out, hsd_out);
 }
 
 extern "C" int otg_kmer_usage_device_results(otg_ctx* ctx, uint32_t n, int32_t k, const double** usage, const double** gc, const double** hsd)

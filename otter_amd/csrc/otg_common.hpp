@@ -87,6 +87,7 @@ enum {
   SLOT_P10, SLOT_P11, SLOT_P12, SLOT_P13, SLOT_P14, SLOT_P15, SLOT_P16, SLOT_P17, SLOT_P18, SLOT_P19,
   SLOT_P20, SLOT_P21, SLOT_P22, SLOT_P23, SLOT_P24, SLOT_P25, SLOT_P26, SLOT_P27, SLOT_P28, SLOT_P29,
   SLOT_KMER_SEQ, SLOT_KMER_META, SLOT_KMER_HIST, SLOT_KMER_OUT,     // otg_kmer_usage_batch (kmer_usage.hip); OUT stays valid for the device results
+  SLOT_KMER_BLK,                                                    // tier L of otg_kmer_usage_resident: gc counts and the workgroup prefix
   SLOT_COUNT
 };
 
@@ -275,6 +276,12 @@ int otg_launch_poa(otg_ctx* ctx, const uint8_t* d_seq_arena, const uint8_t* d_ci
 int otg_genotype_resident(otg_ctx* ctx, const otg_params* params, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len,
                           const uint32_t* d_first, const uint32_t* d_n, const uint32_t* h_n_alleles, uint32_t n_regions, const uint64_t* d_poff,
                           uint64_t n_pairs, uint64_t na, int32_t* d_gt, double* d_hsd, int32_t* d_ngt);
+
+// kmer_usage.hip: the workspace refusal of otg_kmer_usage_batch (OTG_ERR_CAPACITY, nothing allocated) and its launch part on device-resident
+// rows; see the definitions
+int otg_kmer_usage_fits(otg_ctx* ctx, const char* who, uint32_t n, int32_t k);
+int otg_kmer_usage_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, const uint32_t* h_blk,
+                            uint32_t n, int32_t k, double* usage_out, double* gc_out, double* hsd_out);
 
 // cluster.hip (genotype_kernel)
 int otg_launch_genotype(otg_ctx* ctx, const otg_params* P, const uint8_t* d_arena, const uint64_t* d_seq_off,

@@ -103,15 +103,16 @@ void put_u64(std::string& o, uint64_t v)
 } // namespace
 
 void otg_vcf2mat_rows(std::string& o, const otg_vcf_record* records, uint32_t n_records, const char* region_arena, const uint32_t* seq_len,
-                      int32_t k, const double* usage, const double* gc, const double* hsd)
+                      int32_t k, const double* usage, const double* gc, const double* hsd, uint32_t first_index)
 {
   const uint64_t bins = (1ull << (2 * k)) + 1;
   for (uint32_t r = 0; r < n_records; ++r) {
     const otg_vcf_record& R = records[r];
+    const uint64_t i0 = r == 0 ? first_index : 0u;
     for (uint32_t i = 0; i < R.n_alleles; ++i) {
       const uint64_t a = (uint64_t)R.first_allele + i;
       o.append(region_arena + R.region_off, R.region_len);
-      o += '\t'; put_u64(o, i);
+      o += '\t'; put_u64(o, i0 + i);
       o += '\t'; put_dbl(o, gc[a]);
       o += '\t'; put_u64(o, seq_len[a]);
       o += '\t'; put_dbl(o, hsd[a]);

@@ -2,9 +2,10 @@
 // `otter genotype` over their alleles in one pass (otg_cohort_files), the alleles never leaving the device in between.  Host C++ only.
 //   otter_cohort -b regions.bed -r ref.fa [the assemble options of otter_assemble: --haps -p -l -o L[,R] -a N -m Q -q RQ -c COV -F f -A len,f -e err
 //                -h bw[,len,bw] -f flank -s sim -t threads --batch N --gpus 0,1,.. --wfa-heuristic ..] [-E gt-max-error] [-S gt-max-cosdis]
-//                [--alleles-prefix P [--alleles-bam]] NAME=reads.bam ...
+//                [--alleles-prefix P [--alleles-bam]] [--matrix FILE [-k K]] NAME=reads.bam ...
 // The VCF goes to stdout.  NAME is the sample's `-R` and its VCF column.  --alleles-prefix P also writes the allele records of every sample, as
 // `otter assemble -R NAME` prints them, to P<NAME>.sam; with --alleles-bam to P<NAME>.bam + P<NAME>.bam.bai instead (otg_bam_sink).
+// --matrix FILE also writes the k-mer usage matrix of the joint alleles, what `otter vcf2mat -k K` prints for the VCF (K defaults to 3).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -13,6 +14,7 @@
 #include "../include/otter_gpu.h"
 
 static int write_stdout(void*, const char* data, uint64_t len) { return fwrite(data, 1, (size_t)len, stdout) == (size_t)len ? 0 : 1; }
+static int write_file(void* user, const char* data, uint64_t len) { return fwrite(data, 1, (size_t)len, (FILE*)user) == (size_t)len ? 0 : 1; }
 static int write_sample(void* user, uint32_t sample, const char* data, uint64_t len)
 {
   FILE* f = (*(std::vector<FILE*>*)user)[sample];
@@ -38,7 +40,8 @@ int main(int argc, char** argv)
   otg_cohort_job job; memset(&job, 0, sizeof job);
   otg_params_default(&job.params);
   job.ingest.offset_l = 1; job.ingest.offset_r = 0; job.ingest.threads = 1;       // --offset 1,0 and -t 1: the reference's defaults
-  std::string bed, ref, prefix;
+  std::string bed, ref, prefix, matrix;
+  job.matrix_k = 3;                                                               // -k of `otter vcf2mat`
   std::vector<std::string> names, bams;
   std::vector<int32_t> devs;
   bool alleles_bam = false;
@@ -51,6 +54,8 @@ int main(int argc, char** argv)
     else if (a == "-S" || a == "--gt-max-cosdis") job.params.gt_max_cosdis = atof(val().c_str());
     else if (a == "--alleles-prefix") prefix = val();
     else if (a == "--alleles-bam") alleles_bam = true;
+    else if (a == "--matrix") matrix = val();
+    else if (a == "-k" || a == "--kmer-size") job.matrix_k = atoi(val().c_str());
     else if (a == "--haps") job.params.ignore_haps = 0;
     else if (a == "-p" || a == "--non-primary") job.ingest.nonprimary = 1;
     else if (a == "-l" || a == "--omit-nonspanning") job.ingest.omit_nonspanning = 1;
@@ -116,9 +121,16 @@ int main(int argc, char** argv)
     }
     job.allele_write = write_sample; job.allele_user = &files;
   }
+  FILE* fmat = nullptr;
+  if (!matrix.empty()) {
+    fmat = fopen(matrix.c_str(), "wb");
+    if (!fmat) { fprintf(stderr, "[ERROR] cannot write %s\n", matrix.c_str()); for (otg_bam_sink* x : sinks) otg_bam_sink_abort(x); return 1; }
+    job.matrix_write = write_file; job.matrix_user = fmat;
+  }
   otg_job_stats st;
   int rc = otg_cohort_files(&job, write_stdout, nullptr, &st);
   fflush(stdout);
+  const bool matrix_lost = fmat && fclose(fmat) != 0;
   for (FILE* f : files) fclose(f);
   if (rc != OTG_OK) {
     const std::string job_err = otg_last_error(nullptr);
@@ -131,6 +143,7 @@ int main(int argc, char** argv)
     if (rc == OTG_OK) rc = otg_bam_sink_close(sinks[s], nullptr); else otg_bam_sink_abort(sinks[s]);
   }
   if (rc != OTG_OK) { fprintf(stderr, "[ERROR] otter_cohort failed (%d): %s\n", rc, otg_last_error(nullptr)); return 1; }
+  if (matrix_lost) { fprintf(stderr, "[ERROR] cannot write %s\n", matrix.c_str()); return 1; }
   fprintf(stderr, "otter_cohort: %u samples, %llu regions (%llu with a VCF line), %llu reads, %llu alleles, %.1f MB out; %.3f s wall on %u GPU(s); stage busy ms: ingest %.0f, hot path %.0f, emit %.0f\n",
           job.n_samples, (unsigned long long)st.n_regions, (unsigned long long)st.n_regions_ok, (unsigned long long)st.n_reads, (unsigned long long)st.n_alleles, st.output_bytes / 1e6,
           st.ms_total / 1e3, st.n_devices, st.ms_ingest, st.ms_hot_path, st.ms_emit);
