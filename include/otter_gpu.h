@@ -137,14 +137,31 @@ int otg_edit_distance_batch(otg_ctx* ctx,
  * OTG_HEURISTIC_WFADAPTIVE (exact alignment only).  scores_out[i] = unit-cost edit distance.  Op strings as otg_affine_align_batch
  * (M X I D, one char per column, I consumes text, D consumes pattern; bytes compared raw), the tie-break of WFA2-lib's edit piggy-back
  * (DESIGN.md §3).  cigar_arena == NULL: only cigar_len_out (= alignment columns) is produced, cigar_off_out may be NULL.
- * *cigar_bytes_used = total length; OTG_ERR_CAPACITY when cigar_capacity is smaller.                                              */
+ * *cigar_bytes_used = total length; OTG_ERR_CAPACITY when cigar_capacity is smaller.  The same alignment under wfadaptive, asked for by
+ * name and per call: otg_edit_align_heur_batch below.                                                                              */
 int otg_edit_align_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_bytes,
                          const otg_align_task* tasks, uint32_t n_tasks, int32_t* scores_out,
                          uint64_t* cigar_off_out, uint32_t* cigar_len_out,
                          uint8_t* cigar_arena, uint64_t cigar_capacity, uint64_t* cigar_bytes_used);
-/* HIP-event times (ms) of the latest otg_edit_align_batch on this context: the score chain and the provenance pass (which includes
- * the backtrace and the unpack).  Measurement hook; the reference has no counterpart. */
+/* otg_edit_align_batch under a heuristic named per call, the way otg_params.heuristic names the pipeline's: what
+ * WFAlignerEdit(Alignment, MemoryMed)::alignEnd2End returns after setHeuristicNone() / setHeuristicWFadaptive(min_wavefront_length,
+ * max_distance_threshold, steps_between_cutoffs).  OTG_HEURISTIC_NONE: the results of otg_edit_align_batch.  OTG_HEURISTIC_WFADAPTIVE: score
+ * and op string of the alignment the reduced wavefronts find — the score and cells of otg_edit_distance_batch on a context set to that
+ * heuristic, the piggy-back tie-break with sources taken from the wavefront the cut left; a valid alignment of its score,
+ * possibly sub-optimal.  The parameters are validated as otg_set_heuristic validates them; the context's own heuristic is neither consulted
+ * nor left changed.  Ends-free tasks are OTG_ERR_ARG.  Length-only protocol (cigar_arena == NULL) and OTG_ERR_CAPACITY as above.
+ * cells_out (nullable): wavefront cells of the score chain, as otg_edit_distance_batch reports them.                                   */
+int otg_edit_align_heur_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_bytes,
+                              const otg_align_task* tasks, uint32_t n_tasks,
+                              int strategy, int min_wavefront_length, int max_distance_threshold, int steps_between_cutoffs,
+                              int32_t* scores_out, uint64_t* cigar_off_out, uint32_t* cigar_len_out,
+                              uint8_t* cigar_arena, uint64_t cigar_capacity, uint64_t* cigar_bytes_used, uint64_t* cells_out);
+/* HIP-event times (ms) of the latest otg_edit_align_batch / otg_edit_align_heur_batch on this context: the score chain and the provenance
+ * pass (which includes the backtrace and the unpack).  Measurement hook; the reference has no counterpart. */
 int otg_edit_align_last_ms(otg_ctx* ctx, double* score_ms, double* prov_ms);
+/* How many tasks of the latest OTG_HEURISTIC_WFADAPTIVE otg_edit_align_heur_batch on this context were finished by the LDS-window tier
+ * (finished[0]) and by the global-row tier (finished[1]) of its provenance pass.  Test hook, read-only. */
+int otg_edit_align_last_tiers(otg_ctx* ctx, uint32_t finished[2]);
 
 /* Replaces WFAlignerGapAffine(x,o,e, Alignment, MemoryMed)::alignEnd2End/alignEndsFree +
  * getAlignmentCigar() (src/assemble.cpp:50, src/analignments.cpp:25,31,37,268-280).
@@ -593,7 +610,8 @@ int otg_compare_emit(const otg_bed* beds, const char* chr_arena, uint32_t n_regi
                      char* out, uint64_t out_capacity, uint64_t* out_len,
                      char* warn, uint64_t warn_capacity, uint64_t* warn_len, otg_compare_counts* counts);
 /* `otter compare` from files to text in one call — compare() (src/compare.cpp:68-150): BED regions in bounded batches through the two ingests
- * (host threads), the edit alignments of all pairs of a batch on the device (otg_edit_align_batch, exact), and otg_compare_emit; text in BED
+ * (host threads), the edit alignments of all pairs of a batch on the device (otg_edit_align_batch; otg_edit_align_heur_batch when the job
+ * names OTG_HEURISTIC_WFADAPTIVE — a zeroed job is exact), and otg_compare_emit; text in BED
  * order (the reference's threads interleave theirs).  The ingest of the next batch overlaps the device work and the emit of the current one.
  * warn (nullable) receives the reference's warning lines without the timestamp.  stats: n_regions_ok = compared regions, n_regions_skipped
  * the rest, n_alleles = truth + query alleles, n_reads = aligned pairs. */
@@ -607,6 +625,10 @@ typedef struct otg_compare_job {
   uint32_t    reserved;
   otg_write_fn warn;             /* nullable                                                         */
   void*       warn_user;
+  int32_t     heuristic;         /* of the edit alignments: OTG_HEURISTIC_NONE (0, exact) or OTG_HEURISTIC_WFADAPTIVE with the three below */
+  int32_t     heur_min_wavefront_length;
+  int32_t     heur_max_distance_threshold;
+  int32_t     heur_steps_between_cutoffs;
 } otg_compare_job;
 int otg_compare_files(const otg_compare_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
 

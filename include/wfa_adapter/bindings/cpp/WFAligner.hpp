@@ -90,7 +90,12 @@ class WFAligner {
       // WFAlignerEdit(Alignment): score and op string of the edit piggy-back (src/compare.cpp:59-61,95); ends-free keeps the score path
       uint64_t off = 0, used = 0; uint32_t len = 0;
       ops_.resize(pattern.size() + text.size() + 64);
-      rc = otg_edit_align_batch(ctx_, (const uint8_t*)arena_.data(), arena_.size(), &t, 1, &sc, &off, &len, (uint8_t*)&ops_[0], ops_.size(), &used);
+      // under setHeuristicWFadaptive: the traceback of the reduced wavefronts, asked for by name (what a WFA2-lib whose default is adaptive returns)
+      if (heur_ == OTG_HEURISTIC_WFADAPTIVE)
+        rc = otg_edit_align_heur_batch(ctx_, (const uint8_t*)arena_.data(), arena_.size(), &t, 1, heur_, heur_p_[0], heur_p_[1], heur_p_[2], &sc, &off, &len,
+                                       (uint8_t*)&ops_[0], ops_.size(), &used, nullptr);
+      else
+        rc = otg_edit_align_batch(ctx_, (const uint8_t*)arena_.data(), arena_.size(), &t, 1, &sc, &off, &len, (uint8_t*)&ops_[0], ops_.size(), &used);
       if (rc == OTG_OK) { score_ = sc; cigar_.assign(ops_.data() + off, len); }
     } else if (!affine()) {
       rc = otg_edit_distance_batch(ctx_, (const uint8_t*)arena_.data(), arena_.size(), &t, 1, &sc, nullptr);

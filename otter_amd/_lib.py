@@ -19,7 +19,7 @@ EXPORTS = [
     "otg_ingest_regions_named", "otg_emit_reads", "otg_parse_bed_file", "otg_fasta_open", "otg_fasta_close", "otg_fasta_n_seqs",
     "otg_fasta_seq", "otg_fasta_fetch", "otg_fasta_region_flanks",
     "otg_bam_sample_index", "otg_bam_sample", "otg_ingest_alleles", "otg_emit_vcf_header", "otg_emit_vcf_lines", "otg_emit_genotype_lengths", "otg_assemble_files", "otg_assemble_files_release", "otg_assemble_batch_plan", "otg_genotype_files", "otg_wgat",
-    "otg_edit_align_batch", "otg_edit_align_last_ms", "otg_ingest_compare_alleles", "otg_compare_emit", "otg_compare_files",
+    "otg_edit_align_batch", "otg_edit_align_heur_batch", "otg_edit_align_last_ms", "otg_edit_align_last_tiers", "otg_ingest_compare_alleles", "otg_compare_emit", "otg_compare_files",
     "otg_kmer_usage_batch", "otg_kmer_usage_device_results", "otg_kmer_usage_last_ms", "otg_vcf_open", "otg_vcf_close", "otg_vcf_read_alleles",
     "otg_vcf2mat_emit", "otg_vcf2mat_files",
     "otg_cohort_begin", "otg_cohort_stage", "otg_cohort_regroup", "otg_cohort_genotype", "otg_cohort_result_sizes", "otg_cohort_collect",
@@ -138,11 +138,40 @@ class Context:
             return scores, ln
         return scores, [out[int(off[i]):int(off[i]) + int(ln[i])].tobytes() for i in range(n)]
 
+    def edit_align_heur_batch(self, arena, tasks, strategy, a=10, b=50, c=1, want_cigars=True, want_cells=False):
+        """otg_edit_align_heur_batch: edit_align_batch under the heuristic named here (abi.OTG_HEURISTIC_NONE, or abi.OTG_HEURISTIC_WFADAPTIVE
+        with min_wavefront_length a, max_distance_threshold b, steps_between_cutoffs c); the context's own heuristic is left alone.
+        -> (scores, op strings or lengths) and, with want_cells, the score chain's cell counts as a third item."""
+        n = len(tasks)
+        scores = np.zeros(n, dtype=np.int32)
+        off = np.zeros(n, dtype=np.uint64)
+        ln = np.zeros(n, dtype=np.uint32)
+        cells = np.zeros(n, dtype=np.uint64)
+        used = C.c_uint64(0)
+        if want_cigars:
+            cap = int(tasks["pattern_len"].astype(np.int64).sum() + tasks["text_len"].astype(np.int64).sum()) + 64
+            out = np.zeros(cap, dtype=np.uint8)
+        else:
+            cap, out = 0, None
+        rc = self._L.otg_edit_align_heur_batch(self._h, abi.ptr(arena), C.c_uint64(arena.size), abi.ptr(tasks), C.c_uint32(n),
+                                               C.c_int(int(strategy)), C.c_int(int(a)), C.c_int(int(b)), C.c_int(int(c)), abi.ptr(scores),
+                                               abi.ptr(off) if want_cigars else None, abi.ptr(ln), abi.ptr(out) if want_cigars else None,
+                                               C.c_uint64(cap), C.byref(used), abi.ptr(cells) if want_cells else None)
+        self._check(rc, "otg_edit_align_heur_batch")
+        second = [out[int(off[i]):int(off[i]) + int(ln[i])].tobytes() for i in range(n)] if want_cigars else ln
+        return (scores, second, cells) if want_cells else (scores, second)
+
     def edit_align_last_ms(self):
-        """(score chain ms, provenance pass ms) of the latest edit_align_batch (HIP events)."""
+        """(score chain ms, provenance pass ms) of the latest edit_align_batch / edit_align_heur_batch (HIP events)."""
         a, b = C.c_double(0), C.c_double(0)
         self._check(self._L.otg_edit_align_last_ms(self._h, C.byref(a), C.byref(b)), "otg_edit_align_last_ms")
         return a.value, b.value
+
+    def edit_align_last_tiers(self):
+        """(tasks finished by the LDS-window tier, by the global-row tier) of the latest adaptive edit_align_heur_batch."""
+        f = (C.c_uint32 * 2)(0, 0)
+        self._check(self._L.otg_edit_align_last_tiers(self._h, f), "otg_edit_align_last_tiers")
+        return int(f[0]), int(f[1])
 
     def kmer_usage_batch(self, arena, seq_off, seq_len, k=3, device_tensor=False):
         """otg_kmer_usage_batch: per allele the 4^k+1 k-mer frequencies of vcf2mat, its GC fraction and Hill-Shannon diversity ->
@@ -1080,11 +1109,15 @@ def compare_emit(regions, truth, query, pair_first, pair_edit, pair_ops):
     return out.raw[:need.value], w.raw[:wneed.value], {k: getattr(cnt, k) for k, _ in abi.CompareCounts._fields_}
 
 
-def compare_files(truth_bam, query_bam, bed, threads=1, device=0, batch_regions=0):
-    """otg_compare_files: `otter compare` from files to text.  Returns (text bytes, warning bytes, stats dict)."""
+def compare_files(truth_bam, query_bam, bed, threads=1, device=0, batch_regions=0, heuristic=None):
+    """otg_compare_files: `otter compare` from files to text.  heuristic: None = exact edit alignments, or the (min_wavefront_length,
+    max_distance_threshold, steps_between_cutoffs) of wfadaptive.  Returns (text bytes, warning bytes, stats dict)."""
     job = abi.CompareJob()
     job.truth_bam_path = truth_bam.encode(); job.query_bam_path = query_bam.encode(); job.bed_path = bed.encode()
     job.threads = threads; job.device = device; job.batch_regions = batch_regions
+    if heuristic is not None:
+        job.heuristic = abi.OTG_HEURISTIC_WFADAPTIVE
+        job.heur_min_wavefront_length, job.heur_max_distance_threshold, job.heur_steps_between_cutoffs = (int(x) for x in heuristic)
     warns = []
 
     def wsink(_user, data, n):

@@ -183,7 +183,9 @@ class GenotypeJob(C.Structure):
 class CompareJob(C.Structure):
     """otg_compare_job (include/otter_gpu.h)."""
     _fields_ = [("truth_bam_path", C.c_char_p), ("query_bam_path", C.c_char_p), ("bed_path", C.c_char_p), ("threads", C.c_int32),
-                ("device", C.c_int32), ("batch_regions", C.c_uint32), ("reserved", C.c_uint32), ("warn", C.c_void_p), ("warn_user", C.c_void_p)]
+                ("device", C.c_int32), ("batch_regions", C.c_uint32), ("reserved", C.c_uint32), ("warn", C.c_void_p), ("warn_user", C.c_void_p),
+                ("heuristic", C.c_int32), ("heur_min_wavefront_length", C.c_int32), ("heur_max_distance_threshold", C.c_int32),
+                ("heur_steps_between_cutoffs", C.c_int32)]
 
 
 class CompareCounts(C.Structure):

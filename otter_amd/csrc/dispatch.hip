@@ -956,7 +956,11 @@ int otg_compare_files(const otg_compare_job* job, otg_write_fn write, void* user
     scores.assign(tasks.size(), 0); clen.assign(tasks.size(), 0);
     if (!tasks.empty()) {
       uint64_t used = 0;
-      rc = otg_edit_align_batch(ctx.get(), seqs.data(), seqs.size(), tasks.data(), (uint32_t)tasks.size(), scores.data(), nullptr, clen.data(), nullptr, 0, &used);
+      if (job->heuristic == OTG_HEURISTIC_NONE)
+        rc = otg_edit_align_batch(ctx.get(), seqs.data(), seqs.size(), tasks.data(), (uint32_t)tasks.size(), scores.data(), nullptr, clen.data(), nullptr, 0, &used);
+      else
+        rc = otg_edit_align_heur_batch(ctx.get(), seqs.data(), seqs.size(), tasks.data(), (uint32_t)tasks.size(), job->heuristic, job->heur_min_wavefront_length,
+                                       job->heur_max_distance_threshold, job->heur_steps_between_cutoffs, scores.data(), nullptr, clen.data(), nullptr, 0, &used, nullptr);
       if (rc != OTG_OK) return otg_fail(nullptr, rc, "otg_compare_files: %s", ctx_err(ctx.get()).c_str());
     }
     pedit.assign(pair_task.size(), 0.0); pops.assign(pair_task.size(), 0.0);

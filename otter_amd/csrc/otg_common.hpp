@@ -40,6 +40,7 @@ struct otg_ctx {
   hipEvent_t edit_hist_ev[2] = {nullptr, nullptr};
   uint32_t edit_hist_mask[2] = {0u, 0u};          // the mask that pass ran with (0: no history)
   double last_score_ms = 0.0, last_prov_ms = 0.0;  // HIP-event times of the two device passes of the latest otg_edit_align_batch (otg_edit_align_last_ms)
+  uint32_t last_align_tiers[2] = {0u, 0u};         // tasks the LDS / the global-row tier of the latest adaptive otg_edit_align_heur_batch finished (otg_edit_align_last_tiers)
   double last_kmer_count_ms = 0.0, last_kmer_epi_ms = 0.0;  // HIP-event times of the latest otg_kmer_usage_batch (otg_kmer_usage_last_ms)
   hipEvent_t ev2 = nullptr;                       // third timing event, created on first use (kmer_usage.hip)
   double last_kernel_ms = 0.0;                    // HIP-event time of the kernels of the latest operator-level call that reports one (otg_last_kernel_ms)
@@ -227,6 +228,11 @@ int otg_launch_edit(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* 
 // edit_align.hip: scores (the chain above), then the diamond provenance pass and the op strings (host arrays in, host arrays out)
 int otg_launch_edit_align(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* d_tasks, const otg_align_task* h_tasks, uint32_t n_tasks,
                           int32_t* scores_out, uint32_t* len_out, uint8_t* d_cig_base, const uint64_t* cig_slot, double* score_ms, double* prov_ms);
+// the same under wfadaptive (the caller has set ctx's heuristic): the adaptive score chain, then the provenance pass under the cut; also fills
+// cells_out (host) and adds the tasks each of its two tiers finished to finished[0] (LDS window) / finished[1] (global row)
+int otg_launch_edit_align_adaptive(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* d_tasks, const otg_align_task* h_tasks, uint32_t n_tasks,
+                                   int32_t* scores_out, uint64_t* cells_out, uint32_t* len_out, uint8_t* d_cig_base, const uint64_t* cig_slot,
+                                   double* score_ms, double* prov_ms, uint32_t finished[2]);
 
 // bit-parallel edit tiers (myers_edit.hip), narrowest first: <blocks per lane, lanes per pair> = <1,8> <2,8> <3,8> <2,16> <3,16> <2,32> <2,64> <4,64>
 constexpr int OTG_MYERS_TIERS = 8;
