@@ -156,11 +156,27 @@ int otg_edit_align_heur_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t a
                               int strategy, int min_wavefront_length, int max_distance_threshold, int steps_between_cutoffs,
                               int32_t* scores_out, uint64_t* cigar_off_out, uint32_t* cigar_len_out,
                               uint8_t* cigar_arena, uint64_t cigar_capacity, uint64_t* cigar_bytes_used, uint64_t* cells_out);
-/* HIP-event times (ms) of the latest otg_edit_align_batch / otg_edit_align_heur_batch on this context: the score chain and the provenance
- * pass (which includes the backtrace and the unpack).  Measurement hook; the reference has no counterpart. */
+/* Replaces WFAlignerEdit(Alignment, MemoryMed)::alignEnd2End / alignEndsFree + getAlignmentScore() + getAlignmentCigar(): the call above that
+ * also takes tasks with endsfree != 0 (src/analignments.cpp:88-96), mixed freely with end-to-end ones, under the heuristic named per call.
+ * End-to-end tasks give exactly what otg_edit_align_batch / otg_edit_align_heur_batch give.  A task with free ends: scores_out[i] = the edit
+ * operations that are not free = otg_edit_distance_batch on the same task; the alignment starts on a diagonal of the score-0 wavefront
+ * [max(-pattern_begin_free, -pattern_len), min(text_begin_free, text_len)] and ends at the first diagonal, in ascending order, whose
+ * cell has reached the end of the text with at most pattern_end_free of the pattern left or the end of the pattern with at most text_end_free
+ * of the text left.  Op strings over M X I D with the free end gaps explicit, as otg_affine_align_batch writes them: the start
+ * diagonal's I or D run, the operations with their match runs, then I up to the end of the text and D up to the end of the pattern;
+ * cigar_len_out = pattern_len + every I.  Length-only protocol, OTG_ERR_CAPACITY, parameter validation, the untouched context heuristic
+ * and cells_out as above.                                                                                                              */
+int otg_edit_align_span_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_bytes,
+                              const otg_align_task* tasks, uint32_t n_tasks,
+                              int strategy, int min_wavefront_length, int max_distance_threshold, int steps_between_cutoffs,
+                              int32_t* scores_out, uint64_t* cigar_off_out, uint32_t* cigar_len_out,
+                              uint8_t* cigar_arena, uint64_t cigar_capacity, uint64_t* cigar_bytes_used, uint64_t* cells_out);
+/* HIP-event times (ms) of the latest otg_edit_align_batch / otg_edit_align_heur_batch / otg_edit_align_span_batch on this context: the score
+ * chain and the provenance pass (which includes the backtrace and the unpack).  Measurement hook; the reference has no counterpart. */
 int otg_edit_align_last_ms(otg_ctx* ctx, double* score_ms, double* prov_ms);
-/* How many tasks of the latest OTG_HEURISTIC_WFADAPTIVE otg_edit_align_heur_batch on this context were finished by the LDS-window tier
- * (finished[0]) and by the global-row tier (finished[1]) of its provenance pass.  Test hook, read-only. */
+/* How many tasks of the latest edit alignment call on this context were finished by the LDS-window tier (finished[0]) and by the global-row
+ * tier (finished[1]) of its provenance pass; under OTG_HEURISTIC_NONE, where the host knows the width beforehand: how many
+ * were given to each.  Test hook, read-only. */
 int otg_edit_align_last_tiers(otg_ctx* ctx, uint32_t finished[2]);
 
 /* Replaces WFAlignerGapAffine(x,o,e, Alignment, MemoryMed)::alignEnd2End/alignEndsFree +

@@ -86,12 +86,16 @@ class WFAligner {
     t.pattern_begin_free = pbf; t.pattern_end_free = pef; t.text_begin_free = tbf; t.text_end_free = tef; t.endsfree = endsfree; t._pad = 0;
     int32_t sc = 0;
     int rc;
-    if (!affine() && scope_ == Alignment && !endsfree) {
-      // WFAlignerEdit(Alignment): score and op string of the edit piggy-back (src/compare.cpp:59-61,95); ends-free keeps the score path
+    if (!affine() && scope_ == Alignment) {
+      // WFAlignerEdit(Alignment): score and op string of the edit piggy-back (src/compare.cpp:59-61,95)
       uint64_t off = 0, used = 0; uint32_t len = 0;
       ops_.resize(pattern.size() + text.size() + 64);
+      // alignEndsFree: the entry point that takes free ends, under either heuristic; the op string carries the free end gaps
+      if (endsfree)
+        rc = otg_edit_align_span_batch(ctx_, (const uint8_t*)arena_.data(), arena_.size(), &t, 1, heur_, heur_p_[0], heur_p_[1], heur_p_[2], &sc, &off, &len,
+                                       (uint8_t*)&ops_[0], ops_.size(), &used, nullptr);
       // under setHeuristicWFadaptive: the traceback of the reduced wavefronts, asked for by name (what a WFA2-lib whose default is adaptive returns)
-      if (heur_ == OTG_HEURISTIC_WFADAPTIVE)
+      else if (heur_ == OTG_HEURISTIC_WFADAPTIVE)
         rc = otg_edit_align_heur_batch(ctx_, (const uint8_t*)arena_.data(), arena_.size(), &t, 1, heur_, heur_p_[0], heur_p_[1], heur_p_[2], &sc, &off, &len,
                                        (uint8_t*)&ops_[0], ops_.size(), &used, nullptr);
       else

@@ -19,7 +19,7 @@ EXPORTS = [
     "otg_ingest_regions_named", "otg_emit_reads", "otg_parse_bed_file", "otg_fasta_open", "otg_fasta_close", "otg_fasta_n_seqs",
     "otg_fasta_seq", "otg_fasta_fetch", "otg_fasta_region_flanks",
     "otg_bam_sample_index", "otg_bam_sample", "otg_ingest_alleles", "otg_emit_vcf_header", "otg_emit_vcf_lines", "otg_emit_genotype_lengths", "otg_assemble_files", "otg_assemble_files_release", "otg_assemble_batch_plan", "otg_genotype_files", "otg_wgat",
-    "otg_edit_align_batch", "otg_edit_align_heur_batch", "otg_edit_align_last_ms", "otg_edit_align_last_tiers", "otg_ingest_compare_alleles", "otg_compare_emit", "otg_compare_files",
+    "otg_edit_align_batch", "otg_edit_align_heur_batch", "otg_edit_align_span_batch", "otg_edit_align_last_ms", "otg_edit_align_last_tiers", "otg_ingest_compare_alleles", "otg_compare_emit", "otg_compare_files",
     "otg_kmer_usage_batch", "otg_kmer_usage_device_results", "otg_kmer_usage_last_ms", "otg_vcf_open", "otg_vcf_close", "otg_vcf_read_alleles",
     "otg_vcf2mat_emit", "otg_vcf2mat_files",
     "otg_cohort_begin", "otg_cohort_stage", "otg_cohort_regroup", "otg_cohort_genotype", "otg_cohort_result_sizes", "otg_cohort_collect",
@@ -142,6 +142,9 @@ class Context:
         """otg_edit_align_heur_batch: edit_align_batch under the heuristic named here (abi.OTG_HEURISTIC_NONE, or abi.OTG_HEURISTIC_WFADAPTIVE
         with min_wavefront_length a, max_distance_threshold b, steps_between_cutoffs c); the context's own heuristic is left alone.
         -> (scores, op strings or lengths) and, with want_cells, the score chain's cell counts as a third item."""
+        return self._edit_align_named("otg_edit_align_heur_batch", arena, tasks, strategy, a, b, c, want_cigars, want_cells)
+
+    def _edit_align_named(self, entry, arena, tasks, strategy, a, b, c, want_cigars, want_cells):
         n = len(tasks)
         scores = np.zeros(n, dtype=np.int32)
         off = np.zeros(n, dtype=np.uint64)
@@ -153,13 +156,18 @@ class Context:
             out = np.zeros(cap, dtype=np.uint8)
         else:
             cap, out = 0, None
-        rc = self._L.otg_edit_align_heur_batch(self._h, abi.ptr(arena), C.c_uint64(arena.size), abi.ptr(tasks), C.c_uint32(n),
-                                               C.c_int(int(strategy)), C.c_int(int(a)), C.c_int(int(b)), C.c_int(int(c)), abi.ptr(scores),
-                                               abi.ptr(off) if want_cigars else None, abi.ptr(ln), abi.ptr(out) if want_cigars else None,
-                                               C.c_uint64(cap), C.byref(used), abi.ptr(cells) if want_cells else None)
-        self._check(rc, "otg_edit_align_heur_batch")
+        rc = getattr(self._L, entry)(self._h, abi.ptr(arena), C.c_uint64(arena.size), abi.ptr(tasks), C.c_uint32(n),
+                                     C.c_int(int(strategy)), C.c_int(int(a)), C.c_int(int(b)), C.c_int(int(c)), abi.ptr(scores),
+                                     abi.ptr(off) if want_cigars else None, abi.ptr(ln), abi.ptr(out) if want_cigars else None,
+                                     C.c_uint64(cap), C.byref(used), abi.ptr(cells) if want_cells else None)
+        self._check(rc, entry)
         second = [out[int(off[i]):int(off[i]) + int(ln[i])].tobytes() for i in range(n)] if want_cigars else ln
         return (scores, second, cells) if want_cells else (scores, second)
+
+    def edit_align_span_batch(self, arena, tasks, strategy=abi.OTG_HEURISTIC_NONE, a=10, b=50, c=1, want_cigars=True, want_cells=False):
+        """otg_edit_align_span_batch: edit_align_heur_batch that also takes tasks with free ends (alignEndsFree), mixed with end-to-end ones;
+        their op strings carry the free end gaps.  Same arguments and results."""
+        return self._edit_align_named("otg_edit_align_span_batch", arena, tasks, strategy, a, b, c, want_cigars, want_cells)
 
     def edit_align_last_ms(self):
         """(score chain ms, provenance pass ms) of the latest edit_align_batch / edit_align_heur_batch (HIP events)."""
@@ -168,7 +176,7 @@ class Context:
         return a.value, b.value
 
     def edit_align_last_tiers(self):
-        """(tasks finished by the LDS-window tier, by the global-row tier) of the latest adaptive edit_align_heur_batch."""
+        """(tasks finished by the LDS-window tier, by the global-row tier) of the latest edit alignment call (exact: given to each)."""
         f = (C.c_uint32 * 2)(0, 0)
         self._check(self._L.otg_edit_align_last_tiers(self._h, f), "otg_edit_align_last_tiers")
         return int(f[0]), int(f[1])

@@ -211,21 +211,13 @@ int otg_edit_distance_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t are
   return OTG_OK;
 }
 
-int otg_edit_align_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_bytes, const otg_align_task* tasks, uint32_t n_tasks,
-                         int32_t* scores_out, uint64_t* cigar_off_out, uint32_t* cigar_len_out,
-                         uint8_t* cigar_arena, uint64_t cigar_capacity, uint64_t* cigar_bytes_used)
+// Staging shared by the three edit alignment entry points (the caller has validated its arguments and set ctx's heuristic): arena and tasks to
+// the device, device op-string slots, the launch (exact: otg_launch_edit_align, adaptive: otg_launch_edit_align_adaptive), the times and tier
+// counts of the call, the cell counts, then the length-only / capacity protocol and the packed op strings.
+static int edit_align_staged(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_bytes, const otg_align_task* tasks, uint32_t n_tasks, bool adaptive,
+                             int32_t* scores_out, uint64_t* cigar_off_out, uint32_t* cigar_len_out,
+                             uint8_t* cigar_arena, uint64_t cigar_capacity, uint64_t* cigar_bytes_used, uint64_t* cells_out)
 {
-  if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_edit_align_batch: no context (no HIP device?)");
-  if (cigar_bytes_used) *cigar_bytes_used = 0;
-  if (n_tasks == 0) return OTG_OK;
-  if (!seq_arena || !tasks || !scores_out || !cigar_len_out || (cigar_arena && !cigar_off_out))
-    return otg_fail(ctx, OTG_ERR_ARG, "otg_edit_align_batch: NULL argument");
-  if (ctx->heur_strategy != OTG_HEURISTIC_NONE)
-    return otg_fail(ctx, OTG_ERR_ARG, "otg_edit_align_batch: exact alignment only; the context's heuristic is WFadaptive (its traceback is not implemented)");
-  for (uint32_t i = 0; i < n_tasks; ++i)
-    if (tasks[i].endsfree) return otg_fail(ctx, OTG_ERR_ARG, "otg_edit_align_batch: task %u is ends-free; only end-to-end alignment is supported", i);
-  int rc = check_tasks(ctx, tasks, n_tasks, arena_bytes);
-  if (rc) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   // device op-string slots: task i has at most pattern_len + text_len columns
   std::vector<uint64_t> slot(n_tasks + 1);
@@ -240,9 +232,23 @@ int otg_edit_align_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_
   HIP_TRY(ctx, hipMemcpyAsync(d_tasks, tasks, (size_t)n_tasks * sizeof(otg_align_task), hipMemcpyHostToDevice, ctx->stream));
   ctx->max_seq_len = max_len_of(tasks, n_tasks);
   double sms = 0, pms = 0;
-  rc = otg_launch_edit_align(ctx, d_arena, d_tasks, tasks, n_tasks, scores_out, cigar_len_out, d_cig, slot.data(), &sms, &pms);
-  if (rc) return rc;
+  uint32_t fin[2] = {0u, 0u};
+  int rc;
+  if (adaptive) {
+    std::vector<uint64_t> cells(n_tasks);
+    rc = otg_launch_edit_align_adaptive(ctx, d_arena, d_tasks, tasks, n_tasks, scores_out, cells.data(), cigar_len_out, d_cig, slot.data(), &sms, &pms, fin);
+    if (rc) return rc;
+    if (cells_out) memcpy(cells_out, cells.data(), (size_t)n_tasks * sizeof(uint64_t));
+  } else {
+    rc = otg_launch_edit_align(ctx, d_arena, d_tasks, tasks, n_tasks, scores_out, cigar_len_out, d_cig, slot.data(), &sms, &pms, fin);
+    if (rc) return rc;
+    if (cells_out) {        // the exact score chain left its cell counts in SLOT_CELLS
+      if (hipMemcpy(cells_out, ctx->pool[SLOT_CELLS].p, (size_t)n_tasks * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
+        return otg_fail(ctx, OTG_ERR_HIP, "copying the cell counts failed");
+    }
+  }
   ctx->last_score_ms = sms; ctx->last_prov_ms = pms;
+  ctx->last_align_tiers[0] = fin[0]; ctx->last_align_tiers[1] = fin[1];
   uint64_t pos = 0;
   for (uint32_t i = 0; i < n_tasks; ++i) pos += cigar_len_out[i];
   if (cigar_bytes_used) *cigar_bytes_used = pos;
@@ -260,6 +266,25 @@ int otg_edit_align_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_
   return OTG_OK;
 }
 
+int otg_edit_align_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_bytes, const otg_align_task* tasks, uint32_t n_tasks,
+                         int32_t* scores_out, uint64_t* cigar_off_out, uint32_t* cigar_len_out,
+                         uint8_t* cigar_arena, uint64_t cigar_capacity, uint64_t* cigar_bytes_used)
+{
+  if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_edit_align_batch: no context (no HIP device?)");
+  if (cigar_bytes_used) *cigar_bytes_used = 0;
+  if (n_tasks == 0) return OTG_OK;
+  if (!seq_arena || !tasks || !scores_out || !cigar_len_out || (cigar_arena && !cigar_off_out))
+    return otg_fail(ctx, OTG_ERR_ARG, "otg_edit_align_batch: NULL argument");
+  if (ctx->heur_strategy != OTG_HEURISTIC_NONE)
+    return otg_fail(ctx, OTG_ERR_ARG, "otg_edit_align_batch: exact alignment only; the context's heuristic is WFadaptive (its traceback is not implemented)");
+  for (uint32_t i = 0; i < n_tasks; ++i)
+    if (tasks[i].endsfree) return otg_fail(ctx, OTG_ERR_ARG, "otg_edit_align_batch: task %u is ends-free; only end-to-end alignment is supported", i);
+  int rc = check_tasks(ctx, tasks, n_tasks, arena_bytes);
+  if (rc) return rc;
+  return edit_align_staged(ctx, seq_arena, arena_bytes, tasks, n_tasks, false, scores_out, cigar_off_out, cigar_len_out, cigar_arena, cigar_capacity,
+                           cigar_bytes_used, nullptr);
+}
+
 int otg_edit_align_last_ms(otg_ctx* ctx, double* score_ms, double* prov_ms)
 {
   if (!ctx) return otg_fail(nullptr, OTG_ERR_ARG, "otg_edit_align_last_ms: NULL context");
@@ -268,80 +293,57 @@ int otg_edit_align_last_ms(otg_ctx* ctx, double* score_ms, double* prov_ms)
   return OTG_OK;
 }
 
+// otg_edit_align_heur_batch and otg_edit_align_span_batch: the heuristic named per call; the second takes tasks with free ends too
+static int edit_align_named(otg_ctx* ctx, const char* who, bool span, const uint8_t* seq_arena, uint64_t arena_bytes, const otg_align_task* tasks, uint32_t n_tasks,
+                            int strategy, int min_wavefront_length, int max_distance_threshold, int steps_between_cutoffs,
+                            int32_t* scores_out, uint64_t* cigar_off_out, uint32_t* cigar_len_out,
+                            uint8_t* cigar_arena, uint64_t cigar_capacity, uint64_t* cigar_bytes_used, uint64_t* cells_out)
+{
+  if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "%s: no context (no HIP device?)", who);
+  if (cigar_bytes_used) *cigar_bytes_used = 0;
+  if (strategy != OTG_HEURISTIC_NONE && strategy != OTG_HEURISTIC_WFADAPTIVE)
+    return otg_fail(ctx, OTG_ERR_ARG, "%s: unknown strategy %d", who, strategy);
+  if (strategy == OTG_HEURISTIC_WFADAPTIVE && (min_wavefront_length < 0 || max_distance_threshold < 0))
+    return otg_fail(ctx, OTG_ERR_ARG, "%s: negative wavefront length or distance threshold", who);
+  if (n_tasks == 0) return OTG_OK;
+  if (!seq_arena || !tasks || !scores_out || !cigar_len_out || (cigar_arena && !cigar_off_out))
+    return otg_fail(ctx, OTG_ERR_ARG, "%s: NULL argument", who);
+  if (!span)
+    for (uint32_t i = 0; i < n_tasks; ++i)
+      if (tasks[i].endsfree) return otg_fail(ctx, OTG_ERR_ARG, "%s: task %u is ends-free; only end-to-end alignment is supported", who, i);
+  int rc = check_tasks(ctx, tasks, n_tasks, arena_bytes);
+  if (rc) return rc;
+  // the context's own heuristic is neither consulted nor left changed: the score chain reads it, so it is set for the call and put back on every path
+  const int saved[4] = {ctx->heur_strategy, ctx->heur_min_wf_len, ctx->heur_max_dist, ctx->heur_steps};
+  ctx->heur_strategy = strategy;
+  if (strategy == OTG_HEURISTIC_WFADAPTIVE) {
+    ctx->heur_min_wf_len = min_wavefront_length; ctx->heur_max_dist = max_distance_threshold;
+    ctx->heur_steps = steps_between_cutoffs < 1 ? 1 : steps_between_cutoffs;
+  }
+  rc = edit_align_staged(ctx, seq_arena, arena_bytes, tasks, n_tasks, strategy == OTG_HEURISTIC_WFADAPTIVE, scores_out, cigar_off_out, cigar_len_out,
+                         cigar_arena, cigar_capacity, cigar_bytes_used, cells_out);
+  ctx->heur_strategy = saved[0]; ctx->heur_min_wf_len = saved[1]; ctx->heur_max_dist = saved[2]; ctx->heur_steps = saved[3];
+  return rc;
+}
+
 int otg_edit_align_heur_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_bytes, const otg_align_task* tasks, uint32_t n_tasks,
                               int strategy, int min_wavefront_length, int max_distance_threshold, int steps_between_cutoffs,
                               int32_t* scores_out, uint64_t* cigar_off_out, uint32_t* cigar_len_out,
                               uint8_t* cigar_arena, uint64_t cigar_capacity, uint64_t* cigar_bytes_used, uint64_t* cells_out)
 {
-  if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_edit_align_heur_batch: no context (no HIP device?)");
-  if (cigar_bytes_used) *cigar_bytes_used = 0;
-  if (strategy != OTG_HEURISTIC_NONE && strategy != OTG_HEURISTIC_WFADAPTIVE)
-    return otg_fail(ctx, OTG_ERR_ARG, "otg_edit_align_heur_batch: unknown strategy %d", strategy);
-  if (strategy == OTG_HEURISTIC_WFADAPTIVE && (min_wavefront_length < 0 || max_distance_threshold < 0))
-    return otg_fail(ctx, OTG_ERR_ARG, "otg_edit_align_heur_batch: negative wavefront length or distance threshold");
-  if (n_tasks == 0) return OTG_OK;
-  if (!seq_arena || !tasks || !scores_out || !cigar_len_out || (cigar_arena && !cigar_off_out))
-    return otg_fail(ctx, OTG_ERR_ARG, "otg_edit_align_heur_batch: NULL argument");
-  for (uint32_t i = 0; i < n_tasks; ++i)
-    if (tasks[i].endsfree) return otg_fail(ctx, OTG_ERR_ARG, "otg_edit_align_heur_batch: task %u is ends-free; only end-to-end alignment is supported", i);
-  int rc = check_tasks(ctx, tasks, n_tasks, arena_bytes);
-  if (rc) return rc;
-  // the context's own heuristic is neither consulted nor left changed: the score chain reads it, so it is set for the call and put back on every path
-  const int saved[4] = {ctx->heur_strategy, ctx->heur_min_wf_len, ctx->heur_max_dist, ctx->heur_steps};
-  auto restore = [&](int code) {
-    ctx->heur_strategy = saved[0]; ctx->heur_min_wf_len = saved[1]; ctx->heur_max_dist = saved[2]; ctx->heur_steps = saved[3];
-    return code;
-  };
-  ctx->heur_strategy = strategy;
-  if (strategy == OTG_HEURISTIC_NONE) {
-    rc = otg_edit_align_batch(ctx, seq_arena, arena_bytes, tasks, n_tasks, scores_out, cigar_off_out, cigar_len_out, cigar_arena, cigar_capacity, cigar_bytes_used);
-    if ((rc == OTG_OK || rc == OTG_ERR_CAPACITY) && cells_out) {        // the exact score chain left its cell counts in SLOT_CELLS
-      if (hipMemcpy(cells_out, ctx->pool[SLOT_CELLS].p, (size_t)n_tasks * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return restore(otg_fail(ctx, OTG_ERR_HIP, "otg_edit_align_heur_batch: copying the cell counts failed"));
-    }
-    return restore(rc);
-  }
-  ctx->heur_min_wf_len = min_wavefront_length; ctx->heur_max_dist = max_distance_threshold;
-  ctx->heur_steps = steps_between_cutoffs < 1 ? 1 : steps_between_cutoffs;
-  auto run = [&]() -> int {
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // device op-string slots: task i has at most pattern_len + text_len columns
-    std::vector<uint64_t> slot(n_tasks + 1);
-    slot[0] = 0;
-    for (uint32_t i = 0; i < n_tasks; ++i) slot[i + 1] = slot[i] + (cigar_arena ? (((uint64_t)tasks[i].pattern_len + tasks[i].text_len + 15) & ~15ull) : 0);
-    uint8_t* d_arena = (uint8_t*)otg_slot(ctx, SLOT_ARENA, arena_bytes + 64);
-    otg_align_task* d_tasks = (otg_align_task*)otg_slot(ctx, SLOT_TASKS, (size_t)n_tasks * sizeof(otg_align_task));
-    uint8_t* d_cig = cigar_arena ? (uint8_t*)otg_slot(ctx, SLOT_CIG_ARENA, slot[n_tasks] + 64) : nullptr;
-    if (!d_arena || !d_tasks || (cigar_arena && !d_cig)) return OTG_ERR_HIP;
-    HIP_TRY(ctx, hipMemsetAsync(d_arena + arena_bytes, 0, 64, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_arena, seq_arena, arena_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_tasks, tasks, (size_t)n_tasks * sizeof(otg_align_task), hipMemcpyHostToDevice, ctx->stream));
-    ctx->max_seq_len = max_len_of(tasks, n_tasks);
-    double sms = 0, pms = 0;
-    std::vector<uint64_t> cells(n_tasks);
-    uint32_t fin[2] = {0u, 0u};
-    int r = otg_launch_edit_align_adaptive(ctx, d_arena, d_tasks, tasks, n_tasks, scores_out, cells.data(), cigar_len_out, d_cig, slot.data(), &sms, &pms, fin);
-    if (r) return r;
-    ctx->last_score_ms = sms; ctx->last_prov_ms = pms;
-    ctx->last_align_tiers[0] = fin[0]; ctx->last_align_tiers[1] = fin[1];
-    if (cells_out) memcpy(cells_out, cells.data(), (size_t)n_tasks * sizeof(uint64_t));
-    uint64_t pos = 0;
-    for (uint32_t i = 0; i < n_tasks; ++i) pos += cigar_len_out[i];
-    if (cigar_bytes_used) *cigar_bytes_used = pos;
-    if (!cigar_arena) return OTG_OK;
-    if (pos > cigar_capacity) return otg_fail(ctx, OTG_ERR_CAPACITY, "cigar_capacity %llu too small, %llu needed", (unsigned long long)cigar_capacity, (unsigned long long)pos);
-    std::vector<uint8_t> h_cig(slot[n_tasks] + 1);
-    HIP_TRY(ctx, hipMemcpyAsync(h_cig.data(), d_cig, slot[n_tasks], hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    pos = 0;
-    for (uint32_t i = 0; i < n_tasks; ++i) {
-      cigar_off_out[i] = pos;
-      memcpy(cigar_arena + pos, h_cig.data() + slot[i], cigar_len_out[i]);
-      pos += cigar_len_out[i];
-    }
-    return OTG_OK;
-  };
-  return restore(run());
+  return edit_align_named(ctx, "otg_edit_align_heur_batch", false, seq_arena, arena_bytes, tasks, n_tasks, strategy, min_wavefront_length,
+                          max_distance_threshold, steps_between_cutoffs, scores_out, cigar_off_out, cigar_len_out, cigar_arena, cigar_capacity,
+                          cigar_bytes_used, cells_out);
+}
+
+int otg_edit_align_span_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_bytes, const otg_align_task* tasks, uint32_t n_tasks,
+                              int strategy, int min_wavefront_length, int max_distance_threshold, int steps_between_cutoffs,
+                              int32_t* scores_out, uint64_t* cigar_off_out, uint32_t* cigar_len_out,
+                              uint8_t* cigar_arena, uint64_t cigar_capacity, uint64_t* cigar_bytes_used, uint64_t* cells_out)
+{
+  return edit_align_named(ctx, "otg_edit_align_span_batch", true, seq_arena, arena_bytes, tasks, n_tasks, strategy, min_wavefront_length,
+                          max_distance_threshold, steps_between_cutoffs, scores_out, cigar_off_out, cigar_len_out, cigar_arena, cigar_capacity,
+                          cigar_bytes_used, cells_out);
 }
 
 int otg_edit_align_last_tiers(otg_ctx* ctx, uint32_t finished[2])

@@ -225,9 +225,11 @@ __device__ __forceinline__ int otg_wave_match(const uint8_t* P, const uint8_t* T
 int otg_launch_edit(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* d_tasks, uint32_t n_tasks,
                     int32_t* d_scores, uint64_t* d_cells, float* kernel_ms, uint64_t* launches);
 
-// edit_align.hip: scores (the chain above), then the diamond provenance pass and the op strings (host arrays in, host arrays out)
+// edit_align.hip: scores (the chain above), then the diamond provenance pass and the op strings (host arrays in, host arrays out).  Tasks with
+// free ends take the ends-free region and kernels.  finished (nullable): as below, the tasks given to the LDS tier / the global-row tier
 int otg_launch_edit_align(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* d_tasks, const otg_align_task* h_tasks, uint32_t n_tasks,
-                          int32_t* scores_out, uint32_t* len_out, uint8_t* d_cig_base, const uint64_t* cig_slot, double* score_ms, double* prov_ms);
+                          int32_t* scores_out, uint32_t* len_out, uint8_t* d_cig_base, const uint64_t* cig_slot, double* score_ms, double* prov_ms,
+                          uint32_t* finished = nullptr);
 // the same under wfadaptive (the caller has set ctx's heuristic): the adaptive score chain, then the provenance pass under the cut; also fills
 // cells_out (host) and adds the tasks each of its two tiers finished to finished[0] (LDS window) / finished[1] (global row)
 int otg_launch_edit_align_adaptive(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* d_tasks, const otg_align_task* h_tasks, uint32_t n_tasks,
