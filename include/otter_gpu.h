@@ -91,9 +91,20 @@ int         otg_trim(otg_ctx* ctx);
 const char* otg_last_error(otg_ctx* ctx);     /* ctx may be NULL: last global error           */
 int         otg_device_count(void);           /* number of visible HIP devices (0 if none)    */
 /* Which libm exp() rounding variant the device KDE mirrors (1 = glibc FMA build, 0 = non-FMA).
- * Chosen at otg_create by probing the host libm so cluster labels match the reference
- * running on this host (SURVEY.md §7.2 "FP determinism"). */
+ * Chosen at otg_create by probing the host libm: the variant whose restatement equals exp() on every argument of a probe set that
+ * holds the arguments on which the two builds differ (SURVEY.md §7.2 "FP determinism").  The densities then equal the reference's on
+ * this host as far as that set shows; otg_exp_probe_mismatches is the evidence. */
 int         otg_exp_variant(otg_ctx* ctx);
+/* On how many arguments of the probe set the chosen variant differed from the host libm's exp() (0 on a glibc 2.28+ host; non-zero: the
+ * host libm is neither build, and KDE densities may differ from the reference's on this host in the last place).  -1 without a context. */
+long long   otg_exp_probe_mismatches(otg_ctx* ctx);
+/* The probe itself, without a context or a device: the size of the set, on how many of its arguments the two restatements differ from each
+ * other, and each one's mismatches against the host libm.  Returns the variant otg_create would choose.  Any pointer may be NULL. */
+int         otg_exp_probe(uint64_t* n_args, uint64_t* n_differ, uint64_t* mismatches_fma, uint64_t* mismatches_nofma);
+/* For tests: out[i] = the host restatement of glibc's exp() in `variant` (1 = FMA build, 0 = non-FMA) — needs no device — and the device
+ * function the clustering kernel calls (in-place kernel over a copy of x).  Both return OTG_OK or OTG_ERR_ARG / a HIP error. */
+int         otg_exp_host(const double* x, uint64_t n, int variant, double* out);
+int         otg_exp_device(otg_ctx* ctx, const double* x, uint64_t n, int variant, double* out);
 
 /* Heuristic of the L1 aligner calls on this context — wfa::WFAligner::setHeuristicNone() /
  * setHeuristicWFadaptive(min_wavefront_length, max_distance_threshold, steps_between_cutoffs) (bindings/cpp/WFAligner.hpp:107-122 of
@@ -234,6 +245,31 @@ int otg_cluster_batch(otg_ctx* ctx, const otg_params* params,
                       const uint32_t* n_valid, uint32_t n_regions,
                       int32_t* labels_out, int32_t* ic_out, int32_t* fc_out, double* bounds_out);
 
+/* For tests (like otg_affine_last_routing): otg_cluster_batch with the intermediates of every region copied out.  exp_variant -1 = the
+ * context's, 0 / 1 = that variant of exp().  A region that ends in an error code 1-5 does not fail the call: its code is in the trace
+ * (labels -1, ic = fc = 0).  The caller allocates every array; what the kernel does not reach keeps the fill (every byte 0xff).
+ *   per region, OTG_TRACE_GRID doubles (n_grid used): dens_raw = KDE::f on the grid, dens = normalised, sums = the window sums;
+ *   per region, OTG_TRACE_EXT entries (n_max / n_min used): max_i / max_v, min_i / min_v = the extrema of KDE::maximas;
+ *   state, 8 ints per region: evaluated (0: n <= 2 or max_alleles == 1, nothing else written), n_grid, n_max, n_min, do_hclust, err,
+ *     cut_k (clusters of the first cut), recut (1: cutree_k(max_alleles) replaced the labels);  scalars, 2 doubles: bandwidth, dist_final;
+ *   with do_hclust: merge (R convention, column-major, 2(n-1) ints at 2 * len_off[r]), height (n-1 doubles at len_off[r]),
+ *     labels_first (n ints at len_off[r]: the first cut, before the coverage repair).                                                   */
+#define OTG_TRACE_GRID 512
+#define OTG_TRACE_EXT 258
+typedef struct otg_cluster_trace {
+  double *dens_raw, *dens, *sums;
+  int32_t* max_i; double* max_v;
+  int32_t* min_i; double* min_v;
+  int32_t* state; double* scalars;
+  int32_t* merge; double* height; int32_t* labels_first;
+} otg_cluster_trace;
+int otg_cluster_trace_batch(otg_ctx* ctx, const otg_params* params,
+                            const double* dist, const uint64_t* dist_off,
+                            const uint32_t* read_len, const uint64_t* len_off,
+                            const uint32_t* n_valid, uint32_t n_regions,
+                            int32_t* labels_out, int32_t* ic_out, int32_t* fc_out, double* bounds_out,
+                            int exp_variant, const otg_cluster_trace* trace);
+
 /* Replaces PPOA (src/anppoa.hpp:64-380) as driven by rapid_consensus (src/analignments.cpp:261-292):
  * graph g has backbone = task `backbone`, then members inserted in order; each member is a
  * sequence + its op string + spanning flags.  c/t are the adjust_weights arguments.
@@ -268,6 +304,22 @@ int otg_genotype_cluster_batch(otg_ctx* ctx, const otg_params* params,
                                const uint32_t* first_allele, const uint32_t* n_alleles, uint32_t n_regions,
                                int32_t* gt_out, int32_t* gt_l_out, int32_t* gt_k_out, double* hsd_out,
                                int32_t* n_gt_out, int32_t* reps_out);
+
+/* For tests (like otg_affine_last_routing): otg_genotype_cluster_batch with the kernel's matrices copied out.  Region r's condensed matrices
+ * (row-major pairs i < j) start at the running sum of A (A - 1) / 2 over the regions before it, its per-allele rows at first_allele[r]:
+ *   dl = length-ratio matrix, dk = 3-mer cosine-distance matrix (both as computed, before clustering);
+ *   kvec = 65 frequencies per allele (64 three-mers + the bin of three-mers with a byte outside ACGT), vnorm = their Euclidean norm;
+ *   height_l / height_k = the A - 1 merge heights of the two average-linkage clusterings, from the region's first allele on.
+ * The caller allocates: dl, dk [total pairs], kvec [alleles x 65], vnorm, height_l, height_k [alleles].                                    */
+typedef struct otg_genotype_trace {
+  double *dl, *dk, *kvec, *vnorm, *height_l, *height_k;
+} otg_genotype_trace;
+int otg_genotype_cluster_trace_batch(otg_ctx* ctx, const otg_params* params,
+                                     const uint8_t* seq_arena, uint64_t arena_bytes,
+                                     const uint64_t* seq_off, const uint32_t* seq_len,
+                                     const uint32_t* first_allele, const uint32_t* n_alleles, uint32_t n_regions,
+                                     int32_t* gt_out, int32_t* gt_l_out, int32_t* gt_k_out, double* hsd_out,
+                                     int32_t* n_gt_out, int32_t* reps_out, const otg_genotype_trace* trace);
 
 /* HIP-event time (ms, events on the context's own stream) of the device kernels of the latest otg_genotype_cluster_batch on this context:
  * what a roofline figure divides by; host copies excluded.  The reference has no counterpart (measurement hook).        */

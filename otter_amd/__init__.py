@@ -7,4 +7,5 @@ from ._lib import Context, Comm, OtterGpuError, device_count, load, LIB_PATH, EX
 from ._lib import Fasta, parse_bed_file, bed_tuples, emit_reads, assemble_files, assemble_files_release, assemble_batch_plan, genotype_files, wgat  # noqa: F401
 from ._lib import emit_vcf_header, emit_vcf_lines, emit_genotype_lengths, genotype_blocks, compare_emit, compare_files  # noqa: F401
 from ._lib import vcf_read_alleles, vcf2mat_emit, vcf2mat_files, cohort_files, BamSink, merge_bams  # noqa: F401
+from ._lib import exp_host, exp_probe  # noqa: F401
 from .abi import default_params  # noqa: F401

@@ -26,6 +26,7 @@ EXPORTS = [
     "otg_cohort_end", "otg_cohort_files", "otg_kmer_cohort_rows", "otg_kmer_cohort_usage", "otg_kmer_cohort_device_rows",
     "otg_bam_sink_open", "otg_bam_sink_write", "otg_bam_sink_close", "otg_bam_sink_abort", "otg_bam_sink_error", "otg_bam_merge",
     "otg_comm_unique_id", "otg_comm_create", "otg_comm_destroy", "otg_gather_sizes", "otg_gather_records",
+    "otg_exp_probe_mismatches", "otg_exp_probe", "otg_exp_host", "otg_exp_device", "otg_cluster_trace_batch", "otg_genotype_cluster_trace_batch",
 ]
 
 _lib = None
@@ -55,7 +56,38 @@ def load():
         _lib.otg_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
         _lib.otg_destroy.argtypes = [C.c_void_p]
         _lib.otg_trim.argtypes = [C.c_void_p]
+        _lib.otg_exp_probe_mismatches.restype = C.c_longlong
+        _lib.otg_exp_probe_mismatches.argtypes = [C.c_void_p]
     return _lib
+
+
+def exp_host(x, variant):
+    """otg_exp_host: the host restatement of glibc's exp() in `variant` (1 = FMA build, 0 = non-FMA) over a float64 array; needs no device."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    out = np.empty_like(x)
+    rc = load().otg_exp_host(abi.ptr(x), C.c_uint64(x.size), C.c_int(int(variant)), abi.ptr(out))
+    if rc != 0:
+        raise OtterGpuError("otg_exp_host failed (%d): %s" % (rc, (load().otg_last_error(None) or b"").decode()))
+    return out
+
+
+def exp_probe():
+    """otg_exp_probe: the libm probe of otg_create without a device -> dict(variant, n_args, n_differ, mismatches_fma, mismatches_nofma)."""
+    v = [C.c_uint64(0) for _ in range(4)]
+    variant = load().otg_exp_probe(*(C.byref(q) for q in v))
+    return {"variant": int(variant), "n_args": v[0].value, "n_differ": v[1].value, "mismatches_fma": v[2].value, "mismatches_nofma": v[3].value}
+
+
+class otg_cluster_trace(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("dens_raw", "dens", "sums", "max_i", "max_v", "min_i", "min_v", "state", "scalars", "merge", "height", "labels_first")]
+
+
+class otg_genotype_trace(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("dl", "dk", "kvec", "vnorm", "height_l", "height_k")]
+
+
+TRACE_GRID, TRACE_EXT = 512, 258
+TRACE_STATE = ("evaluated", "n_grid", "n_max", "n_min", "do_hclust", "err", "cut_k", "recut")
 
 
 class Context:
@@ -101,6 +133,18 @@ class Context:
     @property
     def exp_variant(self):
         return self._L.otg_exp_variant(self._h)
+
+    @property
+    def exp_probe_mismatches(self):
+        """on how many arguments of otg_create's probe set the chosen exp variant differed from the host libm (otg_exp_probe_mismatches)"""
+        return int(self._L.otg_exp_probe_mismatches(self._h))
+
+    def exp_device(self, x, variant):
+        """otg_exp_device: the device exp() of the clustering kernel in `variant` over a float64 array"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        out = np.empty_like(x)
+        self._check(self._L.otg_exp_device(self._h, abi.ptr(x), C.c_uint64(x.size), C.c_int(int(variant)), abi.ptr(out)), "otg_exp_device")
+        return out
 
     # ------------------------------------------------------------------ L1
     def set_heuristic(self, strategy=abi.OTG_HEURISTIC_NONE, min_wavefront_length=10, max_distance_threshold=50, steps_between_cutoffs=1):
@@ -275,6 +319,29 @@ class Context:
         self._check(rc, "otg_cluster_batch")
         return labels, ic, fc, bounds.reshape(-1, 3)
 
+    def cluster_trace_batch(self, params, dist, dist_off, read_len, len_off, n_valid, exp_variant=-1):
+        """otg_cluster_trace_batch: cluster_batch plus the kernel's intermediates -> (labels, ic, fc, bounds, trace); trace is a dict of
+        arrays with one row per region (dens_raw / dens / sums [TRACE_GRID], max_i / max_v / min_i / min_v [TRACE_EXT], state [8, see
+        TRACE_STATE], scalars [bandwidth, dist_final]) and merge / height / labels_first indexed through len_off.  Bytes the kernel did
+        not write are 0xff."""
+        nreg = len(n_valid)
+        nlen = int(read_len.size)
+        labels = np.full(nlen, -1, dtype=np.int32)
+        ic = np.zeros(nreg, dtype=np.int32)
+        fc = np.zeros(nreg, dtype=np.int32)
+        bounds = np.full(3 * nreg, np.nan)
+        tr = {"dens_raw": np.zeros((nreg, TRACE_GRID)), "dens": np.zeros((nreg, TRACE_GRID)), "sums": np.zeros((nreg, TRACE_GRID)),
+              "max_i": np.zeros((nreg, TRACE_EXT), dtype=np.int32), "max_v": np.zeros((nreg, TRACE_EXT)),
+              "min_i": np.zeros((nreg, TRACE_EXT), dtype=np.int32), "min_v": np.zeros((nreg, TRACE_EXT)),
+              "state": np.zeros((nreg, 8), dtype=np.int32), "scalars": np.zeros((nreg, 2)),
+              "merge": np.zeros(2 * nlen + 2, dtype=np.int32), "height": np.zeros(nlen + 1), "labels_first": np.zeros(nlen + 1, dtype=np.int32)}
+        t = otg_cluster_trace(*(tr[n].ctypes.data for n, _ in otg_cluster_trace._fields_))
+        rc = self._L.otg_cluster_trace_batch(self._h, C.byref(params), abi.ptr(dist), abi.ptr(dist_off), abi.ptr(read_len), abi.ptr(len_off),
+                                             abi.ptr(n_valid), C.c_uint32(nreg), abi.ptr(labels), abi.ptr(ic), abi.ptr(fc), abi.ptr(bounds),
+                                             C.c_int(int(exp_variant)), C.byref(t))
+        self._check(rc, "otg_cluster_trace_batch")
+        return labels, ic, fc, bounds.reshape(-1, 3), tr
+
     def poa_consensus_batch(self, seq_arena, cig_arena, members, graphs):
         ng = len(graphs)
         off = np.zeros(ng, dtype=np.uint64)
@@ -301,6 +368,28 @@ class Context:
                                                 abi.ptr(gt), abi.ptr(gl), abi.ptr(gk), abi.ptr(hsd), abi.ptr(ngt), abi.ptr(reps))
         self._check(rc, "otg_genotype_cluster_batch")
         return gt, gl, gk, hsd, ngt, reps
+
+    def genotype_cluster_trace_batch(self, params, arena, seq_off, seq_len, first_allele, n_alleles):
+        """otg_genotype_cluster_trace_batch: genotype_cluster_batch's tuple plus a dict of the kernel's matrices: dl, dk (condensed, region
+        after region), kvec [alleles, 65], vnorm, height_l, height_k [alleles; A - 1 used from a region's first allele on]."""
+        nreg = len(n_alleles)
+        na = len(seq_off)
+        gt, gl, gk = (np.zeros(na, dtype=np.int32) for _ in range(3))
+        hsd = np.zeros(na)
+        ngt = np.zeros(nreg, dtype=np.int32)
+        reps = np.zeros(na, dtype=np.int32)
+        A = np.asarray(n_alleles, dtype=np.int64)
+        npairs = int((A * (A - 1) // 2).sum())
+        tr = {"dl": np.zeros(npairs + 1), "dk": np.zeros(npairs + 1), "kvec": np.zeros((na + 1, 65)), "vnorm": np.zeros(na + 1),
+              "height_l": np.zeros(na + 1), "height_k": np.zeros(na + 1)}
+        t = otg_genotype_trace(*(tr[n].ctypes.data for n, _ in otg_genotype_trace._fields_))
+        rc = self._L.otg_genotype_cluster_trace_batch(self._h, C.byref(params), abi.ptr(arena), C.c_uint64(arena.size), abi.ptr(seq_off),
+                                                      abi.ptr(seq_len), abi.ptr(first_allele), abi.ptr(n_alleles), C.c_uint32(nreg),
+                                                      abi.ptr(gt), abi.ptr(gl), abi.ptr(gk), abi.ptr(hsd), abi.ptr(ngt), abi.ptr(reps), C.byref(t))
+        self._check(rc, "otg_genotype_cluster_trace_batch")
+        tr = {"dl": tr["dl"][:npairs], "dk": tr["dk"][:npairs], "kvec": tr["kvec"][:na], "vnorm": tr["vnorm"][:na],
+              "height_l": tr["height_l"][:na], "height_k": tr["height_k"][:na]}
+        return (gt, gl, gk, hsd, ngt, reps), tr
 
     def last_kernel_ms(self):
         """HIP-event time of the kernels of the latest genotype_cluster_batch (otg_last_kernel_ms)."""

@@ -8,9 +8,11 @@
 // One 256-thread workgroup per region.  FP64 throughout, compiled with -ffp-contract=off; every sum keeps
 // the reference's order (one thread per KDE grid point looping over the distances in index order;
 // normalisation and extremum scan sequential).  exp() is glibc's algorithm restated (table + degree-5
-// polynomial) in the variant — FMA or not — that the host libm uses, so densities are bit-identical to the
-// reference running on this host.  The integer-valued outputs (labels, ic, fc) are decided by
-// the same comparisons on the same bits.
+// polynomial) in the variant — FMA or not — that equals the host libm on the probe set of otg_create, so the
+// densities equal the reference's on this host bit for bit as long as that probe reports no mismatch
+// (otg_exp_probe_mismatches).  The integer-valued outputs (labels, ic, fc) are decided by the same
+// comparisons on the same bits.  The TRACE instantiations (otg_cluster_trace_batch) write the intermediates out
+// for the tests; the product instantiations carry none of that code.
 #include "otg_common.hpp"
 #include <cmath>
 #include <type_traits>
@@ -55,8 +57,12 @@ __device__ __forceinline__ uint64_t d2u(double x) { return (uint64_t)__double_as
 __device__ __forceinline__ double u2d(uint64_t u) { return __longlong_as_double((long long)u); }
 
 // glibc 2.28+ exp(), N = 128 (sysdeps/ieee754/dbl-64/e_exp.c), restated.  FMA=true mirrors the x86-64
-// ifunc-selected FMA build (gcc contracts r, tmp and the final scale+scale*tmp; the subnormal path is not
-// contracted) — verified bit-for-bit against libm on 4e7 arguments on the build host.
+// ifunc-selected FMA build (gcc contracts kd = InvLn2N*x + Shift, r, tmp and the final scale+scale*tmp; the
+// subnormal path is not contracted).  What is checked, and where: the host restatement of each variant equals
+// libm's matching build on the argument set of tests/exp_args.py (specials, thresholds, every table step and
+// half-way point with neighbours, a KDE stream, large positive arguments) on the machine the tests run on, and
+// this function equals the host restatement on the same set on the device (tests/test_exp_host.py,
+// tests/test_gpu_exp.py).
 template <bool FMA>
 __device__ double otg_exp(double x)
 {
@@ -73,8 +79,9 @@ __device__ double otg_exp(double x)
     }
     abstop = 0;
   }
-  const double z = InvLn2N * x;
-  double kd = z + Shift;
+  double kd;
+  if (FMA) kd = fma(InvLn2N, x, Shift);
+  else kd = InvLn2N * x + Shift;
   const uint64_t ki = d2u(kd);
   kd -= Shift;
   double r;
@@ -108,6 +115,17 @@ __device__ double otg_exp(double x)
   const double scale = u2d(sbits);
   return FMA ? fma(scale, tmp, scale) : scale + scale * tmp;
 }
+
+// otg_exp on its own, for otg_exp_device: out-of-place would need a second buffer, so in place
+template <bool FMA>
+__global__ __launch_bounds__(256) void exp_kernel(double* __restrict__ x, uint64_t n)
+{
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) x[i] = otg_exp<FMA>(x[i]);
+}
+
+// the last kernel argument: the trace arrays in the TRACE instantiations, nothing in the product ones
+struct NoTrace {};
+template <bool TRACE> using trace_arg_t = std::conditional_t<TRACE, otg_cluster_trace, NoTrace>;
 
 __device__ __forceinline__ size_t didx(int N, int r, int c) { return (size_t)((((long long)(2 * N - 3 - r)) * r) >> 1) + c - 1; } // r < c
 __device__ __forceinline__ double dget(const double* D, int N, int i, int j) { return i < j ? D[didx(N, i, j)] : D[didx(N, j, i)]; }
@@ -425,14 +443,14 @@ __device__ void hclust_to_merge(int n, double* D, S& L, int tid)
 // WIDE = false: regions of at most n_split (<= NMAX) valid reads, scratch in LDS; WIDE = true: the regions of `wide_idx` above n_split,
 // per-read scratch in this workgroup's slab of `slab_stride` bytes (capacity `cap` reads).  Each instantiation leaves the other's regions
 // untouched.
-template <bool FMA, bool WIDE>
+template <bool FMA, bool WIDE, bool TRACE>
 __global__ __launch_bounds__(256) void cluster_kernel(
     ClusterArgs A, const double* __restrict__ dist, const uint64_t* __restrict__ dist_off,
     const uint32_t* __restrict__ read_len, const uint64_t* __restrict__ len_off, const uint32_t* __restrict__ n_valid,
     uint32_t n_regions, double* __restrict__ gwork, int n_split, const uint32_t* __restrict__ wide_idx, uint32_t n_wide,
     char* __restrict__ slab, size_t slab_stride, int cap,
     int32_t* __restrict__ labels_out, int32_t* __restrict__ ic_out, int32_t* __restrict__ fc_out,
-    double* __restrict__ bounds_out, int32_t* __restrict__ err_out)
+    double* __restrict__ bounds_out, int32_t* __restrict__ err_out, trace_arg_t<TRACE> T)
 {
   __shared__ LdsT<WIDE> L;
   const int tid = threadIdx.x;
@@ -458,6 +476,9 @@ __global__ __launch_bounds__(256) void cluster_kernel(
     }
     __syncthreads();
     // ---- trivial cases (src/otterclust.cpp:121-156)
+    if constexpr (TRACE) {      // state: evaluated, n_grid, n_max, n_min, do_hclust, err, cut_k, recut
+      if (tid == 0) { T.state[8 * (size_t)r] = !(n <= 2 || A.max_alleles == 1); T.state[8 * (size_t)r + 1] = A.n_grid; }
+    }
     if (n <= 2 || A.max_alleles == 1) {
       if (tid == 0) {
         int ic = 0, fc = 0;
@@ -493,11 +514,15 @@ __global__ __launch_bounds__(256) void cluster_kernel(
         total += inv_h * kk;
       }
       L.dens[p] = total / (double)npairs;
+      if constexpr (TRACE) T.dens_raw[(size_t)r * OTG_TRACE_GRID + p] = L.dens[p];
     }
     __syncthreads();
     if (tid == 0) { double t = 0.0; for (int p = 0; p < A.n_grid; ++p) t += L.dens[p]; L.total = t; }   // :29-30
     __syncthreads();
-    for (int p = tid; p < A.n_grid; p += blockDim.x) L.dens[p] = L.dens[p] / L.total;                     // :31-34
+    for (int p = tid; p < A.n_grid; p += blockDim.x) {                                                   // :31-34
+      L.dens[p] = L.dens[p] / L.total;
+      if constexpr (TRACE) T.dens[(size_t)r * OTG_TRACE_GRID + p] = L.dens[p];
+    }
     __syncthreads();
     // ---- KDE::maximas (src/ankde.cpp:25-62): windowed sums in parallel, extremum scan sequential
     for (int i = tid; i < A.n_grid; i += blockDim.x) {
@@ -506,6 +531,7 @@ __global__ __launch_bounds__(256) void cluster_kernel(
       for (int j = 1; j < A.radius && (i - j) >= 0; ++j) sum += L.dens[i - j];
       for (int j = 1; j < A.radius && (i + j) < A.n_grid; ++j) sum += L.dens[i + j];
       L.sums[i] = sum;
+      if constexpr (TRACE) T.sums[(size_t)r * OTG_TRACE_GRID + i] = sum;
     }
     __syncthreads();
     if (tid == 0) {
@@ -562,6 +588,15 @@ __global__ __launch_bounds__(256) void cluster_kernel(
         if (L.b1 - L.b0 <= A.max_error) L.do_hclust = 0;   // :172-176
         else { L.do_hclust = 1; L.dist_final = (L.b1 == L.bandwidth) ? L.b1 : L.bc + 0.0025; }   // :184
       }
+      if constexpr (TRACE) {
+        const size_t e0 = (size_t)r * OTG_TRACE_EXT;
+        for (int i = 0; i < nmx; ++i) { T.max_i[e0 + i] = L.maxi[i]; T.max_v[e0 + i] = L.maxv[i]; }
+        for (int i = 0; i < nmn; ++i) { T.min_i[e0 + i] = L.mini[i]; T.min_v[e0 + i] = L.minv[i]; }
+        int32_t* st = T.state + 8 * (size_t)r;
+        st[2] = nmx; st[3] = nmn; st[4] = L.do_hclust; st[5] = L.err;
+        T.scalars[2 * (size_t)r] = L.bandwidth;
+        if (L.do_hclust) T.scalars[2 * (size_t)r + 1] = L.dist_final;
+      }
     }
     __syncthreads();
     if (L.err || !L.do_hclust) {
@@ -587,6 +622,14 @@ __global__ __launch_bounds__(256) void cluster_kernel(
     __syncthreads();
     if (tid < 64) cutree_wave(n, L.merge, L.cut_k, L.labels, L.ct_up, L.ct_own, L.ct_first, L.ct_lab, tid);
     __syncthreads();
+    if constexpr (TRACE) {      // merge matrix, heights, the cut and its labels before the coverage repair below rewrites them
+      const size_t l0 = (size_t)len_off[r];
+      for (int i = tid; i < 2 * (n - 1); i += blockDim.x) T.merge[2 * l0 + i] = L.merge[i];
+      for (int i = tid; i < n - 1; i += blockDim.x) T.height[l0 + i] = L.height[i];
+      for (int i = tid; i < n; i += blockDim.x) T.labels_first[l0 + i] = L.labels[i];
+      if (tid == 0) T.state[8 * (size_t)r + 6] = L.cut_k;
+      __syncthreads();
+    }
     if (tid == 0) {
       int total_alleles = 0;
       for (int i = 0; i < n; ++i) if (L.labels[i] > total_alleles) total_alleles = L.labels[i];
@@ -636,6 +679,7 @@ __global__ __launch_bounds__(256) void cluster_kernel(
       ic_out[r] = L.ic; fc_out[r] = L.fc;
       if (bounds_out) { bounds_out[3 * r] = L.b0; bounds_out[3 * r + 1] = L.b1; bounds_out[3 * r + 2] = L.bc; }
       if (err_out) err_out[r] = 0;
+      if constexpr (TRACE) T.state[8 * (size_t)r + 7] = L.recut;
     }
   }
 }
@@ -732,8 +776,11 @@ __device__ void dendrogram_relabel(int n, S& L)
 }
 
 // WIDE = false: regions of at most a_split (<= NMAX) alleles; WIDE = true: the regions of `wide_idx` above a_split, scratch in this
-// workgroup's slab
-template <bool WIDE>
+// workgroup's slab.  TRACE (otg_genotype_cluster_trace_batch, for the tests): the heights of both clusterings go out per allele (region r's
+// A - 1 heights from its first allele on), and a cosine matrix that the product path clusters in place in g_dk is clustered on the working
+// copy instead, which is free by then, so that g_dl / g_dk / g_kvec / g_vnorm can be read back whole after the call.
+struct GtTrace { double* height_l; double* height_k; };
+template <bool WIDE, bool TRACE>
 __global__ __launch_bounds__(256) void genotype_kernel(
     double max_error_l, double max_error_c, const uint8_t* __restrict__ arena, const uint64_t* __restrict__ seq_off,
     const uint32_t* __restrict__ seq_len, const uint32_t* __restrict__ first_allele, const uint32_t* __restrict__ n_alleles,
@@ -741,7 +788,7 @@ __global__ __launch_bounds__(256) void genotype_kernel(
     double* __restrict__ g_work, double* __restrict__ g_kvec, double* __restrict__ g_vnorm,
     int a_split, const uint32_t* __restrict__ wide_idx, uint32_t n_wide, char* __restrict__ slab, size_t slab_stride, int cap,
     int32_t* __restrict__ gt, int32_t* __restrict__ gt_l, int32_t* __restrict__ gt_k, double* __restrict__ hsd,
-    int32_t* __restrict__ n_gt, int32_t* __restrict__ reps, int32_t* __restrict__ err_out)
+    int32_t* __restrict__ n_gt, int32_t* __restrict__ reps, int32_t* __restrict__ err_out, std::conditional_t<TRACE, GtTrace, NoTrace> T)
 {
   __shared__ GLdsT<WIDE> L;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -862,7 +909,7 @@ __global__ __launch_bounds__(256) void genotype_kernel(
     // ---- 4. the two clusterings, one after the other on one scratch: NN-chain on wave 0 (for regions of up to 102 alleles on the LDS working copy:
     // every nearest-neighbour scan and update at LDS latency), rank sort of the merges by all threads, union-find relabel by one thread, tree
     // cut by wave 0
-    auto cluster_one = [&](double* D, double cut, int* labels_out) {
+    auto cluster_one = [&](double* D, double cut, int* labels_out, double* height_out) {
       auto& S = L.u.hc;
       if (wv == 0) nn_chain_average(A, D, S, lane);
       __syncthreads();
@@ -883,11 +930,20 @@ __global__ __launch_bounds__(256) void genotype_kernel(
       if (wv == 0) cutree_wave(A, S.merge, S.cut_k, S.labels, S.ct_up, S.ct_own, S.ct_first, S.ct_lab, lane);
       __syncthreads();
       for (int a2 = tid; a2 < A; a2 += blockDim.x) labels_out[a2] = S.labels[a2];
+      if constexpr (TRACE) { for (int a2 = tid; a2 < A - 1; a2 += blockDim.x) height_out[a2] = S.height[a2]; }
       __syncthreads();
     };
-    cluster_one(in_lds ? &L.dmat[0] : wk, max_error_l, &L.lab_l[0]);
-    if (in_lds) { for (size_t q = tid; q < npairs; q += blockDim.x) L.dmat[q] = dk[q]; __syncthreads(); }
-    cluster_one(in_lds ? &L.dmat[0] : dk, max_error_c, &L.lab_k[0]);
+    if constexpr (TRACE) {
+      cluster_one(in_lds ? &L.dmat[0] : wk, max_error_l, &L.lab_l[0], T.height_l + f);
+      double* D2 = in_lds ? &L.dmat[0] : wk;
+      for (size_t q = tid; q < npairs; q += blockDim.x) D2[q] = dk[q];
+      __syncthreads();
+      cluster_one(D2, max_error_c, &L.lab_k[0], T.height_k + f);
+    } else {
+      cluster_one(in_lds ? &L.dmat[0] : wk, max_error_l, &L.lab_l[0], nullptr);
+      if (in_lds) { for (size_t q = tid; q < npairs; q += blockDim.x) L.dmat[q] = dk[q]; __syncthreads(); }
+      cluster_one(in_lds ? &L.dmat[0] : dk, max_error_c, &L.lab_k[0], nullptr);
+    }
     // ---- 5. genotypes: distinct (gt_l, gt_k) pairs numbered by first appearance (:500-516)
     const int* lab_l = &L.lab_l[0]; const int* lab_k = &L.lab_k[0];
     for (int a = tid; a < A; a += blockDim.x) {
@@ -978,7 +1034,7 @@ static size_t genotype_slab_size(int cap) { static GLdsT<true> probe; return pro
 int otg_launch_cluster(otg_ctx* ctx, const otg_params* P, const double* d_dist, const uint64_t* d_dist_off,
                        const uint32_t* d_read_len, const uint64_t* d_len_off, const uint32_t* d_n_valid,
                        uint32_t n_regions, uint32_t n_max, const uint32_t* h_wide, uint32_t n_wide, int32_t* d_labels, int32_t* d_ic,
-                       int32_t* d_fc, double* d_bounds, int32_t* d_err)
+                       int32_t* d_fc, double* d_bounds, int32_t* d_err, const otg_cluster_trace* d_trace, int exp_variant)
 {
   if (n_regions == 0) return OTG_OK;
   ClusterArgs A;
@@ -999,7 +1055,7 @@ int otg_launch_cluster(otg_ctx* ctx, const otg_params* P, const double* d_dist, 
   int radius = int(P->max_error / error_intervals);     // src/otterclust.cpp:160-161
   A.radius = radius < 1 ? 1 : radius;
   A.dinterval = error_intervals;
-  A.exp_fma = ctx->exp_variant;
+  A.exp_fma = exp_variant < 0 ? ctx->exp_variant : exp_variant;
   static double grid[GMAX];
   int ng = 0;
   for (volatile double x = 0.0; x <= 1.0; x += error_intervals) {     // src/otterclust.cpp:26
@@ -1015,12 +1071,28 @@ int otg_launch_cluster(otg_ctx* ctx, const otg_params* P, const double* d_dist, 
   WideRoute w;
   if (int rc = wide_route(ctx, SLOT_P25, n_regions, n_max, h_wide, n_wide, cluster_slab_size, w)) return rc;
   uint32_t grid_dim = n_regions < (uint32_t)ctx->n_cu * 8 ? n_regions : (uint32_t)ctx->n_cu * 8;
-  auto launch = [&](auto kernel, uint32_t grid, char* slab) {
+  auto launch = [&](auto kernel, uint32_t grid, char* slab, auto trace) {
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, ctx->stream, A, d_dist, d_dist_off, d_read_len, d_len_off,
-                       d_n_valid, n_regions, gwork, w.n_split, w.idx, w.n_wide, slab, w.stride, w.cap, d_labels, d_ic, d_fc, d_bounds, d_err);
+                       d_n_valid, n_regions, gwork, w.n_split, w.idx, w.n_wide, slab, w.stride, w.cap, d_labels, d_ic, d_fc, d_bounds, d_err, trace);
   };
-  if (w.n_split >= 0) { if (A.exp_fma) launch(cluster_kernel<true, false>, grid_dim, nullptr); else launch(cluster_kernel<false, false>, grid_dim, nullptr); }
-  if (w.grid) { if (A.exp_fma) launch(cluster_kernel<true, true>, w.grid, w.slab); else launch(cluster_kernel<false, true>, w.grid, w.slab); }
+  if (!d_trace) {
+    if (w.n_split >= 0) { if (A.exp_fma) launch(cluster_kernel<true, false, false>, grid_dim, nullptr, NoTrace{}); else launch(cluster_kernel<false, false, false>, grid_dim, nullptr, NoTrace{}); }
+    if (w.grid) { if (A.exp_fma) launch(cluster_kernel<true, true, false>, w.grid, w.slab, NoTrace{}); else launch(cluster_kernel<false, true, false>, w.grid, w.slab, NoTrace{}); }
+  } else {      // the same kernels with the trace stores compiled in (otg_cluster_trace_batch)
+    if (w.n_split >= 0) { if (A.exp_fma) launch(cluster_kernel<true, false, true>, grid_dim, nullptr, *d_trace); else launch(cluster_kernel<false, false, true>, grid_dim, nullptr, *d_trace); }
+    if (w.grid) { if (A.exp_fma) launch(cluster_kernel<true, true, true>, w.grid, w.slab, *d_trace); else launch(cluster_kernel<false, true, true>, w.grid, w.slab, *d_trace); }
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  return OTG_OK;
+}
+
+int otg_launch_exp(otg_ctx* ctx, double* d_x, uint64_t n, int variant)
+{
+  if (n == 0) return OTG_OK;
+  const uint64_t want = (n + 255) / 256;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(want, (uint64_t)ctx->n_cu * 16);
+  if (variant) hipLaunchKernelGGL(exp_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, d_x, n);
+  else hipLaunchKernelGGL(exp_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, d_x, n);
   HIP_TRY(ctx, hipGetLastError());
   return OTG_OK;
 }
@@ -1030,7 +1102,7 @@ int otg_launch_genotype(otg_ctx* ctx, const otg_params* P, const uint8_t* d_aren
                         const uint64_t* d_pair_off, uint64_t n_pairs_total, uint64_t n_alleles_total, uint32_t a_max,
                         const uint32_t* h_wide, uint32_t n_wide,
                         int32_t* d_gt, int32_t* d_gtl, int32_t* d_gtk, double* d_hsd, int32_t* d_ngt, int32_t* d_reps,
-                        int32_t* d_err)
+                        int32_t* d_err, double* d_height_l, double* d_height_k)
 {
   if (n_regions == 0) return OTG_OK;
   double* g_dl = (double*)otg_slot(ctx, SLOT_P20, (n_pairs_total + 1) * 8);
@@ -1042,13 +1114,19 @@ int otg_launch_genotype(otg_ctx* ctx, const otg_params* P, const uint8_t* d_aren
   WideRoute w;
   if (int rc = wide_route(ctx, SLOT_P26, n_regions, a_max, h_wide, n_wide, genotype_slab_size, w)) return rc;
   uint32_t grid_dim = n_regions < (uint32_t)ctx->n_cu * 8 ? n_regions : (uint32_t)ctx->n_cu * 8;
-  auto launch = [&](auto kernel, uint32_t grid, char* slab) {
+  auto launch = [&](auto kernel, uint32_t grid, char* slab, auto trace) {
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, ctx->stream, P->gt_max_error, P->gt_max_cosdis, d_arena, d_seq_off,
                        d_seq_len, d_first, d_n, n_regions, d_pair_off, g_dl, g_dk, g_wk, g_kv, g_vn, w.n_split, w.idx, w.n_wide, slab, w.stride, w.cap,
-                       d_gt, d_gtl, d_gtk, d_hsd, d_ngt, d_reps, d_err);
+                       d_gt, d_gtl, d_gtk, d_hsd, d_ngt, d_reps, d_err, trace);
   };
-  if (w.n_split >= 0) launch(genotype_kernel<false>, grid_dim, nullptr);
-  if (w.grid) launch(genotype_kernel<true>, w.grid, w.slab);
+  if (!d_height_l) {
+    if (w.n_split >= 0) launch(genotype_kernel<false, false>, grid_dim, nullptr, NoTrace{});
+    if (w.grid) launch(genotype_kernel<true, false>, w.grid, w.slab, NoTrace{});
+  } else {
+    const GtTrace T{d_height_l, d_height_k};
+    if (w.n_split >= 0) launch(genotype_kernel<false, true>, grid_dim, nullptr, T);
+    if (w.grid) launch(genotype_kernel<true, true>, w.grid, w.slab, T);
+  }
   HIP_TRY(ctx, hipGetLastError());
   return OTG_OK;
 }

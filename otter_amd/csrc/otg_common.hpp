@@ -22,6 +22,7 @@ struct otg_ctx {
   hipDeviceProp_t prop;
   std::string err;
   int exp_variant = 1;
+  long long exp_probe_mismatches = 0;             // of the chosen variant against the host libm over the probe set of otg_create (otg_api.hip)
   int n_cu = 256;
   uint32_t max_seq_len = 65536;   // longest sequence of the current batch (sizes the tier-3 edit workspace)
   // grow-only device scratch, keyed by purpose
@@ -272,7 +273,9 @@ int otg_launch_affine_adaptive_todo(otg_ctx* ctx, const uint8_t* d_arena, const 
 int otg_launch_cluster(otg_ctx* ctx, const otg_params* P, const double* d_dist, const uint64_t* d_dist_off,
                        const uint32_t* d_read_len, const uint64_t* d_len_off, const uint32_t* d_n_valid,
                        uint32_t n_regions, uint32_t n_max, const uint32_t* h_wide, uint32_t n_wide, int32_t* d_labels, int32_t* d_ic,
-                       int32_t* d_fc, double* d_bounds, int32_t* d_err);
+                       int32_t* d_fc, double* d_bounds, int32_t* d_err, const otg_cluster_trace* d_trace = nullptr, int exp_variant = -1);
+// out[i] = otg_exp<variant>(d_x[i]) in place: the function cluster_kernel calls, on its own (otg_exp_device)
+int otg_launch_exp(otg_ctx* ctx, double* d_x, uint64_t n, int variant);
 
 // poa.hip
 int otg_launch_poa(otg_ctx* ctx, const uint8_t* d_seq_arena, const uint8_t* d_cig_arena,
@@ -283,7 +286,7 @@ int otg_launch_poa(otg_ctx* ctx, const uint8_t* d_seq_arena, const uint8_t* d_ci
 // otg_api.hip: anallele_cluster on device-resident inputs (memset of the outputs, ev0, the kernels below, ev1); see its definition
 int otg_genotype_resident(otg_ctx* ctx, const otg_params* params, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len,
                           const uint32_t* d_first, const uint32_t* d_n, const uint32_t* h_n_alleles, uint32_t n_regions, const uint64_t* d_poff,
-                          uint64_t n_pairs, uint64_t na, int32_t* d_gt, double* d_hsd, int32_t* d_ngt);
+                          uint64_t n_pairs, uint64_t na, int32_t* d_gt, double* d_hsd, int32_t* d_ngt, double* d_height = nullptr);
 
 // kmer_usage.hip: the workspace refusal of otg_kmer_usage_batch (OTG_ERR_CAPACITY, nothing allocated) and its launch part on device-resident
 // rows; see the definitions
@@ -297,4 +300,4 @@ int otg_launch_genotype(otg_ctx* ctx, const otg_params* P, const uint8_t* d_aren
                         const uint64_t* d_pair_off, uint64_t n_pairs_total, uint64_t n_alleles_total, uint32_t a_max,
                         const uint32_t* h_wide, uint32_t n_wide,
                         int32_t* d_gt, int32_t* d_gtl, int32_t* d_gtk, double* d_hsd, int32_t* d_ngt, int32_t* d_reps,
-                        int32_t* d_err);
+                        int32_t* d_err, double* d_height_l = nullptr, double* d_height_k = nullptr);

@@ -73,6 +73,27 @@ def test_affine_routing_entry():
     assert lib.otg_affine_last_routing(None, C.c_uint32(4), None, None, None, None, None) == abi.OTG_ERR_ARG
 
 
+def test_trace_entries():
+    """The test-only entries of the clustering kernels: exported, their constants and structs mirrored in _lib.py, and a call without a
+    context or without a trace is an error code with a message, not a crash."""
+    from otter_amd import _lib
+    txt = open(HEADER).read()
+    defs = dict(re.findall(r"#define\s+(OTG_TRACE_[A-Z_]+)\s+(\d+)", txt))
+    assert {k: int(v) for k, v in defs.items()} == {"OTG_TRACE_GRID": _lib.TRACE_GRID, "OTG_TRACE_EXT": _lib.TRACE_EXT}
+    for struct, ctype in (("otg_cluster_trace", _lib.otg_cluster_trace), ("otg_genotype_trace", _lib.otg_genotype_trace)):
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), txt, flags=re.S).group(1)
+        assert re.findall(r"\*\s*(\w+)", body) == [n for n, _ in ctype._fields_]
+    for name in ("otg_exp_host", "otg_exp_device", "otg_exp_probe", "otg_exp_probe_mismatches", "otg_cluster_trace_batch", "otg_genotype_cluster_trace_batch"):
+        assert name in otter_amd.EXPORTS
+    lib = otter_amd.load()
+    x = np.zeros(1)
+    assert lib.otg_exp_device(None, abi.ptr(x), C.c_uint64(1), 1, abi.ptr(x)) == abi.OTG_ERR_NO_DEVICE
+    assert lib.otg_cluster_trace_batch(None, None, None, None, None, None, None, C.c_uint32(1), None, None, None, None, -1, None) == abi.OTG_ERR_ARG
+    t = _lib.otg_cluster_trace()
+    assert lib.otg_cluster_trace_batch(None, None, None, None, None, None, None, C.c_uint32(1), None, None, None, None, -1, C.byref(t)) == abi.OTG_ERR_NO_DEVICE
+    assert lib.otg_genotype_cluster_trace_batch(None, None, None, C.c_uint64(0), None, None, None, None, C.c_uint32(1), None, None, None, None, None, None, None) == abi.OTG_ERR_ARG
+
+
 def test_no_silent_cpu_fallback():
     if otter_amd.device_count() > 0:
         pytest.skip("a GPU is present")

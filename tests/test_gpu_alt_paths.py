@@ -36,7 +36,8 @@ CASES = [
     ("OTG_POA_NO_LDS", ["tests/test_gpu_poa.py"]),                                       # second-generation POA on every graph (the op-string fuzz and the insertion stretches in global memory)
     ("OTG_POA_PIECE_MB=1", ["tests/test_gpu_poa.py", "tests/test_gpu_pipeline.py::test_ont_kb"]),         # graph images in many small pieces that reuse the work arrays
     ("OTG_NO_REASSIGN_REV", ["tests/test_gpu_pipeline.py::test_haps_mode", "tests/test_gpu_pipeline.py::test_ont_kb"]),
-    ("OTG_CLUSTER_WIDE=1", ["tests/test_gpu_cluster.py", "tests/test_gpu_genotype.py", "tests/test_gpu_pipeline.py::test_edge_regions"]),   # every region on the wide clustering kernels (HBM scratch)
+    ("OTG_CLUSTER_WIDE=1", ["tests/test_gpu_cluster.py", "tests/test_gpu_genotype.py", "tests/test_gpu_pipeline.py::test_edge_regions",
+                           "tests/test_gpu_cluster_trace.py", "tests/test_gpu_genotype_trace.py"]),   # every region on the wide clustering kernels (HBM scratch), their intermediates included
     ("OTG_REG_SHAPE=11210", AFFINE_CORE + [ROUTING]),                                      # the other instantiation of every register window: <2,4>, <1,12> at 4 waves, <1,16>, <8,4>
     ("OTG_REG_SHAPE=2200", AFFINE_CORE + [ROUTING]),                                      # <2,6> for the 1536 window, <1,16> without spills for the 2048 one
     ("OTG_AFFINE_CONCURRENT=1", AFFINE_CORE + [ROUTING]),                                 # register tiers side by side on three streams whatever the batch size
