@@ -592,6 +592,10 @@ int otg_assemble_collect(otg_ctx* ctx,
                          uint8_t* seq_out, uint64_t seq_capacity,
                          int32_t* labels_out);
 int otg_assemble_stats(otg_ctx* ctx, otg_run_stats* out);
+/* The distance matrices fill_dist_matrix left on the device in the last run (src/analignments.cpp:103-124), for tests and diagnosis: region r's
+ * condensed matrix over its V valid reads (row-major upper triangle, V (V - 1) / 2 values) starts at the sum of N (N - 1) / 2 over the regions
+ * before it, N = a region's submitted read count (0 for a region above max_cov).  n_slots = that sum over all regions.                  */
+int otg_assemble_collect_dist(otg_ctx* ctx, double* dist_out, uint64_t n_slots);
 
 /* ---------------------------------------------------------------------------------------------
  * The dispatcher: `otter assemble` from files to record text in one call — the role of assemble() /

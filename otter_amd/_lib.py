@@ -13,7 +13,7 @@ EXPORTS = [
     "otg_params_default", "otg_create", "otg_destroy", "otg_trim", "otg_last_error", "otg_device_count", "otg_exp_variant", "otg_set_heuristic",
     "otg_edit_distance_batch", "otg_affine_align_batch", "otg_affine_last_routing", "otg_cluster_batch", "otg_poa_consensus_batch",
     "otg_genotype_cluster_batch", "otg_last_kernel_ms", "otg_assemble_submit", "otg_assemble_run", "otg_assemble_result_sizes",
-    "otg_assemble_collect", "otg_assemble_device_results", "otg_assemble_stats", "otg_assemble_realign", "otg_assemble_collect_reads",
+    "otg_assemble_collect", "otg_assemble_device_results", "otg_assemble_stats", "otg_assemble_realign", "otg_assemble_collect_reads", "otg_assemble_collect_dist",
     "otg_emit_alleles", "otg_emit_sam_header",
     "otg_bam_open", "otg_bam_close", "otg_bam_n_targets", "otg_bam_target", "otg_ingest_regions",
     "otg_ingest_regions_named", "otg_emit_reads", "otg_parse_bed_file", "otg_fasta_open", "otg_fasta_close", "otg_fasta_n_seqs",
@@ -460,6 +460,13 @@ class Context:
         return {"regions": wrap(pr.value, self._n_regions * abi.region_result_dt.itemsize),
                 "alleles": wrap(pa.value, na.value * abi.allele_dt.itemsize),
                 "seqs": wrap(ps.value, sb.value), "n_alleles": int(na.value), "n_regions": int(self._n_regions)}
+
+    def assemble_collect_dist(self, n_slots):
+        """The pair-distance matrices of the last run (otg_assemble_collect_dist): n_slots doubles, region r's condensed matrix at the sum of
+        N (N - 1) / 2 over the regions before it."""
+        out = np.zeros(max(1, int(n_slots)))
+        self._check(self._L.otg_assemble_collect_dist(self._h, abi.ptr(out), C.c_uint64(int(n_slots))), "otg_assemble_collect_dist")
+        return out[:int(n_slots)]
 
     def assemble_stats(self):
         st = np.zeros(1, dtype=abi.run_stats_dt)

@@ -17,13 +17,18 @@
 // narrow bands (within-allele pairs) run four to a wave and only wide ones need the whole wave.
 // The computed score is exact iff it is <= K; otherwise the task is appended to the overflow list and handled
 // by the next tier (larger group / more blocks per lane, finally the wavefront kernel).
-// Pattern match masks (A, C, G, T + at most one further byte value occurring in the pattern, e.g. N) are built
-// once per pair into an L2-resident scratch and fetched when a lane moves to its next superblock; richer
-// alphabets, text-side free ends and patterns > 16384 bytes go to the wavefront kernel.
+// Pattern match masks (A, C, G, T + at most one further byte value occurring in the pattern, e.g. N) are derived from two bit-planes per
+// 64-row block (myers_masks.hpp) when a lane moves to its next superblock.  The pipeline's patterns are whole reads, each compared with
+// every other read of its region: their planes come from a table built once per run (read_masks_kernel; a task's first table block in the
+// side array `pblk`).  Every other pair — the operator-level calls, reads with a byte outside A C G T, the pipeline's reversed copies —
+// has them built by its wave into an L2-resident scratch before the sweep: per block one coalesced 64-byte load and one compare per symbol.
+// Richer alphabets, text-side free ends and patterns > 16384 bytes go to the wavefront kernel.
 // The column step of a block (myers_step.hpp) works on 32-bit halves with three-input bit operations: what a vector instruction costs on
 // gfx950 depends on its class, and the tiers are bound by vector issue.
 #include "otg_common.hpp"
 #include "myers_step.hpp"
+#include "myers_masks.hpp"
+#include <algorithm>
 #include <cstdlib>
 
 namespace {
@@ -58,13 +63,15 @@ __device__ u64 wfa_cells(int s, int m, int n, int pbf, int tbf, int gl)
   return w;
 }
 
+// (<1,8> sits at the edge of six waves per SIMD, 80 vector registers; the bound keeps it there: no spill, private segment 0)
 template <int BPL, int GL, int WPB>
-__global__ __launch_bounds__(WPB * 64) void myers_edit_kernel(
+__global__ __launch_bounds__(WPB * 64, (BPL == 1 && GL == 8) ? 6 : 1) void myers_edit_kernel(
     const uint8_t* __restrict__ arena, const otg_align_task* __restrict__ tasks,
     const uint32_t* __restrict__ todo, const uint32_t* __restrict__ n_todo_ptr, uint32_t n_todo_imm,
     int32_t* __restrict__ scores, uint64_t* __restrict__ cells,
     uint32_t* __restrict__ ticket, uint32_t* __restrict__ n_overflow, uint32_t* __restrict__ overflow_list,
-    u64* __restrict__ peq_ws, int maxblk)
+    otg_myers::MaskBlock* __restrict__ peq_ws, int maxblk,
+    const uint32_t* __restrict__ pblk, const otg_myers::PlaneBlock* __restrict__ tab)
 {
   constexpr int G = 64 / GL;            // pairs per wave
   constexpr int SB = 64 * BPL;
@@ -82,7 +89,8 @@ __global__ __launch_bounds__(WPB * 64) void myers_edit_kernel(
   const int wib = threadIdx.x >> 6;
   const int gl = lane & (GL - 1);       // lane within its group
   const int grp = lane / GL;
-  u64* peq = peq_ws + ((size_t)(blockIdx.x * WPB + wib) * G + grp) * (size_t)maxblk * 5;
+  otg_myers::MaskBlock* const peq_wave = peq_ws + (size_t)(blockIdx.x * WPB + wib) * G * (size_t)maxblk;
+  const otg_myers::MaskBlock* const peq = peq_wave + (size_t)grp * (size_t)maxblk;
   const uint32_t n_todo = n_todo_ptr ? *n_todo_ptr : n_todo_imm;
   using lds_u64 = __attribute__((address_space(3))) u64;
   using lds_u8 = __attribute__((address_space(3))) uint8_t;
@@ -113,7 +121,8 @@ __global__ __launch_bounds__(WPB * 64) void myers_edit_kernel(
     int m = (int)tsk.pattern_len, n = (int)tsk.text_len;
     int pbf = ef ? tsk.pattern_begin_free : 0, pef = ef ? tsk.pattern_end_free : 0;
     bool unsupported = ef && (tsk.text_begin_free != 0 || tsk.text_end_free != 0);
-    if (!ef && m < n) { const uint8_t* q = P; P = T; T = q; const int x = m; m = n; n = x; }   // edit distance is symmetric
+    const bool swapped = !ef && m < n;
+    if (swapped) { const uint8_t* q = P; P = T; T = q; const int x = m; m = n; n = x; }   // edit distance is symmetric
     if (m < n) unsupported = true;
     if (pbf > m) pbf = m;
     if (pef > m) pef = m;
@@ -130,45 +139,43 @@ __global__ __launch_bounds__(WPB * 64) void myers_edit_kernel(
     if (nblk > maxblk || K < d - pbf - pef || K < 1 || KL + KU > R || n < 1 || pbf > d || pef > d) unsupported = true;
     if (!has_task) unsupported = true;
 
-    // ---- pattern match masks per 64-row block: A, C, G, T, X (one further byte value), built by the group
+    // ---- pattern planes per 64-row block: from the table when the task names its blocks there, otherwise built here by the whole wave,
+    // one pair after the other: lane r of the wave holds row r of the block, a compare against a symbol is the block's mask of that symbol
+    const uint32_t tblk = (pblk && tab && !unsupported && !swapped) ? pblk[ti] : otg_myers::NO_MASKS;
+    const bool use_tab = tblk != otg_myers::NO_MASKS;
     int other = -1;
-    bool bad_alpha = false;
-    if (!unsupported) {
-      for (int b = gl; b < nblk; b += GL) {
-        u64 ea = 0, ec = 0, eg = 0, et = 0;
-        const int base = b << 6;
-        for (int r = 0; r < 64; ++r) {
-          const int i = base + r;
-          if (i >= m) break;
-          const uint8_t ch = P[i];
-          const u64 bit = 1ull << r;
-          if (ch == 'A') ea |= bit; else if (ch == 'C') ec |= bit; else if (ch == 'G') eg |= bit; else if (ch == 'T') et |= bit;
-          else { if (other < 0) other = ch; else if (other != ch) bad_alpha = true; }
-        }
-        peq[b * 5 + 0] = ea; peq[b * 5 + 1] = ec; peq[b * 5 + 2] = eg; peq[b * 5 + 3] = et;
-      }
-    }
-    // agree on the single extra symbol across the lanes of the group
     {
-      const u64 gmask = (GL == 64) ? ~0ull : (((1ull << GL) - 1ull) << (grp * GL));
-      const u64 has = __ballot(other >= 0) & gmask;
-      int x = -1;
-      const int src = has ? (int)__builtin_ctzll(has) : lane;
-      const int xo = __shfl(other, src);
-      if (has) x = xo;
-      const u64 bad = __ballot(bad_alpha || (other >= 0 && other != x)) & gmask;
-      if (bad) unsupported = true;
-      other = x;
-      if (!unsupported) {
-        for (int b = gl; b < nblk; b += GL) {
-          u64 ex = 0;
-          if (x >= 0) {
-            const int base = b << 6;
-            for (int r = 0; r < 64; ++r) { const int i = base + r; if (i >= m) break; if (P[i] == (uint8_t)x) ex |= 1ull << r; }
+      const bool build = !unsupported && !use_tab;
+      bool bad_alpha = false;
+      if (__ballot(build)) {
+        const u64 p_off = (u64)(P - arena);
+        for (int g = 0; g < G; ++g) {
+          const int src = g * GL;
+          if (!__builtin_amdgcn_readlane((int)build, src)) continue;
+          const u64 og = (u64)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)p_off, src) | (u64)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(p_off >> 32), src) << 32;
+          const int mg = __builtin_amdgcn_readlane(m, src);
+          const int nb = (mg + 63) >> 6;
+          otg_myers::MaskBlock* const pq = peq_wave + (size_t)g * (size_t)maxblk;
+          int oth = -1;
+          bool bad = false;
+          for (int b4 = 0; b4 < nb; b4 += 4) {
+            uint32_t ch[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { const int i = ((b4 + k) << 6) + lane; ch[k] = i < mg ? (uint32_t)arena[og + (u64)i] : 0u; }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+              if (b4 + k >= nb) break;
+              const u64 rows = otg_myers::block_rows(mg, b4 + k);
+              const uint32_t c = ch[k];
+              const otg_myers::MaskBlock mk = otg_myers::block_masks([&](uint8_t v) { return __ballot(c == (uint32_t)v) & rows; },
+                                                                     [&](int r) { return (uint32_t)__builtin_amdgcn_readlane((int)c, r); }, rows, &oth, &bad);
+              if (lane == 0) pq[b4 + k] = mk;
+            }
           }
-          peq[b * 5 + 4] = ex;
+          if (grp == g) { other = oth; bad_alpha = bad; }
         }
       }
+      if (bad_alpha) unsupported = true;       // a second byte value outside A C G T: the wavefront kernel's
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     if (other != lut_other) {            // group-uniform
@@ -267,9 +274,15 @@ __global__ __launch_bounds__(WPB * 64) void myers_edit_kernel(
 #pragma unroll
           for (int q = 0; q < BPL; ++q) {
             const int b = B * BPL + q;
-            const bool have = b < nblk;
+            otg_myers::MaskBlock mk = {0ull, 0ull, 0ull, 0ull};
+            if (b < nblk) {
+              if (tblk != otg_myers::NO_MASKS) { const otg_myers::PlaneBlock pb = tab[tblk + (uint32_t)b]; mk.b0 = pb.b0; mk.b1 = pb.b1; mk.ok = otg_myers::block_rows(m, b); }
+              else mk = peq[b];
+            }
+            uint64_t rows5[5];                            // A C T G X, the order of the code
+            otg_myers::rows_from_planes(mk.b0, mk.b1, mk.ok, mk.ex, rows5);
 #pragma unroll
-            for (int y = 0; y < 5; ++y) EQ[(y * BPL + q) * NT] = have ? peq[b * 5 + (y == 2 ? 3 : y == 3 ? 2 : y)] : 0ull;   // rows A C T G X <- scratch A C G T X
+            for (int y = 0; y < 5; ++y) EQ[(y * BPL + q) * NT] = rows5[y];
             MvL[q] = MvH[q] = 0;
             u64 pv0 = ~0ull;
             if (exact_init) {
@@ -317,10 +330,48 @@ __global__ __launch_bounds__(WPB * 64) void myers_edit_kernel(
   }
 }
 
+// The per-read table: one wave per read, lane r holds row r of a block.  Block b of read i (64 bases from its CURRENT seq_off: realignment has
+// moved it by now) lands at tab[first_blk[i] + b]; first_blk was laid out from the submitted lengths, which realignment only shortens.  A read
+// with a byte outside A C G T, and a read outside every region (its range was never checked against the arena), gets NO_MASKS in read_blk:
+// its pairs build their masks themselves.  Blocks are kept by lane (b & 63) and stored 64 at a time.
+__global__ __launch_bounds__(256) void read_masks_kernel(const uint8_t* __restrict__ arena, const otg_read* __restrict__ reads, const uint32_t* __restrict__ read_region,
+                                                         uint32_t n_reads, const uint32_t* __restrict__ first_blk, otg_myers::PlaneBlock* __restrict__ tab,
+                                                         uint32_t* __restrict__ read_blk)
+{
+  const int lane = threadIdx.x & 63;
+  const uint32_t nw = gridDim.x * (blockDim.x >> 6);
+  for (uint32_t i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); i < n_reads; i += nw) {
+    if (read_region[i] == 0xffffffffu) { if (lane == 0) read_blk[i] = otg_myers::NO_MASKS; continue; }
+    const uint8_t* const S = arena + reads[i].seq_off;
+    const int m = (int)reads[i].seq_len;
+    const int nb = (m + 63) >> 6;
+    otg_myers::PlaneBlock* const out = tab + first_blk[i];
+    u64 flagged = 0, k0 = 0, k1 = 0;
+    for (int b4 = 0; b4 < nb; b4 += 4) {
+      uint32_t ch[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { const int j = ((b4 + k) << 6) + lane; ch[k] = j < m ? (uint32_t)S[j] : 0u; }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int b = b4 + k;
+        if (b >= nb) break;
+        const u64 rows = otg_myers::block_rows(m, b);
+        const uint32_t c = ch[k];
+        uint64_t rest;
+        const otg_myers::MaskBlock mk = otg_myers::block_planes([&](uint8_t v) { return __ballot(c == (uint32_t)v) & rows; }, rows, &rest);
+        flagged |= rest;
+        if (lane == (b & 63)) { k0 = mk.b0; k1 = mk.b1; }
+        if ((b & 63) == 63 || b == nb - 1) { if (lane <= (b & 63)) out[(b & ~63) + lane] = otg_myers::PlaneBlock{k0, k1}; }
+      }
+    }
+    if (lane == 0) read_blk[i] = flagged ? otg_myers::NO_MASKS : first_blk[i];
+  }
+}
+
 template <int BPL, int GL>
 int launch_one(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* d_tasks, const uint32_t* d_todo,
                const uint32_t* d_n_todo, uint32_t n_tasks, int32_t* d_scores, uint64_t* d_cells,
-               uint32_t* ticket, uint32_t* n_overflow, uint32_t* overflow_list)
+               uint32_t* ticket, uint32_t* n_overflow, uint32_t* overflow_list, const uint32_t* d_pblk, const otg_myers::PlaneBlock* d_masks)
 {
   constexpr int WPB = 4, G = 64 / GL;
   int maxblk = (int)((ctx->max_seq_len + 63) / 64) + 1;
@@ -337,10 +388,10 @@ int launch_one(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* d_tas
   const uint32_t grid_res = (uint32_t)ctx->n_cu * (uint32_t)per_cu;
   uint32_t grid = grid_res < want ? grid_res : want;
   if (grid == 0) return OTG_OK;
-  u64* ws = (u64*)otg_slot(ctx, SLOT_AUX8, (size_t)grid_max * WPB * 8 * (size_t)MAXBLK * 5 * sizeof(u64));   // up to 8 pairs per wave
+  otg_myers::MaskBlock* ws = (otg_myers::MaskBlock*)otg_slot(ctx, SLOT_AUX8, (size_t)grid_max * WPB * 8 * (size_t)MAXBLK * sizeof(otg_myers::MaskBlock));   // up to 8 pairs per wave
   if (!ws) return OTG_ERR_HIP;
   hipLaunchKernelGGL((myers_edit_kernel<BPL, GL, WPB>), dim3(grid), dim3(WPB * 64), 0, ctx->stream, d_arena, d_tasks, d_todo, d_n_todo, n_tasks,
-                     d_scores, d_cells, ticket, n_overflow, overflow_list, ws, maxblk);
+                     d_scores, d_cells, ticket, n_overflow, overflow_list, ws, maxblk, d_pblk, d_masks);
   return OTG_OK;
 }
 
@@ -354,20 +405,32 @@ int launch_one(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* d_tas
 //       0.7 x the cost of <2,32>: a pair pays for the band of its tier, not for its own); last = whole wave x 4 blocks per lane.
 int otg_launch_myers(otg_ctx* ctx, int tier, const uint8_t* d_arena, const otg_align_task* d_tasks, const uint32_t* d_todo,
                      const uint32_t* d_n_todo, uint32_t n_tasks, int32_t* d_scores, uint64_t* d_cells,
-                     uint32_t* ticket, uint32_t* n_overflow, uint32_t* overflow_list)
+                     uint32_t* ticket, uint32_t* n_overflow, uint32_t* overflow_list, const uint32_t* d_pblk, const otg_myers::PlaneBlock* d_masks)
 {
   int rc;
   switch (tier) {
-    case 0: rc = launch_one<1, 8>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list); break;
-    case 1: rc = launch_one<2, 8>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list); break;
-    case 2: rc = launch_one<3, 8>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list); break;
-    case 3: rc = launch_one<2, 16>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list); break;
-    case 4: rc = launch_one<3, 16>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list); break;
-    case 5: rc = launch_one<2, 32>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list); break;
-    case 6: rc = launch_one<2, 64>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list); break;
-    default: rc = launch_one<4, 64>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list); break;
+    case 0: rc = launch_one<1, 8>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks); break;
+    case 1: rc = launch_one<2, 8>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks); break;
+    case 2: rc = launch_one<3, 8>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks); break;
+    case 3: rc = launch_one<2, 16>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks); break;
+    case 4: rc = launch_one<3, 16>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks); break;
+    case 5: rc = launch_one<2, 32>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks); break;
+    case 6: rc = launch_one<2, 64>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks); break;
+    default: rc = launch_one<4, 64>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks); break;
   }
   if (rc) return rc;
+  HIP_TRY(ctx, hipGetLastError());
+  return OTG_OK;
+}
+
+// The per-read plane table of a resident batch (read_masks_kernel): d_first_blk[i] = first table block of read i, d_read_blk[i] = the same
+// or NO_MASKS on return.
+int otg_launch_read_masks(otg_ctx* ctx, const uint8_t* d_arena, const otg_read* d_reads, const uint32_t* d_read_region, uint32_t n_reads,
+                          const uint32_t* d_first_blk, otg_myers::PlaneBlock* d_masks, uint32_t* d_read_blk)
+{
+  if (n_reads == 0) return OTG_OK;
+  const uint32_t grid = std::min<uint32_t>((n_reads + 3) / 4, (uint32_t)ctx->n_cu * 32);
+  hipLaunchKernelGGL(read_masks_kernel, dim3(grid), dim3(256), 0, ctx->stream, d_arena, d_reads, d_read_region, n_reads, d_first_blk, d_masks, d_read_blk);
   HIP_TRY(ctx, hipGetLastError());
   return OTG_OK;
 }

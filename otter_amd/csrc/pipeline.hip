@@ -13,6 +13,7 @@
 // the aligners consume compacted todo lists whose length stays on the device.  The host only reads back a
 // handful of scalars (POA layout totals, output sizes).
 #include "otg_chain.hpp"
+#include "myers_masks.hpp"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -39,6 +40,7 @@ struct Pipeline {
   std::vector<otg_region> h_regions;
   std::vector<uint64_t> h_dist_off, h_re_off, h_cig_off;
   uint64_t n_pair_slots = 0, n_re_slots = 0, cig_bytes = 0;
+  uint64_t n_mask_blocks = 0;             // 64-base blocks of the per-read plane table of the edit tiers (0: no table, OTG_EDIT_MASKS=0)
   uint32_t cl_nmax = 0;                   // upper bound of the valid reads of a clustered region (its read count)
   std::vector<uint32_t> cl_wide;          // regions whose read count exceeds the LDS scratch of the clustering kernel
   std::vector<DevBuf> buf;
@@ -56,6 +58,7 @@ enum {
   B_REDIST, B_RTASKS, B_RKIND, B_CIGLEN, B_CIG,
   B_ALLELES, B_GRAPHS, B_MEMBERS, B_POALEN,
   B_ALLEN, B_ALOFF, B_ALIDX, B_OUTSEQ, B_OUTAL, B_REGRES, B_STATS, B_SCAN_TMP, B_TOTALS,
+  B_MASKS, B_MASK_FIRST, B_MASK_READ, B_MASK_TASK,
   B_COUNT
 };
 
@@ -131,6 +134,16 @@ __device__ int anreads_task(const uint8_t* arena, const otg_read& x, const otg_r
   }
   *known = -1.0;
   return 0;
+}
+
+// first table block of a task's pattern (myers_masks.hpp): the pattern of every task above is a whole read, x or y; the reversed copies of the
+// mirrored tasks are not in the table
+__device__ uint32_t task_mask_block(const uint32_t* __restrict__ read_blk, const otg_align_task& t, const otg_read& x, uint32_t xi, const otg_read& y, uint32_t yi)
+{
+  if (t._pad & 1) return otg_myers::NO_MASKS;
+  if (t.pattern_off == y.seq_off && t.pattern_len == y.seq_len) return read_blk[yi];
+  if (t.pattern_off == x.seq_off && t.pattern_len == x.seq_len) return read_blk[xi];
+  return otg_myers::NO_MASKS;
 }
 
 // ---- local_realignment, part 1 (src/analignments.cpp:15-32)
@@ -238,7 +251,8 @@ __global__ void K_pair_tasks(const uint8_t* __restrict__ arena, const otg_read* 
                              const int32_t* __restrict__ ign, const uint32_t* __restrict__ valid,
                              const uint64_t* __restrict__ dist_off, int max_alleles,
                              otg_align_task* __restrict__ tasks, uint32_t* __restrict__ den, double* __restrict__ dist,
-                             uint32_t* __restrict__ todo, uint32_t* __restrict__ n_todo)
+                             uint32_t* __restrict__ todo, uint32_t* __restrict__ n_todo,
+                             const uint32_t* __restrict__ read_blk, uint32_t* __restrict__ task_blk)
 {
   for (uint32_t r = blockIdx.x; r < n_regions; r += gridDim.x) {
     const int n = (int)n_valid[r];
@@ -248,9 +262,11 @@ __global__ void K_pair_tasks(const uint8_t* __restrict__ arena, const otg_read* 
     const size_t np = (size_t)n * (n - 1) / 2;
     if (max_alleles == 1) { for (size_t q = threadIdx.x; q < np; q += blockDim.x) dist[base + q] = 1.0; continue; }   // DistMatrix default (src/andistmat.cpp:10)
     for (int i = 0; i < n - 1; ++i) {
-      const otg_read x = reads[valid[f + i]];
+      const uint32_t xi = valid[f + i];
+      const otg_read x = reads[xi];
       for (int j = i + 1 + (int)threadIdx.x; j < n; j += (int)blockDim.x) {
-        const otg_read y = reads[valid[f + j]];
+        const uint32_t yi = valid[f + j];
+        const otg_read y = reads[yi];
         const uint64_t slot = base + didx(n, i, j);
         if (!ign[r]) {
           const bool bx = x.ps >= 0 && x.hp >= 0, by = y.ps >= 0 && y.hp >= 0;
@@ -258,7 +274,10 @@ __global__ void K_pair_tasks(const uint8_t* __restrict__ arena, const otg_read* 
         } else {
           double known = 0;
           uint32_t d = 1;
-          if (anreads_task(arena, x, y, tasks[slot], &d, &known)) { den[slot] = d; todo[atomicAdd(n_todo, 1u)] = (uint32_t)slot; }
+          if (anreads_task(arena, x, y, tasks[slot], &d, &known)) {
+            den[slot] = d; todo[atomicAdd(n_todo, 1u)] = (uint32_t)slot;
+            if (task_blk) task_blk[slot] = task_mask_block(read_blk, tasks[slot], x, xi, y, yi);
+          }
           else dist[slot] = known;
         }
       }
@@ -345,7 +364,8 @@ __global__ void K_reassign_tasks(const uint8_t* __restrict__ arena, const otg_re
                                  const uint32_t* __restrict__ n_valid, const int32_t* __restrict__ fc, const int32_t* __restrict__ labels,
                                  const uint64_t* __restrict__ re_off, otg_align_task* __restrict__ tasks,
                                  uint32_t* __restrict__ den, double* __restrict__ dist,
-                                 uint32_t* __restrict__ todo, uint32_t* __restrict__ n_todo, uint64_t rev_base)
+                                 uint32_t* __restrict__ todo, uint32_t* __restrict__ n_todo, uint64_t rev_base,
+                                 const uint32_t* __restrict__ read_blk, uint32_t* __restrict__ task_blk)
 {
   for (uint32_t r = blockIdx.x; r < n_regions; r += gridDim.x) {
     if (status[r] != OTG_REGION_OK || fc[r] <= 0) continue;                            // fc == 0: `-a 0` defect, reference UB
@@ -365,7 +385,10 @@ __global__ void K_reassign_tasks(const uint8_t* __restrict__ arena, const otg_re
         const uint64_t slot = re_off[r] + (uint64_t)i * n + j;
         double known = 0;
         uint32_t d = 1;
-        if (anreads_task(arena, x, y, tasks[slot], &d, &known, rev_base)) { den[slot] = d; todo[atomicAdd(n_todo, 1u)] = (uint32_t)slot; }
+        if (anreads_task(arena, x, y, tasks[slot], &d, &known, rev_base)) {
+          den[slot] = d; todo[atomicAdd(n_todo, 1u)] = (uint32_t)slot;
+          if (task_blk) task_blk[slot] = task_mask_block(read_blk, tasks[slot], x, f + (uint32_t)i, y, f + (uint32_t)j);
+        }
         else dist[slot] = known;
       }
     }
@@ -689,6 +712,16 @@ int otg_assemble_submit(otg_ctx* ctx, const otg_params* params, const uint8_t* s
   for (uint32_t i = 0; i < n_reads; ++i)
     pl->h_cig_off[i + 1] = pl->h_cig_off[i] + (covered[i] ? (((uint64_t)region_maxlen[read_region[i]] + reads[i].seq_len + 15) & ~15ull) : 0);
   pl->n_pair_slots = pl->h_dist_off[n_regions]; pl->n_re_slots = pl->h_re_off[n_regions]; pl->cig_bytes = pl->h_cig_off[n_reads];
+  // per-read plane table of the bit-parallel edit tiers (myers_masks.hpp): 16 bytes per 64 bases of every read of a region, laid out from the
+  // submitted lengths (realignment only shortens a read).  OTG_EDIT_MASKS=0: no table, every pair builds its own masks.
+  static const bool edit_masks = otg_env_int("OTG_EDIT_MASKS", 1) != 0;
+  std::vector<uint32_t> mask_first(n_reads, 0u);
+  pl->n_mask_blocks = 0;
+  if (edit_masks) {
+    uint64_t nb = 0;
+    for (uint32_t i = 0; i < n_reads; ++i) { mask_first[i] = (uint32_t)nb; if (covered[i]) nb += ((uint64_t)reads[i].seq_len + 63) >> 6; if (nb >= 0xffffffffull) break; }
+    pl->n_mask_blocks = nb < 0xffffffffull ? nb : 0;       // (a batch beyond 2^32 blocks — 256 GB of reads — runs without the table)
+  }
   if (pl->n_pair_slots >= 0xffffffffull || pl->n_re_slots >= 0xffffffffull)
     return otg_fail(ctx, OTG_ERR_CAPACITY, "batch too large: split it (pair slots %llu, reassignment slots %llu)", (unsigned long long)pl->n_pair_slots, (unsigned long long)pl->n_re_slots);
   ctx->max_seq_len = maxlen;
@@ -704,6 +737,11 @@ int otg_assemble_submit(otg_ctx* ctx, const otg_params* params, const uint8_t* s
   void* d_co = pbuf(ctx, pl, B_CIG_OFF, (size_t)(n_reads + 1) * 8);
   void* d_f64 = pbuf(ctx, pl, B_FIRST_READ64, (size_t)n_regions * 8);
   if (!d_arena || !d_reads || !d_regions || !d_rr || !d_do || !d_ro || !d_co || !d_f64) return OTG_ERR_HIP;
+  if (pl->n_mask_blocks) {
+    void* d_mf = pbuf(ctx, pl, B_MASK_FIRST, (size_t)n_reads * 4);
+    if (!d_mf) return OTG_ERR_HIP;
+    HIP_TRY(ctx, hipMemcpyAsync(d_mf, mask_first.data(), (size_t)n_reads * 4, hipMemcpyHostToDevice, ctx->stream));
+  }
   HIP_TRY(ctx, hipMemsetAsync(d_arena + arena_bytes, 0, 64, ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(d_arena + pl->rev_base + arena_bytes, 0, 64, ctx->stream));
   if (arena_bytes) HIP_TRY(ctx, hipMemcpyAsync(d_arena, seq_arena, arena_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -731,6 +769,9 @@ int otg_assemble_submit(otg_ctx* ctx, const otg_params* params, const uint8_t* s
       !pbuf(ctx, pl, B_SCAN_TMP, (size_t)n_reads * 4 + 4) || !pbuf(ctx, pl, B_TOTALS, 64) || !pbuf(ctx, pl, B_REGRES, (size_t)(n_regions + 1) * sizeof(otg_region_result)) ||
       !otg_slot(ctx, SLOT_AUX9, (pl->n_pair_slots + 1) * 8))
     return OTG_ERR_HIP;
+  if (pl->n_mask_blocks && (!pbuf(ctx, pl, B_MASKS, (size_t)pl->n_mask_blocks * sizeof(otg_myers::PlaneBlock)) || !pbuf(ctx, pl, B_MASK_READ, (size_t)n_reads * 4) ||
+                            !pbuf(ctx, pl, B_MASK_TASK, ntask * 4)))
+    return OTG_ERR_HIP;
   return OTG_OK;
 }
 
@@ -750,6 +791,18 @@ int otg_assemble_collect_reads(otg_ctx* ctx, otg_read* reads_out, uint32_t n_rea
   if (n_reads != pl->n_reads || (n_reads && !reads_out)) return otg_fail(ctx, OTG_ERR_ARG, "otg_assemble_collect_reads: expected room for %u reads", pl->n_reads);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (n_reads) HIP_TRY(ctx, hipMemcpyAsync(reads_out, pl->buf[B_READS].p, (size_t)n_reads * sizeof(otg_read), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return OTG_OK;
+}
+
+int otg_assemble_collect_dist(otg_ctx* ctx, double* dist_out, uint64_t n_slots)
+{
+  if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_assemble_collect_dist: no context");
+  Pipeline* pl = ctx->pipe;
+  if (!pl || !pl->ran) return otg_fail(ctx, OTG_ERR_ARG, "otg_assemble_collect_dist: no completed run");
+  if (n_slots != pl->n_pair_slots || (n_slots && !dist_out)) return otg_fail(ctx, OTG_ERR_ARG, "otg_assemble_collect_dist: expected room for %llu distances", (unsigned long long)pl->n_pair_slots);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (n_slots) HIP_TRY(ctx, hipMemcpyAsync(dist_out, pl->buf[B_DIST].p, (size_t)n_slots * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return OTG_OK;
 }
@@ -807,6 +860,11 @@ static int assemble_run_body(otg_ctx* ctx, bool realign_only)
   uint64_t* d_cig_off = (uint64_t*)B(B_CIG_OFF);
   uint32_t* d_cig_len = (uint32_t*)B(B_CIGLEN);
   uint8_t* d_cig = (uint8_t*)B(B_CIG);
+  // the plane table serves the exact bit-parallel tiers only (the adaptive chain has none)
+  const bool masks = pl->n_mask_blocks != 0 && ctx->heur_strategy == OTG_HEURISTIC_NONE;
+  otg_myers::PlaneBlock* d_masks = masks ? (otg_myers::PlaneBlock*)B(B_MASKS) : nullptr;
+  uint32_t* d_read_blk = masks ? (uint32_t*)B(B_MASK_READ) : nullptr;
+  uint32_t* d_task_blk = masks ? (uint32_t*)B(B_MASK_TASK) : nullptr;
   memset(&pl->stats, 0, sizeof(pl->stats));
   pl->ran = false;               // a run that fails below must not leave the previous run's results collectable
   pl->out_alleles = 0; pl->out_seq_bytes = 0;
@@ -847,10 +905,15 @@ static int assemble_run_body(otg_ctx* ctx, bool realign_only)
   {
     Timer t(ctx);
     hipLaunchKernelGGL(K_region_prepare, dim3(gr_regions), dim3(TB), 0, st, d_reads, d_regions, NG, P.max_cov, P.ignore_haps, d_status, d_nvalid, d_ign, d_valid, d_vpos, d_vlen);
-    hipLaunchKernelGGL(K_pair_tasks, dim3(gr_blocks), dim3(64), 0, st, d_arena, d_reads, d_regions, NG, d_nvalid, d_ign, d_valid, (const uint64_t*)B(B_DIST_OFF), P.max_alleles, d_tasks, d_den, d_dist, d_todo, d_cnt + 20);
+    if (d_masks) {           // the reads are final from here on: their planes, once for both edit passes
+      rc = otg_launch_read_masks(ctx, d_arena, d_reads, d_rr, NR, (const uint32_t*)B(B_MASK_FIRST), d_masks, d_read_blk);
+      if (rc) return rc;
+    }
+    hipLaunchKernelGGL(K_pair_tasks, dim3(gr_blocks), dim3(64), 0, st, d_arena, d_reads, d_regions, NG, d_nvalid, d_ign, d_valid, (const uint64_t*)B(B_DIST_OFF), P.max_alleles, d_tasks, d_den, d_dist, d_todo, d_cnt + 20,
+                       (const uint32_t*)d_read_blk, d_task_blk);
     float kms = 0; uint64_t kl = 0;
     dbg(ctx, "pair tasks done");
-    rc = otg_launch_edit_todo(ctx, d_arena, d_tasks, d_todo, d_cnt + 20, (uint32_t)pl->n_pair_slots, d_scores, d_cells, &kms, &kl);
+    rc = otg_launch_edit_todo(ctx, d_arena, d_tasks, d_todo, d_cnt + 20, (uint32_t)pl->n_pair_slots, d_scores, d_cells, &kms, &kl, d_task_blk, d_masks);
     if (rc) return rc;
     pl->stats.ms_edit_kernel += kms; pl->stats.edit_kernel_launches += kl;
     hipLaunchKernelGGL(K_dist_epilogue, dim3(1024), dim3(256), 0, st, d_todo, d_cnt + 20, d_scores, d_den, d_dist, d_cnt + 40);
@@ -877,10 +940,10 @@ static int assemble_run_body(otg_ctx* ctx, bool realign_only)
     if (rev_base) hipLaunchKernelGGL(K_reverse_reads, dim3(std::min<uint32_t>((NR + 3) / 4, (uint32_t)ctx->n_cu * 32)), dim3(256), 0, st, d_arena, d_reads, d_regions, d_rr, NR,
                                      d_status, d_nvalid, rev_base);
     hipLaunchKernelGGL(K_reassign_tasks, dim3(gr_blocks), dim3(64), 0, st, d_arena, d_reads, d_regions, NG, d_status, d_nvalid, (const int32_t*)B(B_FC), d_labels,
-                       (const uint64_t*)B(B_RE_OFF), d_tasks, d_den, d_redist, d_todo, d_cnt + 24, rev_base);
+                       (const uint64_t*)B(B_RE_OFF), d_tasks, d_den, d_redist, d_todo, d_cnt + 24, rev_base, (const uint32_t*)d_read_blk, d_task_blk);
     float kms = 0; uint64_t kl = 0;
     ctx->edit_pass_kind = 1;
-    rc = otg_launch_edit_todo(ctx, d_arena, d_tasks, d_todo, d_cnt + 24, (uint32_t)pl->n_re_slots, d_scores, d_cells, &kms, &kl);
+    rc = otg_launch_edit_todo(ctx, d_arena, d_tasks, d_todo, d_cnt + 24, (uint32_t)pl->n_re_slots, d_scores, d_cells, &kms, &kl, d_task_blk, d_masks);
     ctx->edit_pass_kind = 0;
     if (rc) return rc;
     pl->stats.ms_edit_kernel += kms; pl->stats.edit_kernel_launches += kl;

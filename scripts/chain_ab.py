@@ -5,6 +5,7 @@
                                                    byte for byte: OUT/same_bytes.json (the arrays themselves are not kept)
   table OUT OUT.json                               same_bytes.json; per leg the rounds, the medians, the parent's max - min and whether the result's
                                                    median is no worse than the parent's median by more than that spread
+                                                   (legs that the rounds' bench.py arguments switched off are left out)
 Stops at the first process that fails or outlives its limit."""
 import glob
 import hashlib
@@ -49,7 +50,10 @@ if mode == "table":
     print("dumped arrays: %d, differing: %s" % (same["arrays"], same["differing"]))
     ok = same["arrays"] > 0 and not same["differing"]
     for leg, (where, higher) in LEGS.items():
-        v = {t: [pick(r, where) for r in rounds[t]] for t in rounds}
+        try:
+            v = {t: [pick(r, where) for r in rounds[t]] for t in rounds}
+        except KeyError:          # a leg the rounds were run without (--no-legs, --e2e-regions 0, --config N)
+            continue
         mp, mr, spread = statistics.median(v["parent"]), statistics.median(v["result"]), max(v["parent"]) - min(v["parent"])
         good = mr >= mp - spread if higher else mr <= mp + spread
         res["legs"][leg] = dict(v, unit="regions/s" if higher else "ms", median={"parent": mp, "result": mr}, parent_spread=round(spread, 3))
