@@ -321,6 +321,32 @@ int otg_genotype_cluster_trace_batch(otg_ctx* ctx, const otg_params* params,
                                      int32_t* gt_out, int32_t* gt_l_out, int32_t* gt_k_out, double* hsd_out,
                                      int32_t* n_gt_out, int32_t* reps_out, const otg_genotype_trace* trace);
 
+/* The metric of anallele_cluster's FIRST matrix (the one cut at gt_max_error, "Maximum sequence dissimilarity").
+ *   OTG_GT_METRIC_LENGTH  the reference's length-ratio matrix: otg_genotype_cluster_batch, bit for bit.
+ *   OTG_GT_METRIC_EDIT    the sequence dissimilarity align_anreads computes (src/analignments.cpp:62-72): 0.0 for two equal byte strings,
+ *                         otherwise edit(pattern, text) / (double)max(len), end to end, unit cost, the pattern being the longer sequence (the
+ *                         lower index on equal length).  Always the EXACT distance, whatever otg_set_heuristic left on the context (which
+ *                         the call neither reads nor changes).  The clustering, the cut, the 3-mer partition, hsd, the genotypes and the
+ *                         medoids are computed as before, on this matrix.  Alleles with the same bytes are aligned once per region.
+ * otg_genotype_cluster_metric_batch: the arguments and results of otg_genotype_cluster_batch, then the metric (any other value: OTG_ERR_ARG),
+ *   dist_out (nullable): the first matrix as clustered, condensed, region after region at the running sum of A (A - 1) / 2;
+ *   n_aligned_out (nullable): pairs of distinct sequences scored (0 under LENGTH).
+ * OTG_ERR_CAPACITY: "batch too large: split it" when the pair slots of the batch pass 2^32 (EDIT; nothing is allocated), or a pair beyond
+ * the capacity of the edit aligner (the message names the region; no partial results).                                              */
+#define OTG_GT_METRIC_LENGTH 0
+#define OTG_GT_METRIC_EDIT   1
+int otg_genotype_cluster_metric_batch(otg_ctx* ctx, const otg_params* params,
+                                      const uint8_t* seq_arena, uint64_t arena_bytes,
+                                      const uint64_t* seq_off, const uint32_t* seq_len,
+                                      const uint32_t* first_allele, const uint32_t* n_alleles, uint32_t n_regions,
+                                      int32_t* gt_out, int32_t* gt_l_out, int32_t* gt_k_out, double* hsd_out,
+                                      int32_t* n_gt_out, int32_t* reps_out,
+                                      int32_t metric, double* dist_out, uint64_t* n_aligned_out);
+/* HIP-event times (ms) of the two device parts of the latest otg_genotype_cluster_metric_batch / otg_genotype_cohort_metric on this context:
+ * align_ms = allele classes + pair tasks + the edit chain + the fan-out (0 under LENGTH), cluster_ms = the clustering kernels.  Their sum is
+ * what otg_last_kernel_ms reports.  Measurement hook, like otg_edit_align_last_ms.                                                   */
+int otg_genotype_metric_last_ms(otg_ctx* ctx, double* align_ms, double* cluster_ms);
+
 /* HIP-event time (ms, events on the context's own stream) of the device kernels of the latest otg_genotype_cluster_batch on this context:
  * what a roofline figure divides by; host copies excluded.  The reference has no counterpart (measurement hook).        */
 int otg_last_kernel_ms(otg_ctx* ctx, double* ms);
@@ -640,7 +666,7 @@ typedef struct otg_genotype_job {
   int32_t     threads;           /* -t: host threads of the allele ingest                            */
   int32_t     device;            /* HIP device ordinal                                               */
   uint32_t    batch_regions;     /* regions per batch, 0 = 1024                                      */
-  uint32_t    reserved;
+  uint32_t    metric;            /* OTG_GT_METRIC_LENGTH (0) or OTG_GT_METRIC_EDIT; ignored without a FASTA; other values: OTG_ERR_ARG */
 } otg_genotype_job;
 int otg_genotype_files(const otg_genotype_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
 /* ---------------------------------------------------------------------------------------------
@@ -763,6 +789,8 @@ int otg_vcf2mat_files(const otg_vcf2mat_job* job, otg_write_fn write, void* user
  *                        a sample in label order, the reference allele last with sample index n_samples.  A region in which no sample has an
  *                        allele has no alleles at all (src/genotype.cpp:90); a zero-length allele becomes "N" (src/anseqs.cpp:505-507);
  *   otg_cohort_genotype  anallele_cluster on the regrouped buffers (the kernels of otg_genotype_cluster_batch; gt_max_error, gt_max_cosdis);
+ *   otg_genotype_cohort_metric  the same under a metric (otg_genotype_cluster_metric_batch: OTG_GT_METRIC_EDIT aligns the alleles in HBM,
+ *                        exactly, whatever heuristic the assemble runs left on the context); everything after it works unchanged;
  *   otg_cohort_collect   D2H; every output is nullable.  first_allele_out has n_regions + 1 entries; alleles_out are the records in regrouped
  *                        order as otg_ingest_alleles would deliver them (.seq_off into seq_out, .region = batch-local region, .label = sample
  *                        index); sample_out / seq_off_out / seq_len_out are the arrays the kernels read; gt .. reps as
@@ -773,7 +801,8 @@ int otg_vcf2mat_files(const otg_vcf2mat_job* job, otg_write_fn write, void* user
 int otg_cohort_begin(otg_ctx* ctx, uint32_t n_regions, uint32_t n_samples);
 int otg_cohort_stage(otg_ctx* ctx, otg_ctx* src_ctx, uint32_t sample);
 int otg_cohort_regroup(otg_ctx* ctx, const uint8_t* ref_arena, uint64_t ref_bytes, const uint64_t* ref_off, const uint32_t* ref_len);
-int otg_cohort_genotype(otg_ctx* ctx, const otg_params* params);
+int otg_cohort_genotype(otg_ctx* ctx, const otg_params* params);      /* = otg_genotype_cohort_metric(.., OTG_GT_METRIC_LENGTH) */
+int otg_genotype_cohort_metric(otg_ctx* ctx, const otg_params* params, int32_t metric);
 int otg_cohort_result_sizes(otg_ctx* ctx, uint32_t* n_alleles, uint64_t* seq_bytes);
 int otg_cohort_collect(otg_ctx* ctx, uint32_t* first_allele_out, otg_allele* alleles_out, uint32_t allele_capacity, int32_t* sample_out,
                        uint64_t* seq_off_out, uint32_t* seq_len_out, uint8_t* seq_out, uint64_t seq_capacity,
@@ -830,7 +859,7 @@ typedef struct otg_cohort_job {
   otg_params  params;            /* assemble heuristics and gt_max_error / gt_max_cosdis (realign is set by the library)   */
   otg_ingest_opts ingest;        /* one --offset pair for the whole cohort (one `OF:` header line carries it); .threads = host ingest threads */
   int32_t     n_devices;         /* 0: device 0 only                                                                       */
-  int32_t     reserved;
+  int32_t     gt_metric;         /* of the joint genotyping: OTG_GT_METRIC_LENGTH (0) or OTG_GT_METRIC_EDIT; other values: OTG_ERR_ARG */
   const int32_t* devices;        /* HIP device ordinals, one contiguous BED shard each                                     */
   otg_cohort_allele_write_fn allele_write;   /* nullable                                                                   */
   void*       allele_user;

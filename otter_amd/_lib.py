@@ -27,6 +27,7 @@ EXPORTS = [
     "otg_bam_sink_open", "otg_bam_sink_write", "otg_bam_sink_close", "otg_bam_sink_abort", "otg_bam_sink_error", "otg_bam_merge",
     "otg_comm_unique_id", "otg_comm_create", "otg_comm_destroy", "otg_gather_sizes", "otg_gather_records",
     "otg_exp_probe_mismatches", "otg_exp_probe", "otg_exp_host", "otg_exp_device", "otg_cluster_trace_batch", "otg_genotype_cluster_trace_batch",
+    "otg_genotype_cluster_metric_batch", "otg_genotype_metric_last_ms", "otg_genotype_cohort_metric",
 ]
 
 _lib = None
@@ -356,7 +357,11 @@ class Context:
         self._check(rc, "otg_poa_consensus_batch")
         return [out[int(off[i]):int(off[i]) + int(ln[i])].tobytes() for i in range(ng)]
 
-    def genotype_cluster_batch(self, params, arena, seq_off, seq_len, first_allele, n_alleles):
+    def genotype_cluster_batch(self, params, arena, seq_off, seq_len, first_allele, n_alleles, metric="length"):
+        """otg_genotype_cluster_batch -> (gt, gt_l, gt_k, hsd, n_gt, reps); metric="edit": the same tuple from
+        otg_genotype_cluster_metric_batch (the first matrix from exact alignments of the alleles)."""
+        if abi.gt_metric(metric) != abi.OTG_GT_METRIC_LENGTH:
+            return self.genotype_cluster_metric_batch(params, arena, seq_off, seq_len, first_allele, n_alleles, metric)[:6]
         nreg = len(n_alleles)
         na = len(seq_off)
         gt, gl, gk = (np.zeros(na, dtype=np.int32) for _ in range(3))
@@ -368,6 +373,34 @@ class Context:
                                                 abi.ptr(gt), abi.ptr(gl), abi.ptr(gk), abi.ptr(hsd), abi.ptr(ngt), abi.ptr(reps))
         self._check(rc, "otg_genotype_cluster_batch")
         return gt, gl, gk, hsd, ngt, reps
+
+    def genotype_cluster_metric_batch(self, params, arena, seq_off, seq_len, first_allele, n_alleles, metric="length"):
+        """otg_genotype_cluster_metric_batch -> (gt, gt_l, gt_k, hsd, n_gt, reps, dist, n_aligned): metric "length" (the reference's
+        length-ratio matrix) or "edit" (edit distance / longer length, always exact); dist = the first matrix as clustered (condensed,
+        region after region), n_aligned = pairs of distinct sequences scored (0 under "length")."""
+        m = abi.gt_metric(metric)
+        nreg = len(n_alleles)
+        na = len(seq_off)
+        gt, gl, gk = (np.zeros(na, dtype=np.int32) for _ in range(3))
+        hsd = np.zeros(na)
+        ngt = np.zeros(nreg, dtype=np.int32)
+        reps = np.zeros(na, dtype=np.int32)
+        A = np.asarray(n_alleles, dtype=np.int64)
+        npairs = int((A * (A - 1) // 2).sum())
+        dist = np.zeros(npairs + 1)
+        n_aligned = C.c_uint64(0)
+        rc = self._L.otg_genotype_cluster_metric_batch(self._h, C.byref(params), abi.ptr(arena), C.c_uint64(arena.size), abi.ptr(seq_off),
+                                                       abi.ptr(seq_len), abi.ptr(first_allele), abi.ptr(n_alleles), C.c_uint32(nreg),
+                                                       abi.ptr(gt), abi.ptr(gl), abi.ptr(gk), abi.ptr(hsd), abi.ptr(ngt), abi.ptr(reps),
+                                                       C.c_int32(m), abi.ptr(dist), C.byref(n_aligned))
+        self._check(rc, "otg_genotype_cluster_metric_batch")
+        return gt, gl, gk, hsd, ngt, reps, dist[:npairs], int(n_aligned.value)
+
+    def genotype_metric_last_ms(self):
+        """(align_ms, cluster_ms) of the latest genotype_cluster_metric_batch / cohort_genotype (otg_genotype_metric_last_ms)."""
+        a, b = C.c_double(0.0), C.c_double(0.0)
+        self._check(self._L.otg_genotype_metric_last_ms(self._h, C.byref(a), C.byref(b)), "otg_genotype_metric_last_ms")
+        return float(a.value), float(b.value)
 
     def genotype_cluster_trace_batch(self, params, arena, seq_off, seq_len, first_allele, n_alleles):
         """otg_genotype_cluster_trace_batch: genotype_cluster_batch's tuple plus a dict of the kernel's matrices: dl, dk (condensed, region
@@ -497,11 +530,16 @@ class Context:
         ref_len = np.ascontiguousarray(ref_len, dtype=np.uint32)
         self._check(self._L.otg_cohort_regroup(self._h, abi.ptr(ref_arena), C.c_uint64(ref_arena.size), abi.ptr(ref_off), abi.ptr(ref_len)), "otg_cohort_regroup")
 
-    def cohort_genotype(self, params, ref_arena=None, ref_off=None, ref_len=None):
-        """otg_cohort_genotype (after cohort_regroup when the reference alleles are given): anallele_cluster on the regrouped buffers."""
+    def cohort_genotype(self, params, ref_arena=None, ref_off=None, ref_len=None, metric="length"):
+        """otg_cohort_genotype (after cohort_regroup when the reference alleles are given): anallele_cluster on the regrouped buffers;
+        metric="edit": otg_genotype_cohort_metric with OTG_GT_METRIC_EDIT."""
+        m = abi.gt_metric(metric)
         if ref_off is not None:
             self.cohort_regroup(ref_arena, ref_off, ref_len)
-        self._check(self._L.otg_cohort_genotype(self._h, C.byref(params)), "otg_cohort_genotype")
+        if m == abi.OTG_GT_METRIC_LENGTH:
+            self._check(self._L.otg_cohort_genotype(self._h, C.byref(params)), "otg_cohort_genotype")
+        else:
+            self._check(self._L.otg_genotype_cohort_metric(self._h, C.byref(params), C.c_int32(m)), "otg_genotype_cohort_metric")
 
     def cohort_collect(self, clustered=True):
         """otg_cohort_collect -> {"first_allele" [n_regions + 1], "n_alleles", "alleles" (allele_dt, .label = sample index), "sample", "seq_off",
@@ -1096,10 +1134,11 @@ def assemble_batch_plan(n_regions, batch_regions=0):
     return [int(out[i]) for i in range(n.value)]
 
 
-def genotype_files(bam, bed, fasta=None, params=None, threads=1, device=0, batch_regions=0):
+def genotype_files(bam, bed, fasta=None, params=None, threads=1, device=0, batch_regions=0, metric="length"):
     """otg_genotype_files: `otter genotype` from files to text (VCF with a reference FASTA, the two-length table without).
-    Returns (text bytes, stats dict)."""
+    metric: "length" (the reference) or "edit" (alleles clustered by exact edit distance).  Returns (text bytes, stats dict)."""
     job = abi.GenotypeJob()
+    job.metric = abi.gt_metric(metric)
     job.bam_path = bam.encode(); job.bed_path = bed.encode(); job.fasta_path = fasta.encode() if fasta else None
     job.params = params if params is not None else abi.default_params()
     job.threads = threads; job.device = device; job.batch_regions = batch_regions
@@ -1107,19 +1146,19 @@ def genotype_files(bam, bed, fasta=None, params=None, threads=1, device=0, batch
 
 
 def cohort_files(bams, names, bed, fasta, params=None, batch_regions=0, devices=None, offset_l=1, offset_r=0, mapq=0, nonprimary=False,
-                 omit_nonspanning=False, read_quality=0.0, threads=1, alleles=False, *, alleles_bam=None, matrix_k=None):
+                 omit_nonspanning=False, read_quality=0.0, threads=1, alleles=False, *, alleles_bam=None, matrix_k=None, gt_metric="length"):
     """otg_cohort_files: sample BAMs + BED + reference FASTA to one joint VCF, the alleles staying on the device between `otter assemble` and
     `otter genotype`.  Returns (VCF bytes, stats dict), and with alleles=True also the list of per-sample SAM texts (what assemble_files returns
     for each sample with read_group = its name).  alleles_bam: a list of paths, one per sample: the same records as BAM + BAI files.
     matrix_k: also the k-mer usage matrix of the joint alleles at that k (the text vcf2mat_files returns for the VCF), computed while the
-    alleles are in HBM and appended to the returned tuple as its last element."""
+    alleles are in HBM and appended to the returned tuple as its last element.  gt_metric: "length" or "edit", as genotype_files' metric."""
     if alleles_bam is not None and len(alleles_bam) != len(bams):
         raise OtterGpuError("cohort_files: alleles_bam has %d paths for %d samples" % (len(alleles_bam), len(bams)))
     job = abi.CohortJob()
     n = len(bams)
     pb = (C.c_char_p * max(1, n))(*[b.encode() for b in bams])
     pn = (C.c_char_p * max(1, n))(*[x.encode() for x in names])
-    job.n_samples = n; job.batch_regions = batch_regions
+    job.n_samples = n; job.batch_regions = batch_regions; job.gt_metric = abi.gt_metric(gt_metric)
     job.bam_paths = pb; job.sample_names = pn
     job.bed_path = bed.encode(); job.fasta_path = fasta.encode() if fasta else None
     job.params = params if params is not None else abi.default_params()

@@ -33,6 +33,20 @@ class otg_params(C.Structure):
 OTG_HEURISTIC_NONE = 0
 OTG_HEURISTIC_WFADAPTIVE = 1
 
+# the metric of the genotype clustering's first matrix (otg_genotype_cluster_metric_batch)
+OTG_GT_METRIC_LENGTH = 0
+OTG_GT_METRIC_EDIT = 1
+
+
+def gt_metric(metric):
+    """"length" / "edit" -> the OTG_GT_METRIC_* number; an integer passes through (the library refuses unknown values)."""
+    if isinstance(metric, str):
+        try:
+            return {"length": OTG_GT_METRIC_LENGTH, "edit": OTG_GT_METRIC_EDIT}[metric]
+        except KeyError:
+            raise ValueError("unknown genotype metric %r (length, edit)" % (metric,)) from None
+    return int(metric)
+
 # otg_affine_last_routing: routed 0..4 = a register tier, AFFINE_TIER_NONE = straight to tier A; finished 0..4, AFFINE_FIN_A / _B / _C,
 # AFFINE_FIN_NOBODY = the generic kernel gave up too.  AFFINE_N_COUNTS = length of its counts_out.
 AFFINE_REG_TIERS = 5
@@ -177,7 +191,7 @@ class AssembleJob(C.Structure):
 class GenotypeJob(C.Structure):
     """otg_genotype_job (include/otter_gpu.h)."""
     _fields_ = [("bam_path", C.c_char_p), ("bed_path", C.c_char_p), ("fasta_path", C.c_char_p), ("params", otg_params),
-                ("threads", C.c_int32), ("device", C.c_int32), ("batch_regions", C.c_uint32), ("reserved", C.c_uint32)]
+                ("threads", C.c_int32), ("device", C.c_int32), ("batch_regions", C.c_uint32), ("metric", C.c_uint32)]
 
 
 class CompareJob(C.Structure):
@@ -219,6 +233,6 @@ class CohortJob(C.Structure):
     """otg_cohort_job (include/otter_gpu.h)."""
     _fields_ = [("n_samples", C.c_uint32), ("batch_regions", C.c_uint32), ("bam_paths", C.POINTER(C.c_char_p)), ("sample_names", C.POINTER(C.c_char_p)),
                 ("bed_path", C.c_char_p), ("fasta_path", C.c_char_p), ("params", otg_params), ("ingest", IngestOpts),
-                ("n_devices", C.c_int32), ("reserved", C.c_int32), ("devices", C.POINTER(C.c_int32)),
+                ("n_devices", C.c_int32), ("gt_metric", C.c_int32), ("devices", C.POINTER(C.c_int32)),
                 ("allele_write", C.c_void_p), ("allele_user", C.c_void_p),
                 ("matrix_write", C.c_void_p), ("matrix_user", C.c_void_p), ("matrix_k", C.c_int32), ("reserved2", C.c_int32)]

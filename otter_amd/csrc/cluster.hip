@@ -688,7 +688,8 @@ __global__ __launch_bounds__(256) void cluster_kernel(
 // anallele_cluster (reference: src/otterclust.cpp:463-527) for `otter genotype`: length-ratio matrix
 // (:322-327,367-382) and 3-mer-usage cosine matrix rounded to 3 decimals (:384-420; KUSAGE src/anseqs.cpp:111-147,
 // seq2kcounts :149-166), two average-linkage cuts (cluter_to_e :329-349), genotype = distinct (gt_l, gt_k) pairs in
-// first-seen order, representative = medoid under the LENGTH matrix (:517-524).  One 256-thread workgroup per region, every
+// first-seen order, representative = medoid under the LENGTH matrix (:517-524).  With dl_given the first matrix is read from g_dl instead
+// (the sequence-dissimilarity matrix of OTG_GT_METRIC_EDIT) and everything after step 3 runs on it unchanged.  One 256-thread workgroup per region, every
 // phase spread over the block; what the reference sums in a fixed order (the 65-term norm and dot products, the Hill-Shannon sum, a
 // medoid's row sum) is summed in that order by ONE thread per output element, and different elements run in parallel:
 //   1. 3-mer counts: one WAVE per allele (alleles dealt round-robin to the four waves), lanes stride the sequence (coalesced byte
@@ -784,7 +785,7 @@ template <bool WIDE, bool TRACE>
 __global__ __launch_bounds__(256) void genotype_kernel(
     double max_error_l, double max_error_c, const uint8_t* __restrict__ arena, const uint64_t* __restrict__ seq_off,
     const uint32_t* __restrict__ seq_len, const uint32_t* __restrict__ first_allele, const uint32_t* __restrict__ n_alleles,
-    uint32_t n_regions, const uint64_t* __restrict__ pair_off, double* __restrict__ g_dl, double* __restrict__ g_dk,
+    uint32_t n_regions, const uint64_t* __restrict__ pair_off, double* __restrict__ g_dl, bool dl_given, double* __restrict__ g_dk,
     double* __restrict__ g_work, double* __restrict__ g_kvec, double* __restrict__ g_vnorm,
     int a_split, const uint32_t* __restrict__ wide_idx, uint32_t n_wide, char* __restrict__ slab, size_t slab_stride, int cap,
     int32_t* __restrict__ gt, int32_t* __restrict__ gt_l, int32_t* __restrict__ gt_k, double* __restrict__ hsd,
@@ -892,11 +893,15 @@ __global__ __launch_bounds__(256) void genotype_kernel(
       while (i > 0 && (size_t)i * (2 * A - i - 1) / 2 > p) --i;
       while ((size_t)(i + 1) * (2 * A - i - 2) / 2 <= p) ++i;
       const int j = (int)(p - (size_t)i * (2 * A - i - 1) / 2) + i + 1;
-      const uint32_t x = seq_len[f + i], y = seq_len[f + j];
-      const bool xs = x < y;
-      double d = xs ? (double)(y - x) : (double)(x - y);
-      d = xs ? d / y : d / x;
-      dl[p] = d;
+      double d;
+      if (dl_given) d = dl[p];      // the first matrix came precomputed (OTG_GT_METRIC_EDIT, genotype_edit.hip): only its working copy is made
+      else {
+        const uint32_t x = seq_len[f + i], y = seq_len[f + j];
+        const bool xs = x < y;
+        d = xs ? (double)(y - x) : (double)(x - y);
+        d = xs ? d / y : d / x;
+        dl[p] = d;
+      }
       if (in_lds) L.dmat[p] = d; else wk[p] = d;
       const double* vi = kv + (size_t)i * 65; const double* vj = kv + (size_t)j * 65;
       double dot = 0;
@@ -1102,7 +1107,7 @@ int otg_launch_genotype(otg_ctx* ctx, const otg_params* P, const uint8_t* d_aren
                         const uint64_t* d_pair_off, uint64_t n_pairs_total, uint64_t n_alleles_total, uint32_t a_max,
                         const uint32_t* h_wide, uint32_t n_wide,
                         int32_t* d_gt, int32_t* d_gtl, int32_t* d_gtk, double* d_hsd, int32_t* d_ngt, int32_t* d_reps,
-                        int32_t* d_err, double* d_height_l, double* d_height_k)
+                        int32_t* d_err, double* d_height_l, double* d_height_k, bool dl_given)
 {
   if (n_regions == 0) return OTG_OK;
   double* g_dl = (double*)otg_slot(ctx, SLOT_P20, (n_pairs_total + 1) * 8);
@@ -1116,7 +1121,7 @@ int otg_launch_genotype(otg_ctx* ctx, const otg_params* P, const uint8_t* d_aren
   uint32_t grid_dim = n_regions < (uint32_t)ctx->n_cu * 8 ? n_regions : (uint32_t)ctx->n_cu * 8;
   auto launch = [&](auto kernel, uint32_t grid, char* slab, auto trace) {
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, ctx->stream, P->gt_max_error, P->gt_max_cosdis, d_arena, d_seq_off,
-                       d_seq_len, d_first, d_n, n_regions, d_pair_off, g_dl, g_dk, g_wk, g_kv, g_vn, w.n_split, w.idx, w.n_wide, slab, w.stride, w.cap,
+                       d_seq_len, d_first, d_n, n_regions, d_pair_off, g_dl, dl_given, g_dk, g_wk, g_kv, g_vn, w.n_split, w.idx, w.n_wide, slab, w.stride, w.cap,
                        d_gt, d_gtl, d_gtk, d_hsd, d_ngt, d_reps, d_err, trace);
   };
   if (!d_height_l) {

@@ -378,13 +378,16 @@ int otg_cohort_regroup(otg_ctx* ctx, const uint8_t* ref_arena, uint64_t ref_byte
   return OTG_OK;
 }
 
-int otg_cohort_genotype(otg_ctx* ctx, const otg_params* params)
+int otg_cohort_genotype(otg_ctx* ctx, const otg_params* params) { return otg_genotype_cohort_metric(ctx, params, OTG_GT_METRIC_LENGTH); }
+
+int otg_genotype_cohort_metric(otg_ctx* ctx, const otg_params* params, int32_t metric)
 {
   Cohort* cp = cohort_of(ctx, "otg_cohort_genotype");
   if (!cp) return ctx ? OTG_ERR_ARG : OTG_ERR_NO_DEVICE;
   Cohort& c = *cp;
   if (!params) return otg_fail(ctx, OTG_ERR_ARG, "otg_cohort_genotype: NULL argument");
   if (!c.regrouped) return otg_fail(ctx, OTG_ERR_ARG, "otg_cohort_genotype: the batch has not been regrouped (otg_cohort_regroup)");
+  if (int rc0 = otg_genotype_metric_fits(ctx, "otg_cohort_genotype", metric, c.B ? c.h_pair_off[c.B] : 0)) return rc0;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   c.clustered = c.rows_built = false;
   const uint32_t B = c.B;
@@ -393,14 +396,16 @@ int otg_cohort_genotype(otg_ctx* ctx, const otg_params* params)
   if ((rc = grow(ctx, c.gt, (na + 1) * 4 * 4)) || (rc = grow(ctx, c.hsd, (na + 1) * 8)) || (rc = grow(ctx, c.ngt, (size_t)(B + 1) * 2 * 4))) return rc;
   HIP_TRY(ctx, hipMemsetAsync(c.ngt.p, 0, (size_t)(B + 1) * 2 * 4, ctx->stream));
   if (B && na) {
+    uint32_t max_len = 0;      // the edit chain sizes its last tier from the longest sequence: the lengths exist on the device only
+    if (metric == OTG_GT_METRIC_EDIT && (rc = otg_device_max_u32(ctx, (const uint32_t*)c.seq_len.p, na, &max_len))) return rc;
     rc = otg_genotype_resident(ctx, params, (const uint8_t*)c.arena.p, (const uint64_t*)c.seq_off.p, (const uint32_t*)c.seq_len.p, (const uint32_t*)c.first.p,
                                (const uint32_t*)c.n_al.p, c.h_n_al.data(), B, (const uint64_t*)c.pair_off.p, c.h_pair_off[B], na, (int32_t*)c.gt.p,
-                               (double*)c.hsd.p, (int32_t*)c.ngt.p);
+                               (double*)c.hsd.p, (int32_t*)c.ngt.p, nullptr, metric, max_len);
     if (rc) return rc;
     std::vector<int32_t> h_err(B);
     HIP_TRY(ctx, hipMemcpyAsync(h_err.data(), (const int32_t*)c.ngt.p + B, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    { float ms = 0; HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1)); ctx->last_kernel_ms = ms; }
+    if ((rc = otg_genotype_metric_finish(ctx, metric, nullptr))) return rc;
     for (uint32_t r = 0; r < B; ++r)
       if (h_err[r]) return otg_fail(ctx, OTG_ERR_CAPACITY, "region %u: %u alleles, more than the clustering workspace was sized for", r, c.h_n_al[r]);
   } else HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

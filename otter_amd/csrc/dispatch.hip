@@ -659,7 +659,7 @@ int cohort_finish_batch(CohortShared& C, otg_ctx* cctx, const Batch& b, const Co
   *step = "genotype";
   auto t0 = Clock::now();
   int rc = otg_cohort_regroup(cctx, ref.arena.data(), ref.arena.size(), ref.off.data(), ref.len.data());
-  if (rc == OTG_OK) rc = otg_cohort_genotype(cctx, &C.P);
+  if (rc == OTG_OK) rc = otg_genotype_cohort_metric(cctx, &C.P, C.j->gt_metric);
   uint32_t na = 0; uint64_t sb = 0;
   if (rc == OTG_OK) rc = otg_cohort_result_sizes(cctx, &na, &sb);
   if (rc != OTG_OK) return rc;
@@ -1087,6 +1087,9 @@ int otg_vcf2mat_files(const otg_vcf2mat_job* job, otg_write_fn write, void* user
 int otg_genotype_files(const otg_genotype_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
 {
   if (!job || !write || !job->bam_path || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "otg_genotype_files: NULL job, writer, BAM or BED path");
+  const bool with_ref = job->fasta_path && job->fasta_path[0];
+  if (with_ref && job->metric != OTG_GT_METRIC_LENGTH && job->metric != OTG_GT_METRIC_EDIT)      // (the length table involves no clustering: no metric to refuse)
+    return otg_fail(nullptr, OTG_ERR_ARG, "otg_genotype_files: unknown genotype metric %u (OTG_GT_METRIC_LENGTH = 0, OTG_GT_METRIC_EDIT = 1)", job->metric);
   const auto t_all = Clock::now();
   otg_job_stats st{};
   Bed bed;
@@ -1101,7 +1104,6 @@ int otg_genotype_files(const otg_genotype_job* job, otg_write_fn write, void* us
   uint32_t n_samples = 0; int32_t ol = 0, orr = 0;
   rc = otg_bam_sample_index(bam.get(), &n_samples, &ol, &orr);                // SampleIndex::init (src/anbamdb.cpp:42-63)
   if (rc != OTG_OK) return rc;
-  const bool with_ref = job->fasta_path && job->fasta_path[0];
   if (with_ref) {
     rc = open_fasta(job->fasta_path, fasta);
     if (rc != OTG_OK) return rc;
@@ -1159,8 +1161,9 @@ int otg_genotype_files(const otg_genotype_job* job, otg_write_fn write, void* us
       gt.resize((size_t)na + 1); gtl.resize((size_t)na + 1); gtk.resize((size_t)na + 1); reps.resize((size_t)na + 1); hsd.resize((size_t)na + 1); ngt.resize((size_t)n + 1);
       if (arena.size() < used + 64) arena.resize(used + 64);
       if (na) {
-        rc = otg_genotype_cluster_batch(ctx.get(), &job->params, arena.data(), used + 64, seq_off.data(), seq_len.data(), first.data(), n_al.data(), n,
-                                        gt.data(), gtl.data(), gtk.data(), hsd.data(), ngt.data(), reps.data());      // anallele_cluster (src/genotype.cpp:138)
+        rc = otg_genotype_cluster_metric_batch(ctx.get(), &job->params, arena.data(), used + 64, seq_off.data(), seq_len.data(), first.data(), n_al.data(), n,
+                                               gt.data(), gtl.data(), gtk.data(), hsd.data(), ngt.data(), reps.data(),      // anallele_cluster (src/genotype.cpp:138)
+                                               (int32_t)job->metric, nullptr, nullptr);
         if (rc != OTG_OK) return otg_fail(nullptr, rc, "otg_genotype_files: %s", ctx_err(ctx.get()).c_str());
       } else std::fill(ngt.begin(), ngt.end(), 0);
       st.ms_hot_path += ms_since(t0);
@@ -1195,6 +1198,8 @@ int otg_cohort_files(const otg_cohort_job* job, otg_write_fn write, void* user, 
   if (job->n_samples == 0 || !job->bam_paths || !job->sample_names) return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: zero samples (n_samples = %u)", job->n_samples);
   if (!job->fasta_path || !job->fasta_path[0]) return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: no reference FASTA (fasta_path): the joint VCF needs the reference alleles");
   if (job->n_devices < 0 || (job->n_devices > 0 && !job->devices)) return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: bad device list");
+  if (job->gt_metric != OTG_GT_METRIC_LENGTH && job->gt_metric != OTG_GT_METRIC_EDIT)
+    return otg_fail(nullptr, OTG_ERR_ARG, "otg_cohort_files: unknown genotype metric %d (OTG_GT_METRIC_LENGTH = 0, OTG_GT_METRIC_EDIT = 1)", job->gt_metric);
   if (job->matrix_write && (job->matrix_k < 1 || job->matrix_k > OTG_KMER_MAX))
     return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--kmer-size' (%d). Needs to be 1 <= x <= %d.", job->matrix_k, OTG_KMER_MAX);
   const uint32_t S = job->n_samples;

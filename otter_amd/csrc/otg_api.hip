@@ -605,11 +605,13 @@ int otg_poa_consensus_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t are
 
 // The launch part of anallele_cluster on device-resident inputs: what otg_genotype_cluster_batch runs behind its uploads and the cohort path
 // (cohort.hip) runs on its regrouped buffers.  d_height (2 x (na + 1) doubles, or NULL): the traced kernels, see genotype_kernel.
+// metric / max_len: under OTG_GT_METRIC_EDIT the first matrix is built from alignments before the kernels (max_len = the longest allele); the
+// caller has passed otg_genotype_metric_fits and calls otg_genotype_metric_finish after waiting for the stream.
 // h_n_alleles is the host copy of d_n (wide routing).  d_gt holds 4 x (na + 1) int32 (gt, gt_l,
 // gt_k, reps), d_ngt 2 x n_regions (n_gt, then the per-region error flags).  ctx->ev0 / ev1 are recorded around the kernels; no synchronisation.
 int otg_genotype_resident(otg_ctx* ctx, const otg_params* params, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len,
                           const uint32_t* d_first, const uint32_t* d_n, const uint32_t* h_n_alleles, uint32_t n_regions, const uint64_t* d_poff,
-                          uint64_t n_pairs, uint64_t na, int32_t* d_gt, double* d_hsd, int32_t* d_ngt, double* d_height)
+                          uint64_t n_pairs, uint64_t na, int32_t* d_gt, double* d_hsd, int32_t* d_ngt, double* d_height, int metric, uint32_t max_len)
 {
   uint32_t a_max = 0;
   std::vector<uint32_t> wide;          // regions above the LDS scratch of the genotype kernel
@@ -619,9 +621,16 @@ int otg_genotype_resident(otg_ctx* ctx, const otg_params* params, const uint8_t*
   }
   int32_t *d_gtl = d_gt + (na + 1), *d_gtk = d_gtl + (na + 1), *d_reps = d_gtk + (na + 1), *d_err = d_ngt + n_regions;
   HIP_TRY(ctx, hipMemsetAsync(d_gt, 0xff, (na + 1) * 4 * 4, ctx->stream));
+  const bool edit = metric == OTG_GT_METRIC_EDIT;
+  if (edit && !ctx->ev2) HIP_TRY(ctx, hipEventCreate(&ctx->ev2));
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  int rc = otg_launch_genotype(ctx, params, d_arena, d_off, d_len, d_first, d_n, n_regions, d_poff, n_pairs, na, a_max, wide.data(), (uint32_t)wide.size(),
-                               d_gt, d_gtl, d_gtk, d_hsd, d_ngt, d_reps, d_err, d_height, d_height ? d_height + (na + 1) : nullptr);
+  int rc = OTG_OK;
+  if (edit) {      // the first matrix from alignments (genotype_edit.hip), into the slot the kernel reads it from; ev2 between the two parts
+    if ((rc = otg_launch_genotype_edit_matrix(ctx, d_arena, d_off, d_len, d_first, d_n, n_regions, d_poff, n_pairs, na, max_len))) return rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
+  }
+  rc = otg_launch_genotype(ctx, params, d_arena, d_off, d_len, d_first, d_n, n_regions, d_poff, n_pairs, na, a_max, wide.data(), (uint32_t)wide.size(),
+                           d_gt, d_gtl, d_gtk, d_hsd, d_ngt, d_reps, d_err, d_height, d_height ? d_height + (na + 1) : nullptr, edit);
   if (rc) return rc;
   HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   return OTG_OK;
@@ -633,9 +642,12 @@ static int genotype_batch_impl(otg_ctx* ctx, const char* who, const otg_params* 
                                const uint64_t* seq_off, const uint32_t* seq_len,
                                const uint32_t* first_allele, const uint32_t* n_alleles, uint32_t n_regions,
                                int32_t* gt_out, int32_t* gt_l_out, int32_t* gt_k_out, double* hsd_out,
-                               int32_t* n_gt_out, int32_t* reps_out, const otg_genotype_trace* trace)
+                               int32_t* n_gt_out, int32_t* reps_out, const otg_genotype_trace* trace,
+                               int metric = OTG_GT_METRIC_LENGTH, double* dist_out = nullptr, uint64_t* n_aligned_out = nullptr)
 {
   if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "%s: no context (no HIP device?)", who);
+  if (n_aligned_out) *n_aligned_out = 0;
+  if (int rc = otg_genotype_metric_fits(ctx, who, metric, 0)) return rc;
   if (n_regions == 0) return OTG_OK;
   if (!params || !seq_arena || !seq_off || !seq_len || !first_allele || !n_alleles || !gt_out || !gt_l_out || !gt_k_out || !hsd_out || !n_gt_out || !reps_out)
     return otg_fail(ctx, OTG_ERR_ARG, "%s: NULL argument", who);
@@ -649,7 +661,12 @@ static int genotype_batch_impl(otg_ctx* ctx, const char* who, const otg_params* 
     uint64_t A = n_alleles[r];
     pair_off[r + 1] = pair_off[r] + A * (A ? A - 1 : 0) / 2;
   }
-  for (uint64_t i = 0; i < na; ++i) if (seq_off[i] + seq_len[i] > arena_bytes) return otg_fail(ctx, OTG_ERR_ARG, "allele %llu: sequence outside the arena", (unsigned long long)i);
+  uint32_t max_len = 0;
+  for (uint64_t i = 0; i < na; ++i) {
+    if (seq_off[i] + seq_len[i] > arena_bytes) return otg_fail(ctx, OTG_ERR_ARG, "allele %llu: sequence outside the arena", (unsigned long long)i);
+    max_len = std::max(max_len, seq_len[i]);
+  }
+  if (int rc = otg_genotype_metric_fits(ctx, who, metric, pair_off[n_regions])) return rc;
   uint8_t* d_arena = (uint8_t*)otg_slot(ctx, SLOT_ARENA, arena_bytes + 64);
   uint64_t* d_off = (uint64_t*)otg_slot(ctx, SLOT_AUX0, (na + 1) * 8);
   uint32_t* d_len = (uint32_t*)otg_slot(ctx, SLOT_AUX1, (na + 1) * 4);
@@ -675,8 +692,16 @@ static int genotype_batch_impl(otg_ctx* ctx, const char* who, const otg_params* 
     HIP_TRY(ctx, hipMalloc((void**)&tb.p, 2 * (na + 1) * 8));
     HIP_TRY(ctx, hipMemsetAsync(tb.p, 0xff, 2 * (na + 1) * 8, ctx->stream));
   }
-  int rc = otg_genotype_resident(ctx, params, d_arena, d_off, d_len, d_first, d_n, n_alleles, n_regions, d_poff, pair_off[n_regions], na, d_gt, d_hsd, d_ngt, tb.p);
+  int rc = otg_genotype_resident(ctx, params, d_arena, d_off, d_len, d_first, d_n, n_alleles, n_regions, d_poff, pair_off[n_regions], na, d_gt, d_hsd, d_ngt, tb.p,
+                                 metric, max_len);
   if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+  bool finished = false;
+  if (metric == OTG_GT_METRIC_EDIT) {      // a pair the chain gave up fails the call before anything is copied out: no partial results
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc2 = otg_genotype_metric_finish(ctx, metric, n_aligned_out)) return rc2;
+    finished = true;
+  }
+  if (dist_out && pair_off[n_regions]) HIP_TRY(ctx, hipMemcpyAsync(dist_out, ctx->pool[SLOT_P20].p, pair_off[n_regions] * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (trace) {
     const uint64_t np = pair_off[n_regions];
     if (np) HIP_TRY(ctx, hipMemcpyAsync(trace->dl, ctx->pool[SLOT_P20].p, np * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -695,7 +720,7 @@ static int genotype_batch_impl(otg_ctx* ctx, const char* who, const otg_params* 
   HIP_TRY(ctx, hipMemcpyAsync(n_gt_out, d_ngt, (size_t)n_regions * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(h_err.data(), d_err, (size_t)n_regions * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  { float ms = 0; HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1)); ctx->last_kernel_ms = ms; }
+  if (!finished) { if (int rc2 = otg_genotype_metric_finish(ctx, metric, n_aligned_out)) return rc2; }
   for (uint32_t r = 0; r < n_regions; ++r)
     if (h_err[r]) return otg_fail(ctx, OTG_ERR_CAPACITY, "region %u: %u alleles, more than the clustering workspace was sized for", r, n_alleles[r]);
   return OTG_OK;
@@ -722,6 +747,24 @@ int otg_genotype_cluster_trace_batch(otg_ctx* ctx, const otg_params* params, con
   if (!trace) return otg_fail(ctx, OTG_ERR_ARG, "otg_genotype_cluster_trace_batch: no trace");
   return genotype_batch_impl(ctx, "otg_genotype_cluster_trace_batch", params, seq_arena, arena_bytes, seq_off, seq_len, first_allele, n_alleles, n_regions,
                              gt_out, gt_l_out, gt_k_out, hsd_out, n_gt_out, reps_out, trace);
+}
+
+int otg_genotype_cluster_metric_batch(otg_ctx* ctx, const otg_params* params, const uint8_t* seq_arena, uint64_t arena_bytes,
+                                      const uint64_t* seq_off, const uint32_t* seq_len,
+                                      const uint32_t* first_allele, const uint32_t* n_alleles, uint32_t n_regions,
+                                      int32_t* gt_out, int32_t* gt_l_out, int32_t* gt_k_out, double* hsd_out,
+                                      int32_t* n_gt_out, int32_t* reps_out, int32_t metric, double* dist_out, uint64_t* n_aligned_out)
+{
+  return genotype_batch_impl(ctx, "otg_genotype_cluster_metric_batch", params, seq_arena, arena_bytes, seq_off, seq_len, first_allele, n_alleles, n_regions,
+                             gt_out, gt_l_out, gt_k_out, hsd_out, n_gt_out, reps_out, nullptr, metric, dist_out, n_aligned_out);
+}
+
+int otg_genotype_metric_last_ms(otg_ctx* ctx, double* align_ms, double* cluster_ms)
+{
+  if (!ctx) return otg_fail(nullptr, OTG_ERR_ARG, "otg_genotype_metric_last_ms: NULL context");
+  if (align_ms) *align_ms = ctx->last_gt_align_ms;
+  if (cluster_ms) *cluster_ms = ctx->last_gt_cluster_ms;
+  return OTG_OK;
 }
 
 int otg_last_kernel_ms(otg_ctx* ctx, double* ms)

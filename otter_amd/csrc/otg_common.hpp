@@ -45,6 +45,11 @@ struct otg_ctx {
   double last_kmer_count_ms = 0.0, last_kmer_epi_ms = 0.0;  // HIP-event times of the latest otg_kmer_usage_batch (otg_kmer_usage_last_ms)
   hipEvent_t ev2 = nullptr;                       // third timing event, created on first use (kmer_usage.hip)
   double last_kernel_ms = 0.0;                    // HIP-event time of the kernels of the latest operator-level call that reports one (otg_last_kernel_ms)
+  // the latest genotype clustering with a metric (genotype_edit.hip): times of its two parts (otg_genotype_metric_last_ms), whether the edit
+  // matrix was built, and where its counters lie in SLOT_GTE_CLS
+  double last_gt_align_ms = 0.0, last_gt_cluster_ms = 0.0;
+  bool gt_edit_ran = false;
+  size_t gt_edit_cnt_off = 0;
   // aligner heuristic of the L1 calls and of the running pipeline (otg_set_heuristic / otg_params.heuristic; wfa_adaptive.hip)
   int heur_strategy = OTG_HEURISTIC_NONE, heur_min_wf_len = 10, heur_max_dist = 50, heur_steps = 1;
   // What the latest tier chain on this context left behind, for otg_affine_last_routing: which chain it was (the byte offset of its group in
@@ -90,6 +95,7 @@ enum {
   SLOT_P20, SLOT_P21, SLOT_P22, SLOT_P23, SLOT_P24, SLOT_P25, SLOT_P26, SLOT_P27, SLOT_P28, SLOT_P29,
   SLOT_KMER_SEQ, SLOT_KMER_META, SLOT_KMER_HIST, SLOT_KMER_OUT,     // otg_kmer_usage_batch (kmer_usage.hip); OUT stays valid for the device results
   SLOT_KMER_BLK,                                                    // tier L of otg_kmer_usage_resident: gc counts and the workgroup prefix
+  SLOT_GTE_CLS, SLOT_GTE_TASKS, SLOT_GTE_SCORES, SLOT_GTE_DEN, SLOT_GTE_TODO,   // the edit metric of the genotype clustering (genotype_edit.hip)
   SLOT_COUNT
 };
 
@@ -293,7 +299,18 @@ int otg_launch_poa(otg_ctx* ctx, const uint8_t* d_seq_arena, const uint8_t* d_ci
 // otg_api.hip: anallele_cluster on device-resident inputs (memset of the outputs, ev0, the kernels below, ev1); see its definition
 int otg_genotype_resident(otg_ctx* ctx, const otg_params* params, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len,
                           const uint32_t* d_first, const uint32_t* d_n, const uint32_t* h_n_alleles, uint32_t n_regions, const uint64_t* d_poff,
-                          uint64_t n_pairs, uint64_t na, int32_t* d_gt, double* d_hsd, int32_t* d_ngt, double* d_height = nullptr);
+                          uint64_t n_pairs, uint64_t na, int32_t* d_gt, double* d_hsd, int32_t* d_ngt, double* d_height = nullptr,
+                          int metric = OTG_GT_METRIC_LENGTH, uint32_t max_len = 0);
+
+// genotype_edit.hip — the first matrix of anallele_cluster under OTG_GT_METRIC_EDIT, see the definitions: the argument check of the metric
+// entry points (unknown metric: OTG_ERR_ARG; pair slots beyond 2^32: OTG_ERR_CAPACITY, nothing allocated), the longest of n lengths on the
+// device (synchronises), the launch (allele classes, pair tasks, the exact edit chain, the fan-out into SLOT_P20) and what the host reads
+// once the stream has been waited for (times, alignments run, OTG_ERR_CAPACITY when the chain gave a pair up)
+int otg_genotype_metric_fits(otg_ctx* ctx, const char* who, int metric, uint64_t n_pairs);
+int otg_device_max_u32(otg_ctx* ctx, const uint32_t* d_v, uint64_t n, uint32_t* out);
+int otg_launch_genotype_edit_matrix(otg_ctx* ctx, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, const uint32_t* d_first,
+                                    const uint32_t* d_n, uint32_t n_regions, const uint64_t* d_poff, uint64_t n_pairs, uint64_t na, uint32_t max_len);
+int otg_genotype_metric_finish(otg_ctx* ctx, int metric, uint64_t* n_aligned);
 
 // kmer_usage.hip: the workspace refusal of otg_kmer_usage_batch (OTG_ERR_CAPACITY, nothing allocated) and its launch part on device-resident
 // rows; see the definitions
@@ -307,4 +324,4 @@ int otg_launch_genotype(otg_ctx* ctx, const otg_params* P, const uint8_t* d_aren
                         const uint64_t* d_pair_off, uint64_t n_pairs_total, uint64_t n_alleles_total, uint32_t a_max,
                         const uint32_t* h_wide, uint32_t n_wide,
                         int32_t* d_gt, int32_t* d_gtl, int32_t* d_gtk, double* d_hsd, int32_t* d_ngt, int32_t* d_reps,
-                        int32_t* d_err, double* d_height_l = nullptr, double* d_height_k = nullptr);
+                        int32_t* d_err, double* d_height_l = nullptr, double* d_height_k = nullptr, bool dl_given = false);

@@ -2,9 +2,10 @@
 // `otter genotype` over their alleles in one pass (otg_cohort_files), the alleles never leaving the device in between.  Host C++ only.
 //   otter_cohort -b regions.bed -r ref.fa [the assemble options of otter_assemble: --haps -p -l -o L[,R] -a N -m Q -q RQ -c COV -F f -A len,f -e err
 //                -h bw[,len,bw] -f flank -s sim -t threads --batch N --gpus 0,1,.. --wfa-heuristic ..] [-E gt-max-error] [-S gt-max-cosdis]
-//                [--alleles-prefix P [--alleles-bam]] [--matrix FILE [-k K]] NAME=reads.bam ...
+//                [--gt-metric length|edit] [--alleles-prefix P [--alleles-bam]] [--matrix FILE [-k K]] NAME=reads.bam ...
 // The VCF goes to stdout.  NAME is the sample's `-R` and its VCF column.  --alleles-prefix P also writes the allele records of every sample, as
 // `otter assemble -R NAME` prints them, to P<NAME>.sam; with --alleles-bam to P<NAME>.bam + P<NAME>.bam.bai instead (otg_bam_sink).
+// --gt-metric edit clusters the alleles by exact edit distance instead of the length ratio (OTG_GT_METRIC_EDIT); length is the default.
 // --matrix FILE also writes the k-mer usage matrix of the joint alleles, what `otter vcf2mat -k K` prints for the VCF (K defaults to 3).
 #include <cstdio>
 #include <cstdlib>
@@ -52,6 +53,12 @@ int main(int argc, char** argv)
     else if (a == "-r" || a == "--reference") ref = val();
     else if (a == "-E" || a == "--gt-max-error") job.params.gt_max_error = atof(val().c_str());
     else if (a == "-S" || a == "--gt-max-cosdis") job.params.gt_max_cosdis = atof(val().c_str());
+    else if (a == "--gt-metric") {
+      const std::string m = val();
+      if (m == "length") job.gt_metric = OTG_GT_METRIC_LENGTH;
+      else if (m == "edit") job.gt_metric = OTG_GT_METRIC_EDIT;
+      else { fprintf(stderr, "[ERROR] --gt-metric length | edit\n"); return 1; }
+    }
     else if (a == "--alleles-prefix") prefix = val();
     else if (a == "--alleles-bam") alleles_bam = true;
     else if (a == "--matrix") matrix = val();
