@@ -871,6 +871,75 @@ typedef struct otg_cohort_job {
 int otg_cohort_files(const otg_cohort_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
 
 /* ---------------------------------------------------------------------------------------------
+ * Tandem-repeat motif annotation of alleles: which unit, how many copies, how pure.  The reference has no counterpart; this is the
+ * definition (all integers).  For a sequence s of length L, 1 <= max_period <= OTG_MOTIF_MAX_PERIOD and a slack in per mille,
+ * 0 <= slack <= 999:
+ *   1. c[i] = 0..3 for A/a C/c G/g T/t, 4 for any other byte (the table of otg_kmer_usage_batch);
+ *   2. P = min(max_period, L / 2);
+ *   3. m(p) = #{ i in [0, L - p) : c[i] == c[i + p] and c[i] < 4 } for p in 1..P;
+ *   4. best = 1, then for p = 2..P ascending: best = p when m(p) (L - best) > m(best) (L - p) (strict: ties keep the smaller period);
+ *   5. period = the smallest p in 1..best with m(p) (L - best) 1000 >= (1000 - slack) m(best) (L - p).  (Without the slack one substitution
+ *      in (CAG)20 makes p = 30 the best period: its window avoids the mismatch twice.)
+ *   6. P == 0 or m(best) == 0: period = matches = compared = best_period = 0 and the unit is empty (L < 2, an all-N allele, "AC");
+ *   7. unit[j], j < period: the majority base over the ACGT bytes at i = j (mod period); ties to the lower code (A < C < G < T); a phase
+ *      without an ACGT byte gives 'N';
+ *   8. the unit is reported as its lexicographically smallest rotation by byte value, ties to the smallest rotation offset;
+ *   9. matches = m(period), compared = L - period, best_period = best; copies = L / period and purity = matches / compared are the caller's;
+ *  10. L > OTG_MOTIF_MAX_LEN (the bound that keeps step 5 inside 64 bits): period = 0 and flags = OTG_MOTIF_TOO_LONG; the batch does not fail.
+ * A shifted self-comparison is not indel-tolerant: the targets are assembled alleles (consensus sequences), not noisy reads.
+ *   otg_motif_batch           allele i is seq_arena[seq_off[i] .. + seq_len[i]).  out: n records; unit i: period bytes at unit_out + i * unit_stride
+ *                             (the rest of a slot is zero).  unit_stride < min(max_period, max(seq_len) / 2), max_period or slack out of range:
+ *                             OTG_ERR_ARG.  NULL outputs leave the results in HBM.  At most 2^24 alleles per call (OTG_ERR_CAPACITY);
+ *   otg_motif_device_results  device pointers of the latest results on this context (n records, then n x unit_stride unit bytes), valid until
+ *                             the next motif call on the context or otg_destroy; every output is nullable;
+ *   otg_motif_last_ms         HIP-event times (ms) of the latest motif call: count_ms = the pack and match-count kernels, reduce_ms = the reduce
+ *                             and unit kernel;
+ *   otg_motif_cohort          the same kernels over rows [row_begin, row_begin + n) of the row list of otg_kmer_cohort_rows, the alleles read in the
+ *                             regrouped cohort arena in place (as otg_kmer_cohort_usage: not clustered or a range past *n_rows is OTG_ERR_ARG; a
+ *                             zero-length allele is the row of "N");
+ *   otg_motif_emit            per allele a of record r the row region \t i \t seq_len[a] \t period \t unit \t copies \t purity \n with
+ *                             a = records[r].first_allele + i: unit "." when period == 0, copies "%.2f" of seq_len / period (0.00 when period
+ *                             == 0), purity "%.4f" of matches / compared (0.0000 when period == 0).  Buffer protocol of otg_emit_alleles.
+ * The device sweeps all periods of an allele with planes of 32 bases per word; OTG_MOTIF_WIDE=1 in the environment (read once per process)
+ * sends every allele through the tier that keeps the planes in HBM.
+ * ------------------------------------------------------------------------------------------- */
+#define OTG_MOTIF_MAX_PERIOD 4096
+#define OTG_MOTIF_MAX_LEN    1048575
+#define OTG_MOTIF_LDS_LEN    32768       /* alleles up to this length keep their planes in LDS, longer ones in HBM */
+#define OTG_MOTIF_TOO_LONG   1u          /* otg_motif.flags */
+typedef struct otg_motif {
+  uint32_t period;               /* 0: no repeat found                                               */
+  uint32_t matches;              /* m(period)                                                        */
+  uint32_t compared;             /* L - period                                                       */
+  uint32_t best_period;          /* the period of the highest match ratio (step 4)                   */
+  uint32_t flags;                /* OTG_MOTIF_TOO_LONG                                               */
+  uint32_t reserved;
+} otg_motif;
+int otg_motif_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_bytes, const uint64_t* seq_off, const uint32_t* seq_len,
+                    uint32_t n, uint32_t max_period, uint32_t slack, otg_motif* out, uint8_t* unit_out, uint32_t unit_stride);
+int otg_motif_device_results(otg_ctx* ctx, uint32_t* n, const otg_motif** records, const uint8_t** units, uint32_t* unit_stride);
+int otg_motif_last_ms(otg_ctx* ctx, double* count_ms, double* reduce_ms);
+int otg_motif_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, uint32_t max_period, uint32_t slack, otg_motif* out, uint8_t* unit_out,
+                     uint32_t unit_stride);
+int otg_motif_emit(const otg_vcf_record* records, uint32_t n_records, const char* region_arena, const uint32_t* seq_len, const otg_motif* motifs,
+                   const uint8_t* units, uint32_t unit_stride, char* out, uint64_t out_capacity, uint64_t* out_len);
+/* One row of otg_motif_emit per allele of a VCF, in file order: built on otg_vcf_open / otg_vcf_read_alleles and the batching of
+ * otg_vcf2mat_files (same record and allele rules; the BED is parsed and filters nothing; reading the next batch overlaps the device pass and
+ * the emit of the current one).  max_period and slack as above; out-of-range values are OTG_ERR_ARG with the message the tool
+ * prints.  stats as otg_vcf2mat_files. */
+typedef struct otg_motifs_job {
+  const char* vcf_path;          /* positional <VCF[.GZ]>                                            */
+  const char* bed_path;          /* -b: required, parsed, unused                                     */
+  uint32_t    max_period;        /* -p: 1..OTG_MOTIF_MAX_PERIOD (the tool's default: 256)            */
+  uint32_t    slack;             /* --slack: 0..999 per mille (the tool's default: 50)               */
+  int32_t     threads;           /* -t: host threads of the emit                                     */
+  int32_t     device;            /* HIP device ordinal                                               */
+  uint32_t    batch_alleles;     /* alleles per batch, 0 = 65536                                     */
+  uint32_t    reserved;
+} otg_motifs_job;
+int otg_motifs_files(const otg_motifs_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
+
+/* ---------------------------------------------------------------------------------------------
  * Indexed allele BAMs from the product's own SAM text.  Every writer above emits SAM text and every reader wants a
  * coordinate-sorted BAM with its `.bai`; the reference's workflow goes through `samtools view -bh | samtools sort`, `samtools index` and
  * `samtools merge -pco` in between.  Host code (zlib + threads), no device work.

@@ -9,3 +9,4 @@ from ._lib import emit_vcf_header, emit_vcf_lines, emit_genotype_lengths, genoty
 from ._lib import vcf_read_alleles, vcf2mat_emit, vcf2mat_files, cohort_files, BamSink, merge_bams  # noqa: F401
 from ._lib import exp_host, exp_probe  # noqa: F401
 from .abi import default_params  # noqa: F401
+from ._lib import motif_emit, motifs_files  # noqa: F401

@@ -28,6 +28,7 @@ EXPORTS = [
     "otg_comm_unique_id", "otg_comm_create", "otg_comm_destroy", "otg_gather_sizes", "otg_gather_records",
     "otg_exp_probe_mismatches", "otg_exp_probe", "otg_exp_host", "otg_exp_device", "otg_cluster_trace_batch", "otg_genotype_cluster_trace_batch",
     "otg_genotype_cluster_metric_batch", "otg_genotype_metric_last_ms", "otg_genotype_cohort_metric",
+    "otg_motif_batch", "otg_motif_device_results", "otg_motif_last_ms", "otg_motif_cohort", "otg_motif_emit", "otg_motifs_files",
 ]
 
 _lib = None
@@ -265,13 +266,48 @@ class Context:
                 self.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (int(ptr), False), "version": 2, "strides": None}
 
         if 0 in shape:
-            return torch.zeros(shape, dtype={"<f8": torch.float64, "<i4": torch.int32}[typestr], device=dev)
+            return torch.zeros(shape, dtype={"<f8": torch.float64, "<i4": torch.int32, "|u1": torch.uint8}[typestr], device=dev)
         return torch.as_tensor(_Span(ptr, shape), device=dev)
 
     def kmer_usage_last_ms(self):
         """(counting ms, epilogue ms) of the latest kmer_usage_batch (HIP events; k <= 7 counts and finishes in one kernel)."""
         a, b = C.c_double(0), C.c_double(0)
         self._check(self._L.otg_kmer_usage_last_ms(self._h, C.byref(a), C.byref(b)), "otg_kmer_usage_last_ms")
+        return a.value, b.value
+
+    def motif_batch(self, arena, seq_off, seq_len, max_period=256, slack=50, device_tensor=False):
+        """otg_motif_batch: per allele the tandem-repeat period, match counts and unit (include/otter_gpu.h states the rule) ->
+        (records [n] of abi.motif_dt, units [n, stride] uint8 with unit i in units[i, :records[i]["period"]], zero behind it) as numpy arrays,
+        stride = max(1, min(max_period, longest allele // 2)); or with device_tensor=True as torch tensors on this context's device that wrap
+        the results in HBM without a copy (records as int32 [n, 6] in the field order of abi.motif_dt, units as uint8 [n, stride]; valid
+        until the next motif call on this context)."""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+        ln = np.ascontiguousarray(seq_len, dtype=np.uint32)
+        n = len(ln)
+        stride = max(1, min(int(max_period), int(ln.max()) // 2 if n else 0))
+        rec = np.zeros(n, dtype=abi.motif_dt)
+        units = np.zeros((n, stride), dtype=np.uint8)
+        rc = self._L.otg_motif_batch(self._h, abi.ptr(arena), C.c_uint64(arena.size), abi.ptr(off), abi.ptr(ln), C.c_uint32(n),
+                                     C.c_uint32(max_period), C.c_uint32(slack), None if device_tensor else abi.ptr(rec),
+                                     None if device_tensor else abi.ptr(units), C.c_uint32(stride))
+        self._check(rc, "otg_motif_batch")
+        return self._motif_device_results(n, stride) if device_tensor else (rec, units)
+
+    def _motif_device_results(self, n, stride):
+        import torch
+        if n == 0:
+            dev = torch.device("cuda", self.device)
+            return torch.zeros((0, 6), dtype=torch.int32, device=dev), torch.zeros((0, stride), dtype=torch.uint8, device=dev)
+        m, s, pr, pu = C.c_uint32(0), C.c_uint32(0), C.c_void_p(), C.c_void_p()
+        self._check(self._L.otg_motif_device_results(self._h, C.byref(m), C.byref(pr), C.byref(pu), C.byref(s)), "otg_motif_device_results")
+        assert (m.value, s.value) == (n, stride)
+        return self._wrap_device(pr.value, (n, 6), "<i4"), self._wrap_device(pu.value, (n, stride), "|u1")
+
+    def motif_last_ms(self):
+        """(pack and match-count ms, reduce and unit ms) of the latest motif call on this context (HIP events)."""
+        a, b = C.c_double(0), C.c_double(0)
+        self._check(self._L.otg_motif_last_ms(self._h, C.byref(a), C.byref(b)), "otg_motif_last_ms")
         return a.value, b.value
 
     def affine_align_batch(self, arena, tasks, x=4, o=6, e=2, want_cells=False):
@@ -596,6 +632,23 @@ class Context:
         self._check(self._L.otg_kmer_cohort_usage(self._h, C.c_int32(k), C.c_uint32(row_begin), C.c_uint32(n), abi.ptr(usage), abi.ptr(gc), abi.ptr(hsd)),
                     "otg_kmer_cohort_usage")
         return usage, gc, hsd
+
+    def cohort_motifs(self, row_begin=0, n=None, max_period=256, slack=50, unit_stride=None, device_tensor=False):
+        """otg_motif_cohort: the motif annotation of rows [row_begin, row_begin + n) of the row list (n=None: to the end), the alleles read in
+        the cohort arena in place -> (records, units) as motif_batch returns them.  unit_stride=None: max_period (the row lengths are on the
+        device only)."""
+        if n is None:
+            total = C.c_uint32(0)
+            self._check(self._L.otg_kmer_cohort_rows(self._h, C.byref(total), None, None, None), "otg_kmer_cohort_rows")
+            n = max(0, total.value - int(row_begin))
+        n = int(n)
+        stride = int(max_period) if unit_stride is None else int(unit_stride)
+        rec = np.zeros(n, dtype=abi.motif_dt)
+        units = np.zeros((n, max(stride, 1)), dtype=np.uint8)
+        rc = self._L.otg_motif_cohort(self._h, C.c_uint32(row_begin), C.c_uint32(n), C.c_uint32(max_period), C.c_uint32(slack),
+                                      None if device_tensor else abi.ptr(rec), None if device_tensor else abi.ptr(units), C.c_uint32(stride))
+        self._check(rc, "otg_motif_cohort")
+        return self._motif_device_results(n, stride) if device_tensor else (rec, units[:, :stride])
 
     def cohort_end(self):
         self._check(self._L.otg_cohort_end(self._h), "otg_cohort_end")
@@ -1345,3 +1398,35 @@ def vcf2mat_files(vcf, bed, k=3, threads=1, device=0, batch_alleles=0):
     job.vcf_path = vcf.encode(); job.bed_path = bed.encode()
     job.k = k; job.threads = threads; job.device = device; job.batch_alleles = batch_alleles
     return _run_files_job("otg_vcf2mat_files", job, abi.Vcf2matJob)
+
+
+def motif_emit(records, regions, seq_len, motifs, units):
+    """otg_motif_emit: the rows of otter_motifs for the records (vcf_record_dt), per-allele motif records (motif_dt) and units [n, stride] -> text bytes."""
+    L = load()
+    records = np.ascontiguousarray(records, dtype=abi.vcf_record_dt)
+    seq_len = np.ascontiguousarray(seq_len, dtype=np.uint32)
+    motifs = np.ascontiguousarray(motifs, dtype=abi.motif_dt)
+    units = np.ascontiguousarray(units, dtype=np.uint8)
+    stride = units.shape[1] if units.ndim == 2 else 0
+    if units.size == 0:
+        units = np.zeros(1, dtype=np.uint8)
+    reg = np.frombuffer(regions + b"\0", dtype=np.uint8)
+    need = C.c_uint64(0)
+    args = lambda out, cap: (abi.ptr(records), C.c_uint32(len(records)), abi.ptr(reg), abi.ptr(seq_len), abi.ptr(motifs), abi.ptr(units),
+                             C.c_uint32(stride), out, C.c_uint64(cap), C.byref(need))
+    rc = L.otg_motif_emit(*args(None, 0))
+    if rc not in (0, abi.OTG_ERR_CAPACITY):
+        raise OtterGpuError("otg_motif_emit failed (%d): %s" % (rc, _err(L)))
+    out = C.create_string_buffer(need.value + 1)
+    rc = L.otg_motif_emit(*args(out, need.value))
+    if rc != 0:
+        raise OtterGpuError("otg_motif_emit failed (%d): %s" % (rc, _err(L)))
+    return out.raw[:need.value]
+
+
+def motifs_files(vcf, bed, max_period=256, slack=50, threads=1, device=0, batch_alleles=0):
+    """otg_motifs_files: the motif annotation of every allele of a VCF (plain, gzip or BGZF) as text.  Returns (text bytes, stats dict)."""
+    job = abi.MotifsJob()
+    job.vcf_path = vcf.encode(); job.bed_path = bed.encode()
+    job.max_period = max_period; job.slack = slack; job.threads = threads; job.device = device; job.batch_alleles = batch_alleles
+    return _run_files_job("otg_motifs_files", job, abi.MotifsJob)

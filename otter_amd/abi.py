@@ -219,6 +219,21 @@ vcf_record_dt = np.dtype([("region_off", np.uint64), ("region_len", np.uint32), 
 assert vcf_record_dt.itemsize == 24
 KMER_MAX = 12
 
+# otg_motif (include/otter_gpu.h) and the bounds of the motif annotation
+motif_dt = np.dtype([("period", np.uint32), ("matches", np.uint32), ("compared", np.uint32), ("best_period", np.uint32), ("flags", np.uint32),
+                     ("reserved", np.uint32)])
+assert motif_dt.itemsize == 24
+MOTIF_MAX_PERIOD = 4096
+MOTIF_MAX_LEN = 1048575
+MOTIF_LDS_LEN = 32768
+MOTIF_TOO_LONG = 1
+
+
+class MotifsJob(C.Structure):
+    """otg_motifs_job (include/otter_gpu.h)."""
+    _fields_ = [("vcf_path", C.c_char_p), ("bed_path", C.c_char_p), ("max_period", C.c_uint32), ("slack", C.c_uint32), ("threads", C.c_int32),
+                ("device", C.c_int32), ("batch_alleles", C.c_uint32), ("reserved", C.c_uint32)]
+
 
 class JobStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_regions", "n_regions_ok", "n_regions_skipped", "n_reads", "n_alleles", "input_bytes", "output_bytes")] + \

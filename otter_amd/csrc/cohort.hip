@@ -501,6 +501,23 @@ int otg_kmer_cohort_usage(otg_ctx* ctx, int32_t k, uint32_t row_begin, uint32_t 
                                  nullptr, n, k, usage_out, gc_out, hsd_out);
 }
 
+int otg_motif_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, uint32_t max_period, uint32_t slack, otg_motif* out, uint8_t* unit_out, uint32_t unit_stride)
+{
+  Cohort* cp = cohort_of(ctx, "otg_motif_cohort");
+  if (!cp) return ctx ? OTG_ERR_ARG : OTG_ERR_NO_DEVICE;
+  Cohort& c = *cp;
+  if (!c.clustered) return otg_fail(ctx, OTG_ERR_ARG, "otg_motif_cohort: the batch has not been clustered (otg_cohort_genotype)");
+  if (int rc = otg_motif_args(ctx, "otg_motif_cohort", max_period, slack)) return rc;
+  if (int rc = cohort_build_rows(ctx, c, "otg_motif_cohort")) return rc;
+  if ((uint64_t)row_begin + n > c.n_rows) return otg_fail(ctx, OTG_ERR_ARG, "otg_motif_cohort: rows %u .. %llu of %u", row_begin, (unsigned long long)row_begin + n, c.n_rows);
+  uint32_t max_len = 0;      // the row lengths exist on the device only
+  if (n)
+    if (int rc = otg_device_max_u32(ctx, (const uint32_t*)c.row_len.p + row_begin, n, &max_len)) return rc;
+  if (int rc = otg_motif_stride_fits(ctx, "otg_motif_cohort", max_len, max_period, unit_stride)) return rc;
+  return otg_motif_resident(ctx, "otg_motif_cohort", (const uint8_t*)c.arena.p, (const uint64_t*)c.row_off.p + row_begin, (const uint32_t*)c.row_len.p + row_begin, n,
+                            max_period, slack, out, unit_out, unit_stride);
+}
+
 int otg_cohort_end(otg_ctx* ctx)
 {
   if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_cohort_end: no context");

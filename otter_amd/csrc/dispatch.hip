@@ -15,6 +15,7 @@
 #include "otg_compare.hpp"
 #include "otg_dispatch_queue.hpp"
 #include "otg_vcf2mat.hpp"
+#include "otg_motif.hpp"
 #include <cmath>
 #include <algorithm>
 #include <atomic>
@@ -805,6 +806,89 @@ void cohort_shard_worker(CohortShared& C, int device, uint32_t a, uint32_t bnd, 
   for (int t = 0; t < n_gpu_threads; ++t) { M.st.ms_hot_path += ms_gpu[t]; M.st.ms_emit += ms_emit[t]; }
 }
 
+// One row of text per allele of a VCF, from a file to text: what otg_vcf2mat_files and otg_motifs_files share.  The BED is parsed and filters
+// nothing (parse_bed_file, src/vcf2mat.cpp:50-51).  Two batches in flight: while the alleles of one are on the device (on_device(ctx, batch),
+// which keeps its results) and its rows are formatted by `threads` host threads (rows(text, batch, first record, records): contiguous record
+// ranges with about equal allele counts, written in file order), the next one is read on a host thread.  A batch holds at most `per` alleles;
+// a record with more grows the buffers and goes through whole (the device call then reports its workspace).
+struct VcfBatch {
+  std::vector<otg_vcf_record> rec; std::vector<char> regions; std::vector<uint64_t> off; std::vector<uint32_t> len; std::vector<uint8_t> seqs;
+  uint32_t nr = 0, na = 0; uint64_t ru = 0, au = 0, bytes = 0; int rc = OTG_OK; double ms = 0; std::string err;
+};
+
+template <class OnDevice, class Rows>
+int vcf_allele_job(const char* who, const char* vcf_path, const char* bed_path, int device, uint64_t per, int threads, otg_write_fn write, void* user,
+                   otg_job_stats* stats, OnDevice on_device, Rows rows)
+{
+  const auto t_all = Clock::now();
+  otg_job_stats st{};
+  {
+    Bed bed;
+    const int rb = load_bed(bed_path, bed);
+    if (rb != OTG_OK) return rb;
+  }
+  VcfPtr vcf;
+  int rc = open_vcf(vcf_path, vcf);
+  if (rc != OTG_OK) return rc;
+  const PooledCtx ctx = acquire_ctx(device);
+  if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "%s: %s", who, last_err().c_str());
+  per = std::max<uint64_t>(1, std::min<uint64_t>(per, 1ull << 24));
+  if (threads < 1) threads = 1;
+  auto read_into = [&](VcfBatch& B) {
+    const auto t0 = Clock::now();
+    B.bytes = 0;
+    for (;;) {
+      B.rc = otg_vcf_read_alleles(vcf.get(), B.rec.data(), (uint32_t)B.rec.size(), &B.nr, B.regions.data(), B.regions.size(), &B.ru, B.off.data(), B.len.data(),
+                                  (uint32_t)B.off.size(), &B.na, B.seqs.data(), B.seqs.size(), &B.au, &B.bytes);
+      if (B.rc != OTG_ERR_CAPACITY) break;
+      // one record larger than the buffers: grow them to hold it
+      if (B.na > B.off.size()) { B.off.resize(B.na); B.len.resize(B.na); }
+      if (B.ru > B.regions.size()) B.regions.resize(B.ru);
+      if (B.au > B.seqs.size()) B.seqs.resize(B.au);
+    }
+    if (B.rc != OTG_OK) { B.err = last_err(); B.nr = 0; }
+    B.ms = ms_since(t0);
+  };
+  std::vector<std::string> parts((size_t)threads);
+  TwoInFlight<VcfBatch> flight;
+  for (VcfBatch& B : flight) { B.rec.resize(per); B.off.resize(per); B.len.resize(per); B.regions.resize(1 << 20); B.seqs.resize(64ull << 20); }
+  read_into(flight.current());
+  for (;; flight.advance()) {
+    VcfBatch& B = flight.current();
+    st.ms_ingest += B.ms; st.input_bytes += B.bytes;
+    if (B.rc != OTG_OK) return otg_fail(nullptr, B.rc, "%s: %s", who, B.err.c_str());
+    if (B.nr == 0) break;
+    flight.prefetch(read_into);
+    st.n_regions += B.nr; st.n_alleles += B.na;
+    auto t0 = Clock::now();
+    rc = on_device(ctx.get(), B);
+    if (rc != OTG_OK) return otg_fail(nullptr, rc, "%s: %s", who, ctx_err(ctx.get()).c_str());
+    st.ms_hot_path += ms_since(t0);
+    t0 = Clock::now();
+    std::vector<uint32_t> cut((size_t)threads + 1, B.nr);
+    cut[0] = 0;
+    for (uint32_t r = 0, t = 1; r < B.nr && t < (uint32_t)threads; ++r)
+      if ((uint64_t)B.rec[r].first_allele * threads >= (uint64_t)B.na * t) cut[t++] = r;
+    for (int t = 1; t <= threads; ++t) cut[t] = std::max(cut[t], cut[t - 1]);
+    {
+      std::vector<std::thread> pool;
+      for (int t = 0; t < threads; ++t) {
+        parts[t].clear();
+        if (cut[t + 1] > cut[t]) pool.emplace_back([&, t] { rows(parts[t], B, cut[t], cut[t + 1] - cut[t]); });
+      }
+      for (auto& th : pool) th.join();
+    }
+    st.ms_emit += ms_since(t0);
+    for (int t = 0; t < threads; ++t) {
+      if (!parts[t].empty() && write(user, parts[t].data(), parts[t].size()) != 0) return otg_fail(nullptr, OTG_ERR_ARG, "%s: the writer failed", who);
+      st.output_bytes += parts[t].size();
+    }
+  }
+  st.ms_total = ms_since(t_all); st.n_devices = 1; st.n_regions_ok = st.n_regions;
+  if (stats) *stats = st;
+  return OTG_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -990,95 +1074,51 @@ int otg_compare_files(const otg_compare_job* job, otg_write_fn write, void* user
   return OTG_OK;
 }
 
-// `otter vcf2mat` from a file to text — vcf2mat() (src/vcf2mat.cpp:48-77).  Two batches in flight: while the alleles of one are counted on
-// the device and its rows formatted by the host threads, the next one is read on a host thread.  Batches are bounded by alleles and by the
+// `otter vcf2mat` from a file to text — vcf2mat() (src/vcf2mat.cpp:48-77), on vcf_allele_job.  Batches are bounded by alleles and by the
 // bytes of their rows (a row is 4^k+1 doubles: 134 MB at k = 12).
 int otg_vcf2mat_files(const otg_vcf2mat_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
 {
   if (!job || !write || !job->vcf_path || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "otg_vcf2mat_files: NULL job, writer, VCF or BED path");
   const int k = job->k;
   if (k < 1 || k > OTG_KMER_MAX) return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--kmer-size' (%d). Needs to be 1 <= x <= %d.", k, OTG_KMER_MAX);
-  const auto t_all = Clock::now();
-  otg_job_stats st{};
-  {
-    // parse_bed_file (src/vcf2mat.cpp:50-51): required, filters nothing
-    Bed bed;
-    const int rb = load_bed(job->bed_path, bed);
-    if (rb != OTG_OK) return rb;
-  }
-  VcfPtr vcf;
-  int rc = open_vcf(job->vcf_path, vcf);
-  if (rc != OTG_OK) return rc;
-  const PooledCtx ctx = acquire_ctx(job->device);
-  if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_vcf2mat_files: %s", last_err().c_str());
   const uint64_t bins = (1ull << (2 * k)) + 1;
   // alleles per batch: at most 1 GiB of rows on the host and what the device workspace of otg_kmer_usage_batch holds (k >= 8: + u32 histograms)
   const uint64_t dev_row = bins * 8 + (k >= 8 ? bins * 4 : 0);
   uint64_t per = job->batch_alleles ? job->batch_alleles : std::min<uint64_t>(65536, std::max<uint64_t>(1, (1ull << 30) / (bins * 8)));
-  per = std::max<uint64_t>(1, std::min<uint64_t>({per, (4ull << 30) / dev_row, 1ull << 24}));
-  const int threads = job->threads > 0 ? job->threads : 1;
-  struct VBatch {
-    std::vector<otg_vcf_record> rec; std::vector<char> regions; std::vector<uint64_t> off; std::vector<uint32_t> len; std::vector<uint8_t> seqs;
-    uint32_t nr = 0, na = 0; uint64_t ru = 0, au = 0, bytes = 0; int rc = OTG_OK; double ms = 0; std::string err;
-  };
-  auto read_into = [&](VBatch& B) {
-    const auto t0 = Clock::now();
-    B.bytes = 0;
-    for (;;) {
-      B.rc = otg_vcf_read_alleles(vcf.get(), B.rec.data(), (uint32_t)B.rec.size(), &B.nr, B.regions.data(), B.regions.size(), &B.ru, B.off.data(), B.len.data(),
-                                  (uint32_t)B.off.size(), &B.na, B.seqs.data(), B.seqs.size(), &B.au, &B.bytes);
-      if (B.rc != OTG_ERR_CAPACITY) break;
-      // one record larger than the buffers: grow them to hold it (its alleles may exceed `per`; the device call then reports the workspace)
-      if (B.na > B.off.size()) { B.off.resize(B.na); B.len.resize(B.na); }
-      if (B.ru > B.regions.size()) B.regions.resize(B.ru);
-      if (B.au > B.seqs.size()) B.seqs.resize(B.au);
-    }
-    if (B.rc != OTG_OK) { B.err = last_err(); B.nr = 0; }
-    B.ms = ms_since(t0);
-  };
+  per = std::min<uint64_t>(per, (4ull << 30) / dev_row);
   std::vector<double> usage, gc, hsd;
-  std::vector<std::string> parts((size_t)threads);
-  TwoInFlight<VBatch> flight;
-  for (VBatch& B : flight) { B.rec.resize(per); B.off.resize(per); B.len.resize(per); B.regions.resize(1 << 20); B.seqs.resize(64ull << 20); }
-  read_into(flight.current());
-  for (;; flight.advance()) {
-    VBatch& B = flight.current();
-    st.ms_ingest += B.ms; st.input_bytes += B.bytes;
-    if (B.rc != OTG_OK) return otg_fail(nullptr, B.rc, "otg_vcf2mat_files: %s", B.err.c_str());
-    if (B.nr == 0) break;
-    flight.prefetch(read_into);
-    st.n_regions += B.nr; st.n_alleles += B.na;
-    auto t0 = Clock::now();
-    usage.resize((size_t)B.na * bins); gc.resize(B.na); hsd.resize(B.na);
-    rc = otg_kmer_usage_batch(ctx.get(), B.seqs.data(), B.au, B.off.data(), B.len.data(), B.na, k, usage.data(), gc.data(), hsd.data());
-    if (rc != OTG_OK) return otg_fail(nullptr, rc, "otg_vcf2mat_files: %s", ctx_err(ctx.get()).c_str());
-    st.ms_hot_path += ms_since(t0);
-    t0 = Clock::now();
-    // the rows of contiguous record ranges with about equal allele counts, one range per thread, written in file order
-    std::vector<uint32_t> cut((size_t)threads + 1, B.nr);
-    cut[0] = 0;
-    for (uint32_t r = 0, t = 1; r < B.nr && t < (uint32_t)threads; ++r)
-      if ((uint64_t)B.rec[r].first_allele * threads >= (uint64_t)B.na * t) cut[t++] = r;
-    for (int t = 1; t <= threads; ++t) cut[t] = std::max(cut[t], cut[t - 1]);
-    {
-      std::vector<std::thread> pool;
-      for (int t = 0; t < threads; ++t) {
-        parts[t].clear();
-        if (cut[t + 1] > cut[t])
-          pool.emplace_back([&, t] { otg_vcf2mat_rows(parts[t], B.rec.data() + cut[t], cut[t + 1] - cut[t], B.regions.data(), B.len.data(), k,
-                                                      usage.data(), gc.data(), hsd.data()); });
-      }
-      for (auto& th : pool) th.join();
-    }
-    st.ms_emit += ms_since(t0);
-    for (int t = 0; t < threads; ++t) {
-      if (!parts[t].empty() && write(user, parts[t].data(), parts[t].size()) != 0) return otg_fail(nullptr, OTG_ERR_ARG, "otg_vcf2mat_files: the writer failed");
-      st.output_bytes += parts[t].size();
-    }
-  }
-  st.ms_total = ms_since(t_all); st.n_devices = 1; st.n_regions_ok = st.n_regions;
-  if (stats) *stats = st;
-  return OTG_OK;
+  return vcf_allele_job("otg_vcf2mat_files", job->vcf_path, job->bed_path, job->device, per, job->threads, write, user, stats,
+    [&](otg_ctx* ctx, const VcfBatch& B) {
+      usage.resize((size_t)B.na * bins); gc.resize(B.na); hsd.resize(B.na);
+      return otg_kmer_usage_batch(ctx, B.seqs.data(), B.au, B.off.data(), B.len.data(), B.na, k, usage.data(), gc.data(), hsd.data());
+    },
+    [&](std::string& o, const VcfBatch& B, uint32_t r0, uint32_t nr) {
+      otg_vcf2mat_rows(o, B.rec.data() + r0, nr, B.regions.data(), B.len.data(), k, usage.data(), gc.data(), hsd.data());
+    });
+}
+
+// The motif rows of a VCF's alleles (otg_motif_batch), on vcf_allele_job: the reader, the batching and the threaded emit of otg_vcf2mat_files.
+int otg_motifs_files(const otg_motifs_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
+{
+  if (!job || !write || !job->vcf_path || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "otg_motifs_files: NULL job, writer, VCF or BED path");
+  const uint32_t max_period = job->max_period, slack = job->slack;
+  if (max_period < 1 || max_period > OTG_MOTIF_MAX_PERIOD)
+    return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--max-period' (%u). Needs to be 1 <= x <= %d.", max_period, OTG_MOTIF_MAX_PERIOD);
+  if (slack > 999) return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--slack' (%u). Needs to be 0 <= x <= 999.", slack);
+  std::vector<otg_motif> motifs;
+  std::vector<uint8_t> units;
+  uint32_t stride = 1;
+  return vcf_allele_job("otg_motifs_files", job->vcf_path, job->bed_path, job->device, job->batch_alleles ? job->batch_alleles : 65536, job->threads, write, user, stats,
+    [&](otg_ctx* ctx, const VcfBatch& B) {
+      uint32_t max_len = 0;
+      for (uint32_t i = 0; i < B.na; ++i) max_len = std::max(max_len, B.len[i]);
+      stride = std::max<uint32_t>(1, std::min<uint32_t>(max_period, max_len / 2));
+      motifs.resize(B.na); units.resize((size_t)B.na * stride);
+      return otg_motif_batch(ctx, B.seqs.data(), B.au, B.off.data(), B.len.data(), B.na, max_period, slack, motifs.data(), units.data(), stride);
+    },
+    [&](std::string& o, const VcfBatch& B, uint32_t r0, uint32_t nr) {
+      otg_motif_rows(o, B.rec.data() + r0, nr, B.regions.data(), B.len.data(), motifs.data(), units.data(), stride);
+    });
 }
 
 // ---- `otter genotype` from files to text in one call: genotype() / genotype_process() (src/genotype.cpp:69-192).  Regions in bounded

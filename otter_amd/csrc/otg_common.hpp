@@ -43,7 +43,9 @@ struct otg_ctx {
   double last_score_ms = 0.0, last_prov_ms = 0.0;  // HIP-event times of the two device passes of the latest otg_edit_align_batch (otg_edit_align_last_ms)
   uint32_t last_align_tiers[2] = {0u, 0u};         // tasks the LDS / the global-row tier of the latest adaptive otg_edit_align_heur_batch finished (otg_edit_align_last_tiers)
   double last_kmer_count_ms = 0.0, last_kmer_epi_ms = 0.0;  // HIP-event times of the latest otg_kmer_usage_batch (otg_kmer_usage_last_ms)
-  hipEvent_t ev2 = nullptr;                       // third timing event, created on first use (kmer_usage.hip)
+  hipEvent_t ev2 = nullptr;                       // third timing event, created on first use (kmer_usage.hip, motif.hip)
+  double last_motif_count_ms = 0.0, last_motif_reduce_ms = 0.0;   // HIP-event times of the latest otg_motif_batch / otg_motif_cohort (otg_motif_last_ms)
+  uint32_t last_motif_n = 0, last_motif_stride = 0;               // the shape of the results in SLOT_MOTIF_OUT (otg_motif_device_results)
   double last_kernel_ms = 0.0;                    // HIP-event time of the kernels of the latest operator-level call that reports one (otg_last_kernel_ms)
   // the latest genotype clustering with a metric (genotype_edit.hip): times of its two parts (otg_genotype_metric_last_ms), whether the edit
   // matrix was built, and where its counters lie in SLOT_GTE_CLS
@@ -96,6 +98,7 @@ enum {
   SLOT_KMER_SEQ, SLOT_KMER_META, SLOT_KMER_HIST, SLOT_KMER_OUT,     // otg_kmer_usage_batch (kmer_usage.hip); OUT stays valid for the device results
   SLOT_KMER_BLK,                                                    // tier L of otg_kmer_usage_resident: gc counts and the workgroup prefix
   SLOT_GTE_CLS, SLOT_GTE_TASKS, SLOT_GTE_SCORES, SLOT_GTE_DEN, SLOT_GTE_TODO,   // the edit metric of the genotype clustering (genotype_edit.hip)
+  SLOT_MOTIF_SEQ, SLOT_MOTIF_META, SLOT_MOTIF_OFF, SLOT_MOTIF_M, SLOT_MOTIF_PLANES, SLOT_MOTIF_OUT,   // otg_motif_batch (motif.hip); OUT stays valid for the device results
   SLOT_COUNT
 };
 
@@ -317,6 +320,13 @@ int otg_genotype_metric_finish(otg_ctx* ctx, int metric, uint64_t* n_aligned);
 int otg_kmer_usage_fits(otg_ctx* ctx, const char* who, uint32_t n, int32_t k);
 int otg_kmer_usage_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, const uint32_t* h_blk,
                             uint32_t n, int32_t k, double* usage_out, double* gc_out, double* hsd_out);
+
+// motif.hip: the argument refusals of otg_motif_batch (max_period, slack; unit_stride against the longest row) and its launch part on
+// device-resident rows; see the definitions
+int otg_motif_args(otg_ctx* ctx, const char* who, uint32_t max_period, uint32_t slack);
+int otg_motif_stride_fits(otg_ctx* ctx, const char* who, uint32_t max_len, uint32_t max_period, uint32_t unit_stride);
+int otg_motif_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, uint32_t n,
+                       uint32_t max_period, uint32_t slack, otg_motif* out, uint8_t* unit_out, uint32_t unit_stride);
 
 // cluster.hip (genotype_kernel)
 int otg_launch_genotype(otg_ctx* ctx, const otg_params* P, const uint8_t* d_arena, const uint64_t* d_seq_off,
