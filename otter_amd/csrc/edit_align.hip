@@ -271,7 +271,7 @@ __global__ __launch_bounds__(WPB * 64) void edit_align_kernel(
         if constexpr (EF) {
           // the end test, on the last row only: chunks come in ascending order, so the lowest lane of the first chunk that has one wins
           if (sc == s && !found) {
-            const unsigned long long fb = __ballot(valid && ((h >= tl && pl - v <= pef) || (v >= pl && tl - h <= tef)));
+            const unsigned long long fb = __ballot(valid && otg_ends_free_done(h, v, pl, tl, pef, tef));
             if (fb) {
               const int fl = (int)__builtin_ctzll(fb);
               found = true; k_fin = c + fl; h_fin = __shfl(h, fl);
@@ -433,7 +433,7 @@ __global__ __launch_bounds__(WPB * 64) void edit_align_adaptive_kernel(
           }
           if (in) st.wr(k, valid ? h : OTG_NULL_OFF);
           if (valid) dmin = otg_adaptive::imin(dmin, otg_adaptive::left_to_align(h, k, pl, tl, EF, pef, tef));
-          if constexpr (EF) { if (valid && ((h >= tl && pl - v <= pef) || (v >= pl && tl - h <= tef))) kfin = otg_adaptive::imin(kfin, k); }
+          if constexpr (EF) { if (valid && otg_ends_free_done(h, v, pl, tl, pef, tef)) kfin = otg_adaptive::imin(kfin, k); }
           if (sc > 0) {
             const unsigned long long b0 = __ballot(in && (op & 1u));
             const unsigned long long b1 = __ballot(in && (op & 2u));

@@ -193,6 +193,24 @@ __device__ __forceinline__ int otg_myers_threshold(int R, int d, int pbf, int pe
 // ---- match-run extension helpers shared by the wavefront kernels -------------------------------------
 __device__ __forceinline__ uint64_t otg_load8(const uint8_t* p) { uint64_t v; __builtin_memcpy(&v, p, 8); return v; }
 
+// Lane shifts across the whole wave (GFX9 DPP wave_shr:1 / wave_shl:1; the lane at the open end keeps its own value).
+__device__ __forceinline__ int otg_dpp_shr1(int x) { return __builtin_amdgcn_update_dpp(x, x, 0x138, 0xf, 0xf, false); }   // lane i <- lane i-1
+__device__ __forceinline__ int otg_dpp_shl1(int x) { return __builtin_amdgcn_update_dpp(x, x, 0x130, 0xf, 0xf, false); }   // lane i <- lane i+1
+
+// Ends-free end test of a fully extended cell (text offset h, pattern offset v): one sequence is consumed and what is left of the other is free.
+__device__ __forceinline__ bool otg_ends_free_done(int h, int v, int pl, int tl, int pef, int tef)
+{
+  return (h >= tl && pl - v <= pef) || (v >= pl && tl - h <= tef);
+}
+
+// Lane-private: number of equal leading bytes of P+v.. and T+h.., looking at most 16 bytes ahead and at most `rem`.
+__device__ __forceinline__ int otg_match16(const uint8_t* P, const uint8_t* T, int v, int h, int rem)
+{
+  const uint64_t xl = otg_load8(P + v) ^ otg_load8(T + h), xh = otg_load8(P + v + 8) ^ otg_load8(T + h + 8);
+  const int m = xl ? (__builtin_ctzll(xl) >> 3) : (xh ? 8 + (__builtin_ctzll(xh) >> 3) : 16);
+  return m < rem ? m : rem;
+}
+
 // Lane-private: number of equal leading bytes of P+v.. and T+h.., looking at most 64 bytes ahead and at most `rem`.
 // Eight independent 8-byte loads per operand are issued back to back (one latency, not eight).
 __device__ __forceinline__ int otg_match64(const uint8_t* P, const uint8_t* T, int v, int h, int rem)

@@ -32,6 +32,7 @@
 //               byte probes 1 024 -> int32 rings in HBM.
 #include "otg_wfadaptive.hpp"
 #include "otg_chain.hpp"
+#include "otg_match_queue.hpp"
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
@@ -42,7 +43,6 @@ using namespace otg_adaptive;
 namespace {
 
 __device__ __forceinline__ int wave_min_i32(int v) { return -otg_wave_max_i32(-v); }      // |v| <= 2^30 here
-__device__ __forceinline__ int dpp_shr1(int x) { return __builtin_amdgcn_update_dpp(x, x, 0x138, 0xf, 0xf, false); }   // lane i <- lane i-1
 
 // lane masks of comparisons (v_cmp into an SGPR pair; the logic on them runs on the scalar unit) and a select on a lane mask.  Written with bools,
 // hipcc 7.2 turns "does any lane ..." and "or into the flag" into a select, an and and a compare on the vector unit each (see wfa_affine_reg.hip)
@@ -99,6 +99,7 @@ __global__ __launch_bounds__(WPB * 64) void wfa_edit_adaptive_kernel(
     const uint8_t* P = arena + t.pattern_off;
     const uint8_t* T = arena + t.text_off;
     const int pl = (int)t.pattern_len, tl = (int)t.text_len;
+    const otg_mq::Seqs seq{P, T, pl, tl};
     const bool ef = t.endsfree != 0;
     const int pef = ef ? t.pattern_end_free : 0, tef = ef ? t.text_end_free : 0;
     const int kend = tl - pl;
@@ -121,57 +122,18 @@ __global__ __launch_bounds__(WPB * 64) void wfa_edit_adaptive_kernel(
         int qn = 0;
         auto finished = [&](int h, int k) {         // diagonal k is fully extended at offset h
           dmin = imin(dmin, left_to_align(h, k, pl, tl, ef, pef, tef));
-          if (ef) { const int v = h - k; fin_l = fin_l || (h >= tl && pl - v <= pef) || (v >= pl && tl - h <= tef); }
+          if (ef) fin_l = fin_l || otg_ends_free_done(h, h - k, pl, tl, pef, tef);
         };
         auto drain = [&]() {
+          // (otg_match_queue.hpp) entries = k - lo; a global row is fenced at the head of every pass and behind the last.  A queue as long as the
+          // window (2048 / 2048) fills during a sweep from 1985 start diagonals on, which the window admits; the 16384 window and the HBM row
+          // (queue 2048) from the same width on
+          otg_mq::drain<true>(queue, qn, lane, seq,
+              [&](int e) { return lo + e; },
+              [&](int k) { return st.rd(k); }, [&](int k, int h) { st.wr(k, h); },
+              [&](int pass, int v, int h, int rem) { return otg_mq::probe_bytes(seq, pass, v, h, rem); },
+              [&] { st.sync(); }, [&](int h, int k) { finished(h, k); return false; });
           st.sync();
-          int pass = 0;
-          while (qn > 0) {
-            if (qn <= 4 && pass > 0) {
-              for (int q = 0; q < qn; ++q) {
-                const int k = lo + __builtin_amdgcn_readfirstlane((int)queue[q]);
-                int h = __builtin_amdgcn_readfirstlane(st.rd(k));
-                const int v = h - k;
-                const int m = otg_wave_match(P, T, v, h, imin(pl - v, tl - h), lane);
-                h += m;
-                st.wr(k, h);                      // the same value from every lane
-                finished(h, k);
-              }
-              qn = 0;
-              st.sync();
-              break;
-            }
-            int wq = 0;
-            for (int q0 = 0; q0 < qn; q0 += 64) {
-              const bool act = q0 + lane < qn;
-              int k = 0, h = 0, v = 0;
-              bool more = false;
-              if (act) {
-                k = lo + (int)queue[q0 + lane];
-                h = st.rd(k);
-                v = h - k;
-                const int rem = imin(pl - v, tl - h);
-                int m, full;
-                if (pass == 0) {
-                  const uint64_t xl = otg_load8(P + v) ^ otg_load8(T + h), xh = otg_load8(P + v + 8) ^ otg_load8(T + h + 8);
-                  m = xl ? (__builtin_ctzll(xl) >> 3) : (xh ? 8 + (__builtin_ctzll(xh) >> 3) : 16);
-                  m = imin(m, rem); full = 16;
-                } else { m = otg_match64(P, T, v, h, rem); full = 64; }
-                v += m; h += m;
-                more = (m == full) && v < pl && h < tl;
-                st.wr(k, h);
-                if (!more) finished(h, k);
-              }
-              const unsigned long long mm = __ballot(more);
-              if (more) {
-                const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
-                queue[wq + rank] = (uint32_t)(k - lo);
-              }
-              wq += __builtin_popcountll(mm);
-            }
-            qn = wq; ++pass;
-            st.sync();
-          }
         };
         // ---- sweep
         for (int c = lo; c <= hi; c += 64) {
@@ -184,7 +146,7 @@ __global__ __launch_bounds__(WPB * 64) void wfa_edit_adaptive_kernel(
             int o = OTG_NULL_OFF, r = OTG_NULL_OFF;
             if (k >= plo && k <= phi) o = st.rd(k);
             if (k + 1 >= plo && k + 1 <= phi) r = st.rd(k + 1);
-            int l = dpp_shr1(o);
+            int l = otg_dpp_shr1(o);
             if (lane == 0) l = carry;
             carry = __builtin_amdgcn_readlane(o, 63);
             const int a = l + 1, b = o + 1;
@@ -203,12 +165,7 @@ __global__ __launch_bounds__(WPB * 64) void wfa_edit_adaptive_kernel(
           }
           if (in) st.wr(k, valid ? h : OTG_NULL_OFF);
           if (valid && !more) finished(h, k);
-          const unsigned long long mm = __ballot(more);
-          if (more) {
-            const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
-            queue[qn + rank] = (uint32_t)(k - lo);
-          }
-          qn += __builtin_popcountll(mm);
+          otg_mq::push(queue, qn, __ballot(more), more, k - lo);
           if (qn + 64 > QCAP) drain();
         }
         drain();
@@ -421,6 +378,11 @@ __global__ __launch_bounds__(WPB * 64) void wfa_edit_adaptive_lds_kernel(
       // bool per lane the compiler rebuilt it with two selects, an and and a compare per chunk
       unsigned long long finm = 0ull;
       int qn = 0;
+      // This kernel — the edit stage of the adaptive mode runs on it — keeps its own pass loop and writes the ends-free test out, so that its
+      // instruction stream stays what it was before the other kernels moved to otg_mq::drain (DESIGN_LOG, "One match-run queue and drain":
+      // the shared drain laid this kernel's blocks out differently and the stage lost time).  Same plan as otg_mq::drain: packed probes,
+      // entries = k - lo, a fence at the head of every pass (global row: a queued cell is extended by another lane than the one that stored it).  <1024, 512>: the queue fills during a sweep from 449 runs beyond 64
+      // bases on, which the window (up to 956 diagonals) and the global row (wider starts) both admit; <4096, 1024>: from 961 on, admitted up to 4028.
       auto finished = [&](int h, int k) -> bool {          // (the caller collects the lanes' answers: it may be called under a lane condition)
         dmin = imin(dmin, left_to_align(h, k, pl, tl, ef, pef, tef));
         if (ef) { const int v = h - k; return (h >= tl && pl - v <= pef) || (v >= pl && tl - h <= tef); }
@@ -429,7 +391,7 @@ __global__ __launch_bounds__(WPB * 64) void wfa_edit_adaptive_lds_kernel(
       auto drain = [&]() {
         int pass = 0;
         while (qn > 0) {
-          wfs.sync();              // (global row: a queued cell is extended by another lane than the one that stored it)
+          wfs.sync();
           if (qn <= 4 && pass > 0) {
             for (int q = 0; q < qn; ++q) {
               const int k = lo + __builtin_amdgcn_readfirstlane((int)queue[q]);
@@ -458,12 +420,7 @@ __global__ __launch_bounds__(WPB * 64) void wfa_edit_adaptive_lds_kernel(
               if (!more) fin = finished(h, k);
             }
             finm |= __ballot(fin);
-            const unsigned long long mm = __ballot(more);
-            if (more) {
-              const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
-              queue[wq + rank] = (uint16_t)(k - lo);
-            }
-            wq += __builtin_popcountll(mm);
+            otg_mq::push(queue, wq, __ballot(more), more, k - lo);
           }
           qn = wq; ++pass;
         }
@@ -518,11 +475,7 @@ __global__ __launch_bounds__(WPB * 64) void wfa_edit_adaptive_lds_kernel(
         }
         dmin = imin(dmin, sel(hm, d, BIG));
         if (mm) {
-          if (sel(mm, 1, 0)) {
-            const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
-            queue[qn + rank] = (uint16_t)(k - lo);
-          }
-          qn += __builtin_popcountll(mm);
+          otg_mq::push(queue, qn, mm, sel(mm, 1, 0) != 0, k - lo);
           if (qn + 64 > QCAP) drain();
         }
       }
@@ -642,6 +595,7 @@ __global__ __launch_bounds__(NW * 64) void wfa_edit_adaptive_mw_kernel(
     const uint8_t* P = arena + t.pattern_off;
     const uint8_t* T = arena + t.text_off;
     const int pl = (int)t.pattern_len, tl = (int)t.text_len;
+    const otg_mq::Seqs seq{P, T, pl, tl};
     const bool ef = t.endsfree != 0;
     const int pef = ef ? t.pattern_end_free : 0, tef = ef ? t.text_end_free : 0;
     const int kend = tl - pl;
@@ -678,49 +632,17 @@ __global__ __launch_bounds__(NW * 64) void wfa_edit_adaptive_mw_kernel(
       int qn = 0;
       auto finished = [&](int h, int k) -> bool {
         dmin = imin(dmin, left_to_align(h, k, pl, tl, ef, pef, tef));
-        if (ef) { const int v = h - k; return (h >= tl && pl - v <= pef) || (v >= pl && tl - h <= tef); }
+        if (ef) return otg_ends_free_done(h, h - k, pl, tl, pef, tef);
         return k == kend && h >= tl;
       };
       auto drain = [&]() {
-        int pass = 0;
-        while (qn > 0) {
-          if (qn <= 4 && pass > 0) {
-            for (int q = 0; q < qn; ++q) {
-              const int k = lo + U((int)queue[q]);
-              int h = U(rd(rw, k));
-              const int v = h - k;
-              h += otg_wave_match(P, T, v, h, imin(pl - v, tl - h), lane);
-              wr(rw, k, h);                           // the same value from every lane
-              if (finished(h, k)) finm = ~0ull;
-            }
-            qn = 0;
-            break;
-          }
-          int wq = 0;
-          for (int q0 = 0; q0 < qn; q0 += 64) {
-            const bool act = q0 + lane < qn;
-            int k = 0, h = 0, v = 0;
-            bool more = false, fin = false;
-            if (act) {
-              k = lo + (int)queue[q0 + lane];
-              h = rd(rw, k);
-              v = h - k;
-              const int m = pk.match32(v, h, imin(pl - v, tl - h));
-              v += m; h += m;
-              more = (m == 32) && v < pl && h < tl;
-              wr(rw, k, h);
-              if (!more) fin = finished(h, k);
-            }
-            finm |= __ballot(fin);
-            const unsigned long long mm = __ballot(more);
-            if (more) {
-              const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
-              queue[wq + rank] = (uint16_t)(k - lo);
-            }
-            wq += __builtin_popcountll(mm);
-          }
-          qn = wq; ++pass;
-        }
+        // (otg_match_queue.hpp) entries = k - lo, packed probes, this wave's own queue over its own chunks.  <16384, 256, 8>: a wave's queue fills
+        // during a sweep once its share (every eighth chunk) holds 193 runs beyond 64 bases, i.e. from ~1550 start diagonals on; the window admits 16380
+        finm |= otg_mq::drain<true>(queue, qn, lane, seq,
+            [&](int e) { return lo + e; },
+            [&](int k) { return rd(rw, k); }, [&](int k, int h) { wr(rw, k, h); },
+            [&](int, int v, int h, int rem) { return otg_mq::Probe{pk.match32(v, h, rem), 32}; },
+            [] {}, finished);
       };
       // ---- sweep of this wave's chunks (branch-free per lane)
       const int br = rr * (CAP * 2), bw = rw * (CAP * 2);
@@ -771,11 +693,7 @@ __global__ __launch_bounds__(NW * 64) void wfa_edit_adaptive_mw_kernel(
         }
         dmin = imin(dmin, sel(hm, d, BIG));
         if (mm) {
-          if (sel(mm, 1, 0)) {
-            const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
-            queue[qn + rank] = (uint16_t)(k - lo);
-          }
-          qn += __builtin_popcountll(mm);
+          otg_mq::push(queue, qn, mm, sel(mm, 1, 0) != 0, k - lo);
           if (qn + 64 > QCAP) drain();
         }
       }
@@ -896,6 +814,7 @@ __global__ __launch_bounds__(WPB * 64) void wfa_affine_adaptive_kernel(
     const uint8_t* P = arena + t.pattern_off;
     const uint8_t* T = arena + t.text_off;
     const int pl = (int)t.pattern_len, tl = (int)t.text_len;
+    const otg_mq::Seqs seq{P, T, pl, tl};
     const bool ef = t.endsfree != 0;
     const int pef = ef ? t.pattern_end_free : 0, tef = ef ? t.text_end_free : 0;
     const int kend = tl - pl;
@@ -946,58 +865,18 @@ __global__ __launch_bounds__(WPB * 64) void wfa_affine_adaptive_kernel(
         int qn = 0;
         auto finished = [&](int h, int k) {
           dmin = imin(dmin, left_to_align(h, k, pl, tl, ef, pef, tef));
-          if (ef) { const int v = h - k; if ((h >= tl && pl - v <= pef) || (v >= pl && tl - h <= tef)) kfin = imin(kfin, k); }
+          if (ef) { if (otg_ends_free_done(h, h - k, pl, tl, pef, tef)) kfin = imin(kfin, k); }
         };
         auto drain = [&]() {
+          // (otg_match_queue.hpp) entries = k - lo; packed probes where the pair packs, else the byte probes; the global rings are fenced at the
+          // head of every pass and behind the last.  <1024, 1024> (byte probes): the queue fills during a sweep from 961 start diagonals on, the
+          // window admits 1024; <0, 2048> (HBM rings): from 1985 on, any width admitted
+          otg_mq::drain<true>(queue, qn, lane, seq,
+              [&](int e) { return lo + e; },
+              [&](int k) { return st.rdM(sm, k); }, [&](int k, int h) { st.wrM(sm, k, h); },
+              [&](int pass, int v, int h, int rem) { return pk.ok ? otg_mq::Probe{pk.match32(v, h, rem), 32} : otg_mq::probe_bytes(seq, pass, v, h, rem); },
+              [&] { st.sync(); }, [&](int h, int k) { finished(h, k); return false; });
           st.sync();
-          int pass = 0;
-          while (qn > 0) {
-            if (qn <= 4 && pass > 0) {
-              for (int e = 0; e < qn; ++e) {
-                const int kk = lo + U((int)queue[e]);
-                int h = U(st.rdM(sm, kk));
-                const int v = h - kk;
-                const int m = otg_wave_match(P, T, v, h, imin(pl - v, tl - h), lane);
-                h += m;
-                st.wrM(sm, kk, h);                // the same value from every lane
-                finished(h, kk);
-              }
-              qn = 0;
-              st.sync();
-              break;
-            }
-            int wq = 0;
-            for (int q0 = 0; q0 < qn; q0 += 64) {
-              const bool act = q0 + lane < qn;
-              int kk = 0, h = 0, v = 0;
-              bool more = false;
-              if (act) {
-                kk = lo + (int)queue[q0 + lane];
-                h = st.rdM(sm, kk);
-                v = h - kk;
-                const int rem = imin(pl - v, tl - h);
-                int m, full;
-                if (pk.ok) { m = pk.match32(v, h, rem); full = 32; }
-                else if (pass == 0) {
-                  const uint64_t xl = otg_load8(P + v) ^ otg_load8(T + h), xh = otg_load8(P + v + 8) ^ otg_load8(T + h + 8);
-                  m = xl ? (__builtin_ctzll(xl) >> 3) : (xh ? 8 + (__builtin_ctzll(xh) >> 3) : 16);
-                  m = imin(m, rem); full = 16;
-                } else { m = otg_match64(P, T, v, h, rem); full = 64; }
-                v += m; h += m;
-                more = (m == full) && v < pl && h < tl;
-                st.wrM(sm, kk, h);
-                if (!more) finished(h, kk);
-              }
-              const unsigned long long mm = __ballot(more);
-              if (more) {
-                const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
-                queue[wq + rank] = (uint32_t)(kk - lo);
-              }
-              wq += __builtin_popcountll(mm);
-            }
-            qn = wq; ++pass;
-            st.sync();
-          }
         };
         for (int c = lo; c <= hi; c += 64) {
           const int k = c + lane;
@@ -1048,12 +927,7 @@ __global__ __launch_bounds__(WPB * 64) void wfa_affine_adaptive_kernel(
             btrow[k] = (uint8_t)bits;
           }
           if (valid && !more) finished(h, k);
-          const unsigned long long mq = __ballot(more);
-          if (more) {
-            const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mq >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mq, 0u));
-            queue[qn + rank] = (uint32_t)(k - lo);
-          }
-          qn += __builtin_popcountll(mq);
+          otg_mq::push(queue, qn, __ballot(more), more, k - lo);
           if (qn + 64 > QCAP) drain();
         }
         drain();
@@ -1133,7 +1007,6 @@ __global__ __launch_bounds__(WPB * 64) void wfa_affine_adaptive_lds_kernel(
   uint8_t* slab = my + ws.off_slab;
   volatile lds_char* ROWS = (volatile lds_char*)&s_rows[wib][0][0];
   volatile lds_u32* ROWS32 = (volatile lds_u32*)&s_rows[wib][0][0];
-  auto U = [](int x) { return __builtin_amdgcn_readfirstlane(x); };
   volatile lds_u32* queue = (volatile lds_u32*)&s_q[wib][0];
   const uint32_t n_todo = n_todo_ptr ? *n_todo_ptr : n_todo_imm;
   auto rd = [&](int row, int k) -> int { return *(volatile __attribute__((address_space(3))) int16_t*)(ROWS + row * (CAP * 2) + ((k & MASK) << 1)); };
@@ -1187,6 +1060,7 @@ __global__ __launch_bounds__(WPB * 64) void wfa_affine_adaptive_lds_kernel(
     const uint8_t* P = arena + t.pattern_off;
     const uint8_t* T = arena + t.text_off;
     const int pl = (int)t.pattern_len, tl = (int)t.text_len;
+    const otg_mq::Seqs seq{P, T, pl, tl};
     const bool ef = t.endsfree != 0;
     const int pef = ef ? t.pattern_end_free : 0, tef = ef ? t.text_end_free : 0;
     const int kend = tl - pl;
@@ -1248,48 +1122,18 @@ __global__ __launch_bounds__(WPB * 64) void wfa_affine_adaptive_lds_kernel(
       int qn = 0;
       auto finished = [&](int h, int k) {
         dmin = imin(dmin, left_to_align(h, k, pl, tl, ef, pef, tef));
-        if (ef) { const int v = h - k; if ((h >= tl && pl - v <= pef) || (v >= pl && tl - h <= tef)) kfin = imin(kfin, k); }
+        if (ef) { if (otg_ends_free_done(h, h - k, pl, tl, pef, tef)) kfin = imin(kfin, k); }
         else if (k == kend && h >= tl) kfin = k;
       };
       auto drain = [&]() {
-        int pass = 0;
-        while (qn > 0) {
-          if (qn <= 4 && pass > 0) {
-            for (int e = 0; e < qn; ++e) {
-              const int kk = lo + U((int)queue[e]);
-              int h = U(rd(sm, kk));
-              const int v = h - kk;
-              h += otg_wave_match(P, T, v, h, imin(pl - v, tl - h), lane);
-              wr(sm, kk, h);                         // the same value from every lane
-              finished(h, kk);
-            }
-            qn = 0;
-            break;
-          }
-          int wq = 0;
-          for (int q0 = 0; q0 < qn; q0 += 64) {
-            const bool act = q0 + lane < qn;
-            int kk = 0, h = 0, v = 0;
-            bool more = false;
-            if (act) {
-              kk = lo + (int)queue[q0 + lane];
-              h = rd(sm, kk);
-              v = h - kk;
-              const int m = pk.match32(v, h, imin(pl - v, tl - h));
-              v += m; h += m;
-              more = (m == 32) && v < pl && h < tl;
-              wr(sm, kk, h);
-              if (!more) finished(h, kk);
-            }
-            const unsigned long long mm = __ballot(more);
-            if (more) {
-              const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
-              queue[wq + rank] = (uint32_t)(kk - lo);
-            }
-            wq += __builtin_popcountll(mm);
-          }
-          qn = wq; ++pass;
-        }
+        // (otg_match_queue.hpp) entries = k - lo, packed probes.  <256, 256, masked>: the queue fills during a sweep from 193 runs beyond 64 bases
+        // on, the window admits 252 diagonals.  <1024, 1024, unmasked>: it would take 961, and the window admits 956 — the sweep's drain cannot
+        // run in that instantiation
+        otg_mq::drain<true>(queue, qn, lane, seq,
+            [&](int e) { return lo + e; },
+            [&](int k) { return rd(sm, k); }, [&](int k, int h) { wr(sm, k, h); },
+            [&](int, int v, int h, int rem) { return otg_mq::Probe{pk.match32(v, h, rem), 32}; },
+            [] {}, [&](int h, int k) { finished(h, k); return false; });
       };
       // ---- sweep (branch-free per lane)
       const int bx = qx * (CAP * 2), bo = qo * (CAP * 2), bi = qi * (CAP * 2), bd = qd * (CAP * 2);
@@ -1350,11 +1194,7 @@ __global__ __launch_bounds__(WPB * 64) void wfa_affine_adaptive_lds_kernel(
         if (fm) kfin = imin(kfin, sel(fm, k, BIG));
         dmin = imin(dmin, sel(hm, d, BIG));
         if (mq) {
-          if (sel(mq, 1, 0)) {
-            const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mq >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mq, 0u));
-            queue[qn + rank] = (uint32_t)(k - lo);
-          }
-          qn += __builtin_popcountll(mq);
+          otg_mq::push(queue, qn, mq, sel(mq, 1, 0) != 0, k - lo);
           if (qn + 64 > QCAP) drain();
         }
       }
@@ -1483,6 +1323,7 @@ __global__ __launch_bounds__(NW * 64) void wfa_affine_adaptive_mw_kernel(
     const uint8_t* P = arena + t.pattern_off;
     const uint8_t* T = arena + t.text_off;
     const int pl = (int)t.pattern_len, tl = (int)t.text_len;
+    const otg_mq::Seqs seq{P, T, pl, tl};
     const bool ef = t.endsfree != 0;
     const int pef = ef ? t.pattern_end_free : 0, tef = ef ? t.text_end_free : 0;
     const int kend = tl - pl;
@@ -1545,48 +1386,18 @@ __global__ __launch_bounds__(NW * 64) void wfa_affine_adaptive_mw_kernel(
       int qn = 0;
       auto finished = [&](int h, int k) {
         dmin = imin(dmin, left_to_align(h, k, pl, tl, ef, pef, tef));
-        if (ef) { const int v = h - k; if ((h >= tl && pl - v <= pef) || (v >= pl && tl - h <= tef)) kfin = imin(kfin, k); }
+        if (ef) { if (otg_ends_free_done(h, h - k, pl, tl, pef, tef)) kfin = imin(kfin, k); }
         else if (k == kend && h >= tl) kfin = k;
       };
       auto drain = [&]() {
-        int pass = 0;
-        while (qn > 0) {
-          if (qn <= 4 && pass > 0) {
-            for (int e = 0; e < qn; ++e) {
-              const int kk = lo + U((int)queue[e]);
-              int h = U(rd(sm, kk));
-              const int v = h - kk;
-              h += otg_wave_match(P, T, v, h, imin(pl - v, tl - h), lane);
-              wr(sm, kk, h);
-              finished(h, kk);
-            }
-            qn = 0;
-            break;
-          }
-          int wq = 0;
-          for (int q0 = 0; q0 < qn; q0 += 64) {
-            const bool act = q0 + lane < qn;
-            int kk = 0, h = 0, v = 0;
-            bool more = false;
-            if (act) {
-              kk = lo + (int)queue[q0 + lane];
-              h = rd(sm, kk);
-              v = h - kk;
-              const int m = pk.match32(v, h, imin(pl - v, tl - h));
-              v += m; h += m;
-              more = (m == 32) && v < pl && h < tl;
-              wr(sm, kk, h);
-              if (!more) finished(h, kk);
-            }
-            const unsigned long long mm = __ballot(more);
-            if (more) {
-              const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
-              queue[wq + rank] = (uint32_t)(kk - lo);
-            }
-            wq += __builtin_popcountll(mm);
-          }
-          qn = wq; ++pass;
-        }
+        // (otg_match_queue.hpp) entries = k - lo, packed probes, this wave's own queue over its own chunks (256 entries).  <1024, 4 waves>: a wave's
+        // queue fills during a sweep once its four chunks hold 193 runs beyond 64 bases, from ~770 start diagonals on (window: 1020);
+        // <4096, 8 waves>: from ~1550 on (window: 4092)
+        otg_mq::drain<true>(queue, qn, lane, seq,
+            [&](int e) { return lo + e; },
+            [&](int k) { return rd(sm, k); }, [&](int k, int h) { wr(sm, k, h); },
+            [&](int, int v, int h, int rem) { return otg_mq::Probe{pk.match32(v, h, rem), 32}; },
+            [] {}, [&](int h, int k) { finished(h, k); return false; });
       };
       // ---- sweep of this wave's chunks (branch-free per lane, as in the one-wave tier)
       const int bx = qx * (CAP * 2), bo = qo * (CAP * 2), bi = qi * (CAP * 2), bd = qd * (CAP * 2);
@@ -1647,11 +1458,7 @@ __global__ __launch_bounds__(NW * 64) void wfa_affine_adaptive_mw_kernel(
         if (fm) kfin = imin(kfin, sel(fm, k, BIG));
         dmin = imin(dmin, sel(hm, d, BIG));
         if (mq) {
-          if (sel(mq, 1, 0)) {
-            const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mq >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mq, 0u));
-            queue[qn + rank] = (uint32_t)(k - lo);
-          }
-          qn += __builtin_popcountll(mq);
+          otg_mq::push(queue, qn, mq, sel(mq, 1, 0) != 0, k - lo);
           if (qn + 64 > QCAP) drain();
         }
       }

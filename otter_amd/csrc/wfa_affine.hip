@@ -18,6 +18,7 @@
 #include "wfa_affine_common.hpp"
 #include "wfa_affine_reg.hpp"
 #include "otg_chain.hpp"
+#include "otg_match_queue.hpp"
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
@@ -73,6 +74,7 @@ __global__ __launch_bounds__(WPB * 64) void wfa_affine_kernel(
     const uint8_t* P = arena + t.pattern_off;
     const uint8_t* T = arena + t.text_off;
     const int pl = (int)t.pattern_len, tl = (int)t.text_len;
+    const otg_mq::Seqs seq{P, T, pl, tl};
     const bool ef = t.endsfree != 0;
     const int pef = t.pattern_end_free, tef = t.text_end_free;
     const int kb = pl + 1; // ring index of diagonal k is k + kb
@@ -124,41 +126,16 @@ __global__ __launch_bounds__(WPB * 64) void wfa_affine_kernel(
       int32_t* Dc = ringD + (size_t)si * ws.capa;
       bool done = false;
       int qn = 0;
-      // drain: diagonals whose 8-byte probe matched fully are extended 16 bytes per iteration from a
-      // wave-compacted LDS queue (entries = k - lo), so no lane waits for the slowest diagonal of its chunk
+      // drain (otg_match_queue.hpp): 16 bytes in every pass and no wave-wide step, as this last tier was first written; entries = k - lo.
+      // The queue (2048) fills during a sweep for start ranges of 1985 diagonals and more; the rings admit any width.
+      auto wg_fence = [] { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); };
       auto drain = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        while (qn > 0) {
-          int wq = 0;
-          for (int q0 = 0; q0 < qn; q0 += 64) {
-            const bool act = q0 + lane < qn;
-            int kk = 0, h = 0, v = 0;
-            bool more = false;
-            if (act) {
-              kk = lo + (int)queue[q0 + lane];
-              h = Mc[kk + kb];
-              v = h - kk;
-              uint64_t a0, a1, b0, b1;
-              __builtin_memcpy(&a0, P + v, 8); __builtin_memcpy(&a1, P + v + 8, 8);
-              __builtin_memcpy(&b0, T + h, 8); __builtin_memcpy(&b1, T + h + 8, 8);
-              const uint64_t xl = a0 ^ b0, xh = a1 ^ b1;
-              int m = xl ? (__builtin_ctzll(xl) >> 3) : (xh ? 8 + (__builtin_ctzll(xh) >> 3) : 16);
-              const int rem = imin(pl - v, tl - h);
-              m = imin(m, rem);
-              v += m; h += m;
-              more = (m == 16) && v < pl && h < tl;
-              Mc[kk + kb] = h;
-            }
-            const unsigned long long mm = __ballot(more);
-            if (more) {
-              const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
-              queue[wq + rank] = (uint32_t)(kk - lo);
-            }
-            wq += __builtin_popcountll(mm);
-          }
-          qn = wq;
-          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        }
+        otg_mq::drain<false>(queue, qn, lane, seq,
+            [&](int e) { return lo + e; },
+            [&](int k) -> int { return Mc[k + kb]; }, [&](int k, int h) { Mc[k + kb] = h; },
+            [&](int, int v, int h, int rem) { return otg_mq::Probe{otg_match16(P, T, v, h, rem), 16}; },
+            wg_fence, [](int, int) { return false; });
+        wg_fence();
       };
       for (int c = lo; c <= hi; c += 64) {
         const int k = c + lane;
@@ -191,10 +168,7 @@ __global__ __launch_bounds__(WPB * 64) void wfa_affine_kernel(
         const bool valid = in && mx >= 0 && h <= tl && v <= pl;
         bool more = false;
         if (valid && v < pl && h < tl) {
-          uint64_t a, b;
-          __builtin_memcpy(&a, P + v, 8);
-          __builtin_memcpy(&b, T + h, 8);
-          const uint64_t xx = a ^ b;
+          const uint64_t xx = otg_load8(P + v) ^ otg_load8(T + h);
           int m = xx ? (__builtin_ctzll(xx) >> 3) : 8;
           const int rem = imin(pl - v, tl - h);
           m = imin(m, rem);
@@ -206,12 +180,7 @@ __global__ __launch_bounds__(WPB * 64) void wfa_affine_kernel(
           Ic[j] = ins; Dc[j] = del;
           btrow[k] = (uint8_t)bits;
         }
-        const unsigned long long mq = __ballot(more);
-        if (more) {
-          const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mq >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mq, 0u));
-          queue[qn + rank] = (uint32_t)(k - lo);
-        }
-        qn += __builtin_popcountll(mq);
+        otg_mq::push(queue, qn, __ballot(more), more, k - lo);
         if (qn + 64 > QCAP) drain();
       }
       drain();
@@ -225,7 +194,7 @@ __global__ __launch_bounds__(WPB * 64) void wfa_affine_kernel(
           if (k <= hi) {
             const int h = Mc[k + kb];
             const int v = h - k;
-            fin = h >= 0 && ((h >= tl && pl - v <= pef) || (v >= pl && tl - h <= tef));
+            fin = h >= 0 && otg_ends_free_done(h, v, pl, tl, pef, tef);
           }
           const unsigned long long fm = __ballot(fin);
           if (fm) { done = true; s_end = s; k_end = c + (int)__builtin_ctzll(fm); }
@@ -251,8 +220,6 @@ __global__ __launch_bounds__(WPB * 64) void wfa_affine_kernel(
 // alignment of the pair, so its score U is an UPPER bound of the optimum (equal to it whenever the optimal path stays inside the
 // band, which is the normal case for reads of one allele).  The exact tiers use U only to skip cells that cannot lie on an alignment
 // of score <= U, so a loose U costs time, never correctness.  U = INT_MAX when the band cannot hold the start diagonals.
-__device__ __forceinline__ int dpp_shl1(int x) { return __builtin_amdgcn_update_dpp(x, x, 0x130, 0xf, 0xf, false); }   // lane i <- lane i+1
-__device__ __forceinline__ int dpp_shr1b(int x) { return __builtin_amdgcn_update_dpp(x, x, 0x138, 0xf, 0xf, false); }  // lane i <- lane i-1
 
 // Sliding variant of the bound pass: ONE diagonal per lane (64-diagonal band) that follows the diagonal with the
 // furthest anti-diagonal progress (checked every second score, one diagonal per move; the state moves with a DPP
@@ -362,7 +329,7 @@ __global__ __launch_bounds__(256) void wfa_affine_bound1_kernel(
           } while (__ballot(more));
         }
         const int h = cur, v = h - k;
-        const bool fin = h >= 0 && ((h >= tl && pl - v <= pef) || (v >= pl && tl - h <= tef));
+        const bool fin = h >= 0 && otg_ends_free_done(h, v, pl, tl, pef, tef);
         return __ballot(fin) != 0;
       };
       if (extend_and_test()) result = 0;
@@ -377,18 +344,18 @@ __global__ __launch_bounds__(256) void wfa_affine_bound1_kernel(
           if (at) {
             const int bl = (int)__builtin_ctzll(at);
             if (bl >= 40) {                               // band moves up: lane i takes over lane i+1
-              M1 = dpp_shl1(M1); M2 = dpp_shl1(M2); M3 = dpp_shl1(M3); M4 = dpp_shl1(M4); I = dpp_shl1(I); D = dpp_shl1(D);
+              M1 = otg_dpp_shl1(M1); M2 = otg_dpp_shl1(M2); M3 = otg_dpp_shl1(M3); M4 = otg_dpp_shl1(M4); I = otg_dpp_shl1(I); D = otg_dpp_shl1(D);
               if (lane == 63) { M1 = M2 = M3 = M4 = I = D = NULLV; }
               ++bk0;
             } else if (bl < 24) {
-              M1 = dpp_shr1b(M1); M2 = dpp_shr1b(M2); M3 = dpp_shr1b(M3); M4 = dpp_shr1b(M4); I = dpp_shr1b(I); D = dpp_shr1b(D);
+              M1 = otg_dpp_shr1(M1); M2 = otg_dpp_shr1(M2); M3 = otg_dpp_shr1(M3); M4 = otg_dpp_shr1(M4); I = otg_dpp_shr1(I); D = otg_dpp_shr1(D);
               if (lane == 0) { M1 = M2 = M3 = M4 = I = D = NULLV; }
               --bk0;
             }
           }
         }
         const int k = bk0 + lane;
-        int mo_l = dpp_shr1b(M4), i_l = dpp_shr1b(I), mo_r = dpp_shl1(M4), d_r = dpp_shl1(D);
+        int mo_l = otg_dpp_shr1(M4), i_l = otg_dpp_shr1(I), mo_r = otg_dpp_shl1(M4), d_r = otg_dpp_shl1(D);
         if (lane == 0) { mo_l = NULLV; i_l = NULLV; }
         if (lane == 63) { mo_r = NULLV; d_r = NULLV; }
         int ins = imax(i_l, mo_l) + 1;
@@ -419,8 +386,6 @@ __global__ __launch_bounds__(256) void wfa_affine_bound1_kernel(
 //   * per 64-diagonal chunk the HBM traffic drops from ~2.1 KB (five int32 row reads, three row writes) to
 //     ~0.7 KB (two dword row reads, one 16-bit row write, 64 provenance bytes).
 // Same provenance bytes, row table, backtrace and unpack as the generic kernel (its last tier).
-
-__device__ __forceinline__ int dpp_shr1(int x) { return __builtin_amdgcn_update_dpp(x, x, 0x138, 0xf, 0xf, false); }
 
 template <int CAP, int QCAP, int NW>
 __global__ __launch_bounds__(NW * 64) void wfa_affine_kernel_v3(
@@ -463,6 +428,7 @@ __global__ __launch_bounds__(NW * 64) void wfa_affine_kernel_v3(
     const uint8_t* P = arena + t.pattern_off;
     const uint8_t* T = arena + t.text_off;
     const int pl = (int)t.pattern_len, tl = (int)t.text_len;
+    const otg_mq::Seqs seq{P, T, pl, tl};
     const bool ef = t.endsfree != 0;
     const int pef = t.pattern_end_free, tef = t.text_end_free;
     const int kb = pl + 4;                        // ring index of diagonal k (4 entries of slack on the left)
@@ -552,55 +518,18 @@ __global__ __launch_bounds__(NW * 64) void wfa_affine_kernel_v3(
       int16_t* Mc = ringM + (size_t)sm * ws.capa;
       bool done = false;
       int qn = 0;
-      // drain: queued diagonals (probe matched all 8 bytes).  Pass 1 looks 16 bytes ahead; survivors are in long
-      // match runs: 64 bytes per pass, and once <= 4 diagonals remain the whole wave extends them one at a time
-      // (512 bytes per iteration) — TR reads have exact runs of hundreds of bases.
+      // drain (otg_match_queue.hpp): 16 bytes, then 64 per pass, then the wave-wide step; entries = k - lo, offsets in this score's HBM row,
+      // which another lane than the one that stored it reads: a workgroup fence at the head of every pass and behind the last.  The end test
+      // follows the drain, so a finished cell reports nothing.  A wave's queue (512) fills during its share of a sweep (`qn + 128`: the
+      // pipelined probe of one more chunk is still to come) from 1540 start diagonals on; both windows (4096, 12288) admit that.
+      auto wg_fence = [] { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); };
       auto drain = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        int pass = 0;
-        while (qn > 0) {
-          if (qn <= 4 && pass > 0) {
-            for (int e = 0; e < qn; ++e) {
-              const int kk = lo + (int)queue[e];
-              const int h = Mc[kk + kb];
-              const int v = h - kk;
-              const int m = otg_wave_match(P, T, v, h, imin(pl - v, tl - h), lane);
-              Mc[kk + kb] = (int16_t)(h + m);
-            }
-            qn = 0;
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-            break;
-          }
-          int wq = 0;
-          for (int q0 = 0; q0 < qn; q0 += 64) {
-            const bool act = q0 + lane < qn;
-            int kk = 0, h = 0, v = 0;
-            bool more = false;
-            if (act) {
-              kk = lo + (int)queue[q0 + lane];
-              h = Mc[kk + kb];
-              v = h - kk;
-              const int rem = imin(pl - v, tl - h);
-              int m, full;
-              if (pass == 0) {
-                const uint64_t xl = otg_load8(P + v) ^ otg_load8(T + h), xh = otg_load8(P + v + 8) ^ otg_load8(T + h + 8);
-                m = xl ? (__builtin_ctzll(xl) >> 3) : (xh ? 8 + (__builtin_ctzll(xh) >> 3) : 16);
-                m = imin(m, rem); full = 16;
-              } else { m = otg_match64(P, T, v, h, rem); full = 64; }
-              v += m; h += m;
-              more = (m == full) && v < pl && h < tl;
-              Mc[kk + kb] = (int16_t)h;
-            }
-            const unsigned long long mm = __ballot(more);
-            if (more) {
-              const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
-              queue[wq + rank] = (uint16_t)(kk - lo);
-            }
-            wq += __builtin_popcountll(mm);
-          }
-          qn = wq; ++pass;
-          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        }
+        otg_mq::drain<true>(queue, qn, lane, seq,
+            [&](int e) { return lo + e; },
+            [&](int k) -> int { return Mc[k + kb]; }, [&](int k, int h) { Mc[k + kb] = (int16_t)h; },
+            [&](int pass, int v, int h, int rem) { return otg_mq::probe_bytes(seq, pass, v, h, rem); },
+            wg_fence, [](int, int) { return false; });
+        wg_fence();
       };
       // raw 32-bit words (two adjacent 16-bit offsets) are queued untouched: any conversion right after the
       // load would force a wait for it.  Index k + kb - 1 .. : w0 = {Mo[k-1] | Mo[k]} is not used; we load
@@ -635,12 +564,7 @@ __global__ __launch_bounds__(NW * 64) void wfa_affine_kernel_v3(
           more = (m == 8) && v < pl && h < tl;
         }
         if (p_in) Mc[p_k + kb] = (int16_t)(p_valid ? h : NUL16);
-        const unsigned long long mq = __ballot(more);
-        if (more) {
-          const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mq >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mq, 0u));
-          queue[qn + rank] = (uint16_t)(p_k - lo);
-        }
-        qn += __builtin_popcountll(mq);
+        otg_mq::push(queue, qn, __ballot(more), more, p_k - lo);
       };
       for (int c = c0; c < c1; c += 64) {
         const int k = c + lane;
@@ -657,10 +581,10 @@ __global__ __launch_bounds__(NW * 64) void wfa_affine_kernel_v3(
         const int mo = (int)(int16_t)(w0 & 0xFFFFu);          // M[s-o-e][k]
         const int dop = (int)w0 >> 16;                        // M[s-o-e][k+1]
         const int mm = (int)(int16_t)(w1 & 0xFFFFu);          // M[s-x][k]
-        int ix = dpp_shr1(iold);                              // I[s-1][k-1]
+        int ix = otg_dpp_shr1(iold);                              // I[s-1][k-1]
         if (lane == 0) ix = carryI;
         carryI = __builtin_amdgcn_readlane(iold, 63);
-        int io = dpp_shr1(mo);                                // M[s-o-e][k-1]
+        int io = otg_dpp_shr1(mo);                                // M[s-o-e][k-1]
         if (lane == 0) io = carryMo;
         carryMo = __builtin_amdgcn_readlane(mo, 63);
         uint32_t bits = 0;
@@ -708,7 +632,7 @@ __global__ __launch_bounds__(NW * 64) void wfa_affine_kernel_v3(
             if (k <= hi) {
               const int h = Mc[k + kb];
               const int v = h - k;
-              fin = h >= 0 && ((h >= tl && pl - v <= pef) || (v >= pl && tl - h <= tef));
+              fin = h >= 0 && otg_ends_free_done(h, v, pl, tl, pef, tef);
             }
             const unsigned long long fm = __ballot(fin);
             if (fm) cand = c + (int)__builtin_ctzll(fm);

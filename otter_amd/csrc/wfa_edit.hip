@@ -17,19 +17,13 @@
 // when h>tlen or v>plen; k = h - v, offset = h.  End2end stops when M[s][tlen-plen] == tlen; ends-free
 // when any diagonal reaches a permitted boundary (score only: which diagonal does not matter).
 #include "otg_chain.hpp"
+#include "otg_match_queue.hpp"
 #include <algorithm>
 #include <cstdlib>
 
 namespace {
 
 using lds_i32 = __attribute__((address_space(3))) int32_t;
-
-__device__ __forceinline__ uint64_t load8(const uint8_t* p)
-{
-  uint64_t v;
-  __builtin_memcpy(&v, p, 8);
-  return v;
-}
 
 template <int CAP, int WPB, bool GLOBAL_WF>
 __global__ __launch_bounds__(WPB * 64) void wfa_edit_kernel(
@@ -100,7 +94,7 @@ __global__ __launch_bounds__(WPB * 64) void wfa_edit_kernel(
           const bool go = act && v < pl && h < tl;
           if (!__any(go)) break;
           if (go) {
-            const uint64_t x = load8(P + v) ^ load8(T + h);
+            const uint64_t x = otg_load8(P + v) ^ otg_load8(T + h);
             int m = x ? (__builtin_ctzll(x) >> 3) : 8;
             int rem = pl - v < tl - h ? pl - v : tl - h;
             m = m < rem ? m : rem;
@@ -110,7 +104,7 @@ __global__ __launch_bounds__(WPB * 64) void wfa_edit_kernel(
         }
         if (in) wf_wr(j, valid ? h : OTG_NULL_OFF);
         bool fin;
-        if (ef) fin = valid && ((h >= tl && pl - v <= pef) || (v >= pl && tl - h <= tef));
+        if (ef) fin = valid && otg_ends_free_done(h, v, pl, tl, pef, tef);
         else fin = valid && k == kend && h >= tl;
         any_done |= __any(fin) != 0;
       }
@@ -136,29 +130,11 @@ __global__ __launch_bounds__(WPB * 64) void wfa_edit_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------
-// v2 kernel (tiers 1 and 2): 16-bit offsets in LDS (requires sequence lengths < 65535), and the extend step
-// split in two so that no lane waits for the slowest diagonal of its chunk:
-//   sweep : per 64-diagonal chunk compute the new offsets (left neighbour by DPP wave_shr, right neighbour
-//           from LDS), probe 8 bytes, store; diagonals whose probe matched fully are appended to a
-//           wave-compacted queue in LDS (ballot + mbcnt);
-//   drain : the queue is re-read 64 entries at a time, 16 bytes are compared per iteration, finished
-//           diagonals drop out, the rest are re-compacted in place.
-// Work per wavefront is then ~Σ(iterations per diagonal) instead of Σ_chunks max(iterations in chunk).
+// v2 kernel (tiers 1 and 2): 16-bit offsets in LDS (requires sequence lengths < 65535), and the extend step split into a sweep and a
+// drain of the match-run queue (otg_match_queue.hpp): work per wavefront is then ~Σ(iterations per diagonal) instead of
+// Σ_chunks max(iterations in chunk).  Particular to this kernel: the left neighbour comes by DPP wave_shr, the right one from LDS; queue
+// entries are window slots (k - kbase); the queue is as long as the window, so a sweep never has to drain it on the way.
 using lds_u16 = __attribute__((address_space(3))) uint16_t;
-
-__device__ __forceinline__ int dpp_wave_shr1(int x)
-{
-  // lane i receives lane i-1 (lane 0 keeps its own value); GFX9 DPP wave_shr:1
-  return __builtin_amdgcn_update_dpp(x, x, 0x138, 0xf, 0xf, false);
-}
-
-struct u128 { uint64_t lo, hi; };
-__device__ __forceinline__ u128 load16(const uint8_t* p)
-{
-  u128 v;
-  __builtin_memcpy(&v, p, 16);
-  return v;
-}
 
 // bit-parallel tier whose band holds an estimated distance `need` (same threshold function the tier itself applies)
 __device__ __forceinline__ int otg_route_tier(const otg_align_task& t, int need, uint32_t tier_mask)
@@ -201,6 +177,7 @@ __global__ __launch_bounds__(WPB * 64) void wfa_edit_kernel_v2(
     const uint8_t* P = arena + t.pattern_off;
     const uint8_t* T = arena + t.text_off;
     const int pl = (int)t.pattern_len, tl = (int)t.text_len;
+    const otg_mq::Seqs seq{P, T, pl, tl};
     const bool ef = t.endsfree != 0;
     const int pef = t.pattern_end_free, tef = t.text_end_free;
     int lo = ef ? -t.pattern_begin_free : 0, hi = ef ? t.text_begin_free : 0;
@@ -242,7 +219,7 @@ __global__ __launch_bounds__(WPB * 64) void wfa_edit_kernel_v2(
           int o = OTG_NULL_OFF, r = OTG_NULL_OFF;
           if (k >= lo_prev && k <= hi_prev) { const int x = wf[j]; o = x == NUL ? OTG_NULL_OFF : x; }
           if (k + 1 >= lo_prev && k + 1 <= hi_prev) { const int x = wf[j + 1]; r = x == NUL ? OTG_NULL_OFF : x; }
-          int l = dpp_wave_shr1(o);
+          int l = otg_dpp_shr1(o);
           if (lane == 0) l = carry;
           carry = __builtin_amdgcn_readlane(o, 63);
           const int a = l + 1, b = o + 1;
@@ -253,7 +230,7 @@ __global__ __launch_bounds__(WPB * 64) void wfa_edit_kernel_v2(
         const bool valid = in && mx >= 0 && h <= tl && v <= pl;
         bool more = false;
         if (valid && v < pl && h < tl) {
-          const uint64_t x = load8(P + v) ^ load8(T + h);
+          const uint64_t x = otg_load8(P + v) ^ otg_load8(T + h);
           int m = x ? (__builtin_ctzll(x) >> 3) : 8;
           const int rem = pl - v < tl - h ? pl - v : tl - h;
           m = m < rem ? m : rem;
@@ -261,69 +238,17 @@ __global__ __launch_bounds__(WPB * 64) void wfa_edit_kernel_v2(
           more = (m == 8) && v < pl && h < tl;
         }
         if (in) wf[j] = (uint16_t)(valid ? h : NUL);
-        const unsigned long long mm = __ballot(more);
-        if (more) {
-          const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
-          queue[qn + rank] = (uint16_t)j;
-        }
-        qn += __builtin_popcountll(mm);
-        bool fin;
-        if (ef) fin = valid && !more && ((h >= tl && pl - v <= pef) || (v >= pl && tl - h <= tef));
-        else fin = false;
+        otg_mq::push(queue, qn, __ballot(more), more, j);
+        const bool fin = ef && valid && !more && otg_ends_free_done(h, v, pl, tl, pef, tef);
         any_done |= __ballot(fin) != 0ull;
       }
-      // ---- drain: 16 bytes in the first pass, then 64 bytes per pass; when <= 4 diagonals are left the whole
-      // wave extends them one at a time, 512 bytes per iteration (HiFi / TR reads: exact runs of hundreds of bases)
-      int pass = 0;
-      while (qn > 0) {
-        if (qn <= 4 && pass > 0) {
-          for (int q = 0; q < qn; ++q) {
-            const int j = queue[q];
-            int h = wf[j];
-            int v = h - (j + kbase);
-            const int rem = pl - v < tl - h ? pl - v : tl - h;
-            const int m = otg_wave_match(P, T, v, h, rem, lane);
-            h += m; v += m;
-            wf[j] = (uint16_t)h;
-            if (ef && ((h >= tl && pl - v <= pef) || (v >= pl && tl - h <= tef))) any_done = true;
-          }
-          qn = 0;
-          break;
-        }
-        int wq = 0;
-        for (int q0 = 0; q0 < qn; q0 += 64) {
-          const bool act = q0 + lane < qn;
-          int j = 0, h = 0, v = 0;
-          bool more = false;
-          if (act) {
-            j = queue[q0 + lane];
-            h = wf[j];
-            v = h - (j + kbase);
-            const int rem = pl - v < tl - h ? pl - v : tl - h;
-            int m, full;
-            if (pass == 0) {
-              const u128 a = load16(P + v), b = load16(T + h);
-              const uint64_t xl = a.lo ^ b.lo, xh = a.hi ^ b.hi;
-              m = xl ? (__builtin_ctzll(xl) >> 3) : (xh ? 8 + (__builtin_ctzll(xh) >> 3) : 16);
-              m = m < rem ? m : rem; full = 16;
-            } else { m = otg_match64(P, T, v, h, rem); full = 64; }
-            v += m; h += m;
-            more = (m == full) && v < pl && h < tl;
-            wf[j] = (uint16_t)h;
-          }
-          const unsigned long long mm = __ballot(more);
-          if (more) {
-            const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
-            queue[wq + rank] = (uint16_t)j;
-          }
-          wq += __builtin_popcountll(mm);
-          if (ef) {
-            const bool fin = act && !more && ((h >= tl && pl - v <= pef) || (v >= pl && tl - h <= tef));
-            any_done |= __ballot(fin) != 0ull;
-          }
-        }
-        qn = wq; ++pass;
-      }
+      // ---- drain: 16 bytes in the first pass, then 64 bytes per pass, then the wave-wide step (HiFi / TR reads: exact runs of hundreds of bases)
+      any_done |= otg_mq::drain<true>(queue, qn, lane, seq,
+          [&](int e) { return e + kbase; },
+          [&](int k) -> int { return wf[k - kbase]; }, [&](int k, int h) { wf[k - kbase] = (uint16_t)h; },
+          [&](int pass, int v, int h, int rem) { return otg_mq::probe_bytes(seq, pass, v, h, rem); },
+          [] {},
+          [&](int h, int k) { return ef && otg_ends_free_done(h, h - k, pl, tl, pef, tef); }) != 0ull;
       if (!ef && kend >= lo && kend <= hi) {
         const int x = wf[kend - kbase];
         any_done = (x != NUL && x >= tl);

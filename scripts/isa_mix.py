@@ -12,9 +12,11 @@ the mix is taken from the kernel's text: every vector instruction weighted by 8^
 the probe's table.  scripts/pmc_summarize.py multiplies SQ_INSTS_VALU by the resulting cycles per instruction.
 """
 import collections
+import concurrent.futures
 import json
 import os
 import re
+import shutil
 import subprocess
 import sys
 import tempfile
@@ -67,50 +69,61 @@ def short(n):
     return m.group(1) if m else n[:40]
 
 
+def hipcc_S(src, asm, extra=()):
+    """one source file to assembly with the library's flags (device code only); returns what the compiler wrote to stderr"""
+    p = subprocess.run([B.hipcc()] + [x for x in B.FLAGS if x != "-fPIC"] + ["-S", "--cuda-device-only"] + list(extra) + ["-o", asm, src], capture_output=True, text=True)
+    if p.returncode != 0:
+        raise RuntimeError("hipcc -S failed for %s:\n%s" % (src, p.stderr[-2000:]))
+    return p.stderr
+
+
+def kernel_insts(asm):
+    """(mangled function name, loop depth of the block as LLVM annotates it, mnemonic) for every instruction of an assembly file"""
+    cur, depth = None, 0
+    for ln in open(asm, errors="replace"):
+        m = re.match(r"\s*\.type\s+(\S+),@function", ln)
+        if m:
+            cur, depth = m.group(1), 0
+            continue
+        if cur is None:
+            continue
+        if ln.startswith(".Lfunc_end"):
+            cur = None
+            continue
+        m = re.match(r"\.LBB\d+_\d+:(.*)", ln)
+        if m:
+            d = re.search(r"Depth=(\d+)", m.group(1))
+            depth = int(d.group(1)) if d else 0
+            continue
+        m = re.match(r"\s+([a-z][a-z0-9_]+)", ln)
+        if m:
+            yield cur, depth, m.group(1)
+
+
 def main():
     tag = sys.argv[1] if len(sys.argv) > 1 else "r04"
     table = cost_table()
     out = {}
     tmp = tempfile.mkdtemp(prefix="isa_mix_")
-    procs = []
-    for f in FILES:
-        asm = os.path.join(tmp, f.replace(".hip", ".s"))
-        procs.append((f, asm, subprocess.Popen([B.hipcc()] + [x for x in B.FLAGS if x != "-fPIC"] + ["-S", "--cuda-device-only", "-o", asm, os.path.join(B.CSRC, f)],
-                                               stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)))
-    for f, asm, p in procs:
-        if p.wait() != 0:
-            raise RuntimeError("hipcc -S failed for " + f)
-        cur, depth = None, 0
-        acc = None
-        for ln in open(asm, errors="replace"):
-            m = re.match(r"\s*\.type\s+(\S+),@function", ln)
-            if m:
-                cur = m.group(1); depth = 0
-                acc = {"n": 0, "w": 0.0, "wc": 0.0, "cyc": 0.0, "fast": 0, "ops": collections.Counter()}
+    asms = [os.path.join(tmp, f.replace(".hip", ".s")) for f in FILES]
+    with concurrent.futures.ThreadPoolExecutor(len(FILES)) as pool:
+        list(pool.map(lambda fa: hipcc_S(os.path.join(B.CSRC, fa[0]), fa[1]), zip(FILES, asms)))
+    for f, asm in zip(FILES, asms):
+        accs = {}
+        for fn, depth, op in kernel_insts(asm):
+            if not op.startswith("v_"):
                 continue
-            if cur is None:
-                continue
-            if re.match(r"\s*s_endpgm", ln) or ln.startswith(".Lfunc_end"):
-                if acc and acc["n"]:
-                    name = subprocess.run(["c++filt", cur], capture_output=True, text=True).stdout.strip() or cur
-                    k = short(name)
-                    out[k] = {"file": f, "valu_insts_static": acc["n"], "fast_share_static": round(acc["fast"] / acc["n"], 4),
-                              "cycles_per_inst_static": round(acc["cyc"] / acc["n"], 4), "cycles_per_inst": round(acc["wc"] / acc["w"], 4),
-                              "top_ops": dict(acc["ops"].most_common(12))}
-                cur = None; acc = None
-                continue
-            m = re.match(r"\.LBB\d+_\d+:(.*)", ln)
-            if m:
-                d = re.search(r"Depth=(\d+)", m.group(1))
-                depth = int(d.group(1)) if d else 0
-                continue
-            m = re.match(r"\s+(v_[a-z0-9_]+)", ln)
-            if m and acc is not None:
-                op = m.group(1)
-                c = classify(op, table)
-                w = 8.0 ** depth
-                acc["n"] += 1; acc["cyc"] += c; acc["w"] += w; acc["wc"] += w * c; acc["fast"] += c < 3.0
-                acc["ops"][op] += 1
+            acc = accs.setdefault(fn, {"n": 0, "w": 0.0, "wc": 0.0, "cyc": 0.0, "fast": 0, "ops": collections.Counter()})
+            c = classify(op, table)
+            w = 8.0 ** depth
+            acc["n"] += 1; acc["cyc"] += c; acc["w"] += w; acc["wc"] += w * c; acc["fast"] += c < 3.0
+            acc["ops"][op] += 1
+        for fn, acc in accs.items():
+            name = subprocess.run(["c++filt", fn], capture_output=True, text=True).stdout.strip() or fn
+            out[short(name)] = {"file": f, "valu_insts_static": acc["n"], "fast_share_static": round(acc["fast"] / acc["n"], 4),
+                                "cycles_per_inst_static": round(acc["cyc"] / acc["n"], 4), "cycles_per_inst": round(acc["wc"] / acc["w"], 4),
+                                "top_ops": dict(acc["ops"].most_common(12))}
+    shutil.rmtree(tmp)
     res = {"what": "estimated SIMD cycles per wave64 vector instruction of each kernel: instruction classes from profiles/r04_valu_peak.json, weights 8^(loop depth) over the kernel's ISA",
            "cost_table": {k: round(v, 3) for k, v in sorted(table.items())}, "default_cycles": 4.15, "kernels": out}
     path = os.path.join(ROOT, "profiles", "%s_isa_mix.json" % tag)

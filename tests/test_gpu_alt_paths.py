@@ -23,12 +23,16 @@ AFFINE_ALL_BUT_ADMISSION = ["tests/test_gpu_affine.py::" + t for t in (
 # admits; without the register tiers the accounting must say so
 ROUTING = "tests/test_gpu_affine_routing.py"
 
+# the shared extend step (test_gpu_match_runs.py) with each kernel family as the first tier that sees its pairs
+MR_EDIT, MR_AFFINE = "tests/test_gpu_match_runs.py::test_match_runs_edit_exact", "tests/test_gpu_match_runs.py::test_match_runs_affine_exact"
+MR_EDIT_AD, MR_AFFINE_AD = "tests/test_gpu_match_runs.py::test_match_runs_edit_adaptive", "tests/test_gpu_match_runs.py::test_match_runs_affine_adaptive"
+
 CASES = [
     ("OTG_NO_AFFINE_BOUND", ["tests/test_gpu_affine.py"]),                               # no score bound: everything on the HBM-row tiers, un-pruned
-    ("OTG_AFFINE_REG=0", ["tests/test_gpu_affine.py", ROUTING]),                              # bound + HBM-row tiers only (what the register tiers fall back to)
+    ("OTG_AFFINE_REG=0", ["tests/test_gpu_affine.py", ROUTING, MR_AFFINE]),                              # bound + HBM-row tiers only (what the register tiers fall back to)
     ("OTG_AFFINE_REG=25", AFFINE_ALL_BUT_ADMISSION + ["tests/test_gpu_poa.py", ROUTING]),      # register tiers 1024 / 4096 / 8192 only: the 1536 / 2048 windows on the multi-wave tier
-    ("OTG_NO_AFFINE_V3", AFFINE_CORE),                                                   # generic kernel only
-    ("OTG_NO_MYERS", ["tests/test_gpu_edit.py::test_edit_small_mixed", "tests/test_gpu_edit.py::test_edit_long_ont"]),
+    ("OTG_NO_AFFINE_V3", AFFINE_CORE + [MR_AFFINE]),                                                   # generic kernel only
+    ("OTG_NO_MYERS", ["tests/test_gpu_edit.py::test_edit_small_mixed", "tests/test_gpu_edit.py::test_edit_long_ont", MR_EDIT]),
     ("OTG_NO_EDIT_ROUTE OTG_NO_EDIT_SORT", ["tests/test_gpu_edit.py"]),
     ("OTG_NO_EDIT_SAMPLE", ["tests/test_gpu_edit.py"]),
     ("OTG_EDIT_TIERS=255", ["tests/test_gpu_edit.py"]),                                 # all eight bit-parallel tiers (the two three-block ones only run on passes with millions of pairs otherwise)
@@ -43,15 +47,18 @@ CASES = [
     ("OTG_AFFINE_CONCURRENT=1", AFFINE_CORE + [ROUTING]),                                 # register tiers side by side on three streams whatever the batch size
     ("OTG_AFFINE_CONCURRENT=0", ["tests/test_gpu_affine.py::test_affine_small_mixed", "tests/test_gpu_pipeline.py::test_ont_kb", ROUTING]),   # ... and one after the other on a small batch
     # the adaptive mode's tier chains (wfa_adaptive.hip): byte-probe tiers only; the wide packed tier first; the 1024-diagonal LDS tier / the int32 tier alone for the gap-affine aligner
-    ("OTG_ADAPTIVE_EDIT_TIERS=12", ["tests/test_gpu_adaptive.py::test_adaptive_edit_small", "tests/test_gpu_adaptive.py::test_adaptive_edit_long", "tests/test_gpu_adaptive.py::test_adaptive_edit_wide_and_huge"]),
+    ("OTG_ADAPTIVE_EDIT_TIERS=12", ["tests/test_gpu_adaptive.py::test_adaptive_edit_small", "tests/test_gpu_adaptive.py::test_adaptive_edit_long", "tests/test_gpu_adaptive.py::test_adaptive_edit_wide_and_huge", MR_EDIT_AD]),
     ("OTG_ADAPTIVE_NO_WIDE_START", ["tests/test_gpu_adaptive.py::test_adaptive_edit_small", "tests/test_gpu_adaptive.py::test_adaptive_edit_wide_and_huge", "tests/test_gpu_adaptive.py::test_adaptive_pipeline_hifi_and_haps"]),
-    ("OTG_ADAPTIVE_EDIT_TIERS=16", ["tests/test_gpu_adaptive.py::test_adaptive_edit_small", "tests/test_gpu_adaptive.py::test_adaptive_edit_long", "tests/test_gpu_adaptive.py::test_adaptive_edit_parameters", "tests/test_gpu_adaptive.py::test_adaptive_edit_wide_and_huge", "tests/test_gpu_adaptive.py::test_adaptive_pipeline[0]"]),
-    ("OTG_ADAPTIVE_EDIT_TIERS=2", ["tests/test_gpu_adaptive.py::test_adaptive_edit_small", "tests/test_gpu_adaptive.py::test_adaptive_edit_long", "tests/test_gpu_adaptive.py::test_adaptive_edit_parameters", "tests/test_gpu_adaptive.py::test_adaptive_pipeline_hifi_and_haps"]),
-    ("OTG_ADAPTIVE_AFFINE_TIERS=2", ["tests/test_gpu_adaptive.py::test_adaptive_affine_small", "tests/test_gpu_adaptive.py::test_adaptive_affine_long", "tests/test_gpu_adaptive.py::test_adaptive_pipeline[0]"]),
-    ("OTG_ADAPTIVE_AFFINE_TIERS=8", ["tests/test_gpu_adaptive.py::test_adaptive_affine_small", "tests/test_gpu_adaptive.py::test_adaptive_affine_long", "tests/test_gpu_adaptive.py::test_adaptive_affine_parameters", "tests/test_gpu_adaptive.py::test_adaptive_pipeline[0]"]),
+    ("OTG_ADAPTIVE_EDIT_TIERS=16", ["tests/test_gpu_adaptive.py::test_adaptive_edit_small", "tests/test_gpu_adaptive.py::test_adaptive_edit_long", "tests/test_gpu_adaptive.py::test_adaptive_edit_parameters", "tests/test_gpu_adaptive.py::test_adaptive_edit_wide_and_huge", "tests/test_gpu_adaptive.py::test_adaptive_pipeline[0]", MR_EDIT_AD]),
+    ("OTG_ADAPTIVE_EDIT_TIERS=2", ["tests/test_gpu_adaptive.py::test_adaptive_edit_small", "tests/test_gpu_adaptive.py::test_adaptive_edit_long", "tests/test_gpu_adaptive.py::test_adaptive_edit_parameters", "tests/test_gpu_adaptive.py::test_adaptive_pipeline_hifi_and_haps", MR_EDIT_AD]),
+    ("OTG_ADAPTIVE_EDIT_TIERS=8", [MR_EDIT_AD]),                                          # the 16384-diagonal byte-probe tier first
+    ("OTG_ADAPTIVE_EDIT_TIERS=0", [MR_EDIT_AD]),                                          # the int32 row in HBM alone
+    ("OTG_ADAPTIVE_AFFINE_TIERS=2", ["tests/test_gpu_adaptive.py::test_adaptive_affine_small", "tests/test_gpu_adaptive.py::test_adaptive_affine_long", "tests/test_gpu_adaptive.py::test_adaptive_pipeline[0]", MR_AFFINE_AD]),
+    ("OTG_ADAPTIVE_AFFINE_TIERS=4", [MR_AFFINE_AD]),                                      # the byte-probe tier first
+    ("OTG_ADAPTIVE_AFFINE_TIERS=8", ["tests/test_gpu_adaptive.py::test_adaptive_affine_small", "tests/test_gpu_adaptive.py::test_adaptive_affine_long", "tests/test_gpu_adaptive.py::test_adaptive_affine_parameters", "tests/test_gpu_adaptive.py::test_adaptive_pipeline[0]", MR_AFFINE_AD]),
     ("OTG_ADAPTIVE_AFFINE_TIERS=10", ["tests/test_gpu_adaptive.py::test_adaptive_affine_small", "tests/test_gpu_adaptive.py::test_adaptive_affine_long", "tests/test_gpu_adaptive.py::test_adaptive_affine_other_penalties_and_wide", "tests/test_gpu_adaptive.py::test_adaptive_pipeline_hifi_and_haps"]),
-    ("OTG_ADAPTIVE_AFFINE_TIERS=18", ["tests/test_gpu_adaptive.py::test_adaptive_affine_small", "tests/test_gpu_adaptive.py::test_adaptive_affine_long", "tests/test_gpu_adaptive.py::test_adaptive_pipeline[0]"]),
-    ("OTG_ADAPTIVE_AFFINE_TIERS=0", ["tests/test_gpu_adaptive.py::test_adaptive_affine_small", "tests/test_gpu_adaptive.py::test_adaptive_affine_other_penalties_and_wide"]),
+    ("OTG_ADAPTIVE_AFFINE_TIERS=18", ["tests/test_gpu_adaptive.py::test_adaptive_affine_small", "tests/test_gpu_adaptive.py::test_adaptive_affine_long", "tests/test_gpu_adaptive.py::test_adaptive_pipeline[0]", MR_AFFINE_AD]),
+    ("OTG_ADAPTIVE_AFFINE_TIERS=0", ["tests/test_gpu_adaptive.py::test_adaptive_affine_small", "tests/test_gpu_adaptive.py::test_adaptive_affine_other_penalties_and_wide", MR_AFFINE_AD]),
 ]
 
 
