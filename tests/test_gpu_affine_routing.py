@@ -7,7 +7,7 @@ chain's counters and lists back after a launch; these tests compare every batch 
   1. partition: every task has one finisher, no list holds a task twice, the sort's output is a permutation, the segments add up,
      finished >= routed in chain order;
   2. routing: the tier the sort assigned equals affine_window / reg_tier restated below in plain integers;
-  3. the score bound is a bound: U * g >= the oracle's score (penalties 4,6,2: g = 2);
+  3. the score bound is a bound: U * g >= the oracle's score (g = the gcd of the penalties: 2 for 4,6,2; one window also runs 2,3,1 and 6,9,3);
   4. a register tier finishes what it admits: finished == routed, exactly;
   5. a pair with bytes outside ACGT is routed to its register tier, given up by it (the pack check) and finished by tier A;
   6. nothing reaches the generic kernel.
@@ -20,6 +20,7 @@ below is a condition on these inputs (a tighter bound pass moves the G, not the 
 The ends-free pairs of every window have a free begin of 640 bases and more: score 0 then has more start diagonals than a register tier's
 match-run queue holds (QCAP entries, and a push needs room for two per lane).  The tiers once pushed every start diagonal through that
 queue and handed such alignments to tier A; a tier that did so again would fail invariant 4 in every window."""
+import math
 import numpy as np
 import pytest
 import otter_amd
@@ -32,7 +33,15 @@ pytestmark = pytest.mark.gpu
 CAP = (1024, 1536, 2048, 4096, 8192)        # diagonals of window per register tier
 SEQB = (4096, 4608, 6144, 8192, 12288)      # bytes of 2-bit packed sequence pair per register tier
 NONE = 5                                     # routed: no register tier; finished: 5 = A, 6 = B, 7 = C
-G_UNIT = 2                                   # gcd of the penalties (4, 6 + 2, 2)
+PEN = (4, 6, 2)                              # the default penalties; (2,3,1) and (6,9,3) reduce to the same (2,4,1) with another gcd
+
+
+def gcd_unit(pen):
+    """g of wfa_affine_common.hpp (affine_penalties): the gcd of mismatch, gap open + extension and gap extension."""
+    x, o, e = pen
+    return math.gcd(math.gcd(x, o + e), e)
+
+
 QCAP, QPUSH = 384, 128                       # entries of a register tier's match-run queue; room one push asks for (`qn + 128 > QCAP`)
 
 
@@ -70,12 +79,14 @@ def reg_tier(t, U, mask):
 _cache = {}
 
 
-def _batch(name, oracle):
+def _batch(name, oracle, pen=PEN):
     if name not in _cache:
         pairs, forms = BUILDERS[name]()
-        arena, tasks = pair_tasks(pairs, forms)
-        _cache[name] = (arena, tasks, oracle.affine_align_batch(arena, tasks, want_cells=True))
-    return _cache[name]
+        _cache[name] = pair_tasks(pairs, forms)
+    if (name, pen) not in _cache:
+        arena, tasks = _cache[name]
+        _cache[(name, pen)] = (arena, tasks, oracle.affine_align_batch(arena, tasks, *pen, want_cells=True))
+    return _cache[(name, pen)]
 
 
 def _insertion_pair(core, ins, pos, flip):
@@ -243,10 +254,10 @@ BUILDERS.update({"edge%d" % c: _build_edge(c) for c in EDGE})
 
 
 # ---- the checks
-def _align(ctx, oracle, name):
-    """Runs batch `name` on ctx, compares it with the oracle (score, op string, cells) and returns (tasks, oracle scores, routing)."""
-    arena, tasks, (es, ec, ecells) = _batch(name, oracle)
-    gs, gc, gcells = ctx.affine_align_batch(arena, tasks, want_cells=True)
+def _align(ctx, oracle, name, pen=PEN):
+    """Runs batch `name` on ctx under penalties `pen`, compares it with the oracle (score, op string, cells) and returns (tasks, oracle scores, routing)."""
+    arena, tasks, (es, ec, ecells) = _batch(name, oracle, pen)
+    gs, gc, gcells = ctx.affine_align_batch(arena, tasks, *pen, want_cells=True)
     r = ctx.affine_last_routing(len(tasks))
     assert np.array_equal(gs, es), (name, [(int(i), int(gs[i]), int(es[i])) for i in np.flatnonzero(gs != es)[:8]])
     bad = [i for i in range(len(tasks)) if gc[i] != ec[i]]
@@ -269,8 +280,9 @@ def _report(name, tasks, r):
     print("  finished %s" % r["finished"].tolist())
 
 
-def _check_chain(name, tasks, es, r):
+def _check_chain(name, tasks, es, r, pen=PEN):
     """Invariants 1, 2, 3 and 6."""
+    g_unit = gcd_unit(pen)
     _report(name, tasks, r)
     n = len(tasks)
     routed, finished, seg, mask = r["routed"], r["finished"], r["seg"], r["mask"]
@@ -304,7 +316,7 @@ def _check_chain(name, tasks, es, r):
     assert np.array_equal(routed, exp), (name, [(int(i), int(routed[i]), int(exp[i]), int(r["bound"][i])) for i in np.flatnonzero(routed != exp)[:8]])
     # 3. the bound is a bound (in units of g)
     assert np.all(r["bound"] >= 0), name
-    assert np.all(r["bound"].astype(np.int64) * G_UNIT >= es), (name, [(int(i), int(r["bound"][i]), int(es[i])) for i in np.flatnonzero(r["bound"].astype(np.int64) * G_UNIT < es)[:8]])
+    assert np.all(r["bound"].astype(np.int64) * g_unit >= es), (name, [(int(i), int(r["bound"][i]), int(es[i])) for i in np.flatnonzero(r["bound"].astype(np.int64) * g_unit < es)[:8]])
     # 6. nothing reaches the generic kernel
     assert not np.any(finished == 7), (name, np.flatnonzero(finished == 7)[:8])
     if not mask:                                 # the control: without register tiers the accessor reports what ran, not what was planned
@@ -320,14 +332,10 @@ def _check_finishes(name, r):
     assert len(gave_up) == 0, (name, [(int(i), int(r["routed"][i]), int(r["finished"][i]), int(r["bound"][i])) for i in gave_up[:12]])
 
 
-@pytest.mark.parametrize("tier", range(5))
-def test_routing_per_window(gpu, oracle, tier):
-    """Ten end-to-end and twelve ends-free pairs built for one register window; at least 8 of each must be that window's by the restated
-    rule (with every tier enabled), and at least 8 of that window's ends-free pairs must have a free begin with more start diagonals than
-    the tier's match-run queue has room for (both conditions on the inputs); every pair is finished by the tier it was routed to."""
+def _routing_per_window(gpu, oracle, tier, pen):
     name = "window%d" % tier
-    tasks, es, r = _align(gpu, oracle, name)
-    _check_chain(name, tasks, es, r)
+    tasks, es, r = _align(gpu, oracle, name, pen)
+    _check_chain(name, tasks, es, r, pen)
     mine = _expected_tiers(tasks, r, mask=31) == tier
     ef = tasks["endsfree"] != 0
     assert np.count_nonzero(mine & ~ef) >= 8 and np.count_nonzero(mine & ef) >= 8, (name, np.count_nonzero(mine & ~ef), np.count_nonzero(mine & ef))
@@ -336,6 +344,26 @@ def test_routing_per_window(gpu, oracle, tier):
     wide = mine & ef & begin_free & (starts > QCAP + QPUSH)
     assert np.count_nonzero(wide) >= 8, (name, starts[ef].tolist())
     _check_finishes(name, r)
+    return es, r
+
+
+@pytest.mark.parametrize("tier", range(5))
+def test_routing_per_window(gpu, oracle, tier):
+    """Ten end-to-end and twelve ends-free pairs built for one register window; at least 8 of each must be that window's by the restated
+    rule (with every tier enabled), and at least 8 of that window's ends-free pairs must have a free begin with more start diagonals than
+    the tier's match-run queue has room for (both conditions on the inputs); every pair is finished by the tier it was routed to."""
+    _routing_per_window(gpu, oracle, tier, PEN)
+
+
+@pytest.mark.parametrize("pen", [(2, 3, 1), (6, 9, 3)], ids=["2-3-1", "6-9-3"])
+def test_routing_per_window_other_gcd(gpu, oracle, pen):
+    """The 1536 window's batch under penalties that reduce to the same (2,4,1) with g = 1 and g = 3: the same assertions, the bound scaled
+    by that g; bounds and routing are those of the default penalties (the chain works in units of g), the scores are theirs times g / 2."""
+    es, r = _routing_per_window(gpu, oracle, 1, pen)
+    _, es_default, r_default = _align(gpu, oracle, "window1")
+    assert np.array_equal(es.astype(np.int64) * 2, es_default.astype(np.int64) * gcd_unit(pen))
+    for k in ("bound", "routed", "finished"):
+        assert np.array_equal(r[k], r_default[k]), k
 
 
 @pytest.mark.parametrize("cap", sorted(EDGE))

@@ -23,15 +23,19 @@ AFFINE_ALL_BUT_ADMISSION = ["tests/test_gpu_affine.py::" + t for t in (
 # admits; without the register tiers the accounting must say so
 ROUTING = "tests/test_gpu_affine_routing.py"
 
+# the other penalty classes, gcds and ring sizes (test_gpu_affine_penalties.py) without the 6 kb pairs of its tier A / B / C crossings: the generic kernel
+# and the un-bounded tiers then see them too
+PENALTIES = ["tests/test_gpu_affine_penalties.py::" + t for t in ("test_standard_class_every_gcd", "test_generic_class", "test_ring_of_64_rows", "test_penalties_refused")]
+
 # the shared extend step (test_gpu_match_runs.py) with each kernel family as the first tier that sees its pairs
 MR_EDIT, MR_AFFINE = "tests/test_gpu_match_runs.py::test_match_runs_edit_exact", "tests/test_gpu_match_runs.py::test_match_runs_affine_exact"
 MR_EDIT_AD, MR_AFFINE_AD = "tests/test_gpu_match_runs.py::test_match_runs_edit_adaptive", "tests/test_gpu_match_runs.py::test_match_runs_affine_adaptive"
 
 CASES = [
-    ("OTG_NO_AFFINE_BOUND", ["tests/test_gpu_affine.py"]),                               # no score bound: everything on the HBM-row tiers, un-pruned
-    ("OTG_AFFINE_REG=0", ["tests/test_gpu_affine.py", ROUTING, MR_AFFINE]),                              # bound + HBM-row tiers only (what the register tiers fall back to)
+    ("OTG_NO_AFFINE_BOUND", ["tests/test_gpu_affine.py"] + PENALTIES),                               # no score bound: everything on the HBM-row tiers, un-pruned
+    ("OTG_AFFINE_REG=0", ["tests/test_gpu_affine.py", ROUTING, MR_AFFINE] + PENALTIES),                              # bound + HBM-row tiers only (what the register tiers fall back to)
     ("OTG_AFFINE_REG=25", AFFINE_ALL_BUT_ADMISSION + ["tests/test_gpu_poa.py", ROUTING]),      # register tiers 1024 / 4096 / 8192 only: the 1536 / 2048 windows on the multi-wave tier
-    ("OTG_NO_AFFINE_V3", AFFINE_CORE + [MR_AFFINE]),                                                   # generic kernel only
+    ("OTG_NO_AFFINE_V3", AFFINE_CORE + [MR_AFFINE] + PENALTIES),                                                   # generic kernel only
     ("OTG_NO_MYERS", ["tests/test_gpu_edit.py::test_edit_small_mixed", "tests/test_gpu_edit.py::test_edit_long_ont", MR_EDIT]),
     ("OTG_NO_EDIT_ROUTE OTG_NO_EDIT_SORT", ["tests/test_gpu_edit.py"]),
     ("OTG_NO_EDIT_SAMPLE", ["tests/test_gpu_edit.py"]),

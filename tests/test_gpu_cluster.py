@@ -19,6 +19,7 @@ def _compare(gpu, oracle, cases, **kw):
     assert np.array_equal(gl, el)
     assert np.array_equal(np.isnan(gb), np.isnan(eb))
     assert np.array_equal(np.nan_to_num(gb, nan=-7.0), np.nan_to_num(eb, nan=-7.0))
+    return el, eic, efc, eb
 
 
 def test_cluster_synthetic_matrices(gpu, oracle):

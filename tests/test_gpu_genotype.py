@@ -25,13 +25,14 @@ def _regions(rng, n_regions, amax, with_short=False):
     return arena, off, ln, np.asarray(first, dtype=np.uint32), np.asarray(counts, dtype=np.uint32)
 
 
-def _check(gpu, oracle, args):
-    P = abi.default_params()
+def _check(gpu, oracle, args, **kw):
+    P = abi.default_params(**kw)
     e = oracle.genotype_cluster_batch(P, *args)
     g = gpu.genotype_cluster_batch(P, *args)
     for i in (0, 1, 2, 4, 5):
         assert np.array_equal(g[i], e[i]), i
     assert np.allclose(g[3], e[3], rtol=1e-9, atol=0, equal_nan=True)
+    return e
 
 
 def test_genotype_small(gpu, oracle):

@@ -24,9 +24,8 @@ def compare(gpu_res, ora, batch):
         assert gs == os_, "allele %d sequence differs" % i
 
 
-def run_both(gpu, oracle, batch, **kw):
-    P = abi.default_params(**kw)
-    ora = oracle.assemble_batch(P, batch)
+def run_against(gpu, P, batch, ora):
+    """The GPU pipeline under P against `ora`, the oracle's result for the same P and batch: records, sequences and the stats fields."""
     res = gpu.assemble(P, batch)
     compare(res, ora, batch)
     st = gpu.assemble_stats()
@@ -34,6 +33,11 @@ def run_both(gpu, oracle, batch, **kw):
     for f in ("edit_tasks", "edit_cells", "edit_seq_bytes", "affine_tasks", "affine_cells", "affine_seq_bytes", "allele_bytes", "algorithmic_bytes"):
         assert int(st[f]) == int(os_[f]), f
     return res, st
+
+
+def run_both(gpu, oracle, batch, **kw):
+    P = abi.default_params(**kw)
+    return run_against(gpu, P, batch, oracle.assemble_batch(P, batch))
 
 
 def test_config0_hifi_500bp(gpu, oracle):
