@@ -13,7 +13,8 @@
 // whose left(k) exceeds the smallest by more than `max_dist` are dropped from both ends of the wavefront, never past the end
 // diagonal(s); the I / D wavefronts of that score are cut to the same range.  The cut reads the offset of EVERY live diagonal, so none
 // of the exact chain's devices applies here (score bound, diamond, bit-parallel tiers, reversed sequences): these kernels run the
-// plain wavefront recurrence, score by score, on the diagonals the cut leaves.
+// plain wavefront recurrence, score by score, on the diagonals the cut leaves.  The packed pair, its pack loop and the 32-base probe of the
+// window kernels' sweeps are written once, in otg_packed_pair.hpp.
 //
 // What the cut buys: a wavefront no longer grows by two diagonals per score.  On the tandem-repeat workloads it stays 50-500 diagonals
 // wide (shifts by a repeat unit extend as far as the main diagonal, so they survive the cut; scripts/heuristic_widths.py), against
@@ -30,7 +31,7 @@
 //   gap-affine  wfa_affine_adaptive_lds_kernel<256> (eleven i16 rows per wave, null discipline per row) -> the 1 024 window with four waves per
 //               alignment and the 4 096 one with eight (wfa_affine_adaptive_mw_kernel: chunks dealt to the waves, one LDS barrier per score) ->
 //               byte probes 1 024 -> int32 rings in HBM.
-#include "otg_wfadaptive.hpp"
+#include "otg_packed_pair.hpp"
 #include "otg_chain.hpp"
 #include "otg_match_queue.hpp"
 #include <algorithm>
@@ -43,13 +44,6 @@ using namespace otg_adaptive;
 namespace {
 
 __device__ __forceinline__ int wave_min_i32(int v) { return -otg_wave_max_i32(-v); }      // |v| <= 2^30 here
-
-// lane masks of comparisons (v_cmp into an SGPR pair; the logic on them runs on the scalar unit) and a select on a lane mask.  Written with bools,
-// hipcc 7.2 turns "does any lane ..." and "or into the flag" into a select, an and and a compare on the vector unit each (see wfa_affine_reg.hip)
-__device__ __forceinline__ unsigned long long mk_eq(int a, int b) { return __builtin_amdgcn_sicmp(a, b, 32); }
-__device__ __forceinline__ unsigned long long mk_sle(int a, int b) { return __builtin_amdgcn_sicmp(a, b, 41); }
-__device__ __forceinline__ unsigned long long mk_ule(uint32_t a, uint32_t b) { return __builtin_amdgcn_uicmp(a, b, 37); }
-__device__ __forceinline__ int sel(unsigned long long m, int a, int b) { int r; asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m)); return r; }     // lane in m ? a : b
 
 // ---------------------------------------------------------------------------------------------------
 // Edit distance, score only.  Replaces WFAlignerEdit(Score, MemoryMed)::alignEnd2End / alignEndsFree + getAlignmentScore() under the
@@ -205,86 +199,6 @@ __global__ __launch_bounds__(WPB * 64) void wfa_edit_adaptive_kernel(
   }
 }
 
-// ---------------------------------------------------------------------------------------------------
-// The packed pair of PackedPair below written by a whole block (the multi-wave tiers): thread `tid` of `nt` packs words tid, tid + nt, ...; returns
-// whether THIS thread met a byte outside ACGT.
-__device__ __forceinline__ bool pack_pair_block(volatile lds_u32* SQ, const uint8_t* P, int pl, const uint8_t* T, int tl, int offT, int tid, int nt)
-{
-  bool bad = false;
-  auto pack = [&](const uint8_t* S, int len, int woff) {
-    for (int q = tid; q < (len + 15) / 16 + 3; q += nt) {
-      uint32_t w = 0;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int b0 = 16 * q + 8 * j;
-        const uint64_t x = b0 < len ? otg_load8(S + b0) : 0ull;        // (the arena has 64 bytes of slack behind its last sequence)
-#pragma unroll
-        for (int t2 = 0; t2 < 8; ++t2) {
-          const uint32_t c = (uint32_t)(x >> (8 * t2)) & 0xffu;
-          const uint32_t code = (c >> 1) & 3u;
-          if (b0 + t2 < len && c != ((0x47544341u >> (8 * code)) & 0xffu)) bad = true;
-          w |= code << (2 * (8 * j + t2));
-        }
-      }
-      SQ[woff + q] = w;
-    }
-  };
-  pack(P, pl, 0);
-  pack(T, tl, offT);
-  return __ballot(bad) != 0ull;
-}
-
-// Both sequences of a pair packed to 2 bits per base in LDS (word q = bases 16 q .. 16 q + 15, code (byte >> 1) & 3; pattern at word 0,
-// text at word offT): a probe compares 32 bases with six LDS reads instead of two HBM round trips — under the cut a wave advances one
-// score at a time and every score ends in a probe, so the probe latency IS the kernel's speed.  A pair with a byte outside ACGT, or too
-// long for the wave's share of LDS, is not packed (`ok` false) and runs on the byte probes of the generic kernels.
-struct PackedPair {
-  volatile lds_u32* SQ; int offT; bool ok;
-  // seqw = words of LDS this wave owns for the pair (dynamic shared memory, sized by the launcher from the batch's longest read)
-  __device__ __forceinline__ void init(const uint8_t* P, int pl, const uint8_t* T, int tl, int lane, int seqw)
-  {
-    offT = (pl + 15) / 16 + 3;
-    ok = offT + (tl + 15) / 16 + 3 <= seqw;
-    if (!ok) return;
-    bool bad = false;
-    auto pack = [&](const uint8_t* S, int len, int woff) {
-      for (int q = lane; q < (len + 15) / 16 + 3; q += 64) {
-        uint32_t w = 0;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int b0 = 16 * q + 8 * j;
-          const uint64_t x = b0 < len ? otg_load8(S + b0) : 0ull;        // (the arena has 64 bytes of slack behind its last sequence)
-#pragma unroll
-          for (int t2 = 0; t2 < 8; ++t2) {
-            const uint32_t c = (uint32_t)(x >> (8 * t2)) & 0xffu;
-            const uint32_t code = (c >> 1) & 3u;
-            if (b0 + t2 < len && c != ((0x47544341u >> (8 * code)) & 0xffu)) bad = true;
-            w |= code << (2 * (8 * j + t2));
-          }
-        }
-        SQ[woff + q] = w;
-      }
-    };
-    pack(P, pl, 0);
-    pack(T, tl, offT);
-    ok = __ballot(bad) == 0ull;
-  }
-  __device__ __forceinline__ uint64_t ld32(int woff, int pos) const
-  {
-    const int w = woff + (pos >> 4);
-    const uint32_t sh = (uint32_t)(pos & 15) * 2u;
-    const uint32_t d0 = SQ[w], d1 = SQ[w + 1], d2 = SQ[w + 2];
-    return (uint64_t)__builtin_amdgcn_alignbit(d1, d0, sh) | ((uint64_t)__builtin_amdgcn_alignbit(d2, d1, sh) << 32);
-  }
-  // equal bases from pattern position v / text position h on, at most 32 and at most rem (0 <= v, h; rem >= 0)
-  __device__ __forceinline__ int match32(int v, int h, int rem) const
-  {
-    const uint64_t xx = ld32(0, v) ^ ld32(offT, h);
-    const int m = xx ? (int)(__builtin_ctzll(xx) >> 1) : 32;
-    return imin(m, rem);
-  }
-};
-
 // The fast edit tier: window of CAP diagonals (signed 16-bit offsets, null = -32768) + the packed pair in LDS.  Invariant that removes every
 // range test from the sweep: a slot of the window is non-null only while its diagonal is inside the live range — the window is null-filled per
 // pair, and the diagonals a cut drops are nulled right there — so the recurrence reads its neighbours unconditionally.
@@ -426,7 +340,7 @@ __global__ __launch_bounds__(WPB * 64) void wfa_edit_adaptive_lds_kernel(
         }
       };
       // ---- sweep (branch-free per lane)
-      const volatile lds_u32* SQ = pk.SQ;
+      const volatile lds_char* SQB = (const volatile lds_char*)pk.SQ;
       for (int c = lo; c <= hi; c += 64) {
         const int k = c + lane;
         const int o = wfs.ld(k), r = wfs.ld(k + 1);            // null outside the live range: no range tests
@@ -436,29 +350,14 @@ __global__ __launch_bounds__(WPB * 64) void wfa_edit_adaptive_lds_kernel(
         const int v = mx - k;
         const int t1 = tl - mx, t2 = pl - v;                              // what is left of the text / the pattern
         const unsigned long long vm = mk_ule((uint32_t)mx, (uint32_t)tl) & mk_ule((uint32_t)v, (uint32_t)pl) & mk_sle(k, hi);      // valid cells
-        // the probe, wherever the offsets point: equal leading bases of pattern[pv ..] and text[ph ..], at most 32
-        auto probe = [&](int pv, int ph) -> int {
-          const int wp = (pv >> 2) & ~3, wt = offT4 + ((ph >> 2) & ~3);    // byte addresses of the first word of each 32-base window
-          const uint32_t sp = (uint32_t)(pv & 15) * 2u, st = (uint32_t)(ph & 15) * 2u;
-          const volatile lds_u32* pp = (const volatile lds_u32*)((const volatile __attribute__((address_space(3))) char*)SQ + wp);
-          const volatile lds_u32* pt = (const volatile lds_u32*)((const volatile __attribute__((address_space(3))) char*)SQ + wt);
-          const uint32_t p0 = pp[0], p1 = pp[1], p2 = pp[2], q0 = pt[0], q1 = pt[1], q2 = pt[2];
-          const uint32_t xl = __builtin_amdgcn_alignbit(p1, p0, sp) ^ __builtin_amdgcn_alignbit(q1, q0, st);
-          const uint32_t xh = __builtin_amdgcn_alignbit(p2, p1, sp) ^ __builtin_amdgcn_alignbit(q2, q1, st);
-          uint32_t flo, fhi;      // v_ffbl_b32: index of the lowest set bit, 0xffffffff for zero — which is what the min below wants
-          asm("v_ffbl_b32 %0, %1" : "=v"(flo) : "v"(xl));
-          asm("v_ffbl_b32 %0, %1" : "=v"(fhi) : "v"(xh));
-          const uint32_t a = flo < (fhi | 32u) ? flo : (fhi | 32u);
-          return (int)((a < 64u ? a : 64u) >> 1);
-        };
-        const int pm = probe(v, mx);
+        const int pm = probe32(SQB, offT4, v, mx);
         int m = imin(imin(pm, t1), t2);                                  // the run, limited by the sequence ends
         unsigned long long mm = vm & mk_eq(imin(imin(pm, t1 - 1), t2 - 1), 32);        // more: a full probe with more than 32 bases left of both sequences
         // A run that outlives its probe (one cell in 120 at ONT divergence, i.e. four chunks in ten) gets a second probe right here, by the whole
         // wave: the queue, its drain and their loops — a fixed cost of ~40 vector and as many scalar instructions per score — are then left to runs
         // beyond 64 bases (one score in a hundred)
         if (mm) {
-          const int pm2 = probe(v + 32, mx + 32);
+          const int pm2 = probe32(SQB, offT4, v + 32, mx + 32);
           const int m2 = imin(imin(pm2, t1 - 32), t2 - 32);
           m = sel(mm, m2 + 32, m);
           mm &= mk_eq(imin(imin(pm2, t1 - 33), t2 - 33), 32);
@@ -561,7 +460,6 @@ __global__ __launch_bounds__(NW * 64) void wfa_edit_adaptive_mw_kernel(
   __shared__ uint32_t s_tk;
   __shared__ int s_bad;
   extern __shared__ uint32_t s_dyn[];                         // [seqw]: the packed pair of the block's alignment
-  using lds_char = __attribute__((address_space(3))) char;
   const int tid = threadIdx.x, lane = tid & 63;
   auto U = [](int x) { return __builtin_amdgcn_readfirstlane(x); };
   const int ww = U(tid >> 6);
@@ -605,7 +503,7 @@ __global__ __launch_bounds__(NW * 64) void wfa_edit_adaptive_mw_kernel(
     const int offT = (pl + 15) / 16 + 3;
     bool overflow = pl > 32766 || tl > 32766 || hi - lo + PAD > CAP || offT + (tl + 15) / 16 + 3 > seqw;
     if (!overflow) {
-      if (pack_pair_block(SQ, P, pl, T, tl, offT, tid, NT) && lane == 0) s_bad = 1;
+      if (pack_pair(SQ, P, pl, T, tl, offT, tid, NT) && lane == 0) s_bad = 1;
       for (int q = tid; q < CAP; q += NT) ROWS32[q] = 0x80008000u;                  // both rows
     }
     __syncthreads();
@@ -658,25 +556,11 @@ __global__ __launch_bounds__(NW * 64) void wfa_edit_adaptive_mw_kernel(
         const bool inr = k <= hi;
         const unsigned long long inrm = __builtin_amdgcn_ballot_w64(inr);
         const unsigned long long vm = inrm & mk_ule((uint32_t)mx, (uint32_t)tl) & mk_ule((uint32_t)v, (uint32_t)pl);
-        auto probe = [&](int pv, int ph) -> int {
-          const int wp = (pv >> 2) & ~3, wt = offT4 + ((ph >> 2) & ~3);
-          const uint32_t sp = (uint32_t)(pv & 15) * 2u, st = (uint32_t)(ph & 15) * 2u;
-          const volatile lds_u32* pp = (const volatile lds_u32*)(SQB + wp);
-          const volatile lds_u32* pt = (const volatile lds_u32*)(SQB + wt);
-          const uint32_t p0 = pp[0], p1 = pp[1], p2 = pp[2], q0 = pt[0], q1 = pt[1], q2 = pt[2];
-          const uint32_t xl = __builtin_amdgcn_alignbit(p1, p0, sp) ^ __builtin_amdgcn_alignbit(q1, q0, st);
-          const uint32_t xh = __builtin_amdgcn_alignbit(p2, p1, sp) ^ __builtin_amdgcn_alignbit(q2, q1, st);
-          uint32_t flo, fhi;
-          asm("v_ffbl_b32 %0, %1" : "=v"(flo) : "v"(xl));
-          asm("v_ffbl_b32 %0, %1" : "=v"(fhi) : "v"(xh));
-          const uint32_t a = flo < (fhi | 32u) ? flo : (fhi | 32u);
-          return (int)((a < 64u ? a : 64u) >> 1);
-        };
-        const int pm = probe(v, mx);
+        const int pm = probe32(SQB, offT4, v, mx);
         int m = imin(imin(pm, t1), t2);
         unsigned long long mm = vm & mk_eq(imin(imin(pm, t1 - 1), t2 - 1), 32);
         if (mm) {
-          const int pm2 = probe(v + 32, mx + 32);
+          const int pm2 = probe32(SQB, offT4, v + 32, mx + 32);
           const int m2 = imin(imin(pm2, t1 - 32), t2 - 32);
           m = sel(mm, m2 + 32, m);
           mm &= mk_eq(imin(imin(pm2, t1 - 33), t2 - 33), 32);
@@ -998,7 +882,6 @@ __global__ __launch_bounds__(WPB * 64) void wfa_affine_adaptive_lds_kernel(
   __shared__ __attribute__((aligned(16))) int16_t s_rows[WPB][NROWS][CAP];
   __shared__ __attribute__((aligned(16))) uint32_t s_q[WPB][QCAP];
   extern __shared__ uint32_t s_dyn[];                         // [WPB][seqw]: the packed pairs
-  using lds_char = __attribute__((address_space(3))) char;
   const int lane = threadIdx.x & 63;
   const int wib = threadIdx.x >> 6;
   uint8_t* my = ws.base + (size_t)(blockIdx.x * WPB + wib) * ws.stride;
@@ -1155,25 +1038,11 @@ __global__ __launch_bounds__(WPB * 64) void wfa_affine_adaptive_lds_kernel(
         const int v = mx - k;
         const int t1 = tl - mx, t2 = pl - v;
         const unsigned long long vm = inrm & mk_ule((uint32_t)mx, (uint32_t)tl) & mk_ule((uint32_t)v, (uint32_t)pl);      // valid cells
-        auto probe = [&](int pv, int ph) -> int {      // equal leading bases of pattern[pv ..] and text[ph ..], at most 32
-          const int wp = (pv >> 2) & ~3, wt = offT4 + ((ph >> 2) & ~3);
-          const uint32_t sp = (uint32_t)(pv & 15) * 2u, st = (uint32_t)(ph & 15) * 2u;
-          const volatile lds_u32* pp = (const volatile lds_u32*)(SQB + wp);
-          const volatile lds_u32* pt = (const volatile lds_u32*)(SQB + wt);
-          const uint32_t p0 = pp[0], p1 = pp[1], p2 = pp[2], q0 = pt[0], q1 = pt[1], q2 = pt[2];
-          const uint32_t xl = __builtin_amdgcn_alignbit(p1, p0, sp) ^ __builtin_amdgcn_alignbit(q1, q0, st);
-          const uint32_t xh = __builtin_amdgcn_alignbit(p2, p1, sp) ^ __builtin_amdgcn_alignbit(q2, q1, st);
-          uint32_t flo, fhi;
-          asm("v_ffbl_b32 %0, %1" : "=v"(flo) : "v"(xl));
-          asm("v_ffbl_b32 %0, %1" : "=v"(fhi) : "v"(xh));
-          const uint32_t a = flo < (fhi | 32u) ? flo : (fhi | 32u);
-          return (int)((a < 64u ? a : 64u) >> 1);
-        };
-        const int pm = probe(v, mx);
+        const int pm = probe32(SQB, offT4, v, mx);
         int m = imin(imin(pm, t1), t2);
         unsigned long long mq = vm & mk_eq(imin(imin(pm, t1 - 1), t2 - 1), 32);            // more: a full probe with more than 32 bases left of both sequences
         if (mq) {             // a second probe by the whole wave where a run outlives the first (as in the edit tier): the queue is for runs beyond 64 bases
-          const int pm2 = probe(v + 32, mx + 32);
+          const int pm2 = probe32(SQB, offT4, v + 32, mx + 32);
           const int m2 = imin(imin(pm2, t1 - 32), t2 - 32);
           m = sel(mq, m2 + 32, m);
           mq &= mk_eq(imin(imin(pm2, t1 - 33), t2 - 33), 32);
@@ -1256,7 +1125,6 @@ __global__ __launch_bounds__(NW * 64) void wfa_affine_adaptive_mw_kernel(
   __shared__ uint32_t s_tk;
   __shared__ int s_bad;
   extern __shared__ uint32_t s_dyn[];                         // [seqw]: the packed pair of the block's alignment
-  using lds_char = __attribute__((address_space(3))) char;
   const int tid = threadIdx.x, lane = tid & 63;
   auto U = [](int x) { return __builtin_amdgcn_readfirstlane(x); };
   const int ww = U(tid >> 6);
@@ -1334,7 +1202,7 @@ __global__ __launch_bounds__(NW * 64) void wfa_affine_adaptive_mw_kernel(
     const int lo0 = ef ? imax(-t.pattern_begin_free, -pl) : 0, hi0 = ef ? imin(t.text_begin_free, tl) : 0;
     if (hi0 - lo0 + PAD > CAP) fail = true;
     if (!fail) {
-      if (pack_pair_block(SQ, P, pl, T, tl, offT, tid, NT) && lane == 0) s_bad = 1;
+      if (pack_pair(SQ, P, pl, T, tl, offT, tid, NT) && lane == 0) s_bad = 1;
       for (int q = tid; q < NROWS * CAP / 2; q += NT) ROWS32[q] = 0x80008000u;
     }
     __syncthreads();
@@ -1419,25 +1287,11 @@ __global__ __launch_bounds__(NW * 64) void wfa_affine_adaptive_mw_kernel(
         const int v = mx - k;
         const int t1 = tl - mx, t2 = pl - v;
         const unsigned long long vm = inrm & mk_ule((uint32_t)mx, (uint32_t)tl) & mk_ule((uint32_t)v, (uint32_t)pl);      // valid cells
-        auto probe = [&](int pv, int ph) -> int {      // equal leading bases of pattern[pv ..] and text[ph ..], at most 32
-          const int wp = (pv >> 2) & ~3, wt = offT4 + ((ph >> 2) & ~3);
-          const uint32_t sp = (uint32_t)(pv & 15) * 2u, st = (uint32_t)(ph & 15) * 2u;
-          const volatile lds_u32* pp = (const volatile lds_u32*)(SQB + wp);
-          const volatile lds_u32* pt = (const volatile lds_u32*)(SQB + wt);
-          const uint32_t p0 = pp[0], p1 = pp[1], p2 = pp[2], q0 = pt[0], q1 = pt[1], q2 = pt[2];
-          const uint32_t xl = __builtin_amdgcn_alignbit(p1, p0, sp) ^ __builtin_amdgcn_alignbit(q1, q0, st);
-          const uint32_t xh = __builtin_amdgcn_alignbit(p2, p1, sp) ^ __builtin_amdgcn_alignbit(q2, q1, st);
-          uint32_t flo, fhi;
-          asm("v_ffbl_b32 %0, %1" : "=v"(flo) : "v"(xl));
-          asm("v_ffbl_b32 %0, %1" : "=v"(fhi) : "v"(xh));
-          const uint32_t a = flo < (fhi | 32u) ? flo : (fhi | 32u);
-          return (int)((a < 64u ? a : 64u) >> 1);
-        };
-        const int pm = probe(v, mx);
+        const int pm = probe32(SQB, offT4, v, mx);
         int m = imin(imin(pm, t1), t2);
         unsigned long long mq = vm & mk_eq(imin(imin(pm, t1 - 1), t2 - 1), 32);            // more: a full probe with more than 32 bases left of both sequences
         if (mq) {             // a second probe by the whole wave where a run outlives the first (as in the edit tier): the queue is for runs beyond 64 bases
-          const int pm2 = probe(v + 32, mx + 32);
+          const int pm2 = probe32(SQB, offT4, v + 32, mx + 32);
           const int m2 = imin(imin(pm2, t1 - 32), t2 - 32);
           m = sel(mq, m2 + 32, m);
           mq &= mk_eq(imin(imin(pm2, t1 - 33), t2 - 33), 32);

@@ -213,6 +213,49 @@ def test_adaptive_affine_other_penalties_and_wide(gpu, oracle, adaptive):
     _check_affine(gpu, oracle, arena, tasks)
 
 
+EDGE_LENS = [15, 16, 17, 31, 32, 33, 63, 64, 65, 95, 96, 97]
+
+
+def _edge_pairs():
+    """pairs for test_adaptive_packed_pair_edges: (pattern, text) with both lengths from EDGE_LENS, differing by 0, 1 and 16"""
+    rng = np.random.default_rng(52)
+    combos = [(n, n) for n in EDGE_LENS]
+    for a, b in [(x, y) for x in EDGE_LENS for y in EDGE_LENS if y - x in (1, 16)]:
+        combos += [(a, b), (b, a)]
+    sub = lambda s, i, c=None: s[:i] + (c or bytes([next(x for x in b"ACGT" if x != s[i])])) + s[i + 1:]
+    pairs = []
+    for pl, tl in combos:
+        s = rand_seq(rng, max(pl, tl))
+        n = min(pl, tl)
+        pairs.append((s[:pl], s[:tl]))                                 # identical: the run ends exactly at the end of a sequence
+        where = [n - 1] + ([i for i in (31, 32, 33, 63, 64, 65) if i < n - 1] if pl == tl else [])
+        pairs += [(s[:pl], sub(s, i)[:tl]) for i in where]             # one mismatch: the last base, around the probe boundaries
+    for pl, tl in [(33, 33), (64, 65), (16, 32), (97, 96)]:            # a byte outside ACGT: not a pair for the packed tiers
+        s = rand_seq(rng, max(pl, tl))
+        pairs += [(sub(s[:pl], pl - 1, b"N"), s[:tl]), (sub(s[:pl], 0, b"N"), s[:tl]), (s[:pl], sub(s[:tl], tl - 1, b"N")), (s[:pl], sub(s[:tl], 0, b"N"))]
+    s = rand_seq(rng, 65)
+    pairs += [(s.lower(), s), (s[:33].lower(), s[:33].lower())]
+    for L in (289, 300, 305, 320):                                     # long enough for the gap-affine kernels to run more than a few scores
+        s = rand_seq(rng, L)
+        pairs += [(s, mutate(rng, s, 0.08)), (s, sub(s, L - 1)), (s, s[:L - 16])]
+    return pairs
+
+
+def test_adaptive_packed_pair_edges(gpu, oracle, adaptive):
+    """the 2-bit pack and the 32-base probe (otg_packed_pair.hpp) and the extend step of the packed window kernels where they can go wrong: runs that
+    end at the end of a sequence on and around the first probe, the second probe and the queue (32, 64, 65+ bases), one mismatch as the last base
+    and at bases 31 .. 33 and 63 .. 65, bytes outside ACGT at either end of either sequence and lower-case pairs (passed on to the byte probes);
+    every pair end-to-end and ends-free (what the longer sequence has left is free at its end), edit and gap-affine"""
+    pairs = _edge_pairs()
+    ef = [(0, max(len(a) - len(b), 0), 0, max(len(b) - len(a), 0)) for a, b in pairs]
+    arena, tasks = pair_tasks(pairs + pairs, [None] * len(pairs) + ef)
+    got, cells = gpu.edit_distance_batch(arena, tasks, want_cells=True)
+    exp, ecells = oracle.edit_distance_batch(arena, tasks, want_cells=True)
+    assert np.array_equal(got, exp), [(int(i), int(got[i]), int(exp[i])) for i in np.flatnonzero(got != exp)[:8]]
+    assert np.array_equal(cells, ecells)
+    _check_affine(gpu, oracle, arena, tasks)
+
+
 def _compare_pipeline(res, ora):
     assert np.array_equal(res["regions"]["status"], ora["regions"]["status"])
     assert np.array_equal(res["regions"]["fc"], ora["regions"]["fc"])

@@ -31,6 +31,9 @@ PENALTIES = ["tests/test_gpu_affine_penalties.py::" + t for t in ("test_standard
 MR_EDIT, MR_AFFINE = "tests/test_gpu_match_runs.py::test_match_runs_edit_exact", "tests/test_gpu_match_runs.py::test_match_runs_affine_exact"
 MR_EDIT_AD, MR_AFFINE_AD = "tests/test_gpu_match_runs.py::test_match_runs_edit_adaptive", "tests/test_gpu_match_runs.py::test_match_runs_affine_adaptive"
 
+# the packed pair, probe and extend step of the adaptive window kernels, with each of them as the first tier
+PP_EDGES = "tests/test_gpu_adaptive.py::test_adaptive_packed_pair_edges"
+
 CASES = [
     ("OTG_NO_AFFINE_BOUND", ["tests/test_gpu_affine.py"] + PENALTIES),                               # no score bound: everything on the HBM-row tiers, un-pruned
     ("OTG_AFFINE_REG=0", ["tests/test_gpu_affine.py", ROUTING, MR_AFFINE] + PENALTIES),                              # bound + HBM-row tiers only (what the register tiers fall back to)
@@ -53,15 +56,15 @@ CASES = [
     # the adaptive mode's tier chains (wfa_adaptive.hip): byte-probe tiers only; the wide packed tier first; the 1024-diagonal LDS tier / the int32 tier alone for the gap-affine aligner
     ("OTG_ADAPTIVE_EDIT_TIERS=12", ["tests/test_gpu_adaptive.py::test_adaptive_edit_small", "tests/test_gpu_adaptive.py::test_adaptive_edit_long", "tests/test_gpu_adaptive.py::test_adaptive_edit_wide_and_huge", MR_EDIT_AD]),
     ("OTG_ADAPTIVE_NO_WIDE_START", ["tests/test_gpu_adaptive.py::test_adaptive_edit_small", "tests/test_gpu_adaptive.py::test_adaptive_edit_wide_and_huge", "tests/test_gpu_adaptive.py::test_adaptive_pipeline_hifi_and_haps"]),
-    ("OTG_ADAPTIVE_EDIT_TIERS=16", ["tests/test_gpu_adaptive.py::test_adaptive_edit_small", "tests/test_gpu_adaptive.py::test_adaptive_edit_long", "tests/test_gpu_adaptive.py::test_adaptive_edit_parameters", "tests/test_gpu_adaptive.py::test_adaptive_edit_wide_and_huge", "tests/test_gpu_adaptive.py::test_adaptive_pipeline[0]", MR_EDIT_AD]),
-    ("OTG_ADAPTIVE_EDIT_TIERS=2", ["tests/test_gpu_adaptive.py::test_adaptive_edit_small", "tests/test_gpu_adaptive.py::test_adaptive_edit_long", "tests/test_gpu_adaptive.py::test_adaptive_edit_parameters", "tests/test_gpu_adaptive.py::test_adaptive_pipeline_hifi_and_haps", MR_EDIT_AD]),
+    ("OTG_ADAPTIVE_EDIT_TIERS=16", ["tests/test_gpu_adaptive.py::test_adaptive_edit_small", "tests/test_gpu_adaptive.py::test_adaptive_edit_long", "tests/test_gpu_adaptive.py::test_adaptive_edit_parameters", "tests/test_gpu_adaptive.py::test_adaptive_edit_wide_and_huge", "tests/test_gpu_adaptive.py::test_adaptive_pipeline[0]", MR_EDIT_AD, PP_EDGES]),
+    ("OTG_ADAPTIVE_EDIT_TIERS=2", ["tests/test_gpu_adaptive.py::test_adaptive_edit_small", "tests/test_gpu_adaptive.py::test_adaptive_edit_long", "tests/test_gpu_adaptive.py::test_adaptive_edit_parameters", "tests/test_gpu_adaptive.py::test_adaptive_pipeline_hifi_and_haps", MR_EDIT_AD, PP_EDGES]),
     ("OTG_ADAPTIVE_EDIT_TIERS=8", [MR_EDIT_AD]),                                          # the 16384-diagonal byte-probe tier first
     ("OTG_ADAPTIVE_EDIT_TIERS=0", [MR_EDIT_AD]),                                          # the int32 row in HBM alone
-    ("OTG_ADAPTIVE_AFFINE_TIERS=2", ["tests/test_gpu_adaptive.py::test_adaptive_affine_small", "tests/test_gpu_adaptive.py::test_adaptive_affine_long", "tests/test_gpu_adaptive.py::test_adaptive_pipeline[0]", MR_AFFINE_AD]),
+    ("OTG_ADAPTIVE_AFFINE_TIERS=2", ["tests/test_gpu_adaptive.py::test_adaptive_affine_small", "tests/test_gpu_adaptive.py::test_adaptive_affine_long", "tests/test_gpu_adaptive.py::test_adaptive_pipeline[0]", MR_AFFINE_AD, PP_EDGES]),
     ("OTG_ADAPTIVE_AFFINE_TIERS=4", [MR_AFFINE_AD]),                                      # the byte-probe tier first
-    ("OTG_ADAPTIVE_AFFINE_TIERS=8", ["tests/test_gpu_adaptive.py::test_adaptive_affine_small", "tests/test_gpu_adaptive.py::test_adaptive_affine_long", "tests/test_gpu_adaptive.py::test_adaptive_affine_parameters", "tests/test_gpu_adaptive.py::test_adaptive_pipeline[0]", MR_AFFINE_AD]),
+    ("OTG_ADAPTIVE_AFFINE_TIERS=8", ["tests/test_gpu_adaptive.py::test_adaptive_affine_small", "tests/test_gpu_adaptive.py::test_adaptive_affine_long", "tests/test_gpu_adaptive.py::test_adaptive_affine_parameters", "tests/test_gpu_adaptive.py::test_adaptive_pipeline[0]", MR_AFFINE_AD, PP_EDGES]),
     ("OTG_ADAPTIVE_AFFINE_TIERS=10", ["tests/test_gpu_adaptive.py::test_adaptive_affine_small", "tests/test_gpu_adaptive.py::test_adaptive_affine_long", "tests/test_gpu_adaptive.py::test_adaptive_affine_other_penalties_and_wide", "tests/test_gpu_adaptive.py::test_adaptive_pipeline_hifi_and_haps"]),
-    ("OTG_ADAPTIVE_AFFINE_TIERS=18", ["tests/test_gpu_adaptive.py::test_adaptive_affine_small", "tests/test_gpu_adaptive.py::test_adaptive_affine_long", "tests/test_gpu_adaptive.py::test_adaptive_pipeline[0]", MR_AFFINE_AD]),
+    ("OTG_ADAPTIVE_AFFINE_TIERS=18", ["tests/test_gpu_adaptive.py::test_adaptive_affine_small", "tests/test_gpu_adaptive.py::test_adaptive_affine_long", "tests/test_gpu_adaptive.py::test_adaptive_pipeline[0]", MR_AFFINE_AD, PP_EDGES]),
     ("OTG_ADAPTIVE_AFFINE_TIERS=0", ["tests/test_gpu_adaptive.py::test_adaptive_affine_small", "tests/test_gpu_adaptive.py::test_adaptive_affine_other_penalties_and_wide", MR_AFFINE_AD]),
 ]
 
