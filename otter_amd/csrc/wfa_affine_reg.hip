@@ -283,6 +283,8 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
       // the score loop into S2 live registers each (loop-invariant code motion knows nothing about register pressure)
       asm volatile("" : "+v"(lane2));
       asm volatile("" : "+s"(kb));
+      int xes = xe;                              // the same for the end diagonal: tested per slot as hoisted S2 results, it sat in lanes of a spill register
+      asm volatile("" : "+s"(xes));
       int lo, hi;
       if (s == 0) { lo = lo0; hi = hi0; }
       else {
@@ -368,10 +370,13 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
           qn = wq; ++pass;
         }
       };
-      int pushed = 0, qfull = 0;
+      // The queue's state is its length alone, a scalar: 0 = nothing pushed, QFULL = more unfinished match runs in one score than it holds (every
+      // later push of the score then returns at the same test).  Two flags set inside push2 lived in private memory: a store per pushing slot
+      // visit, and two dependent reloads with s_waitcnt vmcnt(0) — behind every provenance store of the sweep — per score.
+      constexpr int QFULL = 2 * QCAP;
       auto push2 = [&](bool moreE, bool moreO, unsigned long long mE, unsigned long long mO, int xE, int hE, int hO) {     // mE / mO = the lane masks of moreE / moreO
         if (mE | mO) {
-          if (qn + 128 > QCAP) { qfull = 1; return; }          // more unfinished match runs in one score than the queue holds: the next tier takes the alignment
+          if (qn + 128 > QCAP) { qn = QFULL; return; }         // more unfinished match runs in one score than the queue holds: the next tier takes the alignment
           const int nE = __builtin_popcountll(mE);
           if (moreE) {
             const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mE >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mE, 0u));
@@ -382,7 +387,6 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
             QU[qn + nE + rank] = (uint32_t)(xE + 1) | ((uint32_t)hO << 16);
           }
           qn += nE + __builtin_popcountll(mO);
-          pushed = 1;
         }
       };
       // end condition of a fully extended cell (ends-free form; the end-to-end form is checked on the one end diagonal)
@@ -507,9 +511,9 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
               const unsigned long long fm = __ballot(fE || fO);
               if (fm) { int kc = fE ? kE : (fO ? kE + 1 : NOCAND); kc = -otg_wave_max_i32(-kc); cand = imin(cand, kc); }
             }
-          } else if (xe >= 128 * gi && xe < 128 * gi + 128) {
-            const bool odd = (xe & 1) != 0;
-            const int hx = __builtin_amdgcn_readlane(sel(odd ? (vmO & ~mmO) : (vmE & ~mmE), odd ? hO : hE, -1), (xe & 127) >> 1);
+          } else if ((xes >> 7) == gi) {
+            const bool odd = (xes & 1) != 0;
+            const int hx = __builtin_amdgcn_readlane(sel(odd ? (vmO & ~mmO) : (vmE & ~mmE), odd ? hO : hE, -1), (xes & 127) >> 1);
             if (hx >= tl) cand = kend;
           }
           if ((mmE | mmO) != 0ull) push2(lane_in(mmE, lane), lane_in(mmO, lane), mmE, mmO, xE, hE, hO);
@@ -520,8 +524,8 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
 #ifdef OTG_REG_TIMING
       tm_n += 1; tm_vis += (unsigned long long)(NW == 1 ? (j1 - j0 + 1) : ((j1 - ww + NW) / NW - (j0 - ww + NW - 1) / NW));
 #endif
-      if (qfull) cand = FAILV;
-      else if (pushed) {
+      if (qn >= QFULL) cand = FAILV;
+      else if (qn > 0) {
         drain();
         // fold the final offsets of the queued cells into M[s] (partial offset <= final offset: one packed max; the table is in the pair layout)
         static_for<0, S2>([&](auto ic) __attribute__((always_inline)) { constexpr int i = decltype(ic)::value;
@@ -600,17 +604,19 @@ void otg_affine_reg_geometry(int tier, int shape, int* aln_per_block, int* block
 {
   int a = 4, b = 4;
   switch (tier * 10 + shape) {
-    case 0: a = 4; b = 4; break;        // <1,8>   16 waves per CU
-    case 1: a = 1; b = 10; break;       // <2,4>   20
-    case 10: a = 4; b = 3; break;       // <1,12>  12 (no spills)
-    case 11: a = 4; b = 4; break;       // <1,12>  16 (32 spilled registers)
-    case 12: a = 1; b = 8; break;       // <2,6>   16
-    case 20: a = 1; b = 8; break;       // <2,8>   16
-    case 21: a = 4; b = 3; break;       // <1,16>  12 (32 spilled registers)
-    case 22: a = 4; b = 2; break;       // <1,16>  8 (no spills)
-    case 30: a = 1; b = 4; break;       // <4,8>   16
-    case 31: a = 1; b = 3; break;       // <8,4>   24
-    case 40: a = 1; b = 2; break;       // <8,8>   16
+    // shape, waves per CU; vector registers and how many of them are spilled, scalar registers spilled (the compiler's metadata; scripts/isa_reg_loop.py).
+    // Of the default shapes (x0) none reads private memory inside its score loop; the two alternatives that spill ~100 vector registers do.
+    case 0: a = 4; b = 4; break;        // <1,8>   16   128 (10 spilled), 47
+    case 1: a = 1; b = 10; break;       // <2,4>   20    96 (none), 59
+    case 10: a = 4; b = 3; break;       // <1,12>  12   168 (11 spilled), 57
+    case 11: a = 4; b = 4; break;       // <1,12>  16   128 (98 spilled), 57
+    case 12: a = 1; b = 8; break;       // <2,6>   16   124 (none), 65
+    case 20: a = 1; b = 8; break;       // <2,8>   16   128 (8 spilled), 75
+    case 21: a = 4; b = 3; break;       // <1,16>  12   168 (112 spilled), 67
+    case 22: a = 4; b = 2; break;       // <1,16>  8    220 (none), 67
+    case 30: a = 1; b = 4; break;       // <4,8>   16   128 (8 spilled), 75
+    case 31: a = 1; b = 3; break;       // <8,4>   24    80 (9 spilled), 57
+    case 40: a = 1; b = 2; break;       // <8,8>   16   128 (8 spilled), 75
     // (r04, measured and not kept: <2,16> for the 4096 window — half the exchange, an even split of ~10 live slots — at 2 waves per SIMD without spills
     //  or 3 with: affine stage of a 2 500-region slice of the 1-10 kb shard 364 ms with <4,8>, 436 / 392 ms with <2,16>: occupancy weighs more)
 

@@ -1,8 +1,8 @@
 """Two builds of the library against each other on bench.py: the parent's tree and the result's, each a checkout with its library built.
   run OUT PARENT RESULT A B [bench.py arguments]   rounds A .. B-1: `bench.py --gpus 1 --steps 3 --warmup 1 --full` plus the given arguments, the parent then
                                                    the result, a fresh process each; bench.py's line goes to OUT/bench_{parent,result}_<round>.json
-  dump OUT PARENT RESULT                           `bench.py --gpus 1 --steps 1 --warmup 1 --dump-outputs DIR` once per tree, the dumped arrays compared
-                                                   byte for byte: OUT/same_bytes.json (the arrays themselves are not kept)
+  dump OUT PARENT RESULT [bench.py arguments]      `bench.py --gpus 1 --steps 1 --warmup 1 --dump-outputs DIR` plus the given arguments (`--config 4`) once
+                                                   per tree, the dumped arrays compared byte for byte: OUT/same_bytes.json (the arrays themselves are not kept)
   table OUT OUT.json                               same_bytes.json; per leg the rounds, the medians, the parent's max - min and whether the result's
                                                    median is no worse than the parent's median by more than that spread
                                                    (legs that the rounds' bench.py arguments switched off are left out)
@@ -69,7 +69,7 @@ if mode == "dump":
     sha = {}
     for t, tree in trees.items():
         d = os.path.abspath(os.path.join(out, "dump_" + t))
-        bench(tree, ["--steps", "1", "--warmup", "1", "--dump-outputs", d], os.path.join(out, "dump_%s.json" % t))
+        bench(tree, ["--steps", "1", "--warmup", "1", "--dump-outputs", d] + sys.argv[5:], os.path.join(out, "dump_%s.json" % t))
         sha[t] = {os.path.basename(p): hashlib.sha256(open(p, "rb").read()).hexdigest() for p in sorted(glob.glob(os.path.join(d, "*.npy")))}
         shutil.rmtree(d)
     same = {"arrays": len(sha["parent"]), "differing": sorted(n for n in set(sha["parent"]) | set(sha["result"]) if sha["parent"].get(n) != sha["result"].get(n)),
