@@ -940,6 +940,96 @@ typedef struct otg_motifs_job {
 int otg_motifs_files(const otg_motifs_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
 
 /* ---------------------------------------------------------------------------------------------
+ * Repeat structure of alleles: every allele as a left-to-right sequence of exact tandem repeats and literals, (CAG)20(CCG)20 or
+ * (CGG)10AGG(CGG)9.  The motif annotation above gives an allele one period; it cannot say where a repeat starts, where it stops, or that
+ * the unit changes along the way.  The reference has no counterpart; this is the definition (all integers).  Parameters:
+ * 1 <= max_period <= OTG_REPEAT_MAX_PERIOD, 2 <= min_copies <= 1024, 2 <= min_span <= 65535 bases.  For a sequence s of length L:
+ *   1. Codes.  c[i] = 0..3 for A/a C/c G/g T/t, 4 for any other byte (the motif table); P = min(max_period, L / 2).
+ *   2. Match bits.  e_p[i] = (c[i] == c[i + p] and c[i] < 4) for i in [0, L - p), p in 1..P (the bits whose number is m(p) above).
+ *   3. Runs.  A run of period p is a maximal interval [a, b) of ones in e_p; it covers the bases [a, e) with e = b + p: that stretch has
+ *      exact period p and all of it is ACGT.  A copy count k at period p is ENOUGH when k >= min_copies and k p >= min_span.  A run is kept
+ *      when k = (e - a) / p is enough; R is the set of kept runs (p, a, e) over all p.
+ *   4. best(lo, hi).  For every run (p, a, e) in R: st = max(a, lo), en = min(e, hi), k = (en - st) / p; the run is skipped when en <= st or
+ *      k is not enough.  Its gain is g = st - lo + k p, its cost w = st - lo + p.  The best run has the highest g / w, compared by
+ *      cross-multiplication in 64 bits; ties go to the smaller st, then to the smaller p (two runs never share (st, p): a total order).
+ *      best may be none.
+ *   5. Parse.  x = 0, H = L, an empty stack, prev = none.  Loop on b = best(x, H):
+ *        b is none:  emit the literal [x, H) and set x = H; stop when the stack is empty, otherwise pop (run, H'), set H = H' and place
+ *                    the run at x;
+ *        b.st > x:   push (b's run, H) and set H = b.st (the gap in front of the run is parsed first, under that horizon);
+ *        otherwise:  place b's run at x; H stays.
+ *   6. Placing the run (p, a, e) at x under the horizon H.  en = min(e, H), st = x.  If prev has the same period p and begins at pb: take
+ *      the smallest t in [x, min(x + p, en - p + 1)) with c[t .. t + p) == c[pb .. pb + p); st = t if such a t exists and (en - t) / p is
+ *      still enough.  (This keeps the unit's phase across an interruption: (CGG)10AGG(CGG)9, not (CGG)10A(GGC)9GG.)  Emit the literal
+ *      [x, st), then the repeat (begin = st, period = p, copies = k = (en - st) / p, length = k p); prev = (p, st) and x = st + k p.
+ *   7. Literals.  Adjacent literals merge; an empty literal is not emitted; a literal is (begin, period 0, copies 0, length).
+ *   8. Per allele the summary n_segments, n_repeats, covered = the sum of the repeat lengths, flags.  L > OTG_REPEAT_MAX_LEN: one literal
+ *      [0, L) and flags = OTG_REPEAT_TOO_LONG; the batch does not fail.  L = 0: no segments.
+ * It follows that the segments tile [0, L) in order, that expanding unit x copies and the literals gives the allele back up to letter case,
+ * and that no two literals are adjacent.  Runs are exact: a substitution inside a copy shows as a literal of one unit, an indel re-phases
+ * the run behind it.
+ *   otg_repeat_batch           allele i is seq_arena[seq_off[i] .. + seq_len[i]).  sums: n summaries; seg_off: n + 1 offsets into the segments,
+ *                              which stay in HBM; *n_segments = seg_off[n].  Every output is nullable.  A parameter out of range or an
+ *                              allele outside the arena: OTG_ERR_ARG.  At most 2^24 alleles per call (OTG_ERR_CAPACITY);
+ *   otg_repeat_collect         copies the segments of the latest call on the context to segs[0 .. total); capacity < total is
+ *                              OTG_ERR_CAPACITY with the needed count in the message;
+ *   otg_repeat_device_results  device pointers of the latest results on this context (n summaries, n + 1 offsets, total segments), valid
+ *                              until the next repeat call on the context or otg_destroy; every output is nullable;
+ *   otg_repeat_last_ms         HIP-event times (ms) of the latest repeat call: runs_ms = pack, count, scans and run write (with the host's
+ *                              read of the run total in between), select_ms = the parse and the compaction of the segments;
+ *   otg_repeat_cohort          the same kernels over rows [row_begin, row_begin + n) of the row list of otg_kmer_cohort_rows, the alleles read
+ *                              in the regrouped cohort arena in place (preconditions and refusals as otg_motif_cohort; a zero-length allele
+ *                              is the row of "N");
+ *   otg_repeat_emit            per allele a = records[r].first_allele + i the row region \t i \t seq_len[a] \t n_repeats \t covered \t
+ *                              structure \n.  structure is the concatenation of the segments of the allele (segs[seg_off[a] ..
+ *                              seg_off[a + 1])), "." when there are none: a repeat is (UNIT)copies with the unit's bases written through the
+ *                              code table (upper case), a literal its own bytes when its length is at most OTG_REPEAT_TEXT_LITERAL, else
+ *                              [length].  A segment outside its allele is OTG_ERR_ARG.  Buffer protocol of otg_emit_alleles.
+ * The planes and their two tiers are those of the motif annotation, OTG_MOTIF_WIDE included.
+ * ------------------------------------------------------------------------------------------- */
+#define OTG_REPEAT_MAX_PERIOD   4096
+#define OTG_REPEAT_MAX_LEN      1048575
+#define OTG_REPEAT_TOO_LONG     1u       /* otg_repeat_sum.flags */
+#define OTG_REPEAT_TEXT_LITERAL 24       /* a longer literal is written [length] by otg_repeat_emit */
+typedef struct otg_repeat_seg {
+  uint32_t begin;                /* first base of the segment                                        */
+  uint32_t period;               /* 0: a literal                                                     */
+  uint32_t copies;               /* whole copies of the unit s[begin .. begin + period); 0: a literal */
+  uint32_t length;               /* bases; period * copies for a repeat                              */
+} otg_repeat_seg;
+typedef struct otg_repeat_sum {
+  uint32_t n_segments;
+  uint32_t n_repeats;
+  uint32_t covered;              /* bases in repeat segments                                         */
+  uint32_t flags;                /* OTG_REPEAT_TOO_LONG                                              */
+} otg_repeat_sum;
+int otg_repeat_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_bytes, const uint64_t* seq_off, const uint32_t* seq_len,
+                     uint32_t n, uint32_t max_period, uint32_t min_copies, uint32_t min_span, otg_repeat_sum* sums, uint64_t* seg_off,
+                     uint64_t* n_segments);
+int otg_repeat_collect(otg_ctx* ctx, otg_repeat_seg* segs, uint64_t capacity);
+int otg_repeat_device_results(otg_ctx* ctx, uint32_t* n, const otg_repeat_sum** sums, const uint64_t** seg_off, const otg_repeat_seg** segs,
+                              uint64_t* total);
+int otg_repeat_last_ms(otg_ctx* ctx, double* runs_ms, double* select_ms);
+int otg_repeat_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, uint32_t max_period, uint32_t min_copies, uint32_t min_span,
+                      otg_repeat_sum* sums, uint64_t* seg_off, uint64_t* n_segments);
+int otg_repeat_emit(const otg_vcf_record* records, uint32_t n_records, const char* region_arena, const uint8_t* seq_arena, const uint64_t* seq_off,
+                    const uint32_t* seq_len, const otg_repeat_sum* sums, const uint64_t* seg_off, const otg_repeat_seg* segs, char* out,
+                    uint64_t out_capacity, uint64_t* out_len);
+/* One row of otg_repeat_emit per allele of a VCF, in file order, built exactly as otg_motifs_files is.  Out-of-range parameters are
+ * OTG_ERR_ARG with the message the tool prints.  stats as otg_vcf2mat_files. */
+typedef struct otg_repeats_job {
+  const char* vcf_path;          /* positional <VCF[.GZ]>                                            */
+  const char* bed_path;          /* -b: required, parsed, unused                                     */
+  uint32_t    max_period;        /* -p: 1..OTG_REPEAT_MAX_PERIOD (the tool's default: 256)           */
+  uint32_t    min_copies;        /* --min-copies: 2..1024 (the tool's default: 2)                    */
+  uint32_t    min_span;          /* --min-span: 2..65535 bases (the tool's default: 12)              */
+  int32_t     threads;           /* -t: host threads of the emit                                     */
+  int32_t     device;            /* HIP device ordinal                                               */
+  uint32_t    batch_alleles;     /* alleles per batch, 0 = 65536                                     */
+} otg_repeats_job;
+int otg_repeats_files(const otg_repeats_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
+
+/* ---------------------------------------------------------------------------------------------
  * Indexed allele BAMs from the product's own SAM text.  Every writer above emits SAM text and every reader wants a
  * coordinate-sorted BAM with its `.bai`; the reference's workflow goes through `samtools view -bh | samtools sort`, `samtools index` and
  * `samtools merge -pco` in between.  Host code (zlib + threads), no device work.

@@ -10,3 +10,4 @@ from ._lib import vcf_read_alleles, vcf2mat_emit, vcf2mat_files, cohort_files, B
 from ._lib import exp_host, exp_probe  # noqa: F401
 from .abi import default_params  # noqa: F401
 from ._lib import motif_emit, motifs_files  # noqa: F401
+from ._lib import repeat_emit, repeats_files  # noqa: F401

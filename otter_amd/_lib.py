@@ -29,6 +29,7 @@ EXPORTS = [
     "otg_exp_probe_mismatches", "otg_exp_probe", "otg_exp_host", "otg_exp_device", "otg_cluster_trace_batch", "otg_genotype_cluster_trace_batch",
     "otg_genotype_cluster_metric_batch", "otg_genotype_metric_last_ms", "otg_genotype_cohort_metric",
     "otg_motif_batch", "otg_motif_device_results", "otg_motif_last_ms", "otg_motif_cohort", "otg_motif_emit", "otg_motifs_files",
+    "otg_repeat_batch", "otg_repeat_collect", "otg_repeat_device_results", "otg_repeat_last_ms", "otg_repeat_cohort", "otg_repeat_emit", "otg_repeats_files",
 ]
 
 _lib = None
@@ -266,7 +267,7 @@ class Context:
                 self.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (int(ptr), False), "version": 2, "strides": None}
 
         if 0 in shape:
-            return torch.zeros(shape, dtype={"<f8": torch.float64, "<i4": torch.int32, "|u1": torch.uint8}[typestr], device=dev)
+            return torch.zeros(shape, dtype={"<f8": torch.float64, "<i4": torch.int32, "<i8": torch.int64, "|u1": torch.uint8}[typestr], device=dev)
         return torch.as_tensor(_Span(ptr, shape), device=dev)
 
     def kmer_usage_last_ms(self):
@@ -308,6 +309,46 @@ class Context:
         """(pack and match-count ms, reduce and unit ms) of the latest motif call on this context (HIP events)."""
         a, b = C.c_double(0), C.c_double(0)
         self._check(self._L.otg_motif_last_ms(self._h, C.byref(a), C.byref(b)), "otg_motif_last_ms")
+        return a.value, b.value
+
+    def repeat_batch(self, arena, seq_off, seq_len, max_period=256, min_copies=2, min_span=12, device_tensor=False):
+        """otg_repeat_batch (and otg_repeat_collect): per allele its structure as exact tandem repeats and literals (include/otter_gpu.h states
+        the rule) -> (sums [n] of abi.repeat_sum_dt, seg_off [n + 1] uint64, segs [total] of abi.repeat_seg_dt; the segments of allele i are
+        segs[seg_off[i]:seg_off[i + 1]]) as numpy arrays; or with device_tensor=True as torch tensors on this context's device that wrap the
+        results in HBM without a copy (int32 [n, 4], int64 [n + 1], int32 [total, 4]; valid until the next repeat call on this context)."""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+        ln = np.ascontiguousarray(seq_len, dtype=np.uint32)
+        n = len(ln)
+        return self._repeat_results(n, device_tensor, lambda sums, seg_off, total: self._L.otg_repeat_batch(
+            self._h, abi.ptr(arena), C.c_uint64(arena.size), abi.ptr(off), abi.ptr(ln), C.c_uint32(n), C.c_uint32(max_period), C.c_uint32(min_copies),
+            C.c_uint32(min_span), sums, seg_off, total), "otg_repeat_batch")
+
+    def _repeat_results(self, n, device_tensor, call, who):
+        total = C.c_uint64(0)
+        if device_tensor:
+            self._check(call(None, None, C.byref(total)), who)
+            if n == 0:
+                import torch
+                dev = torch.device("cuda", self.device)
+                return (torch.zeros((0, 4), dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
+                        torch.zeros((0, 4), dtype=torch.int32, device=dev))
+            m, t, ps, po, pg = C.c_uint32(0), C.c_uint64(0), C.c_void_p(), C.c_void_p(), C.c_void_p()
+            self._check(self._L.otg_repeat_device_results(self._h, C.byref(m), C.byref(ps), C.byref(po), C.byref(pg), C.byref(t)), "otg_repeat_device_results")
+            assert (m.value, t.value) == (n, total.value)
+            return self._wrap_device(ps.value, (n, 4), "<i4"), self._wrap_device(po.value, (n + 1,), "<i8"), self._wrap_device(pg.value, (t.value, 4), "<i4")
+        sums = np.zeros(n, dtype=abi.repeat_sum_dt)
+        seg_off = np.zeros(n + 1, dtype=np.uint64)
+        self._check(call(abi.ptr(sums), abi.ptr(seg_off), C.byref(total)), who)
+        segs = np.zeros(total.value, dtype=abi.repeat_seg_dt)
+        if n and total.value:
+            self._check(self._L.otg_repeat_collect(self._h, abi.ptr(segs), C.c_uint64(total.value)), "otg_repeat_collect")
+        return sums, seg_off, segs
+
+    def repeat_last_ms(self):
+        """(runs ms, select ms) of the latest repeat call on this context (HIP events)."""
+        a, b = C.c_double(0), C.c_double(0)
+        self._check(self._L.otg_repeat_last_ms(self._h, C.byref(a), C.byref(b)), "otg_repeat_last_ms")
         return a.value, b.value
 
     def affine_align_batch(self, arena, tasks, x=4, o=6, e=2, want_cells=False):
@@ -649,6 +690,18 @@ class Context:
                                       None if device_tensor else abi.ptr(rec), None if device_tensor else abi.ptr(units), C.c_uint32(stride))
         self._check(rc, "otg_motif_cohort")
         return self._motif_device_results(n, stride) if device_tensor else (rec, units[:, :stride])
+
+    def cohort_repeats(self, row_begin=0, n=None, max_period=256, min_copies=2, min_span=12, device_tensor=False):
+        """otg_repeat_cohort: the repeat structure of rows [row_begin, row_begin + n) of the row list (n=None: to the end), the alleles read in
+        the cohort arena in place -> (sums, seg_off, segs) as repeat_batch returns them."""
+        if n is None:
+            total = C.c_uint32(0)
+            self._check(self._L.otg_kmer_cohort_rows(self._h, C.byref(total), None, None, None), "otg_kmer_cohort_rows")
+            n = max(0, total.value - int(row_begin))
+        n = int(n)
+        return self._repeat_results(n, device_tensor, lambda sums, seg_off, total: self._L.otg_repeat_cohort(
+            self._h, C.c_uint32(row_begin), C.c_uint32(n), C.c_uint32(max_period), C.c_uint32(min_copies), C.c_uint32(min_span), sums, seg_off, total),
+            "otg_repeat_cohort")
 
     def cohort_end(self):
         self._check(self._L.otg_cohort_end(self._h), "otg_cohort_end")
@@ -1430,3 +1483,41 @@ def motifs_files(vcf, bed, max_period=256, slack=50, threads=1, device=0, batch_
     job.vcf_path = vcf.encode(); job.bed_path = bed.encode()
     job.max_period = max_period; job.slack = slack; job.threads = threads; job.device = device; job.batch_alleles = batch_alleles
     return _run_files_job("otg_motifs_files", job, abi.MotifsJob)
+
+
+def repeat_emit(records, regions, arena, seq_off, seq_len, sums, seg_off, segs):
+    """otg_repeat_emit: the rows of otter_repeats for the records (vcf_record_dt), the alleles (arena, seq_off, seq_len) and their structure as
+    Context.repeat_batch returns it -> text bytes."""
+    L = load()
+    records = np.ascontiguousarray(records, dtype=abi.vcf_record_dt)
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+    seq_len = np.ascontiguousarray(seq_len, dtype=np.uint32)
+    sums = np.ascontiguousarray(sums, dtype=abi.repeat_sum_dt)
+    seg_off = np.ascontiguousarray(seg_off, dtype=np.uint64)
+    segs = np.ascontiguousarray(segs, dtype=abi.repeat_seg_dt)
+    if arena.size == 0:
+        arena = np.zeros(1, dtype=np.uint8)
+    if segs.size == 0:
+        segs = np.zeros(1, dtype=abi.repeat_seg_dt)
+    reg = np.frombuffer(regions + b"\0", dtype=np.uint8)
+    need = C.c_uint64(0)
+    args = lambda out, cap: (abi.ptr(records), C.c_uint32(len(records)), abi.ptr(reg), abi.ptr(arena), abi.ptr(seq_off), abi.ptr(seq_len), abi.ptr(sums),
+                             abi.ptr(seg_off), abi.ptr(segs), out, C.c_uint64(cap), C.byref(need))
+    rc = L.otg_repeat_emit(*args(None, 0))
+    if rc not in (0, abi.OTG_ERR_CAPACITY):
+        raise OtterGpuError("otg_repeat_emit failed (%d): %s" % (rc, _err(L)))
+    out = C.create_string_buffer(need.value + 1)
+    rc = L.otg_repeat_emit(*args(out, need.value))
+    if rc != 0:
+        raise OtterGpuError("otg_repeat_emit failed (%d): %s" % (rc, _err(L)))
+    return out.raw[:need.value]
+
+
+def repeats_files(vcf, bed, max_period=256, min_copies=2, min_span=12, threads=1, device=0, batch_alleles=0):
+    """otg_repeats_files: the repeat structure of every allele of a VCF (plain, gzip or BGZF) as text.  Returns (text bytes, stats dict)."""
+    job = abi.RepeatsJob()
+    job.vcf_path = vcf.encode(); job.bed_path = bed.encode()
+    job.max_period = max_period; job.min_copies = min_copies; job.min_span = min_span
+    job.threads = threads; job.device = device; job.batch_alleles = batch_alleles
+    return _run_files_job("otg_repeats_files", job, abi.RepeatsJob)

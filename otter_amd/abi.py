@@ -235,6 +235,22 @@ class MotifsJob(C.Structure):
                 ("device", C.c_int32), ("batch_alleles", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+# otg_repeat_seg / otg_repeat_sum (include/otter_gpu.h) and the bounds of the repeat structure
+repeat_seg_dt = np.dtype([("begin", np.uint32), ("period", np.uint32), ("copies", np.uint32), ("length", np.uint32)])
+repeat_sum_dt = np.dtype([("n_segments", np.uint32), ("n_repeats", np.uint32), ("covered", np.uint32), ("flags", np.uint32)])
+assert repeat_seg_dt.itemsize == 16 and repeat_sum_dt.itemsize == 16
+REPEAT_MAX_PERIOD = 4096
+REPEAT_MAX_LEN = 1048575
+REPEAT_TOO_LONG = 1
+REPEAT_TEXT_LITERAL = 24
+
+
+class RepeatsJob(C.Structure):
+    """otg_repeats_job (include/otter_gpu.h)."""
+    _fields_ = [("vcf_path", C.c_char_p), ("bed_path", C.c_char_p), ("max_period", C.c_uint32), ("min_copies", C.c_uint32), ("min_span", C.c_uint32),
+                ("threads", C.c_int32), ("device", C.c_int32), ("batch_alleles", C.c_uint32)]
+
+
 class JobStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_regions", "n_regions_ok", "n_regions_skipped", "n_reads", "n_alleles", "input_bytes", "output_bytes")] + \
                [("n_devices", C.c_uint32), ("reserved", C.c_uint32)] + [(k, C.c_double) for k in ("ms_total", "ms_ingest", "ms_hot_path", "ms_emit")]

@@ -518,6 +518,20 @@ int otg_motif_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, uint32_t max_
                             max_period, slack, out, unit_out, unit_stride);
 }
 
+int otg_repeat_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, uint32_t max_period, uint32_t min_copies, uint32_t min_span, otg_repeat_sum* sums,
+                      uint64_t* seg_off, uint64_t* n_segments)
+{
+  Cohort* cp = cohort_of(ctx, "otg_repeat_cohort");
+  if (!cp) return ctx ? OTG_ERR_ARG : OTG_ERR_NO_DEVICE;
+  Cohort& c = *cp;
+  if (!c.clustered) return otg_fail(ctx, OTG_ERR_ARG, "otg_repeat_cohort: the batch has not been clustered (otg_cohort_genotype)");
+  if (int rc = otg_repeat_args(ctx, "otg_repeat_cohort", max_period, min_copies, min_span)) return rc;
+  if (int rc = cohort_build_rows(ctx, c, "otg_repeat_cohort")) return rc;
+  if ((uint64_t)row_begin + n > c.n_rows) return otg_fail(ctx, OTG_ERR_ARG, "otg_repeat_cohort: rows %u .. %llu of %u", row_begin, (unsigned long long)row_begin + n, c.n_rows);
+  return otg_repeat_resident(ctx, "otg_repeat_cohort", (const uint8_t*)c.arena.p, (const uint64_t*)c.row_off.p + row_begin, (const uint32_t*)c.row_len.p + row_begin, n,
+                             max_period, min_copies, min_span, sums, seg_off, n_segments);
+}
+
 int otg_cohort_end(otg_ctx* ctx)
 {
   if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_cohort_end: no context");

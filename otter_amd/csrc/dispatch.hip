@@ -16,6 +16,7 @@
 #include "otg_dispatch_queue.hpp"
 #include "otg_vcf2mat.hpp"
 #include "otg_motif.hpp"
+#include "otg_repeat.hpp"
 #include <cmath>
 #include <algorithm>
 #include <atomic>
@@ -1118,6 +1119,31 @@ int otg_motifs_files(const otg_motifs_job* job, otg_write_fn write, void* user, 
     },
     [&](std::string& o, const VcfBatch& B, uint32_t r0, uint32_t nr) {
       otg_motif_rows(o, B.rec.data() + r0, nr, B.regions.data(), B.len.data(), motifs.data(), units.data(), stride);
+    });
+}
+
+// The repeat-structure rows of a VCF's alleles (otg_repeat_batch, otg_repeat_collect), on vcf_allele_job as otg_motifs_files.
+int otg_repeats_files(const otg_repeats_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
+{
+  if (!job || !write || !job->vcf_path || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "otg_repeats_files: NULL job, writer, VCF or BED path");
+  const uint32_t max_period = job->max_period, min_copies = job->min_copies, min_span = job->min_span;
+  if (max_period < 1 || max_period > OTG_REPEAT_MAX_PERIOD)
+    return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--max-period' (%u). Needs to be 1 <= x <= %d.", max_period, OTG_REPEAT_MAX_PERIOD);
+  if (min_copies < 2 || min_copies > 1024) return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--min-copies' (%u). Needs to be 2 <= x <= 1024.", min_copies);
+  if (min_span < 2 || min_span > 65535) return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--min-span' (%u). Needs to be 2 <= x <= 65535.", min_span);
+  std::vector<otg_repeat_sum> sums;
+  std::vector<uint64_t> seg_off;
+  std::vector<otg_repeat_seg> segs;
+  return vcf_allele_job("otg_repeats_files", job->vcf_path, job->bed_path, job->device, job->batch_alleles ? job->batch_alleles : 65536, job->threads, write, user, stats,
+    [&](otg_ctx* ctx, const VcfBatch& B) {
+      sums.resize(B.na); seg_off.resize((size_t)B.na + 1);
+      uint64_t total = 0;
+      if (int rc = otg_repeat_batch(ctx, B.seqs.data(), B.au, B.off.data(), B.len.data(), B.na, max_period, min_copies, min_span, sums.data(), seg_off.data(), &total)) return rc;
+      segs.resize(total);
+      return B.na ? otg_repeat_collect(ctx, segs.data(), total) : OTG_OK;
+    },
+    [&](std::string& o, const VcfBatch& B, uint32_t r0, uint32_t nr) {
+      otg_repeat_rows(o, B.rec.data() + r0, nr, B.regions.data(), B.seqs.data(), B.off.data(), B.len.data(), sums.data(), seg_off.data(), segs.data());
     });
 }
 

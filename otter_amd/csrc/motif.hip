@@ -203,6 +203,21 @@ bool motif_force_wide()
 
 } // namespace
 
+uint32_t otg_motif_lds_len() { return motif_force_wide() ? 0u : MOTIF_LDS_LEN; }
+
+void otg_motif_plane_scan(otg_ctx* ctx, const uint32_t* d_len, uint32_t n, uint32_t max_period, uint32_t lds_len, uint64_t* d_ploff, uint64_t* d_total)
+{
+  hipLaunchKernelGGL((otg_scan_kernel<uint64_t, uint64_t, MoPlaneWords>), dim3(1), dim3(1024), 0, ctx->stream, MoPlaneWords{d_len, max_period, lds_len}, n,
+                     d_ploff, d_total);
+}
+
+// a grid over every allele: the workgroups of an allele without planes in HBM (pl_off unchanged) return at once
+void otg_motif_pack_planes(otg_ctx* ctx, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, uint32_t n, const uint64_t* d_ploff,
+                           uint32_t* d_planes)
+{
+  hipLaunchKernelGGL(motif_pack_hbm, dim3(n, 8), dim3(MOTIF_T), 0, ctx->stream, d_arena, d_off, d_len, n, d_ploff, d_planes);
+}
+
 int otg_motif_args(otg_ctx* ctx, const char* who, uint32_t max_period, uint32_t slack)
 {
   if (max_period < 1 || max_period > OTG_MOTIF_MAX_PERIOD)
@@ -223,7 +238,7 @@ int otg_motif_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, co
   if (n > (1u << 24)) return otg_fail(ctx, OTG_ERR_CAPACITY, "%s: %u alleles in one call, at most %u", who, n, 1u << 24);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (!ctx->ev2) HIP_TRY(ctx, hipEventCreate(&ctx->ev2));
-  const uint32_t lds_len = motif_force_wide() ? 0u : MOTIF_LDS_LEN;
+  const uint32_t lds_len = otg_motif_lds_len();
   // offsets: m_off (u64, n + 1) | pl_off (u64, n + 1) | the two totals
   uint64_t* d_moff = (uint64_t*)otg_slot(ctx, SLOT_MOTIF_OFF, ((size_t)2 * n + 4) * 8);
   const size_t rec_bytes = (size_t)n * sizeof(otg_motif), unit_bytes = (size_t)n * unit_stride;
@@ -232,8 +247,7 @@ int otg_motif_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, co
   uint64_t* d_ploff = d_moff + (n + 1);
   uint64_t* d_tot = d_ploff + (n + 1);
   hipLaunchKernelGGL((otg_scan_kernel<uint64_t, uint64_t, MoPeriods>), dim3(1), dim3(1024), 0, ctx->stream, MoPeriods{d_len, max_period}, n, d_moff, d_tot);
-  hipLaunchKernelGGL((otg_scan_kernel<uint64_t, uint64_t, MoPlaneWords>), dim3(1), dim3(1024), 0, ctx->stream, MoPlaneWords{d_len, max_period, lds_len}, n,
-                     d_ploff, d_tot + 1);
+  otg_motif_plane_scan(ctx, d_len, n, max_period, lds_len, d_ploff, d_tot + 1);
   HIP_TRY(ctx, hipGetLastError());
   uint64_t tot[2] = {0, 0};
   HIP_TRY(ctx, hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, ctx->stream));
@@ -248,7 +262,7 @@ int otg_motif_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, co
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   if (lds_len) hipLaunchKernelGGL(motif_count_lds, dim3(grid), dim3(MOTIF_T), 0, ctx->stream, d_arena, d_off, d_len, n, max_period, lds_len, d_moff, d_m);
   if (tot[1]) {              // grids over every allele: the workgroups of an allele without planes in HBM (pl_off unchanged) return at once
-    hipLaunchKernelGGL(motif_pack_hbm, dim3(n, 8), dim3(MOTIF_T), 0, ctx->stream, d_arena, d_off, d_len, n, d_ploff, d_planes);
+    otg_motif_pack_planes(ctx, d_arena, d_off, d_len, n, d_ploff, d_planes);
     hipLaunchKernelGGL(motif_count_hbm, dim3(n, (max_period + MOTIF_T - 1) / MOTIF_T), dim3(MOTIF_T), 0, ctx->stream, d_len, n, max_period, d_ploff, d_planes, d_moff, d_m);
   }
   HIP_TRY(ctx, hipGetLastError());

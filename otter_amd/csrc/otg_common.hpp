@@ -46,6 +46,10 @@ struct otg_ctx {
   hipEvent_t ev2 = nullptr;                       // third timing event, created on first use (kmer_usage.hip, motif.hip)
   double last_motif_count_ms = 0.0, last_motif_reduce_ms = 0.0;   // HIP-event times of the latest otg_motif_batch / otg_motif_cohort (otg_motif_last_ms)
   uint32_t last_motif_n = 0, last_motif_stride = 0;               // the shape of the results in SLOT_MOTIF_OUT (otg_motif_device_results)
+  double last_repeat_runs_ms = 0.0, last_repeat_select_ms = 0.0;  // HIP-event times of the latest otg_repeat_batch / otg_repeat_cohort (otg_repeat_last_ms)
+  uint32_t last_repeat_n = 0;                                     // the shape of the results in SLOT_REPEAT_RES / SLOT_REPEAT_SEGS (otg_repeat_device_results);
+  uint64_t last_repeat_total = 0;                                 // valid: a repeat call with n > 0 has succeeded since the last one began
+  bool last_repeat_valid = false;
   double last_kernel_ms = 0.0;                    // HIP-event time of the kernels of the latest operator-level call that reports one (otg_last_kernel_ms)
   // the latest genotype clustering with a metric (genotype_edit.hip): times of its two parts (otg_genotype_metric_last_ms), whether the edit
   // matrix was built, and where its counters lie in SLOT_GTE_CLS
@@ -99,6 +103,8 @@ enum {
   SLOT_KMER_BLK,                                                    // tier L of otg_kmer_usage_resident: gc counts and the workgroup prefix
   SLOT_GTE_CLS, SLOT_GTE_TASKS, SLOT_GTE_SCORES, SLOT_GTE_DEN, SLOT_GTE_TODO,   // the edit metric of the genotype clustering (genotype_edit.hip)
   SLOT_MOTIF_SEQ, SLOT_MOTIF_META, SLOT_MOTIF_OFF, SLOT_MOTIF_M, SLOT_MOTIF_PLANES, SLOT_MOTIF_OUT,   // otg_motif_batch (motif.hip); OUT stays valid for the device results
+  SLOT_REPEAT_SEQ, SLOT_REPEAT_META, SLOT_REPEAT_OFF, SLOT_REPEAT_CNT, SLOT_REPEAT_PLANES, SLOT_REPEAT_RUNS, SLOT_REPEAT_STACK, SLOT_REPEAT_SCRATCH,   // otg_repeat_batch (repeat.hip)
+  SLOT_REPEAT_RES, SLOT_REPEAT_SEGS,                                // its summaries and offsets / its segments: they stay valid for the device results
   SLOT_COUNT
 };
 
@@ -345,6 +351,16 @@ int otg_motif_args(otg_ctx* ctx, const char* who, uint32_t max_period, uint32_t 
 int otg_motif_stride_fits(otg_ctx* ctx, const char* who, uint32_t max_len, uint32_t max_period, uint32_t unit_stride);
 int otg_motif_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, uint32_t n,
                        uint32_t max_period, uint32_t slack, otg_motif* out, uint8_t* unit_out, uint32_t unit_stride);
+// motif.hip: the HBM plane tier, shared with repeat.hip.  The longest allele of the LDS tier (0 under OTG_MOTIF_WIDE); the scan of the plane
+// words per allele into d_ploff (n + 1; an allele of the LDS tier or without a period has none) and *d_total; the pack kernel on those offsets.
+uint32_t otg_motif_lds_len();
+void otg_motif_plane_scan(otg_ctx* ctx, const uint32_t* d_len, uint32_t n, uint32_t max_period, uint32_t lds_len, uint64_t* d_ploff, uint64_t* d_total);
+void otg_motif_pack_planes(otg_ctx* ctx, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, uint32_t n, const uint64_t* d_ploff,
+                           uint32_t* d_planes);
+// repeat.hip: the argument refusals of otg_repeat_batch and its launch part on device-resident rows (cohort.hip), as the motif pair above
+int otg_repeat_args(otg_ctx* ctx, const char* who, uint32_t max_period, uint32_t min_copies, uint32_t min_span);
+int otg_repeat_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, uint32_t n,
+                        uint32_t max_period, uint32_t min_copies, uint32_t min_span, otg_repeat_sum* sums, uint64_t* seg_off, uint64_t* n_segments);
 
 // cluster.hip (genotype_kernel)
 int otg_launch_genotype(otg_ctx* ctx, const otg_params* P, const uint8_t* d_arena, const uint64_t* d_seq_off,

@@ -71,6 +71,15 @@ OTG_MOTIF_HD void mo_pack_word(const uint8_t* s, uint32_t L, uint32_t w, uint32_
   *lo = l; *hi = h; *v = ok;
 }
 
+// The match bits of one word of a shifted compare at p = 32 q + r: bit k = (s[i] == s[i + p], both ACGT) for i = 32 w + k, from word w of
+// the planes (lo, hi, v) and the words w + q (x0) and w + q + 1 (x1) that hold i + p.  What mo_count popcounts and otg_repeat_core.hpp walks.
+OTG_MOTIF_HD uint32_t mo_eq_word(uint32_t lo, uint32_t hi, uint32_t v, uint32_t l0, uint32_t l1, uint32_t h0, uint32_t h1, uint32_t v0, uint32_t v1,
+                                 uint32_t r)
+{
+  const uint32_t ls = mo_funnel(l1, l0, r), hs = mo_funnel(h1, h0, r), vs = mo_funnel(v1, v0, r);
+  return ~((lo ^ ls) | (hi ^ hs)) & v & vs;
+}
+
 // m(p), 1 <= p <= L / 2, from planes of (L + 31) / 32 words followed by at least one zero word.  The zero tail makes every base at or past
 // L invalid, so i + p < L needs no mask of its own; the words w < ceil((L - p) / 32) hold every i < L - p, and the highest word read is
 // w + (p >> 5) + 1 <= (L + 31) / 32.  Per word: one funnel shift per plane, ~((lo ^ lo') | (hi ^ hi')) & v & v', a popcount.
@@ -80,8 +89,7 @@ OTG_MOTIF_HD uint32_t mo_count(const uint32_t* LO, const uint32_t* HI, const uin
   uint32_t l0 = LO[q], h0 = HI[q], v0 = V[q], cnt = 0;
   for (uint32_t w = 0; w < nw; ++w) {
     const uint32_t l1 = LO[w + q + 1], h1 = HI[w + q + 1], v1 = V[w + q + 1];
-    const uint32_t ls = mo_funnel(l1, l0, r), hs = mo_funnel(h1, h0, r), vs = mo_funnel(v1, v0, r);
-    cnt += mo_popc(~((LO[w] ^ ls) | (HI[w] ^ hs)) & V[w] & vs);
+    cnt += mo_popc(mo_eq_word(LO[w], HI[w], V[w], l0, l1, h0, h1, v0, v1, r));
     l0 = l1; h0 = h1; v0 = v1;
   }
   return cnt;
