@@ -226,8 +226,51 @@ __global__ __launch_bounds__(WPB * 64) void wfa_affine_kernel(
 // shift).  Four times cheaper per score than the static 256-diagonal band and not limited by the distance
 // between start and end diagonals; the bound is as valid (any alignment found is an alignment), just looser
 // when the optimal path strays more than ~20 diagonals from the leader.
-template <int XS, int OES>
-__global__ __launch_bounds__(256) void wfa_affine_bound1_kernel(
+//
+// A pair packed to 2 bits per base in the wave's LDS (every pair of ACGT reads that fits SEQW words) runs the score loop below; a pair with
+// a byte outside ACGT, or too long for SEQW, runs the byte loop behind it (8-base probes from HBM).  Both compute the same cells.  What the
+// packed loop does NOT spend per score, against the byte loop that states the recurrence plainly:
+//   * the four rows M(s-1) .. M(s-4) rotate by renaming: four scores per trip, row r lives in register r & 3;
+//   * a null offset is ANY negative value, never reset: nulls only grow by one per score from -2^29 and a score is at most smax < 2^17, so a
+//     component needs one test (above the diagonal's limit lim = min(tl, pl + k), kept per lane) where the byte loop makes three;
+//   * max(I, M) and max(D, M) are taken before the lane shift: two shifts per score, and the edge lanes get their null through the DPP `old`
+//     operand;
+//   * probes read wherever the offset points (LDS reads outside the allocation return zero, inside it harmless words) and one select drops
+//     what a null cell probed; the first 32 bases are probed inline, the rolled loop is entered only when a lane matched all 32;
+//   * the end test runs only when a cell reached its limit (h == tl or v == pl);
+//   * the leader is one maximum over keys (2 h - k) * 64 + 63 - lane: the lowest lane of the furthest anti-diagonal without compare and ballot.
+namespace bound_pass {
+using lds_char = __attribute__((address_space(3))) char;
+using lds_cu32 = __attribute__((address_space(3))) uint32_t;
+// lane masks of comparisons (v_cmp into an SGPR pair; the logic on them runs on the scalar unit) and a select on a lane mask
+__device__ __forceinline__ unsigned long long mk_eq(int a, int b) { return __builtin_amdgcn_sicmp(a, b, 32); }
+__device__ __forceinline__ unsigned long long mk_ne(int a, int b) { return __builtin_amdgcn_sicmp(a, b, 33); }
+__device__ __forceinline__ unsigned long long mk_sgt(int a, int b) { return __builtin_amdgcn_sicmp(a, b, 38); }
+__device__ __forceinline__ int sel(unsigned long long m, int a, int b) { int r; asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m)); return r; }     // lane in m ? a : b
+// lane i <- lane i-1 / lane i+1 across the wave; the lane at the open end gets `edge`
+__device__ __forceinline__ int shr1(int x, int edge) { return __builtin_amdgcn_update_dpp(edge, x, 0x138, 0xf, 0xf, false); }
+__device__ __forceinline__ int shl1(int x, int edge) { return __builtin_amdgcn_update_dpp(edge, x, 0x130, 0xf, 0xf, false); }
+// equal leading bases of pattern[pv ..] and text[ph ..], at most 32, wherever the offsets point.  SQB = the packed pair, offT4 = 4 * offT.
+__device__ __forceinline__ int probe32(const lds_char* SQB, int offT4, int pv, int ph)
+{
+  const lds_cu32* pp = (const lds_cu32*)(SQB + ((pv >> 2) & ~3));
+  const lds_cu32* pt = (const lds_cu32*)(SQB + offT4 + ((ph >> 2) & ~3));
+  const uint32_t sp = (uint32_t)pv * 2u, st = (uint32_t)ph * 2u;      // v_alignbit takes the low five bits
+  const uint32_t p0 = pp[0], p1 = pp[1], p2 = pp[2], q0 = pt[0], q1 = pt[1], q2 = pt[2];
+  const uint32_t xl = __builtin_amdgcn_alignbit(p1, p0, sp) ^ __builtin_amdgcn_alignbit(q1, q0, st);
+  const uint32_t xh = __builtin_amdgcn_alignbit(p2, p1, sp) ^ __builtin_amdgcn_alignbit(q2, q1, st);
+  uint32_t flo, fhi;      // v_ffbl_b32: index of the lowest set bit, 0xffffffff for zero — which is what the min below wants
+  asm("v_ffbl_b32 %0, %1" : "=v"(flo) : "v"(xl));
+  asm("v_ffbl_b32 %0, %1" : "=v"(fhi) : "v"(xh));
+  const uint32_t a = flo < (fhi | 32u) ? flo : (fhi | 32u);
+  return (int)((a < 64u ? a : 64u) >> 1);
+}
+} // namespace bound_pass
+
+// SEQW = words of LDS per wave for the packed pair, WPB = waves (alignments) per block; the launcher picks both from the batch's longest read
+// (otg_bound_pass_shape below): LDS, not registers, sets how many waves a CU holds.
+template <int XS, int OES, int SEQW, int WPB>
+__global__ __launch_bounds__(WPB * 64) void wfa_affine_bound1_kernel(
     const uint8_t* __restrict__ arena, const otg_align_task* __restrict__ tasks,
     const uint32_t* __restrict__ todo, const uint32_t* __restrict__ n_todo_ptr, uint32_t n_todo_imm,
     int32_t* __restrict__ bound, uint32_t* __restrict__ ticket)
@@ -236,8 +279,7 @@ __global__ __launch_bounds__(256) void wfa_affine_bound1_kernel(
   constexpr int NULLV = -(1 << 29);
   // per wave: both sequences packed to 2 bits per base (as in the LDS tiers of the exact pass): a probe covers 32 bases
   // and comes from LDS; pairs that do not fit or contain a byte outside ACGT use the byte probes from HBM
-  constexpr int SEQW = 800;                               // words per wave: pl + tl up to ~12.6 kb
-  __shared__ uint32_t s_pk[4][SEQW];
+  __shared__ uint32_t s_pk[WPB][SEQW];
   using lds_u32b = __attribute__((address_space(3))) uint32_t;
   const int lane = threadIdx.x & 63;
   volatile lds_u32b* SQ = (volatile lds_u32b*)&s_pk[threadIdx.x >> 6][0];
@@ -294,30 +336,83 @@ __global__ __launch_bounds__(256) void wfa_affine_bound1_kernel(
         pack(T, tl, offT);
         packed = __ballot(bad) == 0ull;
       }
-      auto ld32b = [&](int woff, int pos) -> uint64_t {
-        const int w = woff + (pos >> 4);
-        const uint32_t sh = (uint32_t)(pos & 15) * 2u;
-        const uint32_t d0 = SQ[w], d1 = SQ[w + 1], d2 = SQ[w + 2];
-        return (uint64_t)__builtin_amdgcn_alignbit(d1, d0, sh) | ((uint64_t)__builtin_amdgcn_alignbit(d2, d1, sh) << 32);
-      };
-      int bk0 = ((lo0 + hi0) >> 1) - 32;                 // diagonal of lane 0
-      int M1 = NULLV, M2 = NULLV, M3 = NULLV, M4 = NULLV, I = NULLV, D = NULLV, cur;
-      { const int k = bk0 + lane, h = k > 0 ? k : 0, v = h - k;
+      const int bk00 = ((lo0 + hi0) >> 1) - 32;          // diagonal of lane 0
+      int cur;
+      { const int k = bk00 + lane, h = k > 0 ? k : 0, v = h - k;
         cur = (k >= lo0 && k <= hi0 && h <= tl && v <= pl) ? h : NULLV; }
-      auto extend_and_test = [&]() -> bool {
-        const int k = bk0 + lane;
-        bool more = cur >= 0;
-        if (packed) {
-          do {
-            const int h = cur, v = h - k;
-            const int vc = imin(imax(v, 0), pl), hc = imin(imax(h, 0), tl);
-            const uint64_t xx = ld32b(0, vc) ^ ld32b(offT, hc);
-            int m = xx ? (int)(__builtin_ctzll(xx) >> 1) : 32;
-            m = imin(m, imin(pl - v, tl - h));
-            if (more) cur = h + m;
-            more = more && m == 32 && v + 32 < pl && h + 32 < tl;
-          } while (__ballot(more));
-        } else {
+      const int smax = pl + tl + 64;
+      if (packed) {
+        using namespace bound_pass;
+        __builtin_amdgcn_wave_barrier();                  // the probes below read what other lanes packed (one wave: LDS operations stay in order)
+        const lds_char* SQB = (const lds_char*)&s_pk[threadIdx.x >> 6][0];
+        const int offT4 = 4 * offT;
+        int kv = bk00 + lane;                             // this lane's diagonal
+        int lim = imin(tl, pl + kv);                      // largest text offset on it: h <= tl and v = h - k <= pl
+        int lc = 64 * kv + lane - 63;                     // leader key of a cell = 128 h - lc
+        // extends the cells of row c along their matches; true when the alignment ends in this row
+        auto extend = [&](int& c) __attribute__((always_inline)) -> bool {
+          {
+            const unsigned long long valid = mk_sgt(c, -1);
+            const int rem = lim - c;                      // = min(pl - v, tl - h)
+            const int m = imin(probe32(SQB, offT4, c - kv, c), rem);
+            unsigned long long more = mk_eq(m, 32) & mk_ne(rem, 32) & valid;
+            c = sel(valid, c + m, c);
+            while (more) {                                // a lane matched 32 bases and has more to compare
+              const int rem2 = lim - c;
+              const int m2 = imin(probe32(SQB, offT4, c - kv, c), rem2);
+              c = sel(more, c + m2, c);
+              more &= mk_eq(m2, 32) & mk_ne(rem2, 32);
+            }
+          }
+          if (mk_eq(c, lim)) {                            // some cell consumed a sequence: the only cells that can end the alignment
+            const bool fin = c >= 0 && otg_ends_free_done(c, c - kv, pl, tl, pef, tef);
+            return __ballot(fin) != 0ull;
+          }
+          return false;
+        };
+        // one score: row s from rows s-4 (Mo, overwritten by row s), s-2 (Mm) and, for the leader, s-1 (Ml); Mk is row s-3
+        auto step = [&](bool lead, int& Mo, int& Mk, int& Mm, int& Ml, int& I, int& D) __attribute__((always_inline)) -> bool {
+          if (lead) {
+            // follow the leader: keep the diagonal with the furthest anti-diagonal inside lanes [24, 40)
+            const int key = sel(mk_sgt(Ml, -1), (int)(((uint32_t)Ml << 7) - (uint32_t)lc), -1);
+            const int best = otg_wave_max_i32(key);
+            if (best >= 0) {
+              const int bl = 63 - (best & 63);
+              if (bl >= 40) {                             // band moves up: lane i takes over lane i+1
+                for (int* r : {&Mo, &Mk, &Mm, &Ml, &I, &D}) *r = sel(1ull << 63, NULLV, otg_dpp_shl1(*r));
+                ++kv; lim = imin(tl, pl + kv); lc += 64;
+              } else if (bl < 24) {
+                for (int* r : {&Mo, &Mk, &Mm, &Ml, &I, &D}) *r = sel(1ull, NULLV, otg_dpp_shr1(*r));
+                --kv; lim = imin(tl, pl + kv); lc -= 64;
+              }
+            }
+          }
+          int ins = shr1(imax(I, Mo), NULLV) + 1;
+          int del = shl1(imax(D, Mo), NULLV);
+          ins = sel(mk_sgt(ins, lim), NULLV, ins);
+          del = sel(mk_sgt(del, lim), NULLV, del);
+          int mx = imax(del, imax(Mm + 1, ins));
+          mx = sel(mk_sgt(mx, lim), NULLV, mx);
+          I = ins; D = del; Mo = mx;
+          return extend(Mo);
+        };
+        int R0 = cur, R1 = NULLV, R2 = NULLV, R3 = NULLV, I = NULLV, D = NULLV;     // row r in R(r & 3)
+        if (extend(R0)) result = 0;
+        else {
+          for (int s = 1; s <= smax; s += 4) {            // a trip may run up to three scores past smax: dropped below
+            if (step(false, R1, R2, R3, R0, I, D)) { result = s; break; }
+            if (step(true, R2, R3, R0, R1, I, D)) { result = s + 1; break; }
+            if (step(false, R3, R0, R1, R2, I, D)) { result = s + 2; break; }
+            if (step(true, R0, R1, R2, R3, I, D)) { result = s + 3; break; }
+          }
+          if (result > smax) result = 0x7fffffff;
+        }
+      } else {                                            // the byte loop: the recurrence stated plainly, 8-base probes from HBM
+        int bk0 = bk00;
+        int M1 = NULLV, M2 = NULLV, M3 = NULLV, M4 = NULLV, I = NULLV, D = NULLV;
+        auto extend_and_test = [&]() -> bool {
+          const int k = bk0 + lane;
+          bool more = cur >= 0;
           do {
             const int h = cur, v = h - k;
             const int vc = imin(imax(v, 0), pl), hc = imin(imax(h, 0), tl);
@@ -327,46 +422,45 @@ __global__ __launch_bounds__(256) void wfa_affine_bound1_kernel(
             if (more) cur = h + m;
             more = more && m == 8 && v + 8 < pl && h + 8 < tl;
           } while (__ballot(more));
-        }
-        const int h = cur, v = h - k;
-        const bool fin = h >= 0 && otg_ends_free_done(h, v, pl, tl, pef, tef);
-        return __ballot(fin) != 0;
-      };
-      if (extend_and_test()) result = 0;
-      const int smax = pl + tl + 64;
-      for (int s = 1; result == 0x7fffffff && s <= smax; ++s) {
-        M4 = M3; M3 = M2; M2 = M1; M1 = cur;             // M1 = row s-1 ... M4 = row s-4
-        if ((s & 1) == 0) {
-          // follow the leader: keep the diagonal with the furthest anti-diagonal inside lanes [24, 40)
-          const int prog = M1 >= 0 ? 2 * M1 - (bk0 + lane) : NULLV;
-          const int best = otg_wave_max_i32(prog);
-          const unsigned long long at = __ballot(prog == best && best > NULLV);
-          if (at) {
-            const int bl = (int)__builtin_ctzll(at);
-            if (bl >= 40) {                               // band moves up: lane i takes over lane i+1
-              M1 = otg_dpp_shl1(M1); M2 = otg_dpp_shl1(M2); M3 = otg_dpp_shl1(M3); M4 = otg_dpp_shl1(M4); I = otg_dpp_shl1(I); D = otg_dpp_shl1(D);
-              if (lane == 63) { M1 = M2 = M3 = M4 = I = D = NULLV; }
-              ++bk0;
-            } else if (bl < 24) {
-              M1 = otg_dpp_shr1(M1); M2 = otg_dpp_shr1(M2); M3 = otg_dpp_shr1(M3); M4 = otg_dpp_shr1(M4); I = otg_dpp_shr1(I); D = otg_dpp_shr1(D);
-              if (lane == 0) { M1 = M2 = M3 = M4 = I = D = NULLV; }
-              --bk0;
+          const int h = cur, v = h - k;
+          const bool fin = h >= 0 && otg_ends_free_done(h, v, pl, tl, pef, tef);
+          return __ballot(fin) != 0;
+        };
+        if (extend_and_test()) result = 0;
+        for (int s = 1; result == 0x7fffffff && s <= smax; ++s) {
+          M4 = M3; M3 = M2; M2 = M1; M1 = cur;             // M1 = row s-1 ... M4 = row s-4
+          if ((s & 1) == 0) {
+            // follow the leader: keep the diagonal with the furthest anti-diagonal inside lanes [24, 40)
+            const int prog = M1 >= 0 ? 2 * M1 - (bk0 + lane) : NULLV;
+            const int best = otg_wave_max_i32(prog);
+            const unsigned long long at = __ballot(prog == best && best > NULLV);
+            if (at) {
+              const int bl = (int)__builtin_ctzll(at);
+              if (bl >= 40) {                               // band moves up: lane i takes over lane i+1
+                M1 = otg_dpp_shl1(M1); M2 = otg_dpp_shl1(M2); M3 = otg_dpp_shl1(M3); M4 = otg_dpp_shl1(M4); I = otg_dpp_shl1(I); D = otg_dpp_shl1(D);
+                if (lane == 63) { M1 = M2 = M3 = M4 = I = D = NULLV; }
+                ++bk0;
+              } else if (bl < 24) {
+                M1 = otg_dpp_shr1(M1); M2 = otg_dpp_shr1(M2); M3 = otg_dpp_shr1(M3); M4 = otg_dpp_shr1(M4); I = otg_dpp_shr1(I); D = otg_dpp_shr1(D);
+                if (lane == 0) { M1 = M2 = M3 = M4 = I = D = NULLV; }
+                --bk0;
+              }
             }
           }
+          const int k = bk0 + lane;
+          int mo_l = otg_dpp_shr1(M4), i_l = otg_dpp_shr1(I), mo_r = otg_dpp_shl1(M4), d_r = otg_dpp_shl1(D);
+          if (lane == 0) { mo_l = NULLV; i_l = NULLV; }
+          if (lane == 63) { mo_r = NULLV; d_r = NULLV; }
+          int ins = imax(i_l, mo_l) + 1;
+          int del = imax(d_r, mo_r);
+          const int mis = M2 + 1;
+          if (ins < 0 || ins > tl || ins - k > pl) ins = NULLV;
+          if (del < 0 || del > tl || del - k > pl) del = NULLV;
+          int mx = imax(del, imax(mis, ins));
+          if (mx < 0 || mx > tl || mx - k > pl) mx = NULLV;
+          I = ins; D = del; cur = mx;
+          if (extend_and_test()) result = s;
         }
-        const int k = bk0 + lane;
-        int mo_l = otg_dpp_shr1(M4), i_l = otg_dpp_shr1(I), mo_r = otg_dpp_shl1(M4), d_r = otg_dpp_shl1(D);
-        if (lane == 0) { mo_l = NULLV; i_l = NULLV; }
-        if (lane == 63) { mo_r = NULLV; d_r = NULLV; }
-        int ins = imax(i_l, mo_l) + 1;
-        int del = imax(d_r, mo_r);
-        const int mis = M2 + 1;
-        if (ins < 0 || ins > tl || ins - k > pl) ins = NULLV;
-        if (del < 0 || del > tl || del - k > pl) del = NULLV;
-        int mx = imax(del, imax(mis, ins));
-        if (mx < 0 || mx > tl || mx - k > pl) mx = NULLV;
-        I = ins; D = del; cur = mx;
-        if (extend_and_test()) result = s;
       }
     }
     bound[ti] = result;      // wave-uniform value, same store from every lane
@@ -896,8 +990,17 @@ int otg_launch_affine_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align
     if (bounded) {
       d_bound = (int32_t*)otg_slot(ctx, SLOT_BT_POOL, (size_t)n_tasks * sizeof(int32_t));
       if (!d_bound) return OTG_ERR_HIP;
-      const uint32_t gridU = std::min<uint32_t>(ncu * 8, (n_tasks + 3) / 4);
-      hipLaunchKernelGGL((wfa_affine_bound1_kernel<2, 4>), dim3(gridU), dim3(256), 0, ctx->stream, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_bound, &cnt->bound_ticket);
+      // The packed pair of a wave takes 2 * (length / 16 + 3) words of LDS, so the batch's longest read picks the shape: words per wave, waves per
+      // block, blocks per CU (160 KB of LDS).  Reads up to 8 kb keep eight waves per SIMD, which the score loop's dependent LDS reads want; longer
+      // reads trade waves for staying off the byte probes from HBM.  Pairs beyond the chosen shape's words take the byte loop one by one.
+      auto launch_bound = [&](auto kernel, uint32_t wpb, uint32_t bpc) {
+        const uint32_t gridU = std::min<uint32_t>(ncu * bpc, (n_tasks + wpb - 1) / wpb);
+        hipLaunchKernelGGL(kernel, dim3(gridU), dim3(wpb * 64), 0, ctx->stream, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_bound, &cnt->bound_ticket);
+      };
+      if (maxlen <= 8192) launch_bound(wfa_affine_bound1_kernel<2, 4, 1030, 4>, 4, 8);            // 16.1 KB per block
+      else if (maxlen <= 12288) launch_bound(wfa_affine_bound1_kernel<2, 4, 1542, 4>, 4, 6);      // 24.1 KB
+      else if (maxlen <= 16384) launch_bound(wfa_affine_bound1_kernel<2, 4, 2054, 4>, 4, 4);      // 32.1 KB
+      else launch_bound(wfa_affine_bound1_kernel<2, 4, 4102, 2>, 2, 4);                           // 32.0 KB: every pair of sequences below 32 766
     }
     if (d_bound && reg_mask) {
       uint32_t* hist = (uint32_t*)otg_slot(ctx, SLOT_ROWTAB, TSORT_BUCKETS * sizeof(uint32_t));
