@@ -1030,6 +1030,107 @@ typedef struct otg_repeats_job {
 int otg_repeats_files(const otg_repeats_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
 
 /* ---------------------------------------------------------------------------------------------
+ * Indel-tolerant copy numbers: an allele aligned to a cyclic repeat unit.  The two annotations above compare an allele with itself, so one
+ * inserted base moves every later copy out of phase.  Here the allele is aligned against a given unit repeated without end, free in where
+ * it starts and stops on the unit (the wraparound dynamic programme), which gives the edit count and the number of unit bases spanned
+ * whatever indels lie in between.  The reference has no counterpart; this is the definition (all integers).  For a sequence s
+ * of length L and a unit u of length p, 1 <= p <= OTG_UNITALIGN_MAX_UNIT:
+ *   1. Codes.  c = 0..3 for A/a C/c G/g T/t, 4 for any other byte (the motif table).  Code 4 matches nothing, in s or in u, not even
+ *      another 4.
+ *   2. Let t range over the substrings of u repeated infinitely, the empty one included.  edits = the minimum over t of the unit-cost edit
+ *      distance between s and t; unit_bases = the length of the shortest t that reaches that minimum.
+ *   3. end_phase comes from this DP.  Cell (i, j) is "i bases of s consumed, the next unit base is u[j]"; its key is
+ *      edits * 2^32 + unit_bases.
+ *        V[0][j] = 0 for every j;
+ *        the diagonal step:              V[i+1][(j+1) % p] <= V[i][j] + (c_s[i] == c_u[j] && c_s[i] < 4 ? 0 : 2^32) + 1;
+ *        a base of s outside the unit:   V[i+1][j] <= V[i][j] + 2^32;
+ *        a skipped unit base:            V[i][(j+1) % p] <= V[i][j] + 2^32 + 1, taken to its least fixed point around the cycle;
+ *      end_phase = the smallest j with V[L][j] minimal; (edits, unit_bases) are the fields of that minimum.
+ *   4. The start phase follows as (end_phase - unit_bases) mod p and is not stored.
+ *   5. L = 0: (0, 0, 0).
+ *   6. p = 0: zeros and flags = OTG_UNITALIGN_NO_UNIT.
+ *   7. L > OTG_UNITALIGN_MAX_LEN: zeros and flags = OTG_UNITALIGN_TOO_LONG; the batch does not fail.
+ *   8. p > OTG_UNITALIGN_MAX_UNIT: OTG_ERR_ARG when the caller passes the unit in; zeros and flags = OTG_UNITALIGN_UNIT_TOO_LONG when the
+ *      unit comes from the motif annotation (max_period goes to OTG_MOTIF_MAX_PERIOD there).
+ * It follows that edits <= L, that unit_bases <= L + edits, that rotating the unit changes only end_phase, and that letter case changes
+ * nothing.  copies = unit_bases / p and identity = 1 - edits / max(L, unit_bases) are the caller's.
+ *   otg_unitalign_batch           allele i is seq_arena[seq_off[i] .. + seq_len[i]) as in otg_motif_batch; unit k is unit_arena[unit_off[k] ..
+ *                                 + unit_len[k]); task t aligns allele task_seq[t] to unit task_unit[t].  out: n_tasks records, NULL leaves
+ *                                 them in HBM.  An index out of range, a unit over OTG_UNITALIGN_MAX_UNIT bytes, an allele or a unit outside
+ *                                 its arena: OTG_ERR_ARG.  More than 2^24 tasks: OTG_ERR_CAPACITY;
+ *   otg_unitalign_motifs          task i = allele i of the latest motif call on the context (otg_motif_batch / otg_motif_cohort) against that
+ *                                 call's unit i; both are read where they lie in HBM.  No motif results on the context: OTG_ERR_ARG;
+ *   otg_unitalign_cohort          rows [row_begin, row_begin + n) of the row list of otg_kmer_cohort_rows, the alleles read in the regrouped
+ *                                 cohort arena in place (preconditions and refusals as otg_motif_cohort).  unit_arena == NULL: task i = row
+ *                                 row_begin + i against unit i of the latest otg_motif_cohort, which must have covered the same rows.
+ *                                 Otherwise the caller's units and task lists as in otg_unitalign_batch, task_seq relative to row_begin;
+ *   otg_unitalign_device_results  the device pointer of the latest records on this context, valid until the next unit alignment on the
+ *                                 context or otg_destroy; every output is nullable;
+ *   otg_unitalign_last_ms         HIP-event time (ms) of the latest call: the binning and the alignment kernels;
+ *   otg_parse_bed_units           the units of a tandem-repeat catalogue: record i is record i of otg_parse_bed_file on the same file.  When
+ *                                 column 4 holds `MOTIFS=` at its start or after a `;` the value up to the next `;` is taken, otherwise the
+ *                                 whole field; it is split on `,`.  If every item is 1..OTG_UNITALIGN_MAX_UNIT bytes of ACGTNacgtn the items
+ *                                 are the record's units in that order (duplicates kept); otherwise, and with fewer than four columns, the
+ *                                 record has none (the column is a name).  rec_first[i] .. rec_first[i + 1] are the units of record i
+ *                                 (rec_first has *n_records + 1 entries); capacities too small: OTG_ERR_CAPACITY with the needs in the outputs;
+ *   otg_unitalign_emit            per task t the row region \t i \t seq_len \t source \t unit \t edits \t unit_bases \t copies \t identity \n.
+ *                                 The tasks of allele a = records[r].first_allele + i are task_first[a] .. task_first[a + 1] (one entry per
+ *                                 allele and one more), in that order.  source = "bed" or "motif" (task_source[t] = OTG_UNITALIGN_SOURCE_*),
+ *                                 unit = the task_unit_len[t] bytes at unit_arena + task_unit_off[t] as given ("." when there are none),
+ *                                 copies "%.2f" of unit_bases / p and identity "%.4f" of 1 - edits / max(seq_len, unit_bases); both are 0.00 /
+ *                                 0.0000 when the denominator is 0 or a flag is set.  Buffer protocol of otg_emit_alleles.
+ * The row lives in registers, unit positions across lanes; a task takes 4 .. 64 lanes by its unit length, so a wave carries up to sixteen.
+ * Alleles up to OTG_UNITALIGN_NARROW_LEN keep the key in 32 bits (two 16-bit fields; the bound is derived in otg_unitalign_core.hpp from
+ * every value a lane can hold).  OTG_UNITALIGN_WIDE=1 sends every task through the 64-bit tier, OTG_UNITALIGN_SEG64=1 gives every task a
+ * whole wave (both read once per process).
+ * ------------------------------------------------------------------------------------------- */
+#define OTG_UNITALIGN_MAX_UNIT      256
+#define OTG_UNITALIGN_MAX_LEN       1048575
+#define OTG_UNITALIGN_NARROW_LEN    ((65535 - 2 * OTG_UNITALIGN_MAX_UNIT + 1) / 2)   /* 32512: the longest allele of the 32-bit key */
+#define OTG_UNITALIGN_NO_UNIT       1u   /* otg_unitalign.flags */
+#define OTG_UNITALIGN_TOO_LONG      2u
+#define OTG_UNITALIGN_UNIT_TOO_LONG 4u
+#define OTG_UNITALIGN_SOURCE_BED    0u
+#define OTG_UNITALIGN_SOURCE_MOTIF  1u
+typedef struct otg_unitalign {
+  uint32_t edits;                /* the fewest edits against any stretch of the repeated unit        */
+  uint32_t unit_bases;           /* the length of the shortest such stretch                          */
+  uint32_t end_phase;            /* the unit position after its last base                            */
+  uint32_t flags;                /* OTG_UNITALIGN_NO_UNIT / _TOO_LONG / _UNIT_TOO_LONG               */
+} otg_unitalign;
+int otg_unitalign_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_bytes, const uint64_t* seq_off, const uint32_t* seq_len,
+                        uint32_t n_seqs, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off, const uint32_t* unit_len,
+                        uint32_t n_units, const uint32_t* task_seq, const uint32_t* task_unit, uint32_t n_tasks, otg_unitalign* out);
+int otg_unitalign_motifs(otg_ctx* ctx, otg_unitalign* out);
+int otg_unitalign_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off,
+                         const uint32_t* unit_len, uint32_t n_units, const uint32_t* task_seq, const uint32_t* task_unit, uint32_t n_tasks,
+                         otg_unitalign* out);
+int otg_unitalign_device_results(otg_ctx* ctx, uint32_t* n_tasks, const otg_unitalign** records);
+int otg_unitalign_last_ms(otg_ctx* ctx, double* ms);
+int otg_parse_bed_units(const char* path, uint64_t* rec_first, uint64_t rec_capacity, uint64_t* n_records, uint64_t* unit_off, uint32_t* unit_len,
+                        uint64_t unit_capacity, uint64_t* n_units, uint8_t* unit_arena, uint64_t arena_capacity, uint64_t* arena_bytes);
+int otg_unitalign_emit(const otg_vcf_record* records, uint32_t n_records, const char* region_arena, const uint32_t* seq_len, const uint64_t* task_first,
+                       const uint8_t* task_source, const uint8_t* unit_arena, const uint64_t* task_unit_off, const uint32_t* task_unit_len,
+                       const otg_unitalign* aligned, char* out, uint64_t out_capacity, uint64_t* out_len);
+/* Copy numbers of the alleles of a VCF against a tandem-repeat catalogue, in file order, built as otg_motifs_files is.  Per VCF record the
+ * BED record whose region string (chr:start-end, as the VCF writer prints it) equals the ID column is looked up; the first one wins when the
+ * BED repeats a region.  Where that record has units (otg_parse_bed_units) every allele gets one row per unit with source = bed.  Otherwise,
+ * and for a region the BED does not hold, every allele gets one row against its own motif-annotation unit (max_period, slack as
+ * otg_motifs_files; the unit stays on the device in between) with source = motif; the unit is "." with zeros when the period is 0.
+ * Out-of-range parameters are OTG_ERR_ARG with the message the tool prints.  stats as otg_vcf2mat_files. */
+typedef struct otg_copies_job {
+  const char* vcf_path;          /* positional <VCF[.GZ]>                                            */
+  const char* bed_path;          /* -b: required, the catalogue                                      */
+  uint32_t    max_period;        /* -p: 1..OTG_MOTIF_MAX_PERIOD (the tool's default: 256)            */
+  uint32_t    slack;             /* --slack: 0..999 per mille (the tool's default: 50)               */
+  int32_t     threads;           /* -t: host threads of the emit                                     */
+  int32_t     device;            /* HIP device ordinal                                               */
+  uint32_t    batch_alleles;     /* alleles per batch, 0 = 65536                                     */
+  uint32_t    reserved;
+} otg_copies_job;
+int otg_copies_files(const otg_copies_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
+
+/* ---------------------------------------------------------------------------------------------
  * Indexed allele BAMs from the product's own SAM text.  Every writer above emits SAM text and every reader wants a
  * coordinate-sorted BAM with its `.bai`; the reference's workflow goes through `samtools view -bh | samtools sort`, `samtools index` and
  * `samtools merge -pco` in between.  Host code (zlib + threads), no device work.

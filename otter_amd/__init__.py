@@ -11,3 +11,4 @@ from ._lib import exp_host, exp_probe  # noqa: F401
 from .abi import default_params  # noqa: F401
 from ._lib import motif_emit, motifs_files  # noqa: F401
 from ._lib import repeat_emit, repeats_files  # noqa: F401
+from ._lib import parse_bed_units, unitalign_emit, copies_files  # noqa: F401

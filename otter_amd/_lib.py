@@ -30,6 +30,8 @@ EXPORTS = [
     "otg_genotype_cluster_metric_batch", "otg_genotype_metric_last_ms", "otg_genotype_cohort_metric",
     "otg_motif_batch", "otg_motif_device_results", "otg_motif_last_ms", "otg_motif_cohort", "otg_motif_emit", "otg_motifs_files",
     "otg_repeat_batch", "otg_repeat_collect", "otg_repeat_device_results", "otg_repeat_last_ms", "otg_repeat_cohort", "otg_repeat_emit", "otg_repeats_files",
+    "otg_unitalign_batch", "otg_unitalign_motifs", "otg_unitalign_cohort", "otg_unitalign_device_results", "otg_unitalign_last_ms", "otg_unitalign_emit",
+    "otg_parse_bed_units", "otg_copies_files",
 ]
 
 _lib = None
@@ -350,6 +352,51 @@ class Context:
         a, b = C.c_double(0), C.c_double(0)
         self._check(self._L.otg_repeat_last_ms(self._h, C.byref(a), C.byref(b)), "otg_repeat_last_ms")
         return a.value, b.value
+
+    def unitalign_batch(self, arena, seq_off, seq_len, units, task_seq, task_unit, device_tensor=False):
+        """otg_unitalign_batch: allele task_seq[t] aligned to the cyclic repeat unit units[task_unit[t]] (a list of byte strings; include/otter_gpu.h
+        states the rule) -> records [n_tasks] of abi.unitalign_dt as a numpy array; or with device_tensor=True an int32 [n_tasks, 4] torch tensor
+        on this context's device that wraps the records in HBM without a copy (valid until the next unit alignment on this context)."""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+        ln = np.ascontiguousarray(seq_len, dtype=np.uint32)
+        uarena, uoff, ulen = _pack_units(units)
+        ts = np.ascontiguousarray(task_seq, dtype=np.uint32)
+        tu = np.ascontiguousarray(task_unit, dtype=np.uint32)
+        if len(ts) != len(tu):
+            raise ValueError("task_seq and task_unit differ in length")
+        n = len(ts)
+        out = np.zeros(n, dtype=abi.unitalign_dt)
+        rc = self._L.otg_unitalign_batch(self._h, abi.ptr(arena), C.c_uint64(arena.size), abi.ptr(off), abi.ptr(ln), C.c_uint32(len(ln)), abi.ptr(uarena),
+                                         C.c_uint64(int(ulen.sum())), abi.ptr(uoff), abi.ptr(ulen), C.c_uint32(len(ulen)), abi.ptr(ts), abi.ptr(tu), C.c_uint32(n),
+                                         None if device_tensor else abi.ptr(out))
+        self._check(rc, "otg_unitalign_batch")
+        return self._unitalign_device_results(n) if device_tensor else out
+
+    def unitalign_motifs(self, device_tensor=False):
+        """otg_unitalign_motifs: every allele of the latest motif call on this context (motif_batch, cohort_motifs) aligned to the unit that call
+        found for it, both read where they lie in HBM -> records as unitalign_batch returns them (period 0: flags UNITALIGN_NO_UNIT, a unit
+        over UNITALIGN_MAX_UNIT bytes: UNITALIGN_UNIT_TOO_LONG)."""
+        m = C.c_uint32(0)
+        self._check(self._L.otg_motif_device_results(self._h, C.byref(m), None, None, None), "otg_unitalign_motifs")
+        out = np.zeros(m.value, dtype=abi.unitalign_dt)
+        self._check(self._L.otg_unitalign_motifs(self._h, None if device_tensor else abi.ptr(out)), "otg_unitalign_motifs")
+        return self._unitalign_device_results(m.value) if device_tensor else out
+
+    def _unitalign_device_results(self, n):
+        if n == 0:
+            import torch
+            return torch.zeros((0, 4), dtype=torch.int32, device=torch.device("cuda", self.device))
+        m, p = C.c_uint32(0), C.c_void_p()
+        self._check(self._L.otg_unitalign_device_results(self._h, C.byref(m), C.byref(p)), "otg_unitalign_device_results")
+        assert m.value == n
+        return self._wrap_device(p.value, (n, 4), "<i4")
+
+    def unitalign_last_ms(self):
+        """binning and alignment ms of the latest unit alignment on this context (HIP events)."""
+        a = C.c_double(0)
+        self._check(self._L.otg_unitalign_last_ms(self._h, C.byref(a)), "otg_unitalign_last_ms")
+        return a.value
 
     def affine_align_batch(self, arena, tasks, x=4, o=6, e=2, want_cells=False):
         n = len(tasks)
@@ -702,6 +749,31 @@ class Context:
         return self._repeat_results(n, device_tensor, lambda sums, seg_off, total: self._L.otg_repeat_cohort(
             self._h, C.c_uint32(row_begin), C.c_uint32(n), C.c_uint32(max_period), C.c_uint32(min_copies), C.c_uint32(min_span), sums, seg_off, total),
             "otg_repeat_cohort")
+
+    def cohort_unitalign(self, row_begin=0, n=None, units=None, task_seq=None, task_unit=None, device_tensor=False):
+        """otg_unitalign_cohort: rows [row_begin, row_begin + n) of the row list (n=None: to the end) aligned to cyclic repeat units, the alleles
+        read in the cohort arena in place -> records as unitalign_batch returns them.  units=None: row i against the unit the latest
+        cohort_motifs over the same rows found for it.  Otherwise a list of byte strings with task lists as in unitalign_batch, task_seq
+        counted from row_begin."""
+        if n is None:
+            total = C.c_uint32(0)
+            self._check(self._L.otg_kmer_cohort_rows(self._h, C.byref(total), None, None, None), "otg_kmer_cohort_rows")
+            n = max(0, total.value - int(row_begin))
+        n = int(n)
+        if units is None:
+            nt, args = n, (None, C.c_uint64(0), None, None, C.c_uint32(0), None, None, C.c_uint32(0))
+        else:
+            uarena, uoff, ulen = _pack_units(units)
+            ts = np.ascontiguousarray(task_seq, dtype=np.uint32)
+            tu = np.ascontiguousarray(task_unit, dtype=np.uint32)
+            if len(ts) != len(tu):
+                raise ValueError("task_seq and task_unit differ in length")
+            nt, args = len(ts), (abi.ptr(uarena), C.c_uint64(int(ulen.sum())), abi.ptr(uoff), abi.ptr(ulen), C.c_uint32(len(ulen)), abi.ptr(ts), abi.ptr(tu),
+                                 C.c_uint32(len(ts)))
+        out = np.zeros(nt, dtype=abi.unitalign_dt)
+        rc = self._L.otg_unitalign_cohort(self._h, C.c_uint32(row_begin), C.c_uint32(n), *args, None if device_tensor else abi.ptr(out))
+        self._check(rc, "otg_unitalign_cohort")
+        return self._unitalign_device_results(nt) if device_tensor else out
 
     def cohort_end(self):
         self._check(self._L.otg_cohort_end(self._h), "otg_cohort_end")
@@ -1521,3 +1593,67 @@ def repeats_files(vcf, bed, max_period=256, min_copies=2, min_span=12, threads=1
     job.max_period = max_period; job.min_copies = min_copies; job.min_span = min_span
     job.threads = threads; job.device = device; job.batch_alleles = batch_alleles
     return _run_files_job("otg_repeats_files", job, abi.RepeatsJob)
+
+
+def _pack_units(units):
+    """a list of byte strings as (arena uint8 (never empty), offsets uint64, lengths uint32)"""
+    units = [bytes(u) for u in units]
+    ulen = np.array([len(u) for u in units], dtype=np.uint32)
+    uoff = (np.cumsum(ulen, dtype=np.uint64) - ulen).astype(np.uint64)
+    return np.frombuffer(b"".join(units) + b"\0", dtype=np.uint8).copy(), uoff, ulen
+
+
+def parse_bed_units(path):
+    """otg_parse_bed_units: the repeat units of a tandem-repeat catalogue -> one list of byte strings per BED record (the records of
+    parse_bed_file, in its order); empty where column 4 is missing or a name."""
+    L = load()
+    cap_r, cap_u, cap_a = 1024, 1024, 1 << 14
+    while True:
+        first = np.zeros(cap_r + 1, dtype=np.uint64)
+        uoff, ulen, arena = np.zeros(cap_u, dtype=np.uint64), np.zeros(cap_u, dtype=np.uint32), np.zeros(cap_a, dtype=np.uint8)
+        nr, nu, ab = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        rc = L.otg_parse_bed_units(C.c_char_p(path.encode()), abi.ptr(first), C.c_uint64(cap_r + 1), C.byref(nr), abi.ptr(uoff), abi.ptr(ulen), C.c_uint64(cap_u),
+                                   C.byref(nu), abi.ptr(arena), C.c_uint64(cap_a), C.byref(ab))
+        if rc == abi.OTG_ERR_CAPACITY:
+            cap_r, cap_u, cap_a = max(cap_r, nr.value), max(cap_u, nu.value), max(cap_a, ab.value)
+            continue
+        if rc != 0:
+            raise OtterGpuError("otg_parse_bed_units failed (%d): %s" % (rc, _err(L)))
+        raw = arena.tobytes()
+        return [[raw[int(uoff[k]):int(uoff[k]) + int(ulen[k])] for k in range(int(first[r]), int(first[r + 1]))] for r in range(nr.value)]
+
+
+def unitalign_emit(records, regions, seq_len, task_first, task_source, units, aligned):
+    """otg_unitalign_emit: the rows of otter_copies for the records (vcf_record_dt): the tasks of allele a are task_first[a] .. task_first[a + 1],
+    task t has source task_source[t] (abi.UNITALIGN_SOURCE_*), the unit units[t] (bytes, b"" for none) and the record aligned[t]
+    (unitalign_dt) -> text bytes."""
+    L = load()
+    records = np.ascontiguousarray(records, dtype=abi.vcf_record_dt)
+    seq_len = np.ascontiguousarray(seq_len, dtype=np.uint32)
+    task_first = np.ascontiguousarray(task_first, dtype=np.uint64)
+    task_source = np.ascontiguousarray(task_source, dtype=np.uint8)
+    aligned = np.ascontiguousarray(aligned, dtype=abi.unitalign_dt)
+    uarena, uoff, ulen = _pack_units(units)
+    if aligned.size == 0:
+        aligned, task_source, uoff, ulen = np.zeros(1, dtype=abi.unitalign_dt), np.zeros(1, dtype=np.uint8), np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint32)
+    reg = np.frombuffer(regions + b"\0", dtype=np.uint8)
+    need = C.c_uint64(0)
+    args = lambda out, cap: (abi.ptr(records), C.c_uint32(len(records)), abi.ptr(reg), abi.ptr(seq_len), abi.ptr(task_first), abi.ptr(task_source), abi.ptr(uarena),
+                             abi.ptr(uoff), abi.ptr(ulen), abi.ptr(aligned), out, C.c_uint64(cap), C.byref(need))
+    rc = L.otg_unitalign_emit(*args(None, 0))
+    if rc not in (0, abi.OTG_ERR_CAPACITY):
+        raise OtterGpuError("otg_unitalign_emit failed (%d): %s" % (rc, _err(L)))
+    out = C.create_string_buffer(need.value + 1)
+    rc = L.otg_unitalign_emit(*args(out, need.value))
+    if rc != 0:
+        raise OtterGpuError("otg_unitalign_emit failed (%d): %s" % (rc, _err(L)))
+    return out.raw[:need.value]
+
+
+def copies_files(vcf, bed, max_period=256, slack=50, threads=1, device=0, batch_alleles=0):
+    """otg_copies_files: the copy numbers of every allele of a VCF (plain, gzip or BGZF) against the units of a tandem-repeat catalogue, or
+    against the allele's own motif-annotation unit where the catalogue gives none, as text.  Returns (text bytes, stats dict)."""
+    job = abi.CopiesJob()
+    job.vcf_path = vcf.encode(); job.bed_path = bed.encode()
+    job.max_period = max_period; job.slack = slack; job.threads = threads; job.device = device; job.batch_alleles = batch_alleles
+    return _run_files_job("otg_copies_files", job, abi.CopiesJob)

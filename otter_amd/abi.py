@@ -251,6 +251,25 @@ class RepeatsJob(C.Structure):
                 ("threads", C.c_int32), ("device", C.c_int32), ("batch_alleles", C.c_uint32)]
 
 
+# otg_unitalign (include/otter_gpu.h) and the bounds of the unit alignment
+unitalign_dt = np.dtype([("edits", np.uint32), ("unit_bases", np.uint32), ("end_phase", np.uint32), ("flags", np.uint32)])
+assert unitalign_dt.itemsize == 16
+UNITALIGN_MAX_UNIT = 256
+UNITALIGN_MAX_LEN = 1048575
+UNITALIGN_NARROW_LEN = (65535 - 2 * UNITALIGN_MAX_UNIT + 1) // 2
+UNITALIGN_NO_UNIT = 1
+UNITALIGN_TOO_LONG = 2
+UNITALIGN_UNIT_TOO_LONG = 4
+UNITALIGN_SOURCE_BED = 0
+UNITALIGN_SOURCE_MOTIF = 1
+
+
+class CopiesJob(C.Structure):
+    """otg_copies_job (include/otter_gpu.h)."""
+    _fields_ = [("vcf_path", C.c_char_p), ("bed_path", C.c_char_p), ("max_period", C.c_uint32), ("slack", C.c_uint32), ("threads", C.c_int32),
+                ("device", C.c_int32), ("batch_alleles", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class JobStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_regions", "n_regions_ok", "n_regions_skipped", "n_reads", "n_alleles", "input_bytes", "output_bytes")] + \
                [("n_devices", C.c_uint32), ("reserved", C.c_uint32)] + [(k, C.c_double) for k in ("ms_total", "ms_ingest", "ms_hot_path", "ms_emit")]

@@ -132,20 +132,15 @@ int64_t fa_fetch(const otg_fasta* f, const std::string& chr, int beg, int end, s
   return (int64_t)seq.size();
 }
 
-} // namespace
-
-extern "C" {
-
-int otg_parse_bed_file(const char* path, otg_bed* beds, uint32_t beds_capacity, uint32_t* n_beds, char* chr_arena,
-                       uint64_t chr_capacity, uint64_t* chr_used, uint32_t* n_skipped)
+// The line loop of the BED readers (otg_parse_bed_file, otg_parse_bed_units): rec(chr, start, end, cols) per record, so record i of one
+// reader is record i of the other on the same file.
+template <class Rec>
+int bed_lines(const char* path, const char* who, uint32_t* n_skipped, Rec rec)
 {
-  if (!path || !n_beds || !chr_used) return otg_fail(nullptr, OTG_ERR_ARG, "otg_parse_bed_file: null argument");
   FILE* fp = fopen(path, "rb");
   // an unreadable file is an empty list in the reference (std::ifstream, no check); reported here instead
-  if (!fp) return otg_fail(nullptr, OTG_ERR_ARG, "otg_parse_bed_file: cannot open %s", path);
-  uint32_t n = 0, skipped = 0;
-  uint64_t used = 0;
-  bool overflow = false;
+  if (!fp) return otg_fail(nullptr, OTG_ERR_ARG, "%s: cannot open %s", who, path);
+  uint32_t skipped = 0;
   std::string line;
   std::vector<std::string> cols;
   int rc = OTG_OK;
@@ -182,12 +177,7 @@ int otg_parse_bed_file(const char* path, otg_bed* beds, uint32_t beds_capacity, 
       if (!stoul_like(cols[1], &a) || !stoul_like(cols[2], &b)) { rc = OTG_ERR_ARG; return; }
       chr = cols[0]; start = (int)(uint32_t)a; end = (int)(uint32_t)b;
     }
-    if (n < beds_capacity && beds && chr_arena && used + chr.size() <= chr_capacity) {
-      memset(&beds[n], 0, sizeof(otg_bed));
-      beds[n].chr_off = used; beds[n].chr_len = (uint32_t)chr.size(); beds[n].start = (int32_t)start; beds[n].end = (int32_t)end;
-      memcpy(chr_arena + used, chr.data(), chr.size());
-    } else overflow = true;
-    ++n; used += chr.size();
+    rec(chr, start, end, cols);
   };
   int ci;
   bool any = false;
@@ -199,9 +189,86 @@ int otg_parse_bed_file(const char* path, otg_bed* beds, uint32_t beds_capacity, 
   }
   if (rc == OTG_OK && any) handle();                          // last line without a newline
   fclose(fp);
-  if (rc != OTG_OK) return otg_fail(nullptr, rc, "otg_parse_bed_file: %s line %ld: coordinate is not a number (the reference terminates here)", path, lineno);
+  if (rc != OTG_OK) return otg_fail(nullptr, rc, "%s: %s line %ld: coordinate is not a number (the reference terminates here)", who, path, lineno);
+  if (n_skipped) *n_skipped = skipped;
+  return OTG_OK;
+}
+
+// the units of column 4 of a catalogue line (otg_parse_bed_units states the rule); empty: the column is a name
+void bed_units_of(const std::string& col, std::vector<std::string>& items)
+{
+  items.clear();
+  std::string value = col;
+  for (size_t at = 0; at != std::string::npos && at <= col.size();) {
+    if (col.compare(at, 7, "MOTIFS=") == 0) {
+      const size_t b = at + 7, e = col.find(';', b);
+      value = col.substr(b, e == std::string::npos ? std::string::npos : e - b);
+      break;
+    }
+    const size_t semi = col.find(';', at);
+    at = semi == std::string::npos ? semi : semi + 1;
+  }
+  for (size_t b = 0;;) {
+    const size_t e = value.find(',', b);
+    items.push_back(value.substr(b, e == std::string::npos ? std::string::npos : e - b));
+    if (e == std::string::npos) break;
+    b = e + 1;
+  }
+  for (const std::string& it : items) {
+    bool ok = !it.empty() && it.size() <= OTG_UNITALIGN_MAX_UNIT;
+    for (size_t k = 0; ok && k < it.size(); ++k) ok = strchr("ACGTNacgtn", it[k]) != nullptr;
+    if (!ok) { items.clear(); return; }
+  }
+}
+
+} // namespace
+
+extern "C" {
+
+int otg_parse_bed_file(const char* path, otg_bed* beds, uint32_t beds_capacity, uint32_t* n_beds, char* chr_arena,
+                       uint64_t chr_capacity, uint64_t* chr_used, uint32_t* n_skipped)
+{
+  if (!path || !n_beds || !chr_used) return otg_fail(nullptr, OTG_ERR_ARG, "otg_parse_bed_file: null argument");
+  uint32_t n = 0, skipped = 0;
+  uint64_t used = 0;
+  bool overflow = false;
+  const int rc = bed_lines(path, "otg_parse_bed_file", &skipped, [&](const std::string& chr, long long start, long long end, const std::vector<std::string>&) {
+    if (n < beds_capacity && beds && chr_arena && used + chr.size() <= chr_capacity) {
+      memset(&beds[n], 0, sizeof(otg_bed));
+      beds[n].chr_off = used; beds[n].chr_len = (uint32_t)chr.size(); beds[n].start = (int32_t)start; beds[n].end = (int32_t)end;
+      memcpy(chr_arena + used, chr.data(), chr.size());
+    } else overflow = true;
+    ++n; used += chr.size();
+  });
+  if (rc != OTG_OK) return rc;
   *n_beds = n; *chr_used = used;
   if (n_skipped) *n_skipped = skipped;
+  return overflow ? OTG_ERR_CAPACITY : OTG_OK;
+}
+
+int otg_parse_bed_units(const char* path, uint64_t* rec_first, uint64_t rec_capacity, uint64_t* n_records, uint64_t* unit_off, uint32_t* unit_len,
+                        uint64_t unit_capacity, uint64_t* n_units, uint8_t* unit_arena, uint64_t arena_capacity, uint64_t* arena_bytes)
+{
+  if (!path || !n_records || !n_units || !arena_bytes) return otg_fail(nullptr, OTG_ERR_ARG, "otg_parse_bed_units: null argument");
+  uint64_t nr = 0, nu = 0, used = 0;
+  bool overflow = false;
+  std::vector<std::string> items;
+  const int rc = bed_lines(path, "otg_parse_bed_units", nullptr, [&](const std::string&, long long, long long, const std::vector<std::string>& cols) {
+    if (rec_first && nr < rec_capacity) rec_first[nr] = nu; else overflow = true;
+    ++nr;
+    if (cols.size() < 4) return;
+    bed_units_of(cols[3], items);
+    for (const std::string& it : items) {
+      if (unit_off && unit_len && unit_arena && nu < unit_capacity && used + it.size() <= arena_capacity) {
+        unit_off[nu] = used; unit_len[nu] = (uint32_t)it.size();
+        memcpy(unit_arena + used, it.data(), it.size());
+      } else overflow = true;
+      ++nu; used += it.size();
+    }
+  });
+  if (rc != OTG_OK) return rc;
+  if (rec_first && nr < rec_capacity) rec_first[nr] = nu; else overflow = true;      // n_records + 1 entries
+  *n_records = nr; *n_units = nu; *arena_bytes = used;
   return overflow ? OTG_ERR_CAPACITY : OTG_OK;
 }
 

@@ -532,6 +532,33 @@ int otg_repeat_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, uint32_t max
                              max_period, min_copies, min_span, sums, seg_off, n_segments);
 }
 
+int otg_unitalign_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off,
+                         const uint32_t* unit_len, uint32_t n_units, const uint32_t* task_seq, const uint32_t* task_unit, uint32_t n_tasks, otg_unitalign* out)
+{
+  Cohort* cp = cohort_of(ctx, "otg_unitalign_cohort");
+  if (!cp) return ctx ? OTG_ERR_ARG : OTG_ERR_NO_DEVICE;
+  Cohort& c = *cp;
+  if (!c.clustered) return otg_fail(ctx, OTG_ERR_ARG, "otg_unitalign_cohort: the batch has not been clustered (otg_cohort_genotype)");
+  if (int rc = cohort_build_rows(ctx, c, "otg_unitalign_cohort")) return rc;
+  if ((uint64_t)row_begin + n > c.n_rows) return otg_fail(ctx, OTG_ERR_ARG, "otg_unitalign_cohort: rows %u .. %llu of %u", row_begin, (unsigned long long)row_begin + n, c.n_rows);
+  const uint64_t* d_off = (const uint64_t*)c.row_off.p + row_begin;
+  const uint32_t* d_len = (const uint32_t*)c.row_len.p + row_begin;
+  if (!unit_arena && !n_units) {                                   // the units of the latest otg_motif_cohort, which stay where they are
+    if (ctx->last_motif_n == 0 || ctx->last_motif_arena != (const uint8_t*)c.arena.p || ctx->last_motif_off != d_off || ctx->last_motif_n != n)
+      return otg_fail(ctx, OTG_ERR_ARG, "otg_unitalign_cohort: the latest motif call on this context was not otg_motif_cohort over rows %u .. %llu", row_begin,
+                      (unsigned long long)row_begin + n);
+    return otg_unitalign_motifs(ctx, out);
+  }
+  if (int rc = otg_unitalign_check(ctx, "otg_unitalign_cohort", n, unit_arena, unit_bytes, unit_off, unit_len, n_units, task_seq, task_unit, n_tasks)) return rc;
+  ctx->last_unitalign_ms = 0.0; ctx->last_unitalign_n = 0;
+  if (n_tasks == 0) return OTG_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  OtgUnitSource units;
+  const uint32_t *d_ts = nullptr, *d_tu = nullptr;
+  if (int rc = otg_unitalign_upload(ctx, unit_arena, unit_bytes, unit_off, unit_len, n_units, task_seq, task_unit, n_tasks, &units, &d_ts, &d_tu)) return rc;
+  return otg_unitalign_resident(ctx, "otg_unitalign_cohort", (const uint8_t*)c.arena.p, d_off, d_len, units, d_ts, d_tu, n_tasks, out);
+}
+
 int otg_cohort_end(otg_ctx* ctx)
 {
   if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_cohort_end: no context");
@@ -540,3 +567,10 @@ int otg_cohort_end(otg_ctx* ctx)
 }
 
 } // extern "C"
+
+// unitalign.hip: do the rows a motif call read at d_arena still lie there?
+bool otg_cohort_holds_rows(otg_ctx* ctx, const uint8_t* d_arena)
+{
+  const Cohort* c = ctx ? ctx->cohort : nullptr;
+  return c && c->open && c->clustered && c->rows_built && d_arena && (const uint8_t*)c->arena.p == d_arena;
+}

@@ -17,6 +17,7 @@
 #include "otg_vcf2mat.hpp"
 #include "otg_motif.hpp"
 #include "otg_repeat.hpp"
+#include "otg_unitalign.hpp"
 #include <cmath>
 #include <algorithm>
 #include <atomic>
@@ -1144,6 +1145,112 @@ int otg_repeats_files(const otg_repeats_job* job, otg_write_fn write, void* user
     },
     [&](std::string& o, const VcfBatch& B, uint32_t r0, uint32_t nr) {
       otg_repeat_rows(o, B.rec.data() + r0, nr, B.regions.data(), B.seqs.data(), B.off.data(), B.len.data(), sums.data(), seg_off.data(), segs.data());
+    });
+}
+
+// Copy numbers of a VCF's alleles against a tandem-repeat catalogue, on vcf_allele_job as otg_motifs_files.  A batch makes up to two device
+// passes: the alleles of catalogue regions against their units (otg_unitalign_batch, only the units the batch uses are uploaded), the others
+// through otg_motif_batch and otg_unitalign_motifs, whose units never leave the device in between.
+int otg_copies_files(const otg_copies_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
+{
+  if (!job || !write || !job->vcf_path || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "otg_copies_files: NULL job, writer, VCF or BED path");
+  const uint32_t max_period = job->max_period, slack = job->slack;
+  if (max_period < 1 || max_period > OTG_MOTIF_MAX_PERIOD)
+    return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--max-period' (%u). Needs to be 1 <= x <= %d.", max_period, OTG_MOTIF_MAX_PERIOD);
+  if (slack > 999) return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--slack' (%u). Needs to be 0 <= x <= 999.", slack);
+  // the catalogue: region string -> BED record (the first one wins), and the units of every record
+  Bed bed;
+  if (int rc = load_bed(job->bed_path, bed)) return rc;
+  std::vector<uint64_t> cat_first, cat_off;
+  std::vector<uint32_t> cat_len;
+  std::vector<uint8_t> cat_arena;
+  {
+    uint64_t nr = 0, nu = 0, ab = 0;
+    int rc = otg_parse_bed_units(job->bed_path, nullptr, 0, &nr, nullptr, nullptr, 0, &nu, nullptr, 0, &ab);
+    if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) return rc;
+    cat_first.resize(nr + 1); cat_off.resize(nu + 1); cat_len.resize(nu + 1); cat_arena.resize(ab + 1);
+    rc = otg_parse_bed_units(job->bed_path, cat_first.data(), cat_first.size(), &nr, cat_off.data(), cat_len.data(), nu, &nu, cat_arena.data(), ab, &ab);
+    if (rc != OTG_OK) return rc;
+    if (nr != bed.beds.size()) return otg_fail(nullptr, OTG_ERR_FATAL, "otg_copies_files: the two BED readers disagree on %s", job->bed_path);
+  }
+  std::map<std::string, uint32_t> by_region;
+  {
+    std::string name;
+    for (uint32_t r = 0; r < bed.beds.size(); ++r) {
+      name.clear();
+      otg_region_name(name, bed.chr_arena.data() + bed.beds[r].chr_off, bed.beds[r].chr_len, bed.beds[r].start, bed.beds[r].end);
+      by_region.emplace(name, r);
+    }
+  }
+  // per batch: the tasks in file order (allele a: task_first[a] .. task_first[a + 1]) and where each one's unit and record lie
+  std::vector<uint64_t> task_first, unit_off, m_off, b_uoff;
+  std::vector<uint32_t> unit_len, m_len, b_ulen, b_tseq, b_tunit, b_task, m_task;
+  std::vector<uint8_t> source, units, b_units, m_units;
+  std::vector<otg_unitalign> aligned, part;
+  std::vector<otg_motif> motifs;
+  return vcf_allele_job("otg_copies_files", job->vcf_path, job->bed_path, job->device, job->batch_alleles ? job->batch_alleles : 65536, job->threads, write, user, stats,
+    [&](otg_ctx* ctx, const VcfBatch& B) {
+      task_first.assign((size_t)B.na + 1, 0);
+      unit_off.clear(); unit_len.clear(); source.clear(); units.clear();
+      b_uoff.clear(); b_ulen.clear(); b_units.clear(); b_tseq.clear(); b_tunit.clear(); b_task.clear();
+      m_off.clear(); m_len.clear(); m_task.clear();
+      std::string name;
+      for (uint32_t r = 0; r < B.nr; ++r) {
+        const otg_vcf_record& R = B.rec[r];
+        name.assign(B.regions.data() + R.region_off, R.region_len);
+        const auto it = by_region.find(name);
+        const uint64_t u0 = it == by_region.end() ? 0 : cat_first[it->second], u1 = it == by_region.end() ? 0 : cat_first[it->second + 1];
+        const uint32_t bu0 = (uint32_t)b_ulen.size();
+        for (uint64_t k = u0; k < u1; ++k) {                       // the record's units, once per record
+          b_uoff.push_back(b_units.size()); b_ulen.push_back(cat_len[k]);
+          b_units.insert(b_units.end(), cat_arena.begin() + cat_off[k], cat_arena.begin() + cat_off[k] + cat_len[k]);
+        }
+        for (uint32_t i = 0; i < R.n_alleles; ++i) {
+          const uint32_t a = R.first_allele + i;
+          task_first[a] = source.size();
+          if (u1 > u0) {
+            for (uint64_t k = u0; k < u1; ++k) {
+              b_task.push_back((uint32_t)source.size()); b_tseq.push_back(a); b_tunit.push_back(bu0 + (uint32_t)(k - u0));
+              source.push_back(OTG_UNITALIGN_SOURCE_BED);
+              unit_off.push_back(units.size()); unit_len.push_back(cat_len[k]);
+              units.insert(units.end(), cat_arena.begin() + cat_off[k], cat_arena.begin() + cat_off[k] + cat_len[k]);
+            }
+          } else {
+            m_task.push_back((uint32_t)source.size()); m_off.push_back(B.off[a]); m_len.push_back(B.len[a]);
+            source.push_back(OTG_UNITALIGN_SOURCE_MOTIF);
+            unit_off.push_back(0); unit_len.push_back(0);         // filled in behind the motif pass
+          }
+        }
+      }
+      task_first[B.na] = source.size();
+      aligned.assign(source.size(), otg_unitalign{0u, 0u, 0u, 0u});
+      if (!b_task.empty()) {
+        part.resize(b_task.size());
+        if (int rc = otg_unitalign_batch(ctx, B.seqs.data(), B.au, B.off.data(), B.len.data(), B.na, b_units.data(), b_units.size(), b_uoff.data(), b_ulen.data(),
+                                         (uint32_t)b_ulen.size(), b_tseq.data(), b_tunit.data(), (uint32_t)b_task.size(), part.data())) return rc;
+        for (size_t k = 0; k < b_task.size(); ++k) aligned[b_task[k]] = part[k];
+      }
+      if (!m_task.empty()) {
+        const uint32_t nm = (uint32_t)m_task.size();
+        uint32_t max_len = 0;
+        for (uint32_t L : m_len) max_len = std::max(max_len, L);
+        const uint32_t stride = std::max<uint32_t>(1, std::min<uint32_t>(max_period, max_len / 2));
+        motifs.resize(nm); m_units.resize((size_t)nm * stride); part.resize(nm);
+        if (int rc = otg_motif_batch(ctx, B.seqs.data(), B.au, m_off.data(), m_len.data(), nm, max_period, slack, motifs.data(), m_units.data(), stride)) return rc;
+        if (int rc = otg_unitalign_motifs(ctx, part.data())) return rc;
+        for (uint32_t k = 0; k < nm; ++k) {
+          const uint32_t t = m_task[k], p = motifs[k].period;
+          aligned[t] = part[k];
+          unit_off[t] = units.size(); unit_len[t] = p;
+          units.insert(units.end(), m_units.begin() + (size_t)k * stride, m_units.begin() + (size_t)k * stride + p);
+        }
+      }
+      units.push_back(0);                                          // (never empty: the emit takes its address)
+      return (int)OTG_OK;
+    },
+    [&](std::string& o, const VcfBatch& B, uint32_t r0, uint32_t nr) {
+      otg_unitalign_rows(o, B.rec.data() + r0, nr, B.regions.data(), B.len.data(), task_first.data(), source.data(), units.data(), unit_off.data(), unit_len.data(),
+                         aligned.data());
     });
 }
 

@@ -164,6 +164,7 @@ int otg_emit_vcf_lines(const otg_bed* beds, const char* chr_arena, uint32_t n_re
   if ((n_regions && (!beds || !first_allele || !gt || !hsd || !n_gt || !reps)) || !out_len) return otg_fail(nullptr, OTG_ERR_ARG, "otg_emit_vcf_lines: null argument");
   Sink s{out, out_capacity, 0};
   std::vector<int> first(n_samples + 1), second(n_samples + 1), g2, rc;
+  std::string region_name;
   for (uint32_t r = 0; r < n_regions; ++r) {
     const uint32_t a0 = first_allele[r], na = first_allele[r + 1] - a0;
     if (na == 0) continue;                                        // "[WARNING] no alleles found": no line
@@ -191,7 +192,9 @@ int otg_emit_vcf_lines(const otg_bed* beds, const char* chr_arena, uint32_t n_re
     const otg_bed& b = beds[r];
     const char* chr = chr_arena + b.chr_off;
     s.put(chr, b.chr_len); s.ch('\t'); s.u64((uint32_t)(1u + (uint32_t)b.start - (uint32_t)offset_l)); s.ch('\t');
-    s.put(chr, b.chr_len); s.ch(':'); s.u64((uint32_t)b.start); s.ch('-'); s.u64((uint32_t)b.end); s.ch('\t');
+    region_name.clear();
+    otg_region_name(region_name, chr, b.chr_len, b.start, b.end);
+    s.put(region_name.data(), region_name.size()); s.ch('\t');
     s.put((const char*)seqs + A[ref_i].seq_off, A[ref_i].seq_len); s.ch('\t');
     if (ngt == 1) s.ch('.');
     else for (int i = 1; i < ngt; ++i) {

@@ -278,6 +278,7 @@ int otg_motif_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, co
   HIP_TRY(ctx, hipEventElapsedTime(&r_ms, ctx->ev1, ctx->ev2));
   ctx->last_motif_count_ms = c_ms; ctx->last_motif_reduce_ms = r_ms;
   ctx->last_motif_n = n; ctx->last_motif_stride = unit_stride;
+  ctx->last_motif_arena = d_arena; ctx->last_motif_off = d_off; ctx->last_motif_len = d_len;
   return OTG_OK;
 }
 

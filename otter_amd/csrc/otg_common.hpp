@@ -50,6 +50,12 @@ struct otg_ctx {
   uint32_t last_repeat_n = 0;                                     // the shape of the results in SLOT_REPEAT_RES / SLOT_REPEAT_SEGS (otg_repeat_device_results);
   uint64_t last_repeat_total = 0;                                 // valid: a repeat call with n > 0 has succeeded since the last one began
   bool last_repeat_valid = false;
+  // where the latest motif call read its alleles (device pointers, n = last_motif_n): otg_unitalign_motifs aligns them in place
+  const uint8_t* last_motif_arena = nullptr;
+  const uint64_t* last_motif_off = nullptr;
+  const uint32_t* last_motif_len = nullptr;
+  double last_unitalign_ms = 0.0;                                 // HIP-event time of the latest unit alignment (otg_unitalign_last_ms)
+  uint32_t last_unitalign_n = 0;                                  // the records in SLOT_UNITALIGN_OUT (otg_unitalign_device_results); 0: none
   double last_kernel_ms = 0.0;                    // HIP-event time of the kernels of the latest operator-level call that reports one (otg_last_kernel_ms)
   // the latest genotype clustering with a metric (genotype_edit.hip): times of its two parts (otg_genotype_metric_last_ms), whether the edit
   // matrix was built, and where its counters lie in SLOT_GTE_CLS
@@ -105,8 +111,18 @@ enum {
   SLOT_MOTIF_SEQ, SLOT_MOTIF_META, SLOT_MOTIF_OFF, SLOT_MOTIF_M, SLOT_MOTIF_PLANES, SLOT_MOTIF_OUT,   // otg_motif_batch (motif.hip); OUT stays valid for the device results
   SLOT_REPEAT_SEQ, SLOT_REPEAT_META, SLOT_REPEAT_OFF, SLOT_REPEAT_CNT, SLOT_REPEAT_PLANES, SLOT_REPEAT_RUNS, SLOT_REPEAT_STACK, SLOT_REPEAT_SCRATCH,   // otg_repeat_batch (repeat.hip)
   SLOT_REPEAT_RES, SLOT_REPEAT_SEGS,                                // its summaries and offsets / its segments: they stay valid for the device results
+  SLOT_UNITALIGN_SEQ, SLOT_UNITALIGN_META, SLOT_UNITALIGN_UNITS, SLOT_UNITALIGN_BINS, SLOT_UNITALIGN_ORDER,   // otg_unitalign_batch (unitalign.hip)
+  SLOT_UNITALIGN_OUT,                                               // its records: they stay valid for the device results
   SLOT_COUNT
 };
+
+// The region string of a BED record as the VCF writer prints it in the ID column (BED::toScString, src/anbed.cpp:17-20: coordinates unsigned);
+// appended to o.  otg_emit_vcf_lines writes it, otg_copies_files looks VCF records up by it.
+inline void otg_region_name(std::string& o, const char* chr, uint32_t chr_len, int32_t start, int32_t end)
+{
+  o.append(chr, chr_len);
+  o += ':'; o += std::to_string((uint32_t)start); o += '-'; o += std::to_string((uint32_t)end);
+}
 
 void otg_pipeline_free(otg_ctx* ctx);
 int64_t otg_pipeline_run_regions(otg_ctx* ctx);
@@ -357,6 +373,20 @@ uint32_t otg_motif_lds_len();
 void otg_motif_plane_scan(otg_ctx* ctx, const uint32_t* d_len, uint32_t n, uint32_t max_period, uint32_t lds_len, uint64_t* d_ploff, uint64_t* d_total);
 void otg_motif_pack_planes(otg_ctx* ctx, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, uint32_t n, const uint64_t* d_ploff,
                            uint32_t* d_planes);
+// unitalign.hip: the launch part of the unit alignment on device-resident alleles and units.  Allele a is d_arena[d_off[a] .. + d_len[a]) (the
+// arena extends 15 bytes past every row).  Unit k is d_units[d_unit_off[k] .. + d_unit_len[k]), or with d_unit_off == NULL the slot
+// d_units + k * unit_stride whose length is d_motifs[k].period.  Task t aligns allele d_task_seq[t] to unit d_task_unit[t]; NULL lists: t.
+struct OtgUnitSource {
+  const uint8_t* d_units; const uint64_t* d_unit_off; const uint32_t* d_unit_len; const otg_motif* d_motifs; uint32_t unit_stride;
+};
+int otg_unitalign_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, const OtgUnitSource& units,
+                           const uint32_t* d_task_seq, const uint32_t* d_task_unit, uint32_t n_tasks, otg_unitalign* out);
+// its refusals of a caller's units and task lists (host arrays), and the upload of both into the context's slots
+int otg_unitalign_check(otg_ctx* ctx, const char* who, uint32_t n_seqs, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off,
+                        const uint32_t* unit_len, uint32_t n_units, const uint32_t* task_seq, const uint32_t* task_unit, uint32_t n_tasks);
+int otg_unitalign_upload(otg_ctx* ctx, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off, const uint32_t* unit_len, uint32_t n_units,
+                         const uint32_t* task_seq, const uint32_t* task_unit, uint32_t n_tasks, OtgUnitSource* units, const uint32_t** d_task_seq,
+                         const uint32_t** d_task_unit);
 // repeat.hip: the argument refusals of otg_repeat_batch and its launch part on device-resident rows (cohort.hip), as the motif pair above
 int otg_repeat_args(otg_ctx* ctx, const char* who, uint32_t max_period, uint32_t min_copies, uint32_t min_span);
 int otg_repeat_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, uint32_t n,

@@ -1,0 +1,10 @@
+// otg_unitalign.hpp — the row text of `otter_copies`, shared by unitalign_emit.hip and the dispatcher.
+#pragma once
+#include <cstdint>
+#include <string>
+#include "../../include/otter_gpu.h"
+
+// appends the rows of records[0 .. n_records) to o (the text of otg_unitalign_emit)
+void otg_unitalign_rows(std::string& o, const otg_vcf_record* records, uint32_t n_records, const char* region_arena, const uint32_t* seq_len,
+                        const uint64_t* task_first, const uint8_t* task_source, const uint8_t* unit_arena, const uint64_t* task_unit_off,
+                        const uint32_t* task_unit_len, const otg_unitalign* aligned);
