@@ -1131,6 +1131,120 @@ typedef struct otg_copies_job {
 int otg_copies_files(const otg_copies_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
 
 /* ---------------------------------------------------------------------------------------------
+ * Joint parse of an allele against several repeat units.  A catalogue describes a locus as several units (MOTIFS=CAG,CCG); the unit
+ * alignment above takes one unit per task, so each unit counts the other's tract as edits and nothing says where one tract ends.  Here one
+ * alignment runs over all units of a set, joined at their unit boundaries, and a traceback gives the segments: how many copies of each unit,
+ * in which order, over which allele bases, at how many edits.  The reference has no counterpart; this is the definition (all integers;
+ * DESIGN.md §9).  A task is a sequence s of length L and an ordered unit set u_0 .. u_{K-1}, 1 <= K <= OTG_UNITPARSE_MAX_UNITS, every p_k in
+ * 1..OTG_UNITALIGN_MAX_UNIT.  Codes and matching are those of the unit alignment: code 4 matches nothing, letter case changes nothing.
+ *   1. Language.  Let t range over the concatenations of pieces, the empty one included.  A piece is a non-empty substring of one u_k
+ *      repeated without end.  Two adjacent pieces belong to different units and meet at a unit boundary: the left one ends with the last base
+ *      of a copy, the right one starts at base 0.  switches(t) = pieces - 1, 0 for the empty t.  The result is the lexicographic minimum over
+ *      t of (the unit-cost edit distance of s and t, switches(t), |t|), reported as edits, switches, unit_bases.
+ *   2. The DP that defines phases, ties and the path.  Cell (i, k, j) is "i bases of s consumed, the next unit base is u_k[j]"; its key is
+ *      edits * 2^42 + switches * 2^21 + unit_bases, so one unsigned minimum gives the lexicographic order.
+ *        V[0][k][j] = 0 everywhere;
+ *        the diagonal step:              V[i+1][k][(j+1) % p_k] <= V[i][k][j] + (c_s[i] == c_u[j] && c_s[i] < 4 ? 0 : 2^42) + 1;
+ *        a base of s outside the unit:   V[i+1][k][j] <= V[i][k][j] + 2^42;
+ *        a skipped unit base:            V[i][k][(j+1) % p_k] <= V[i][k][j] + 2^42 + 1;
+ *        a switch, only at phase 0:      V[i][k'][0] <= V[i][k][0] + 2^21 for k' != k;
+ *      the skip and the switch are taken together to their least fixed point within a row.  The end cell is the smallest (k, j) in unit-set
+ *      order with V[L] minimal: end_unit, end_phase.
+ *   3. The reported path is traced back from the end cell.  At every cell the first predecessor in this order whose value plus step cost
+ *      equals the cell's value is taken: the diagonal; the base outside the unit; the skip from position j - 1 of the same unit (for j = 0
+ *      from p_k - 1); the switch from the lowest k'.  The trace stops at row 0 (every cell there is 0).  In-row steps all cost something, so
+ *      the trace cannot cycle.
+ *   4. Segments.  A segment is a maximal stretch of the path inside one unit: {unit, begin, end, unit_bases, edits, start_phase}.  [begin,
+ *      end) are allele positions (the rows the stretch consumed) and the segments tile [0, L); start_phase is the unit position at the
+ *      path's start for the first segment and 0 for the others; the edits and unit_bases of the segments sum to the task's; n_segments =
+ *      switches + 1 when L > 0.  L = 0: no segments, all zeros.
+ *   5. Refusals.  An empty unit set, K > OTG_UNITPARSE_MAX_UNITS, a unit of 0 or over OTG_UNITALIGN_MAX_UNIT bytes, or a set that does not fit
+ *      one wave (the sum of ceil(p_k / 4) over the set exceeds OTG_UNITPARSE_MAX_LANES) is OTG_ERR_ARG from a caller.  L >
+ *      OTG_UNITPARSE_MAX_LEN: zeros, no segments and flags = OTG_UNITPARSE_TOO_LONG; the batch does not fail.  OTG_UNITPARSE_MAX_LEN is the
+ *      largest L for which no key field carries (derived value by value in otg_unitparse_core.hpp).
+ * It follows that K = 1 gives the (edits, unit_bases, end_phase) of the unit alignment, and that an interruption that is itself a unit of
+ * the set is a segment, not an edit.
+ *   otg_unitparse_batch           alleles and units as in otg_unitalign_batch; set q is units set_first[q] .. set_first[q + 1) in that order
+ *                                 (the rec_first of otg_parse_bed_units); task t parses allele task_seq[t] against set task_set[t].  sums:
+ *                                 n_tasks summaries; seg_off: n_tasks + 1 offsets into the segments, which stay in HBM; *n_segments =
+ *                                 seg_off[n_tasks].  Every output is nullable.  An index out of range, an allele or a unit outside its arena
+ *                                 and the refusals of step 5: OTG_ERR_ARG.  More than 2^24 tasks: OTG_ERR_CAPACITY;
+ *   otg_unitparse_collect         copies the segments of the latest call on the context to segs[0 .. total); capacity < total is
+ *                                 OTG_ERR_CAPACITY with the needed count in the message;
+ *   otg_unitparse_device_results  device pointers of the latest results on this context (n summaries, n + 1 offsets, total segments), valid
+ *                                 until the next unit parse on the context or otg_destroy; every output is nullable;
+ *   otg_unitparse_last_ms         HIP-event times (ms) of the latest call: forward_ms = the alignment kernels, trace_ms = the scan of the
+ *                                 segment counts and the backward walk;
+ *   otg_unitparse_cohort          rows [row_begin, row_begin + n) of the row list of otg_kmer_cohort_rows, the alleles read in the regrouped
+ *                                 cohort arena in place (preconditions and refusals as otg_unitalign_cohort with caller units; only the row
+ *                                 lengths come to the host, where the tasks are ordered); task_seq is relative to row_begin;
+ *   otg_unitparse_emit            per allele a = records[r].first_allele + i the row region \t i \t seq_len[a] \t units \t edits \t switches \t
+ *                                 unit_bases \t identity \t counts \t structure \n.  The unit set of allele a is set allele_set[a] (units
+ *                                 set_first[q] .. set_first[q + 1), or OTG_UNITPARSE_NO_SET), unit k the unit_len[k] bytes at unit_arena +
+ *                                 unit_off[k]; sums[a] and seg_off[a] are the allele's; units = the set comma-joined as given; identity as in otg_unitalign_emit; counts = per unit of
+ *                                 the set the unit bases of its segments / p_k as "%.2f", comma-joined; structure = the segments
+ *                                 (segs[seg_off[a] .. seg_off[a + 1])) left to right as (UNIT)c, c = unit_bases / p as an integer when it
+ *                                 divides and "%.2f" otherwise, followed by ~e when the segment has e > 0 edits; "." when there are none.  An
+ *                                 allele without units gives "." for units, zeros, and "." for counts and structure.  A segment that names a
+ *                                 unit outside its set is OTG_ERR_ARG.  Buffer protocol of otg_emit_alleles.
+ * The forward pass keeps the row in registers as the unit alignment does, every unit at a lane boundary.  It stores decisions, not keys:
+ * two bits per cell and one per unit and row, as wave ballots (2 R + 1 words of 64 bits per row and wave).  A call is cut into chunks of
+ * tasks whose store stays under OTG_UNITPARSE_TRACE_MB megabytes (default 1024; read once per process; a single task above it runs alone;
+ * DESIGN.md §8); with more than one chunk the forward pass runs once more without the store, for the segment counts.
+ * ------------------------------------------------------------------------------------------- */
+#define OTG_UNITPARSE_MAX_UNITS 8
+#define OTG_UNITPARSE_MAX_LANES 64
+#define OTG_UNITPARSE_MAX_LEN   ((2097151 - 2 * OTG_UNITALIGN_MAX_UNIT + 1) / 2)   /* 1048320 */
+#define OTG_UNITPARSE_TOO_LONG  1u   /* otg_unitparse_sum.flags */
+#define OTG_UNITPARSE_NO_SET    0xffffffffu   /* otg_unitparse_emit: an allele without units */
+typedef struct otg_unitparse_sum {
+  uint32_t edits;                /* the fewest edits against any word of the language               */
+  uint32_t switches;             /* the fewest switches at those edits                               */
+  uint32_t unit_bases;           /* the shortest such word                                           */
+  uint32_t n_segments;           /* switches + 1; 0 for an empty or refused allele                   */
+  uint32_t end_unit;             /* the unit of the end cell, an index into the set                  */
+  uint32_t end_phase;            /* the unit position after the path's last base                     */
+  uint32_t flags;                /* OTG_UNITPARSE_TOO_LONG                                           */
+  uint32_t reserved;             /* 0                                                                */
+} otg_unitparse_sum;
+typedef struct otg_unitparse_seg {
+  uint32_t unit;                 /* an index into the task's unit set                                */
+  uint32_t begin;                /* allele positions [begin, end)                                    */
+  uint32_t end;
+  uint32_t unit_bases;
+  uint32_t edits;
+  uint32_t start_phase;          /* the unit position at the path's start; 0 behind a switch         */
+} otg_unitparse_seg;
+int otg_unitparse_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_bytes, const uint64_t* seq_off, const uint32_t* seq_len,
+                        uint32_t n_seqs, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off, const uint32_t* unit_len,
+                        uint32_t n_units, const uint64_t* set_first, uint32_t n_sets, const uint32_t* task_seq, const uint32_t* task_set,
+                        uint32_t n_tasks, otg_unitparse_sum* sums, uint64_t* seg_off, uint64_t* n_segments);
+int otg_unitparse_collect(otg_ctx* ctx, otg_unitparse_seg* segs, uint64_t capacity);
+int otg_unitparse_device_results(otg_ctx* ctx, uint32_t* n_tasks, const otg_unitparse_sum** sums, const uint64_t** seg_off,
+                                 const otg_unitparse_seg** segs, uint64_t* total);
+int otg_unitparse_last_ms(otg_ctx* ctx, double* forward_ms, double* trace_ms);
+int otg_unitparse_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off,
+                         const uint32_t* unit_len, uint32_t n_units, const uint64_t* set_first, uint32_t n_sets, const uint32_t* task_seq,
+                         const uint32_t* task_set, uint32_t n_tasks, otg_unitparse_sum* sums, uint64_t* seg_off, uint64_t* n_segments);
+int otg_unitparse_emit(const otg_vcf_record* records, uint32_t n_records, const char* region_arena, const uint32_t* seq_len,
+                       const uint32_t* allele_set, const uint64_t* set_first, const uint8_t* unit_arena, const uint64_t* unit_off,
+                       const uint32_t* unit_len, const otg_unitparse_sum* sums, const uint64_t* seg_off, const otg_unitparse_seg* segs, char* out, uint64_t out_capacity,
+                       uint64_t* out_len);
+/* The joint parse of the alleles of a VCF against a tandem-repeat catalogue, in file order, built as otg_copies_files is.  Per VCF record the
+ * BED record whose region string equals the ID column is looked up (the first one wins); every allele gets one row against that record's
+ * unit set.  A region with no units in the catalogue, or one not in it, gives the row without units.  A unit set the parse refuses (step 5)
+ * is OTG_ERR_ARG with the region in the message.  stats as otg_vcf2mat_files. */
+typedef struct otg_unitparse_job {
+  const char* vcf_path;          /* positional <VCF[.GZ]>                                            */
+  const char* bed_path;          /* -b: required, the catalogue                                      */
+  int32_t     threads;           /* -t: host threads of the emit                                     */
+  int32_t     device;            /* HIP device ordinal                                               */
+  uint32_t    batch_alleles;     /* alleles per batch, 0 = 65536                                     */
+  uint32_t    reserved;
+} otg_unitparse_job;
+int otg_unitparse_files(const otg_unitparse_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
+
+/* ---------------------------------------------------------------------------------------------
  * Indexed allele BAMs from the product's own SAM text.  Every writer above emits SAM text and every reader wants a
  * coordinate-sorted BAM with its `.bai`; the reference's workflow goes through `samtools view -bh | samtools sort`, `samtools index` and
  * `samtools merge -pco` in between.  Host code (zlib + threads), no device work.

@@ -32,6 +32,8 @@ EXPORTS = [
     "otg_repeat_batch", "otg_repeat_collect", "otg_repeat_device_results", "otg_repeat_last_ms", "otg_repeat_cohort", "otg_repeat_emit", "otg_repeats_files",
     "otg_unitalign_batch", "otg_unitalign_motifs", "otg_unitalign_cohort", "otg_unitalign_device_results", "otg_unitalign_last_ms", "otg_unitalign_emit",
     "otg_parse_bed_units", "otg_copies_files",
+    "otg_unitparse_batch", "otg_unitparse_collect", "otg_unitparse_device_results", "otg_unitparse_last_ms", "otg_unitparse_cohort", "otg_unitparse_emit",
+    "otg_unitparse_files",
 ]
 
 _lib = None
@@ -397,6 +399,47 @@ class Context:
         a = C.c_double(0)
         self._check(self._L.otg_unitalign_last_ms(self._h, C.byref(a)), "otg_unitalign_last_ms")
         return a.value
+
+    def unitparse_batch(self, arena, seq_off, seq_len, unit_sets, task_seq, task_set, device_tensor=False):
+        """otg_unitparse_batch (and otg_unitparse_collect): allele task_seq[t] parsed against the unit set unit_sets[task_set[t]] (a list of lists
+        of byte strings; include/otter_gpu.h states the rule) -> (sums [n_tasks] of abi.unitparse_sum_dt, seg_off [n_tasks + 1] uint64, segs [total]
+        of abi.unitparse_seg_dt; the segments of task t are segs[seg_off[t]:seg_off[t + 1]]) as numpy arrays; or with device_tensor=True as torch
+        tensors on this context's device that wrap the results in HBM without a copy (int32 [n, 8], int64 [n + 1], int32 [total, 6]; valid until
+        the next unit parse on this context)."""
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+        ln = np.ascontiguousarray(seq_len, dtype=np.uint32)
+        sets, ts, tq = _pack_unit_sets(unit_sets, task_seq, task_set)
+        return self._unitparse_results(len(ts), device_tensor, lambda sums, seg_off, total: self._L.otg_unitparse_batch(
+            self._h, abi.ptr(arena), C.c_uint64(arena.size), abi.ptr(off), abi.ptr(ln), C.c_uint32(len(ln)), *sets, abi.ptr(ts), abi.ptr(tq), C.c_uint32(len(ts)),
+            sums, seg_off, total), "otg_unitparse_batch")
+
+    def _unitparse_results(self, n, device_tensor, call, who):
+        total = C.c_uint64(0)
+        if device_tensor:
+            self._check(call(None, None, C.byref(total)), who)
+            if n == 0:
+                import torch
+                dev = torch.device("cuda", self.device)
+                return (torch.zeros((0, 8), dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
+                        torch.zeros((0, 6), dtype=torch.int32, device=dev))
+            m, t, ps, po, pg = C.c_uint32(0), C.c_uint64(0), C.c_void_p(), C.c_void_p(), C.c_void_p()
+            self._check(self._L.otg_unitparse_device_results(self._h, C.byref(m), C.byref(ps), C.byref(po), C.byref(pg), C.byref(t)), "otg_unitparse_device_results")
+            assert (m.value, t.value) == (n, total.value)
+            return self._wrap_device(ps.value, (n, 8), "<i4"), self._wrap_device(po.value, (n + 1,), "<i8"), self._wrap_device(pg.value, (t.value, 6), "<i4")
+        sums = np.zeros(n, dtype=abi.unitparse_sum_dt)
+        seg_off = np.zeros(n + 1, dtype=np.uint64)
+        self._check(call(abi.ptr(sums), abi.ptr(seg_off), C.byref(total)), who)
+        segs = np.zeros(total.value, dtype=abi.unitparse_seg_dt)
+        if n and total.value:
+            self._check(self._L.otg_unitparse_collect(self._h, abi.ptr(segs), C.c_uint64(total.value)), "otg_unitparse_collect")
+        return sums, seg_off, segs
+
+    def unitparse_last_ms(self):
+        """(forward ms, traceback ms) of the latest unit parse on this context (HIP events)."""
+        a, b = C.c_double(0), C.c_double(0)
+        self._check(self._L.otg_unitparse_last_ms(self._h, C.byref(a), C.byref(b)), "otg_unitparse_last_ms")
+        return a.value, b.value
 
     def affine_align_batch(self, arena, tasks, x=4, o=6, e=2, want_cells=False):
         n = len(tasks)
@@ -774,6 +817,18 @@ class Context:
         rc = self._L.otg_unitalign_cohort(self._h, C.c_uint32(row_begin), C.c_uint32(n), *args, None if device_tensor else abi.ptr(out))
         self._check(rc, "otg_unitalign_cohort")
         return self._unitalign_device_results(nt) if device_tensor else out
+
+    def cohort_unitparse(self, unit_sets, task_seq, task_set, row_begin=0, n=None, device_tensor=False):
+        """otg_unitparse_cohort: rows [row_begin, row_begin + n) of the row list (n=None: to the end) parsed against unit sets, the alleles read
+        in the cohort arena in place -> (sums, seg_off, segs) as unitparse_batch returns them; task_seq counts from row_begin."""
+        if n is None:
+            total = C.c_uint32(0)
+            self._check(self._L.otg_kmer_cohort_rows(self._h, C.byref(total), None, None, None), "otg_kmer_cohort_rows")
+            n = max(0, total.value - int(row_begin))
+        n = int(n)
+        sets, ts, tq = _pack_unit_sets(unit_sets, task_seq, task_set)
+        return self._unitparse_results(len(ts), device_tensor, lambda sums, seg_off, total: self._L.otg_unitparse_cohort(
+            self._h, C.c_uint32(row_begin), C.c_uint32(n), *sets, abi.ptr(ts), abi.ptr(tq), C.c_uint32(len(ts)), sums, seg_off, total), "otg_unitparse_cohort")
 
     def cohort_end(self):
         self._check(self._L.otg_cohort_end(self._h), "otg_cohort_end")
@@ -1603,6 +1658,29 @@ def _pack_units(units):
     return np.frombuffer(b"".join(units) + b"\0", dtype=np.uint8).copy(), uoff, ulen
 
 
+def _pack_unit_sets(unit_sets, task_seq, task_set):
+    """a list of unit sets (lists of byte strings) and the task lists as the arguments of otg_unitparse_batch between the alleles and the tasks"""
+    unit_sets = [[bytes(u) for u in s] for s in unit_sets]
+    uarena, uoff, ulen = _pack_units([u for s in unit_sets for u in s])
+    first = np.concatenate(([0], np.cumsum([len(s) for s in unit_sets], dtype=np.uint64))).astype(np.uint64)
+    ts = np.ascontiguousarray(task_seq, dtype=np.uint32)
+    tq = np.ascontiguousarray(task_set, dtype=np.uint32)
+    if len(ts) != len(tq):
+        raise ValueError("task_seq and task_set differ in length")
+    keep = (uarena, uoff, ulen, first)
+    args = (abi.ptr(uarena), C.c_uint64(int(ulen.sum())), abi.ptr(uoff), abi.ptr(ulen), C.c_uint32(len(ulen)), abi.ptr(first), C.c_uint32(len(unit_sets)))
+    return _Kept(args, keep), ts, tq
+
+
+class _Kept(tuple):
+    """ctypes arguments that keep the arrays they point into alive"""
+
+    def __new__(cls, args, keep):
+        self = super().__new__(cls, args)
+        self.keep = keep
+        return self
+
+
 def parse_bed_units(path):
     """otg_parse_bed_units: the repeat units of a tandem-repeat catalogue -> one list of byte strings per BED record (the records of
     parse_bed_file, in its order); empty where column 4 is missing or a name."""
@@ -1648,6 +1726,44 @@ def unitalign_emit(records, regions, seq_len, task_first, task_source, units, al
     if rc != 0:
         raise OtterGpuError("otg_unitalign_emit failed (%d): %s" % (rc, _err(L)))
     return out.raw[:need.value]
+
+
+def unitparse_emit(records, regions, seq_len, allele_sets, unit_sets, sums, seg_off, segs):
+    """otg_unitparse_emit: the rows of otter_unitparse for the records (vcf_record_dt): allele a has the unit set unit_sets[allele_sets[a]] (None or
+    abi.UNITPARSE_NO_SET: none), the summary sums[a] and the segments segs[seg_off[a]:seg_off[a + 1]] -> text bytes."""
+    L = load()
+    records = np.ascontiguousarray(records, dtype=abi.vcf_record_dt)
+    seq_len = np.ascontiguousarray(seq_len, dtype=np.uint32)
+    aset = np.ascontiguousarray([abi.UNITPARSE_NO_SET if q is None else q for q in allele_sets] + [abi.UNITPARSE_NO_SET], dtype=np.uint32)
+    sets, _, _ = _pack_unit_sets(unit_sets, [], [])
+    sums = np.ascontiguousarray(sums, dtype=abi.unitparse_sum_dt)
+    seg_off = np.ascontiguousarray(seg_off, dtype=np.uint64)
+    segs = np.ascontiguousarray(segs, dtype=abi.unitparse_seg_dt)
+    if sums.size == 0:
+        sums = np.zeros(1, dtype=abi.unitparse_sum_dt)
+    if segs.size == 0:
+        segs = np.zeros(1, dtype=abi.unitparse_seg_dt)
+    reg = np.frombuffer(regions + b"\0", dtype=np.uint8)
+    need = C.c_uint64(0)
+    args = lambda out, cap: (abi.ptr(records), C.c_uint32(len(records)), abi.ptr(reg), abi.ptr(seq_len), abi.ptr(aset), sets[5], sets[0], sets[2], sets[3],
+                             abi.ptr(sums), abi.ptr(seg_off), abi.ptr(segs), out, C.c_uint64(cap), C.byref(need))
+    rc = L.otg_unitparse_emit(*args(None, 0))
+    if rc not in (0, abi.OTG_ERR_CAPACITY):
+        raise OtterGpuError("otg_unitparse_emit failed (%d): %s" % (rc, _err(L)))
+    out = C.create_string_buffer(need.value + 1)
+    rc = L.otg_unitparse_emit(*args(out, need.value))
+    if rc != 0:
+        raise OtterGpuError("otg_unitparse_emit failed (%d): %s" % (rc, _err(L)))
+    return out.raw[:need.value]
+
+
+def unitparse_files(vcf, bed, threads=1, device=0, batch_alleles=0):
+    """otg_unitparse_files: every allele of a VCF (plain, gzip or BGZF) parsed against the unit set its region has in a tandem-repeat catalogue,
+    as text.  Returns (text bytes, stats dict)."""
+    job = abi.UnitparseJob()
+    job.vcf_path = vcf.encode(); job.bed_path = bed.encode()
+    job.threads = threads; job.device = device; job.batch_alleles = batch_alleles
+    return _run_files_job("otg_unitparse_files", job, abi.UnitparseJob)
 
 
 def copies_files(vcf, bed, max_period=256, slack=50, threads=1, device=0, batch_alleles=0):

@@ -264,6 +264,25 @@ UNITALIGN_SOURCE_BED = 0
 UNITALIGN_SOURCE_MOTIF = 1
 
 
+# otg_unitparse_sum / otg_unitparse_seg (include/otter_gpu.h) and the bounds of the joint unit parse
+unitparse_sum_dt = np.dtype([("edits", np.uint32), ("switches", np.uint32), ("unit_bases", np.uint32), ("n_segments", np.uint32), ("end_unit", np.uint32),
+                             ("end_phase", np.uint32), ("flags", np.uint32), ("reserved", np.uint32)])
+unitparse_seg_dt = np.dtype([("unit", np.uint32), ("begin", np.uint32), ("end", np.uint32), ("unit_bases", np.uint32), ("edits", np.uint32),
+                             ("start_phase", np.uint32)])
+assert unitparse_sum_dt.itemsize == 32 and unitparse_seg_dt.itemsize == 24
+UNITPARSE_MAX_UNITS = 8
+UNITPARSE_MAX_LANES = 64
+UNITPARSE_MAX_LEN = (2097151 - 2 * UNITALIGN_MAX_UNIT + 1) // 2
+UNITPARSE_TOO_LONG = 1
+UNITPARSE_NO_SET = 0xffffffff
+
+
+class UnitparseJob(C.Structure):
+    """otg_unitparse_job (include/otter_gpu.h)."""
+    _fields_ = [("vcf_path", C.c_char_p), ("bed_path", C.c_char_p), ("threads", C.c_int32), ("device", C.c_int32), ("batch_alleles", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class CopiesJob(C.Structure):
     """otg_copies_job (include/otter_gpu.h)."""
     _fields_ = [("vcf_path", C.c_char_p), ("bed_path", C.c_char_p), ("max_period", C.c_uint32), ("slack", C.c_uint32), ("threads", C.c_int32),

@@ -559,6 +559,23 @@ int otg_unitalign_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, const uin
   return otg_unitalign_resident(ctx, "otg_unitalign_cohort", (const uint8_t*)c.arena.p, d_off, d_len, units, d_ts, d_tu, n_tasks, out);
 }
 
+int otg_unitparse_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off,
+                         const uint32_t* unit_len, uint32_t n_units, const uint64_t* set_first, uint32_t n_sets, const uint32_t* task_seq,
+                         const uint32_t* task_set, uint32_t n_tasks, otg_unitparse_sum* sums, uint64_t* seg_off, uint64_t* n_segments)
+{
+  Cohort* cp = cohort_of(ctx, "otg_unitparse_cohort");
+  if (!cp) return ctx ? OTG_ERR_ARG : OTG_ERR_NO_DEVICE;
+  Cohort& c = *cp;
+  if (!c.clustered) return otg_fail(ctx, OTG_ERR_ARG, "otg_unitparse_cohort: the batch has not been clustered (otg_cohort_genotype)");
+  if (int rc = cohort_build_rows(ctx, c, "otg_unitparse_cohort")) return rc;
+  if ((uint64_t)row_begin + n > c.n_rows) return otg_fail(ctx, OTG_ERR_ARG, "otg_unitparse_cohort: rows %u .. %llu of %u", row_begin, (unsigned long long)row_begin + n, c.n_rows);
+  if (int rc = otg_unitparse_check(ctx, "otg_unitparse_cohort", n, unit_arena, unit_bytes, unit_off, unit_len, n_units, set_first, n_sets, task_seq, task_set, n_tasks))
+    return rc;
+  return otg_unitparse_resident(ctx, "otg_unitparse_cohort", (const uint8_t*)c.arena.p, (const uint64_t*)c.row_off.p + row_begin, (const uint32_t*)c.row_len.p + row_begin,
+                                nullptr, n, unit_arena, unit_bytes, unit_off, unit_len, n_units, set_first, n_sets, task_seq, task_set, n_tasks, sums, seg_off,
+                                n_segments);
+}
+
 int otg_cohort_end(otg_ctx* ctx)
 {
   if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_cohort_end: no context");

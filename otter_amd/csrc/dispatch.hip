@@ -18,6 +18,8 @@
 #include "otg_motif.hpp"
 #include "otg_repeat.hpp"
 #include "otg_unitalign.hpp"
+#include "otg_unitparse.hpp"
+#include "otg_unitparse_core.hpp"
 #include <cmath>
 #include <algorithm>
 #include <atomic>
@@ -1251,6 +1253,93 @@ int otg_copies_files(const otg_copies_job* job, otg_write_fn write, void* user, 
     [&](std::string& o, const VcfBatch& B, uint32_t r0, uint32_t nr) {
       otg_unitalign_rows(o, B.rec.data() + r0, nr, B.regions.data(), B.len.data(), task_first.data(), source.data(), units.data(), unit_off.data(), unit_len.data(),
                          aligned.data());
+    });
+}
+
+// The joint parse of a VCF's alleles against the unit sets of a tandem-repeat catalogue, on vcf_allele_job as otg_copies_files: one task per
+// allele of a catalogue region with units (otg_unitparse_batch, only the sets the batch uses are uploaded); the others get the row without units.
+int otg_unitparse_files(const otg_unitparse_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
+{
+  if (!job || !write || !job->vcf_path || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "otg_unitparse_files: NULL job, writer, VCF or BED path");
+  Bed bed;
+  if (int rc = load_bed(job->bed_path, bed)) return rc;
+  std::vector<uint64_t> cat_first, cat_off;
+  std::vector<uint32_t> cat_len;
+  std::vector<uint8_t> cat_arena;
+  {
+    uint64_t nr = 0, nu = 0, ab = 0;
+    int rc = otg_parse_bed_units(job->bed_path, nullptr, 0, &nr, nullptr, nullptr, 0, &nu, nullptr, 0, &ab);
+    if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) return rc;
+    cat_first.resize(nr + 1); cat_off.resize(nu + 1); cat_len.resize(nu + 1); cat_arena.resize(ab + 1);
+    rc = otg_parse_bed_units(job->bed_path, cat_first.data(), cat_first.size(), &nr, cat_off.data(), cat_len.data(), nu, &nu, cat_arena.data(), ab, &ab);
+    if (rc != OTG_OK) return rc;
+    if (nr != bed.beds.size()) return otg_fail(nullptr, OTG_ERR_FATAL, "otg_unitparse_files: the two BED readers disagree on %s", job->bed_path);
+  }
+  std::map<std::string, uint32_t> by_region;
+  {
+    std::string name;
+    for (uint32_t r = 0; r < bed.beds.size(); ++r) {
+      name.clear();
+      otg_region_name(name, bed.chr_arena.data() + bed.beds[r].chr_off, bed.beds[r].chr_len, bed.beds[r].start, bed.beds[r].end);
+      by_region.emplace(name, r);
+    }
+  }
+  // per batch: one set per record with units, one task per allele of such a record; the results per allele, in file order
+  std::vector<uint64_t> set_first, uoff, seg_off, t_seg_off;
+  std::vector<uint32_t> ulen, allele_set, tseq, tset;
+  std::vector<uint8_t> units;
+  std::vector<otg_unitparse_sum> sums, t_sums;
+  std::vector<otg_unitparse_seg> segs;
+  return vcf_allele_job("otg_unitparse_files", job->vcf_path, job->bed_path, job->device, job->batch_alleles ? job->batch_alleles : 65536, job->threads, write, user, stats,
+    [&](otg_ctx* ctx, const VcfBatch& B) {
+      set_first.assign(1, 0); uoff.clear(); ulen.clear(); units.clear(); tseq.clear(); tset.clear();
+      allele_set.assign(B.na, OTG_UNITPARSE_NO_SET);
+      std::string name;
+      for (uint32_t r = 0; r < B.nr; ++r) {
+        const otg_vcf_record& R = B.rec[r];
+        name.assign(B.regions.data() + R.region_off, R.region_len);
+        const auto it = by_region.find(name);
+        if (it == by_region.end() || cat_first[it->second + 1] == cat_first[it->second]) continue;
+        const uint64_t u0 = cat_first[it->second], u1 = cat_first[it->second + 1];
+        if (u1 - u0 > OTG_UNITPARSE_MAX_UNITS)
+          return otg_fail(ctx, OTG_ERR_ARG, "%s has %llu units in the catalogue, at most %d", name.c_str(), (unsigned long long)(u1 - u0),
+                          OTG_UNITPARSE_MAX_UNITS);
+        if (otg_unitparse_core::up_class(cat_len.data() + u0, (uint32_t)(u1 - u0)) == otg_unitparse_core::UP_NO_CLASS)
+          return otg_fail(ctx, OTG_ERR_ARG, "the units of %s do not fit one wave (%u lanes at four positions each, at most %d)", name.c_str(),
+                          otg_unitparse_core::up_lanes(cat_len.data() + u0, (uint32_t)(u1 - u0), 4u), OTG_UNITPARSE_MAX_LANES);
+        const uint32_t q = (uint32_t)set_first.size() - 1u;
+        for (uint64_t k = u0; k < u1; ++k) {
+          uoff.push_back(units.size()); ulen.push_back(cat_len[k]);
+          units.insert(units.end(), cat_arena.begin() + cat_off[k], cat_arena.begin() + cat_off[k] + cat_len[k]);
+        }
+        set_first.push_back(ulen.size());
+        for (uint32_t i = 0; i < R.n_alleles; ++i) { allele_set[R.first_allele + i] = q; tseq.push_back(R.first_allele + i); tset.push_back(q); }
+      }
+      units.push_back(0); uoff.push_back(0); ulen.push_back(0);      // (never empty: the emit takes their addresses)
+      const uint32_t nt = (uint32_t)tseq.size();
+      t_sums.resize(nt); t_seg_off.assign((size_t)nt + 1, 0);
+      uint64_t total = 0;
+      if (nt) {
+        if (int rc = otg_unitparse_batch(ctx, B.seqs.data(), B.au, B.off.data(), B.len.data(), B.na, units.data(), units.size() - 1, uoff.data(), ulen.data(),
+                                         (uint32_t)ulen.size() - 1u, set_first.data(), (uint32_t)set_first.size() - 1u, tseq.data(), tset.data(), nt, t_sums.data(),
+                                         t_seg_off.data(), &total)) return rc;
+      }
+      segs.resize(total + 1);
+      if (total)
+        if (int rc = otg_unitparse_collect(ctx, segs.data(), total)) return rc;
+      // the tasks are the alleles with units, in allele order: their segments lie in that order too
+      sums.assign(B.na, otg_unitparse_sum{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}); seg_off.assign((size_t)B.na + 1, 0);
+      uint32_t cur = 0;
+      for (uint32_t a = 0; a < B.na; ++a) {
+        seg_off[a] = t_seg_off[cur];
+        if (cur < nt && tseq[cur] == a) sums[a] = t_sums[cur++];
+      }
+      seg_off[B.na] = total;
+      return (int)OTG_OK;
+    },
+    [&](std::string& o, const VcfBatch& B, uint32_t r0, uint32_t nr) {
+      otg_unitparse_rows(o, B.rec.data() + r0, nr, B.regions.data(), B.len.data(), allele_set.data(), set_first.data(), units.data(), uoff.data(), ulen.data(),
+                         sums.data(), seg_off.data(), segs.data());
     });
 }
 

@@ -56,6 +56,10 @@ struct otg_ctx {
   const uint32_t* last_motif_len = nullptr;
   double last_unitalign_ms = 0.0;                                 // HIP-event time of the latest unit alignment (otg_unitalign_last_ms)
   uint32_t last_unitalign_n = 0;                                  // the records in SLOT_UNITALIGN_OUT (otg_unitalign_device_results); 0: none
+  double last_unitparse_forward_ms = 0.0, last_unitparse_trace_ms = 0.0;   // HIP-event times of the latest unit parse (otg_unitparse_last_ms)
+  uint32_t last_unitparse_n = 0;                                  // the shape of the results in SLOT_UNITPARSE_RES / SLOT_UNITPARSE_SEGS (otg_unitparse_device_results);
+  uint64_t last_unitparse_total = 0;                              // valid: a unit parse with n > 0 has succeeded since the last one began
+  bool last_unitparse_valid = false;
   double last_kernel_ms = 0.0;                    // HIP-event time of the kernels of the latest operator-level call that reports one (otg_last_kernel_ms)
   // the latest genotype clustering with a metric (genotype_edit.hip): times of its two parts (otg_genotype_metric_last_ms), whether the edit
   // matrix was built, and where its counters lie in SLOT_GTE_CLS
@@ -113,6 +117,8 @@ enum {
   SLOT_REPEAT_RES, SLOT_REPEAT_SEGS,                                // its summaries and offsets / its segments: they stay valid for the device results
   SLOT_UNITALIGN_SEQ, SLOT_UNITALIGN_META, SLOT_UNITALIGN_UNITS, SLOT_UNITALIGN_BINS, SLOT_UNITALIGN_ORDER,   // otg_unitalign_batch (unitalign.hip)
   SLOT_UNITALIGN_OUT,                                               // its records: they stay valid for the device results
+  SLOT_UNITPARSE_SEQ, SLOT_UNITPARSE_META, SLOT_UNITPARSE_UNITS, SLOT_UNITPARSE_PLAN, SLOT_UNITPARSE_TRACE,   // otg_unitparse_batch (unitparse.hip)
+  SLOT_UNITPARSE_RES, SLOT_UNITPARSE_SEGS,                          // its summaries and offsets / its segments: they stay valid for the device results
   SLOT_COUNT
 };
 
@@ -387,6 +393,16 @@ int otg_unitalign_check(otg_ctx* ctx, const char* who, uint32_t n_seqs, const ui
 int otg_unitalign_upload(otg_ctx* ctx, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off, const uint32_t* unit_len, uint32_t n_units,
                          const uint32_t* task_seq, const uint32_t* task_unit, uint32_t n_tasks, OtgUnitSource* units, const uint32_t** d_task_seq,
                          const uint32_t** d_task_unit);
+// unitparse.hip: the refusals of a caller's unit sets and task lists (host arrays), and the launch part of the joint unit parse on
+// device-resident alleles (the arena extends 15 bytes past every row).  The units, sets and task lists are host arrays and are uploaded here;
+// h_len = the allele lengths on the host, NULL: they are read back from d_len.
+int otg_unitparse_check(otg_ctx* ctx, const char* who, uint32_t n_seqs, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off,
+                        const uint32_t* unit_len, uint32_t n_units, const uint64_t* set_first, uint32_t n_sets, const uint32_t* task_seq,
+                        const uint32_t* task_set, uint32_t n_tasks);
+int otg_unitparse_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, const uint32_t* h_len,
+                           uint32_t n_seqs, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off, const uint32_t* unit_len,
+                           uint32_t n_units, const uint64_t* set_first, uint32_t n_sets, const uint32_t* task_seq, const uint32_t* task_set, uint32_t n_tasks,
+                           otg_unitparse_sum* sums, uint64_t* seg_off, uint64_t* n_segments);
 // repeat.hip: the argument refusals of otg_repeat_batch and its launch part on device-resident rows (cohort.hip), as the motif pair above
 int otg_repeat_args(otg_ctx* ctx, const char* who, uint32_t max_period, uint32_t min_copies, uint32_t min_span);
 int otg_repeat_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, uint32_t n,

@@ -1,0 +1,10 @@
+// otg_unitparse.hpp — the row text of `otter_unitparse`, shared by unitparse_emit.hip and the dispatcher.
+#pragma once
+#include <cstdint>
+#include <string>
+#include "../../include/otter_gpu.h"
+
+// appends the rows of records[0 .. n_records) to o (the text of otg_unitparse_emit)
+void otg_unitparse_rows(std::string& o, const otg_vcf_record* records, uint32_t n_records, const char* region_arena, const uint32_t* seq_len,
+                        const uint32_t* allele_set, const uint64_t* set_first, const uint8_t* unit_arena, const uint64_t* unit_off, const uint32_t* unit_len,
+                        const otg_unitparse_sum* sums, const uint64_t* seg_off, const otg_unitparse_seg* segs);

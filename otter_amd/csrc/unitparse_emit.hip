@@ -1,0 +1,87 @@
+// unitparse_emit.hip — the host side of the joint unit parse: the row text (otg_unitparse_emit).  No device work; the kernels are unitparse.hip.
+#include "otg_common.hpp"
+#include "otg_unitparse.hpp"
+#include <algorithm>
+#include <string>
+
+void otg_unitparse_rows(std::string& o, const otg_vcf_record* records, uint32_t n_records, const char* region_arena, const uint32_t* seq_len,
+                        const uint32_t* allele_set, const uint64_t* set_first, const uint8_t* unit_arena, const uint64_t* unit_off, const uint32_t* unit_len,
+                        const otg_unitparse_sum* sums, const uint64_t* seg_off, const otg_unitparse_seg* segs)
+{
+  char b[128];
+  uint64_t per_unit[OTG_UNITPARSE_MAX_UNITS];
+  for (uint32_t r = 0; r < n_records; ++r) {
+    const otg_vcf_record& R = records[r];
+    for (uint32_t i = 0; i < R.n_alleles; ++i) {
+      const uint64_t a = (uint64_t)R.first_allele + i;
+      const uint32_t q = allele_set[a];
+      const uint64_t u0 = q == OTG_UNITPARSE_NO_SET ? 0 : set_first[q], K = q == OTG_UNITPARSE_NO_SET ? 0 : set_first[q + 1] - u0;
+      const uint32_t L = seq_len[a];
+      o.append(region_arena + R.region_off, R.region_len);
+      o.append(b, (size_t)snprintf(b, sizeof b, "\t%u\t%u\t", i, L));
+      if (K == 0) {
+        o += ".\t0\t0\t0\t0.0000\t.\t.\n";
+        continue;
+      }
+      const otg_unitparse_sum& A = sums[a];
+      for (uint64_t k = 0; k < K; ++k) {
+        if (k) o += ',';
+        o.append((const char*)unit_arena + unit_off[u0 + k], unit_len[u0 + k]);
+        per_unit[k] = 0;
+      }
+      const uint32_t span = std::max(L, A.unit_bases);
+      const double identity = A.flags == 0u && span ? 1.0 - (double)A.edits / (double)span : 0.0;
+      o.append(b, (size_t)snprintf(b, sizeof b, "\t%u\t%u\t%u\t%.4f\t", A.edits, A.switches, A.unit_bases, identity));
+      for (uint64_t g = seg_off[a]; g < seg_off[a + 1]; ++g) per_unit[segs[g].unit] += segs[g].unit_bases;
+      for (uint64_t k = 0; k < K; ++k)
+        o.append(b, (size_t)snprintf(b, sizeof b, "%s%.2f", k ? "," : "", (double)per_unit[k] / (double)unit_len[u0 + k]));
+      o += '\t';
+      if (seg_off[a + 1] == seg_off[a]) o += '.';
+      for (uint64_t g = seg_off[a]; g < seg_off[a + 1]; ++g) {
+        const otg_unitparse_seg& G = segs[g];
+        const uint32_t p = unit_len[u0 + G.unit];
+        o += '(';
+        o.append((const char*)unit_arena + unit_off[u0 + G.unit], p);
+        o += ')';
+        if (G.unit_bases % p == 0u) o.append(b, (size_t)snprintf(b, sizeof b, "%u", G.unit_bases / p));
+        else o.append(b, (size_t)snprintf(b, sizeof b, "%.2f", (double)G.unit_bases / (double)p));
+        if (G.edits) o.append(b, (size_t)snprintf(b, sizeof b, "~%u", G.edits));
+      }
+      o += '\n';
+    }
+  }
+}
+
+extern "C" int otg_unitparse_emit(const otg_vcf_record* records, uint32_t n_records, const char* region_arena, const uint32_t* seq_len,
+                                  const uint32_t* allele_set, const uint64_t* set_first, const uint8_t* unit_arena, const uint64_t* unit_off, const uint32_t* unit_len,
+                                  const otg_unitparse_sum* sums, const uint64_t* seg_off, const otg_unitparse_seg* segs, char* out, uint64_t out_capacity,
+                                  uint64_t* out_len)
+{
+  if (!out_len) return otg_fail(nullptr, OTG_ERR_ARG, "otg_unitparse_emit: NULL out_len");
+  if (n_records && (!records || !region_arena || !seq_len || !allele_set)) return otg_fail(nullptr, OTG_ERR_ARG, "otg_unitparse_emit: NULL argument");
+  for (uint32_t r = 0; r < n_records; ++r)
+    for (uint32_t i = 0; i < records[r].n_alleles; ++i) {
+      const uint64_t a = (uint64_t)records[r].first_allele + i;
+      const uint32_t q = allele_set[a];
+      if (q == OTG_UNITPARSE_NO_SET) continue;
+      if (!set_first) return otg_fail(nullptr, OTG_ERR_ARG, "otg_unitparse_emit: NULL argument");
+      if (set_first[q + 1] <= set_first[q]) return otg_fail(nullptr, OTG_ERR_ARG, "otg_unitparse_emit: set %u of allele %u of record %u is empty", q, i, r);
+      const uint64_t K = set_first[q + 1] - set_first[q];
+      if (K > OTG_UNITPARSE_MAX_UNITS) return otg_fail(nullptr, OTG_ERR_ARG, "otg_unitparse_emit: allele %u of record %u has %llu units, at most %d", i, r,
+                                                       (unsigned long long)K, OTG_UNITPARSE_MAX_UNITS);
+      if (!unit_arena || !unit_off || !unit_len || !sums || !seg_off) return otg_fail(nullptr, OTG_ERR_ARG, "otg_unitparse_emit: NULL argument");
+      for (uint64_t k = set_first[q]; k < set_first[q + 1]; ++k)
+        if (unit_len[k] == 0u) return otg_fail(nullptr, OTG_ERR_ARG, "otg_unitparse_emit: allele %u of record %u has an empty unit", i, r);
+      if (seg_off[a + 1] < seg_off[a]) return otg_fail(nullptr, OTG_ERR_ARG, "otg_unitparse_emit: seg_off decreases at allele %u of record %u", i, r);
+      if (seg_off[a + 1] > seg_off[a] && !segs) return otg_fail(nullptr, OTG_ERR_ARG, "otg_unitparse_emit: NULL argument");
+      for (uint64_t g = seg_off[a]; g < seg_off[a + 1]; ++g)
+        if (segs[g].unit >= K) return otg_fail(nullptr, OTG_ERR_ARG, "otg_unitparse_emit: segment %llu of allele %u of record %u names unit %u of %llu",
+                                               (unsigned long long)(g - seg_off[a]), i, r, segs[g].unit, (unsigned long long)K);
+    }
+  std::string text;
+  otg_unitparse_rows(text, records, n_records, region_arena, seq_len, allele_set, set_first, unit_arena, unit_off, unit_len, sums, seg_off, segs);
+  *out_len = text.size();
+  if (text.size() > out_capacity || (!out && !text.empty())) return otg_fail(nullptr, OTG_ERR_CAPACITY, "otg_unitparse_emit: output buffer too small");
+  if (!text.empty()) memcpy(out, text.data(), text.size());
+  return OTG_OK;
+}
