@@ -344,6 +344,9 @@ int otg_launch_poa(otg_ctx* ctx, const uint8_t* d_seq_arena, const uint8_t* d_ci
                    const otg_poa_member* d_members, uint32_t n_members, const otg_poa_graph* d_graphs,
                    const otg_poa_graph* h_graphs, uint32_t n_graphs, uint32_t* d_out_len,
                    std::vector<uint64_t>& node_off);
+// the same for graphs and members that are on the device only: planned on the device, no host copy of the graphs (see the definition)
+int otg_launch_poa_resident(otg_ctx* ctx, const uint8_t* d_seq_arena, const uint8_t* d_cig_arena,
+                            const otg_poa_member* d_members, uint32_t n_members, const otg_poa_graph* d_graphs, uint32_t n_graphs, uint32_t* d_out_len);
 
 // otg_api.hip: anallele_cluster on device-resident inputs (memset of the outputs, ev0, the kernels below, ev1); see its definition
 int otg_genotype_resident(otg_ctx* ctx, const otg_params* params, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len,

@@ -14,6 +14,7 @@
 // handful of scalars (POA layout totals, output sizes).
 #include "otg_chain.hpp"
 #include "myers_masks.hpp"
+#include "otg_scan.hpp"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -57,10 +58,14 @@ enum {
   B_CLLAB, B_IC, B_FC, B_BOUNDS, B_CLERR, B_LABELS,
   B_REDIST, B_RTASKS, B_RKIND, B_CIGLEN, B_CIG,
   B_ALLELES, B_GRAPHS, B_MEMBERS, B_POALEN,
-  B_ALLEN, B_ALOFF, B_ALIDX, B_OUTSEQ, B_OUTAL, B_REGRES, B_STATS, B_SCAN_TMP, B_TOTALS,
+  B_ALLEN, B_ALOFF, B_ALIDX, B_OUTSEQ, B_OUTAL, B_REGRES, B_SCAN_TMP, B_TOTALS,
   B_MASKS, B_MASK_FIRST, B_MASK_READ, B_MASK_TASK,
   B_COUNT
 };
+
+// The counter block B_CNT (128 words): todo-list lengths at words 16 / 20 / 24 / 28, and in one contiguous range, read back in one copy at the
+// end of a run, the failure flags (words 40-42) and the eight 64-bit statistics words
+constexpr uint32_t RUN_FLAGS_WORD = 40, RUN_STATS_WORD = 44;
 
 static void* pbuf(otg_ctx* ctx, Pipeline* pl, int i, size_t bytes)
 {
@@ -245,7 +250,19 @@ __global__ void K_region_prepare(const otg_read* __restrict__ reads, const otg_r
   status[r] = st; n_valid[r] = (st == OTG_REGION_OK) ? nv : 0; ign[r] = lig;
 }
 
-// ---- fill_dist_matrix (src/analignments.cpp:103-124): one block per region
+// Appends the slots of the lanes that have a task to the todo list with ONE atomic per wave: the leader reserves a run, a lane's place in it
+// is its rank among the lanes with a task.  Call from wave-uniform control flow.  (The list's order is free: the edit chain routes and sorts
+// it, scores land in their slots.)
+__device__ __forceinline__ void todo_append(uint32_t* __restrict__ todo, uint32_t* __restrict__ n_todo, bool has, uint32_t slot)
+{
+  const unsigned long long m = __ballot(has);
+  if (!m) return;
+  const uint32_t at = otg_wave_atomic_add(n_todo, (uint32_t)__popcll(m));
+  if (has) todo[at + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = slot;
+}
+
+// ---- fill_dist_matrix (src/analignments.cpp:103-124): one wave per region, a lane per pair: slot base + q holds pair q of the row-major
+// upper triangle, so the 64 lanes of a trip take 64 consecutive slots whatever the row length
 __global__ void K_pair_tasks(const uint8_t* __restrict__ arena, const otg_read* __restrict__ reads,
                              const otg_region* __restrict__ regions, uint32_t n_regions, const uint32_t* __restrict__ n_valid,
                              const int32_t* __restrict__ ign, const uint32_t* __restrict__ valid,
@@ -261,26 +278,37 @@ __global__ void K_pair_tasks(const uint8_t* __restrict__ arena, const otg_read* 
     const uint64_t base = dist_off[r];
     const size_t np = (size_t)n * (n - 1) / 2;
     if (max_alleles == 1) { for (size_t q = threadIdx.x; q < np; q += blockDim.x) dist[base + q] = 1.0; continue; }   // DistMatrix default (src/andistmat.cpp:10)
-    for (int i = 0; i < n - 1; ++i) {
-      const uint32_t xi = valid[f + i];
-      const otg_read x = reads[xi];
-      for (int j = i + 1 + (int)threadIdx.x; j < n; j += (int)blockDim.x) {
-        const uint32_t yi = valid[f + j];
+    const bool haps = !ign[r];
+    for (size_t q0 = 0; q0 < np; q0 += blockDim.x) {                                    // wave-uniform trips (blockDim.x = 64)
+      const size_t q = q0 + threadIdx.x;
+      const bool in = q < np;
+      const uint64_t slot = base + q;
+      bool has = false;
+      if (in) {
+        // row i of pair q: the largest i whose row begins at or before q (row i begins at (2n - 1 - i) i / 2)
+        int i = (int)(((double)(2 * n - 1) - sqrt((double)(2 * n - 1) * (double)(2 * n - 1) - 8.0 * (double)q)) * 0.5);
+        if (i < 0) i = 0;
+        if (i > n - 2) i = n - 2;
+        while (i > 0 && didx(n, i, i + 1) > q) --i;
+        while (i < n - 2 && didx(n, i + 1, i + 2) <= q) ++i;
+        const int j = i + 1 + (int)(q - didx(n, i, i + 1));
+        const uint32_t xi = valid[f + i], yi = valid[f + j];
+        const otg_read x = reads[xi];
         const otg_read y = reads[yi];
-        const uint64_t slot = base + didx(n, i, j);
-        if (!ign[r]) {
+        if (haps) {
           const bool bx = x.ps >= 0 && x.hp >= 0, by = y.ps >= 0 && y.hp >= 0;
           dist[slot] = (bx && by && x.ps == y.ps && x.hp == y.hp) ? 0.0 : 1.0;      // get_dist_anreads :108-113
         } else {
           double known = 0;
           uint32_t d = 1;
           if (anreads_task(arena, x, y, tasks[slot], &d, &known)) {
-            den[slot] = d; todo[atomicAdd(n_todo, 1u)] = (uint32_t)slot;
+            den[slot] = d; has = true;
             if (task_blk) task_blk[slot] = task_mask_block(read_blk, tasks[slot], x, xi, y, yi);
           }
           else dist[slot] = known;
         }
       }
+      todo_append(todo, n_todo, has, (uint32_t)slot);
     }
   }
 }
@@ -376,20 +404,24 @@ __global__ void K_reassign_tasks(const uint8_t* __restrict__ arena, const otg_re
     for (int i = 0; i < n; ++i) {
       if (labels[f + i] >= 0) continue;
       const otg_read x = reads[f + i];
-      for (int j = (int)threadIdx.x; j < n; j += (int)blockDim.x) {
-        if (j == i) continue;
-        const otg_read y = reads[f + j];
-        if (!(y.spanning_l && y.spanning_r)) continue;
-        // targets are reads that are labelled now OR may become labelled earlier in this pass (unlabelled spanning reads, --haps)
-        if (labels[f + j] < 0 && j > i) continue;
-        const uint64_t slot = re_off[r] + (uint64_t)i * n + j;
-        double known = 0;
-        uint32_t d = 1;
-        if (anreads_task(arena, x, y, tasks[slot], &d, &known, rev_base)) {
-          den[slot] = d; todo[atomicAdd(n_todo, 1u)] = (uint32_t)slot;
-          if (task_blk) task_blk[slot] = task_mask_block(read_blk, tasks[slot], x, f + (uint32_t)i, y, f + (uint32_t)j);
+      for (int j0 = 0; j0 < n; j0 += (int)blockDim.x) {                                 // wave-uniform trips (blockDim.x = 64)
+        const int j = j0 + (int)threadIdx.x;
+        const uint64_t slot = re_off[r] + (uint64_t)i * n + (uint64_t)j;
+        bool has = false;
+        if (j < n && j != i) {
+          const otg_read y = reads[f + j];
+          // targets are spanning reads that are labelled now OR may become labelled earlier in this pass (unlabelled spanning reads, --haps)
+          if (y.spanning_l && y.spanning_r && !(labels[f + j] < 0 && j > i)) {
+            double known = 0;
+            uint32_t d = 1;
+            if (anreads_task(arena, x, y, tasks[slot], &d, &known, rev_base)) {
+              den[slot] = d; has = true;
+              if (task_blk) task_blk[slot] = task_mask_block(read_blk, tasks[slot], x, f + (uint32_t)i, y, f + (uint32_t)j);
+            }
+            else dist[slot] = known;
+          }
         }
-        else dist[slot] = known;
+        todo_append(todo, n_todo, has, (uint32_t)slot);
       }
     }
   }
@@ -584,23 +616,6 @@ __global__ void K_allele_len(const AlleleSlot* __restrict__ alleles, const int32
   al_len[i] = len; al_flag[i] = flag;
 }
 
-// single-block exclusive scan (u32 -> u64), total to *total
-__global__ __launch_bounds__(1024) void K_scan(const uint32_t* __restrict__ in, uint64_t* __restrict__ out, uint32_t n, uint64_t* __restrict__ total)
-{
-  __shared__ uint64_t part[1024];
-  const uint32_t t = threadIdx.x;
-  const uint32_t chunk = (n + 1023) / 1024;
-  const uint32_t a = t * chunk, b = a + chunk < n ? a + chunk : n;
-  uint64_t s = 0;
-  for (uint32_t i = a; i < b; ++i) s += in[i];
-  part[t] = s;
-  __syncthreads();
-  if (t == 0) { uint64_t acc = 0; for (int i = 0; i < 1024; ++i) { const uint64_t v = part[i]; part[i] = acc; acc += v; } *total = acc; }
-  __syncthreads();
-  uint64_t acc = part[t];
-  for (uint32_t i = a; i < b; ++i) { out[i] = acc; acc += in[i]; }
-}
-
 __global__ void K_gather(const uint8_t* __restrict__ arena, const AlleleSlot* __restrict__ alleles, const uint32_t* __restrict__ al_len,
                          const uint32_t* __restrict__ al_flag, const uint64_t* __restrict__ al_off, const uint64_t* __restrict__ al_idx,
                          const uint32_t* __restrict__ read_region, const otg_region* __restrict__ regions, const int32_t* __restrict__ ic,
@@ -756,7 +771,7 @@ int otg_assemble_submit(otg_ctx* ctx, const otg_params* params, const uint8_t* s
   const size_t ntask = std::max<size_t>(std::max<size_t>(pl->n_pair_slots, pl->n_re_slots), n_reads) + 1;
   if (!pbuf(ctx, pl, B_TASKS, ntask * sizeof(otg_align_task)) || !pbuf(ctx, pl, B_TODO, ntask * 4) || !pbuf(ctx, pl, B_SCORES, ntask * 4) ||
       !pbuf(ctx, pl, B_DEN, ntask * 4) || !pbuf(ctx, pl, B_CELLS, ntask * 8) || !pbuf(ctx, pl, B_DIST, (pl->n_pair_slots + 1) * 8) ||
-      !pbuf(ctx, pl, B_REDIST, (pl->n_re_slots + 1) * 8) || !pbuf(ctx, pl, B_CNT, 64 * 8) || !pbuf(ctx, pl, B_STATS, 64 * 8) ||
+      !pbuf(ctx, pl, B_REDIST, (pl->n_re_slots + 1) * 8) || !pbuf(ctx, pl, B_CNT, 64 * 8) ||
       !pbuf(ctx, pl, B_STATUS, (size_t)n_regions * 4 + 4) || !pbuf(ctx, pl, B_NVALID, (size_t)n_regions * 4 + 4) ||
       !pbuf(ctx, pl, B_IGNHAPS, (size_t)n_regions * 4 + 4) || !pbuf(ctx, pl, B_VALID, (size_t)n_reads * 4 + 4) ||
       !pbuf(ctx, pl, B_VPOS, (size_t)n_reads * 4 + 4) || !pbuf(ctx, pl, B_VLEN, (size_t)n_reads * 4 + 4) ||
@@ -849,7 +864,7 @@ static int assemble_run_body(otg_ctx* ctx, bool realign_only)
   double* d_dist = (double*)B(B_DIST);
   double* d_redist = (double*)B(B_REDIST);
   uint32_t* d_cnt = (uint32_t*)B(B_CNT);
-  unsigned long long* d_stats = (unsigned long long*)B(B_STATS);
+  unsigned long long* d_stats = (unsigned long long*)(d_cnt + RUN_STATS_WORD);
   int32_t* d_status = (int32_t*)B(B_STATUS);
   uint32_t* d_nvalid = (uint32_t*)B(B_NVALID);
   int32_t* d_ign = (int32_t*)B(B_IGNHAPS);
@@ -872,8 +887,7 @@ static int assemble_run_body(otg_ctx* ctx, bool realign_only)
   Timer total(ctx);
   // the resident read descriptors are restored from the submitted ones (realignment mutates them)
   HIP_TRY(ctx, hipMemcpyAsync(d_reads, pl->h_reads.data(), (size_t)NR * sizeof(otg_read), hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, 64 * 8, st));
-  HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, 64 * 8, st));
+  HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, 64 * 8, st));       // the statistics words with it
   if (unsigned long long* visited = otg_affine_visited(ctx)) HIP_TRY(ctx, hipMemsetAsync(visited, 0, 8, st));
   const int TB = 256;
   const uint32_t gr_reads = (NR + TB - 1) / TB, gr_regions = (NG + TB - 1) / TB;
@@ -955,7 +969,6 @@ static int assemble_run_body(otg_ctx* ctx, bool realign_only)
   }
   dbg(ctx, "reassign done");
   // ------------------------------------------------------------------ rapid_consensus
-  std::vector<uint64_t> node_off;
   {
     Timer t(ctx);
     HIP_TRY(ctx, hipMemsetAsync(d_cig_len, 0, (size_t)NR * 4, st));
@@ -975,11 +988,7 @@ static int assemble_run_body(otg_ctx* ctx, bool realign_only)
     pl->stats.ms_affine = t.ms();
     dbg(ctx, "affine done");
     Timer t2(ctx);
-    std::vector<otg_poa_graph> h_graphs(NR);
-    HIP_TRY(ctx, hipMemcpyAsync(h_graphs.data(), B(B_GRAPHS), (size_t)NR * sizeof(otg_poa_graph), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    rc = otg_launch_poa(ctx, d_arena, d_cig, (const otg_poa_member*)B(B_MEMBERS), NR, (const otg_poa_graph*)B(B_GRAPHS), h_graphs.data(), NR,
-                        (uint32_t*)B(B_POALEN), node_off);
+    rc = otg_launch_poa_resident(ctx, d_arena, d_cig, (const otg_poa_member*)B(B_MEMBERS), NR, (const otg_poa_graph*)B(B_GRAPHS), NR, (uint32_t*)B(B_POALEN));
     if (rc) return rc;
     pl->stats.ms_poa = t2.ms();
   }
@@ -993,8 +1002,12 @@ static int assemble_run_body(otg_ctx* ctx, bool realign_only)
     uint64_t* d_tot = (uint64_t*)B(B_TOTALS);
     hipLaunchKernelGGL(K_allele_len, dim3(gr_reads), dim3(TB), 0, st, (const AlleleSlot*)B(B_ALLELES), d_status, d_rr, (const uint32_t*)B(B_POALEN),
                        (const int32_t*)ctx->pool[SLOT_P28].p, NR, d_allen, d_alflag, d_status);
-    hipLaunchKernelGGL(K_scan, dim3(1), dim3(1024), 0, st, d_allen, d_aloff, NR, d_tot + 0);
-    hipLaunchKernelGGL(K_scan, dim3(1), dim3(1024), 0, st, d_alflag, d_alidx, NR, d_tot + 1);
+    {
+      OtgScanJobs sj;
+      sj.j[0].in = d_allen; sj.j[0].out = d_aloff; sj.j[0].n = NR; sj.j[0].total = d_tot + 0;
+      sj.j[1].in = d_alflag; sj.j[1].out = d_alidx; sj.j[1].n = NR; sj.j[1].total = d_tot + 1;
+      hipLaunchKernelGGL(otg_scan_jobs_kernel<8>, dim3(2), dim3(1024), 0, st, sj);
+    }
     uint64_t h_tot[2];
     HIP_TRY(ctx, hipMemcpyAsync(h_tot, d_tot, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -1011,27 +1024,33 @@ static int assemble_run_body(otg_ctx* ctx, bool realign_only)
   }
   dbg(ctx, "gather done");
   HIP_TRY(ctx, hipGetLastError());
+  // What the host reads of a finished run comes back behind the last kernel and is waited for once: the failure flags and the statistics
+  // words share the counter block (one copy), the visited-cell counter lies with the aligner chain's counters, the region results follow.
+  struct { uint32_t flags[RUN_STATS_WORD - RUN_FLAGS_WORD]; unsigned long long stats[8]; } tail;
+  static_assert(sizeof(tail) == (RUN_STATS_WORD - RUN_FLAGS_WORD) * 4 + 64, "the flags and the statistics words are one contiguous range");
+  unsigned long long h_visited = 0;
+  const unsigned long long* d_visited = otg_affine_visited(ctx);
+  std::vector<otg_region_result> rr(NG);
+  HIP_TRY(ctx, hipMemcpyAsync(&tail, d_cnt + RUN_FLAGS_WORD, sizeof(tail), hipMemcpyDeviceToHost, st));
+  if (d_visited) HIP_TRY(ctx, hipMemcpyAsync(&h_visited, d_visited, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(rr.data(), B(B_REGRES), (size_t)NG * sizeof(otg_region_result), hipMemcpyDeviceToHost, st));
   pl->stats.ms_total = total.ms();
   {
-    uint32_t hf[3];
-    HIP_TRY(ctx, hipMemcpy(hf, d_cnt + 40, sizeof(hf), hipMemcpyDeviceToHost));
+    const uint32_t* hf = tail.flags;
     if (hf[0]) return otg_fail(ctx, OTG_ERR_FATAL, "an edit-distance alignment did not complete on the device");
     // hf[1]: a consensus alignment outgrew the last-resort tier's workspace: its region carries OTG_REGION_ALIGN_CAPACITY, everything else is delivered
     if (hf[2]) return otg_fail(ctx, OTG_ERR_CAPACITY, "a flank re-alignment exhausted its backtrace storage on the device");
   }
   // statistics
-  unsigned long long hs[8];
-  HIP_TRY(ctx, hipMemcpy(hs, d_stats, sizeof(hs), hipMemcpyDeviceToHost));
+  const unsigned long long* hs = tail.stats;
   pl->stats.edit_cells = hs[0]; pl->stats.edit_seq_bytes = hs[1]; pl->stats.edit_tasks = hs[2];
   pl->stats.affine_cells = hs[4]; pl->stats.affine_seq_bytes = hs[5]; pl->stats.affine_tasks = hs[6];
   pl->stats.n_regions = NG;
-  if (const unsigned long long* visited = otg_affine_visited(ctx)) { unsigned long long v = 0; HIP_TRY(ctx, hipMemcpy(&v, visited, 8, hipMemcpyDeviceToHost)); pl->stats.affine_visited_cells = v; }
+  if (d_visited) pl->stats.affine_visited_cells = h_visited;
   pl->stats.allele_bytes = pl->out_seq_bytes + 40ull * pl->out_alleles;
   pl->stats.algorithmic_bytes = pl->stats.edit_seq_bytes + 4 * pl->stats.edit_cells + pl->stats.affine_seq_bytes + 4 * pl->stats.affine_cells +
                                 (pl->stats.affine_cells + 1) / 2 + pl->stats.allele_bytes;
   {
-    std::vector<otg_region_result> rr(NG);
-    HIP_TRY(ctx, hipMemcpy(rr.data(), B(B_REGRES), (size_t)NG * sizeof(otg_region_result), hipMemcpyDeviceToHost));
     uint64_t ok = 0;
     for (auto& r : rr) { if (r.status < 0) return otg_fail(ctx, OTG_ERR_FATAL, "a region hit a condition on which the reference exit(1)s (status %d)", r.status); ok += (r.n_alleles > 0); }
     pl->stats.n_regions_ok = ok;

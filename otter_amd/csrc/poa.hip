@@ -16,7 +16,9 @@
 // ties), first candidate always accepted; the end node is the lowest id among the heaviest ending nodes.
 // Damping is applied on the fly with the reference's FP32 operations (-ffp-contract=off).
 #include "otg_common.hpp"
+#include "otg_scan.hpp"
 #include <vector>
+#include <cstddef>
 #include <cstdlib>
 #include <algorithm>
 
@@ -79,6 +81,171 @@ __global__ void poa_count_kernel(const uint8_t* __restrict__ cig_arena, const ot
     prev = op;
   }
   n_alt[m] = alt; n_mrun[m] = mrun;
+}
+
+// ---- the plan of a device-resident batch, made on the device (otg_launch_poa_resident) ----------------------------------------------
+// What the host planner of otg_launch_poa derives from a download of every graph slot and of two counts per member — capacities and their
+// running sums, the LDS size, the two launch lists in their order, the place of every graph's image in the work arrays — comes from the
+// kernels below with the same integer formulas; the host reads back one PoaPlanRec to size its allocations and grids.
+constexpr uint32_t POA_LDS_NODE_B = 18, POA_LDS_EDGE_B = 8;      // NodeL 12 + bbc 2 + queue 2 + base 1 + end 1; EdgeL 8 (poa_graph_lds_kernel)
+constexpr uint32_t POA_EST_STEP = 512, POA_EST_MAX = 16u * 1024u, POA_EST_BUCKETS = POA_EST_MAX / POA_EST_STEP + 2;   // [0] unused, [1..32], [33] = beyond 16 KB
+enum { CAP_NODE = 0, CAP_EDGE, CAP_START, CAP_ANCHOR, CAP_KINDS };
+struct PoaPlanRec {
+  uint64_t nn;                    // sum of the node capacities = bytes of out_arena
+  uint64_t tot[2][CAP_KINDS];     // per launch list (0: LDS kernel, 1: global-memory kernel) the summed capacities = sizes of one piece
+  uint32_t n_list[2];             // graphs per launch list
+  uint32_t first[2];              // where each list begins in the launch order (0, n_list[0])
+  uint32_t n_live, lds_bytes;
+  uint32_t wide;                  // a node capacity reached 2^24 - 2: no second-generation path
+  uint32_t unsortable;            // a weight does not fit the sort key: the host planner takes the batch
+  uint32_t est_hist[POA_EST_BUCKETS];   // live graphs by LDS estimate in 512-byte steps (device only, not read back)
+};
+constexpr size_t POA_PLAN_REC_HOST_BYTES = offsetof(PoaPlanRec, est_hist);
+static_assert(POA_PLAN_REC_HOST_BYTES <= 128, "the host reads one record of at most 128 bytes");
+
+// One wave per graph slot.  The op strings of the graph's members are read 64 ops per load (POA_PLAN_U loads in flight); alt and mrun are
+// popcounts of ballots, the 'M' before a chunk is carried in `carry` and forgotten at a member's start, as poa_count_kernel's `prev` is.
+// The LDS estimate is the host's double expression: every term is an integer or a half below 2^53, so no operation rounds and a fused
+// multiply-add gives the same value.
+constexpr uint32_t POA_PLAN_U = 8;
+__global__ __launch_bounds__(256) void poa_plan_count_kernel(const uint8_t* __restrict__ cig_arena, const otg_poa_member* __restrict__ members,
+                                                             const otg_poa_graph* __restrict__ graphs, uint32_t n_graphs,
+                                                             uint64_t* __restrict__ cap, uint32_t* __restrict__ est, uint32_t* __restrict__ weight,
+                                                             PoaPlanRec* __restrict__ rec)
+{
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t g = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (g >= n_graphs) return;
+  const otg_poa_graph G = graphs[g];
+  uint64_t alt = 0, mrun = 0;
+  for (uint32_t m = 0; m < G.n_members; ++m) {
+    const otg_poa_member M = members[G.first_member + m];
+    const uint8_t* c = cig_arena + M.cigar_off;
+    const uint32_t n = M.cigar_len;
+    unsigned long long carry = 0;
+    for (uint32_t base = 0; base < n; base += 64u * POA_PLAN_U) {
+      uint8_t op[POA_PLAN_U];
+#pragma unroll
+      for (uint32_t u = 0; u < POA_PLAN_U; ++u) { const uint32_t i = base + u * 64u + lane; op[u] = (i >= base && i < n) ? c[i] : (uint8_t)0; }
+#pragma unroll
+      for (uint32_t u = 0; u < POA_PLAN_U; ++u) {
+        const unsigned long long a = __ballot(op[u] == 'X' || op[u] == 'I'), mm = __ballot(op[u] == 'M');
+        alt += (uint64_t)__popcll(a);
+        mrun += (uint64_t)__popcll(mm & ~((mm << 1) | carry));
+        carry = mm >> 63;
+      }
+    }
+  }
+  if (lane != 0) return;
+  const uint64_t ncap = ((uint64_t)G.backbone_len + alt + 2 + 3) & ~3ull, ecap = (alt + mrun + 2 + 1) & ~1ull;
+  const size_t stride = (size_t)n_graphs + 1;
+  cap[CAP_NODE * stride + g] = ncap;
+  cap[CAP_EDGE * stride + g] = ecap;
+  cap[CAP_START * stride + g] = (uint64_t)G.n_members + 2;
+  cap[CAP_ANCHOR * stride + g] = ((uint64_t)G.backbone_len + 2 + 3) & ~3ull;
+  if (ncap >= (1ull << 24) - 2) rec->wide = 1u;
+  uint32_t e = 0, w = 0;
+  if (!(G.backbone_len == 0 && G.n_members == 0)) {
+    const double B = (double)G.backbone_len;
+    const double need = (double)POA_LDS_NODE_B * (B + 0.5 * ((double)ncap - B) + 4.0) + (double)POA_LDS_EDGE_B * (0.5 * (double)ecap + 4.0) + (double)((2u * (G.n_members + 2u) + 7u) & ~7u) + 32.0 + 64.0;
+    e = need > 4.0e9 ? 0xffffffffu : (uint32_t)need;          // > 0: the constant terms alone are 200
+    const uint64_t bucket = ((uint64_t)e + POA_EST_STEP - 1) / POA_EST_STEP;
+    atomicAdd(&rec->est_hist[bucket < POA_EST_BUCKETS - 1 ? bucket : POA_EST_BUCKETS - 1], 1u);
+    atomicAdd(&rec->n_live, 1u);
+    if (ncap + ecap >= (1ull << 31)) rec->unsortable = 1u; else w = (uint32_t)(ncap + ecap);
+  }
+  est[g] = e; weight[g] = w;               // est 0: the slot is not live
+}
+
+// The LDS size of the batch from the histogram, as the host takes it: the estimate of rank floor((n_live - 1) * 0.97), rounded up to 512 bytes,
+// if that is at most 16 KB (floor 4096), else none.  Rounding up to 512 is monotone, so the rank's bucket is the rounded value.
+__device__ uint32_t poa_plan_lds_bytes(const PoaPlanRec* rec, int no_lds)
+{
+  const uint32_t n_live = rec->n_live;
+  if (n_live == 0 || no_lds) return 0u;
+  const uint64_t k = (uint64_t)((double)(n_live - 1) * 0.97);
+  uint64_t seen = 0;
+  for (uint32_t b = 1; b < POA_EST_BUCKETS - 1; ++b) {
+    seen += rec->est_hist[b];
+    if (seen > k) { const uint32_t v = b * POA_EST_STEP; return v > 4096u ? v : 4096u; }
+  }
+  return 0u;
+}
+
+// Sort keys, one per slot: list (0 LDS, 1 global memory, 2 not live) above the inverted weight, so that an ascending stable sort gives the
+// LDS list, then the other, each by weight descending and, among equal weights, by graph index ascending — the host planner's order.
+constexpr uint32_t POA_SORT_BITS = 11, POA_SORT_RADIX = 1u << POA_SORT_BITS, POA_SORT_PASSES = 3, POA_SORT_CHUNK = 4096;   // 2 + 31 key bits
+__global__ __launch_bounds__(256) void poa_plan_keys_kernel(const uint32_t* __restrict__ est, const uint32_t* __restrict__ weight, uint32_t n_graphs, int no_lds,
+                                                            uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, PoaPlanRec* __restrict__ rec)
+{
+  __shared__ uint32_t s_lds;
+  if (threadIdx.x == 0) s_lds = poa_plan_lds_bytes(rec, no_lds);
+  __syncthreads();
+  const uint32_t lds_bytes = s_lds;
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t list = 2;
+  if (g < n_graphs) {
+    const uint32_t e = est[g];
+    if (e) list = (lds_bytes && e <= lds_bytes) ? 0u : 1u;
+    keys[g] = ((uint64_t)list << 31) | (uint64_t)(0x7fffffffu - weight[g]);
+    vals[g] = g;
+  }
+  const unsigned long long m0 = __ballot(list == 0), m1 = __ballot(list == 1);
+  if ((threadIdx.x & 63u) == 0) {
+    if (m0) atomicAdd(&rec->n_list[0], (uint32_t)__popcll(m0));
+    if (m1) atomicAdd(&rec->n_list[1], (uint32_t)__popcll(m1));
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) rec->lds_bytes = lds_bytes;
+}
+
+// rec->first[1] = n_list[0] once the counts are complete (its own launch: the keys kernel's blocks finish in any order)
+__global__ void poa_plan_first_kernel(PoaPlanRec* rec) { rec->first[0] = 0u; rec->first[1] = rec->n_list[0]; }
+
+// Stable LSD radix sort, 11 bits per pass: wave w owns the POA_SORT_CHUNK consecutive entries from w * POA_SORT_CHUNK.  Pass = histogram per wave
+// (table[digit * W + w]), an exclusive scan of the table in that order (otg_scan_jobs_kernel), and a scatter in which a wave walks its chunk
+// in order, 64 entries per trip: lanes with the same digit find each other by ballots over the digit's bits, an entry's place is the wave's
+// running offset of that digit plus its rank among those lanes.
+__global__ __launch_bounds__(64) void poa_plan_sort_hist_kernel(const uint64_t* __restrict__ keys, uint32_t n, uint32_t shift, uint32_t W, uint32_t* __restrict__ table)
+{
+  __shared__ uint32_t h[POA_SORT_RADIX];
+  const uint32_t lane = threadIdx.x, w = blockIdx.x;
+  for (uint32_t d = lane; d < POA_SORT_RADIX; d += 64) h[d] = 0;
+  __syncthreads();
+  const uint32_t a = w * POA_SORT_CHUNK, b = a + POA_SORT_CHUNK < n ? a + POA_SORT_CHUNK : n;
+  for (uint32_t i = a + lane; i < b; i += 64) atomicAdd(&h[(uint32_t)(keys[i] >> shift) & (POA_SORT_RADIX - 1)], 1u);
+  __syncthreads();
+  for (uint32_t d = lane; d < POA_SORT_RADIX; d += 64) table[(size_t)d * W + w] = h[d];
+}
+
+__global__ __launch_bounds__(64) void poa_plan_sort_scatter_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint32_t n, uint32_t shift,
+                                                                   uint32_t W, const uint64_t* __restrict__ offs, uint64_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out)
+{
+  __shared__ uint32_t pos[POA_SORT_RADIX];
+  const uint32_t lane = threadIdx.x, w = blockIdx.x;
+  for (uint32_t d = lane; d < POA_SORT_RADIX; d += 64) pos[d] = (uint32_t)offs[(size_t)d * W + w];
+  __syncthreads();
+  const uint32_t a = w * POA_SORT_CHUNK, b = a + POA_SORT_CHUNK < n ? a + POA_SORT_CHUNK : n;
+  for (uint32_t base = a; base < b; base += 64) {
+    const uint32_t i = base + lane;
+    const bool in = i < b;
+    const uint64_t key = in ? keys[i] : 0ull;
+    const uint32_t d = (uint32_t)(key >> shift) & (POA_SORT_RADIX - 1);
+    unsigned long long peers = __ballot(in);
+#pragma unroll
+    for (uint32_t bit = 0; bit < POA_SORT_BITS; ++bit) {
+      const bool s = (d >> bit) & 1u;
+      const unsigned long long mb = __ballot(in && s);
+      peers &= s ? mb : ~mb;
+    }
+    uint32_t p = 0;
+    if (in) p = pos[d] + (uint32_t)__popcll(peers & ((1ull << lane) - 1ull));
+    __syncthreads();                                                           // every lane has read its offset
+    if (in) {
+      keys_out[p] = key; vals_out[p] = vals[i];
+      if (lane == 63u - (uint32_t)__builtin_clzll(peers)) pos[d] += (uint32_t)__popcll(peers);      // the last lane of a digit moves the offset on
+    }
+    __syncthreads();
+  }
 }
 
 // Mapping: one WAVE per graph.  Everything that is sequential in the reference stays sequential but runs
@@ -972,7 +1139,6 @@ __device__ __forceinline__ bool poa_graph_body(const PoaDev& P, const uint32_t g
 
 // LDS instantiation: one single-wave block per graph (the dispatcher refills the slot as soon as its graph is done); a graph
 // that does not fit, or outgrows its optimistic capacities, goes onto the list of the global-memory kernel below.
-constexpr uint32_t POA_LDS_NODE_B = 18, POA_LDS_EDGE_B = 8;      // NodeL 12 + bbc 2 + queue 2 + base 1 + end 1; EdgeL 8
 __global__ __launch_bounds__(64) void poa_graph_lds_kernel(PoaDev P, const uint32_t* __restrict__ list, uint32_t lds_bytes)
 {
   extern __shared__ __attribute__((aligned(16))) uint8_t s_graph[];
@@ -1044,6 +1210,206 @@ __global__ __launch_bounds__(64, OTG_POA_WPEU) void poa_graph_wave_kernel(PoaDev
     L.ops = (volatile lds_u32*)&s_ops[0]; L.stage = (volatile lds_u32*)&s_stage[0]; L.hw = (volatile lds_f32*)&s_hw[0]; L.pred = (volatile lds_i32*)&s_pred[0];
     poa_graph_body<false>(P, g, S, S.node_cap, X, L, P.v2 != 0);
   }
+}
+
+// ---- host side shared by the two planners ------------------------------------------------------------------------------------------
+struct PoaPiece { uint32_t k0, k1; bool lds; };            // entries [k0, k1) of the launch order, for which kernel
+struct PoaLayout {
+  uint64_t NN = 0, maxN = 0, maxE = 0, maxS = 0, maxA = 0;  // out_arena bytes; the largest piece's summed capacities
+  uint32_t lds_bytes = 0, n_lds = 0, n_glob = 0;
+  std::vector<PoaPiece> pieces;
+};
+
+// bytes of the graph images of a piece with these summed capacities
+inline uint64_t poa_image_bytes(uint64_t cn, uint64_t ce, uint64_t cs, uint64_t ca) { return cn * (sizeof(NodeG) + 10) + ce * (sizeof(EdgeG) + 4) + cs * 4 + ca * 12; }
+
+// The graph images are sized for the worst case (every X / I op a new node), ~0.5 MB per allele of a 3 kb locus: a batch of 100 000 regions
+// would ask for 150 GB at once.  So the launch lists are cut into pieces whose images fit a fixed budget; the pieces run one after the
+// other on the stream and reuse the same work arrays (a piece of 24 GB holds tens of thousands of graphs, several times what the device
+// keeps in flight).  Only the consensus arena and the per-graph outputs span the whole batch.
+int poa_piece_budget(otg_ctx* ctx, size_t* out)
+{
+  static const size_t piece_budget_cfg = getenv("OTG_POA_PIECE_MB") ? (size_t)atoll(getenv("OTG_POA_PIECE_MB")) << 20 : (size_t)24 << 30;
+  // ... and never more than half of what the device can still give (what the work arrays hold already counts as available)
+  size_t free_b = 0, total_b = 0, held = 0;
+  HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
+  for (int sl : {SLOT_P3, SLOT_P4, SLOT_P6, SLOT_P7, SLOT_P8, SLOT_P9, SLOT_P10, SLOT_P11, SLOT_P12, SLOT_P13, SLOT_P16}) held += ctx->pool[sl].cap;
+  *out = std::min(piece_budget_cfg, std::max<size_t>((size_t)1 << 30, (free_b + held) / 2));
+  return OTG_OK;
+}
+
+// the per-graph offsets and the launch order, which a planner fills: SLOT_P0 node_off, SLOT_P1 edge_off, SLOT_P2 the four w* arrays, SLOT_P18 the order
+int poa_offset_slots(otg_ctx* ctx, PoaDev& P, uint32_t n_graphs)
+{
+  uint64_t* d_node_off = (uint64_t*)otg_slot(ctx, SLOT_P0, (size_t)(n_graphs + 1) * sizeof(uint64_t));
+  uint64_t* d_edge_off = (uint64_t*)otg_slot(ctx, SLOT_P1, (size_t)(n_graphs + 1) * sizeof(uint64_t));
+  uint64_t* d_woff = (uint64_t*)otg_slot(ctx, SLOT_P2, (size_t)4 * (n_graphs + 1) * sizeof(uint64_t));
+  uint32_t* d_order = (uint32_t*)otg_slot(ctx, SLOT_P18, (size_t)(n_graphs + 1) * sizeof(uint32_t));
+  if (!d_node_off || !d_edge_off || !d_woff || !d_order) return OTG_ERR_HIP;
+  P.node_off = d_node_off; P.edge_off = d_edge_off;
+  P.wnode_off = d_woff; P.wedge_off = d_woff + (n_graphs + 1); P.wstart_off = d_woff + 2 * (size_t)(n_graphs + 1); P.wanch_off = d_woff + 3 * (size_t)(n_graphs + 1);
+  P.out_off = d_node_off;     // consensus g is written into [node_off[g], node_off[g+1]) of out_arena
+  P.order = d_order;
+  return OTG_OK;
+}
+
+// The launches of a planned batch: P carries the inputs, v2 and the offsets (poa_offset_slots, filled on the stream by the planner); the work
+// arrays are sized here from the layout.
+int poa_launch_planned(otg_ctx* ctx, PoaDev& P, const PoaLayout& L, uint32_t* d_out_len)
+{
+  const uint32_t n_graphs = P.n_graphs;
+  P.node_base = (uint8_t*)otg_slot(ctx, SLOT_P3, L.maxN);
+  P.is_end = (uint8_t*)otg_slot(ctx, SLOT_P4, L.maxN);
+  P.nodes = (NodeG*)otg_slot(ctx, SLOT_P6, L.maxN * sizeof(NodeG));
+  P.bb_cnt = (uint32_t*)otg_slot(ctx, SLOT_P9, L.maxN * 4);
+  P.queue = (uint32_t*)otg_slot(ctx, SLOT_P12, L.maxN * 4);
+  P.edges = (EdgeG*)otg_slot(ctx, SLOT_P13, L.maxE * sizeof(EdgeG));
+  P.start_list = (uint32_t*)otg_slot(ctx, SLOT_P16, L.maxS * 4);
+  P.out_arena = (uint8_t*)otg_slot(ctx, SLOT_P17, L.NN);
+  P.out_start = (uint32_t*)otg_slot(ctx, SLOT_P29, (size_t)n_graphs * 4);
+  P.status = (int32_t*)otg_slot(ctx, SLOT_P28, (size_t)n_graphs * 4);
+  P.anext = nullptr; P.ahead = nullptr; P.atail = nullptr; P.acnt = nullptr;
+  if (P.v2) {
+    P.anext = (int32_t*)otg_slot(ctx, SLOT_P7, L.maxE * 4);
+    P.ahead = (int32_t*)otg_slot(ctx, SLOT_P8, L.maxA * 4);
+    P.atail = (int32_t*)otg_slot(ctx, SLOT_P10, L.maxA * 4);
+    P.acnt = (uint32_t*)otg_slot(ctx, SLOT_P11, L.maxA * 4);
+    if (!P.anext || !P.ahead || !P.atail || !P.acnt) return OTG_ERR_HIP;
+  }
+  if (!P.node_base || !P.is_end || !P.nodes || !P.bb_cnt || !P.queue || !P.edges || !P.start_list || !P.out_arena || !P.out_start || !P.status)
+    return OTG_ERR_HIP;
+  P.out_len = d_out_len;
+  HIP_TRY(ctx, hipMemsetAsync(d_out_len, 0, (size_t)n_graphs * sizeof(uint32_t), ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(P.out_start, 0, (size_t)n_graphs * sizeof(uint32_t), ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(P.status, 0, (size_t)n_graphs * sizeof(int32_t), ctx->stream));
+  static const bool profile = getenv("OTG_POA_PROFILE") != nullptr;
+  P.prof = nullptr; P.prof_graph = nullptr;
+  if (profile) {
+    P.prof_graph = (unsigned long long*)otg_slot(ctx, SLOT_P23, (size_t)n_graphs * 9 * sizeof(unsigned long long));
+    if (!P.prof_graph) return OTG_ERR_HIP;
+    HIP_TRY(ctx, hipMemsetAsync(P.prof_graph, 0, (size_t)n_graphs * 9 * sizeof(unsigned long long), ctx->stream));
+    P.prof = (unsigned long long*)otg_slot(ctx, SLOT_P19, 32 * sizeof(unsigned long long));
+    if (!P.prof) return OTG_ERR_HIP;
+    HIP_TRY(ctx, hipMemsetAsync(P.prof, 0, 32 * sizeof(unsigned long long), ctx->stream));
+  }
+  P.fb_list = (uint32_t*)otg_slot(ctx, SLOT_P22, (size_t)(n_graphs + 1) * sizeof(uint32_t));
+  if (!P.fb_list) return OTG_ERR_HIP;
+  P.fb_count = P.fb_list + n_graphs;
+  const uint32_t lds_bytes = L.lds_bytes, n_lds = L.n_lds, n_glob = L.n_glob;
+  for (const PoaPiece& pc : L.pieces) {
+    const uint32_t n = pc.k1 - pc.k0;
+    // one single-wave block per graph: the dispatcher refills a wave slot as soon as its graph is done
+    if (!pc.lds) hipLaunchKernelGGL(poa_graph_wave_kernel, dim3(n), dim3(64), 0, ctx->stream, P, P.order + pc.k0, (const uint32_t*)nullptr, n);
+    else {
+      HIP_TRY(ctx, hipMemsetAsync(P.fb_count, 0, sizeof(uint32_t), ctx->stream));
+      hipLaunchKernelGGL(poa_graph_lds_kernel, dim3(n), dim3(64), lds_bytes, ctx->stream, P, P.order + pc.k0, lds_bytes);
+      const uint32_t fg = n < (uint32_t)ctx->n_cu * 32 ? n : (uint32_t)ctx->n_cu * 32;
+      hipLaunchKernelGGL(poa_graph_wave_kernel, dim3(fg), dim3(64), 0, ctx->stream, P, (const uint32_t*)P.fb_list, (const uint32_t*)P.fb_count, 0u);
+    }
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  if (profile) {
+    unsigned long long h[32];
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(h, P.prof, sizeof(h), hipMemcpyDeviceToHost));
+    const double n = h[3] ? (double)h[3] : 1.0;     // wall_clock64: 100 MHz
+    fprintf(stderr, "[otg] poa profile: %u LDS + %u global launches; %llu graphs done (%llu in LDS, %u bytes each), per graph: insert %.1f us, sweep %.1f us, emit %.1f us; nodes %.0f (backbone %.0f), edges %.0f\n",
+            n_lds, n_glob, h[3], h[7], lds_bytes, h[0] / n / 100.0, h[1] / n / 100.0, h[2] / n / 100.0, h[4] / n, h[6] / n, h[5] / n);
+    fprintf(stderr, "[otg] poa profile: threading chunks per graph: %.1f wide (%.0f ops each), %.1f narrow one-lane-per-run, %.1f serial; slowest graph: insert %.1f us, whole %.1f us\n",
+            h[8] / n, h[8] ? (double)h[9] / (double)h[8] : 0.0, h[10] / n, h[11] / n, h[12] / 100.0, h[13] / 100.0);
+    { const double nw = h[8] ? (double)h[8] : 1.0;
+      fprintf(stderr, "[otg] poa profile: a wide chunk, us: layout %.2f, bases + marks + staging %.2f, subtree walk %.2f, ids %.2f, chains %.2f; narrow + serial code per graph %.1f us\n",
+              h[27] / nw / 100.0, h[28] / nw / 100.0, h[29] / nw / 100.0, h[30] / nw / 100.0, h[31] / nw / 100.0, h[20] / n / 100.0); }
+    {
+      std::vector<unsigned long long> pg((size_t)n_graphs * 9);
+      HIP_TRY(ctx, hipMemcpy(pg.data(), P.prof_graph, pg.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+      std::vector<uint32_t> idx(n_graphs);
+      for (uint32_t g = 0; g < n_graphs; ++g) idx[g] = g;
+      const size_t top = std::min<size_t>(5, n_graphs);
+      std::partial_sort(idx.begin(), idx.begin() + top, idx.end(), [&](uint32_t a, uint32_t b) { return pg[9 * (size_t)a] > pg[9 * (size_t)b]; });
+      for (size_t t = 0; t < top; ++t) {
+        const unsigned long long* q = &pg[9 * (size_t)idx[t]];
+        fprintf(stderr, "[otg] poa profile: slow graph %u: %llu members on a backbone of %llu, threading %.1f us = %llu wide + %llu narrow + %llu serial chunks; %.1f us in the narrow + serial code (%llu steps taken as a retraced chain)\n",
+                idx[t], q[5] & 0xffffffffull, q[5] >> 32, q[0] / 100.0, q[1], q[2], q[3], (q[4] & ((1ull << 40) - 1ull)) / 100.0, q[4] >> 40);
+        fprintf(stderr, "[otg] poa profile:   its serial code: %llu windows without an 'M', %llu member heads, %llu others; ops taken one by one: %llu M, %llu X, %llu I, %llu D\n",
+                q[8] & 0xfffffull, (q[8] >> 20) & 0xfffffull, q[8] >> 40, q[6] & 0xffffffffull, q[6] >> 32, q[7] & 0xffffffffull, q[7] >> 32);
+      }
+    }
+  }
+  return OTG_OK;
+}
+
+// The plan of a device-resident batch made on the device.  *planned = false (nothing launched, nothing to undo) where the host planner has to
+// take the batch: a launch list whose image exceeds the piece budget, or a weight beyond the sort key.
+int poa_plan_on_device(otg_ctx* ctx, PoaDev& P, uint32_t* d_out_len, bool no_lds, bool* planned)
+{
+  *planned = false;
+  const uint32_t n = P.n_graphs;
+  hipStream_t st = ctx->stream;
+  size_t piece_budget = 0;
+  if (int rc = poa_piece_budget(ctx, &piece_budget)) return rc;
+  if (int rc = poa_offset_slots(ctx, P, n)) return rc;
+  const size_t stride = (size_t)n + 1;
+  const uint32_t W = (n + POA_SORT_CHUNK - 1) / POA_SORT_CHUNK;
+  const size_t table_n = (size_t)POA_SORT_RADIX * W;
+  uint64_t* d_cap = (uint64_t*)otg_slot(ctx, SLOT_P20, CAP_KINDS * stride * sizeof(uint64_t));
+  uint32_t* d_est = (uint32_t*)otg_slot(ctx, SLOT_P21, 2 * stride * sizeof(uint32_t));
+  uint64_t* d_keys = (uint64_t*)otg_slot(ctx, SLOT_P14, 2 * stride * sizeof(uint64_t) + 2 * stride * sizeof(uint32_t));
+  uint64_t* d_offs = (uint64_t*)otg_slot(ctx, SLOT_P15, table_n * (sizeof(uint64_t) + sizeof(uint32_t)));
+  PoaPlanRec* d_rec = (PoaPlanRec*)otg_slot(ctx, SLOT_P5, sizeof(PoaPlanRec));
+  if (!d_cap || !d_est || !d_keys || !d_offs || !d_rec) return OTG_ERR_HIP;
+  uint32_t* d_weight = d_est + stride;
+  uint64_t* keys[2] = {d_keys, d_keys + stride};
+  uint32_t* vals[2] = {(uint32_t*)(d_keys + 2 * stride), (uint32_t*)(d_keys + 2 * stride) + stride};
+  uint32_t* d_table = (uint32_t*)(d_offs + table_n);
+  HIP_TRY(ctx, hipMemsetAsync(d_rec, 0, sizeof(PoaPlanRec), st));
+  hipLaunchKernelGGL(poa_plan_count_kernel, dim3((n + 3) / 4), dim3(256), 0, st, P.cig_arena, P.members, P.graphs, n, d_cap, d_est, d_weight, d_rec);
+  {   // node_off, edge_off: n + 1 running sums each
+    OtgScanJobs sj;
+    sj.j[0].in = d_cap + CAP_NODE * stride; sj.j[0].in_u64 = 1; sj.j[0].out = (uint64_t*)P.node_off; sj.j[0].n = n; sj.j[0].write_end = 1; sj.j[0].total = &d_rec->nn;
+    sj.j[1].in = d_cap + CAP_EDGE * stride; sj.j[1].in_u64 = 1; sj.j[1].out = (uint64_t*)P.edge_off; sj.j[1].n = n; sj.j[1].write_end = 1;
+    hipLaunchKernelGGL(otg_scan_jobs_kernel<8>, dim3(2), dim3(1024), 0, st, sj);
+  }
+  hipLaunchKernelGGL(poa_plan_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, st, (const uint32_t*)d_est, (const uint32_t*)d_weight, n, no_lds ? 1 : 0, keys[0], vals[0], d_rec);
+  hipLaunchKernelGGL(poa_plan_first_kernel, dim3(1), dim3(1), 0, st, d_rec);
+  for (uint32_t pass = 0; pass < POA_SORT_PASSES; ++pass) {
+    const uint32_t src = pass & 1u, dst = src ^ 1u, shift = pass * POA_SORT_BITS;
+    hipLaunchKernelGGL(poa_plan_sort_hist_kernel, dim3(W), dim3(64), 0, st, (const uint64_t*)keys[src], n, shift, W, d_table);
+    OtgScanJobs sj;
+    sj.j[0].in = d_table; sj.j[0].out = d_offs; sj.j[0].n = (uint32_t)table_n;
+    hipLaunchKernelGGL(otg_scan_jobs_kernel<8>, dim3(1), dim3(1024), 0, st, sj);
+    // the last pass leaves the graph indices in the launch order itself
+    hipLaunchKernelGGL(poa_plan_sort_scatter_kernel, dim3(W), dim3(64), 0, st, (const uint64_t*)keys[src], (const uint32_t*)vals[src], n, shift, W, (const uint64_t*)d_offs,
+                       keys[dst], pass + 1 == POA_SORT_PASSES ? (uint32_t*)P.order : vals[dst]);
+  }
+  {   // the place of every graph's image in the work arrays: running sums along each launch list (one piece per list), scattered to the graphs
+    OtgScanJobs sj;
+    uint64_t* w[CAP_KINDS] = {(uint64_t*)P.wnode_off, (uint64_t*)P.wedge_off, (uint64_t*)P.wstart_off, (uint64_t*)P.wanch_off};
+    for (int l = 0; l < 2; ++l)
+      for (int k = 0; k < CAP_KINDS; ++k) {
+        OtgScanJob& j = sj.j[l * CAP_KINDS + k];
+        j.in = d_cap + k * stride; j.in_u64 = 1; j.idx = P.order; j.first_ptr = &d_rec->first[l]; j.n_ptr = &d_rec->n_list[l]; j.out = w[k]; j.total = &d_rec->tot[l][k];
+      }
+    static_assert(2 * CAP_KINDS <= OTG_SCAN_MAX_JOBS, "one block per list and capacity kind");
+    hipLaunchKernelGGL(otg_scan_jobs_kernel<8>, dim3(2 * CAP_KINDS), dim3(1024), 0, st, sj);
+  }
+  PoaPlanRec rec;
+  HIP_TRY(ctx, hipMemcpyAsync(&rec, d_rec, POA_PLAN_REC_HOST_BYTES, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  HIP_TRY(ctx, hipGetLastError());
+  if (rec.unsortable) return OTG_OK;
+  for (int l = 0; l < 2; ++l)
+    if (rec.n_list[l] > 1 && poa_image_bytes(rec.tot[l][CAP_NODE], rec.tot[l][CAP_EDGE], rec.tot[l][CAP_START], rec.tot[l][CAP_ANCHOR]) > piece_budget) return OTG_OK;
+  if (rec.wide) P.v2 = 0;
+  PoaLayout L;
+  L.NN = rec.nn;
+  L.maxN = std::max(rec.tot[0][CAP_NODE], rec.tot[1][CAP_NODE]); L.maxE = std::max(rec.tot[0][CAP_EDGE], rec.tot[1][CAP_EDGE]);
+  L.maxS = std::max(rec.tot[0][CAP_START], rec.tot[1][CAP_START]); L.maxA = std::max(rec.tot[0][CAP_ANCHOR], rec.tot[1][CAP_ANCHOR]);
+  L.lds_bytes = rec.lds_bytes; L.n_lds = rec.n_list[0]; L.n_glob = rec.n_list[1];
+  if (L.n_glob) L.pieces.push_back({L.n_lds, L.n_lds + L.n_glob, false});      // the host planner's order of launches: global-memory list first
+  if (L.n_lds) L.pieces.push_back({0u, L.n_lds, true});
+  *planned = true;
+  return poa_launch_planned(ctx, P, L, d_out_len);
 }
 
 } // namespace
@@ -1122,20 +1488,10 @@ int otg_launch_poa(otg_ctx* ctx, const uint8_t* d_seq_arena, const uint8_t* d_ci
     std::sort(order.begin(), order.begin() + n_lds, heavier);
     std::sort(order.begin() + n_lds, order.end(), heavier);
   }
-  // The graph images are sized for the worst case (every X / I op a new node), ~0.5 MB per allele of a 3 kb locus: a batch of 100 000 regions
-  // would ask for 150 GB at once.  So the launch lists are cut into pieces whose images fit a fixed budget; the pieces run one after the
-  // other on the stream and reuse the same work arrays (a piece of 24 GB holds tens of thousands of graphs, several times what the device
-  // keeps in flight).  Only the consensus arena and the per-graph outputs span the whole batch.
-  static const size_t piece_budget_cfg = getenv("OTG_POA_PIECE_MB") ? (size_t)atoll(getenv("OTG_POA_PIECE_MB")) << 20 : (size_t)24 << 30;
-  size_t piece_budget = piece_budget_cfg;
-  {   // ... and never more than half of what the device can still give (what the work arrays hold already counts as available)
-    size_t free_b = 0, total_b = 0, held = 0;
-    HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
-    for (int sl : {SLOT_P3, SLOT_P4, SLOT_P6, SLOT_P7, SLOT_P8, SLOT_P9, SLOT_P10, SLOT_P11, SLOT_P12, SLOT_P13, SLOT_P16}) held += ctx->pool[sl].cap;
-    piece_budget = std::min(piece_budget, std::max<size_t>((size_t)1 << 30, (free_b + held) / 2));
-  }
-  struct Piece { uint32_t k0, k1; bool lds; };
-  std::vector<Piece> pieces;
+  // the launch lists, cut into pieces whose images fit the budget (poa_piece_budget)
+  size_t piece_budget = 0;
+  if (int rc = poa_piece_budget(ctx, &piece_budget)) return rc;
+  std::vector<PoaPiece> pieces;
   std::vector<uint64_t> wnode(n_graphs + 1, 0), wedge(n_graphs + 1, 0), wstart(n_graphs + 1, 0), wanch(n_graphs + 1, 0);
   uint64_t maxN = 0, maxE = 0, maxS = 0, maxA = 0;
   {
@@ -1157,99 +1513,43 @@ int otg_launch_poa(otg_ctx* ctx, const uint8_t* d_seq_arena, const uint8_t* d_ci
     cut(n_lds, n_lds + n_glob, false);
     cut(0, n_lds, true);
   }
-  uint64_t* d_node_off = (uint64_t*)otg_slot(ctx, SLOT_P0, (size_t)(n_graphs + 1) * sizeof(uint64_t));
-  uint64_t* d_edge_off = (uint64_t*)otg_slot(ctx, SLOT_P1, (size_t)(n_graphs + 1) * sizeof(uint64_t));
-  uint64_t* d_woff = (uint64_t*)otg_slot(ctx, SLOT_P2, (size_t)4 * (n_graphs + 1) * sizeof(uint64_t));
-  P.node_base = (uint8_t*)otg_slot(ctx, SLOT_P3, maxN);
-  P.is_end = (uint8_t*)otg_slot(ctx, SLOT_P4, maxN);
-  P.nodes = (NodeG*)otg_slot(ctx, SLOT_P6, maxN * sizeof(NodeG));
-  P.bb_cnt = (uint32_t*)otg_slot(ctx, SLOT_P9, maxN * 4);
-  P.queue = (uint32_t*)otg_slot(ctx, SLOT_P12, maxN * 4);
-  P.edges = (EdgeG*)otg_slot(ctx, SLOT_P13, maxE * sizeof(EdgeG));
-  P.start_list = (uint32_t*)otg_slot(ctx, SLOT_P16, maxS * 4);
-  P.out_arena = (uint8_t*)otg_slot(ctx, SLOT_P17, NN);
-  P.out_start = (uint32_t*)otg_slot(ctx, SLOT_P29, (size_t)n_graphs * 4);
-  P.status = (int32_t*)otg_slot(ctx, SLOT_P28, (size_t)n_graphs * 4);
-  P.anext = nullptr; P.ahead = nullptr; P.atail = nullptr; P.acnt = nullptr;
-  if (P.v2) {
-    P.anext = (int32_t*)otg_slot(ctx, SLOT_P7, maxE * 4);
-    P.ahead = (int32_t*)otg_slot(ctx, SLOT_P8, maxA * 4);
-    P.atail = (int32_t*)otg_slot(ctx, SLOT_P10, maxA * 4);
-    P.acnt = (uint32_t*)otg_slot(ctx, SLOT_P11, maxA * 4);
-    if (!P.anext || !P.ahead || !P.atail || !P.acnt) return OTG_ERR_HIP;
-  }
-  uint32_t* d_order = (uint32_t*)otg_slot(ctx, SLOT_P18, (size_t)(n_graphs + 1) * sizeof(uint32_t));
-  if (!d_node_off || !d_edge_off || !d_woff || !P.node_base || !P.is_end || !P.nodes || !P.bb_cnt || !P.queue ||
-      !P.edges || !P.start_list || !P.out_arena || !P.out_start || !P.status || !d_order)
-    return OTG_ERR_HIP;
-  P.node_off = d_node_off; P.edge_off = d_edge_off;
-  P.wnode_off = d_woff; P.wedge_off = d_woff + (n_graphs + 1); P.wstart_off = d_woff + 2 * (size_t)(n_graphs + 1); P.wanch_off = d_woff + 3 * (size_t)(n_graphs + 1);
-  P.out_off = d_node_off;     // consensus g is written into [node_off[g], node_off[g+1]) of out_arena
-  P.out_len = d_out_len;
-  P.order = d_order;
-  if (!order.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_order, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(d_out_len, 0, (size_t)n_graphs * sizeof(uint32_t), ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(P.out_start, 0, (size_t)n_graphs * sizeof(uint32_t), ctx->stream));
-  HIP_TRY(ctx, hipMemsetAsync(P.status, 0, (size_t)n_graphs * sizeof(int32_t), ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_node_off, node_off.data(), (size_t)(n_graphs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_edge_off, edge_off.data(), (size_t)(n_graphs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+  if (int rc = poa_offset_slots(ctx, P, n_graphs)) return rc;
+  uint64_t* d_woff = (uint64_t*)P.wnode_off;
+  if (!order.empty()) HIP_TRY(ctx, hipMemcpyAsync((uint32_t*)P.order, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync((uint64_t*)P.node_off, node_off.data(), (size_t)(n_graphs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync((uint64_t*)P.edge_off, edge_off.data(), (size_t)(n_graphs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_woff, wnode.data(), (size_t)(n_graphs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_woff + (n_graphs + 1), wedge.data(), (size_t)(n_graphs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_woff + 2 * (size_t)(n_graphs + 1), wstart.data(), (size_t)(n_graphs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_woff + 3 * (size_t)(n_graphs + 1), wanch.data(), (size_t)(n_graphs + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // host vectors go out of scope after return
-  static const bool profile = getenv("OTG_POA_PROFILE") != nullptr;
-  P.prof = nullptr; P.prof_graph = nullptr;
-  if (profile) {
-    P.prof_graph = (unsigned long long*)otg_slot(ctx, SLOT_P23, (size_t)n_graphs * 9 * sizeof(unsigned long long));
-    if (!P.prof_graph) return OTG_ERR_HIP;
-    HIP_TRY(ctx, hipMemsetAsync(P.prof_graph, 0, (size_t)n_graphs * 9 * sizeof(unsigned long long), ctx->stream));
-    P.prof = (unsigned long long*)otg_slot(ctx, SLOT_P19, 32 * sizeof(unsigned long long));
-    if (!P.prof) return OTG_ERR_HIP;
-    HIP_TRY(ctx, hipMemsetAsync(P.prof, 0, 32 * sizeof(unsigned long long), ctx->stream));
+  PoaLayout L;
+  L.NN = NN; L.maxN = maxN; L.maxE = maxE; L.maxS = maxS; L.maxA = maxA;
+  L.lds_bytes = lds_bytes; L.n_lds = n_lds; L.n_glob = n_glob;
+  L.pieces = std::move(pieces);
+  return poa_launch_planned(ctx, P, L, d_out_len);
+}
+
+// The consensus stage of a batch whose graphs and members are on the device (pipeline.hip): planned on the device, the host reads back one
+// record (poa_plan_on_device).  The host planner above takes the batch — after a download of the graph slots — under OTG_POA_HOST_PLAN
+// (a test compares the two planners) and OTG_POA_V1, and where the images of a launch list exceed the piece budget.  Outputs as above.
+int otg_launch_poa_resident(otg_ctx* ctx, const uint8_t* d_seq_arena, const uint8_t* d_cig_arena,
+                            const otg_poa_member* d_members, uint32_t n_members, const otg_poa_graph* d_graphs, uint32_t n_graphs, uint32_t* d_out_len)
+{
+  if (n_graphs == 0) return OTG_OK;
+  static const bool host_plan = getenv("OTG_POA_HOST_PLAN") != nullptr || getenv("OTG_POA_V1") != nullptr;
+  static const bool no_lds = getenv("OTG_POA_NO_LDS") != nullptr;
+  if (!host_plan) {
+    PoaDev P;
+    P.seq_arena = d_seq_arena; P.cig_arena = d_cig_arena; P.members = d_members; P.graphs = d_graphs; P.n_graphs = n_graphs;
+    P.v2 = 1;
+    bool planned = false;
+    const int rc = poa_plan_on_device(ctx, P, d_out_len, no_lds, &planned);
+    if (rc || planned) return rc;
   }
-  P.fb_list = (uint32_t*)otg_slot(ctx, SLOT_P22, (size_t)(n_graphs + 1) * sizeof(uint32_t));
-  if (!P.fb_list) return OTG_ERR_HIP;
-  P.fb_count = P.fb_list + n_graphs;
-  for (const Piece& pc : pieces) {
-    const uint32_t n = pc.k1 - pc.k0;
-    // one single-wave block per graph: the dispatcher refills a wave slot as soon as its graph is done
-    if (!pc.lds) hipLaunchKernelGGL(poa_graph_wave_kernel, dim3(n), dim3(64), 0, ctx->stream, P, P.order + pc.k0, (const uint32_t*)nullptr, n);
-    else {
-      HIP_TRY(ctx, hipMemsetAsync(P.fb_count, 0, sizeof(uint32_t), ctx->stream));
-      hipLaunchKernelGGL(poa_graph_lds_kernel, dim3(n), dim3(64), lds_bytes, ctx->stream, P, P.order + pc.k0, lds_bytes);
-      const uint32_t fg = n < (uint32_t)ctx->n_cu * 32 ? n : (uint32_t)ctx->n_cu * 32;
-      hipLaunchKernelGGL(poa_graph_wave_kernel, dim3(fg), dim3(64), 0, ctx->stream, P, (const uint32_t*)P.fb_list, (const uint32_t*)P.fb_count, 0u);
-    }
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  if (profile) {
-    unsigned long long h[32];
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy(h, P.prof, sizeof(h), hipMemcpyDeviceToHost));
-    const double n = h[3] ? (double)h[3] : 1.0;     // wall_clock64: 100 MHz
-    fprintf(stderr, "[otg] poa profile: %u LDS + %u global launches; %llu graphs done (%llu in LDS, %u bytes each), per graph: insert %.1f us, sweep %.1f us, emit %.1f us; nodes %.0f (backbone %.0f), edges %.0f\n",
-            n_lds, n_glob, h[3], h[7], lds_bytes, h[0] / n / 100.0, h[1] / n / 100.0, h[2] / n / 100.0, h[4] / n, h[6] / n, h[5] / n);
-    fprintf(stderr, "[otg] poa profile: threading chunks per graph: %.1f wide (%.0f ops each), %.1f narrow one-lane-per-run, %.1f serial; slowest graph: insert %.1f us, whole %.1f us\n",
-            h[8] / n, h[8] ? (double)h[9] / (double)h[8] : 0.0, h[10] / n, h[11] / n, h[12] / 100.0, h[13] / 100.0);
-    { const double nw = h[8] ? (double)h[8] : 1.0;
-      fprintf(stderr, "[otg] poa profile: a wide chunk, us: layout %.2f, bases + marks + staging %.2f, subtree walk %.2f, ids %.2f, chains %.2f; narrow + serial code per graph %.1f us\n",
-              h[27] / nw / 100.0, h[28] / nw / 100.0, h[29] / nw / 100.0, h[30] / nw / 100.0, h[31] / nw / 100.0, h[20] / n / 100.0); }
-    {
-      std::vector<unsigned long long> pg((size_t)n_graphs * 9);
-      HIP_TRY(ctx, hipMemcpy(pg.data(), P.prof_graph, pg.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-      std::vector<uint32_t> idx(n_graphs);
-      for (uint32_t g = 0; g < n_graphs; ++g) idx[g] = g;
-      const size_t top = std::min<size_t>(5, n_graphs);
-      std::partial_sort(idx.begin(), idx.begin() + top, idx.end(), [&](uint32_t a, uint32_t b) { return pg[9 * (size_t)a] > pg[9 * (size_t)b]; });
-      for (size_t t = 0; t < top; ++t) {
-        const unsigned long long* q = &pg[9 * (size_t)idx[t]];
-        fprintf(stderr, "[otg] poa profile: slow graph %u: %llu members on a backbone of %llu, threading %.1f us = %llu wide + %llu narrow + %llu serial chunks; %.1f us in the narrow + serial code (%llu steps taken as a retraced chain)\n",
-                idx[t], q[5] & 0xffffffffull, q[5] >> 32, q[0] / 100.0, q[1], q[2], q[3], (q[4] & ((1ull << 40) - 1ull)) / 100.0, q[4] >> 40);
-        fprintf(stderr, "[otg] poa profile:   its serial code: %llu windows without an 'M', %llu member heads, %llu others; ops taken one by one: %llu M, %llu X, %llu I, %llu D\n",
-                q[8] & 0xfffffull, (q[8] >> 20) & 0xfffffull, q[8] >> 40, q[6] & 0xffffffffull, q[6] >> 32, q[7] & 0xffffffffull, q[7] >> 32);
-      }
-    }
-  }
-  return OTG_OK;
+  std::vector<otg_poa_graph> h_graphs(n_graphs);
+  HIP_TRY(ctx, hipMemcpyAsync(h_graphs.data(), d_graphs, (size_t)n_graphs * sizeof(otg_poa_graph), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<uint64_t> node_off;
+  return otg_launch_poa(ctx, d_seq_arena, d_cig_arena, d_members, n_members, d_graphs, h_graphs.data(), n_graphs, d_out_len, node_off);
 }
