@@ -20,8 +20,11 @@
 // Pattern match masks (A, C, G, T + at most one further byte value occurring in the pattern, e.g. N) are derived from two bit-planes per
 // 64-row block (myers_masks.hpp) when a lane moves to its next superblock.  The pipeline's patterns are whole reads, each compared with
 // every other read of its region: their planes come from a table built once per run (read_masks_kernel; a task's first table block in the
-// side array `pblk`).  Every other pair — the operator-level calls, reads with a byte outside A C G T, the pipeline's reversed copies —
+// side array `pblk`; the reversed copies of the reassignment pass have theirs in a second region of the table, written as they are copied).
+// Every other pair — the operator-level calls, reads with a byte outside A C G T —
 // has them built by its wave into an L2-resident scratch before the sweep: per block one coalesced 64-byte load and one compare per symbol.
+// The text of a task with table blocks is read as row codes, one per arena byte, written with the table (`codes`); every other task
+// translates its text bytes through an LDS byte map.
 // Richer alphabets, text-side free ends and patterns > 16384 bytes go to the wavefront kernel.
 // The column step of a block (myers_step.hpp) works on 32-bit halves with three-input bit operations: what a vector instruction costs on
 // gfx950 depends on its class, and the tiers are bound by vector issue.
@@ -71,9 +74,12 @@ __global__ __launch_bounds__(WPB * 64, (BPL == 1 && GL == 8) ? 6 : 1) void myers
     int32_t* __restrict__ scores, uint64_t* __restrict__ cells,
     uint32_t* __restrict__ ticket, uint32_t* __restrict__ n_overflow, uint32_t* __restrict__ overflow_list,
     otg_myers::MaskBlock* __restrict__ peq_ws, int maxblk,
-    const uint32_t* __restrict__ pblk, const otg_myers::PlaneBlock* __restrict__ tab)
+    const uint32_t* __restrict__ pblk, const otg_myers::PlaneBlock* __restrict__ tab, const uint8_t* __restrict__ codes)
 {
   constexpr int G = 64 / GL;            // pairs per wave
+  // The text of a table task comes as row codes (one per arena byte, read_masks_kernel) instead of bytes.  The two whole-wave tiers stay on
+  // the byte map: they carry 0.1 ms of a step and take scalar spills with both paths in one kernel.
+  constexpr bool CODES = GL < 64;
   constexpr int SB = 64 * BPL;
   constexpr int NT = WPB * 64;
   // Match-mask table of the lane's CURRENT superblock: row (sym * BPL + q), column = thread; a lane only ever reads
@@ -102,8 +108,7 @@ __global__ __launch_bounds__(WPB * 64, (BPL == 1 && GL == 8) ? 6 : 1) void myers
 #pragma unroll
     for (int q = 0; q < BPL; ++q) EQ[(5 * BPL + q) * NT] = 0ull;
     for (int c = gl; c < 256; c += GL) {
-      const uint32_t code = ((uint32_t)c >> 1) & 3u;
-      LUT[c] = (uint8_t)(((uint32_t)c == ((0x47544341u >> (8 * code)) & 0xffu) ? code : 5u) * BPL * 8);
+      LUT[c] = (uint8_t)(otg_myers::text_row_code((uint32_t)c) * BPL);
     }
   }
   int lut_other = -1;                    // byte currently mapped to row 4 in this group's map
@@ -143,6 +148,9 @@ __global__ __launch_bounds__(WPB * 64, (BPL == 1 && GL == 8) ? 6 : 1) void myers
     // one pair after the other: lane r of the wave holds row r of the block, a compare against a symbol is the block's mask of that symbol
     const uint32_t tblk = (pblk && tab && !unsupported && !swapped) ? pblk[ti] : otg_myers::NO_MASKS;
     const bool use_tab = tblk != otg_myers::NO_MASKS;
+    // a table pattern has no extra symbol, so the row of a text byte is the same for every pair: read it from the code buffer
+    const bool use_codes = CODES && codes != nullptr && use_tab;
+    if (use_codes) T = codes + (T - arena);
     int other = -1;
     {
       const bool build = !unsupported && !use_tab;
@@ -223,10 +231,17 @@ __global__ __launch_bounds__(WPB * 64, (BPL == 1 && GL == 8) ? 6 : 1) void myers
       u64 x;
       if (a >= 0) x = load8(T + a);
       else { const int sh = -a; x = sh < 8 ? (load8(T) << (8 * sh)) : 0ull; }
+      Txt c;
+      if (use_codes) {
+        // x holds 8 codes (8 x row index, at most 40): times BPL a byte is the map entry of the other path, with no carry between bytes
+        const uint32_t lo = (uint32_t)x * (uint32_t)BPL, hi = (uint32_t)(x >> 32) * (uint32_t)BPL;
+        c.w[0] = __builtin_amdgcn_perm(lo, lo, 0x010c000cu); c.w[1] = __builtin_amdgcn_perm(lo, lo, 0x030c020cu);     // (byte 2i << 8) | (byte 2i+1 << 24)
+        c.w[2] = __builtin_amdgcn_perm(hi, hi, 0x010c000cu); c.w[3] = __builtin_amdgcn_perm(hi, hi, 0x030c020cu);
+        return c;
+      }
       uint32_t r[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) r[i] = LUT[(uint32_t)(x >> (8 * i)) & 0xffu];
-      Txt c;
 #pragma unroll
       for (int i = 0; i < 4; ++i) c.w[i] = __builtin_amdgcn_perm(r[2 * i + 1], r[2 * i], 0x040c000cu);       // (r[2i] << 8) | (r[2i+1] << 24)
       return c;
@@ -333,10 +348,10 @@ __global__ __launch_bounds__(WPB * 64, (BPL == 1 && GL == 8) ? 6 : 1) void myers
 // The per-read table: one wave per read, lane r holds row r of a block.  Block b of read i (64 bases from its CURRENT seq_off: realignment has
 // moved it by now) lands at tab[first_blk[i] + b]; first_blk was laid out from the submitted lengths, which realignment only shortens.  A read
 // with a byte outside A C G T, and a read outside every region (its range was never checked against the arena), gets NO_MASKS in read_blk:
-// its pairs build their masks themselves.  Blocks are kept by lane (b & 63) and stored 64 at a time.
+// its pairs build their masks themselves.  The read's row codes go to codes + seq_off (nullable).
 __global__ __launch_bounds__(256) void read_masks_kernel(const uint8_t* __restrict__ arena, const otg_read* __restrict__ reads, const uint32_t* __restrict__ read_region,
                                                          uint32_t n_reads, const uint32_t* __restrict__ first_blk, otg_myers::PlaneBlock* __restrict__ tab,
-                                                         uint32_t* __restrict__ read_blk)
+                                                         uint32_t* __restrict__ read_blk, uint8_t* __restrict__ codes)
 {
   const int lane = threadIdx.x & 63;
   const uint32_t nw = gridDim.x * (blockDim.x >> 6);
@@ -344,26 +359,8 @@ __global__ __launch_bounds__(256) void read_masks_kernel(const uint8_t* __restri
     if (read_region[i] == 0xffffffffu) { if (lane == 0) read_blk[i] = otg_myers::NO_MASKS; continue; }
     const uint8_t* const S = arena + reads[i].seq_off;
     const int m = (int)reads[i].seq_len;
-    const int nb = (m + 63) >> 6;
-    otg_myers::PlaneBlock* const out = tab + first_blk[i];
-    u64 flagged = 0, k0 = 0, k1 = 0;
-    for (int b4 = 0; b4 < nb; b4 += 4) {
-      uint32_t ch[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { const int j = ((b4 + k) << 6) + lane; ch[k] = j < m ? (uint32_t)S[j] : 0u; }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int b = b4 + k;
-        if (b >= nb) break;
-        const u64 rows = otg_myers::block_rows(m, b);
-        const uint32_t c = ch[k];
-        uint64_t rest;
-        const otg_myers::MaskBlock mk = otg_myers::block_planes([&](uint8_t v) { return __ballot(c == (uint32_t)v) & rows; }, rows, &rest);
-        flagged |= rest;
-        if (lane == (b & 63)) { k0 = mk.b0; k1 = mk.b1; }
-        if ((b & 63) == 63 || b == nb - 1) { if (lane <= (b & 63)) out[(b & ~63) + lane] = otg_myers::PlaneBlock{k0, k1}; }
-      }
-    }
+    if (codes) otg_myers::wave_read_codes<false>(S, m, lane, nullptr, codes + reads[i].seq_off);
+    const bool flagged = otg_myers::wave_read_planes([&](int j) { return S[j]; }, m, lane, tab + first_blk[i]);
     if (lane == 0) read_blk[i] = flagged ? otg_myers::NO_MASKS : first_blk[i];
   }
 }
@@ -371,7 +368,7 @@ __global__ __launch_bounds__(256) void read_masks_kernel(const uint8_t* __restri
 template <int BPL, int GL>
 int launch_one(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* d_tasks, const uint32_t* d_todo,
                const uint32_t* d_n_todo, uint32_t n_tasks, int32_t* d_scores, uint64_t* d_cells,
-               uint32_t* ticket, uint32_t* n_overflow, uint32_t* overflow_list, const uint32_t* d_pblk, const otg_myers::PlaneBlock* d_masks)
+               uint32_t* ticket, uint32_t* n_overflow, uint32_t* overflow_list, const uint32_t* d_pblk, const otg_myers::PlaneBlock* d_masks, const uint8_t* d_codes)
 {
   constexpr int WPB = 4, G = 64 / GL;
   int maxblk = (int)((ctx->max_seq_len + 63) / 64) + 1;
@@ -391,7 +388,7 @@ int launch_one(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* d_tas
   otg_myers::MaskBlock* ws = (otg_myers::MaskBlock*)otg_slot(ctx, SLOT_AUX8, (size_t)grid_max * WPB * 8 * (size_t)MAXBLK * sizeof(otg_myers::MaskBlock));   // up to 8 pairs per wave
   if (!ws) return OTG_ERR_HIP;
   hipLaunchKernelGGL((myers_edit_kernel<BPL, GL, WPB>), dim3(grid), dim3(WPB * 64), 0, ctx->stream, d_arena, d_tasks, d_todo, d_n_todo, n_tasks,
-                     d_scores, d_cells, ticket, n_overflow, overflow_list, ws, maxblk, d_pblk, d_masks);
+                     d_scores, d_cells, ticket, n_overflow, overflow_list, ws, maxblk, d_pblk, d_masks, d_codes);
   return OTG_OK;
 }
 
@@ -405,18 +402,18 @@ int launch_one(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* d_tas
 //       0.7 x the cost of <2,32>: a pair pays for the band of its tier, not for its own); last = whole wave x 4 blocks per lane.
 int otg_launch_myers(otg_ctx* ctx, int tier, const uint8_t* d_arena, const otg_align_task* d_tasks, const uint32_t* d_todo,
                      const uint32_t* d_n_todo, uint32_t n_tasks, int32_t* d_scores, uint64_t* d_cells,
-                     uint32_t* ticket, uint32_t* n_overflow, uint32_t* overflow_list, const uint32_t* d_pblk, const otg_myers::PlaneBlock* d_masks)
+                     uint32_t* ticket, uint32_t* n_overflow, uint32_t* overflow_list, const uint32_t* d_pblk, const otg_myers::PlaneBlock* d_masks, const uint8_t* d_codes)
 {
   int rc;
   switch (tier) {
-    case 0: rc = launch_one<1, 8>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks); break;
-    case 1: rc = launch_one<2, 8>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks); break;
-    case 2: rc = launch_one<3, 8>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks); break;
-    case 3: rc = launch_one<2, 16>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks); break;
-    case 4: rc = launch_one<3, 16>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks); break;
-    case 5: rc = launch_one<2, 32>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks); break;
-    case 6: rc = launch_one<2, 64>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks); break;
-    default: rc = launch_one<4, 64>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks); break;
+    case 0: rc = launch_one<1, 8>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks, d_codes); break;
+    case 1: rc = launch_one<2, 8>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks, d_codes); break;
+    case 2: rc = launch_one<3, 8>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks, d_codes); break;
+    case 3: rc = launch_one<2, 16>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks, d_codes); break;
+    case 4: rc = launch_one<3, 16>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks, d_codes); break;
+    case 5: rc = launch_one<2, 32>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks, d_codes); break;
+    case 6: rc = launch_one<2, 64>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks, d_codes); break;
+    default: rc = launch_one<4, 64>(ctx, d_arena, d_tasks, d_todo, d_n_todo, n_tasks, d_scores, d_cells, ticket, n_overflow, overflow_list, d_pblk, d_masks, d_codes); break;
   }
   if (rc) return rc;
   HIP_TRY(ctx, hipGetLastError());
@@ -426,11 +423,11 @@ int otg_launch_myers(otg_ctx* ctx, int tier, const uint8_t* d_arena, const otg_a
 // The per-read plane table of a resident batch (read_masks_kernel): d_first_blk[i] = first table block of read i, d_read_blk[i] = the same
 // or NO_MASKS on return.
 int otg_launch_read_masks(otg_ctx* ctx, const uint8_t* d_arena, const otg_read* d_reads, const uint32_t* d_read_region, uint32_t n_reads,
-                          const uint32_t* d_first_blk, otg_myers::PlaneBlock* d_masks, uint32_t* d_read_blk)
+                          const uint32_t* d_first_blk, otg_myers::PlaneBlock* d_masks, uint32_t* d_read_blk, uint8_t* d_codes)
 {
   if (n_reads == 0) return OTG_OK;
   const uint32_t grid = std::min<uint32_t>((n_reads + 3) / 4, (uint32_t)ctx->n_cu * 32);
-  hipLaunchKernelGGL(read_masks_kernel, dim3(grid), dim3(256), 0, ctx->stream, d_arena, d_reads, d_read_region, n_reads, d_first_blk, d_masks, d_read_blk);
+  hipLaunchKernelGGL(read_masks_kernel, dim3(grid), dim3(256), 0, ctx->stream, d_arena, d_reads, d_read_region, n_reads, d_first_blk, d_masks, d_read_blk, d_codes);
   HIP_TRY(ctx, hipGetLastError());
   return OTG_OK;
 }

@@ -297,18 +297,20 @@ constexpr int OTG_MYERS_TIERS = 8;
 // register-resident gap-affine tiers (wfa_affine_reg.hpp)
 constexpr int OTG_REG_TIERS = 5;
 // d_pblk / d_masks (both or neither): the per-read plane table of the batch (otg_launch_read_masks) and, per task slot, the first table block of
-// the task's pattern or 0xffffffff — the bit-parallel tiers then take such a pattern's match masks from the table (myers_masks.hpp)
+// the task's pattern or 0xffffffff — the bit-parallel tiers then take such a pattern's match masks from the table (myers_masks.hpp).
+// d_codes (nullable, only with the table): one row code per arena byte, written by otg_launch_read_masks for every read it covers; a task with
+// table blocks then reads its text from there
 namespace otg_myers { struct PlaneBlock; }
 int otg_launch_myers(otg_ctx* ctx, int tier, const uint8_t* d_arena, const otg_align_task* d_tasks, const uint32_t* d_todo,
                      const uint32_t* d_n_todo, uint32_t n_tasks, int32_t* d_scores, uint64_t* d_cells,
                      uint32_t* ticket, uint32_t* n_overflow, uint32_t* overflow_list,
-                     const uint32_t* d_pblk = nullptr, const otg_myers::PlaneBlock* d_masks = nullptr);
+                     const uint32_t* d_pblk = nullptr, const otg_myers::PlaneBlock* d_masks = nullptr, const uint8_t* d_codes = nullptr);
 int otg_launch_edit_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* d_tasks, const uint32_t* d_todo,
                          const uint32_t* d_n_todo, uint32_t n_task_slots, int32_t* d_scores, uint64_t* d_cells,
                          float* kernel_ms, uint64_t* launches,
-                         const uint32_t* d_pblk = nullptr, const otg_myers::PlaneBlock* d_masks = nullptr);
+                         const uint32_t* d_pblk = nullptr, const otg_myers::PlaneBlock* d_masks = nullptr, const uint8_t* d_codes = nullptr);
 int otg_launch_read_masks(otg_ctx* ctx, const uint8_t* d_arena, const otg_read* d_reads, const uint32_t* d_read_region, uint32_t n_reads,
-                          const uint32_t* d_first_blk, otg_myers::PlaneBlock* d_masks, uint32_t* d_read_blk);
+                          const uint32_t* d_first_blk, otg_myers::PlaneBlock* d_masks, uint32_t* d_read_blk, uint8_t* d_codes = nullptr);
 int otg_launch_affine_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* d_tasks, const uint32_t* d_todo,
                            const uint32_t* d_n_todo, uint32_t n_task_slots, int x, int o, int e, int32_t* d_scores,
                            const uint64_t* d_cig_off, uint32_t* d_cig_len, uint8_t* d_cig_arena, uint64_t* d_cells,

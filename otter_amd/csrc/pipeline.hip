@@ -42,6 +42,8 @@ struct Pipeline {
   std::vector<uint64_t> h_dist_off, h_re_off, h_cig_off;
   uint64_t n_pair_slots = 0, n_re_slots = 0, cig_bytes = 0;
   uint64_t n_mask_blocks = 0;             // 64-base blocks of the per-read plane table of the edit tiers (0: no table, OTG_EDIT_MASKS=0)
+  uint64_t n_rev_blocks = 0;              // blocks of its second region, behind those: the reversed copies of the reads that reassignment can mirror
+  bool text_codes = false;                // one row code per arena byte next to the table (OTG_EDIT_TEXT_CODES, default on; never without the table)
   uint32_t cl_nmax = 0;                   // upper bound of the valid reads of a clustered region (its read count)
   std::vector<uint32_t> cl_wide;          // regions whose read count exceeds the LDS scratch of the clustering kernel
   std::vector<DevBuf> buf;
@@ -59,7 +61,7 @@ enum {
   B_REDIST, B_RTASKS, B_RKIND, B_CIGLEN, B_CIG,
   B_ALLELES, B_GRAPHS, B_MEMBERS, B_POALEN,
   B_ALLEN, B_ALOFF, B_ALIDX, B_OUTSEQ, B_OUTAL, B_REGRES, B_SCAN_TMP, B_TOTALS,
-  B_MASKS, B_MASK_FIRST, B_MASK_READ, B_MASK_TASK,
+  B_MASKS, B_MASK_FIRST, B_MASK_READ, B_MASK_TASK, B_CODES, B_MASK_RFIRST, B_MASK_RREAD,
   B_COUNT
 };
 
@@ -141,11 +143,12 @@ __device__ int anreads_task(const uint8_t* arena, const otg_read& x, const otg_r
   return 0;
 }
 
-// first table block of a task's pattern (myers_masks.hpp): the pattern of every task above is a whole read, x or y; the reversed copies of the
-// mirrored tasks are not in the table
-__device__ uint32_t task_mask_block(const uint32_t* __restrict__ read_blk, const otg_align_task& t, const otg_read& x, uint32_t xi, const otg_read& y, uint32_t yi)
+// first table block of a task's pattern (myers_masks.hpp): the pattern of every task above is a whole read, x or y; that of a mirrored task
+// the reversed copy of the spanning read y, whose blocks K_reverse_reads wrote (rev_blk; null: no such blocks)
+__device__ uint32_t task_mask_block(const uint32_t* __restrict__ read_blk, const otg_align_task& t, const otg_read& x, uint32_t xi, const otg_read& y, uint32_t yi,
+                                    uint64_t rev_base = 0, const uint32_t* __restrict__ rev_blk = nullptr)
 {
-  if (t._pad & 1) return otg_myers::NO_MASKS;
+  if (t._pad & 1) return (rev_blk && t.pattern_off == rev_base + y.seq_off && t.pattern_len == y.seq_len) ? rev_blk[yi] : otg_myers::NO_MASKS;
   if (t.pattern_off == y.seq_off && t.pattern_len == y.seq_len) return read_blk[yi];
   if (t.pattern_off == x.seq_off && t.pattern_len == x.seq_len) return read_blk[xi];
   return otg_myers::NO_MASKS;
@@ -371,9 +374,15 @@ __global__ void K_scatter_labels(const uint32_t* __restrict__ read_region, const
 // ---- invalid_reassignment, task generation (src/analignments.cpp:129-157): slot(i,j) = re_off[r] + i*n + j
 // reversed copy (at + rev_base) of every read of a region that has reads to reassign: a non-spanning read that spans only the
 // right side is compared from the other end (see anreads_task)
-__global__ void K_reverse_reads(uint8_t* __restrict__ arena, const otg_read* __restrict__ reads, const otg_region* __restrict__ regions,
-                                const uint32_t* __restrict__ read_region, uint32_t n_reads, const int32_t* __restrict__ status,
-                                const uint32_t* __restrict__ n_valid, uint64_t rev_base)
+// One wave per read, eight bytes per lane (wave_read_codes).  In the same pass the reversed read gets what read_masks_kernel gives a forward one (myers_masks.hpp): its
+// plane blocks at tab[rev_first[i] + b] — the second region of the table, laid out at submit for the reads of every region that can have a
+// read to reassign — with rev_blk[i] = rev_first[i], or NO_MASKS for a read with a byte outside A C G T or without room there; and its row
+// codes at codes + rev_base + seq_off.  tab == nullptr: the copies alone.
+__global__ __launch_bounds__(256) void K_reverse_reads(uint8_t* __restrict__ arena, const otg_read* __restrict__ reads, const otg_region* __restrict__ regions,
+                                                       const uint32_t* __restrict__ read_region, uint32_t n_reads, const int32_t* __restrict__ status,
+                                                       const uint32_t* __restrict__ n_valid, uint64_t rev_base,
+                                                       const uint32_t* __restrict__ rev_first, otg_myers::PlaneBlock* __restrict__ tab,
+                                                       uint32_t* __restrict__ rev_blk, uint8_t* __restrict__ codes)
 {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t nw = gridDim.x * (blockDim.x >> 6);
@@ -383,7 +392,13 @@ __global__ void K_reverse_reads(uint8_t* __restrict__ arena, const otg_read* __r
     const otg_read rd = reads[i];
     const uint8_t* src = arena + rd.seq_off;
     uint8_t* dst = arena + rev_base + rd.seq_off;
-    for (uint32_t j = lane; j < rd.seq_len; j += 64) dst[j] = src[rd.seq_len - 1 - j];
+    const uint32_t len = rd.seq_len;
+    otg_myers::wave_read_codes<true>(src, (int)len, (int)lane, dst, (tab && codes) ? codes + rev_base + rd.seq_off : nullptr);
+    if (!tab) continue;
+    const uint32_t first = rev_first[i];
+    const bool flagged = otg_myers::wave_read_planes([&](int j) { return src[len - 1 - (uint32_t)j]; }, (int)len, (int)lane,
+                                                     first != otg_myers::NO_MASKS ? tab + first : nullptr);
+    if (lane == 0) rev_blk[i] = flagged ? otg_myers::NO_MASKS : first;
   }
 }
 
@@ -393,7 +408,7 @@ __global__ void K_reassign_tasks(const uint8_t* __restrict__ arena, const otg_re
                                  const uint64_t* __restrict__ re_off, otg_align_task* __restrict__ tasks,
                                  uint32_t* __restrict__ den, double* __restrict__ dist,
                                  uint32_t* __restrict__ todo, uint32_t* __restrict__ n_todo, uint64_t rev_base,
-                                 const uint32_t* __restrict__ read_blk, uint32_t* __restrict__ task_blk)
+                                 const uint32_t* __restrict__ read_blk, uint32_t* __restrict__ task_blk, const uint32_t* __restrict__ rev_blk)
 {
   for (uint32_t r = blockIdx.x; r < n_regions; r += gridDim.x) {
     if (status[r] != OTG_REGION_OK || fc[r] <= 0) continue;                            // fc == 0: `-a 0` defect, reference UB
@@ -416,7 +431,7 @@ __global__ void K_reassign_tasks(const uint8_t* __restrict__ arena, const otg_re
             uint32_t d = 1;
             if (anreads_task(arena, x, y, tasks[slot], &d, &known, rev_base)) {
               den[slot] = d; has = true;
-              if (task_blk) task_blk[slot] = task_mask_block(read_blk, tasks[slot], x, f + (uint32_t)i, y, f + (uint32_t)j);
+              if (task_blk) task_blk[slot] = task_mask_block(read_blk, tasks[slot], x, f + (uint32_t)i, y, f + (uint32_t)j, rev_base, rev_blk);
             }
             else dist[slot] = known;
           }
@@ -427,14 +442,21 @@ __global__ void K_reassign_tasks(const uint8_t* __restrict__ arena, const otg_re
   }
 }
 
-// ---- invalid_reassignment, decision (:134-175): sequential in read order, one thread per region
-__global__ void K_reassign_apply(const otg_read* __restrict__ reads, const otg_region* __restrict__ regions, uint32_t n_regions,
-                                 const int32_t* __restrict__ status, const uint32_t* __restrict__ n_valid,
-                                 const int32_t* __restrict__ fc, const uint64_t* __restrict__ re_off,
-                                 const double* __restrict__ dist, double min_sim, double max_error,
-                                 int32_t* __restrict__ labels, int32_t* __restrict__ status_out)
+// ---- invalid_reassignment, decision (:134-175): one wave per region.  The reads are decided one after the other, in read order — a label
+// given to read i makes it a target of the reads after it — and inside one read the lanes share the (label, target) terms: lane k holds the
+// targets k, k + 64, ..., and the best similarity of a label is a maximum over the wave.  Every quantity the decision needs is a maximum, a
+// minimum or a count of equalities of doubles, none of which depends on the order of the terms:
+//   max_val, max_label   the best similarity and the lowest label that reaches it
+//   same                 the labels that reach max_val
+//   min_diff             min(1, max_val - the best similarity of any other label); the subtraction is monotone, so the runner-up gives it
+__global__ __launch_bounds__(256) void K_reassign_apply(const otg_read* __restrict__ reads, const otg_region* __restrict__ regions, uint32_t n_regions,
+                                                        const int32_t* __restrict__ status, const uint32_t* __restrict__ n_valid,
+                                                        const int32_t* __restrict__ fc, const uint64_t* __restrict__ re_off,
+                                                        const double* __restrict__ dist, double min_sim, double max_error,
+                                                        int32_t* labels, int32_t* __restrict__ status_out)
 {
-  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = (int)(threadIdx.x & 63u);
+  const uint32_t r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (r >= n_regions || status[r] != OTG_REGION_OK) return;
   const otg_region rg = regions[r];
   const int n = (int)rg.n_reads;
@@ -442,37 +464,40 @@ __global__ void K_reassign_apply(const otg_read* __restrict__ reads, const otg_r
   const uint32_t f = rg.first_read;
   const int total = fc[r];
   if (total <= 0) return;
+  auto wave_max = [](double v) { for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_xor(v, off); v = o > v ? o : v; } return v; };
   for (int i = 0; i < n; ++i) {
     if (labels[f + i] >= 0) continue;
-    // max similarity per allele, first pass finds the best label, later passes the rest (no per-thread arrays)
-    int max_label = 0; double max_val = 0.0; int same = 0;
+    const double* const row = dist + re_off[r] + (uint64_t)i * n;
+    // the term of target j: its label and its distance to read i; label -1 where j is no target
+    auto term = [&](int j, double* d) -> int {
+      if (j >= n || j == i) return -1;
+      const int l = labels[f + j];
+      if (l < 0 || l >= total) return -1;
+      const otg_read& y = reads[f + j];
+      if (!(y.spanning_l && y.spanning_r)) return -1;
+      *d = row[j];
+      return l;
+    };
+    double d0 = 0.0;
+    const int lab0 = term(lane, &d0);
+    const double sim0 = 1 - d0;
+    bool neg = lab0 >= 0 && d0 < 0;                   // a distance below 0: an alignment that failed
+    for (int j = lane + 64; j < n; j += 64) { double d = 0.0; if (term(j, &d) >= 0 && d < 0) neg = true; }
+    if (__ballot(neg)) { if (lane == 0) status_out[r] = OTG_ERR_FATAL; return; }
+    int max_label = 0, same = 0; double max_val = 0.0, second = 0.0;      // second: the best similarity of the labels other than max_label
     for (int l = 0; l < total; ++l) {
-      double ms = 0.0;
-      for (int j = 0; j < n; ++j) {
-        if (j == i || labels[f + j] != l) continue;
-        const otg_read& y = reads[f + j];
-        if (!(y.spanning_l && y.spanning_r)) continue;
-        const double d = dist[re_off[r] + (uint64_t)i * n + j];
-        if (d < 0) { status_out[r] = OTG_ERR_FATAL; return; }
-        const double sim = 1 - d;
-        if (sim > ms) ms = sim;
-      }
-      if (l == 0 || ms > max_val) { max_val = ms; max_label = l; }
+      double ms = (lab0 == l && sim0 > 0.0) ? sim0 : 0.0;      // similarities below 0 never count: the maximum starts at 0
+      for (int j = lane + 64; j < n; j += 64) { double d = 0.0; if (term(j, &d) == l && 1 - d > ms) ms = 1 - d; }
+      ms = wave_max(ms);
+      if (l == 0 || ms > max_val) { if (l > 0) second = max_val; max_val = ms; max_label = l; same = 1; }
+      else { if (ms == max_val) ++same; if (ms > second) second = ms; }
     }
     double min_diff = 1.0;
-    for (int l = 0; l < total; ++l) {
-      double ms = 0.0;
-      for (int j = 0; j < n; ++j) {
-        if (j == i || labels[f + j] != l) continue;
-        const otg_read& y = reads[f + j];
-        if (!(y.spanning_l && y.spanning_r)) continue;
-        const double sim = 1 - dist[re_off[r] + (uint64_t)i * n + j];
-        if (sim > ms) ms = sim;
-      }
-      if (ms == max_val) ++same;
-      if (l != max_label) { const double diff = max_val - ms; if (diff < min_diff) min_diff = diff; }
+    if (total > 1) { const double diff = max_val - second; if (diff < min_diff) min_diff = diff; }
+    if (same == 1 && max_val >= min_sim && min_diff >= max_error) {
+      if (lane == 0) labels[f + i] = max_label;
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");          // the lanes read it as a target's label from the next read on
     }
-    if (same == 1 && max_val >= min_sim && min_diff >= max_error) labels[f + i] = max_label;
   }
 }
 
@@ -737,6 +762,30 @@ int otg_assemble_submit(otg_ctx* ctx, const otg_params* params, const uint8_t* s
     for (uint32_t i = 0; i < n_reads; ++i) { mask_first[i] = (uint32_t)nb; if (covered[i]) nb += ((uint64_t)reads[i].seq_len + 63) >> 6; if (nb >= 0xffffffffull) break; }
     pl->n_mask_blocks = nb < 0xffffffffull ? nb : 0;       // (a batch beyond 2^32 blocks — 256 GB of reads — runs without the table)
   }
+  // second region of the table: the reversed copies K_reverse_reads makes, i.e. the reads of the regions that can have a read to reassign
+  // (n_valid < n_reads).  Realignment only turns one-sided reads into spanning ones, so a region whose submitted reads are all valid stays
+  // without; without the haplotags a valid read is a spanning one, with them a tagged spanning one (K_region_prepare).
+  std::vector<uint32_t> rev_first(n_reads, otg_myers::NO_MASKS);
+  pl->n_rev_blocks = 0;
+  if (pl->n_mask_blocks) {
+    uint64_t nb = pl->n_mask_blocks;
+    for (uint32_t r = 0; r < n_regions && nb < 0xffffffffull; ++r) {
+      const otg_region& g = regions[r];
+      bool all_valid = true;
+      for (uint32_t i = 0; i < g.n_reads && all_valid; ++i) {
+        const otg_read& q = reads[g.first_read + i];
+        all_valid = q.spanning_l && q.spanning_r && (params->ignore_haps || (q.ps >= 0 && q.hp >= 0));
+      }
+      if (all_valid) continue;
+      for (uint32_t i = 0; i < g.n_reads; ++i) { rev_first[g.first_read + i] = (uint32_t)nb; nb += ((uint64_t)reads[g.first_read + i].seq_len + 63) >> 6; }
+    }
+    if (nb < 0xffffffffull) pl->n_rev_blocks = nb - pl->n_mask_blocks;
+    else std::fill(rev_first.begin(), rev_first.end(), otg_myers::NO_MASKS);      // (no room below 2^32 blocks: the mirrored tasks build their masks)
+  }
+  // the text side of a table task: its row codes, one byte per arena byte (the 64 bytes past the end are read like the arena's, never used).
+  // OTG_EDIT_TEXT_CODES=0: every task translates its text through the byte map.
+  static const bool edit_text_codes = otg_env_int("OTG_EDIT_TEXT_CODES", 1) != 0;
+  pl->text_codes = edit_text_codes && pl->n_mask_blocks != 0;
   if (pl->n_pair_slots >= 0xffffffffull || pl->n_re_slots >= 0xffffffffull)
     return otg_fail(ctx, OTG_ERR_CAPACITY, "batch too large: split it (pair slots %llu, reassignment slots %llu)", (unsigned long long)pl->n_pair_slots, (unsigned long long)pl->n_re_slots);
   ctx->max_seq_len = maxlen;
@@ -756,6 +805,9 @@ int otg_assemble_submit(otg_ctx* ctx, const otg_params* params, const uint8_t* s
     void* d_mf = pbuf(ctx, pl, B_MASK_FIRST, (size_t)n_reads * 4);
     if (!d_mf) return OTG_ERR_HIP;
     HIP_TRY(ctx, hipMemcpyAsync(d_mf, mask_first.data(), (size_t)n_reads * 4, hipMemcpyHostToDevice, ctx->stream));
+    void* d_rf = pbuf(ctx, pl, B_MASK_RFIRST, (size_t)n_reads * 4);
+    if (!d_rf) return OTG_ERR_HIP;
+    HIP_TRY(ctx, hipMemcpyAsync(d_rf, rev_first.data(), (size_t)n_reads * 4, hipMemcpyHostToDevice, ctx->stream));
   }
   HIP_TRY(ctx, hipMemsetAsync(d_arena + arena_bytes, 0, 64, ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(d_arena + pl->rev_base + arena_bytes, 0, 64, ctx->stream));
@@ -784,9 +836,11 @@ int otg_assemble_submit(otg_ctx* ctx, const otg_params* params, const uint8_t* s
       !pbuf(ctx, pl, B_SCAN_TMP, (size_t)n_reads * 4 + 4) || !pbuf(ctx, pl, B_TOTALS, 64) || !pbuf(ctx, pl, B_REGRES, (size_t)(n_regions + 1) * sizeof(otg_region_result)) ||
       !otg_slot(ctx, SLOT_AUX9, (pl->n_pair_slots + 1) * 8))
     return OTG_ERR_HIP;
-  if (pl->n_mask_blocks && (!pbuf(ctx, pl, B_MASKS, (size_t)pl->n_mask_blocks * sizeof(otg_myers::PlaneBlock)) || !pbuf(ctx, pl, B_MASK_READ, (size_t)n_reads * 4) ||
+  if (pl->n_mask_blocks && (!pbuf(ctx, pl, B_MASKS, (size_t)(pl->n_mask_blocks + pl->n_rev_blocks) * sizeof(otg_myers::PlaneBlock)) || !pbuf(ctx, pl, B_MASK_READ, (size_t)n_reads * 4) ||
+                            !pbuf(ctx, pl, B_MASK_RREAD, (size_t)n_reads * 4) ||
                             !pbuf(ctx, pl, B_MASK_TASK, ntask * 4)))
     return OTG_ERR_HIP;
+  if (pl->text_codes && !pbuf(ctx, pl, B_CODES, (size_t)pl->rev_base + arena_bytes + 64)) return OTG_ERR_HIP;      // parallel to both halves of the arena
   return OTG_OK;
 }
 
@@ -880,6 +934,7 @@ static int assemble_run_body(otg_ctx* ctx, bool realign_only)
   otg_myers::PlaneBlock* d_masks = masks ? (otg_myers::PlaneBlock*)B(B_MASKS) : nullptr;
   uint32_t* d_read_blk = masks ? (uint32_t*)B(B_MASK_READ) : nullptr;
   uint32_t* d_task_blk = masks ? (uint32_t*)B(B_MASK_TASK) : nullptr;
+  uint8_t* d_codes = masks && pl->text_codes ? (uint8_t*)B(B_CODES) : nullptr;
   memset(&pl->stats, 0, sizeof(pl->stats));
   pl->ran = false;               // a run that fails below must not leave the previous run's results collectable
   pl->out_alleles = 0; pl->out_seq_bytes = 0;
@@ -919,15 +974,15 @@ static int assemble_run_body(otg_ctx* ctx, bool realign_only)
   {
     Timer t(ctx);
     hipLaunchKernelGGL(K_region_prepare, dim3(gr_regions), dim3(TB), 0, st, d_reads, d_regions, NG, P.max_cov, P.ignore_haps, d_status, d_nvalid, d_ign, d_valid, d_vpos, d_vlen);
-    if (d_masks) {           // the reads are final from here on: their planes, once for both edit passes
-      rc = otg_launch_read_masks(ctx, d_arena, d_reads, d_rr, NR, (const uint32_t*)B(B_MASK_FIRST), d_masks, d_read_blk);
+    if (d_masks) {           // the reads are final from here on: their planes and row codes, once for both edit passes
+      rc = otg_launch_read_masks(ctx, d_arena, d_reads, d_rr, NR, (const uint32_t*)B(B_MASK_FIRST), d_masks, d_read_blk, d_codes);
       if (rc) return rc;
     }
     hipLaunchKernelGGL(K_pair_tasks, dim3(gr_blocks), dim3(64), 0, st, d_arena, d_reads, d_regions, NG, d_nvalid, d_ign, d_valid, (const uint64_t*)B(B_DIST_OFF), P.max_alleles, d_tasks, d_den, d_dist, d_todo, d_cnt + 20,
                        (const uint32_t*)d_read_blk, d_task_blk);
     float kms = 0; uint64_t kl = 0;
     dbg(ctx, "pair tasks done");
-    rc = otg_launch_edit_todo(ctx, d_arena, d_tasks, d_todo, d_cnt + 20, (uint32_t)pl->n_pair_slots, d_scores, d_cells, &kms, &kl, d_task_blk, d_masks);
+    rc = otg_launch_edit_todo(ctx, d_arena, d_tasks, d_todo, d_cnt + 20, (uint32_t)pl->n_pair_slots, d_scores, d_cells, &kms, &kl, d_task_blk, d_masks, d_codes);
     if (rc) return rc;
     pl->stats.ms_edit_kernel += kms; pl->stats.edit_kernel_launches += kl;
     hipLaunchKernelGGL(K_dist_epilogue, dim3(1024), dim3(256), 0, st, d_todo, d_cnt + 20, d_scores, d_den, d_dist, d_cnt + 40);
@@ -951,19 +1006,20 @@ static int assemble_run_body(otg_ctx* ctx, bool realign_only)
     static const bool no_rev = otg_env_set("OTG_NO_REASSIGN_REV");
     // (under the adaptive heuristic an alignment and its mirror image are different computations: no reversed copies there)
     const uint64_t rev_base = (no_rev || ctx->heur_strategy != OTG_HEURISTIC_NONE) ? 0 : pl->rev_base;
+    uint32_t* d_rev_blk = d_masks ? (uint32_t*)B(B_MASK_RREAD) : nullptr;
     if (rev_base) hipLaunchKernelGGL(K_reverse_reads, dim3(std::min<uint32_t>((NR + 3) / 4, (uint32_t)ctx->n_cu * 32)), dim3(256), 0, st, d_arena, d_reads, d_regions, d_rr, NR,
-                                     d_status, d_nvalid, rev_base);
+                                     d_status, d_nvalid, rev_base, (const uint32_t*)B(B_MASK_RFIRST), d_masks, d_rev_blk, d_codes);
     hipLaunchKernelGGL(K_reassign_tasks, dim3(gr_blocks), dim3(64), 0, st, d_arena, d_reads, d_regions, NG, d_status, d_nvalid, (const int32_t*)B(B_FC), d_labels,
-                       (const uint64_t*)B(B_RE_OFF), d_tasks, d_den, d_redist, d_todo, d_cnt + 24, rev_base, (const uint32_t*)d_read_blk, d_task_blk);
+                       (const uint64_t*)B(B_RE_OFF), d_tasks, d_den, d_redist, d_todo, d_cnt + 24, rev_base, (const uint32_t*)d_read_blk, d_task_blk, (const uint32_t*)d_rev_blk);
     float kms = 0; uint64_t kl = 0;
     ctx->edit_pass_kind = 1;
-    rc = otg_launch_edit_todo(ctx, d_arena, d_tasks, d_todo, d_cnt + 24, (uint32_t)pl->n_re_slots, d_scores, d_cells, &kms, &kl, d_task_blk, d_masks);
+    rc = otg_launch_edit_todo(ctx, d_arena, d_tasks, d_todo, d_cnt + 24, (uint32_t)pl->n_re_slots, d_scores, d_cells, &kms, &kl, d_task_blk, d_masks, d_codes);
     ctx->edit_pass_kind = 0;
     if (rc) return rc;
     pl->stats.ms_edit_kernel += kms; pl->stats.edit_kernel_launches += kl;
     hipLaunchKernelGGL(K_dist_epilogue, dim3(1024), dim3(256), 0, st, d_todo, d_cnt + 24, d_scores, d_den, d_redist, d_cnt + 40);
     hipLaunchKernelGGL(K_stats, dim3(64), dim3(256), 0, st, d_todo, d_cnt + 24, d_tasks, d_cells, d_stats + 0, d_scores, d_cnt + 40);
-    hipLaunchKernelGGL(K_reassign_apply, dim3((NG + 63) / 64), dim3(64), 0, st, d_reads, d_regions, NG, d_status, d_nvalid, (const int32_t*)B(B_FC),
+    hipLaunchKernelGGL(K_reassign_apply, dim3((NG + 3) / 4), dim3(256), 0, st, d_reads, d_regions, NG, d_status, d_nvalid, (const int32_t*)B(B_FC),
                        (const uint64_t*)B(B_RE_OFF), d_redist, P.min_sim, P.max_error, d_labels, d_status);
     pl->stats.ms_reassign = t.ms();
   }

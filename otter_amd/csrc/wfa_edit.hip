@@ -497,7 +497,7 @@ int otg_launch_edit(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* 
 // then the number of task SLOTS (upper bound, sizes the overflow lists and the grid).
 int otg_launch_edit_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_task* d_tasks, const uint32_t* d_todo,
                          const uint32_t* d_n_todo, uint32_t n_tasks, int32_t* d_scores, uint64_t* d_cells,
-                         float* kernel_ms, uint64_t* launches, const uint32_t* d_pblk, const otg_myers::PlaneBlock* d_masks)
+                         float* kernel_ms, uint64_t* launches, const uint32_t* d_pblk, const otg_myers::PlaneBlock* d_masks, const uint8_t* d_codes)
 {
   if (n_tasks == 0) return OTG_OK;
   if (ctx->heur_strategy == OTG_HEURISTIC_WFADAPTIVE)
@@ -586,7 +586,7 @@ int otg_launch_edit_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align_t
         in = sorted;
       }
       const int rc_ = otg_launch_myers(ctx, tier, d_arena, d_tasks, in, rc + tier, n_tasks, d_scores, d_cells,
-                                       &cnt->tier_ticket[tier], rc + next, lists + (size_t)next * n_tasks, d_pblk, d_masks);
+                                       &cnt->tier_ticket[tier], rc + next, lists + (size_t)next * n_tasks, d_pblk, d_masks, d_codes);
       if (rc_) return rc_;
     }
   }
