@@ -236,20 +236,16 @@ class Context:
         """otg_kmer_usage_batch: per allele the 4^k+1 k-mer frequencies of vcf2mat, its GC fraction and Hill-Shannon diversity ->
         (usage [n, 4^k+1] float64, gc [n], hsd [n]) as numpy arrays, or with device_tensor=True as float64 torch tensors on this context's
         device that wrap the results in HBM without a copy (valid until the next kmer_usage_batch on this context)."""
-        arena = np.ascontiguousarray(arena, dtype=np.uint8)
-        off = np.ascontiguousarray(seq_off, dtype=np.uint64)
-        ln = np.ascontiguousarray(seq_len, dtype=np.uint32)
+        rows, ln = _rows(arena, seq_off, seq_len)
         n, bins = len(ln), 4 ** int(k) + 1
         if device_tensor:
-            rc = self._L.otg_kmer_usage_batch(self._h, abi.ptr(arena), C.c_uint64(arena.size), abi.ptr(off), abi.ptr(ln), C.c_uint32(n),
-                                              C.c_int32(k), None, None, None)
+            rc = self._L.otg_kmer_usage_batch(self._h, *rows, C.c_int32(k), None, None, None)
             self._check(rc, "otg_kmer_usage_batch")
             return self._kmer_device_results(n, k)
         usage = np.zeros((n, bins), dtype=np.float64)
         gc = np.zeros(n, dtype=np.float64)
         hsd = np.zeros(n, dtype=np.float64)
-        rc = self._L.otg_kmer_usage_batch(self._h, abi.ptr(arena), C.c_uint64(arena.size), abi.ptr(off), abi.ptr(ln), C.c_uint32(n), C.c_int32(k),
-                                          abi.ptr(usage), abi.ptr(gc), abi.ptr(hsd))
+        rc = self._L.otg_kmer_usage_batch(self._h, *rows, C.c_int32(k), abi.ptr(usage), abi.ptr(gc), abi.ptr(hsd))
         self._check(rc, "otg_kmer_usage_batch")
         return usage, gc, hsd
 
@@ -276,9 +272,7 @@ class Context:
 
     def kmer_usage_last_ms(self):
         """(counting ms, epilogue ms) of the latest kmer_usage_batch (HIP events; k <= 7 counts and finishes in one kernel)."""
-        a, b = C.c_double(0), C.c_double(0)
-        self._check(self._L.otg_kmer_usage_last_ms(self._h, C.byref(a), C.byref(b)), "otg_kmer_usage_last_ms")
-        return a.value, b.value
+        return self._last_ms("otg_kmer_usage_last_ms", 2)
 
     def motif_batch(self, arena, seq_off, seq_len, max_period=256, slack=50, device_tensor=False):
         """otg_motif_batch: per allele the tandem-repeat period, match counts and unit (include/otter_gpu.h states the rule) ->
@@ -286,15 +280,12 @@ class Context:
         stride = max(1, min(max_period, longest allele // 2)); or with device_tensor=True as torch tensors on this context's device that wrap
         the results in HBM without a copy (records as int32 [n, 6] in the field order of abi.motif_dt, units as uint8 [n, stride]; valid
         until the next motif call on this context)."""
-        arena = np.ascontiguousarray(arena, dtype=np.uint8)
-        off = np.ascontiguousarray(seq_off, dtype=np.uint64)
-        ln = np.ascontiguousarray(seq_len, dtype=np.uint32)
+        rows, ln = _rows(arena, seq_off, seq_len)
         n = len(ln)
         stride = max(1, min(int(max_period), int(ln.max()) // 2 if n else 0))
         rec = np.zeros(n, dtype=abi.motif_dt)
         units = np.zeros((n, stride), dtype=np.uint8)
-        rc = self._L.otg_motif_batch(self._h, abi.ptr(arena), C.c_uint64(arena.size), abi.ptr(off), abi.ptr(ln), C.c_uint32(n),
-                                     C.c_uint32(max_period), C.c_uint32(slack), None if device_tensor else abi.ptr(rec),
+        rc = self._L.otg_motif_batch(self._h, *rows, C.c_uint32(max_period), C.c_uint32(slack), None if device_tensor else abi.ptr(rec),
                                      None if device_tensor else abi.ptr(units), C.c_uint32(stride))
         self._check(rc, "otg_motif_batch")
         return self._motif_device_results(n, stride) if device_tensor else (rec, units)
@@ -311,57 +302,60 @@ class Context:
 
     def motif_last_ms(self):
         """(pack and match-count ms, reduce and unit ms) of the latest motif call on this context (HIP events)."""
-        a, b = C.c_double(0), C.c_double(0)
-        self._check(self._L.otg_motif_last_ms(self._h, C.byref(a), C.byref(b)), "otg_motif_last_ms")
-        return a.value, b.value
+        return self._last_ms("otg_motif_last_ms", 2)
 
     def repeat_batch(self, arena, seq_off, seq_len, max_period=256, min_copies=2, min_span=12, device_tensor=False):
         """otg_repeat_batch (and otg_repeat_collect): per allele its structure as exact tandem repeats and literals (include/otter_gpu.h states
         the rule) -> (sums [n] of abi.repeat_sum_dt, seg_off [n + 1] uint64, segs [total] of abi.repeat_seg_dt; the segments of allele i are
         segs[seg_off[i]:seg_off[i + 1]]) as numpy arrays; or with device_tensor=True as torch tensors on this context's device that wrap the
         results in HBM without a copy (int32 [n, 4], int64 [n + 1], int32 [total, 4]; valid until the next repeat call on this context)."""
-        arena = np.ascontiguousarray(arena, dtype=np.uint8)
-        off = np.ascontiguousarray(seq_off, dtype=np.uint64)
-        ln = np.ascontiguousarray(seq_len, dtype=np.uint32)
-        n = len(ln)
-        return self._repeat_results(n, device_tensor, lambda sums, seg_off, total: self._L.otg_repeat_batch(
-            self._h, abi.ptr(arena), C.c_uint64(arena.size), abi.ptr(off), abi.ptr(ln), C.c_uint32(n), C.c_uint32(max_period), C.c_uint32(min_copies),
-            C.c_uint32(min_span), sums, seg_off, total), "otg_repeat_batch")
+        rows, ln = _rows(arena, seq_off, seq_len)
+        return self._seg_results("repeat", len(ln), device_tensor, lambda sums, seg_off, total: self._L.otg_repeat_batch(
+            self._h, *rows, C.c_uint32(max_period), C.c_uint32(min_copies), C.c_uint32(min_span), sums, seg_off, total), "otg_repeat_batch")
 
-    def _repeat_results(self, n, device_tensor, call, who):
+    def _seg_results(self, kind, n, device_tensor, call, who):
+        """the results of an operator with segments ("repeat", "unitparse"): call(sums, seg_off, total) is its entry `who` on the C arguments of
+        the three; -> (sums [n], seg_off [n + 1], segs [total]) as numpy arrays of its record types, or as int32 / int64 device tensors"""
+        sum_dt, seg_dt = _SEG_TYPES[kind]
+        sum_w, seg_w = sum_dt.itemsize // 4, seg_dt.itemsize // 4
         total = C.c_uint64(0)
         if device_tensor:
             self._check(call(None, None, C.byref(total)), who)
             if n == 0:
                 import torch
                 dev = torch.device("cuda", self.device)
-                return (torch.zeros((0, 4), dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
-                        torch.zeros((0, 4), dtype=torch.int32, device=dev))
+                return (torch.zeros((0, sum_w), dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
+                        torch.zeros((0, seg_w), dtype=torch.int32, device=dev))
             m, t, ps, po, pg = C.c_uint32(0), C.c_uint64(0), C.c_void_p(), C.c_void_p(), C.c_void_p()
-            self._check(self._L.otg_repeat_device_results(self._h, C.byref(m), C.byref(ps), C.byref(po), C.byref(pg), C.byref(t)), "otg_repeat_device_results")
+            entry = "otg_%s_device_results" % kind
+            self._check(getattr(self._L, entry)(self._h, C.byref(m), C.byref(ps), C.byref(po), C.byref(pg), C.byref(t)), entry)
             assert (m.value, t.value) == (n, total.value)
-            return self._wrap_device(ps.value, (n, 4), "<i4"), self._wrap_device(po.value, (n + 1,), "<i8"), self._wrap_device(pg.value, (t.value, 4), "<i4")
-        sums = np.zeros(n, dtype=abi.repeat_sum_dt)
+            return (self._wrap_device(ps.value, (n, sum_w), "<i4"), self._wrap_device(po.value, (n + 1,), "<i8"),
+                    self._wrap_device(pg.value, (t.value, seg_w), "<i4"))
+        sums = np.zeros(n, dtype=sum_dt)
         seg_off = np.zeros(n + 1, dtype=np.uint64)
         self._check(call(abi.ptr(sums), abi.ptr(seg_off), C.byref(total)), who)
-        segs = np.zeros(total.value, dtype=abi.repeat_seg_dt)
+        segs = np.zeros(total.value, dtype=seg_dt)
         if n and total.value:
-            self._check(self._L.otg_repeat_collect(self._h, abi.ptr(segs), C.c_uint64(total.value)), "otg_repeat_collect")
+            entry = "otg_%s_collect" % kind
+            self._check(getattr(self._L, entry)(self._h, abi.ptr(segs), C.c_uint64(total.value)), entry)
         return sums, seg_off, segs
+
+    def _last_ms(self, entry, n_values):
+        """the n_values HIP-event times the entry reports of the latest call of its operator on this context"""
+        ms = [C.c_double(0) for _ in range(n_values)]
+        self._check(getattr(self._L, entry)(self._h, *[C.byref(x) for x in ms]), entry)
+        return tuple(x.value for x in ms) if n_values > 1 else ms[0].value
 
     def repeat_last_ms(self):
         """(runs ms, select ms) of the latest repeat call on this context (HIP events)."""
-        a, b = C.c_double(0), C.c_double(0)
-        self._check(self._L.otg_repeat_last_ms(self._h, C.byref(a), C.byref(b)), "otg_repeat_last_ms")
-        return a.value, b.value
+        return self._last_ms("otg_repeat_last_ms", 2)
 
     def unitalign_batch(self, arena, seq_off, seq_len, units, task_seq, task_unit, device_tensor=False):
         """otg_unitalign_batch: allele task_seq[t] aligned to the cyclic repeat unit units[task_unit[t]] (a list of byte strings; include/otter_gpu.h
         states the rule) -> records [n_tasks] of abi.unitalign_dt as a numpy array; or with device_tensor=True an int32 [n_tasks, 4] torch tensor
         on this context's device that wraps the records in HBM without a copy (valid until the next unit alignment on this context)."""
-        arena = np.ascontiguousarray(arena, dtype=np.uint8)
-        off = np.ascontiguousarray(seq_off, dtype=np.uint64)
-        ln = np.ascontiguousarray(seq_len, dtype=np.uint32)
+        rows, ln = _rows(arena, seq_off, seq_len)
         uarena, uoff, ulen = _pack_units(units)
         ts = np.ascontiguousarray(task_seq, dtype=np.uint32)
         tu = np.ascontiguousarray(task_unit, dtype=np.uint32)
@@ -369,8 +363,7 @@ class Context:
             raise ValueError("task_seq and task_unit differ in length")
         n = len(ts)
         out = np.zeros(n, dtype=abi.unitalign_dt)
-        rc = self._L.otg_unitalign_batch(self._h, abi.ptr(arena), C.c_uint64(arena.size), abi.ptr(off), abi.ptr(ln), C.c_uint32(len(ln)), abi.ptr(uarena),
-                                         C.c_uint64(int(ulen.sum())), abi.ptr(uoff), abi.ptr(ulen), C.c_uint32(len(ulen)), abi.ptr(ts), abi.ptr(tu), C.c_uint32(n),
+        rc = self._L.otg_unitalign_batch(self._h, *rows, abi.ptr(uarena), C.c_uint64(int(ulen.sum())), abi.ptr(uoff), abi.ptr(ulen), C.c_uint32(len(ulen)), abi.ptr(ts), abi.ptr(tu), C.c_uint32(n),
                                          None if device_tensor else abi.ptr(out))
         self._check(rc, "otg_unitalign_batch")
         return self._unitalign_device_results(n) if device_tensor else out
@@ -396,9 +389,7 @@ class Context:
 
     def unitalign_last_ms(self):
         """binning and alignment ms of the latest unit alignment on this context (HIP events)."""
-        a = C.c_double(0)
-        self._check(self._L.otg_unitalign_last_ms(self._h, C.byref(a)), "otg_unitalign_last_ms")
-        return a.value
+        return self._last_ms("otg_unitalign_last_ms", 1)
 
     def unitparse_batch(self, arena, seq_off, seq_len, unit_sets, task_seq, task_set, device_tensor=False):
         """otg_unitparse_batch (and otg_unitparse_collect): allele task_seq[t] parsed against the unit set unit_sets[task_set[t]] (a list of lists
@@ -406,40 +397,14 @@ class Context:
         of abi.unitparse_seg_dt; the segments of task t are segs[seg_off[t]:seg_off[t + 1]]) as numpy arrays; or with device_tensor=True as torch
         tensors on this context's device that wrap the results in HBM without a copy (int32 [n, 8], int64 [n + 1], int32 [total, 6]; valid until
         the next unit parse on this context)."""
-        arena = np.ascontiguousarray(arena, dtype=np.uint8)
-        off = np.ascontiguousarray(seq_off, dtype=np.uint64)
-        ln = np.ascontiguousarray(seq_len, dtype=np.uint32)
+        rows, ln = _rows(arena, seq_off, seq_len)
         sets, ts, tq = _pack_unit_sets(unit_sets, task_seq, task_set)
-        return self._unitparse_results(len(ts), device_tensor, lambda sums, seg_off, total: self._L.otg_unitparse_batch(
-            self._h, abi.ptr(arena), C.c_uint64(arena.size), abi.ptr(off), abi.ptr(ln), C.c_uint32(len(ln)), *sets, abi.ptr(ts), abi.ptr(tq), C.c_uint32(len(ts)),
-            sums, seg_off, total), "otg_unitparse_batch")
-
-    def _unitparse_results(self, n, device_tensor, call, who):
-        total = C.c_uint64(0)
-        if device_tensor:
-            self._check(call(None, None, C.byref(total)), who)
-            if n == 0:
-                import torch
-                dev = torch.device("cuda", self.device)
-                return (torch.zeros((0, 8), dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
-                        torch.zeros((0, 6), dtype=torch.int32, device=dev))
-            m, t, ps, po, pg = C.c_uint32(0), C.c_uint64(0), C.c_void_p(), C.c_void_p(), C.c_void_p()
-            self._check(self._L.otg_unitparse_device_results(self._h, C.byref(m), C.byref(ps), C.byref(po), C.byref(pg), C.byref(t)), "otg_unitparse_device_results")
-            assert (m.value, t.value) == (n, total.value)
-            return self._wrap_device(ps.value, (n, 8), "<i4"), self._wrap_device(po.value, (n + 1,), "<i8"), self._wrap_device(pg.value, (t.value, 6), "<i4")
-        sums = np.zeros(n, dtype=abi.unitparse_sum_dt)
-        seg_off = np.zeros(n + 1, dtype=np.uint64)
-        self._check(call(abi.ptr(sums), abi.ptr(seg_off), C.byref(total)), who)
-        segs = np.zeros(total.value, dtype=abi.unitparse_seg_dt)
-        if n and total.value:
-            self._check(self._L.otg_unitparse_collect(self._h, abi.ptr(segs), C.c_uint64(total.value)), "otg_unitparse_collect")
-        return sums, seg_off, segs
+        return self._seg_results("unitparse", len(ts), device_tensor, lambda sums, seg_off, total: self._L.otg_unitparse_batch(
+            self._h, *rows, *sets, abi.ptr(ts), abi.ptr(tq), C.c_uint32(len(ts)), sums, seg_off, total), "otg_unitparse_batch")
 
     def unitparse_last_ms(self):
         """(forward ms, traceback ms) of the latest unit parse on this context (HIP events)."""
-        a, b = C.c_double(0), C.c_double(0)
-        self._check(self._L.otg_unitparse_last_ms(self._h, C.byref(a), C.byref(b)), "otg_unitparse_last_ms")
-        return a.value, b.value
+        return self._last_ms("otg_unitparse_last_ms", 2)
 
     def affine_align_batch(self, arena, tasks, x=4, o=6, e=2, want_cells=False):
         n = len(tasks)
@@ -789,7 +754,7 @@ class Context:
             self._check(self._L.otg_kmer_cohort_rows(self._h, C.byref(total), None, None, None), "otg_kmer_cohort_rows")
             n = max(0, total.value - int(row_begin))
         n = int(n)
-        return self._repeat_results(n, device_tensor, lambda sums, seg_off, total: self._L.otg_repeat_cohort(
+        return self._seg_results("repeat", n, device_tensor, lambda sums, seg_off, total: self._L.otg_repeat_cohort(
             self._h, C.c_uint32(row_begin), C.c_uint32(n), C.c_uint32(max_period), C.c_uint32(min_copies), C.c_uint32(min_span), sums, seg_off, total),
             "otg_repeat_cohort")
 
@@ -827,7 +792,7 @@ class Context:
             n = max(0, total.value - int(row_begin))
         n = int(n)
         sets, ts, tq = _pack_unit_sets(unit_sets, task_seq, task_set)
-        return self._unitparse_results(len(ts), device_tensor, lambda sums, seg_off, total: self._L.otg_unitparse_cohort(
+        return self._seg_results("unitparse", len(ts), device_tensor, lambda sums, seg_off, total: self._L.otg_unitparse_cohort(
             self._h, C.c_uint32(row_begin), C.c_uint32(n), *sets, abi.ptr(ts), abi.ptr(tq), C.c_uint32(len(ts)), sums, seg_off, total), "otg_unitparse_cohort")
 
     def cohort_end(self):
@@ -1648,6 +1613,18 @@ def repeats_files(vcf, bed, max_period=256, min_copies=2, min_span=12, threads=1
     job.max_period = max_period; job.min_copies = min_copies; job.min_span = min_span
     job.threads = threads; job.device = device; job.batch_alleles = batch_alleles
     return _run_files_job("otg_repeats_files", job, abi.RepeatsJob)
+
+
+_SEG_TYPES = {"repeat": (abi.repeat_sum_dt, abi.repeat_seg_dt), "unitparse": (abi.unitparse_sum_dt, abi.unitparse_seg_dt)}
+
+
+def _rows(arena, seq_off, seq_len):
+    """an operator's rows -> (the five leading arguments of its *_batch entry: arena, its bytes, offsets, lengths, their number; the lengths
+    as a uint32 array)"""
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+    ln = np.ascontiguousarray(seq_len, dtype=np.uint32)
+    return _Kept((abi.ptr(arena), C.c_uint64(arena.size), abi.ptr(off), abi.ptr(ln), C.c_uint32(len(ln))), (arena, off, ln)), ln
 
 
 def _pack_units(units):

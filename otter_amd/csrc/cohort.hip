@@ -251,6 +251,24 @@ int cohort_build_rows(otg_ctx* ctx, Cohort& c, const char* who)
   return OTG_OK;
 }
 
+// the row operators (otg_*_cohort): the open, clustered batch or the refusal; then, behind the operator's own argument check, rows
+// [row_begin, row_begin + n) of it
+int cohort_clustered(otg_ctx* ctx, const char* who, Cohort** out)
+{
+  Cohort* cp = cohort_of(ctx, who);
+  if (!cp) return ctx ? OTG_ERR_ARG : OTG_ERR_NO_DEVICE;
+  if (!cp->clustered) return otg_fail(ctx, OTG_ERR_ARG, "%s: the batch has not been clustered (otg_cohort_genotype)", who);
+  *out = cp;
+  return OTG_OK;
+}
+int cohort_rows(otg_ctx* ctx, Cohort& c, const char* who, uint32_t row_begin, uint32_t n, OtgRows* rows)
+{
+  if (int rc = cohort_build_rows(ctx, c, who)) return rc;
+  if ((uint64_t)row_begin + n > c.n_rows) return otg_fail(ctx, OTG_ERR_ARG, "%s: rows %u .. %llu of %u", who, row_begin, (unsigned long long)row_begin + n, c.n_rows);
+  *rows = OtgRows{(const uint8_t*)c.arena.p, (const uint64_t*)c.row_off.p + row_begin, (const uint32_t*)c.row_len.p + row_begin};
+  return OTG_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -489,62 +507,49 @@ int otg_kmer_cohort_device_rows(otg_ctx* ctx, uint32_t* n_rows, const uint32_t**
 
 int otg_kmer_cohort_usage(otg_ctx* ctx, int32_t k, uint32_t row_begin, uint32_t n, double* usage_out, double* gc_out, double* hsd_out)
 {
-  Cohort* cp = cohort_of(ctx, "otg_kmer_cohort_usage");
-  if (!cp) return ctx ? OTG_ERR_ARG : OTG_ERR_NO_DEVICE;
-  Cohort& c = *cp;
-  if (!c.clustered) return otg_fail(ctx, OTG_ERR_ARG, "otg_kmer_cohort_usage: the batch has not been clustered (otg_cohort_genotype)");
+  Cohort* c = nullptr;
+  OtgRows rows;
+  if (int rc = cohort_clustered(ctx, "otg_kmer_cohort_usage", &c)) return rc;
   if (k < 1 || k > OTG_KMER_MAX) return otg_fail(ctx, OTG_ERR_ARG, "otg_kmer_cohort_usage: k = %d outside 1..%d", k, OTG_KMER_MAX);
-  if (int rc = cohort_build_rows(ctx, c, "otg_kmer_cohort_usage")) return rc;
-  if ((uint64_t)row_begin + n > c.n_rows) return otg_fail(ctx, OTG_ERR_ARG, "otg_kmer_cohort_usage: rows %u .. %llu of %u", row_begin, (unsigned long long)row_begin + n, c.n_rows);
+  if (int rc = cohort_rows(ctx, *c, "otg_kmer_cohort_usage", row_begin, n, &rows)) return rc;
   if (int rc = otg_kmer_usage_fits(ctx, "otg_kmer_cohort_usage", n, k)) return rc;
-  return otg_kmer_usage_resident(ctx, "otg_kmer_cohort_usage", (const uint8_t*)c.arena.p, (const uint64_t*)c.row_off.p + row_begin, (const uint32_t*)c.row_len.p + row_begin,
-                                 nullptr, n, k, usage_out, gc_out, hsd_out);
+  return otg_kmer_usage_resident(ctx, "otg_kmer_cohort_usage", rows, nullptr, n, k, usage_out, gc_out, hsd_out);
 }
 
 int otg_motif_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, uint32_t max_period, uint32_t slack, otg_motif* out, uint8_t* unit_out, uint32_t unit_stride)
 {
-  Cohort* cp = cohort_of(ctx, "otg_motif_cohort");
-  if (!cp) return ctx ? OTG_ERR_ARG : OTG_ERR_NO_DEVICE;
-  Cohort& c = *cp;
-  if (!c.clustered) return otg_fail(ctx, OTG_ERR_ARG, "otg_motif_cohort: the batch has not been clustered (otg_cohort_genotype)");
+  Cohort* c = nullptr;
+  OtgRows rows;
+  if (int rc = cohort_clustered(ctx, "otg_motif_cohort", &c)) return rc;
   if (int rc = otg_motif_args(ctx, "otg_motif_cohort", max_period, slack)) return rc;
-  if (int rc = cohort_build_rows(ctx, c, "otg_motif_cohort")) return rc;
-  if ((uint64_t)row_begin + n > c.n_rows) return otg_fail(ctx, OTG_ERR_ARG, "otg_motif_cohort: rows %u .. %llu of %u", row_begin, (unsigned long long)row_begin + n, c.n_rows);
+  if (int rc = cohort_rows(ctx, *c, "otg_motif_cohort", row_begin, n, &rows)) return rc;
   uint32_t max_len = 0;      // the row lengths exist on the device only
   if (n)
-    if (int rc = otg_device_max_u32(ctx, (const uint32_t*)c.row_len.p + row_begin, n, &max_len)) return rc;
+    if (int rc = otg_device_max_u32(ctx, rows.len, n, &max_len)) return rc;
   if (int rc = otg_motif_stride_fits(ctx, "otg_motif_cohort", max_len, max_period, unit_stride)) return rc;
-  return otg_motif_resident(ctx, "otg_motif_cohort", (const uint8_t*)c.arena.p, (const uint64_t*)c.row_off.p + row_begin, (const uint32_t*)c.row_len.p + row_begin, n,
-                            max_period, slack, out, unit_out, unit_stride);
+  return otg_motif_resident(ctx, "otg_motif_cohort", rows, n, max_period, slack, out, unit_out, unit_stride);
 }
 
 int otg_repeat_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, uint32_t max_period, uint32_t min_copies, uint32_t min_span, otg_repeat_sum* sums,
                       uint64_t* seg_off, uint64_t* n_segments)
 {
-  Cohort* cp = cohort_of(ctx, "otg_repeat_cohort");
-  if (!cp) return ctx ? OTG_ERR_ARG : OTG_ERR_NO_DEVICE;
-  Cohort& c = *cp;
-  if (!c.clustered) return otg_fail(ctx, OTG_ERR_ARG, "otg_repeat_cohort: the batch has not been clustered (otg_cohort_genotype)");
+  Cohort* c = nullptr;
+  OtgRows rows;
+  if (int rc = cohort_clustered(ctx, "otg_repeat_cohort", &c)) return rc;
   if (int rc = otg_repeat_args(ctx, "otg_repeat_cohort", max_period, min_copies, min_span)) return rc;
-  if (int rc = cohort_build_rows(ctx, c, "otg_repeat_cohort")) return rc;
-  if ((uint64_t)row_begin + n > c.n_rows) return otg_fail(ctx, OTG_ERR_ARG, "otg_repeat_cohort: rows %u .. %llu of %u", row_begin, (unsigned long long)row_begin + n, c.n_rows);
-  return otg_repeat_resident(ctx, "otg_repeat_cohort", (const uint8_t*)c.arena.p, (const uint64_t*)c.row_off.p + row_begin, (const uint32_t*)c.row_len.p + row_begin, n,
-                             max_period, min_copies, min_span, sums, seg_off, n_segments);
+  if (int rc = cohort_rows(ctx, *c, "otg_repeat_cohort", row_begin, n, &rows)) return rc;
+  return otg_repeat_resident(ctx, "otg_repeat_cohort", rows, n, max_period, min_copies, min_span, sums, seg_off, n_segments);
 }
 
 int otg_unitalign_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off,
                          const uint32_t* unit_len, uint32_t n_units, const uint32_t* task_seq, const uint32_t* task_unit, uint32_t n_tasks, otg_unitalign* out)
 {
-  Cohort* cp = cohort_of(ctx, "otg_unitalign_cohort");
-  if (!cp) return ctx ? OTG_ERR_ARG : OTG_ERR_NO_DEVICE;
-  Cohort& c = *cp;
-  if (!c.clustered) return otg_fail(ctx, OTG_ERR_ARG, "otg_unitalign_cohort: the batch has not been clustered (otg_cohort_genotype)");
-  if (int rc = cohort_build_rows(ctx, c, "otg_unitalign_cohort")) return rc;
-  if ((uint64_t)row_begin + n > c.n_rows) return otg_fail(ctx, OTG_ERR_ARG, "otg_unitalign_cohort: rows %u .. %llu of %u", row_begin, (unsigned long long)row_begin + n, c.n_rows);
-  const uint64_t* d_off = (const uint64_t*)c.row_off.p + row_begin;
-  const uint32_t* d_len = (const uint32_t*)c.row_len.p + row_begin;
+  Cohort* c = nullptr;
+  OtgRows rows;
+  if (int rc = cohort_clustered(ctx, "otg_unitalign_cohort", &c)) return rc;
+  if (int rc = cohort_rows(ctx, *c, "otg_unitalign_cohort", row_begin, n, &rows)) return rc;
   if (!unit_arena && !n_units) {                                   // the units of the latest otg_motif_cohort, which stay where they are
-    if (ctx->last_motif_n == 0 || ctx->last_motif_arena != (const uint8_t*)c.arena.p || ctx->last_motif_off != d_off || ctx->last_motif_n != n)
+    if (ctx->last_motif_n == 0 || ctx->last_motif_rows.arena != rows.arena || ctx->last_motif_rows.off != rows.off || ctx->last_motif_n != n)
       return otg_fail(ctx, OTG_ERR_ARG, "otg_unitalign_cohort: the latest motif call on this context was not otg_motif_cohort over rows %u .. %llu", row_begin,
                       (unsigned long long)row_begin + n);
     return otg_unitalign_motifs(ctx, out);
@@ -556,24 +561,21 @@ int otg_unitalign_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, const uin
   OtgUnitSource units;
   const uint32_t *d_ts = nullptr, *d_tu = nullptr;
   if (int rc = otg_unitalign_upload(ctx, unit_arena, unit_bytes, unit_off, unit_len, n_units, task_seq, task_unit, n_tasks, &units, &d_ts, &d_tu)) return rc;
-  return otg_unitalign_resident(ctx, "otg_unitalign_cohort", (const uint8_t*)c.arena.p, d_off, d_len, units, d_ts, d_tu, n_tasks, out);
+  return otg_unitalign_resident(ctx, "otg_unitalign_cohort", rows, units, d_ts, d_tu, n_tasks, out);
 }
 
 int otg_unitparse_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off,
                          const uint32_t* unit_len, uint32_t n_units, const uint64_t* set_first, uint32_t n_sets, const uint32_t* task_seq,
                          const uint32_t* task_set, uint32_t n_tasks, otg_unitparse_sum* sums, uint64_t* seg_off, uint64_t* n_segments)
 {
-  Cohort* cp = cohort_of(ctx, "otg_unitparse_cohort");
-  if (!cp) return ctx ? OTG_ERR_ARG : OTG_ERR_NO_DEVICE;
-  Cohort& c = *cp;
-  if (!c.clustered) return otg_fail(ctx, OTG_ERR_ARG, "otg_unitparse_cohort: the batch has not been clustered (otg_cohort_genotype)");
-  if (int rc = cohort_build_rows(ctx, c, "otg_unitparse_cohort")) return rc;
-  if ((uint64_t)row_begin + n > c.n_rows) return otg_fail(ctx, OTG_ERR_ARG, "otg_unitparse_cohort: rows %u .. %llu of %u", row_begin, (unsigned long long)row_begin + n, c.n_rows);
+  Cohort* c = nullptr;
+  OtgRows rows;
+  if (int rc = cohort_clustered(ctx, "otg_unitparse_cohort", &c)) return rc;
+  if (int rc = cohort_rows(ctx, *c, "otg_unitparse_cohort", row_begin, n, &rows)) return rc;
   if (int rc = otg_unitparse_check(ctx, "otg_unitparse_cohort", n, unit_arena, unit_bytes, unit_off, unit_len, n_units, set_first, n_sets, task_seq, task_set, n_tasks))
     return rc;
-  return otg_unitparse_resident(ctx, "otg_unitparse_cohort", (const uint8_t*)c.arena.p, (const uint64_t*)c.row_off.p + row_begin, (const uint32_t*)c.row_len.p + row_begin,
-                                nullptr, n, unit_arena, unit_bytes, unit_off, unit_len, n_units, set_first, n_sets, task_seq, task_set, n_tasks, sums, seg_off,
-                                n_segments);
+  return otg_unitparse_resident(ctx, "otg_unitparse_cohort", rows, nullptr, n, unit_arena, unit_bytes, unit_off, unit_len, n_units, set_first, n_sets, task_seq, task_set,
+                                n_tasks, sums, seg_off, n_segments);
 }
 
 int otg_cohort_end(otg_ctx* ctx)

@@ -109,13 +109,11 @@ extern "C" int otg_compare_emit(const otg_bed* beds, const char* chr_arena, uint
     }
   }
   if (counts) *counts = cnt;
-  *out_len = text.size();
+  *out_len = text.size();                                          // (here as well: the sizing call learns it even where the warnings do not fit)
   if (warn_len) {
     *warn_len = wtext.size();
     if (wtext.size() > warn_capacity || (!warn && !wtext.empty())) return otg_fail(nullptr, OTG_ERR_CAPACITY, "otg_compare_emit: warning buffer too small");
     if (!wtext.empty()) memcpy(warn, wtext.data(), wtext.size());
   }
-  if (text.size() > out_capacity || (!out && !text.empty())) return otg_fail(nullptr, OTG_ERR_CAPACITY, "otg_compare_emit: output buffer too small");
-  if (!text.empty()) memcpy(out, text.data(), text.size());
-  return OTG_OK;
+  return otg_text_out("otg_compare_emit", text, out, out_capacity, out_len);
 }

@@ -893,6 +893,56 @@ int vcf_allele_job(const char* who, const char* vcf_path, const char* bed_path, 
   return OTG_OK;
 }
 
+// the motif arguments of a job, refused in the command line's words; and the unit stride a motif call over rows of these lengths takes
+int motif_cli_args(uint32_t max_period, uint32_t slack)
+{
+  if (max_period < 1 || max_period > OTG_MOTIF_MAX_PERIOD)
+    return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--max-period' (%u). Needs to be 1 <= x <= %d.", max_period, OTG_MOTIF_MAX_PERIOD);
+  if (slack > 999) return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--slack' (%u). Needs to be 0 <= x <= 999.", slack);
+  return OTG_OK;
+}
+uint32_t motif_unit_stride(const uint32_t* len, uint32_t n, uint32_t max_period)
+{
+  uint32_t max_len = 0;
+  for (uint32_t i = 0; i < n; ++i) max_len = std::max(max_len, len[i]);
+  return std::max<uint32_t>(1, std::min<uint32_t>(max_period, max_len / 2));
+}
+
+// The tandem-repeat catalogue of a BED: the units of every record (record r: units first[r] .. first[r + 1], unit k = arena[off[k] .. + len[k]))
+// and the records by region string as the VCF names them (the first record of a region wins).
+struct UnitCatalogue {
+  std::vector<uint64_t> first, off;
+  std::vector<uint32_t> len;
+  std::vector<uint8_t> arena;
+  std::map<std::string, uint32_t> by_region;
+  int load(const char* who, const char* bed_path)
+  {
+    Bed bed;
+    if (int rc = load_bed(bed_path, bed)) return rc;
+    uint64_t nr = 0, nu = 0, ab = 0;
+    int rc = otg_parse_bed_units(bed_path, nullptr, 0, &nr, nullptr, nullptr, 0, &nu, nullptr, 0, &ab);
+    if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) return rc;
+    first.resize(nr + 1); off.resize(nu + 1); len.resize(nu + 1); arena.resize(ab + 1);
+    rc = otg_parse_bed_units(bed_path, first.data(), first.size(), &nr, off.data(), len.data(), nu, &nu, arena.data(), ab, &ab);
+    if (rc != OTG_OK) return rc;
+    if (nr != bed.beds.size()) return otg_fail(nullptr, OTG_ERR_FATAL, "%s: the two BED readers disagree on %s", who, bed_path);
+    std::string name;
+    for (uint32_t r = 0; r < bed.beds.size(); ++r) {
+      name.clear();
+      otg_region_name(name, bed.chr_arena.data() + bed.beds[r].chr_off, bed.beds[r].chr_len, bed.beds[r].start, bed.beds[r].end);
+      by_region.emplace(name, r);
+    }
+    return OTG_OK;
+  }
+  // the units [u0, u1) of the record of this region; none: u0 = u1 = 0
+  void units_of(const std::string& region, uint64_t* u0, uint64_t* u1) const
+  {
+    const auto it = by_region.find(region);
+    *u0 = it == by_region.end() ? 0 : first[it->second];
+    *u1 = it == by_region.end() ? 0 : first[it->second + 1];
+  }
+};
+
 } // namespace
 
 extern "C" {
@@ -1106,17 +1156,13 @@ int otg_motifs_files(const otg_motifs_job* job, otg_write_fn write, void* user, 
 {
   if (!job || !write || !job->vcf_path || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "otg_motifs_files: NULL job, writer, VCF or BED path");
   const uint32_t max_period = job->max_period, slack = job->slack;
-  if (max_period < 1 || max_period > OTG_MOTIF_MAX_PERIOD)
-    return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--max-period' (%u). Needs to be 1 <= x <= %d.", max_period, OTG_MOTIF_MAX_PERIOD);
-  if (slack > 999) return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--slack' (%u). Needs to be 0 <= x <= 999.", slack);
+  if (int rc = motif_cli_args(max_period, slack)) return rc;
   std::vector<otg_motif> motifs;
   std::vector<uint8_t> units;
   uint32_t stride = 1;
   return vcf_allele_job("otg_motifs_files", job->vcf_path, job->bed_path, job->device, job->batch_alleles ? job->batch_alleles : 65536, job->threads, write, user, stats,
     [&](otg_ctx* ctx, const VcfBatch& B) {
-      uint32_t max_len = 0;
-      for (uint32_t i = 0; i < B.na; ++i) max_len = std::max(max_len, B.len[i]);
-      stride = std::max<uint32_t>(1, std::min<uint32_t>(max_period, max_len / 2));
+      stride = motif_unit_stride(B.len.data(), B.na, max_period);
       motifs.resize(B.na); units.resize((size_t)B.na * stride);
       return otg_motif_batch(ctx, B.seqs.data(), B.au, B.off.data(), B.len.data(), B.na, max_period, slack, motifs.data(), units.data(), stride);
     },
@@ -1157,33 +1203,9 @@ int otg_copies_files(const otg_copies_job* job, otg_write_fn write, void* user, 
 {
   if (!job || !write || !job->vcf_path || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "otg_copies_files: NULL job, writer, VCF or BED path");
   const uint32_t max_period = job->max_period, slack = job->slack;
-  if (max_period < 1 || max_period > OTG_MOTIF_MAX_PERIOD)
-    return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--max-period' (%u). Needs to be 1 <= x <= %d.", max_period, OTG_MOTIF_MAX_PERIOD);
-  if (slack > 999) return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--slack' (%u). Needs to be 0 <= x <= 999.", slack);
-  // the catalogue: region string -> BED record (the first one wins), and the units of every record
-  Bed bed;
-  if (int rc = load_bed(job->bed_path, bed)) return rc;
-  std::vector<uint64_t> cat_first, cat_off;
-  std::vector<uint32_t> cat_len;
-  std::vector<uint8_t> cat_arena;
-  {
-    uint64_t nr = 0, nu = 0, ab = 0;
-    int rc = otg_parse_bed_units(job->bed_path, nullptr, 0, &nr, nullptr, nullptr, 0, &nu, nullptr, 0, &ab);
-    if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) return rc;
-    cat_first.resize(nr + 1); cat_off.resize(nu + 1); cat_len.resize(nu + 1); cat_arena.resize(ab + 1);
-    rc = otg_parse_bed_units(job->bed_path, cat_first.data(), cat_first.size(), &nr, cat_off.data(), cat_len.data(), nu, &nu, cat_arena.data(), ab, &ab);
-    if (rc != OTG_OK) return rc;
-    if (nr != bed.beds.size()) return otg_fail(nullptr, OTG_ERR_FATAL, "otg_copies_files: the two BED readers disagree on %s", job->bed_path);
-  }
-  std::map<std::string, uint32_t> by_region;
-  {
-    std::string name;
-    for (uint32_t r = 0; r < bed.beds.size(); ++r) {
-      name.clear();
-      otg_region_name(name, bed.chr_arena.data() + bed.beds[r].chr_off, bed.beds[r].chr_len, bed.beds[r].start, bed.beds[r].end);
-      by_region.emplace(name, r);
-    }
-  }
+  if (int rc = motif_cli_args(max_period, slack)) return rc;
+  UnitCatalogue cat;
+  if (int rc = cat.load("otg_copies_files", job->bed_path)) return rc;
   // per batch: the tasks in file order (allele a: task_first[a] .. task_first[a + 1]) and where each one's unit and record lie
   std::vector<uint64_t> task_first, unit_off, m_off, b_uoff;
   std::vector<uint32_t> unit_len, m_len, b_ulen, b_tseq, b_tunit, b_task, m_task;
@@ -1200,12 +1222,12 @@ int otg_copies_files(const otg_copies_job* job, otg_write_fn write, void* user, 
       for (uint32_t r = 0; r < B.nr; ++r) {
         const otg_vcf_record& R = B.rec[r];
         name.assign(B.regions.data() + R.region_off, R.region_len);
-        const auto it = by_region.find(name);
-        const uint64_t u0 = it == by_region.end() ? 0 : cat_first[it->second], u1 = it == by_region.end() ? 0 : cat_first[it->second + 1];
+        uint64_t u0, u1;
+        cat.units_of(name, &u0, &u1);
         const uint32_t bu0 = (uint32_t)b_ulen.size();
         for (uint64_t k = u0; k < u1; ++k) {                       // the record's units, once per record
-          b_uoff.push_back(b_units.size()); b_ulen.push_back(cat_len[k]);
-          b_units.insert(b_units.end(), cat_arena.begin() + cat_off[k], cat_arena.begin() + cat_off[k] + cat_len[k]);
+          b_uoff.push_back(b_units.size()); b_ulen.push_back(cat.len[k]);
+          b_units.insert(b_units.end(), cat.arena.begin() + cat.off[k], cat.arena.begin() + cat.off[k] + cat.len[k]);
         }
         for (uint32_t i = 0; i < R.n_alleles; ++i) {
           const uint32_t a = R.first_allele + i;
@@ -1214,8 +1236,8 @@ int otg_copies_files(const otg_copies_job* job, otg_write_fn write, void* user, 
             for (uint64_t k = u0; k < u1; ++k) {
               b_task.push_back((uint32_t)source.size()); b_tseq.push_back(a); b_tunit.push_back(bu0 + (uint32_t)(k - u0));
               source.push_back(OTG_UNITALIGN_SOURCE_BED);
-              unit_off.push_back(units.size()); unit_len.push_back(cat_len[k]);
-              units.insert(units.end(), cat_arena.begin() + cat_off[k], cat_arena.begin() + cat_off[k] + cat_len[k]);
+              unit_off.push_back(units.size()); unit_len.push_back(cat.len[k]);
+              units.insert(units.end(), cat.arena.begin() + cat.off[k], cat.arena.begin() + cat.off[k] + cat.len[k]);
             }
           } else {
             m_task.push_back((uint32_t)source.size()); m_off.push_back(B.off[a]); m_len.push_back(B.len[a]);
@@ -1234,9 +1256,7 @@ int otg_copies_files(const otg_copies_job* job, otg_write_fn write, void* user, 
       }
       if (!m_task.empty()) {
         const uint32_t nm = (uint32_t)m_task.size();
-        uint32_t max_len = 0;
-        for (uint32_t L : m_len) max_len = std::max(max_len, L);
-        const uint32_t stride = std::max<uint32_t>(1, std::min<uint32_t>(max_period, max_len / 2));
+        const uint32_t stride = motif_unit_stride(m_len.data(), nm, max_period);
         motifs.resize(nm); m_units.resize((size_t)nm * stride); part.resize(nm);
         if (int rc = otg_motif_batch(ctx, B.seqs.data(), B.au, m_off.data(), m_len.data(), nm, max_period, slack, motifs.data(), m_units.data(), stride)) return rc;
         if (int rc = otg_unitalign_motifs(ctx, part.data())) return rc;
@@ -1261,29 +1281,8 @@ int otg_copies_files(const otg_copies_job* job, otg_write_fn write, void* user, 
 int otg_unitparse_files(const otg_unitparse_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
 {
   if (!job || !write || !job->vcf_path || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "otg_unitparse_files: NULL job, writer, VCF or BED path");
-  Bed bed;
-  if (int rc = load_bed(job->bed_path, bed)) return rc;
-  std::vector<uint64_t> cat_first, cat_off;
-  std::vector<uint32_t> cat_len;
-  std::vector<uint8_t> cat_arena;
-  {
-    uint64_t nr = 0, nu = 0, ab = 0;
-    int rc = otg_parse_bed_units(job->bed_path, nullptr, 0, &nr, nullptr, nullptr, 0, &nu, nullptr, 0, &ab);
-    if (rc != OTG_OK && rc != OTG_ERR_CAPACITY) return rc;
-    cat_first.resize(nr + 1); cat_off.resize(nu + 1); cat_len.resize(nu + 1); cat_arena.resize(ab + 1);
-    rc = otg_parse_bed_units(job->bed_path, cat_first.data(), cat_first.size(), &nr, cat_off.data(), cat_len.data(), nu, &nu, cat_arena.data(), ab, &ab);
-    if (rc != OTG_OK) return rc;
-    if (nr != bed.beds.size()) return otg_fail(nullptr, OTG_ERR_FATAL, "otg_unitparse_files: the two BED readers disagree on %s", job->bed_path);
-  }
-  std::map<std::string, uint32_t> by_region;
-  {
-    std::string name;
-    for (uint32_t r = 0; r < bed.beds.size(); ++r) {
-      name.clear();
-      otg_region_name(name, bed.chr_arena.data() + bed.beds[r].chr_off, bed.beds[r].chr_len, bed.beds[r].start, bed.beds[r].end);
-      by_region.emplace(name, r);
-    }
-  }
+  UnitCatalogue cat;
+  if (int rc = cat.load("otg_unitparse_files", job->bed_path)) return rc;
   // per batch: one set per record with units, one task per allele of such a record; the results per allele, in file order
   std::vector<uint64_t> set_first, uoff, seg_off, t_seg_off;
   std::vector<uint32_t> ulen, allele_set, tseq, tset;
@@ -1298,19 +1297,19 @@ int otg_unitparse_files(const otg_unitparse_job* job, otg_write_fn write, void* 
       for (uint32_t r = 0; r < B.nr; ++r) {
         const otg_vcf_record& R = B.rec[r];
         name.assign(B.regions.data() + R.region_off, R.region_len);
-        const auto it = by_region.find(name);
-        if (it == by_region.end() || cat_first[it->second + 1] == cat_first[it->second]) continue;
-        const uint64_t u0 = cat_first[it->second], u1 = cat_first[it->second + 1];
+        uint64_t u0, u1;
+        cat.units_of(name, &u0, &u1);
+        if (u1 == u0) continue;
         if (u1 - u0 > OTG_UNITPARSE_MAX_UNITS)
           return otg_fail(ctx, OTG_ERR_ARG, "%s has %llu units in the catalogue, at most %d", name.c_str(), (unsigned long long)(u1 - u0),
                           OTG_UNITPARSE_MAX_UNITS);
-        if (otg_unitparse_core::up_class(cat_len.data() + u0, (uint32_t)(u1 - u0)) == otg_unitparse_core::UP_NO_CLASS)
+        if (otg_unitparse_core::up_class(cat.len.data() + u0, (uint32_t)(u1 - u0)) == otg_unitparse_core::UP_NO_CLASS)
           return otg_fail(ctx, OTG_ERR_ARG, "the units of %s do not fit one wave (%u lanes at four positions each, at most %d)", name.c_str(),
-                          otg_unitparse_core::up_lanes(cat_len.data() + u0, (uint32_t)(u1 - u0), 4u), OTG_UNITPARSE_MAX_LANES);
+                          otg_unitparse_core::up_lanes(cat.len.data() + u0, (uint32_t)(u1 - u0), 4u), OTG_UNITPARSE_MAX_LANES);
         const uint32_t q = (uint32_t)set_first.size() - 1u;
         for (uint64_t k = u0; k < u1; ++k) {
-          uoff.push_back(units.size()); ulen.push_back(cat_len[k]);
-          units.insert(units.end(), cat_arena.begin() + cat_off[k], cat_arena.begin() + cat_off[k] + cat_len[k]);
+          uoff.push_back(units.size()); ulen.push_back(cat.len[k]);
+          units.insert(units.end(), cat.arena.begin() + cat.off[k], cat.arena.begin() + cat.off[k] + cat.len[k]);
         }
         set_first.push_back(ulen.size());
         for (uint32_t i = 0; i < R.n_alleles; ++i) { allele_set[R.first_allele + i] = q; tseq.push_back(R.first_allele + i); tset.push_back(q); }

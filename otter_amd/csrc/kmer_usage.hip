@@ -302,12 +302,12 @@ int otg_kmer_usage_fits(otg_ctx* ctx, const char* who, uint32_t n, int32_t k)
   return OTG_OK;
 }
 
-// The launch part of otg_kmer_usage_batch on device-resident rows: row i is d_arena[d_off[i] .. + d_len[i]), and the tiers read up to 32 bytes
+// The launch part of otg_kmer_usage_batch on device-resident rows: row i is rows.arena[rows.off[i] .. + rows.len[i]), and the tiers read up to 32 bytes
 // past a row's last window, so the arena must extend that far past every row.  h_blk (nullable, read for k >= 8 only) is the workgroup prefix
 // of tier L (n + 1 entries) where the caller has the lengths on the host; without it the prefix is scanned on the device and only its total
 // read back.  The results land in SLOT_KMER_OUT (otg_kmer_usage_device_results); the caller has checked otg_kmer_usage_fits.
-int otg_kmer_usage_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, const uint32_t* h_blk,
-                            uint32_t n, int32_t k, double* usage_out, double* gc_out, double* hsd_out)
+int otg_kmer_usage_resident(otg_ctx* ctx, const char* who, const OtgRows& rows, const uint32_t* h_blk, uint32_t n, int32_t k, double* usage_out,
+                            double* gc_out, double* hsd_out)
 {
   ctx->last_kmer_count_ms = ctx->last_kmer_epi_ms = 0.0;
   if (n == 0) return OTG_OK;
@@ -331,7 +331,7 @@ int otg_kmer_usage_resident(otg_ctx* ctx, const char* who, const uint8_t* d_aren
     if (h_blk) HIP_TRY(ctx, hipMemcpyAsync(d_blk, h_blk, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
     else {
       uint64_t* d_total = (uint64_t*)(d_gc + blk_words);
-      hipLaunchKernelGGL((otg_scan_kernel<uint64_t, uint32_t, KuChunks>), dim3(1), dim3(1024), 0, ctx->stream, KuChunks{d_len}, n, d_blk, d_total);
+      hipLaunchKernelGGL((otg_scan_kernel<uint64_t, uint32_t, KuChunks>), dim3(1), dim3(1024), 0, ctx->stream, KuChunks{rows.len}, n, d_blk, d_total);
       HIP_TRY(ctx, hipGetLastError());
       HIP_TRY(ctx, hipMemcpyAsync(&acc, d_total, 8, hipMemcpyDeviceToHost, ctx->stream));
       HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -341,7 +341,7 @@ int otg_kmer_usage_resident(otg_ctx* ctx, const char* who, const uint8_t* d_aren
     HIP_TRY(ctx, hipMemsetAsync(d_hist, 0, (size_t)n * bins * sizeof(uint32_t), ctx->stream));
   }
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  kLaunch[k](ctx, d_arena, d_off, d_len, d_blk, n, (uint32_t)acc, d_usage, d_hist, d_gc, d_gcv, d_hsd);
+  kLaunch[k](ctx, rows.arena, rows.off, rows.len, d_blk, n, (uint32_t)acc, d_usage, d_hist, d_gc, d_gcv, d_hsd);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
   if (usage_out) HIP_TRY(ctx, hipMemcpyAsync(usage_out, d_usage, usage_bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -360,11 +360,7 @@ extern "C" int otg_kmer_usage_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint
 {
   if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_kmer_usage_batch: no context (no HIP device?)");
   if (k < 1 || k > OTG_KMER_MAX) return otg_fail(ctx, OTG_ERR_ARG, "otg_kmer_usage_batch: k = %d outside 1..%d", k, OTG_KMER_MAX);
-  if (n && (!seq_off || !seq_len || (arena_bytes && !seq_arena))) return otg_fail(ctx, OTG_ERR_ARG, "otg_kmer_usage_batch: NULL argument");
-  for (uint32_t i = 0; i < n; ++i)
-    if (seq_off[i] > arena_bytes || seq_len[i] > arena_bytes - seq_off[i])
-      return otg_fail(ctx, OTG_ERR_ARG, "otg_kmer_usage_batch: allele %u (offset %llu, length %u) lies outside the %llu-byte arena", i,
-                      (unsigned long long)seq_off[i], seq_len[i], (unsigned long long)arena_bytes);
+  if (int rc = otg_rows_check(ctx, "otg_kmer_usage_batch", seq_arena, arena_bytes, seq_off, seq_len, n, nullptr)) return rc;
   if (int rc = otg_kmer_usage_fits(ctx, "otg_kmer_usage_batch", n, k)) return rc;
   ctx->last_kmer_count_ms = ctx->last_kmer_epi_ms = 0.0;
   if (n == 0) return OTG_OK;
@@ -376,18 +372,9 @@ extern "C" int otg_kmer_usage_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint
     if (acc > 0x7fffffffull) return otg_fail(ctx, OTG_ERR_CAPACITY, "otg_kmer_usage_batch: the batch needs %llu workgroups", (unsigned long long)acc);
     blk[n] = (uint32_t)acc;
   }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  // the rows: the arena and seq_off (u64) | seq_len (u32)
-  uint8_t* d_arena = (uint8_t*)otg_slot(ctx, SLOT_KMER_SEQ, arena_bytes + 64);
-  uint8_t* d_meta = (uint8_t*)otg_slot(ctx, SLOT_KMER_META, (size_t)n * 12);
-  if (!d_arena || !d_meta) return OTG_ERR_HIP;
-  uint64_t* d_off = (uint64_t*)d_meta;
-  uint32_t* d_len = (uint32_t*)(d_meta + (size_t)n * 8);
-  HIP_TRY(ctx, hipMemsetAsync(d_arena + arena_bytes, 0, 64, ctx->stream));
-  if (arena_bytes) HIP_TRY(ctx, hipMemcpyAsync(d_arena, seq_arena, arena_bytes, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_off, seq_off, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_len, seq_len, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-  return otg_kmer_usage_resident(ctx, "otg_kmer_usage_batch", d_arena, d_off, d_len, k >= 8 ? blk.data() : nullptr, n, k, usage_out, gc_out, hsd_out);
+  OtgRows rows;
+  if (int rc = otg_rows_upload(ctx, SLOT_KMER_SEQ, SLOT_KMER_META, seq_arena, arena_bytes, seq_off, seq_len, n, &rows)) return rc;
+  return otg_kmer_usage_resident(ctx, "otg_kmer_usage_batch", rows, k >= 8 ? blk.data() : nullptr, n, k, usage_out, gc_out, hsd_out);
 }
 
 extern "C" int otg_kmer_usage_device_results(otg_ctx* ctx, uint32_t n, int32_t k, const double** usage, const double** gc, const double** hsd)

@@ -226,11 +226,11 @@ int otg_motif_args(otg_ctx* ctx, const char* who, uint32_t max_period, uint32_t 
   return OTG_OK;
 }
 
-// The launch part of otg_motif_batch on device-resident rows: row i is d_arena[d_off[i] .. + d_len[i]), and the pack reads up to 31 bytes past
+// The launch part of otg_motif_batch on device-resident rows: row i is rows.arena[rows.off[i] .. + rows.len[i]), and the pack reads up to 31 bytes past
 // a row, so the arena must extend that far past every row.  The caller has checked unit_stride against the longest row
 // (otg_motif_stride_fits).  The results land in SLOT_MOTIF_OUT (otg_motif_device_results): n records, then n x unit_stride unit bytes (zero beyond a unit's period).
-int otg_motif_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, uint32_t n,
-                       uint32_t max_period, uint32_t slack, otg_motif* out, uint8_t* unit_out, uint32_t unit_stride)
+int otg_motif_resident(otg_ctx* ctx, const char* who, const OtgRows& rows, uint32_t n, uint32_t max_period, uint32_t slack, otg_motif* out,
+                       uint8_t* unit_out, uint32_t unit_stride)
 {
   ctx->last_motif_count_ms = ctx->last_motif_reduce_ms = 0.0;
   ctx->last_motif_n = 0; ctx->last_motif_stride = 0;
@@ -246,8 +246,8 @@ int otg_motif_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, co
   if (!d_moff || !d_out) return OTG_ERR_HIP;
   uint64_t* d_ploff = d_moff + (n + 1);
   uint64_t* d_tot = d_ploff + (n + 1);
-  hipLaunchKernelGGL((otg_scan_kernel<uint64_t, uint64_t, MoPeriods>), dim3(1), dim3(1024), 0, ctx->stream, MoPeriods{d_len, max_period}, n, d_moff, d_tot);
-  otg_motif_plane_scan(ctx, d_len, n, max_period, lds_len, d_ploff, d_tot + 1);
+  hipLaunchKernelGGL((otg_scan_kernel<uint64_t, uint64_t, MoPeriods>), dim3(1), dim3(1024), 0, ctx->stream, MoPeriods{rows.len, max_period}, n, d_moff, d_tot);
+  otg_motif_plane_scan(ctx, rows.len, n, max_period, lds_len, d_ploff, d_tot + 1);
   HIP_TRY(ctx, hipGetLastError());
   uint64_t tot[2] = {0, 0};
   HIP_TRY(ctx, hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, ctx->stream));
@@ -260,14 +260,14 @@ int otg_motif_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, co
   if (unit_bytes) HIP_TRY(ctx, hipMemsetAsync(d_unit, 0, unit_bytes, ctx->stream));
   const uint32_t grid = std::min<uint32_t>(n, 1u << 20);
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  if (lds_len) hipLaunchKernelGGL(motif_count_lds, dim3(grid), dim3(MOTIF_T), 0, ctx->stream, d_arena, d_off, d_len, n, max_period, lds_len, d_moff, d_m);
+  if (lds_len) hipLaunchKernelGGL(motif_count_lds, dim3(grid), dim3(MOTIF_T), 0, ctx->stream, rows.arena, rows.off, rows.len, n, max_period, lds_len, d_moff, d_m);
   if (tot[1]) {              // grids over every allele: the workgroups of an allele without planes in HBM (pl_off unchanged) return at once
-    otg_motif_pack_planes(ctx, d_arena, d_off, d_len, n, d_ploff, d_planes);
-    hipLaunchKernelGGL(motif_count_hbm, dim3(n, (max_period + MOTIF_T - 1) / MOTIF_T), dim3(MOTIF_T), 0, ctx->stream, d_len, n, max_period, d_ploff, d_planes, d_moff, d_m);
+    otg_motif_pack_planes(ctx, rows.arena, rows.off, rows.len, n, d_ploff, d_planes);
+    hipLaunchKernelGGL(motif_count_hbm, dim3(n, (max_period + MOTIF_T - 1) / MOTIF_T), dim3(MOTIF_T), 0, ctx->stream, rows.len, n, max_period, d_ploff, d_planes, d_moff, d_m);
   }
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  hipLaunchKernelGGL(motif_reduce_unit, dim3(grid), dim3(MOTIF_T), 0, ctx->stream, d_arena, d_off, d_len, n, max_period, slack, d_moff, d_m, d_rec, d_unit, unit_stride);
+  hipLaunchKernelGGL(motif_reduce_unit, dim3(grid), dim3(MOTIF_T), 0, ctx->stream, rows.arena, rows.off, rows.len, n, max_period, slack, d_moff, d_m, d_rec, d_unit, unit_stride);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
   if (out) HIP_TRY(ctx, hipMemcpyAsync(out, d_rec, rec_bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -278,7 +278,7 @@ int otg_motif_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, co
   HIP_TRY(ctx, hipEventElapsedTime(&r_ms, ctx->ev1, ctx->ev2));
   ctx->last_motif_count_ms = c_ms; ctx->last_motif_reduce_ms = r_ms;
   ctx->last_motif_n = n; ctx->last_motif_stride = unit_stride;
-  ctx->last_motif_arena = d_arena; ctx->last_motif_off = d_off; ctx->last_motif_len = d_len;
+  ctx->last_motif_rows = rows;
   return OTG_OK;
 }
 
@@ -295,30 +295,15 @@ extern "C" int otg_motif_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t 
 {
   if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_motif_batch: no context (no HIP device?)");
   if (int rc = otg_motif_args(ctx, "otg_motif_batch", max_period, slack)) return rc;
-  if (n && (!seq_off || !seq_len || (arena_bytes && !seq_arena))) return otg_fail(ctx, OTG_ERR_ARG, "otg_motif_batch: NULL argument");
   uint32_t max_len = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (seq_off[i] > arena_bytes || seq_len[i] > arena_bytes - seq_off[i])
-      return otg_fail(ctx, OTG_ERR_ARG, "otg_motif_batch: allele %u (offset %llu, length %u) lies outside the %llu-byte arena", i,
-                      (unsigned long long)seq_off[i], seq_len[i], (unsigned long long)arena_bytes);
-    max_len = std::max(max_len, seq_len[i]);
-  }
+  if (int rc = otg_rows_check(ctx, "otg_motif_batch", seq_arena, arena_bytes, seq_off, seq_len, n, &max_len)) return rc;
   if (int rc = otg_motif_stride_fits(ctx, "otg_motif_batch", max_len, max_period, unit_stride)) return rc;
   ctx->last_motif_count_ms = ctx->last_motif_reduce_ms = 0.0;
   ctx->last_motif_n = 0; ctx->last_motif_stride = 0;
   if (n == 0) return OTG_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  // the rows: the arena and seq_off (u64) | seq_len (u32)
-  uint8_t* d_arena = (uint8_t*)otg_slot(ctx, SLOT_MOTIF_SEQ, arena_bytes + 64);
-  uint8_t* d_meta = (uint8_t*)otg_slot(ctx, SLOT_MOTIF_META, (size_t)n * 12);
-  if (!d_arena || !d_meta) return OTG_ERR_HIP;
-  uint64_t* d_off = (uint64_t*)d_meta;
-  uint32_t* d_len = (uint32_t*)(d_meta + (size_t)n * 8);
-  HIP_TRY(ctx, hipMemsetAsync(d_arena + arena_bytes, 0, 64, ctx->stream));
-  if (arena_bytes) HIP_TRY(ctx, hipMemcpyAsync(d_arena, seq_arena, arena_bytes, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_off, seq_off, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_len, seq_len, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-  return otg_motif_resident(ctx, "otg_motif_batch", d_arena, d_off, d_len, n, max_period, slack, out, unit_out, unit_stride);
+  OtgRows rows;
+  if (int rc = otg_rows_upload(ctx, SLOT_MOTIF_SEQ, SLOT_MOTIF_META, seq_arena, arena_bytes, seq_off, seq_len, n, &rows)) return rc;
+  return otg_motif_resident(ctx, "otg_motif_batch", rows, n, max_period, slack, out, unit_out, unit_stride);
 }
 
 extern "C" int otg_motif_device_results(otg_ctx* ctx, uint32_t* n, const otg_motif** records, const uint8_t** units, uint32_t* unit_stride)

@@ -35,8 +35,5 @@ extern "C" int otg_motif_emit(const otg_vcf_record* records, uint32_t n_records,
                         motifs[(uint64_t)records[r].first_allele + i].period, unit_stride);
   std::string text;
   otg_motif_rows(text, records, n_records, region_arena, seq_len, motifs, units, unit_stride);
-  *out_len = text.size();
-  if (text.size() > out_capacity || (!out && !text.empty())) return otg_fail(nullptr, OTG_ERR_CAPACITY, "otg_motif_emit: output buffer too small");
-  if (!text.empty()) memcpy(out, text.data(), text.size());
-  return OTG_OK;
+  return otg_text_out("otg_motif_emit", text, out, out_capacity, out_len);
 }

@@ -47,6 +47,76 @@ void* otg_slot(otg_ctx* ctx, int slot, size_t bytes)
   return b.p;
 }
 
+int otg_rows_check(otg_ctx* ctx, const char* who, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* off, const uint32_t* len, uint32_t n,
+                   uint32_t* max_len)
+{
+  if (n && (!off || !len || (arena_bytes && !arena))) return otg_fail(ctx, OTG_ERR_ARG, "%s: NULL argument", who);
+  uint32_t longest = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (off[i] > arena_bytes || len[i] > arena_bytes - off[i])
+      return otg_fail(ctx, OTG_ERR_ARG, "%s: allele %u (offset %llu, length %u) lies outside the %llu-byte arena", who, i, (unsigned long long)off[i], len[i],
+                      (unsigned long long)arena_bytes);
+    longest = std::max(longest, len[i]);
+  }
+  if (max_len) *max_len = longest;
+  return OTG_OK;
+}
+
+int otg_rows_upload(otg_ctx* ctx, int slot_seq, int slot_meta, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* off, const uint32_t* len,
+                    uint32_t n, OtgRows* out)
+{
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  uint8_t* d_arena = (uint8_t*)otg_slot(ctx, slot_seq, arena_bytes + 64);
+  uint8_t* d_meta = (uint8_t*)otg_slot(ctx, slot_meta, (size_t)n * 12);
+  if (!d_arena || !d_meta) return OTG_ERR_HIP;
+  uint64_t* d_off = (uint64_t*)d_meta;
+  uint32_t* d_len = (uint32_t*)(d_meta + (size_t)n * 8);
+  HIP_TRY(ctx, hipMemsetAsync(d_arena + arena_bytes, 0, 64, ctx->stream));
+  if (arena_bytes) HIP_TRY(ctx, hipMemcpyAsync(d_arena, arena, arena_bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_off, off, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_len, len, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+  *out = OtgRows{d_arena, d_off, d_len};
+  return OTG_OK;
+}
+
+int otg_seg_collect(otg_ctx* ctx, const char* who, const char* noun, OtgSegLast otg_ctx::*which, int slot_segs, size_t seg_bytes, void* segs, uint64_t capacity)
+{
+  if (!ctx) return otg_fail(nullptr, OTG_ERR_ARG, "%s: NULL context", who);
+  if (!(ctx->*which).valid) return otg_fail(ctx, OTG_ERR_ARG, "%s: no %s results on this context", who, noun);
+  const uint64_t total = (ctx->*which).total;
+  if (capacity < total)
+    return otg_fail(ctx, OTG_ERR_CAPACITY, "%s: capacity %llu, the latest call has %llu segments", who, (unsigned long long)capacity, (unsigned long long)total);
+  if (total == 0) return OTG_OK;
+  if (!segs) return otg_fail(ctx, OTG_ERR_ARG, "%s: NULL segs", who);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipMemcpyAsync(segs, ctx->pool[slot_segs].p, (size_t)total * seg_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return OTG_OK;
+}
+
+int otg_seg_device_results(otg_ctx* ctx, const char* who, const char* noun, OtgSegLast otg_ctx::*which, int slot_res, int slot_segs, size_t sum_bytes, uint32_t* n,
+                           const void** sums, const uint64_t** seg_off, const void** segs, uint64_t* total)
+{
+  if (!ctx) return otg_fail(nullptr, OTG_ERR_ARG, "%s: NULL context", who);
+  const OtgSegLast& last = ctx->*which;
+  if (!last.valid) return otg_fail(ctx, OTG_ERR_ARG, "%s: no %s results on this context", who, noun);
+  const uint8_t* res = (const uint8_t*)ctx->pool[slot_res].p;
+  if (n) *n = last.n;
+  if (sums) *sums = res;
+  if (seg_off) *seg_off = (const uint64_t*)(res + (size_t)last.n * sum_bytes);
+  if (segs) *segs = ctx->pool[slot_segs].p;
+  if (total) *total = last.total;
+  return OTG_OK;
+}
+
+int otg_text_out(const char* who, const std::string& text, char* out, uint64_t capacity, uint64_t* out_len)
+{
+  *out_len = text.size();
+  if (text.size() > capacity || (!out && !text.empty())) return otg_fail(nullptr, OTG_ERR_CAPACITY, "%s: output buffer too small", who);
+  if (!text.empty()) memcpy(out, text.data(), text.size());
+  return OTG_OK;
+}
+
 // ---- glibc exp() restated on the host, used ONLY to detect which build of exp() the host libm runs
 // (the device KDE mirrors that build bit for bit; see cluster.hip / DESIGN.md §5). -------------------
 #include "exp_table.inc"

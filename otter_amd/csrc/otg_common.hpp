@@ -16,6 +16,18 @@ struct DevBuf {
   size_t cap = 0;
 };
 
+// The rows of an allele operator on the device: row i is arena[off[i] .. + len[i]).  A caller's rows come through otg_rows_check and
+// otg_rows_upload into the operator's own slot pair (64 zero bytes behind the arena: the kernels read past a row's end); a cohort's lie
+// in its staging area (cohort.hip).  Kernels and their argument structs take it whole.
+struct OtgRows { const uint8_t* arena; const uint64_t* off; const uint32_t* len; };
+
+// What an operator with segments leaves on the context: n summaries and n + 1 offsets in its RES slot, `total` segments in its SEGS slot
+// (otg_seg_collect, otg_seg_device_results) and its two HIP-event times.  valid: such a call with n > 0 has succeeded since the last one began.
+struct OtgSegLast {
+  uint32_t n = 0; uint64_t total = 0; bool valid = false;
+  double ms[2] = {0.0, 0.0};
+};
+
 struct otg_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -46,20 +58,11 @@ struct otg_ctx {
   hipEvent_t ev2 = nullptr;                       // third timing event, created on first use (kmer_usage.hip, motif.hip)
   double last_motif_count_ms = 0.0, last_motif_reduce_ms = 0.0;   // HIP-event times of the latest otg_motif_batch / otg_motif_cohort (otg_motif_last_ms)
   uint32_t last_motif_n = 0, last_motif_stride = 0;               // the shape of the results in SLOT_MOTIF_OUT (otg_motif_device_results)
-  double last_repeat_runs_ms = 0.0, last_repeat_select_ms = 0.0;  // HIP-event times of the latest otg_repeat_batch / otg_repeat_cohort (otg_repeat_last_ms)
-  uint32_t last_repeat_n = 0;                                     // the shape of the results in SLOT_REPEAT_RES / SLOT_REPEAT_SEGS (otg_repeat_device_results);
-  uint64_t last_repeat_total = 0;                                 // valid: a repeat call with n > 0 has succeeded since the last one began
-  bool last_repeat_valid = false;
-  // where the latest motif call read its alleles (device pointers, n = last_motif_n): otg_unitalign_motifs aligns them in place
-  const uint8_t* last_motif_arena = nullptr;
-  const uint64_t* last_motif_off = nullptr;
-  const uint32_t* last_motif_len = nullptr;
+  OtgSegLast last_repeat;                                         // the latest otg_repeat_batch / otg_repeat_cohort: SLOT_REPEAT_RES / SLOT_REPEAT_SEGS, ms = runs, select
+  OtgRows last_motif_rows = {nullptr, nullptr, nullptr};                                  // where the latest motif call read its alleles (n = last_motif_n): otg_unitalign_motifs aligns them in place
   double last_unitalign_ms = 0.0;                                 // HIP-event time of the latest unit alignment (otg_unitalign_last_ms)
   uint32_t last_unitalign_n = 0;                                  // the records in SLOT_UNITALIGN_OUT (otg_unitalign_device_results); 0: none
-  double last_unitparse_forward_ms = 0.0, last_unitparse_trace_ms = 0.0;   // HIP-event times of the latest unit parse (otg_unitparse_last_ms)
-  uint32_t last_unitparse_n = 0;                                  // the shape of the results in SLOT_UNITPARSE_RES / SLOT_UNITPARSE_SEGS (otg_unitparse_device_results);
-  uint64_t last_unitparse_total = 0;                              // valid: a unit parse with n > 0 has succeeded since the last one began
-  bool last_unitparse_valid = false;
+  OtgSegLast last_unitparse;                                      // the latest unit parse: SLOT_UNITPARSE_RES / SLOT_UNITPARSE_SEGS, ms = forward, traceback
   double last_kernel_ms = 0.0;                    // HIP-event time of the kernels of the latest operator-level call that reports one (otg_last_kernel_ms)
   // the latest genotype clustering with a metric (genotype_edit.hip): times of its two parts (otg_genotype_metric_last_ms), whether the edit
   // matrix was built, and where its counters lie in SLOT_GTE_CLS
@@ -98,6 +101,38 @@ int otg_fail(otg_ctx* ctx, int code, const char* fmt, ...);
 
 // Grow-only device allocation slot; returns nullptr on failure (error recorded).
 void* otg_slot(otg_ctx* ctx, int slot, size_t bytes);
+// A caller's rows (host arrays): the NULL and range refusals under the entry's name `who` (max_len, nullable: the longest row), and the
+// copy into the slot pair slot_seq (arena_bytes + 64, the tail zeroed) / slot_meta (off | len), enqueued on ctx->stream.
+int otg_rows_check(otg_ctx* ctx, const char* who, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* off, const uint32_t* len, uint32_t n,
+                   uint32_t* max_len);
+int otg_rows_upload(otg_ctx* ctx, int slot_seq, int slot_meta, const uint8_t* arena, uint64_t arena_bytes, const uint64_t* off, const uint32_t* len,
+                    uint32_t n, OtgRows* out);
+// The segments of the latest call behind the context's member `which` into the caller's buffer, and where its results lie on the device; who = the exported
+// entry, noun = what the refusal calls the results ("repeat", "unit parse"), sum_bytes / seg_bytes = the sizes of a summary and a segment.
+int otg_seg_collect(otg_ctx* ctx, const char* who, const char* noun, OtgSegLast otg_ctx::*which, int slot_segs, size_t seg_bytes, void* segs, uint64_t capacity);
+int otg_seg_device_results(otg_ctx* ctx, const char* who, const char* noun, OtgSegLast otg_ctx::*which, int slot_res, int slot_segs, size_t sum_bytes, uint32_t* n,
+                           const void** sums, const uint64_t** seg_off, const void** segs, uint64_t* total);
+// The tail of an emit entry: the size into *out_len, the text into the caller's buffer, or OTG_ERR_CAPACITY
+int otg_text_out(const char* who, const std::string& text, char* out, uint64_t capacity, uint64_t* out_len);
+
+// The refusals otg_unitalign_check and otg_unitparse_check share, in their order: the NULL test (lists_null: one of the caller's own lists is
+// missing), per unit the caller's length rule (unit_rule(k, length) -> its refusal or OTG_OK) and the range, the caller's own lists
+// (lists() -> likewise), the task cap.
+template <typename UnitRule, typename Lists>
+int otg_unit_lists_check(otg_ctx* ctx, const char* who, bool lists_null, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off,
+                         const uint32_t* unit_len, uint32_t n_units, uint32_t n_tasks, UnitRule unit_rule, Lists lists)
+{
+  if ((n_units && (!unit_off || !unit_len || (unit_bytes && !unit_arena))) || lists_null) return otg_fail(ctx, OTG_ERR_ARG, "%s: NULL argument", who);
+  for (uint32_t k = 0; k < n_units; ++k) {
+    if (int rc = unit_rule(k, unit_len[k])) return rc;
+    if (unit_off[k] > unit_bytes || unit_len[k] > unit_bytes - unit_off[k])
+      return otg_fail(ctx, OTG_ERR_ARG, "%s: unit %u (offset %llu, length %u) lies outside the %llu-byte unit arena", who, k, (unsigned long long)unit_off[k],
+                      unit_len[k], (unsigned long long)unit_bytes);
+  }
+  if (int rc = lists()) return rc;
+  if (n_tasks > (1u << 24)) return otg_fail(ctx, OTG_ERR_CAPACITY, "%s: %u tasks in one call, at most %u", who, n_tasks, 1u << 24);
+  return OTG_OK;
+}
 
 // cluster.hip: regions of up to this many valid reads (assemble) / alleles (genotype) keep their clustering scratch in LDS; the callers of
 // otg_launch_cluster / otg_launch_genotype list the regions above it, which run on the wide kernels
@@ -369,14 +404,14 @@ int otg_genotype_metric_finish(otg_ctx* ctx, int metric, uint64_t* n_aligned);
 // kmer_usage.hip: the workspace refusal of otg_kmer_usage_batch (OTG_ERR_CAPACITY, nothing allocated) and its launch part on device-resident
 // rows; see the definitions
 int otg_kmer_usage_fits(otg_ctx* ctx, const char* who, uint32_t n, int32_t k);
-int otg_kmer_usage_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, const uint32_t* h_blk,
+int otg_kmer_usage_resident(otg_ctx* ctx, const char* who, const OtgRows& rows, const uint32_t* h_blk,
                             uint32_t n, int32_t k, double* usage_out, double* gc_out, double* hsd_out);
 
 // motif.hip: the argument refusals of otg_motif_batch (max_period, slack; unit_stride against the longest row) and its launch part on
 // device-resident rows; see the definitions
 int otg_motif_args(otg_ctx* ctx, const char* who, uint32_t max_period, uint32_t slack);
 int otg_motif_stride_fits(otg_ctx* ctx, const char* who, uint32_t max_len, uint32_t max_period, uint32_t unit_stride);
-int otg_motif_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, uint32_t n,
+int otg_motif_resident(otg_ctx* ctx, const char* who, const OtgRows& rows, uint32_t n,
                        uint32_t max_period, uint32_t slack, otg_motif* out, uint8_t* unit_out, uint32_t unit_stride);
 // motif.hip: the HBM plane tier, shared with repeat.hip.  The longest allele of the LDS tier (0 under OTG_MOTIF_WIDE); the scan of the plane
 // words per allele into d_ploff (n + 1; an allele of the LDS tier or without a period has none) and *d_total; the pack kernel on those offsets.
@@ -384,13 +419,13 @@ uint32_t otg_motif_lds_len();
 void otg_motif_plane_scan(otg_ctx* ctx, const uint32_t* d_len, uint32_t n, uint32_t max_period, uint32_t lds_len, uint64_t* d_ploff, uint64_t* d_total);
 void otg_motif_pack_planes(otg_ctx* ctx, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, uint32_t n, const uint64_t* d_ploff,
                            uint32_t* d_planes);
-// unitalign.hip: the launch part of the unit alignment on device-resident alleles and units.  Allele a is d_arena[d_off[a] .. + d_len[a]) (the
+// unitalign.hip: the launch part of the unit alignment on device-resident alleles and units.  Allele a is rows.arena[rows.off[a] .. + rows.len[a]) (the
 // arena extends 15 bytes past every row).  Unit k is d_units[d_unit_off[k] .. + d_unit_len[k]), or with d_unit_off == NULL the slot
 // d_units + k * unit_stride whose length is d_motifs[k].period.  Task t aligns allele d_task_seq[t] to unit d_task_unit[t]; NULL lists: t.
 struct OtgUnitSource {
   const uint8_t* d_units; const uint64_t* d_unit_off; const uint32_t* d_unit_len; const otg_motif* d_motifs; uint32_t unit_stride;
 };
-int otg_unitalign_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, const OtgUnitSource& units,
+int otg_unitalign_resident(otg_ctx* ctx, const char* who, const OtgRows& rows, const OtgUnitSource& units,
                            const uint32_t* d_task_seq, const uint32_t* d_task_unit, uint32_t n_tasks, otg_unitalign* out);
 // its refusals of a caller's units and task lists (host arrays), and the upload of both into the context's slots
 int otg_unitalign_check(otg_ctx* ctx, const char* who, uint32_t n_seqs, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off,
@@ -400,17 +435,17 @@ int otg_unitalign_upload(otg_ctx* ctx, const uint8_t* unit_arena, uint64_t unit_
                          const uint32_t** d_task_unit);
 // unitparse.hip: the refusals of a caller's unit sets and task lists (host arrays), and the launch part of the joint unit parse on
 // device-resident alleles (the arena extends 15 bytes past every row).  The units, sets and task lists are host arrays and are uploaded here;
-// h_len = the allele lengths on the host, NULL: they are read back from d_len.
+// h_len = the allele lengths on the host, NULL: they are read back from rows.len.
 int otg_unitparse_check(otg_ctx* ctx, const char* who, uint32_t n_seqs, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off,
                         const uint32_t* unit_len, uint32_t n_units, const uint64_t* set_first, uint32_t n_sets, const uint32_t* task_seq,
                         const uint32_t* task_set, uint32_t n_tasks);
-int otg_unitparse_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, const uint32_t* h_len,
+int otg_unitparse_resident(otg_ctx* ctx, const char* who, const OtgRows& rows, const uint32_t* h_len,
                            uint32_t n_seqs, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off, const uint32_t* unit_len,
                            uint32_t n_units, const uint64_t* set_first, uint32_t n_sets, const uint32_t* task_seq, const uint32_t* task_set, uint32_t n_tasks,
                            otg_unitparse_sum* sums, uint64_t* seg_off, uint64_t* n_segments);
 // repeat.hip: the argument refusals of otg_repeat_batch and its launch part on device-resident rows (cohort.hip), as the motif pair above
 int otg_repeat_args(otg_ctx* ctx, const char* who, uint32_t max_period, uint32_t min_copies, uint32_t min_span);
-int otg_repeat_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, uint32_t n,
+int otg_repeat_resident(otg_ctx* ctx, const char* who, const OtgRows& rows, uint32_t n,
                         uint32_t max_period, uint32_t min_copies, uint32_t min_span, otg_repeat_sum* sums, uint64_t* seg_off, uint64_t* n_segments);
 
 // cluster.hip (genotype_kernel)

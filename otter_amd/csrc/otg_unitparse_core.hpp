@@ -31,6 +31,7 @@ namespace otg_unitparse_core {
 using otg_unitalign_core::ua_class_lanes;
 using otg_unitalign_core::ua_class_regs;
 using otg_unitalign_core::ua_fold;
+using otg_unitalign_core::ua_scan_take;
 using otg_unitalign_core::ua_unit_key;
 
 constexpr int UP_FIELD = 21;                                       // bits of unit_bases and of switches; the edits take the 22 above
@@ -77,7 +78,6 @@ OTG_UP_HD uint64_t up_vert(uint64_t up) { return up + up_e(); }
 // the scan bias of position j of a unit of p bases and the way on from phase 0 to j (otg_unitalign_core.hpp derives the scan)
 OTG_UP_HD uint64_t up_bias(uint32_t j, uint32_t p) { return (uint64_t)(p - 1u - j) * up_w(); }
 OTG_UP_HD uint64_t up_onward(uint32_t j) { return (uint64_t)j * up_w(); }
-OTG_UP_HD uint64_t up_scan_take(uint64_t x, uint64_t from, bool ok) { return ok && from < x ? from : x; }
 // the phase-0 candidate of a unit from inside it: its own phase-0 cell, or its last position (after the scan) plus one skip
 OTG_UP_HD uint64_t up_phase0(uint64_t cell0, uint64_t last) { return up_min(cell0, last + up_w()); }
 // what reaches phase 0 of a unit from behind: its own last position, or the smallest phase-0 candidate of the set plus one switch

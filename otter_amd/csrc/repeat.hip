@@ -224,12 +224,6 @@ __global__ __launch_bounds__(REPEAT_T) void repeat_compact(uint32_t n, const otg
   }
 }
 
-void repeat_forget(otg_ctx* ctx)
-{
-  ctx->last_repeat_runs_ms = ctx->last_repeat_select_ms = 0.0;
-  ctx->last_repeat_n = 0; ctx->last_repeat_total = 0; ctx->last_repeat_valid = false;
-}
-
 } // namespace
 
 int otg_repeat_args(otg_ctx* ctx, const char* who, uint32_t max_period, uint32_t min_copies, uint32_t min_span)
@@ -241,12 +235,12 @@ int otg_repeat_args(otg_ctx* ctx, const char* who, uint32_t max_period, uint32_t
   return OTG_OK;
 }
 
-// The launch part of otg_repeat_batch on device-resident rows, as otg_motif_resident: row i is d_arena[d_off[i] .. + d_len[i]), the arena
+// The launch part of otg_repeat_batch on device-resident rows, as otg_motif_resident: row i is rows.arena[rows.off[i] .. + rows.len[i]), the arena
 // extends 31 bytes past every row.  The results land in SLOT_REPEAT_RES (n summaries, then n + 1 offsets) and SLOT_REPEAT_SEGS.
-int otg_repeat_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, uint32_t n,
-                        uint32_t max_period, uint32_t min_copies, uint32_t min_span, otg_repeat_sum* sums, uint64_t* seg_off, uint64_t* n_segments)
+int otg_repeat_resident(otg_ctx* ctx, const char* who, const OtgRows& rows, uint32_t n, uint32_t max_period, uint32_t min_copies, uint32_t min_span,
+                        otg_repeat_sum* sums, uint64_t* seg_off, uint64_t* n_segments)
 {
-  repeat_forget(ctx);
+  ctx->last_repeat = OtgSegLast{};
   if (n_segments) *n_segments = 0;
   if (n == 0) {
     if (seg_off) seg_off[0] = 0;
@@ -269,8 +263,8 @@ int otg_repeat_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, c
   otg_repeat_sum* d_sums = (otg_repeat_sum*)d_res;
   uint64_t* d_segoff = (uint64_t*)(d_res + (size_t)n * sizeof(otg_repeat_sum));
   HIP_TRY(ctx, hipMemsetAsync(d_tot, 0, 40, ctx->stream));
-  hipLaunchKernelGGL((otg_scan_kernel<uint64_t, uint64_t, RpPeriods>), dim3(1), dim3(1024), 0, ctx->stream, RpPeriods{d_len, max_period}, n, d_moff, d_tot);
-  otg_motif_plane_scan(ctx, d_len, n, max_period, lds_len, d_ploff, d_tot + 1);
+  hipLaunchKernelGGL((otg_scan_kernel<uint64_t, uint64_t, RpPeriods>), dim3(1), dim3(1024), 0, ctx->stream, RpPeriods{rows.len, max_period}, n, d_moff, d_tot);
+  otg_motif_plane_scan(ctx, rows.len, n, max_period, lds_len, d_ploff, d_tot + 1);
   HIP_TRY(ctx, hipGetLastError());
   uint64_t tot[4] = {0, 0, 0, 0};
   HIP_TRY(ctx, hipMemcpyAsync(tot, d_tot, 16, hipMemcpyDeviceToHost, ctx->stream));
@@ -284,14 +278,14 @@ int otg_repeat_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, c
   const dim3 hbm_grid(n, (max_period + REPEAT_T - 1) / REPEAT_T);
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   if (lds_len)
-    hipLaunchKernelGGL(repeat_runs_lds<false>, dim3(grid), dim3(REPEAT_T), 0, ctx->stream, d_arena, d_off, d_len, n, max_period, lds_len, min_copies, min_span,
+    hipLaunchKernelGGL(repeat_runs_lds<false>, dim3(grid), dim3(REPEAT_T), 0, ctx->stream, rows.arena, rows.off, rows.len, n, max_period, lds_len, min_copies, min_span,
                        d_moff, d_cnt, nullptr, nullptr, nullptr);
   if (tot[1]) {
-    otg_motif_pack_planes(ctx, d_arena, d_off, d_len, n, d_ploff, d_planes);
-    hipLaunchKernelGGL(repeat_runs_hbm<false>, hbm_grid, dim3(REPEAT_T), 0, ctx->stream, d_len, n, max_period, min_copies, min_span, d_ploff, d_planes, d_moff,
+    otg_motif_pack_planes(ctx, rows.arena, rows.off, rows.len, n, d_ploff, d_planes);
+    hipLaunchKernelGGL(repeat_runs_hbm<false>, hbm_grid, dim3(REPEAT_T), 0, ctx->stream, rows.len, n, max_period, min_copies, min_span, d_ploff, d_planes, d_moff,
                        d_cnt, nullptr, nullptr, nullptr);
   }
-  hipLaunchKernelGGL(repeat_scan_periods, dim3(grid), dim3(REPEAT_T), 0, ctx->stream, d_len, n, max_period, d_moff, d_cnt, d_pre, d_k);
+  hipLaunchKernelGGL(repeat_scan_periods, dim3(grid), dim3(REPEAT_T), 0, ctx->stream, rows.len, n, max_period, d_moff, d_cnt, d_pre, d_k);
   hipLaunchKernelGGL((otg_scan_kernel<uint64_t, uint64_t, OtgScanPtr<uint32_t>>), dim3(1), dim3(1024), 0, ctx->stream, OtgScanPtr<uint32_t>{d_k}, n, d_runoff, d_tot + 2);
   hipLaunchKernelGGL((otg_scan_kernel<uint64_t, uint64_t, RpSegCap>), dim3(1), dim3(1024), 0, ctx->stream, RpSegCap{d_k}, n, d_scoff, d_tot + 3);
   HIP_TRY(ctx, hipGetLastError());
@@ -304,15 +298,15 @@ int otg_repeat_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, c
   if (!d_runs || !d_stack || !d_scratch) return OTG_ERR_HIP;
   if (tot[2]) {
     if (lds_len)
-      hipLaunchKernelGGL(repeat_runs_lds<true>, dim3(grid), dim3(REPEAT_T), 0, ctx->stream, d_arena, d_off, d_len, n, max_period, lds_len, min_copies, min_span,
+      hipLaunchKernelGGL(repeat_runs_lds<true>, dim3(grid), dim3(REPEAT_T), 0, ctx->stream, rows.arena, rows.off, rows.len, n, max_period, lds_len, min_copies, min_span,
                          d_moff, d_cnt, d_pre, d_runoff, d_runs);
     if (tot[1])
-      hipLaunchKernelGGL(repeat_runs_hbm<true>, hbm_grid, dim3(REPEAT_T), 0, ctx->stream, d_len, n, max_period, min_copies, min_span, d_ploff, d_planes, d_moff,
+      hipLaunchKernelGGL(repeat_runs_hbm<true>, hbm_grid, dim3(REPEAT_T), 0, ctx->stream, rows.len, n, max_period, min_copies, min_span, d_ploff, d_planes, d_moff,
                          d_cnt, d_pre, d_runoff, d_runs);
   }
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  hipLaunchKernelGGL(repeat_select, dim3(grid), dim3(REPEAT_T), 0, ctx->stream, d_arena, d_off, d_len, n, min_copies, min_span, d_runoff, d_runs, d_stack, d_scoff,
+  hipLaunchKernelGGL(repeat_select, dim3(grid), dim3(REPEAT_T), 0, ctx->stream, rows.arena, rows.off, rows.len, n, min_copies, min_span, d_runoff, d_runs, d_stack, d_scoff,
                      d_scratch, d_sums, d_over);
   hipLaunchKernelGGL((otg_scan_kernel<uint64_t, uint64_t, RpSegCount>), dim3(1), dim3(1024), 0, ctx->stream, RpSegCount{d_sums}, n, d_segoff, d_tot);
   HIP_TRY(ctx, hipGetLastError());
@@ -332,8 +326,7 @@ int otg_repeat_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, c
   float r_ms = 0.f, s_ms = 0.f;
   HIP_TRY(ctx, hipEventElapsedTime(&r_ms, ctx->ev0, ctx->ev1));
   HIP_TRY(ctx, hipEventElapsedTime(&s_ms, ctx->ev1, ctx->ev2));
-  ctx->last_repeat_runs_ms = r_ms; ctx->last_repeat_select_ms = s_ms;
-  ctx->last_repeat_n = n; ctx->last_repeat_total = total; ctx->last_repeat_valid = true;
+  ctx->last_repeat = OtgSegLast{n, total, true, {r_ms, s_ms}};
   if (n_segments) *n_segments = total;
   return OTG_OK;
 }
@@ -344,61 +337,29 @@ extern "C" int otg_repeat_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t
 {
   if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_repeat_batch: no context (no HIP device?)");
   if (int rc = otg_repeat_args(ctx, "otg_repeat_batch", max_period, min_copies, min_span)) return rc;
-  if (n && (!seq_off || !seq_len || (arena_bytes && !seq_arena))) return otg_fail(ctx, OTG_ERR_ARG, "otg_repeat_batch: NULL argument");
-  for (uint32_t i = 0; i < n; ++i)
-    if (seq_off[i] > arena_bytes || seq_len[i] > arena_bytes - seq_off[i])
-      return otg_fail(ctx, OTG_ERR_ARG, "otg_repeat_batch: allele %u (offset %llu, length %u) lies outside the %llu-byte arena", i,
-                      (unsigned long long)seq_off[i], seq_len[i], (unsigned long long)arena_bytes);
-  if (n == 0 || n > (1u << 24))
-    return otg_repeat_resident(ctx, "otg_repeat_batch", nullptr, nullptr, nullptr, n, max_period, min_copies, min_span, sums, seg_off, n_segments);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  // the rows: the arena and seq_off (u64) | seq_len (u32)
-  uint8_t* d_arena = (uint8_t*)otg_slot(ctx, SLOT_REPEAT_SEQ, arena_bytes + 64);
-  uint8_t* d_meta = (uint8_t*)otg_slot(ctx, SLOT_REPEAT_META, (size_t)n * 12);
-  if (!d_arena || !d_meta) return OTG_ERR_HIP;
-  uint64_t* d_off = (uint64_t*)d_meta;
-  uint32_t* d_len = (uint32_t*)(d_meta + (size_t)n * 8);
-  HIP_TRY(ctx, hipMemsetAsync(d_arena + arena_bytes, 0, 64, ctx->stream));
-  if (arena_bytes) HIP_TRY(ctx, hipMemcpyAsync(d_arena, seq_arena, arena_bytes, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_off, seq_off, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_len, seq_len, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-  return otg_repeat_resident(ctx, "otg_repeat_batch", d_arena, d_off, d_len, n, max_period, min_copies, min_span, sums, seg_off, n_segments);
+  if (int rc = otg_rows_check(ctx, "otg_repeat_batch", seq_arena, arena_bytes, seq_off, seq_len, n, nullptr)) return rc;
+  OtgRows rows = {nullptr, nullptr, nullptr};
+  if (n != 0 && n <= (1u << 24))                                  // (otherwise the launch part answers before it reads a row)
+    if (int rc = otg_rows_upload(ctx, SLOT_REPEAT_SEQ, SLOT_REPEAT_META, seq_arena, arena_bytes, seq_off, seq_len, n, &rows)) return rc;
+  return otg_repeat_resident(ctx, "otg_repeat_batch", rows, n, max_period, min_copies, min_span, sums, seg_off, n_segments);
 }
 
 extern "C" int otg_repeat_collect(otg_ctx* ctx, otg_repeat_seg* segs, uint64_t capacity)
 {
-  if (!ctx) return otg_fail(nullptr, OTG_ERR_ARG, "otg_repeat_collect: NULL context");
-  if (!ctx->last_repeat_valid) return otg_fail(ctx, OTG_ERR_ARG, "otg_repeat_collect: no repeat results on this context");
-  const uint64_t total = ctx->last_repeat_total;
-  if (capacity < total)
-    return otg_fail(ctx, OTG_ERR_CAPACITY, "otg_repeat_collect: capacity %llu, the latest call has %llu segments", (unsigned long long)capacity,
-                    (unsigned long long)total);
-  if (total == 0) return OTG_OK;
-  if (!segs) return otg_fail(ctx, OTG_ERR_ARG, "otg_repeat_collect: NULL segs");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipMemcpyAsync(segs, ctx->pool[SLOT_REPEAT_SEGS].p, (size_t)total * sizeof(otg_repeat_seg), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return OTG_OK;
+  return otg_seg_collect(ctx, "otg_repeat_collect", "repeat", &otg_ctx::last_repeat, SLOT_REPEAT_SEGS, sizeof(otg_repeat_seg), segs, capacity);
 }
 
 extern "C" int otg_repeat_device_results(otg_ctx* ctx, uint32_t* n, const otg_repeat_sum** sums, const uint64_t** seg_off, const otg_repeat_seg** segs,
                                          uint64_t* total)
 {
-  if (!ctx) return otg_fail(nullptr, OTG_ERR_ARG, "otg_repeat_device_results: NULL context");
-  if (!ctx->last_repeat_valid) return otg_fail(ctx, OTG_ERR_ARG, "otg_repeat_device_results: no repeat results on this context");
-  const uint8_t* res = (const uint8_t*)ctx->pool[SLOT_REPEAT_RES].p;
-  if (n) *n = ctx->last_repeat_n;
-  if (sums) *sums = (const otg_repeat_sum*)res;
-  if (seg_off) *seg_off = (const uint64_t*)(res + (size_t)ctx->last_repeat_n * sizeof(otg_repeat_sum));
-  if (segs) *segs = (const otg_repeat_seg*)ctx->pool[SLOT_REPEAT_SEGS].p;
-  if (total) *total = ctx->last_repeat_total;
-  return OTG_OK;
+  return otg_seg_device_results(ctx, "otg_repeat_device_results", "repeat", &otg_ctx::last_repeat, SLOT_REPEAT_RES, SLOT_REPEAT_SEGS, sizeof(otg_repeat_sum), n,
+                                (const void**)sums, seg_off, (const void**)segs, total);
 }
 
 extern "C" int otg_repeat_last_ms(otg_ctx* ctx, double* runs_ms, double* select_ms)
 {
   if (!ctx) return otg_fail(nullptr, OTG_ERR_ARG, "otg_repeat_last_ms: NULL context");
-  if (runs_ms) *runs_ms = ctx->last_repeat_runs_ms;
-  if (select_ms) *select_ms = ctx->last_repeat_select_ms;
+  if (runs_ms) *runs_ms = ctx->last_repeat.ms[0];
+  if (select_ms) *select_ms = ctx->last_repeat.ms[1];
   return OTG_OK;
 }

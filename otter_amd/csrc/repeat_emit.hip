@@ -48,8 +48,5 @@ extern "C" int otg_repeat_emit(const otg_vcf_record* records, uint32_t n_records
     }
   std::string text;
   otg_repeat_rows(text, records, n_records, region_arena, seq_arena, seq_off, seq_len, sums, seg_off, segs);
-  *out_len = text.size();
-  if (text.size() > out_capacity || (!out && !text.empty())) return otg_fail(nullptr, OTG_ERR_CAPACITY, "otg_repeat_emit: output buffer too small");
-  if (!text.empty()) memcpy(out, text.data(), text.size());
-  return OTG_OK;
+  return otg_text_out("otg_repeat_emit", text, out, out_capacity, out_len);
 }

@@ -4,10 +4,10 @@
 // One task is a pair (allele, unit).  The row of the wraparound DP lives in registers, unit positions across lanes, and the kernel walks the
 // bases of the allele.  A task takes a segment of S = 4 .. 64 lanes, the smallest power of two that holds its unit, so a wave carries 16 .. 1
 // tasks; units of 65 .. 128 and 129 .. 256 bases take 2 and 4 positions per lane at S = 64.  Per row (otg_unitalign_core.hpp):
-//   rotate   position j takes the cell of j - 1, position 0 that of p - 1: one ds_bpermute with a source lane fixed per task;
+//   rotate   position j takes the cell of j - 1, position 0 that of p - 1: one lane exchange (otg_lane.hpp) with a source lane fixed per task;
 //   cell     the diagonal step and the base outside the unit, a compare and a minimum;
 //   closure  the skipped unit bases around the cycle: a prefix minimum of the biased cells, segmented (DPP row shifts inside 16 lanes,
-//            ds_bpermute above), and a broadcast of position p - 1 for the paths that wrap.
+//            lane exchanges above), and a broadcast of position p - 1 for the paths that wrap.
 // The unit's bases are read once, one register per position (not LDS: no row needs another lane's base); the allele is read
 // 16 bytes at a time, every lane of a segment the same 16.  A task that has consumed its allele keeps its row while its neighbours go on.
 // The key is edits and unit_bases packed for one unsigned minimum: 32 bits up to OTG_UNITALIGN_NARROW_LEN, 64 bits above.
@@ -16,6 +16,7 @@
 // descending order, by a histogram, a scan and a scatter; every class is one launch over its stretch of the order.  Results land at the
 // task's own index, so the order inside a bucket (atomics) does not show.
 #include "otg_common.hpp"
+#include "otg_lane.hpp"
 #include "otg_scan.hpp"
 #include "otg_unitalign_core.hpp"
 #include <algorithm>
@@ -27,13 +28,14 @@ bool otg_cohort_holds_rows(otg_ctx* ctx, const uint8_t* d_arena);
 namespace {
 
 using namespace otg_unitalign_core;
+using namespace otg_lane;
 
 constexpr uint32_t UA_T = 256;                                   // threads of every workgroup here
 constexpr uint32_t UA_NBINS = 2u * UA_CLASSES * UA_BUCKETS;      // (tier, class, bucket)
 constexpr uint32_t UA_NO_BIN = 0xffffffffu;
 
 struct UaIn {
-  const uint8_t* arena; const uint64_t* off; const uint32_t* len;
+  OtgRows rows;
   OtgUnitSource u;
   const uint32_t* task_seq; const uint32_t* task_unit;
   __device__ __forceinline__ uint32_t seq(uint32_t t) const { return task_seq ? task_seq[t] : t; }
@@ -48,7 +50,7 @@ __global__ __launch_bounds__(UA_T) void ua_classify(UaIn in, uint32_t n, bool wi
 {
   const uint32_t t = blockIdx.x * UA_T + threadIdx.x;
   if (t >= n) return;
-  const uint32_t L = in.len[in.seq(t)], p = in.unit_len(in.unit(t));
+  const uint32_t L = in.rows.len[in.seq(t)], p = in.unit_len(in.unit(t));
   const uint32_t refusal = ua_refusal(L, p);
   if (refusal || L == 0u) {                                       // nothing to align: the record is final
     otg_unitalign rec;
@@ -73,38 +75,6 @@ __global__ __launch_bounds__(UA_T) void ua_scatter(uint32_t n, const uint32_t* _
   order[start[bin] + atomicAdd(&cursor[bin], 1u)] = t;            // start[bin] + count(bin) = start[bin + 1] <= n
 }
 
-// ---- lane exchanges, for both key widths
-__device__ __forceinline__ uint32_t ua_from_lane(uint32_t x, uint32_t src) { return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)x); }
-__device__ __forceinline__ uint64_t ua_from_lane(uint64_t x, uint32_t src)
-{
-  return ((uint64_t)ua_from_lane((uint32_t)(x >> 32), src) << 32) | ua_from_lane((uint32_t)x, src);
-}
-// the value D lanes below inside a row of 16 (DPP row_shr); a lane without such a source keeps its own
-template <int D> __device__ __forceinline__ uint32_t ua_row_up(uint32_t x) { return (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, 0x110 + D, 0xf, 0xf, false); }
-template <int D> __device__ __forceinline__ uint64_t ua_row_up(uint64_t x)
-{
-  return ((uint64_t)ua_row_up<D>((uint32_t)(x >> 32)) << 32) | ua_row_up<D>((uint32_t)x);
-}
-// one step of the segmented prefix minimum over lanes, distance D < S
-template <typename K, int S, int D> __device__ __forceinline__ K ua_scan_step(K x, uint32_t lane, uint32_t jl)
-{
-  if constexpr (D < S) {
-    K from;
-    if constexpr (S <= 16) from = ua_row_up<D>(x);
-    else from = ua_from_lane(x, lane - D);                         // (lane < D reads a lane of the wave that `ok` discards)
-    return ua_scan_take<K>(x, from, jl >= (uint32_t)D);
-  } else {
-    return x;
-  }
-}
-template <typename K, int R> __device__ __forceinline__ K ua_pick(const K (&v)[R], uint32_t r)
-{
-  K x = v[0];
-#pragma unroll
-  for (int q = 1; q < R; ++q) x = r == (uint32_t)q ? v[q] : x;
-  return x;
-}
-
 // ---- the alignment: tasks order[first .. first + count), 64 / S to a wave
 template <typename K, int S, int R>
 __global__ __launch_bounds__(UA_T) void ua_align(UaIn in, const uint32_t* __restrict__ order, uint32_t first, uint32_t count, otg_unitalign* __restrict__ out)
@@ -119,7 +89,7 @@ __global__ __launch_bounds__(UA_T) void ua_align(UaIn in, const uint32_t* __rest
   if (live) {
     t = order[first + slot];
     const uint32_t a = in.seq(t), k = in.unit(t);
-    L = in.len[a]; s = in.arena + in.off[a];
+    L = in.rows.len[a]; s = in.rows.arena + in.rows.off[a];
     p = in.unit_len(k); u = in.unit_at(k);
   }
   // position j = R jl + r of the unit: its base (ua_unit_key), its bias, its row cell
@@ -140,8 +110,8 @@ __global__ __launch_bounds__(UA_T) void ua_align(UaIn in, const uint32_t* __rest
   const bool is_last = lane == last_lane;
   uint32_t um_prev[R];
   {
-    const uint32_t send = is_last ? ua_pick<uint32_t, R>(um, last_reg) : um[R - 1];
-    um_prev[0] = ua_from_lane(send, below);
+    const uint32_t send = is_last ? pick<uint32_t, R>(um, last_reg) : um[R - 1];
+    um_prev[0] = from_lane(send, below);
 #pragma unroll
     for (int r = 1; r < R; ++r) um_prev[r] = um[r - 1];
   }
@@ -154,8 +124,8 @@ __global__ __launch_bounds__(UA_T) void ua_align(UaIn in, const uint32_t* __rest
     for (int k = 0; k < 16; ++k) {
       const uint32_t sc = (w[k >> 2] >> (8 * (k & 3))) & 255u;     // the folded base of this row
       const bool act = i0 + (uint32_t)k < L;
-      const K send = (R > 1 && is_last) ? ua_pick<K, R>(V, last_reg) : V[R - 1];
-      const K d0 = ua_from_lane(send, below);
+      const K send = (R > 1 && is_last) ? pick<K, R>(V, last_reg) : V[R - 1];
+      const K d0 = from_lane(send, below);
       K T[R];
 #pragma unroll
       for (int r = 0; r < R; ++r) {
@@ -166,19 +136,19 @@ __global__ __launch_bounds__(UA_T) void ua_align(UaIn in, const uint32_t* __rest
 #pragma unroll
       for (int r = 1; r < R; ++r) T[r] = ua_scan_take<K>(T[r], T[r - 1], true);
       K x = T[R - 1];
-      x = ua_scan_step<K, S, 1>(x, lane, jl);
-      x = ua_scan_step<K, S, 2>(x, lane, jl);
-      x = ua_scan_step<K, S, 4>(x, lane, jl);
-      x = ua_scan_step<K, S, 8>(x, lane, jl);
-      x = ua_scan_step<K, S, 16>(x, lane, jl);
-      x = ua_scan_step<K, S, 32>(x, lane, jl);
+      x = scan_step<K, S, 1>(x, lane, jl);
+      x = scan_step<K, S, 2>(x, lane, jl);
+      x = scan_step<K, S, 4>(x, lane, jl);
+      x = scan_step<K, S, 8>(x, lane, jl);
+      x = scan_step<K, S, 16>(x, lane, jl);
+      x = scan_step<K, S, 32>(x, lane, jl);
       if constexpr (R > 1) {
-        const K ex = ua_from_lane(x, lane - 1u);
+        const K ex = from_lane(x, lane - 1u);
 #pragma unroll
         for (int r = 0; r < R - 1; ++r) T[r] = ua_scan_take<K>(T[r], ex, jl > 0u);
       }
       T[R - 1] = x;
-      const K last = ua_from_lane(ua_pick<K, R>(T, last_reg), last_lane);
+      const K last = from_lane(pick<K, R>(T, last_reg), last_lane);
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         const K h = ua_close<K>(T[r], last, jl * R + r, p);
@@ -194,8 +164,8 @@ __global__ __launch_bounds__(UA_T) void ua_align(UaIn in, const uint32_t* __rest
     if (valid[r] && ua_better<K>(V[r], jl * R + r, best, bj)) { best = V[r]; bj = jl * R + r; }
 #pragma unroll
   for (uint32_t d = 1; d < (uint32_t)S; d <<= 1) {
-    const K ob = ua_from_lane(best, lane ^ d);
-    const uint32_t oj = ua_from_lane(bj, lane ^ d);
+    const K ob = from_lane(best, lane ^ d);
+    const uint32_t oj = from_lane(bj, lane ^ d);
     if (ua_better<K>(ob, oj, best, bj)) { best = ob; bj = oj; }
   }
   if (live && jl == 0u) {
@@ -236,8 +206,8 @@ bool ua_force_seg64() { static const bool on = ua_env("OTG_UNITALIGN_SEG64"); re
 
 } // namespace
 
-int otg_unitalign_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, const OtgUnitSource& units,
-                           const uint32_t* d_task_seq, const uint32_t* d_task_unit, uint32_t n, otg_unitalign* out)
+int otg_unitalign_resident(otg_ctx* ctx, const char* who, const OtgRows& rows, const OtgUnitSource& units, const uint32_t* d_task_seq,
+                           const uint32_t* d_task_unit, uint32_t n, otg_unitalign* out)
 {
   ctx->last_unitalign_ms = 0.0; ctx->last_unitalign_n = 0;
   if (n == 0) return OTG_OK;
@@ -251,7 +221,7 @@ int otg_unitalign_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena
   uint32_t* d_hist = d_start + UA_NBINS + 1;
   uint32_t* d_cursor = d_hist + UA_NBINS;
   uint32_t* d_bin = d_cursor + UA_NBINS;
-  const UaIn in{d_arena, d_off, d_len, units, d_task_seq, d_task_unit};
+  const UaIn in{rows, units, d_task_seq, d_task_unit};
   const uint32_t grid = (n + UA_T - 1) / UA_T;
   HIP_TRY(ctx, hipMemsetAsync(d_hist, 0, (size_t)2 * UA_NBINS * 4, ctx->stream));
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
@@ -282,20 +252,17 @@ int otg_unitalign_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena
 int otg_unitalign_check(otg_ctx* ctx, const char* who, uint32_t n_seqs, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off,
                         const uint32_t* unit_len, uint32_t n_units, const uint32_t* task_seq, const uint32_t* task_unit, uint32_t n_tasks)
 {
-  if ((n_units && (!unit_off || !unit_len || (unit_bytes && !unit_arena))) || (n_tasks && (!task_seq || !task_unit)))
-    return otg_fail(ctx, OTG_ERR_ARG, "%s: NULL argument", who);
-  for (uint32_t k = 0; k < n_units; ++k) {
-    if (unit_len[k] > OTG_UNITALIGN_MAX_UNIT)
-      return otg_fail(ctx, OTG_ERR_ARG, "%s: unit %u has %u bytes, at most %d", who, k, unit_len[k], OTG_UNITALIGN_MAX_UNIT);
-    if (unit_off[k] > unit_bytes || unit_len[k] > unit_bytes - unit_off[k])
-      return otg_fail(ctx, OTG_ERR_ARG, "%s: unit %u (offset %llu, length %u) lies outside the %llu-byte unit arena", who, k, (unsigned long long)unit_off[k],
-                      unit_len[k], (unsigned long long)unit_bytes);
-  }
-  for (uint32_t t = 0; t < n_tasks; ++t)
-    if (task_seq[t] >= n_seqs || task_unit[t] >= n_units)
-      return otg_fail(ctx, OTG_ERR_ARG, "%s: task %u names allele %u of %u and unit %u of %u", who, t, task_seq[t], n_seqs, task_unit[t], n_units);
-  if (n_tasks > (1u << 24)) return otg_fail(ctx, OTG_ERR_CAPACITY, "%s: %u tasks in one call, at most %u", who, n_tasks, 1u << 24);
-  return OTG_OK;
+  return otg_unit_lists_check(
+      ctx, who, n_tasks && (!task_seq || !task_unit), unit_arena, unit_bytes, unit_off, unit_len, n_units, n_tasks,
+      [&](uint32_t k, uint32_t len) {
+        return len > OTG_UNITALIGN_MAX_UNIT ? otg_fail(ctx, OTG_ERR_ARG, "%s: unit %u has %u bytes, at most %d", who, k, len, OTG_UNITALIGN_MAX_UNIT) : (int)OTG_OK;
+      },
+      [&] {
+        for (uint32_t t = 0; t < n_tasks; ++t)
+          if (task_seq[t] >= n_seqs || task_unit[t] >= n_units)
+            return otg_fail(ctx, OTG_ERR_ARG, "%s: task %u names allele %u of %u and unit %u of %u", who, t, task_seq[t], n_seqs, task_unit[t], n_units);
+        return (int)OTG_OK;
+      });
 }
 
 int otg_unitalign_upload(otg_ctx* ctx, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off, const uint32_t* unit_len, uint32_t n_units,
@@ -330,29 +297,16 @@ extern "C" int otg_unitalign_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint6
                                    uint32_t n_units, const uint32_t* task_seq, const uint32_t* task_unit, uint32_t n_tasks, otg_unitalign* out)
 {
   if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_unitalign_batch: no context (no HIP device?)");
-  if (n_seqs && (!seq_off || !seq_len || (arena_bytes && !seq_arena))) return otg_fail(ctx, OTG_ERR_ARG, "otg_unitalign_batch: NULL argument");
-  for (uint32_t i = 0; i < n_seqs; ++i)
-    if (seq_off[i] > arena_bytes || seq_len[i] > arena_bytes - seq_off[i])
-      return otg_fail(ctx, OTG_ERR_ARG, "otg_unitalign_batch: allele %u (offset %llu, length %u) lies outside the %llu-byte arena", i,
-                      (unsigned long long)seq_off[i], seq_len[i], (unsigned long long)arena_bytes);
+  if (int rc = otg_rows_check(ctx, "otg_unitalign_batch", seq_arena, arena_bytes, seq_off, seq_len, n_seqs, nullptr)) return rc;
   if (int rc = otg_unitalign_check(ctx, "otg_unitalign_batch", n_seqs, unit_arena, unit_bytes, unit_off, unit_len, n_units, task_seq, task_unit, n_tasks)) return rc;
   ctx->last_unitalign_ms = 0.0; ctx->last_unitalign_n = 0;
   if (n_tasks == 0) return OTG_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  // the rows: the arena and seq_off (u64) | seq_len (u32)
-  uint8_t* d_arena = (uint8_t*)otg_slot(ctx, SLOT_UNITALIGN_SEQ, arena_bytes + 64);
-  uint8_t* d_meta = (uint8_t*)otg_slot(ctx, SLOT_UNITALIGN_META, (size_t)n_seqs * 12);
-  if (!d_arena || !d_meta) return OTG_ERR_HIP;
-  uint64_t* d_off = (uint64_t*)d_meta;
-  uint32_t* d_len = (uint32_t*)(d_meta + (size_t)n_seqs * 8);
-  HIP_TRY(ctx, hipMemsetAsync(d_arena + arena_bytes, 0, 64, ctx->stream));
-  if (arena_bytes) HIP_TRY(ctx, hipMemcpyAsync(d_arena, seq_arena, arena_bytes, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_off, seq_off, (size_t)n_seqs * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_len, seq_len, (size_t)n_seqs * 4, hipMemcpyHostToDevice, ctx->stream));
+  OtgRows rows;
+  if (int rc = otg_rows_upload(ctx, SLOT_UNITALIGN_SEQ, SLOT_UNITALIGN_META, seq_arena, arena_bytes, seq_off, seq_len, n_seqs, &rows)) return rc;
   OtgUnitSource units;
   const uint32_t *d_ts = nullptr, *d_tu = nullptr;
   if (int rc = otg_unitalign_upload(ctx, unit_arena, unit_bytes, unit_off, unit_len, n_units, task_seq, task_unit, n_tasks, &units, &d_ts, &d_tu)) return rc;
-  return otg_unitalign_resident(ctx, "otg_unitalign_batch", d_arena, d_off, d_len, units, d_ts, d_tu, n_tasks, out);
+  return otg_unitalign_resident(ctx, "otg_unitalign_batch", rows, units, d_ts, d_tu, n_tasks, out);
 }
 
 extern "C" int otg_unitalign_motifs(otg_ctx* ctx, otg_unitalign* out)
@@ -361,11 +315,11 @@ extern "C" int otg_unitalign_motifs(otg_ctx* ctx, otg_unitalign* out)
   const DevBuf& b = ctx->pool[SLOT_MOTIF_OUT];
   if (!b.p || ctx->last_motif_n == 0) return otg_fail(ctx, OTG_ERR_ARG, "otg_unitalign_motifs: no motif results on this context");
   // the alleles of that call must still lie where it read them: the context's own copy, or the rows of the cohort batch
-  if (ctx->last_motif_arena != (const uint8_t*)ctx->pool[SLOT_MOTIF_SEQ].p && !otg_cohort_holds_rows(ctx, ctx->last_motif_arena))
+  if (ctx->last_motif_rows.arena != (const uint8_t*)ctx->pool[SLOT_MOTIF_SEQ].p && !otg_cohort_holds_rows(ctx, ctx->last_motif_rows.arena))
     return otg_fail(ctx, OTG_ERR_ARG, "otg_unitalign_motifs: the alleles of the latest motif call are no longer on the device");
   const uint32_t n = ctx->last_motif_n;
   const OtgUnitSource units{(const uint8_t*)b.p + (size_t)n * sizeof(otg_motif), nullptr, nullptr, (const otg_motif*)b.p, ctx->last_motif_stride};
-  return otg_unitalign_resident(ctx, "otg_unitalign_motifs", ctx->last_motif_arena, ctx->last_motif_off, ctx->last_motif_len, units, nullptr, nullptr, n, out);
+  return otg_unitalign_resident(ctx, "otg_unitalign_motifs", ctx->last_motif_rows, units, nullptr, nullptr, n, out);
 }
 
 extern "C" int otg_unitalign_device_results(otg_ctx* ctx, uint32_t* n_tasks, const otg_unitalign** records)

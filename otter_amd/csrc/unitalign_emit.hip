@@ -45,8 +45,5 @@ extern "C" int otg_unitalign_emit(const otg_vcf_record* records, uint32_t n_reco
     }
   std::string text;
   otg_unitalign_rows(text, records, n_records, region_arena, seq_len, task_first, task_source, unit_arena, task_unit_off, task_unit_len, aligned);
-  *out_len = text.size();
-  if (text.size() > out_capacity || (!out && !text.empty())) return otg_fail(nullptr, OTG_ERR_CAPACITY, "otg_unitalign_emit: output buffer too small");
-  if (!text.empty()) memcpy(out, text.data(), text.size());
-  return OTG_OK;
+  return otg_text_out("otg_unitalign_emit", text, out, out_capacity, out_len);
 }

@@ -6,9 +6,9 @@
 // boundary, so "position inside its unit" is a per-lane constant and the scan guards and the rotate's source lane are fixed per task.  A
 // task takes the smallest power of two of 4 .. 64 lanes that holds its set, at 1, 2 or 4 positions per lane.  Per row
 // (otg_unitparse_core.hpp):
-//   rotate   inside each unit, one ds_bpermute;
+//   rotate   inside each unit, one lane exchange (otg_lane.hpp);
 //   cell     the diagonal step and the base outside the unit, kept apart: the traceback wants to know which one won;
-//   scan     the biased prefix minimum, segmented by unit (DPP row shifts where the task lies inside 16 lanes, ds_bpermute above);
+//   scan     the biased prefix minimum, segmented by unit (DPP row shifts where the task lies inside 16 lanes, lane exchanges above);
 //   phase 0  per unit the candidate from inside it, one minimum of those over the task's lanes, plus one switch where that is smaller;
 //   close    the way on from phase 0 around every unit.
 // It stores decisions, not keys: two bits per cell (diagonal, outside base, skip, switch) and per row the units that hold the smallest
@@ -22,6 +22,7 @@
 // chunks of waves whose store fits the budget (OTG_UNITPARSE_TRACE_MB); with more than one chunk the forward pass first runs without the
 // store to count the segments, then once more chunk by chunk with the walk behind it.
 #include "otg_common.hpp"
+#include "otg_lane.hpp"
 #include "otg_scan.hpp"
 #include "otg_unitparse_core.hpp"
 #include <algorithm>
@@ -30,6 +31,7 @@
 namespace {
 
 using namespace otg_unitparse_core;
+using namespace otg_lane;
 
 constexpr uint32_t UP_T = 256;                                   // threads of a forward workgroup
 constexpr uint32_t UP_WALK_T = 64;                               // threads of a walk workgroup: the walk is latency-bound, so the waves are spread
@@ -38,7 +40,7 @@ constexpr uint32_t UP_NONE = 0xffffffffu;
 constexpr size_t UP_TRACE_MB = 1024;                             // the default budget of the traceback store
 
 struct UpIn {
-  const uint8_t* arena; const uint64_t* off; const uint32_t* len;
+  OtgRows rows;
   const uint8_t* units; const uint64_t* unit_off; const uint32_t* unit_len; const uint64_t* set_first;
   const uint32_t* task_seq; const uint32_t* task_set;
 };
@@ -49,41 +51,8 @@ __global__ __launch_bounds__(UP_T) void up_init(UpIn in, uint32_t n, otg_unitpar
   if (t >= n) return;
   otg_unitparse_sum rec;
   rec.edits = rec.switches = rec.unit_bases = rec.n_segments = rec.end_unit = rec.end_phase = rec.reserved = 0u;
-  rec.flags = in.len[in.task_seq[t]] > OTG_UNITPARSE_MAX_LEN ? OTG_UNITPARSE_TOO_LONG : 0u;
+  rec.flags = in.rows.len[in.task_seq[t]] > OTG_UNITPARSE_MAX_LEN ? OTG_UNITPARSE_TOO_LONG : 0u;
   sums[t] = rec;
-}
-
-// ---- lane exchanges
-__device__ __forceinline__ uint32_t up_from_lane(uint32_t x, uint32_t src) { return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)x); }
-__device__ __forceinline__ uint64_t up_from_lane(uint64_t x, uint32_t src)
-{
-  return ((uint64_t)up_from_lane((uint32_t)(x >> 32), src) << 32) | up_from_lane((uint32_t)x, src);
-}
-// the value D lanes below inside a row of 16 (DPP row_shr); a lane without such a source keeps its own
-template <int D> __device__ __forceinline__ uint64_t up_row_up(uint64_t x)
-{
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp((int)(x >> 32), (int)(x >> 32), 0x110 + D, 0xf, 0xf, false);
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, 0x110 + D, 0xf, 0xf, false);
-  return ((uint64_t)hi << 32) | lo;
-}
-// one step of the prefix minimum segmented by unit, distance D < S: ul = the lane's place inside its unit
-template <int S, int D> __device__ __forceinline__ uint64_t up_scan_step(uint64_t x, uint32_t lane, uint32_t ul)
-{
-  if constexpr (D < S) {
-    uint64_t from;
-    if constexpr (S <= 16) from = up_row_up<D>(x);
-    else from = up_from_lane(x, lane - D);                         // (lane < D reads a lane of the wave that `ok` discards)
-    return up_scan_take(x, from, ul >= (uint32_t)D);
-  } else {
-    return x;
-  }
-}
-template <typename K, int R> __device__ __forceinline__ K up_pick(const K (&v)[R], uint32_t r)
-{
-  K x = v[0];
-#pragma unroll
-  for (int q = 1; q < R; ++q) x = r == (uint32_t)q ? v[q] : x;
-  return x;
 }
 
 // ---- the forward pass: tasks order[first .. first + count), 64 / S to a wave; wave w of the launch is wave wave0 + w of the plan
@@ -103,7 +72,7 @@ __global__ __launch_bounds__(UP_T) void up_forward(UpIn in, const uint32_t* __re
   if (live) {
     t = order[first + slot];
     const uint32_t a = in.task_seq[t], q = in.task_set[t];
-    L = in.len[a]; s = in.arena + in.off[a];
+    L = in.rows.len[a]; s = in.rows.arena + in.rows.off[a];
     uf = in.set_first[q]; K = (uint32_t)(in.set_first[q + 1] - uf);
   }
   // the lane's unit: k, its length p, the lane's place ul inside it and the unit's first lane
@@ -133,8 +102,8 @@ __global__ __launch_bounds__(UP_T) void up_forward(UpIn in, const uint32_t* __re
   const bool is_last = lane == last_lane, is_first = ul == 0u && valid[0];
   uint32_t um_prev[R];
   {
-    const uint32_t send = is_last ? up_pick<uint32_t, R>(um, last_reg) : um[R - 1];
-    um_prev[0] = up_from_lane(send, below);
+    const uint32_t send = is_last ? pick<uint32_t, R>(um, last_reg) : um[R - 1];
+    um_prev[0] = from_lane(send, below);
 #pragma unroll
     for (int r = 1; r < R; ++r) um_prev[r] = um[r - 1];
   }
@@ -153,8 +122,8 @@ __global__ __launch_bounds__(UP_T) void up_forward(UpIn in, const uint32_t* __re
     for (int kk = 0; kk < 16; ++kk) {
       const uint32_t sc = (w[kk >> 2] >> (8 * (kk & 3))) & 255u;   // the folded base of this row
       const bool act = i0 + (uint32_t)kk < L;
-      const uint64_t send = (R > 1 && is_last) ? up_pick<uint64_t, R>(V, last_reg) : V[R - 1];
-      const uint64_t d0 = up_from_lane(send, below);
+      const uint64_t send = (R > 1 && is_last) ? pick<uint64_t, R>(V, last_reg) : V[R - 1];
+      const uint64_t d0 = from_lane(send, below);
       uint64_t d[R], v[R], T[R];
 #pragma unroll
       for (int r = 0; r < R; ++r) {
@@ -165,26 +134,26 @@ __global__ __launch_bounds__(UP_T) void up_forward(UpIn in, const uint32_t* __re
       const uint64_t cell0 = up_min(d[0], v[0]);
       // the prefix minimum of the biased cells: inside the lane, across the lanes of the unit, and back into the lane
 #pragma unroll
-      for (int r = 1; r < R; ++r) T[r] = up_scan_take(T[r], T[r - 1], true);
+      for (int r = 1; r < R; ++r) T[r] = ua_scan_take<uint64_t>(T[r], T[r - 1], true);
       uint64_t x = T[R - 1];
-      x = up_scan_step<S, 1>(x, lane, ul);
-      x = up_scan_step<S, 2>(x, lane, ul);
-      x = up_scan_step<S, 4>(x, lane, ul);
-      x = up_scan_step<S, 8>(x, lane, ul);
-      x = up_scan_step<S, 16>(x, lane, ul);
-      x = up_scan_step<S, 32>(x, lane, ul);
+      x = scan_step<uint64_t, S, 1>(x, lane, ul);
+      x = scan_step<uint64_t, S, 2>(x, lane, ul);
+      x = scan_step<uint64_t, S, 4>(x, lane, ul);
+      x = scan_step<uint64_t, S, 8>(x, lane, ul);
+      x = scan_step<uint64_t, S, 16>(x, lane, ul);
+      x = scan_step<uint64_t, S, 32>(x, lane, ul);
       if constexpr (R > 1) {
-        const uint64_t ex = up_from_lane(x, lane - 1u);
+        const uint64_t ex = from_lane(x, lane - 1u);
 #pragma unroll
-        for (int r = 0; r < R - 1; ++r) T[r] = up_scan_take(T[r], ex, ul > 0u);
+        for (int r = 0; r < R - 1; ++r) T[r] = ua_scan_take<uint64_t>(T[r], ex, ul > 0u);
       }
       T[R - 1] = x;
-      const uint64_t last = up_from_lane(up_pick<uint64_t, R>(T, last_reg), last_lane);
+      const uint64_t last = from_lane(pick<uint64_t, R>(T, last_reg), last_lane);
       // phase 0: the unit's candidate at its first lane, the smallest of the task, and what enters every unit from behind
       const uint64_t cand = is_first ? up_phase0(cell0, last) : up_inf();
       uint64_t best0 = cand;
 #pragma unroll
-      for (uint32_t dd = 1; dd < (uint32_t)S; dd <<= 1) best0 = up_min(best0, up_from_lane(best0, lane ^ dd));
+      for (uint32_t dd = 1; dd < (uint32_t)S; dd <<= 1) best0 = up_min(best0, from_lane(best0, lane ^ dd));
       const uint64_t entry = up_entry(last, best0);
       uint32_t code[R];
 #pragma unroll
@@ -213,8 +182,8 @@ __global__ __launch_bounds__(UP_T) void up_forward(UpIn in, const uint32_t* __re
     if (valid[r] && (V[r] < best || (V[r] == best && lane * R + r < bg))) { best = V[r]; bg = lane * R + r; }
 #pragma unroll
   for (uint32_t dd = 1; dd < (uint32_t)S; dd <<= 1) {
-    const uint64_t ob = up_from_lane(best, lane ^ dd);
-    const uint32_t og = up_from_lane(bg, lane ^ dd);
+    const uint64_t ob = from_lane(best, lane ^ dd);
+    const uint32_t og = from_lane(bg, lane ^ dd);
     if (ob < best || (ob == best && og < bg)) { best = ob; bg = og; }
   }
   if (live && bg != UP_NONE && bg / R == lane) {
@@ -245,7 +214,7 @@ __global__ __launch_bounds__(UP_WALK_T) void up_walk_kernel(UpIn in, const uint3
   const uint64_t so = seg_off[t];
   const uint32_t room = (uint32_t)(seg_off[t + 1] - so);
   const uint32_t bad = room != rec.n_segments ? 7u
-                                              : up_walk(trace + wave_off[wave0 + wave], R, lane0, S, in.arena + in.off[a], in.len[a], in.units, in.unit_off + uf,
+                                              : up_walk(trace + wave_off[wave0 + wave], R, lane0, S, in.rows.arena + in.rows.off[a], in.rows.len[a], in.units, in.unit_off + uf,
                                                         in.unit_len + uf, (uint32_t)(in.set_first[q + 1] - uf), rec.end_unit, rec.end_phase, segs + so, room);
   if (bad) atomicMax(defect, bad);
 }
@@ -295,40 +264,37 @@ int otg_unitparse_check(otg_ctx* ctx, const char* who, uint32_t n_seqs, const ui
                         const uint32_t* unit_len, uint32_t n_units, const uint64_t* set_first, uint32_t n_sets, const uint32_t* task_seq,
                         const uint32_t* task_set, uint32_t n_tasks)
 {
-  if ((n_units && (!unit_off || !unit_len || (unit_bytes && !unit_arena))) || !set_first || (n_tasks && (!task_seq || !task_set)))
-    return otg_fail(ctx, OTG_ERR_ARG, "%s: NULL argument", who);
-  for (uint32_t k = 0; k < n_units; ++k) {
-    if (unit_len[k] == 0u || unit_len[k] > OTG_UNITALIGN_MAX_UNIT)
-      return otg_fail(ctx, OTG_ERR_ARG, "%s: unit %u has %u bytes, 1 to %d are allowed", who, k, unit_len[k], OTG_UNITALIGN_MAX_UNIT);
-    if (unit_off[k] > unit_bytes || unit_len[k] > unit_bytes - unit_off[k])
-      return otg_fail(ctx, OTG_ERR_ARG, "%s: unit %u (offset %llu, length %u) lies outside the %llu-byte unit arena", who, k, (unsigned long long)unit_off[k],
-                      unit_len[k], (unsigned long long)unit_bytes);
-  }
-  for (uint32_t q = 0; q < n_sets; ++q) {
-    if (set_first[q] > set_first[q + 1] || set_first[q + 1] > n_units)
-      return otg_fail(ctx, OTG_ERR_ARG, "%s: set %u spans units %llu .. %llu of %u", who, q, (unsigned long long)set_first[q], (unsigned long long)set_first[q + 1],
-                      n_units);
-    const uint64_t K = set_first[q + 1] - set_first[q];
-    if (K == 0) return otg_fail(ctx, OTG_ERR_ARG, "%s: set %u is empty", who, q);
-    if (K > OTG_UNITPARSE_MAX_UNITS) return otg_fail(ctx, OTG_ERR_ARG, "%s: set %u has %llu units, at most %d", who, q, (unsigned long long)K, OTG_UNITPARSE_MAX_UNITS);
-    if (otg_unitparse_core::up_class(unit_len + set_first[q], (uint32_t)K) == otg_unitparse_core::UP_NO_CLASS)
-      return otg_fail(ctx, OTG_ERR_ARG, "%s: set %u does not fit one wave (its units take %u lanes at four positions each, at most %d)", who, q,
-                      otg_unitparse_core::up_lanes(unit_len + set_first[q], (uint32_t)K, 4u), OTG_UNITPARSE_MAX_LANES);
-  }
-  for (uint32_t t = 0; t < n_tasks; ++t)
-    if (task_seq[t] >= n_seqs || task_set[t] >= n_sets)
-      return otg_fail(ctx, OTG_ERR_ARG, "%s: task %u names allele %u of %u and set %u of %u", who, t, task_seq[t], n_seqs, task_set[t], n_sets);
-  if (n_tasks > (1u << 24)) return otg_fail(ctx, OTG_ERR_CAPACITY, "%s: %u tasks in one call, at most %u", who, n_tasks, 1u << 24);
-  return OTG_OK;
+  return otg_unit_lists_check(
+      ctx, who, !set_first || (n_tasks && (!task_seq || !task_set)), unit_arena, unit_bytes, unit_off, unit_len, n_units, n_tasks,
+      [&](uint32_t k, uint32_t len) {
+        return len == 0u || len > OTG_UNITALIGN_MAX_UNIT
+                   ? otg_fail(ctx, OTG_ERR_ARG, "%s: unit %u has %u bytes, 1 to %d are allowed", who, k, len, OTG_UNITALIGN_MAX_UNIT)
+                   : (int)OTG_OK;
+      },
+      [&] {
+        for (uint32_t q = 0; q < n_sets; ++q) {
+          if (set_first[q] > set_first[q + 1] || set_first[q + 1] > n_units)
+            return otg_fail(ctx, OTG_ERR_ARG, "%s: set %u spans units %llu .. %llu of %u", who, q, (unsigned long long)set_first[q], (unsigned long long)set_first[q + 1],
+                            n_units);
+          const uint64_t K = set_first[q + 1] - set_first[q];
+          if (K == 0) return otg_fail(ctx, OTG_ERR_ARG, "%s: set %u is empty", who, q);
+          if (K > OTG_UNITPARSE_MAX_UNITS) return otg_fail(ctx, OTG_ERR_ARG, "%s: set %u has %llu units, at most %d", who, q, (unsigned long long)K, OTG_UNITPARSE_MAX_UNITS);
+          if (otg_unitparse_core::up_class(unit_len + set_first[q], (uint32_t)K) == otg_unitparse_core::UP_NO_CLASS)
+            return otg_fail(ctx, OTG_ERR_ARG, "%s: set %u does not fit one wave (its units take %u lanes at four positions each, at most %d)", who, q,
+                            otg_unitparse_core::up_lanes(unit_len + set_first[q], (uint32_t)K, 4u), OTG_UNITPARSE_MAX_LANES);
+        }
+        for (uint32_t t = 0; t < n_tasks; ++t)
+          if (task_seq[t] >= n_seqs || task_set[t] >= n_sets)
+            return otg_fail(ctx, OTG_ERR_ARG, "%s: task %u names allele %u of %u and set %u of %u", who, t, task_seq[t], n_seqs, task_set[t], n_sets);
+        return (int)OTG_OK;
+      });
 }
 
-int otg_unitparse_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena, const uint64_t* d_off, const uint32_t* d_len, const uint32_t* h_len,
-                           uint32_t n_seqs, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off, const uint32_t* unit_len,
-                           uint32_t n_units, const uint64_t* set_first, uint32_t n_sets, const uint32_t* task_seq, const uint32_t* task_set, uint32_t n,
+int otg_unitparse_resident(otg_ctx* ctx, const char* who, const OtgRows& rows, const uint32_t* h_len, uint32_t n_seqs, const uint8_t* unit_arena,
+                           uint64_t unit_bytes, const uint64_t* unit_off, const uint32_t* unit_len, uint32_t n_units, const uint64_t* set_first, uint32_t n_sets, const uint32_t* task_seq, const uint32_t* task_set, uint32_t n,
                            otg_unitparse_sum* sums, uint64_t* seg_off, uint64_t* n_segments)
 {
-  ctx->last_unitparse_forward_ms = ctx->last_unitparse_trace_ms = 0.0;
-  ctx->last_unitparse_n = 0; ctx->last_unitparse_total = 0; ctx->last_unitparse_valid = false;
+  ctx->last_unitparse = OtgSegLast{};
   if (n_segments) *n_segments = 0;
   if (n == 0) {
     if (seg_off) seg_off[0] = 0;
@@ -339,7 +305,7 @@ int otg_unitparse_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena
   std::vector<uint32_t> lens;
   if (!h_len) {                                                    // the rows of a cohort: only their lengths come to the host
     lens.resize(n_seqs);
-    HIP_TRY(ctx, hipMemcpyAsync(lens.data(), d_len, (size_t)n_seqs * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(lens.data(), rows.len, (size_t)n_seqs * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     h_len = lens.data();
   }
@@ -415,7 +381,7 @@ int otg_unitparse_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena
     HIP_TRY(ctx, hipMemcpyAsync(d_wrows, wave_rows.data(), n_waves * 4, hipMemcpyHostToDevice, ctx->stream));
   }
   HIP_TRY(ctx, hipMemsetAsync(d_defect, 0, 4, ctx->stream));
-  const UpIn in{d_arena, d_off, d_len, d_ub, d_uoff, d_ulen, d_sf, d_ts, d_tq};
+  const UpIn in{rows, d_ub, d_uoff, d_ulen, d_sf, d_ts, d_tq};
   const bool one = chunks.size() <= 1;
   double forward_ms = 0.0, trace_ms = 0.0;
   float ms = 0.f;
@@ -474,8 +440,7 @@ int otg_unitparse_resident(otg_ctx* ctx, const char* who, const uint8_t* d_arena
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (defect) return otg_fail(ctx, OTG_ERR_FATAL, "%s: the traceback store contradicts the forward pass (code %u)", who, defect);
   if (n_segments) *n_segments = total;
-  ctx->last_unitparse_forward_ms = forward_ms; ctx->last_unitparse_trace_ms = trace_ms;
-  ctx->last_unitparse_n = n; ctx->last_unitparse_total = total; ctx->last_unitparse_valid = true;
+  ctx->last_unitparse = OtgSegLast{n, total, true, {forward_ms, trace_ms}};
   return OTG_OK;
 }
 
@@ -485,66 +450,34 @@ extern "C" int otg_unitparse_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint6
                                    uint32_t n_tasks, otg_unitparse_sum* sums, uint64_t* seg_off, uint64_t* n_segments)
 {
   if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_unitparse_batch: no context (no HIP device?)");
-  if (n_seqs && (!seq_off || !seq_len || (arena_bytes && !seq_arena))) return otg_fail(ctx, OTG_ERR_ARG, "otg_unitparse_batch: NULL argument");
-  for (uint32_t i = 0; i < n_seqs; ++i)
-    if (seq_off[i] > arena_bytes || seq_len[i] > arena_bytes - seq_off[i])
-      return otg_fail(ctx, OTG_ERR_ARG, "otg_unitparse_batch: allele %u (offset %llu, length %u) lies outside the %llu-byte arena", i,
-                      (unsigned long long)seq_off[i], seq_len[i], (unsigned long long)arena_bytes);
+  if (int rc = otg_rows_check(ctx, "otg_unitparse_batch", seq_arena, arena_bytes, seq_off, seq_len, n_seqs, nullptr)) return rc;
   if (int rc = otg_unitparse_check(ctx, "otg_unitparse_batch", n_seqs, unit_arena, unit_bytes, unit_off, unit_len, n_units, set_first, n_sets, task_seq, task_set,
                                    n_tasks))
     return rc;
-  ctx->last_unitparse_valid = false;
-  if (n_tasks == 0) return otg_unitparse_resident(ctx, "otg_unitparse_batch", nullptr, nullptr, nullptr, seq_len, n_seqs, unit_arena, unit_bytes, unit_off, unit_len,
-                                                  n_units, set_first, n_sets, task_seq, task_set, 0, sums, seg_off, n_segments);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  // the rows: the arena and seq_off (u64) | seq_len (u32)
-  uint8_t* d_arena = (uint8_t*)otg_slot(ctx, SLOT_UNITPARSE_SEQ, arena_bytes + 64);
-  uint8_t* d_meta = (uint8_t*)otg_slot(ctx, SLOT_UNITPARSE_META, (size_t)n_seqs * 12);
-  if (!d_arena || !d_meta) return OTG_ERR_HIP;
-  uint64_t* d_off = (uint64_t*)d_meta;
-  uint32_t* d_len = (uint32_t*)(d_meta + (size_t)n_seqs * 8);
-  HIP_TRY(ctx, hipMemsetAsync(d_arena + arena_bytes, 0, 64, ctx->stream));
-  if (arena_bytes) HIP_TRY(ctx, hipMemcpyAsync(d_arena, seq_arena, arena_bytes, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_off, seq_off, (size_t)n_seqs * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_len, seq_len, (size_t)n_seqs * 4, hipMemcpyHostToDevice, ctx->stream));
-  return otg_unitparse_resident(ctx, "otg_unitparse_batch", d_arena, d_off, d_len, seq_len, n_seqs, unit_arena, unit_bytes, unit_off, unit_len, n_units, set_first,
-                                n_sets, task_seq, task_set, n_tasks, sums, seg_off, n_segments);
+  ctx->last_unitparse.valid = false;
+  OtgRows rows = {nullptr, nullptr, nullptr};
+  if (n_tasks != 0)                                                // (without tasks the launch part answers before it reads a row)
+    if (int rc = otg_rows_upload(ctx, SLOT_UNITPARSE_SEQ, SLOT_UNITPARSE_META, seq_arena, arena_bytes, seq_off, seq_len, n_seqs, &rows)) return rc;
+  return otg_unitparse_resident(ctx, "otg_unitparse_batch", rows, seq_len, n_seqs, unit_arena, unit_bytes, unit_off, unit_len, n_units, set_first, n_sets, task_seq,
+                                task_set, n_tasks, sums, seg_off, n_segments);
 }
 
 extern "C" int otg_unitparse_collect(otg_ctx* ctx, otg_unitparse_seg* segs, uint64_t capacity)
 {
-  if (!ctx) return otg_fail(nullptr, OTG_ERR_ARG, "otg_unitparse_collect: NULL context");
-  if (!ctx->last_unitparse_valid) return otg_fail(ctx, OTG_ERR_ARG, "otg_unitparse_collect: no unit parse results on this context");
-  const uint64_t total = ctx->last_unitparse_total;
-  if (capacity < total)
-    return otg_fail(ctx, OTG_ERR_CAPACITY, "otg_unitparse_collect: capacity %llu, the latest call has %llu segments", (unsigned long long)capacity,
-                    (unsigned long long)total);
-  if (total == 0) return OTG_OK;
-  if (!segs) return otg_fail(ctx, OTG_ERR_ARG, "otg_unitparse_collect: NULL segs");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipMemcpyAsync(segs, ctx->pool[SLOT_UNITPARSE_SEGS].p, (size_t)total * sizeof(otg_unitparse_seg), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return OTG_OK;
+  return otg_seg_collect(ctx, "otg_unitparse_collect", "unit parse", &otg_ctx::last_unitparse, SLOT_UNITPARSE_SEGS, sizeof(otg_unitparse_seg), segs, capacity);
 }
 
 extern "C" int otg_unitparse_device_results(otg_ctx* ctx, uint32_t* n_tasks, const otg_unitparse_sum** sums, const uint64_t** seg_off,
                                             const otg_unitparse_seg** segs, uint64_t* total)
 {
-  if (!ctx) return otg_fail(nullptr, OTG_ERR_ARG, "otg_unitparse_device_results: NULL context");
-  if (!ctx->last_unitparse_valid) return otg_fail(ctx, OTG_ERR_ARG, "otg_unitparse_device_results: no unit parse results on this context");
-  const uint8_t* res = (const uint8_t*)ctx->pool[SLOT_UNITPARSE_RES].p;
-  if (n_tasks) *n_tasks = ctx->last_unitparse_n;
-  if (sums) *sums = (const otg_unitparse_sum*)res;
-  if (seg_off) *seg_off = (const uint64_t*)(res + (size_t)ctx->last_unitparse_n * sizeof(otg_unitparse_sum));
-  if (segs) *segs = (const otg_unitparse_seg*)ctx->pool[SLOT_UNITPARSE_SEGS].p;
-  if (total) *total = ctx->last_unitparse_total;
-  return OTG_OK;
+  return otg_seg_device_results(ctx, "otg_unitparse_device_results", "unit parse", &otg_ctx::last_unitparse, SLOT_UNITPARSE_RES, SLOT_UNITPARSE_SEGS,
+                                sizeof(otg_unitparse_sum), n_tasks, (const void**)sums, seg_off, (const void**)segs, total);
 }
 
 extern "C" int otg_unitparse_last_ms(otg_ctx* ctx, double* forward_ms, double* trace_ms)
 {
   if (!ctx) return otg_fail(nullptr, OTG_ERR_ARG, "otg_unitparse_last_ms: NULL context");
-  if (forward_ms) *forward_ms = ctx->last_unitparse_forward_ms;
-  if (trace_ms) *trace_ms = ctx->last_unitparse_trace_ms;
+  if (forward_ms) *forward_ms = ctx->last_unitparse.ms[0];
+  if (trace_ms) *trace_ms = ctx->last_unitparse.ms[1];
   return OTG_OK;
 }

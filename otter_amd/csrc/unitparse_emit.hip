@@ -80,8 +80,5 @@ extern "C" int otg_unitparse_emit(const otg_vcf_record* records, uint32_t n_reco
     }
   std::string text;
   otg_unitparse_rows(text, records, n_records, region_arena, seq_len, allele_set, set_first, unit_arena, unit_off, unit_len, sums, seg_off, segs);
-  *out_len = text.size();
-  if (text.size() > out_capacity || (!out && !text.empty())) return otg_fail(nullptr, OTG_ERR_CAPACITY, "otg_unitparse_emit: output buffer too small");
-  if (!text.empty()) memcpy(out, text.data(), text.size());
-  return OTG_OK;
+  return otg_text_out("otg_unitparse_emit", text, out, out_capacity, out_len);
 }

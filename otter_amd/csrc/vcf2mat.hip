@@ -203,10 +203,7 @@ int otg_vcf2mat_emit(const otg_vcf_record* records, uint32_t n_records, const ch
   if (n_records && (!records || !region_arena || !seq_len || !usage || !gc || !hsd)) return otg_fail(nullptr, OTG_ERR_ARG, "otg_vcf2mat_emit: NULL argument");
   std::string text;
   otg_vcf2mat_rows(text, records, n_records, region_arena, seq_len, k, usage, gc, hsd);
-  *out_len = text.size();
-  if (text.size() > out_capacity || (!out && !text.empty())) return otg_fail(nullptr, OTG_ERR_CAPACITY, "otg_vcf2mat_emit: output buffer too small");
-  if (!text.empty()) memcpy(out, text.data(), text.size());
-  return OTG_OK;
+  return otg_text_out("otg_vcf2mat_emit", text, out, out_capacity, out_len);
 }
 
 } // extern "C"

@@ -40,7 +40,7 @@ template <int S, int D> static void scan_step(uint64_t (&x)[64], const uint32_t 
   uint64_t nx[64];
   for (uint32_t lane = 0; lane < 64; ++lane) {
     const uint64_t from = S <= 16 ? row_up<D>(x, lane) : from_lane(x, lane - D);
-    nx[lane] = up_scan_take(x[lane], from, ul[lane] >= (uint32_t)D);
+    nx[lane] = ua_scan_take<uint64_t>(x[lane], from, ul[lane] >= (uint32_t)D);
   }
   for (uint32_t lane = 0; lane < 64; ++lane) x[lane] = nx[lane];
 }
@@ -124,14 +124,14 @@ template <int S, int R> static int wave(const Task* const* tasks, Rec* const* re
           T[lane][r] = valid[lane][r] ? up_min(d[lane][r], v[lane][r]) + bias[lane][r] : up_inf();
         }
         cell0[lane] = up_min(d[lane][0], v[lane][0]);
-        for (int r = 1; r < R; ++r) T[lane][r] = up_scan_take(T[lane][r], T[lane][r - 1], true);
+        for (int r = 1; r < R; ++r) T[lane][r] = ua_scan_take<uint64_t>(T[lane][r], T[lane][r - 1], true);
         x[lane] = T[lane][R - 1];
       }
       scan_step<S, 1>(x, ul); scan_step<S, 2>(x, ul); scan_step<S, 4>(x, ul); scan_step<S, 8>(x, ul); scan_step<S, 16>(x, ul); scan_step<S, 32>(x, ul);
       if (R > 1) {
         for (uint32_t lane = 0; lane < 64; ++lane) ex[lane] = from_lane(x, lane - 1u);
         for (uint32_t lane = 0; lane < 64; ++lane)
-          for (int r = 0; r < R - 1; ++r) T[lane][r] = up_scan_take(T[lane][r], ex[lane], ul[lane] > 0u);
+          for (int r = 0; r < R - 1; ++r) T[lane][r] = ua_scan_take<uint64_t>(T[lane][r], ex[lane], ul[lane] > 0u);
       }
       for (uint32_t lane = 0; lane < 64; ++lane) { T[lane][R - 1] = x[lane]; lsend[lane] = pick<uint64_t, R>(T[lane], last_reg[lane]); }
       for (uint32_t lane = 0; lane < 64; ++lane) last[lane] = from_lane(lsend, last_lane[lane]);
