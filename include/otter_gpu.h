@@ -272,7 +272,14 @@ int otg_cluster_trace_batch(otg_ctx* ctx, const otg_params* params,
 
 /* Replaces PPOA (src/anppoa.hpp:64-380) as driven by rapid_consensus (src/analignments.cpp:261-292):
  * graph g has backbone = task `backbone`, then members inserted in order; each member is a
- * sequence + its op string + spanning flags.  c/t are the adjust_weights arguments.
+ * sequence + its op string + spanning flags.  c/t are the adjust_weights arguments, per graph:
+ * every edge weight w (a count, at most n_members + 1) becomes w - max(c, t * w) before the
+ * heaviest-path sweep, in FP32, the product and the subtraction rounded separately (no
+ * contraction into a fused multiply-add), as the reference's own build computes it.  Any finite
+ * float of any sign is supported for both: c = 0, t = 1 makes every weight zero (the tie-breaks
+ * alone pick the path), c > n_members + 1 makes every weight negative; the results match the
+ * reference bit for bit there too.  NaN and infinities are the caller's problem (not checked).
+ * rapid_consensus passes c = (float)(n * 0.4), 1 below four reads, and t = 0.3f.
  * Output consensus strings in out_arena (same off/len convention as cigars).                   */
 typedef struct otg_poa_member {
   uint64_t seq_off;   uint32_t seq_len;   uint32_t cigar_len;

@@ -129,6 +129,16 @@ def consensus_weights(n_reads_in_allele):
     return c, np.float32(0.3)
 
 
+def poa_specs_with_weights(specs, weights):
+    """The graph specs with other adjust_weights arguments: weights(n, c, t) -> (c, t) per graph, n = its member count (an edge weight is at
+    most n + 1), (c, t) = what the spec holds.  Both are narrowed to float32, as otg_poa_graph stores them; the specs are left unchanged."""
+    out = []
+    for bb, mem, c, t in specs:
+        c2, t2 = weights(len(mem), c, t)
+        out.append((bb, mem, np.float32(c2), np.float32(t2)))
+    return out
+
+
 def random_poa_specs(rng, oracle, n_graphs, lmin, lmax, err=0.07, partial=True):
     """Allele-like read sets aligned to their first read with the oracle's affine WFA (end2end or the
     ends-free forms rapid_consensus uses, src/analignments.cpp:266-279)."""

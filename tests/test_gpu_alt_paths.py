@@ -34,6 +34,10 @@ MR_EDIT_AD, MR_AFFINE_AD = "tests/test_gpu_match_runs.py::test_match_runs_edit_a
 # the packed pair, probe and extend step of the adaptive window kernels, with each of them as the first tier
 PP_EDGES = "tests/test_gpu_adaptive.py::test_adaptive_packed_pair_edges"
 
+# the consensus under other adjust_weights arguments (test_gpu_poa_weights.py: every damped edge weight zero, every one negative, a (c, t) per
+# graph): the first-generation Kahn sweep, the second generation on every graph and the piece loop then see them too
+POA_WEIGHTS = "tests/test_gpu_poa_weights.py"
+
 CASES = [
     ("OTG_NO_AFFINE_BOUND", ["tests/test_gpu_affine.py"] + PENALTIES),                               # no score bound: everything on the HBM-row tiers, un-pruned
     ("OTG_AFFINE_REG=0", ["tests/test_gpu_affine.py", ROUTING, MR_AFFINE] + PENALTIES),                              # bound + HBM-row tiers only (what the register tiers fall back to)
@@ -43,9 +47,9 @@ CASES = [
     ("OTG_NO_EDIT_ROUTE OTG_NO_EDIT_SORT", ["tests/test_gpu_edit.py"]),
     ("OTG_NO_EDIT_SAMPLE", ["tests/test_gpu_edit.py"]),
     ("OTG_EDIT_TIERS=255", ["tests/test_gpu_edit.py"]),                                 # all eight bit-parallel tiers (the two three-block ones only run on passes with millions of pairs otherwise)
-    ("OTG_POA_V1 OTG_POA_NO_LDS", ["tests/test_gpu_poa.py", "tests/test_gpu_pipeline.py::test_ont_kb"]),   # first-generation POA (serial threading, Kahn sweep), global memory only
-    ("OTG_POA_NO_LDS", ["tests/test_gpu_poa.py"]),                                       # second-generation POA on every graph (the op-string fuzz and the insertion stretches in global memory)
-    ("OTG_POA_PIECE_MB=1", ["tests/test_gpu_poa.py", "tests/test_gpu_pipeline.py::test_ont_kb"]),         # graph images in many small pieces that reuse the work arrays
+    ("OTG_POA_V1 OTG_POA_NO_LDS", ["tests/test_gpu_poa.py", POA_WEIGHTS, "tests/test_gpu_pipeline.py::test_ont_kb"]),   # first-generation POA (serial threading, Kahn sweep), global memory only
+    ("OTG_POA_NO_LDS", ["tests/test_gpu_poa.py", POA_WEIGHTS]),                                       # second-generation POA on every graph (the op-string fuzz and the insertion stretches in global memory)
+    ("OTG_POA_PIECE_MB=1", ["tests/test_gpu_poa.py", POA_WEIGHTS, "tests/test_gpu_pipeline.py::test_ont_kb"]),         # graph images in many small pieces that reuse the work arrays
     ("OTG_NO_REASSIGN_REV", ["tests/test_gpu_pipeline.py::test_haps_mode", "tests/test_gpu_pipeline.py::test_ont_kb"]),
     ("OTG_CLUSTER_WIDE=1", ["tests/test_gpu_cluster.py", "tests/test_gpu_genotype.py", "tests/test_gpu_pipeline.py::test_edge_regions",
                            "tests/test_gpu_cluster_trace.py", "tests/test_gpu_genotype_trace.py"]),   # every region on the wide clustering kernels (HBM scratch), their intermediates included

@@ -47,14 +47,13 @@ def test_poa_hifi(gpu, oracle):
     _check(gpu, oracle, random_poa_specs(rng, oracle, 60, 300, 700, err=0.002))
 
 
-def test_poa_op_string_fuzz(gpu, oracle):
+def op_string_fuzz_specs(rng, n_graphs):
     """Op strings that are NOT alignment output: random valid op sequences (M/X/D count = backbone length, M/X/I count =
     read length) built from runs whose lengths straddle the 64-op chunks the wave kernel reads, starting with any op,
     with long gap runs, consecutive insertions and deletions, for spanning and non-spanning members."""
     from helpers import rand_seq
-    rng = np.random.default_rng(44)
     specs = []
-    for g in range(120):
+    for g in range(n_graphs):
         B = int(rng.integers(2, 400)) if g % 4 else int(rng.choice([2, 3, 11, 63, 64, 65, 127, 128, 129, 192]))
         bb = rand_seq(rng, B)
         mem = []
@@ -76,23 +75,29 @@ def test_poa_op_string_fuzz(gpu, oracle):
         n = len(mem)
         c = np.float32(n * 0.4) if n >= 4 else np.float32(1.0)
         specs.append((bb, mem, c, np.float32(0.3)))
-    _check(gpu, oracle, specs)
+    return specs
 
 
-def test_poa_lds_capacity_mix(gpu, oracle):
+def test_poa_op_string_fuzz(gpu, oracle):
+    """120 graphs of op_string_fuzz_specs."""
+    _check(gpu, oracle, op_string_fuzz_specs(np.random.default_rng(44), 120))
+
+
+def lds_capacity_mix_specs(rng, n_graphs, every=20, kinds=(1, 2, 3), noisy_members=(8, 30)):
     """The LDS kernel sizes its block for the optimistic need of 97 % of the batch: a crowd of small, clean windows sets a small
     block; graphs of the same backbone length whose members disagree everywhere (random target bases: alt nodes and edges close
     to the worst-case bound) outgrow it mid-way and must be redone by the global-memory kernel; a few long backbones never fit.
-    With 40 members a window also passes 255 edges per node list.  All must equal the oracle."""
+    With 40 members a window also passes 255 edges per node list.  All must equal the oracle.
+    Every `every`-th graph is not of the crowd: kinds[k] of the k-th such graph says which (1: 40 noisy members, 2: `noisy_members` noisy ones,
+    3: a long backbone)."""
     from helpers import rand_seq, mutate
-    rng = np.random.default_rng(45)
     specs = []
-    for g in range(400):
+    for g in range(n_graphs):
         B = int(rng.integers(120, 180))
         bb = rand_seq(rng, B)
-        kind = 0 if g % 20 else (1 + (g // 20) % 3)
+        kind = 0 if g % every else kinds[(g // every) % len(kinds)]
         mem = []
-        nmem = 40 if kind == 1 else int(rng.integers(8, 30))
+        nmem = 40 if kind == 1 else int(rng.integers(*(noisy_members if kind == 2 else (8, 30))))
         if kind == 3:
             B = int(rng.integers(2500, 4000)); bb = rand_seq(rng, B); nmem = 6
         for _ in range(nmem):
@@ -109,19 +114,26 @@ def test_poa_lds_capacity_mix(gpu, oracle):
             mem.append((rand_seq(rng, max(tlen, 1))[:tlen], cig, bool(rng.random() < 0.9), bool(rng.random() < 0.9)))
         n = len(mem)
         specs.append((bb, mem, np.float32(n * 0.4), np.float32(0.3)))
-    _check(gpu, oracle, specs)
+    return specs
 
 
-def test_poa_crowded_anchors_and_long_jumps(gpu, oracle):
+def test_poa_lds_capacity_mix(gpu, oracle):
+    """400 graphs of lds_capacity_mix_specs: 380 in the crowd, 20 others.  With 5 % of its graphs large this batch's graph of rank 97 % needs
+    more than the 16 KB a block may have, so the launch plan gives ALL of it to the global-memory kernel (OTG_POA_PROFILE: 0 LDS + 400 global
+    launches); the mix that starts in LDS and is redone half-way is the `ldsmix` set of poa_weights_cases.py, which test_gpu_poa_weights.py runs
+    at the defaults too (test_poa_defaults_after_other_weights) and whose launch lists it counts (test_fixtures_reach_both_kernels_and_the_redo)."""
+    _check(gpu, oracle, lds_capacity_mix_specs(np.random.default_rng(45), 400))
+
+
+def crowded_anchor_specs(rng, n_graphs):
     """Shapes the second-generation path handles apart: many members leaving the backbone at the SAME node with long, different
     insertions (one anchor with hundreds of subtree edges: swept in pieces of 64), shared insertion prefixes (subtrees that branch),
     deletions longer than the 128-node window of backbone weights (landings written straight to memory), members that start off
     the backbone (start-node subtrees), and 300-op runs without an 'M' (serial threading in the middle of an op string).  Large
     backbones so that the graphs stay out of LDS."""
     from helpers import rand_seq
-    rng = np.random.default_rng(46)
     specs = []
-    for g in range(12):
+    for g in range(n_graphs):
         B = int(rng.integers(2600, 3400))
         bb = rand_seq(rng, B)
         pos = int(rng.integers(200, B - 900))
@@ -167,7 +179,12 @@ def test_poa_crowded_anchors_and_long_jumps(gpu, oracle):
         n = len(mem)
         c = np.float32(n * 0.4) if n >= 4 else np.float32(1.0)
         specs.append((bb, mem, c, np.float32(0.3)))
-    _check(gpu, oracle, specs)
+    return specs
+
+
+def test_poa_crowded_anchors_and_long_jumps(gpu, oracle):
+    """12 graphs of crowded_anchor_specs."""
+    _check(gpu, oracle, crowded_anchor_specs(np.random.default_rng(46), 12))
 
 
 def test_poa_shared_and_private_insertions(gpu, oracle):
