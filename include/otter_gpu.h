@@ -1252,6 +1252,107 @@ typedef struct otg_unitparse_job {
 int otg_unitparse_files(const otg_unitparse_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
 
 /* ---------------------------------------------------------------------------------------------
+ * Tract mode of the copy numbers: find the repeat inside a flanked allele.  The unit alignment above is global in the allele, so flank
+ * bases inside a region count as edits.  Here a local (Smith-Waterman style) wraparound alignment locates the tract, and the unit
+ * alignment is then applied to exactly that tract.  The reference has no counterpart; this is the definition (all integers).
+ * Codes, folding and matching are those of the unit alignment: code 4 matches nothing, letter case changes nothing.  The scores are
+ * otg_tract_params {match, mismatch, indel, min_score}; otg_tract_params_default gives (2, 7, 7, 24); 1 <= match <= 16, 1 <= mismatch <= 64,
+ * 1 <= indel <= 64 and min_score <= 2^24, anything else is OTG_ERR_ARG.  For an allele s of length L and a unit u of length p,
+ * 1 <= p <= OTG_UNITALIGN_MAX_UNIT:
+ *   1. Cell (i, j) is "i bases of s consumed, the next unit base is u[j]".  Its value is the pair (score, begin), ordered by the larger
+ *      score, then the LARGER begin (the tight tract).
+ *   2. C[0][j] = (0, 0).
+ *   3. Row i + 1 starts every position at the fresh start (0, i + 1) and takes the maximum of
+ *        the diagonal step             C[i][j] -> C[i+1][(j+1) % p] with + match when c_s[i] == c_u[j] && c_s[i] < 4, else - mismatch;
+ *        a base of s outside the unit  C[i][j] -> C[i+1][j] with - indel;
+ *        a skipped unit base           C[i+1][j] -> C[i+1][(j+1) % p] with - indel, taken to its fixed point around the cycle.
+ *      A candidate whose score is not positive is dropped (a fresh start beats it: it has the largest begin a row can hold).  Steps keep begin.
+ *   4. The best cell over all rows 0..L and positions: the largest score, then the SMALLEST i (= end), then the larger begin, then the
+ *      smallest j.
+ *   5. score = 0 or score < min_score: begin = end = edits = unit_bases = end_phase = start_phase = 0, flags = OTG_TRACT_NONE; score is
+ *      still reported.
+ *   6. Otherwise (edits, unit_bases, end_phase) are, by definition, the otg_unitalign record of the bytes s[begin, end) against u, and
+ *      start_phase = (end_phase - unit_bases) mod p.
+ *   7. p = 0: zeros and OTG_TRACT_NO_UNIT.  L > OTG_TRACT_MAX_LEN: zeros and OTG_TRACT_TOO_LONG.  p > OTG_UNITALIGN_MAX_UNIT: OTG_ERR_ARG when
+ *      the caller passes the unit in, zeros and OTG_TRACT_UNIT_TOO_LONG when it comes from the motif annotation.  L = 0: score 0 and
+ *      OTG_TRACT_NONE.
+ * It follows that N bytes in front of s move begin and end by their count and change nothing else, that N bytes behind s change nothing,
+ * that a rotated unit changes only the two phases, that score <= match * (end - begin), and that a tract begins and ends on a match.
+ *   otg_tract_batch           alleles, units and tasks as in otg_unitalign_batch; params == NULL: the defaults.  out: n_tasks records, NULL
+ *                             leaves them in HBM.  Refusals as otg_unitalign_batch, and OTG_ERR_ARG for scores out of range;
+ *   otg_tract_motifs          task i = allele i of the latest motif call on the context against that call's unit i, both read where they
+ *                             lie in HBM (as otg_unitalign_motifs): a motif unit found on a flanked allele;
+ *   otg_tract_cohort          rows of the cohort arena in place, with the caller's units or (unit_arena == NULL) those of the latest
+ *                             otg_motif_cohort; preconditions and refusals as otg_unitalign_cohort;
+ *   otg_tract_device_results  the device pointer of the latest records on this context, valid until the next tract call on the context or
+ *                             otg_destroy; every output is nullable;
+ *   otg_tract_last_ms         HIP-event times (ms) of the latest call: *ms = both passes, *local_ms (nullable) = the local pass alone;
+ *   otg_tract_emit            per task t the row region \t i \t seq_len \t source \t unit \t begin \t end \t score \t edits \t unit_bases \t
+ *                             copies \t identity \n, arguments as otg_unitalign_emit: copies "%.2f" of unit_bases / p and identity "%.4f" of
+ *                             1 - edits / max(end - begin, unit_bases); both are 0.00 / 0.0000 when a flag is set or the denominator is 0.
+ *                             Buffer protocol of otg_emit_alleles.
+ * A tract call runs the unit alignment as its second pass, on sub-rows of the same arena, so it counts as a unit alignment on the context:
+ * it replaces what otg_unitalign_device_results and otg_unitalign_last_ms return (task t: the record of s[begin, end), an empty row for a
+ * task without a tract).  The local pass has the layout of the unit alignment (the row in registers, 4 .. 64 lanes per task).  The key is
+ * score * 2^16 + begin in 32 bits while the allele is no longer than the bound otg_tract_core.hpp derives from the call's scores and the
+ * unit length, 32 / 32 in 64 bits above.  OTG_TRACT_WIDE=1 sends every task through the 64-bit tier, OTG_TRACT_SEG64=1 gives every task a
+ * whole wave (both read once per process).
+ * ------------------------------------------------------------------------------------------- */
+#define OTG_TRACT_MAX_LEN       1048575
+#define OTG_TRACT_NO_UNIT       1u   /* otg_tract.flags */
+#define OTG_TRACT_TOO_LONG      2u
+#define OTG_TRACT_UNIT_TOO_LONG 4u
+#define OTG_TRACT_NONE          8u   /* no tract: score 0 or below min_score                             */
+typedef struct otg_tract_params {
+  uint32_t match;                /* added per matching base: 1..16                                   */
+  uint32_t mismatch;             /* taken off per mismatching base: 1..64                            */
+  uint32_t indel;                /* taken off per inserted or skipped base: 1..64                    */
+  uint32_t min_score;            /* a tract scores at least this: 0..2^24                            */
+} otg_tract_params;
+typedef struct otg_tract {
+  uint32_t score;                /* of the best local alignment, also when there is no tract         */
+  uint32_t begin;                /* the tract is s[begin, end)                                       */
+  uint32_t end;
+  uint32_t edits;                /* the otg_unitalign record of the tract                            */
+  uint32_t unit_bases;
+  uint32_t end_phase;
+  uint32_t start_phase;          /* (end_phase - unit_bases) mod p                                   */
+  uint32_t flags;                /* OTG_TRACT_NO_UNIT / _TOO_LONG / _UNIT_TOO_LONG / _NONE           */
+} otg_tract;
+void otg_tract_params_default(otg_tract_params* params);
+int otg_tract_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_bytes, const uint64_t* seq_off, const uint32_t* seq_len,
+                    uint32_t n_seqs, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off, const uint32_t* unit_len,
+                    uint32_t n_units, const uint32_t* task_seq, const uint32_t* task_unit, uint32_t n_tasks, const otg_tract_params* params,
+                    otg_tract* out);
+int otg_tract_motifs(otg_ctx* ctx, const otg_tract_params* params, otg_tract* out);
+int otg_tract_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off,
+                     const uint32_t* unit_len, uint32_t n_units, const uint32_t* task_seq, const uint32_t* task_unit, uint32_t n_tasks,
+                     const otg_tract_params* params, otg_tract* out);
+int otg_tract_device_results(otg_ctx* ctx, uint32_t* n_tasks, const otg_tract** records);
+int otg_tract_last_ms(otg_ctx* ctx, double* ms, double* local_ms);
+int otg_tract_emit(const otg_vcf_record* records, uint32_t n_records, const char* region_arena, const uint32_t* seq_len, const uint64_t* task_first,
+                   const uint8_t* task_source, const uint8_t* unit_arena, const uint64_t* task_unit_off, const uint32_t* task_unit_len,
+                   const otg_tract* tracts, char* out, uint64_t out_capacity, uint64_t* out_len);
+/* The tracts of the alleles of a VCF against a tandem-repeat catalogue, in file order, built as otg_copies_files is: the same catalogue
+ * lookup, the motif-annotation unit where the catalogue gives none, one otg_tract_emit row per allele and unit.  Out-of-range parameters
+ * are OTG_ERR_ARG with the message the tool prints.  stats as otg_vcf2mat_files. */
+typedef struct otg_tracts_job {
+  const char* vcf_path;          /* positional <VCF[.GZ]>                                            */
+  const char* bed_path;          /* -b: required, the catalogue                                      */
+  uint32_t    max_period;        /* -p: 1..OTG_MOTIF_MAX_PERIOD (the tool's default: 256)            */
+  uint32_t    slack;             /* --slack: 0..999 per mille (the tool's default: 50)               */
+  uint32_t    match;             /* --scores match,mismatch,indel (the tool's default: 2,7,7)        */
+  uint32_t    mismatch;
+  uint32_t    indel;
+  uint32_t    min_score;         /* --min-score: 0..2^24 (the tool's default: 24)                    */
+  int32_t     threads;           /* -t: host threads of the emit                                     */
+  int32_t     device;            /* HIP device ordinal                                               */
+  uint32_t    batch_alleles;     /* alleles per batch, 0 = 65536                                     */
+  uint32_t    reserved;
+} otg_tracts_job;
+int otg_tracts_files(const otg_tracts_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
+
+/* ---------------------------------------------------------------------------------------------
  * Indexed allele BAMs from the product's own SAM text.  Every writer above emits SAM text and every reader wants a
  * coordinate-sorted BAM with its `.bai`; the reference's workflow goes through `samtools view -bh | samtools sort`, `samtools index` and
  * `samtools merge -pco` in between.  Host code (zlib + threads), no device work.

@@ -34,6 +34,8 @@ EXPORTS = [
     "otg_parse_bed_units", "otg_copies_files",
     "otg_unitparse_batch", "otg_unitparse_collect", "otg_unitparse_device_results", "otg_unitparse_last_ms", "otg_unitparse_cohort", "otg_unitparse_emit",
     "otg_unitparse_files",
+    "otg_tract_params_default", "otg_tract_batch", "otg_tract_motifs", "otg_tract_cohort", "otg_tract_device_results", "otg_tract_last_ms", "otg_tract_emit",
+    "otg_tracts_files",
 ]
 
 _lib = None
@@ -390,6 +392,49 @@ class Context:
     def unitalign_last_ms(self):
         """binning and alignment ms of the latest unit alignment on this context (HIP events)."""
         return self._last_ms("otg_unitalign_last_ms", 1)
+
+    def tract_batch(self, arena, seq_off, seq_len, units, task_seq, task_unit, match=2, mismatch=7, indel=7, min_score=24, device_tensor=False):
+        """otg_tract_batch: the repeat tract of unit units[task_unit[t]] inside allele task_seq[t] (a local wraparound alignment; include/otter_gpu.h
+        states the rule) and the unit alignment of exactly that tract -> records [n_tasks] of abi.tract_dt as a numpy array; or with
+        device_tensor=True an int32 [n_tasks, 8] torch tensor on this context's device that wraps the records in HBM without a copy (valid until
+        the next tract call on this context).  The call counts as a unit alignment on the context."""
+        rows, ln = _rows(arena, seq_off, seq_len)
+        uarena, uoff, ulen = _pack_units(units)
+        ts = np.ascontiguousarray(task_seq, dtype=np.uint32)
+        tu = np.ascontiguousarray(task_unit, dtype=np.uint32)
+        if len(ts) != len(tu):
+            raise ValueError("task_seq and task_unit differ in length")
+        n = len(ts)
+        out = np.zeros(n, dtype=abi.tract_dt)
+        q = abi.TractParams(match, mismatch, indel, min_score)
+        rc = self._L.otg_tract_batch(self._h, *rows, abi.ptr(uarena), C.c_uint64(int(ulen.sum())), abi.ptr(uoff), abi.ptr(ulen), C.c_uint32(len(ulen)), abi.ptr(ts), abi.ptr(tu), C.c_uint32(n),
+                                     C.byref(q), None if device_tensor else abi.ptr(out))
+        self._check(rc, "otg_tract_batch")
+        return self._tract_device_results(n) if device_tensor else out
+
+    def tract_motifs(self, match=2, mismatch=7, indel=7, min_score=24, device_tensor=False):
+        """otg_tract_motifs: inside every allele of the latest motif call on this context (motif_batch, cohort_motifs) the tract of the unit that
+        call found for it, both read where they lie in HBM -> records as tract_batch returns them (period 0: flags TRACT_NO_UNIT, a unit over
+        UNITALIGN_MAX_UNIT bytes: TRACT_UNIT_TOO_LONG)."""
+        m = C.c_uint32(0)
+        self._check(self._L.otg_motif_device_results(self._h, C.byref(m), None, None, None), "otg_tract_motifs")
+        out = np.zeros(m.value, dtype=abi.tract_dt)
+        q = abi.TractParams(match, mismatch, indel, min_score)
+        self._check(self._L.otg_tract_motifs(self._h, C.byref(q), None if device_tensor else abi.ptr(out)), "otg_tract_motifs")
+        return self._tract_device_results(m.value) if device_tensor else out
+
+    def _tract_device_results(self, n):
+        if n == 0:
+            import torch
+            return torch.zeros((0, 8), dtype=torch.int32, device=torch.device("cuda", self.device))
+        m, p = C.c_uint32(0), C.c_void_p()
+        self._check(self._L.otg_tract_device_results(self._h, C.byref(m), C.byref(p)), "otg_tract_device_results")
+        assert m.value == n
+        return self._wrap_device(p.value, (n, 8), "<i4")
+
+    def tract_last_ms(self):
+        """(both passes ms, the local pass alone ms) of the latest tract call on this context (HIP events)."""
+        return self._last_ms("otg_tract_last_ms", 2)
 
     def unitparse_batch(self, arena, seq_off, seq_len, unit_sets, task_seq, task_set, device_tensor=False):
         """otg_unitparse_batch (and otg_unitparse_collect): allele task_seq[t] parsed against the unit set unit_sets[task_set[t]] (a list of lists
@@ -782,6 +827,31 @@ class Context:
         rc = self._L.otg_unitalign_cohort(self._h, C.c_uint32(row_begin), C.c_uint32(n), *args, None if device_tensor else abi.ptr(out))
         self._check(rc, "otg_unitalign_cohort")
         return self._unitalign_device_results(nt) if device_tensor else out
+
+    def cohort_tracts(self, row_begin=0, n=None, units=None, task_seq=None, task_unit=None, match=2, mismatch=7, indel=7, min_score=24, device_tensor=False):
+        """otg_tract_cohort: the tracts inside rows [row_begin, row_begin + n) of the row list (n=None: to the end), the alleles read in the cohort
+        arena in place -> records as tract_batch returns them.  units=None: row i against the unit the latest cohort_motifs over the same rows
+        found for it.  Otherwise a list of byte strings with task lists as in tract_batch, task_seq counted from row_begin."""
+        if n is None:
+            total = C.c_uint32(0)
+            self._check(self._L.otg_kmer_cohort_rows(self._h, C.byref(total), None, None, None), "otg_kmer_cohort_rows")
+            n = max(0, total.value - int(row_begin))
+        n = int(n)
+        if units is None:
+            nt, args = n, (None, C.c_uint64(0), None, None, C.c_uint32(0), None, None, C.c_uint32(0))
+        else:
+            uarena, uoff, ulen = _pack_units(units)
+            ts = np.ascontiguousarray(task_seq, dtype=np.uint32)
+            tu = np.ascontiguousarray(task_unit, dtype=np.uint32)
+            if len(ts) != len(tu):
+                raise ValueError("task_seq and task_unit differ in length")
+            nt, args = len(ts), (abi.ptr(uarena), C.c_uint64(int(ulen.sum())), abi.ptr(uoff), abi.ptr(ulen), C.c_uint32(len(ulen)), abi.ptr(ts), abi.ptr(tu),
+                                 C.c_uint32(len(ts)))
+        out = np.zeros(nt, dtype=abi.tract_dt)
+        q = abi.TractParams(match, mismatch, indel, min_score)
+        rc = self._L.otg_tract_cohort(self._h, C.c_uint32(row_begin), C.c_uint32(n), *args, C.byref(q), None if device_tensor else abi.ptr(out))
+        self._check(rc, "otg_tract_cohort")
+        return self._tract_device_results(nt) if device_tensor else out
 
     def cohort_unitparse(self, unit_sets, task_seq, task_set, row_begin=0, n=None, device_tensor=False):
         """otg_unitparse_cohort: rows [row_begin, row_begin + n) of the row list (n=None: to the end) parsed against unit sets, the alleles read
@@ -1750,3 +1820,39 @@ def copies_files(vcf, bed, max_period=256, slack=50, threads=1, device=0, batch_
     job.vcf_path = vcf.encode(); job.bed_path = bed.encode()
     job.max_period = max_period; job.slack = slack; job.threads = threads; job.device = device; job.batch_alleles = batch_alleles
     return _run_files_job("otg_copies_files", job, abi.CopiesJob)
+
+
+def tract_emit(records, regions, seq_len, task_first, task_source, units, tracts):
+    """otg_tract_emit: the rows of otter_tracts for the records (vcf_record_dt), arguments as unitalign_emit with tracts[t] (tract_dt) the record
+    of task t -> text bytes."""
+    L = load()
+    records = np.ascontiguousarray(records, dtype=abi.vcf_record_dt)
+    seq_len = np.ascontiguousarray(seq_len, dtype=np.uint32)
+    task_first = np.ascontiguousarray(task_first, dtype=np.uint64)
+    task_source = np.ascontiguousarray(task_source, dtype=np.uint8)
+    tracts = np.ascontiguousarray(tracts, dtype=abi.tract_dt)
+    uarena, uoff, ulen = _pack_units(units)
+    if tracts.size == 0:
+        tracts, task_source, uoff, ulen = np.zeros(1, dtype=abi.tract_dt), np.zeros(1, dtype=np.uint8), np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint32)
+    reg = np.frombuffer(regions + b"\0", dtype=np.uint8)
+    need = C.c_uint64(0)
+    args = lambda out, cap: (abi.ptr(records), C.c_uint32(len(records)), abi.ptr(reg), abi.ptr(seq_len), abi.ptr(task_first), abi.ptr(task_source), abi.ptr(uarena),
+                             abi.ptr(uoff), abi.ptr(ulen), abi.ptr(tracts), out, C.c_uint64(cap), C.byref(need))
+    rc = L.otg_tract_emit(*args(None, 0))
+    if rc not in (0, abi.OTG_ERR_CAPACITY):
+        raise OtterGpuError("otg_tract_emit failed (%d): %s" % (rc, _err(L)))
+    out = C.create_string_buffer(need.value + 1)
+    rc = L.otg_tract_emit(*args(out, need.value))
+    if rc != 0:
+        raise OtterGpuError("otg_tract_emit failed (%d): %s" % (rc, _err(L)))
+    return out.raw[:need.value]
+
+
+def tracts_files(vcf, bed, max_period=256, slack=50, match=2, mismatch=7, indel=7, min_score=24, threads=1, device=0, batch_alleles=0):
+    """otg_tracts_files: the repeat tract inside every allele of a VCF (plain, gzip or BGZF) against the units of a tandem-repeat catalogue, or
+    against the allele's own motif-annotation unit where the catalogue gives none, as text.  Returns (text bytes, stats dict)."""
+    job = abi.TractsJob()
+    job.vcf_path = vcf.encode(); job.bed_path = bed.encode()
+    job.max_period = max_period; job.slack = slack; job.match = match; job.mismatch = mismatch; job.indel = indel; job.min_score = min_score
+    job.threads = threads; job.device = device; job.batch_alleles = batch_alleles
+    return _run_files_job("otg_tracts_files", job, abi.TractsJob)

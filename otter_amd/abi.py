@@ -289,6 +289,29 @@ class CopiesJob(C.Structure):
                 ("device", C.c_int32), ("batch_alleles", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+# otg_tract / otg_tract_params (include/otter_gpu.h) and the bounds of the tract mode
+tract_dt = np.dtype([("score", np.uint32), ("begin", np.uint32), ("end", np.uint32), ("edits", np.uint32), ("unit_bases", np.uint32),
+                     ("end_phase", np.uint32), ("start_phase", np.uint32), ("flags", np.uint32)])
+assert tract_dt.itemsize == 32
+TRACT_MAX_LEN = 1048575
+TRACT_NO_UNIT = 1
+TRACT_TOO_LONG = 2
+TRACT_UNIT_TOO_LONG = 4
+TRACT_NONE = 8
+
+
+class TractParams(C.Structure):
+    """otg_tract_params (include/otter_gpu.h)."""
+    _fields_ = [("match", C.c_uint32), ("mismatch", C.c_uint32), ("indel", C.c_uint32), ("min_score", C.c_uint32)]
+
+
+class TractsJob(C.Structure):
+    """otg_tracts_job (include/otter_gpu.h)."""
+    _fields_ = [("vcf_path", C.c_char_p), ("bed_path", C.c_char_p), ("max_period", C.c_uint32), ("slack", C.c_uint32), ("match", C.c_uint32),
+                ("mismatch", C.c_uint32), ("indel", C.c_uint32), ("min_score", C.c_uint32), ("threads", C.c_int32), ("device", C.c_int32),
+                ("batch_alleles", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class JobStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_regions", "n_regions_ok", "n_regions_skipped", "n_reads", "n_alleles", "input_bytes", "output_bytes")] + \
                [("n_devices", C.c_uint32), ("reserved", C.c_uint32)] + [(k, C.c_double) for k in ("ms_total", "ms_ingest", "ms_hot_path", "ms_emit")]

@@ -564,6 +564,31 @@ int otg_unitalign_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, const uin
   return otg_unitalign_resident(ctx, "otg_unitalign_cohort", rows, units, d_ts, d_tu, n_tasks, out);
 }
 
+int otg_tract_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off,
+                     const uint32_t* unit_len, uint32_t n_units, const uint32_t* task_seq, const uint32_t* task_unit, uint32_t n_tasks,
+                     const otg_tract_params* params, otg_tract* out)
+{
+  Cohort* c = nullptr;
+  OtgRows rows;
+  otg_tract_params q;
+  if (int rc = cohort_clustered(ctx, "otg_tract_cohort", &c)) return rc;
+  if (int rc = otg_tract_args(ctx, "otg_tract_cohort", params, &q)) return rc;
+  if (int rc = cohort_rows(ctx, *c, "otg_tract_cohort", row_begin, n, &rows)) return rc;
+  if (!unit_arena && !n_units) {                                   // the units of the latest otg_motif_cohort, which stay where they are
+    if (ctx->last_motif_n == 0 || ctx->last_motif_rows.arena != rows.arena || ctx->last_motif_rows.off != rows.off || ctx->last_motif_n != n)
+      return otg_fail(ctx, OTG_ERR_ARG, "otg_tract_cohort: the latest motif call on this context was not otg_motif_cohort over rows %u .. %llu", row_begin,
+                      (unsigned long long)row_begin + n);
+    return otg_tract_motifs(ctx, &q, out);
+  }
+  if (int rc = otg_unitalign_check(ctx, "otg_tract_cohort", n, unit_arena, unit_bytes, unit_off, unit_len, n_units, task_seq, task_unit, n_tasks)) return rc;
+  if (n_tasks == 0) return otg_tract_resident(ctx, "otg_tract_cohort", rows, OtgUnitSource{nullptr, nullptr, nullptr, nullptr, 0u}, nullptr, nullptr, 0, q, out);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  OtgUnitSource units;
+  const uint32_t *d_ts = nullptr, *d_tu = nullptr;
+  if (int rc = otg_unitalign_upload(ctx, unit_arena, unit_bytes, unit_off, unit_len, n_units, task_seq, task_unit, n_tasks, &units, &d_ts, &d_tu, SLOT_TRACT_UNITS)) return rc;
+  return otg_tract_resident(ctx, "otg_tract_cohort", rows, units, d_ts, d_tu, n_tasks, q, out);
+}
+
 int otg_unitparse_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off,
                          const uint32_t* unit_len, uint32_t n_units, const uint64_t* set_first, uint32_t n_sets, const uint32_t* task_seq,
                          const uint32_t* task_set, uint32_t n_tasks, otg_unitparse_sum* sums, uint64_t* seg_off, uint64_t* n_segments)

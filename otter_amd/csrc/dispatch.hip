@@ -18,6 +18,7 @@
 #include "otg_motif.hpp"
 #include "otg_repeat.hpp"
 #include "otg_unitalign.hpp"
+#include "otg_tract.hpp"
 #include "otg_unitparse.hpp"
 #include "otg_unitparse_core.hpp"
 #include <cmath>
@@ -1196,23 +1197,25 @@ int otg_repeats_files(const otg_repeats_job* job, otg_write_fn write, void* user
     });
 }
 
-// Copy numbers of a VCF's alleles against a tandem-repeat catalogue, on vcf_allele_job as otg_motifs_files.  A batch makes up to two device
-// passes: the alleles of catalogue regions against their units (otg_unitalign_batch, only the units the batch uses are uploaded), the others
-// through otg_motif_batch and otg_unitalign_motifs, whose units never leave the device in between.
-int otg_copies_files(const otg_copies_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
+// The rows of a VCF's alleles against the units of a tandem-repeat catalogue, on vcf_allele_job as otg_motifs_files: what otg_copies_files and
+// otg_tracts_files share.  A batch makes up to two device passes: the alleles of catalogue regions against their units (batch_fn, only the
+// units the batch uses are uploaded), the others through otg_motif_batch and motifs_fn, whose units never leave the device in between.
+// Rec = the operator's record (zero: the record of a task that was not run); rows_fn = its row text.
+extern "C++" {
+template <typename Rec, typename BatchFn, typename MotifsFn, typename RowsFn>
+int catalogue_units_job(const char* who, const char* vcf_path, const char* bed_path, uint32_t max_period, uint32_t slack, int32_t device, uint32_t batch_alleles,
+                        int32_t threads, otg_write_fn write, void* user, otg_job_stats* stats, BatchFn batch_fn, MotifsFn motifs_fn, RowsFn rows_fn)
 {
-  if (!job || !write || !job->vcf_path || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "otg_copies_files: NULL job, writer, VCF or BED path");
-  const uint32_t max_period = job->max_period, slack = job->slack;
   if (int rc = motif_cli_args(max_period, slack)) return rc;
   UnitCatalogue cat;
-  if (int rc = cat.load("otg_copies_files", job->bed_path)) return rc;
+  if (int rc = cat.load(who, bed_path)) return rc;
   // per batch: the tasks in file order (allele a: task_first[a] .. task_first[a + 1]) and where each one's unit and record lie
   std::vector<uint64_t> task_first, unit_off, m_off, b_uoff;
   std::vector<uint32_t> unit_len, m_len, b_ulen, b_tseq, b_tunit, b_task, m_task;
   std::vector<uint8_t> source, units, b_units, m_units;
-  std::vector<otg_unitalign> aligned, part;
+  std::vector<Rec> aligned, part;
   std::vector<otg_motif> motifs;
-  return vcf_allele_job("otg_copies_files", job->vcf_path, job->bed_path, job->device, job->batch_alleles ? job->batch_alleles : 65536, job->threads, write, user, stats,
+  return vcf_allele_job(who, vcf_path, bed_path, device, batch_alleles ? batch_alleles : 65536, threads, write, user, stats,
     [&](otg_ctx* ctx, const VcfBatch& B) {
       task_first.assign((size_t)B.na + 1, 0);
       unit_off.clear(); unit_len.clear(); source.clear(); units.clear();
@@ -1247,11 +1250,11 @@ int otg_copies_files(const otg_copies_job* job, otg_write_fn write, void* user, 
         }
       }
       task_first[B.na] = source.size();
-      aligned.assign(source.size(), otg_unitalign{0u, 0u, 0u, 0u});
+      aligned.assign(source.size(), Rec{});
       if (!b_task.empty()) {
         part.resize(b_task.size());
-        if (int rc = otg_unitalign_batch(ctx, B.seqs.data(), B.au, B.off.data(), B.len.data(), B.na, b_units.data(), b_units.size(), b_uoff.data(), b_ulen.data(),
-                                         (uint32_t)b_ulen.size(), b_tseq.data(), b_tunit.data(), (uint32_t)b_task.size(), part.data())) return rc;
+        if (int rc = batch_fn(ctx, B.seqs.data(), B.au, B.off.data(), B.len.data(), B.na, b_units.data(), b_units.size(), b_uoff.data(), b_ulen.data(),
+                              (uint32_t)b_ulen.size(), b_tseq.data(), b_tunit.data(), (uint32_t)b_task.size(), part.data())) return rc;
         for (size_t k = 0; k < b_task.size(); ++k) aligned[b_task[k]] = part[k];
       }
       if (!m_task.empty()) {
@@ -1259,7 +1262,7 @@ int otg_copies_files(const otg_copies_job* job, otg_write_fn write, void* user, 
         const uint32_t stride = motif_unit_stride(m_len.data(), nm, max_period);
         motifs.resize(nm); m_units.resize((size_t)nm * stride); part.resize(nm);
         if (int rc = otg_motif_batch(ctx, B.seqs.data(), B.au, m_off.data(), m_len.data(), nm, max_period, slack, motifs.data(), m_units.data(), stride)) return rc;
-        if (int rc = otg_unitalign_motifs(ctx, part.data())) return rc;
+        if (int rc = motifs_fn(ctx, part.data())) return rc;
         for (uint32_t k = 0; k < nm; ++k) {
           const uint32_t t = m_task[k], p = motifs[k].period;
           aligned[t] = part[k];
@@ -1271,9 +1274,35 @@ int otg_copies_files(const otg_copies_job* job, otg_write_fn write, void* user, 
       return (int)OTG_OK;
     },
     [&](std::string& o, const VcfBatch& B, uint32_t r0, uint32_t nr) {
-      otg_unitalign_rows(o, B.rec.data() + r0, nr, B.regions.data(), B.len.data(), task_first.data(), source.data(), units.data(), unit_off.data(), unit_len.data(),
-                         aligned.data());
+      rows_fn(o, B.rec.data() + r0, nr, B.regions.data(), B.len.data(), task_first.data(), source.data(), units.data(), unit_off.data(), unit_len.data(), aligned.data());
     });
+}
+} // extern "C++"
+
+// Copy numbers of a VCF's alleles against a tandem-repeat catalogue: otg_unitalign_batch and otg_unitalign_motifs on catalogue_units_job.
+int otg_copies_files(const otg_copies_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
+{
+  if (!job || !write || !job->vcf_path || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "otg_copies_files: NULL job, writer, VCF or BED path");
+  return catalogue_units_job<otg_unitalign>("otg_copies_files", job->vcf_path, job->bed_path, job->max_period, job->slack, job->device, job->batch_alleles, job->threads,
+                                            write, user, stats, otg_unitalign_batch, otg_unitalign_motifs, otg_unitalign_rows);
+}
+
+// The tracts of a VCF's alleles against a tandem-repeat catalogue: otg_tract_batch and otg_tract_motifs on catalogue_units_job, with the scores.
+int otg_tracts_files(const otg_tracts_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
+{
+  if (!job || !write || !job->vcf_path || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "otg_tracts_files: NULL job, writer, VCF or BED path");
+  const otg_tract_params q{job->match, job->mismatch, job->indel, job->min_score};
+  if (q.match < 1 || q.match > 16 || q.mismatch < 1 || q.mismatch > 64 || q.indel < 1 || q.indel > 64)
+    return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--scores' (%u,%u,%u). Needs to be 1 <= match <= 16, 1 <= mismatch <= 64, 1 <= indel <= 64.", q.match, q.mismatch,
+                    q.indel);
+  if (q.min_score > (1u << 24)) return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--min-score' (%u). Needs to be 0 <= x <= %u.", q.min_score, 1u << 24);
+  return catalogue_units_job<otg_tract>(
+      "otg_tracts_files", job->vcf_path, job->bed_path, job->max_period, job->slack, job->device, job->batch_alleles, job->threads, write, user, stats,
+      [&](otg_ctx* ctx, const uint8_t* seqs, uint64_t au, const uint64_t* off, const uint32_t* len, uint32_t na, const uint8_t* ua, uint64_t ub, const uint64_t* uoff,
+          const uint32_t* ulen, uint32_t nu, const uint32_t* ts, const uint32_t* tu, uint32_t nt, otg_tract* out) {
+        return otg_tract_batch(ctx, seqs, au, off, len, na, ua, ub, uoff, ulen, nu, ts, tu, nt, &q, out);
+      },
+      [&](otg_ctx* ctx, otg_tract* out) { return otg_tract_motifs(ctx, &q, out); }, otg_tract_rows);
 }
 
 // The joint parse of a VCF's alleles against the unit sets of a tandem-repeat catalogue, on vcf_allele_job as otg_copies_files: one task per

@@ -62,6 +62,8 @@ struct otg_ctx {
   OtgRows last_motif_rows = {nullptr, nullptr, nullptr};                                  // where the latest motif call read its alleles (n = last_motif_n): otg_unitalign_motifs aligns them in place
   double last_unitalign_ms = 0.0;                                 // HIP-event time of the latest unit alignment (otg_unitalign_last_ms)
   uint32_t last_unitalign_n = 0;                                  // the records in SLOT_UNITALIGN_OUT (otg_unitalign_device_results); 0: none
+  double last_tract_ms = 0.0, last_tract_local_ms = 0.0;          // HIP-event times of the latest tract call: both passes, the local pass alone (otg_tract_last_ms)
+  uint32_t last_tract_n = 0;                                      // the records in SLOT_TRACT_OUT (otg_tract_device_results); 0: none
   OtgSegLast last_unitparse;                                      // the latest unit parse: SLOT_UNITPARSE_RES / SLOT_UNITPARSE_SEGS, ms = forward, traceback
   double last_kernel_ms = 0.0;                    // HIP-event time of the kernels of the latest operator-level call that reports one (otg_last_kernel_ms)
   // the latest genotype clustering with a metric (genotype_edit.hip): times of its two parts (otg_genotype_metric_last_ms), whether the edit
@@ -154,6 +156,8 @@ enum {
   SLOT_UNITALIGN_OUT,                                               // its records: they stay valid for the device results
   SLOT_UNITPARSE_SEQ, SLOT_UNITPARSE_META, SLOT_UNITPARSE_UNITS, SLOT_UNITPARSE_PLAN, SLOT_UNITPARSE_TRACE,   // otg_unitparse_batch (unitparse.hip)
   SLOT_UNITPARSE_RES, SLOT_UNITPARSE_SEGS,                          // its summaries and offsets / its segments: they stay valid for the device results
+  SLOT_TRACT_SEQ, SLOT_TRACT_META, SLOT_TRACT_UNITS, SLOT_TRACT_BINS, SLOT_TRACT_ORDER, SLOT_TRACT_SUB,   // otg_tract_batch (tract.hip); SUB: the sub-rows of the second pass
+  SLOT_TRACT_OUT,                                                   // its records: they stay valid for the device results
   SLOT_COUNT
 };
 
@@ -432,7 +436,13 @@ int otg_unitalign_check(otg_ctx* ctx, const char* who, uint32_t n_seqs, const ui
                         const uint32_t* unit_len, uint32_t n_units, const uint32_t* task_seq, const uint32_t* task_unit, uint32_t n_tasks);
 int otg_unitalign_upload(otg_ctx* ctx, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off, const uint32_t* unit_len, uint32_t n_units,
                          const uint32_t* task_seq, const uint32_t* task_unit, uint32_t n_tasks, OtgUnitSource* units, const uint32_t** d_task_seq,
-                         const uint32_t** d_task_unit);
+                         const uint32_t** d_task_unit, int slot = SLOT_UNITALIGN_UNITS);
+// tract.hip: the launch part of the tract mode on device-resident alleles and units, arguments as otg_unitalign_resident.  The local pass,
+// then otg_unitalign_resident on the tracts as sub-rows of the same arena, then the merge into SLOT_TRACT_OUT; params has been checked.
+int otg_tract_resident(otg_ctx* ctx, const char* who, const OtgRows& rows, const OtgUnitSource& units, const uint32_t* d_task_seq,
+                       const uint32_t* d_task_unit, uint32_t n_tasks, const otg_tract_params& params, otg_tract* out);
+// the params of a tract entry: NULL gives the defaults, scores out of range are OTG_ERR_ARG
+int otg_tract_args(otg_ctx* ctx, const char* who, const otg_tract_params* params, otg_tract_params* out);
 // unitparse.hip: the refusals of a caller's unit sets and task lists (host arrays), and the launch part of the joint unit parse on
 // device-resident alleles (the arena extends 15 bytes past every row).  The units, sets and task lists are host arrays and are uploaded here;
 // h_len = the allele lengths on the host, NULL: they are read back from rows.len.

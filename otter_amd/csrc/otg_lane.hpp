@@ -1,4 +1,4 @@
-// otg_lane.hpp — the lane exchanges of the kernels that keep a DP row across the lanes of a wave (unitalign.hip, unitparse.hip), for keys of
+// otg_lane.hpp — the lane exchanges of the kernels that keep a DP row across the lanes of a wave (unitalign.hip, unitparse.hip, tract.hip), for keys of
 // 32 and 64 bits: a value from any lane (ds_bpermute), from D lanes below inside a row of 16 (DPP), one register of a lane's few by a
 // runtime index, and the step of the segmented prefix minimum built on them.  Device code only.
 #pragma once
@@ -25,14 +25,14 @@ template <typename K, int R> __device__ __forceinline__ K pick(const K (&v)[R], 
   for (int q = 1; q < R; ++q) x = r == (uint32_t)q ? v[q] : x;
   return x;
 }
-// one step of the segmented prefix minimum over lanes, distance D < S: pos = the lane's place inside its segment of at most S lanes
-template <typename K, int S, int D> __device__ __forceinline__ K scan_step(K x, uint32_t lane, uint32_t pos)
+// one step of the segmented prefix minimum (MAX: maximum) over lanes, distance D < S: pos = the lane's place inside its segment of at most S lanes
+template <typename K, int S, int D, bool MAX = false> __device__ __forceinline__ K scan_step(K x, uint32_t lane, uint32_t pos)
 {
   if constexpr (D < S) {
     K from;
     if constexpr (S <= 16) from = row_up<D>(x);
     else from = from_lane(x, lane - D);                            // (lane < D reads a lane of the wave that `ok` discards)
-    return otg_unitalign_core::ua_scan_take<K>(x, from, pos >= (uint32_t)D);
+    return otg_unitalign_core::ua_scan_take<K, MAX>(x, from, pos >= (uint32_t)D);
   } else {
     return x;
   }

@@ -88,8 +88,9 @@ template <typename K> OTG_UA_HD K ua_cell(K diag, K up, bool match)
 // The skipped-unit-base step, H[j] = min over k of T[k] + ((j - k) mod p) W, in one prefix scan.  With the bias c(j) = (p - 1 - j) W,
 // H1[j] = min over k <= j of T[k] + (j - k) W = (min over k <= j of T[k] + c(k)) - c(j): a plain prefix minimum of the biased cells.
 template <typename K> OTG_UA_HD K ua_bias(uint32_t j, uint32_t p) { return (K)(p - 1u - j) * ua_w<K>(); }
-// one step of that prefix minimum: `from` is the value `d` positions below, `ok` says it exists inside the segment
-template <typename K> OTG_UA_HD K ua_scan_take(K x, K from, bool ok) { return ok && from < x ? from : x; }
+// one step of that prefix minimum: `from` is the value `d` positions below, `ok` says it exists inside the segment (MAX: of the prefix
+// maximum of the tract mode, otg_tract_core.hpp)
+template <typename K, bool MAX = false> OTG_UA_HD K ua_scan_take(K x, K from, bool ok) { return ok && (MAX ? from > x : from < x) ? from : x; }
 // m = the scanned biased cell of position j, last = that of position p - 1 (its bias is 0, so it is H1[p - 1]): the paths that wrap
 // from p - 1 to 0 and go on to j cost (j + 1) W more
 template <typename K> OTG_UA_HD K ua_close(K m, K last, uint32_t j, uint32_t p)

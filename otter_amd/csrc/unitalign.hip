@@ -19,6 +19,7 @@
 #include "otg_lane.hpp"
 #include "otg_scan.hpp"
 #include "otg_unitalign_core.hpp"
+#include "otg_unit_tasks.hpp"
 #include <algorithm>
 #include <cstdlib>
 
@@ -30,21 +31,7 @@ namespace {
 using namespace otg_unitalign_core;
 using namespace otg_lane;
 
-constexpr uint32_t UA_T = 256;                                   // threads of every workgroup here
-constexpr uint32_t UA_NBINS = 2u * UA_CLASSES * UA_BUCKETS;      // (tier, class, bucket)
-constexpr uint32_t UA_NO_BIN = 0xffffffffu;
-
-struct UaIn {
-  OtgRows rows;
-  OtgUnitSource u;
-  const uint32_t* task_seq; const uint32_t* task_unit;
-  __device__ __forceinline__ uint32_t seq(uint32_t t) const { return task_seq ? task_seq[t] : t; }
-  __device__ __forceinline__ uint32_t unit(uint32_t t) const { return task_unit ? task_unit[t] : t; }
-  __device__ __forceinline__ uint32_t unit_len(uint32_t k) const { return u.d_unit_off ? u.d_unit_len[k] : u.d_motifs[k].period; }
-  __device__ __forceinline__ const uint8_t* unit_at(uint32_t k) const { return u.d_units + (u.d_unit_off ? u.d_unit_off[k] : (uint64_t)k * u.unit_stride); }
-};
-
-// ---- binning
+// ---- binning (the scatter is otg_unit_tasks.hpp's)
 __global__ __launch_bounds__(UA_T) void ua_classify(UaIn in, uint32_t n, bool wide, bool seg64, uint32_t* __restrict__ task_bin, uint32_t* __restrict__ hist,
                                                    otg_unitalign* __restrict__ out)
 {
@@ -63,16 +50,6 @@ __global__ __launch_bounds__(UA_T) void ua_classify(UaIn in, uint32_t n, bool wi
   const uint32_t bin = (tier * UA_CLASSES + ua_class(p, seg64)) * UA_BUCKETS + (UA_BUCKETS - 1u - ua_bucket(L));      // the longest first
   task_bin[t] = bin;
   atomicAdd(&hist[bin], 1u);
-}
-
-__global__ __launch_bounds__(UA_T) void ua_scatter(uint32_t n, const uint32_t* __restrict__ task_bin, const uint32_t* __restrict__ start,
-                                                  uint32_t* __restrict__ cursor, uint32_t* __restrict__ order)
-{
-  const uint32_t t = blockIdx.x * UA_T + threadIdx.x;
-  if (t >= n) return;
-  const uint32_t bin = task_bin[t];
-  if (bin == UA_NO_BIN) return;
-  order[start[bin] + atomicAdd(&cursor[bin], 1u)] = t;            // start[bin] + count(bin) = start[bin + 1] <= n
 }
 
 // ---- the alignment: tasks order[first .. first + count), 64 / S to a wave
@@ -196,11 +173,6 @@ void ua_launch_class(otg_ctx* ctx, uint32_t c, const UaIn& in, const uint32_t* d
   }
 }
 
-bool ua_env(const char* name)
-{
-  const char* e = getenv(name);
-  return e && *e && strcmp(e, "0") != 0;
-}
 bool ua_force_wide() { static const bool on = ua_env("OTG_UNITALIGN_WIDE"); return on; }
 bool ua_force_seg64() { static const bool on = ua_env("OTG_UNITALIGN_SEG64"); return on; }
 
@@ -267,11 +239,11 @@ int otg_unitalign_check(otg_ctx* ctx, const char* who, uint32_t n_seqs, const ui
 
 int otg_unitalign_upload(otg_ctx* ctx, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off, const uint32_t* unit_len, uint32_t n_units,
                          const uint32_t* task_seq, const uint32_t* task_unit, uint32_t n_tasks, OtgUnitSource* units, const uint32_t** d_task_seq,
-                         const uint32_t** d_task_unit)
+                         const uint32_t** d_task_unit, int slot)
 {
   // unit_off (u64, n_units) | unit_len (u32, n_units) | task_seq, task_unit (u32, n_tasks) | the unit bytes
   const size_t meta = (size_t)n_units * 12 + (size_t)n_tasks * 8;
-  uint8_t* d = (uint8_t*)otg_slot(ctx, SLOT_UNITALIGN_UNITS, meta + unit_bytes + 16);
+  uint8_t* d = (uint8_t*)otg_slot(ctx, slot, meta + unit_bytes + 16);
   if (!d) return OTG_ERR_HIP;
   uint64_t* d_uoff = (uint64_t*)d;
   uint32_t* d_ulen = (uint32_t*)(d + (size_t)n_units * 8);
