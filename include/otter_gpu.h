@@ -1353,6 +1353,106 @@ typedef struct otg_tracts_job {
 int otg_tracts_files(const otg_tracts_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
 
 /* ---------------------------------------------------------------------------------------------
+ * Locus mode: the joint unit-set parse inside a flanked allele.  The joint parse above is global in the allele, so flank bases count as edits
+ * and are attributed to segments; the tract mode above trims the flanks, but for one unit.  Here a local wraparound alignment over the whole
+ * unit set locates the repeat, and the joint parse is then applied to exactly that stretch.  The reference has no counterpart; this is the
+ * definition (all integers).  A task is an allele s of length L and an ordered unit set u_0 .. u_{K-1}; the refusals are
+ * exactly those of the joint parse (step 5 there).  Codes, folding and matching are those of the unit alignment.  The scores are an
+ * otg_tract_params with the same ranges and the same defaults (2, 7, 7, 24).
+ *   1. Cell (i, k, j) is "i bases of s consumed, the next unit base is u_k[j]".  Its value is the pair (score, begin), ordered by the larger
+ *      score, then the LARGER begin.
+ *   2. C[0][k][j] = (0, 0).
+ *   3. Row i + 1 starts every position at the fresh start (0, i + 1) and takes the maximum of
+ *        the diagonal step             C[i][k][j] -> C[i+1][k][(j+1) % p_k] with + match when c_s[i] == c_u[j] && c_s[i] < 4, else - mismatch;
+ *        a base of s outside the unit  C[i][k][j] -> C[i+1][k][j] with - indel;
+ *        a skipped unit base           C[i+1][k][j] -> C[i+1][k][(j+1) % p_k] with - indel;
+ *        a switch, only at phase 0     C[i+1][k][0] -> C[i+1][k'][0] for k' != k, at no score;
+ *      the last two taken together to their fixed point within the row.  A candidate whose score is not positive is dropped.  Steps keep
+ *      begin.  A switch is free here for the reason it costs no edit in the joint parse; the second pass orders the switches, the local
+ *      pass only finds where the repeat lies.
+ *   4. The best cell over all rows and positions: the largest score, then the SMALLEST i (= end), then the larger begin, then the smallest
+ *      (k, j) in set order.
+ *   5. score = 0 or score < min_score: everything but score is 0, no segments, flags = OTG_LOCUS_NONE.
+ *   6. Otherwise (edits, switches, unit_bases, n_segments) and the segments are, by definition, the joint parse of the bytes s[begin, end)
+ *      against the same set, the segments' begin and end shifted by the tract's begin: they are allele positions and tile [begin, end).
+ *   7. L > OTG_LOCUS_MAX_LEN (= OTG_UNITPARSE_MAX_LEN, the smaller cap of the two passes): zeros and OTG_LOCUS_TOO_LONG; the batch does not
+ *      fail.  L = 0: OTG_LOCUS_NONE.
+ * It follows that K = 1 gives the (score, begin, end, edits, unit_bases) of otg_tract_batch for that unit, that N bytes in front of s move
+ * begin, end and the segment positions by their count and change nothing else, that N bytes behind s change nothing, that letter case
+ * changes nothing, and that score <= match * (end - begin).  There is one tract per allele: a spacer between two repeats that is cheaper
+ * than a restart lies inside it.
+ *   otg_locus_batch           alleles, units, sets and tasks as in otg_unitparse_batch; params == NULL: the defaults.  out: n_tasks records;
+ *                             seg_off: n_tasks + 1 offsets into the segments, which stay in HBM; *n_segments = seg_off[n_tasks].  Every
+ *                             output is nullable.  Refusals as otg_unitparse_batch, and OTG_ERR_ARG for scores out of range;
+ *   otg_locus_collect         copies the segments of the latest locus call on the context to segs[0 .. total), as otg_unitparse_collect;
+ *   otg_locus_device_results  device pointers of the latest results on this context (n records, n + 1 offsets, total segments), valid until
+ *                             the next locus call or unit parse on the context or otg_destroy; every output is nullable;
+ *   otg_locus_last_ms         HIP-event times (ms) of the latest call: *ms = both passes, *local_ms (nullable) = the local pass alone;
+ *   otg_locus_last_tiers      how many tasks of the latest call the local pass ran on the 32-bit key and on the 64-bit key (tasks that were
+ *                             not aligned, L = 0 or over the cap, count for neither); every output is nullable;
+ *   otg_locus_cohort          rows of the cohort arena in place; arguments, preconditions and refusals as otg_unitparse_cohort, plus params;
+ *   otg_locus_emit            per allele a = records[r].first_allele + i the row region \t i \t seq_len[a] \t units \t begin \t end \t score \t
+ *                             edits \t switches \t unit_bases \t identity \t counts \t structure \n, arguments as otg_unitparse_emit with
+ *                             loci[a] the allele's record: identity "%.4f" of 1 - edits / max(end - begin, unit_bases), 0.0000 when a flag
+ *                             is set; counts and structure as otg_unitparse_emit formats them; an allele without a tract gives zeros (the
+ *                             score stays) and "." for the structure, one without a set zeros and "." for units, counts and structure.  Buffer protocol of
+ *                             otg_emit_alleles.
+ * A locus call runs the joint parse as its second pass, on sub-rows of the same arena, so it counts as a unit parse on the context: afterwards
+ * otg_unitparse_device_results and otg_unitparse_collect give, per task, the summary of the sub-row s[begin, end) (an empty row for a task
+ * without a tract: zeros) and the segments already in allele coordinates; otg_unitparse_last_ms gives the second pass.  The local pass has
+ * the lane layout of the joint parse (every unit at a lane boundary, 4 .. 64 lanes per task) and the key of the tract mode: score * 2^16 +
+ * begin in 32 bits while the allele is no longer than the bound otg_locus_core.hpp derives from the call's scores and the largest unit of
+ * the set, 32 / 32 in 64 bits above.  OTG_LOCUS_WIDE=1 sends every task through the 64-bit tier, OTG_LOCUS_SEG64=1 gives every task a
+ * whole wave (both read once per process).
+ * ------------------------------------------------------------------------------------------- */
+#define OTG_LOCUS_MAX_LEN  OTG_UNITPARSE_MAX_LEN
+#define OTG_LOCUS_TOO_LONG 1u   /* otg_locus.flags */
+#define OTG_LOCUS_NONE     2u   /* no tract: score 0 or below min_score                             */
+typedef struct otg_locus {
+  uint32_t score;                /* of the best local alignment, also when there is no tract         */
+  uint32_t begin;                /* the tract is s[begin, end)                                       */
+  uint32_t end;
+  uint32_t edits;                /* the joint parse of the tract                                     */
+  uint32_t switches;
+  uint32_t unit_bases;
+  uint32_t n_segments;           /* switches + 1; 0 without a tract                                  */
+  uint32_t flags;                /* OTG_LOCUS_TOO_LONG / _NONE                                       */
+} otg_locus;
+int otg_locus_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_bytes, const uint64_t* seq_off, const uint32_t* seq_len,
+                    uint32_t n_seqs, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off, const uint32_t* unit_len,
+                    uint32_t n_units, const uint64_t* set_first, uint32_t n_sets, const uint32_t* task_seq, const uint32_t* task_set,
+                    uint32_t n_tasks, const otg_tract_params* params, otg_locus* out, uint64_t* seg_off, uint64_t* n_segments);
+int otg_locus_collect(otg_ctx* ctx, otg_unitparse_seg* segs, uint64_t capacity);
+int otg_locus_device_results(otg_ctx* ctx, uint32_t* n_tasks, const otg_locus** records, const uint64_t** seg_off,
+                             const otg_unitparse_seg** segs, uint64_t* total);
+int otg_locus_last_ms(otg_ctx* ctx, double* ms, double* local_ms);
+int otg_locus_last_tiers(otg_ctx* ctx, uint32_t* narrow, uint32_t* wide);
+int otg_locus_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off,
+                     const uint32_t* unit_len, uint32_t n_units, const uint64_t* set_first, uint32_t n_sets, const uint32_t* task_seq,
+                     const uint32_t* task_set, uint32_t n_tasks, const otg_tract_params* params, otg_locus* out, uint64_t* seg_off,
+                     uint64_t* n_segments);
+int otg_locus_emit(const otg_vcf_record* records, uint32_t n_records, const char* region_arena, const uint32_t* seq_len,
+                   const uint32_t* allele_set, const uint64_t* set_first, const uint8_t* unit_arena, const uint64_t* unit_off,
+                   const uint32_t* unit_len, const otg_locus* loci, const uint64_t* seg_off, const otg_unitparse_seg* segs, char* out,
+                   uint64_t out_capacity, uint64_t* out_len);
+/* The locus mode over the alleles of a VCF against a tandem-repeat catalogue, in file order, built as otg_unitparse_files is: the same
+ * catalogue lookup, one otg_locus_emit row per allele, a refused unit set is OTG_ERR_ARG with the region in the message.  Out-of-range
+ * scores are OTG_ERR_ARG with the message the tool prints.  stats as otg_vcf2mat_files. */
+typedef struct otg_loci_job {
+  const char* vcf_path;          /* positional <VCF[.GZ]>                                            */
+  const char* bed_path;          /* -b: required, the catalogue                                      */
+  uint32_t    match;             /* --scores match,mismatch,indel (the tool's default: 2,7,7)        */
+  uint32_t    mismatch;
+  uint32_t    indel;
+  uint32_t    min_score;         /* --min-score: 0..2^24 (the tool's default: 24)                    */
+  int32_t     threads;           /* -t: host threads of the emit                                     */
+  int32_t     device;            /* HIP device ordinal                                               */
+  uint32_t    batch_alleles;     /* alleles per batch, 0 = 65536                                     */
+  uint32_t    reserved;
+} otg_loci_job;
+int otg_loci_files(const otg_loci_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
+
+/* ---------------------------------------------------------------------------------------------
  * Indexed allele BAMs from the product's own SAM text.  Every writer above emits SAM text and every reader wants a
  * coordinate-sorted BAM with its `.bai`; the reference's workflow goes through `samtools view -bh | samtools sort`, `samtools index` and
  * `samtools merge -pco` in between.  Host code (zlib + threads), no device work.

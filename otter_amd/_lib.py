@@ -36,6 +36,7 @@ EXPORTS = [
     "otg_unitparse_files",
     "otg_tract_params_default", "otg_tract_batch", "otg_tract_motifs", "otg_tract_cohort", "otg_tract_device_results", "otg_tract_last_ms", "otg_tract_emit",
     "otg_tracts_files",
+    "otg_locus_batch", "otg_locus_collect", "otg_locus_device_results", "otg_locus_last_ms", "otg_locus_last_tiers", "otg_locus_cohort", "otg_locus_emit", "otg_loci_files",
 ]
 
 _lib = None
@@ -316,7 +317,7 @@ class Context:
             self._h, *rows, C.c_uint32(max_period), C.c_uint32(min_copies), C.c_uint32(min_span), sums, seg_off, total), "otg_repeat_batch")
 
     def _seg_results(self, kind, n, device_tensor, call, who):
-        """the results of an operator with segments ("repeat", "unitparse"): call(sums, seg_off, total) is its entry `who` on the C arguments of
+        """the results of an operator with segments ("repeat", "unitparse", "locus"): call(sums, seg_off, total) is its entry `who` on the C arguments of
         the three; -> (sums [n], seg_off [n + 1], segs [total]) as numpy arrays of its record types, or as int32 / int64 device tensors"""
         sum_dt, seg_dt = _SEG_TYPES[kind]
         sum_w, seg_w = sum_dt.itemsize // 4, seg_dt.itemsize // 4
@@ -450,6 +451,28 @@ class Context:
     def unitparse_last_ms(self):
         """(forward ms, traceback ms) of the latest unit parse on this context (HIP events)."""
         return self._last_ms("otg_unitparse_last_ms", 2)
+
+    def locus_batch(self, arena, seq_off, seq_len, unit_sets, task_seq, task_set, match=2, mismatch=7, indel=7, min_score=24, device_tensor=False):
+        """otg_locus_batch (and otg_locus_collect): the repeat of the unit set unit_sets[task_set[t]] inside allele task_seq[t] (a local wraparound
+        alignment over the set; include/otter_gpu.h states the rule) and the joint parse of exactly that stretch -> (records [n_tasks] of
+        abi.locus_dt, seg_off [n_tasks + 1] uint64, segs [total] of abi.unitparse_seg_dt in allele positions) as numpy arrays; or with
+        device_tensor=True as torch tensors on this context's device that wrap the results in HBM without a copy (int32 [n, 8], int64 [n + 1],
+        int32 [total, 6]; valid until the next locus call or unit parse on this context).  The call counts as a unit parse on the context."""
+        rows, ln = _rows(arena, seq_off, seq_len)
+        sets, ts, tq = _pack_unit_sets(unit_sets, task_seq, task_set)
+        q = abi.TractParams(match, mismatch, indel, min_score)
+        return self._seg_results("locus", len(ts), device_tensor, lambda recs, seg_off, total: self._L.otg_locus_batch(
+            self._h, *rows, *sets, abi.ptr(ts), abi.ptr(tq), C.c_uint32(len(ts)), C.byref(q), recs, seg_off, total), "otg_locus_batch")
+
+    def locus_last_ms(self):
+        """(both passes ms, the local pass alone ms) of the latest locus call on this context (HIP events)."""
+        return self._last_ms("otg_locus_last_ms", 2)
+
+    def locus_last_tiers(self):
+        """(tasks on the 32-bit key, tasks on the 64-bit key) of the local pass of the latest locus call on this context."""
+        a, b = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._L.otg_locus_last_tiers(self._h, C.byref(a), C.byref(b)), "otg_locus_last_tiers")
+        return a.value, b.value
 
     def affine_align_batch(self, arena, tasks, x=4, o=6, e=2, want_cells=False):
         n = len(tasks)
@@ -864,6 +887,19 @@ class Context:
         sets, ts, tq = _pack_unit_sets(unit_sets, task_seq, task_set)
         return self._seg_results("unitparse", len(ts), device_tensor, lambda sums, seg_off, total: self._L.otg_unitparse_cohort(
             self._h, C.c_uint32(row_begin), C.c_uint32(n), *sets, abi.ptr(ts), abi.ptr(tq), C.c_uint32(len(ts)), sums, seg_off, total), "otg_unitparse_cohort")
+
+    def cohort_loci(self, unit_sets, task_seq, task_set, row_begin=0, n=None, match=2, mismatch=7, indel=7, min_score=24, device_tensor=False):
+        """otg_locus_cohort: the locus mode over rows [row_begin, row_begin + n) of the row list (n=None: to the end), the alleles read in the
+        cohort arena in place -> (records, seg_off, segs) as locus_batch returns them; task_seq counts from row_begin."""
+        if n is None:
+            total = C.c_uint32(0)
+            self._check(self._L.otg_kmer_cohort_rows(self._h, C.byref(total), None, None, None), "otg_kmer_cohort_rows")
+            n = max(0, total.value - int(row_begin))
+        n = int(n)
+        sets, ts, tq = _pack_unit_sets(unit_sets, task_seq, task_set)
+        q = abi.TractParams(match, mismatch, indel, min_score)
+        return self._seg_results("locus", len(ts), device_tensor, lambda recs, seg_off, total: self._L.otg_locus_cohort(
+            self._h, C.c_uint32(row_begin), C.c_uint32(n), *sets, abi.ptr(ts), abi.ptr(tq), C.c_uint32(len(ts)), C.byref(q), recs, seg_off, total), "otg_locus_cohort")
 
     def cohort_end(self):
         self._check(self._L.otg_cohort_end(self._h), "otg_cohort_end")
@@ -1685,7 +1721,8 @@ def repeats_files(vcf, bed, max_period=256, min_copies=2, min_span=12, threads=1
     return _run_files_job("otg_repeats_files", job, abi.RepeatsJob)
 
 
-_SEG_TYPES = {"repeat": (abi.repeat_sum_dt, abi.repeat_seg_dt), "unitparse": (abi.unitparse_sum_dt, abi.unitparse_seg_dt)}
+_SEG_TYPES = {"repeat": (abi.repeat_sum_dt, abi.repeat_seg_dt), "unitparse": (abi.unitparse_sum_dt, abi.unitparse_seg_dt),
+              "locus": (abi.locus_dt, abi.unitparse_seg_dt)}
 
 
 def _rows(arena, seq_off, seq_len):
@@ -1856,3 +1893,42 @@ def tracts_files(vcf, bed, max_period=256, slack=50, match=2, mismatch=7, indel=
     job.max_period = max_period; job.slack = slack; job.match = match; job.mismatch = mismatch; job.indel = indel; job.min_score = min_score
     job.threads = threads; job.device = device; job.batch_alleles = batch_alleles
     return _run_files_job("otg_tracts_files", job, abi.TractsJob)
+
+
+def locus_emit(records, regions, seq_len, allele_sets, unit_sets, loci, seg_off, segs):
+    """otg_locus_emit: the rows of otter_loci for the records (vcf_record_dt), arguments as unitparse_emit with loci[a] (locus_dt) the record of
+    allele a and its segments in allele positions -> text bytes."""
+    L = load()
+    records = np.ascontiguousarray(records, dtype=abi.vcf_record_dt)
+    seq_len = np.ascontiguousarray(seq_len, dtype=np.uint32)
+    aset = np.ascontiguousarray([abi.UNITPARSE_NO_SET if q is None else q for q in allele_sets] + [abi.UNITPARSE_NO_SET], dtype=np.uint32)
+    sets, _, _ = _pack_unit_sets(unit_sets, [], [])
+    loci = np.ascontiguousarray(loci, dtype=abi.locus_dt)
+    seg_off = np.ascontiguousarray(seg_off, dtype=np.uint64)
+    segs = np.ascontiguousarray(segs, dtype=abi.unitparse_seg_dt)
+    if loci.size == 0:
+        loci = np.zeros(1, dtype=abi.locus_dt)
+    if segs.size == 0:
+        segs = np.zeros(1, dtype=abi.unitparse_seg_dt)
+    reg = np.frombuffer(regions + b"\0", dtype=np.uint8)
+    need = C.c_uint64(0)
+    args = lambda out, cap: (abi.ptr(records), C.c_uint32(len(records)), abi.ptr(reg), abi.ptr(seq_len), abi.ptr(aset), sets[5], sets[0], sets[2], sets[3],
+                             abi.ptr(loci), abi.ptr(seg_off), abi.ptr(segs), out, C.c_uint64(cap), C.byref(need))
+    rc = L.otg_locus_emit(*args(None, 0))
+    if rc not in (0, abi.OTG_ERR_CAPACITY):
+        raise OtterGpuError("otg_locus_emit failed (%d): %s" % (rc, _err(L)))
+    out = C.create_string_buffer(need.value + 1)
+    rc = L.otg_locus_emit(*args(out, need.value))
+    if rc != 0:
+        raise OtterGpuError("otg_locus_emit failed (%d): %s" % (rc, _err(L)))
+    return out.raw[:need.value]
+
+
+def loci_files(vcf, bed, match=2, mismatch=7, indel=7, min_score=24, threads=1, device=0, batch_alleles=0):
+    """otg_loci_files: the joint parse of the repeat inside every allele of a VCF (plain, gzip or BGZF) against the unit set its region has in a
+    tandem-repeat catalogue, as text.  Returns (text bytes, stats dict)."""
+    job = abi.LociJob()
+    job.vcf_path = vcf.encode(); job.bed_path = bed.encode()
+    job.match = match; job.mismatch = mismatch; job.indel = indel; job.min_score = min_score
+    job.threads = threads; job.device = device; job.batch_alleles = batch_alleles
+    return _run_files_job("otg_loci_files", job, abi.LociJob)

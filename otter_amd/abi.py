@@ -312,6 +312,21 @@ class TractsJob(C.Structure):
                 ("batch_alleles", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+# otg_locus (include/otter_gpu.h) and the bounds of the locus mode
+locus_dt = np.dtype([("score", np.uint32), ("begin", np.uint32), ("end", np.uint32), ("edits", np.uint32), ("switches", np.uint32), ("unit_bases", np.uint32),
+                     ("n_segments", np.uint32), ("flags", np.uint32)])
+assert locus_dt.itemsize == 32
+LOCUS_MAX_LEN = UNITPARSE_MAX_LEN
+LOCUS_TOO_LONG = 1
+LOCUS_NONE = 2
+
+
+class LociJob(C.Structure):
+    """otg_loci_job (include/otter_gpu.h)."""
+    _fields_ = [("vcf_path", C.c_char_p), ("bed_path", C.c_char_p), ("match", C.c_uint32), ("mismatch", C.c_uint32), ("indel", C.c_uint32),
+                ("min_score", C.c_uint32), ("threads", C.c_int32), ("device", C.c_int32), ("batch_alleles", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class JobStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_regions", "n_regions_ok", "n_regions_skipped", "n_reads", "n_alleles", "input_bytes", "output_bytes")] + \
                [("n_devices", C.c_uint32), ("reserved", C.c_uint32)] + [(k, C.c_double) for k in ("ms_total", "ms_ingest", "ms_hot_path", "ms_emit")]

@@ -603,6 +603,22 @@ int otg_unitparse_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, const uin
                                 n_tasks, sums, seg_off, n_segments);
 }
 
+int otg_locus_cohort(otg_ctx* ctx, uint32_t row_begin, uint32_t n, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off,
+                     const uint32_t* unit_len, uint32_t n_units, const uint64_t* set_first, uint32_t n_sets, const uint32_t* task_seq,
+                     const uint32_t* task_set, uint32_t n_tasks, const otg_tract_params* params, otg_locus* out, uint64_t* seg_off, uint64_t* n_segments)
+{
+  Cohort* c = nullptr;
+  OtgRows rows;
+  otg_tract_params q;
+  if (int rc = cohort_clustered(ctx, "otg_locus_cohort", &c)) return rc;
+  if (int rc = otg_tract_args(ctx, "otg_locus_cohort", params, &q)) return rc;
+  if (int rc = cohort_rows(ctx, *c, "otg_locus_cohort", row_begin, n, &rows)) return rc;
+  if (int rc = otg_unitparse_check(ctx, "otg_locus_cohort", n, unit_arena, unit_bytes, unit_off, unit_len, n_units, set_first, n_sets, task_seq, task_set, n_tasks))
+    return rc;
+  return otg_locus_resident(ctx, "otg_locus_cohort", rows, nullptr, n, unit_arena, unit_bytes, unit_off, unit_len, n_units, set_first, n_sets, task_seq, task_set, n_tasks,
+                            q, out, seg_off, n_segments);
+}
+
 int otg_cohort_end(otg_ctx* ctx)
 {
   if (!ctx) return otg_fail(nullptr, OTG_ERR_NO_DEVICE, "otg_cohort_end: no context");

@@ -18,6 +18,7 @@
 #include "otg_motif.hpp"
 #include "otg_repeat.hpp"
 #include "otg_unitalign.hpp"
+#include "otg_locus.hpp"
 #include "otg_tract.hpp"
 #include "otg_unitparse.hpp"
 #include "otg_unitparse_core.hpp"
@@ -1287,15 +1288,22 @@ int otg_copies_files(const otg_copies_job* job, otg_write_fn write, void* user, 
                                             write, user, stats, otg_unitalign_batch, otg_unitalign_motifs, otg_unitalign_rows);
 }
 
+// the refusals of --scores and --min-score that otter_tracts and otter_loci share, with the message the tools print
+static int tract_cli_args(const otg_tract_params& q)
+{
+  if (q.match < 1 || q.match > 16 || q.mismatch < 1 || q.mismatch > 64 || q.indel < 1 || q.indel > 64)
+    return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--scores' (%u,%u,%u). Needs to be 1 <= match <= 16, 1 <= mismatch <= 64, 1 <= indel <= 64.", q.match, q.mismatch,
+                    q.indel);
+  if (q.min_score > (1u << 24)) return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--min-score' (%u). Needs to be 0 <= x <= %u.", q.min_score, 1u << 24);
+  return OTG_OK;
+}
+
 // The tracts of a VCF's alleles against a tandem-repeat catalogue: otg_tract_batch and otg_tract_motifs on catalogue_units_job, with the scores.
 int otg_tracts_files(const otg_tracts_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
 {
   if (!job || !write || !job->vcf_path || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "otg_tracts_files: NULL job, writer, VCF or BED path");
   const otg_tract_params q{job->match, job->mismatch, job->indel, job->min_score};
-  if (q.match < 1 || q.match > 16 || q.mismatch < 1 || q.mismatch > 64 || q.indel < 1 || q.indel > 64)
-    return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--scores' (%u,%u,%u). Needs to be 1 <= match <= 16, 1 <= mismatch <= 64, 1 <= indel <= 64.", q.match, q.mismatch,
-                    q.indel);
-  if (q.min_score > (1u << 24)) return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--min-score' (%u). Needs to be 0 <= x <= %u.", q.min_score, 1u << 24);
+  if (int rc = tract_cli_args(q)) return rc;
   return catalogue_units_job<otg_tract>(
       "otg_tracts_files", job->vcf_path, job->bed_path, job->max_period, job->slack, job->device, job->batch_alleles, job->threads, write, user, stats,
       [&](otg_ctx* ctx, const uint8_t* seqs, uint64_t au, const uint64_t* off, const uint32_t* len, uint32_t na, const uint8_t* ua, uint64_t ub, const uint64_t* uoff,
@@ -1305,20 +1313,24 @@ int otg_tracts_files(const otg_tracts_job* job, otg_write_fn write, void* user, 
       [&](otg_ctx* ctx, otg_tract* out) { return otg_tract_motifs(ctx, &q, out); }, otg_tract_rows);
 }
 
-// The joint parse of a VCF's alleles against the unit sets of a tandem-repeat catalogue, on vcf_allele_job as otg_copies_files: one task per
-// allele of a catalogue region with units (otg_unitparse_batch, only the sets the batch uses are uploaded); the others get the row without units.
-int otg_unitparse_files(const otg_unitparse_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
+// The rows of a VCF's alleles against the unit sets of a tandem-repeat catalogue, on vcf_allele_job as otg_copies_files: what
+// otg_unitparse_files and otg_loci_files share.  One task per allele of a catalogue region with units (batch_fn, only the sets the batch
+// uses are uploaded; collect_fn brings its segments); the others get the row without units.  Rec = the operator's record (zero: an allele
+// that was not a task); rows_fn = its row text.
+extern "C++" {
+template <typename Rec, typename BatchFn, typename CollectFn, typename RowsFn>
+int unit_sets_job(const char* who, const char* vcf_path, const char* bed_path, int32_t device, uint32_t batch_alleles, int32_t threads, otg_write_fn write, void* user,
+                  otg_job_stats* stats, BatchFn batch_fn, CollectFn collect_fn, RowsFn rows_fn)
 {
-  if (!job || !write || !job->vcf_path || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "otg_unitparse_files: NULL job, writer, VCF or BED path");
   UnitCatalogue cat;
-  if (int rc = cat.load("otg_unitparse_files", job->bed_path)) return rc;
+  if (int rc = cat.load(who, bed_path)) return rc;
   // per batch: one set per record with units, one task per allele of such a record; the results per allele, in file order
   std::vector<uint64_t> set_first, uoff, seg_off, t_seg_off;
   std::vector<uint32_t> ulen, allele_set, tseq, tset;
   std::vector<uint8_t> units;
-  std::vector<otg_unitparse_sum> sums, t_sums;
+  std::vector<Rec> sums, t_sums;
   std::vector<otg_unitparse_seg> segs;
-  return vcf_allele_job("otg_unitparse_files", job->vcf_path, job->bed_path, job->device, job->batch_alleles ? job->batch_alleles : 65536, job->threads, write, user, stats,
+  return vcf_allele_job(who, vcf_path, bed_path, device, batch_alleles ? batch_alleles : 65536, threads, write, user, stats,
     [&](otg_ctx* ctx, const VcfBatch& B) {
       set_first.assign(1, 0); uoff.clear(); ulen.clear(); units.clear(); tseq.clear(); tset.clear();
       allele_set.assign(B.na, OTG_UNITPARSE_NO_SET);
@@ -1348,15 +1360,15 @@ int otg_unitparse_files(const otg_unitparse_job* job, otg_write_fn write, void* 
       t_sums.resize(nt); t_seg_off.assign((size_t)nt + 1, 0);
       uint64_t total = 0;
       if (nt) {
-        if (int rc = otg_unitparse_batch(ctx, B.seqs.data(), B.au, B.off.data(), B.len.data(), B.na, units.data(), units.size() - 1, uoff.data(), ulen.data(),
-                                         (uint32_t)ulen.size() - 1u, set_first.data(), (uint32_t)set_first.size() - 1u, tseq.data(), tset.data(), nt, t_sums.data(),
-                                         t_seg_off.data(), &total)) return rc;
+        if (int rc = batch_fn(ctx, B.seqs.data(), B.au, B.off.data(), B.len.data(), B.na, units.data(), units.size() - 1, uoff.data(), ulen.data(),
+                              (uint32_t)ulen.size() - 1u, set_first.data(), (uint32_t)set_first.size() - 1u, tseq.data(), tset.data(), nt, t_sums.data(),
+                              t_seg_off.data(), &total)) return rc;
       }
       segs.resize(total + 1);
       if (total)
-        if (int rc = otg_unitparse_collect(ctx, segs.data(), total)) return rc;
+        if (int rc = collect_fn(ctx, segs.data(), total)) return rc;
       // the tasks are the alleles with units, in allele order: their segments lie in that order too
-      sums.assign(B.na, otg_unitparse_sum{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}); seg_off.assign((size_t)B.na + 1, 0);
+      sums.assign(B.na, Rec{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}); seg_off.assign((size_t)B.na + 1, 0);
       uint32_t cur = 0;
       for (uint32_t a = 0; a < B.na; ++a) {
         seg_off[a] = t_seg_off[cur];
@@ -1366,9 +1378,32 @@ int otg_unitparse_files(const otg_unitparse_job* job, otg_write_fn write, void* 
       return (int)OTG_OK;
     },
     [&](std::string& o, const VcfBatch& B, uint32_t r0, uint32_t nr) {
-      otg_unitparse_rows(o, B.rec.data() + r0, nr, B.regions.data(), B.len.data(), allele_set.data(), set_first.data(), units.data(), uoff.data(), ulen.data(),
-                         sums.data(), seg_off.data(), segs.data());
+      rows_fn(o, B.rec.data() + r0, nr, B.regions.data(), B.len.data(), allele_set.data(), set_first.data(), units.data(), uoff.data(), ulen.data(), sums.data(),
+              seg_off.data(), segs.data());
     });
+}
+}
+
+// The joint parse of a VCF's alleles against the unit sets of a tandem-repeat catalogue: otg_unitparse_batch on unit_sets_job.
+int otg_unitparse_files(const otg_unitparse_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
+{
+  if (!job || !write || !job->vcf_path || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "otg_unitparse_files: NULL job, writer, VCF or BED path");
+  return unit_sets_job<otg_unitparse_sum>("otg_unitparse_files", job->vcf_path, job->bed_path, job->device, job->batch_alleles, job->threads, write, user, stats,
+                                          otg_unitparse_batch, otg_unitparse_collect, otg_unitparse_rows);
+}
+
+// The locus mode over a VCF's alleles: otg_locus_batch on unit_sets_job, with the scores.
+int otg_loci_files(const otg_loci_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
+{
+  if (!job || !write || !job->vcf_path || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "otg_loci_files: NULL job, writer, VCF or BED path");
+  const otg_tract_params q{job->match, job->mismatch, job->indel, job->min_score};
+  if (int rc = tract_cli_args(q)) return rc;
+  return unit_sets_job<otg_locus>(
+      "otg_loci_files", job->vcf_path, job->bed_path, job->device, job->batch_alleles, job->threads, write, user, stats,
+      [&](otg_ctx* ctx, const uint8_t* seqs, uint64_t au, const uint64_t* off, const uint32_t* len, uint32_t na, const uint8_t* ua, uint64_t ub, const uint64_t* uoff,
+          const uint32_t* ulen, uint32_t nu, const uint64_t* sf, uint32_t ns, const uint32_t* ts, const uint32_t* tq, uint32_t nt, otg_locus* out, uint64_t* seg_off,
+          uint64_t* total) { return otg_locus_batch(ctx, seqs, au, off, len, na, ua, ub, uoff, ulen, nu, sf, ns, ts, tq, nt, &q, out, seg_off, total); },
+      otg_locus_collect, otg_locus_rows);
 }
 
 // ---- `otter genotype` from files to text in one call: genotype() / genotype_process() (src/genotype.cpp:69-192).  Regions in bounded

@@ -65,6 +65,8 @@ struct otg_ctx {
   double last_tract_ms = 0.0, last_tract_local_ms = 0.0;          // HIP-event times of the latest tract call: both passes, the local pass alone (otg_tract_last_ms)
   uint32_t last_tract_n = 0;                                      // the records in SLOT_TRACT_OUT (otg_tract_device_results); 0: none
   OtgSegLast last_unitparse;                                      // the latest unit parse: SLOT_UNITPARSE_RES / SLOT_UNITPARSE_SEGS, ms = forward, traceback
+  OtgSegLast last_locus;                                          // the latest locus call: SLOT_LOCUS_OUT / SLOT_UNITPARSE_SEGS, ms = both passes, the local pass; a later unit parse ends it
+  uint32_t last_locus_tiers[2] = {0u, 0u};                        // tasks the narrow / the wide tier of that call's local pass took (otg_locus_last_tiers)
   double last_kernel_ms = 0.0;                    // HIP-event time of the kernels of the latest operator-level call that reports one (otg_last_kernel_ms)
   // the latest genotype clustering with a metric (genotype_edit.hip): times of its two parts (otg_genotype_metric_last_ms), whether the edit
   // matrix was built, and where its counters lie in SLOT_GTE_CLS
@@ -158,6 +160,8 @@ enum {
   SLOT_UNITPARSE_RES, SLOT_UNITPARSE_SEGS,                          // its summaries and offsets / its segments: they stay valid for the device results
   SLOT_TRACT_SEQ, SLOT_TRACT_META, SLOT_TRACT_UNITS, SLOT_TRACT_BINS, SLOT_TRACT_ORDER, SLOT_TRACT_SUB,   // otg_tract_batch (tract.hip); SUB: the sub-rows of the second pass
   SLOT_TRACT_OUT,                                                   // its records: they stay valid for the device results
+  SLOT_LOCUS_SEQ, SLOT_LOCUS_META, SLOT_LOCUS_UNITS, SLOT_LOCUS_SUB,   // otg_locus_batch (locus.hip); SUB: the sub-rows of the second pass and the task order
+  SLOT_LOCUS_OUT,                                                   // its records and segment offsets: they stay valid for the device results
   SLOT_COUNT
 };
 
@@ -443,6 +447,16 @@ int otg_tract_resident(otg_ctx* ctx, const char* who, const OtgRows& rows, const
                        const uint32_t* d_task_unit, uint32_t n_tasks, const otg_tract_params& params, otg_tract* out);
 // the params of a tract entry: NULL gives the defaults, scores out of range are OTG_ERR_ARG
 int otg_tract_args(otg_ctx* ctx, const char* who, const otg_tract_params* params, otg_tract_params* out);
+// What the kernels over unit sets read (unitparse.hip, locus.hip): the alleles, the units (unit k = d_unit_len[k] bytes at units + unit_off[k]), set q = units
+// set_first[q] .. set_first[q + 1), task t = allele task_seq[t] against set task_set[t]; all device pointers.  otg_unit_sets_upload copies
+// the caller's host arrays into `slot` (enqueued on ctx->stream) and fills the view.
+struct OtgSetTasks {
+  OtgRows rows;
+  const uint8_t* units; const uint64_t* unit_off; const uint32_t* unit_len; const uint64_t* set_first;
+  const uint32_t* task_seq; const uint32_t* task_set;
+};
+int otg_unit_sets_upload(otg_ctx* ctx, int slot, const OtgRows& rows, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off, const uint32_t* unit_len,
+                         uint32_t n_units, const uint64_t* set_first, uint32_t n_sets, const uint32_t* task_seq, const uint32_t* task_set, uint32_t n_tasks, OtgSetTasks* out);
 // unitparse.hip: the refusals of a caller's unit sets and task lists (host arrays), and the launch part of the joint unit parse on
 // device-resident alleles (the arena extends 15 bytes past every row).  The units, sets and task lists are host arrays and are uploaded here;
 // h_len = the allele lengths on the host, NULL: they are read back from rows.len.
@@ -453,6 +467,11 @@ int otg_unitparse_resident(otg_ctx* ctx, const char* who, const OtgRows& rows, c
                            uint32_t n_seqs, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off, const uint32_t* unit_len,
                            uint32_t n_units, const uint64_t* set_first, uint32_t n_sets, const uint32_t* task_seq, const uint32_t* task_set, uint32_t n_tasks,
                            otg_unitparse_sum* sums, uint64_t* seg_off, uint64_t* n_segments);
+// locus.hip: the launch part of the locus mode, arguments as otg_unitparse_resident.  The local pass over the unit sets, then
+// otg_unitparse_resident on the tracts as sub-rows of the same arena, then the merge into SLOT_LOCUS_OUT; params has been checked.
+int otg_locus_resident(otg_ctx* ctx, const char* who, const OtgRows& rows, const uint32_t* h_len, uint32_t n_seqs, const uint8_t* unit_arena, uint64_t unit_bytes,
+                       const uint64_t* unit_off, const uint32_t* unit_len, uint32_t n_units, const uint64_t* set_first, uint32_t n_sets, const uint32_t* task_seq,
+                       const uint32_t* task_set, uint32_t n_tasks, const otg_tract_params& params, otg_locus* out, uint64_t* seg_off, uint64_t* n_segments);
 // repeat.hip: the argument refusals of otg_repeat_batch and its launch part on device-resident rows (cohort.hip), as the motif pair above
 int otg_repeat_args(otg_ctx* ctx, const char* who, uint32_t max_period, uint32_t min_copies, uint32_t min_span);
 int otg_repeat_resident(otg_ctx* ctx, const char* who, const OtgRows& rows, uint32_t n,

@@ -39,11 +39,7 @@ constexpr uint32_t UP_WALK_SPREAD = 8;                           // and only eve
 constexpr uint32_t UP_NONE = 0xffffffffu;
 constexpr size_t UP_TRACE_MB = 1024;                             // the default budget of the traceback store
 
-struct UpIn {
-  OtgRows rows;
-  const uint8_t* units; const uint64_t* unit_off; const uint32_t* unit_len; const uint64_t* set_first;
-  const uint32_t* task_seq; const uint32_t* task_set;
-};
+using UpIn = OtgSetTasks;
 
 __global__ __launch_bounds__(UP_T) void up_init(UpIn in, uint32_t n, otg_unitparse_sum* __restrict__ sums)
 {
@@ -290,11 +286,35 @@ int otg_unitparse_check(otg_ctx* ctx, const char* who, uint32_t n_seqs, const ui
       });
 }
 
+int otg_unit_sets_upload(otg_ctx* ctx, int slot, const OtgRows& rows, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off, const uint32_t* unit_len,
+                         uint32_t n_units, const uint64_t* set_first, uint32_t n_sets, const uint32_t* task_seq, const uint32_t* task_set, uint32_t n, OtgSetTasks* out)
+{
+  // unit_off (u64) | set_first (u64) | unit_len, task_seq, task_set (u32) | the unit bytes
+  const size_t meta = (size_t)n_units * 12 + (size_t)(n_sets + 1) * 8 + (size_t)n * 8;
+  uint8_t* d_u = (uint8_t*)otg_slot(ctx, slot, meta + unit_bytes + 16);
+  if (!d_u) return OTG_ERR_HIP;
+  uint64_t* d_uoff = (uint64_t*)d_u;
+  uint64_t* d_sf = d_uoff + n_units;
+  uint32_t* d_ulen = (uint32_t*)(d_sf + n_sets + 1);
+  uint32_t* d_ts = d_ulen + n_units;
+  uint32_t* d_tq = d_ts + n;
+  uint8_t* d_ub = d_u + meta;
+  HIP_TRY(ctx, hipMemcpyAsync(d_uoff, unit_off, (size_t)n_units * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_sf, set_first, (size_t)(n_sets + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_ulen, unit_len, (size_t)n_units * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_ts, task_seq, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_tq, task_set, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (unit_bytes) HIP_TRY(ctx, hipMemcpyAsync(d_ub, unit_arena, unit_bytes, hipMemcpyHostToDevice, ctx->stream));
+  *out = OtgSetTasks{rows, d_ub, d_uoff, d_ulen, d_sf, d_ts, d_tq};
+  return OTG_OK;
+}
+
 int otg_unitparse_resident(otg_ctx* ctx, const char* who, const OtgRows& rows, const uint32_t* h_len, uint32_t n_seqs, const uint8_t* unit_arena,
                            uint64_t unit_bytes, const uint64_t* unit_off, const uint32_t* unit_len, uint32_t n_units, const uint64_t* set_first, uint32_t n_sets, const uint32_t* task_seq, const uint32_t* task_set, uint32_t n,
                            otg_unitparse_sum* sums, uint64_t* seg_off, uint64_t* n_segments)
 {
   ctx->last_unitparse = OtgSegLast{};
+  ctx->last_locus.valid = false;                                   // (its segments lie in this operator's slot)
   if (n_segments) *n_segments = 0;
   if (n == 0) {
     if (seg_off) seg_off[0] = 0;
@@ -348,40 +368,27 @@ int otg_unitparse_resident(otg_ctx* ctx, const char* who, const OtgRows& rows, c
   }
   uint64_t trace_words = 0;
   for (const UpChunk& ch : chunks) trace_words = std::max(trace_words, ch.words);
-  // ---- the device copies.  UNITS: unit_off (u64) | set_first (u64) | unit_len, task_seq, task_set (u32) | the unit bytes
+  // ---- the device copies
   const size_t n_waves = wave_rows.size();
-  const size_t meta = (size_t)n_units * 12 + (size_t)(n_sets + 1) * 8 + (size_t)n * 8;
-  uint8_t* d_u = (uint8_t*)otg_slot(ctx, SLOT_UNITPARSE_UNITS, meta + unit_bytes + 16);
+  UpIn in;
+  if (int rc = otg_unit_sets_upload(ctx, SLOT_UNITPARSE_UNITS, rows, unit_arena, unit_bytes, unit_off, unit_len, n_units, set_first, n_sets, task_seq, task_set, n, &in)) return rc;
   // PLAN: wave_off (u64) | order, wave_rows, defect (u32)
   uint8_t* d_p = (uint8_t*)otg_slot(ctx, SLOT_UNITPARSE_PLAN, n_waves * 12 + order.size() * 4 + 16);
   uint8_t* d_res = (uint8_t*)otg_slot(ctx, SLOT_UNITPARSE_RES, (size_t)n * sizeof(otg_unitparse_sum) + ((size_t)n + 1) * 8);
   uint64_t* d_trace = (uint64_t*)otg_slot(ctx, SLOT_UNITPARSE_TRACE, (size_t)trace_words * 8 + 16);
-  if (!d_u || !d_p || !d_res || !d_trace) return OTG_ERR_HIP;
-  uint64_t* d_uoff = (uint64_t*)d_u;
-  uint64_t* d_sf = d_uoff + n_units;
-  uint32_t* d_ulen = (uint32_t*)(d_sf + n_sets + 1);
-  uint32_t* d_ts = d_ulen + n_units;
-  uint32_t* d_tq = d_ts + n;
-  uint8_t* d_ub = d_u + meta;
+  if (!d_p || !d_res || !d_trace) return OTG_ERR_HIP;
   uint64_t* d_woff = (uint64_t*)d_p;
   uint32_t* d_order = (uint32_t*)(d_woff + n_waves);
   uint32_t* d_wrows = d_order + order.size();
   uint32_t* d_defect = d_wrows + n_waves;
   otg_unitparse_sum* d_sums = (otg_unitparse_sum*)d_res;
   uint64_t* d_segoff = (uint64_t*)(d_res + (size_t)n * sizeof(otg_unitparse_sum));
-  HIP_TRY(ctx, hipMemcpyAsync(d_uoff, unit_off, (size_t)n_units * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_sf, set_first, (size_t)(n_sets + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_ulen, unit_len, (size_t)n_units * 4, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_ts, task_seq, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_tq, task_set, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (unit_bytes) HIP_TRY(ctx, hipMemcpyAsync(d_ub, unit_arena, unit_bytes, hipMemcpyHostToDevice, ctx->stream));
   if (n_waves) {
     HIP_TRY(ctx, hipMemcpyAsync(d_woff, wave_off.data(), n_waves * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_order, order.data(), order.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_wrows, wave_rows.data(), n_waves * 4, hipMemcpyHostToDevice, ctx->stream));
   }
   HIP_TRY(ctx, hipMemsetAsync(d_defect, 0, 4, ctx->stream));
-  const UpIn in{rows, d_ub, d_uoff, d_ulen, d_sf, d_ts, d_tq};
   const bool one = chunks.size() <= 1;
   double forward_ms = 0.0, trace_ms = 0.0;
   float ms = 0.f;
