@@ -1416,7 +1416,7 @@ typedef struct otg_locus {
   uint32_t switches;
   uint32_t unit_bases;
   uint32_t n_segments;           /* switches + 1; 0 without a tract                                  */
-  uint32_t flags;                /* OTG_LOCUS_TOO_LONG / _NONE                                       */
+  uint32_t flags;                /* OTG_LOCUS_TOO_LONG / _NONE (OTG_UNITSET_LOCUS_NO_SET after otg_unitset_locus) */
 } otg_locus;
 int otg_locus_batch(otg_ctx* ctx, const uint8_t* seq_arena, uint64_t arena_bytes, const uint64_t* seq_off, const uint32_t* seq_len,
                     uint32_t n_seqs, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off, const uint32_t* unit_len,
@@ -1451,6 +1451,133 @@ typedef struct otg_loci_job {
   uint32_t    reserved;
 } otg_loci_job;
 int otg_loci_files(const otg_loci_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
+
+/* ---------------------------------------------------------------------------------------------
+ * Unit sets from the alleles: the repeat units of a region, discovered from the repeat structure of its alleles.  The joint parse and the
+ * locus mode above need a unit set per region; a three-column BED has none.  The repeat structure already writes, per allele, the exact
+ * units that occur; this operator turns "the units seen in the alleles of a region" into "the unit set of that region", one set for all
+ * alleles of the region, so that their parses are comparable.  The reference has no counterpart; this is the definition (all integers;
+ * DESIGN.md §9).  The input is the latest repeat call on the context (its n alleles, its segments, its parameters), a grouping of those
+ * alleles into n_groups contiguous groups, group_first[0] = 0 <= group_first[1] <= .. <= group_first[n_groups] = n (a group is a region: the
+ * alleles of a VCF record, or row_first of otg_kmer_cohort_rows), and otg_unitset_params {min_bases, min_permille, redundant_permille,
+ * reserved}: 1..2^24, 0..1000, 0..1000, 0; otg_unitset_params_default gives (12, 50, 100, 0).  Per group:
+ *   1. Candidates.  Every repeat segment (begin, period p, copies, length) of every allele of the group with p <= OTG_UNITALIGN_MAX_UNIT.
+ *      Its unit is the p codes c[begin .. begin + p) (the motif table: letter case folds; a run is exact and code 4 matches nothing, so a
+ *      unit holds only ACGT).  Longer periods and literals are ignored.  The repeat parse prefers the smaller period, so a unit is never a
+ *      repetition of a shorter one.
+ *   2. Classes.  The class of a unit is its smallest rotation, compared code by code: CAG, AGC and GCA are one class.  Per class: weight =
+ *      the sum of the segment lengths (64 bits), segments = their number, length = p, and the REPRESENTATIVE = the unit exactly as the
+ *      class's longest segment wrote it, ties to the lower allele index, then to the lower begin.  The set carries the representative,
+ *      not the smallest rotation: the joint parse switches units only at phase 0, so a rotated unit costs edits at every junction.
+ *   3. Rank.  Classes in the order weight descending, length ascending, smallest rotation ascending code by code (a total order).  A class
+ *      with weight < min_bases, or with weight * 1000 < min_permille * (the largest weight of the group), is dropped; the first
+ *      OTG_UNITSET_TOP of the rest are ranked, later ones are dropped.
+ *   4. Redundancy.  Ranked class c with representative u of length p is redundant when for some class d ranked before it (redundant or
+ *      not) the unit alignment (the rule of otg_unitalign_*, unchanged) of the sequence u u against rep(d) has edits * 1000 <=
+ *      redundant_permille * 2 p.  Two copies, so that the junction counts: AGAA is a substring of GAA repeated, AGAAAGAA needs one edit.
+ *   5. Selection.  In rank order over the ranked classes that are not redundant: a class is taken when fewer than OTG_UNITPARSE_MAX_UNITS
+ *      are taken and the lanes used so far plus ceil(p / 4) stay within OTG_UNITPARSE_MAX_LANES; otherwise it is skipped and the walk goes
+ *      on.  The set of the group is the representatives of the taken classes in rank order, as upper-case ACGT bytes: the joint parse and
+ *      the locus mode accept every discovered set.
+ *   6. The group's record otg_unitset: n_units; n_classes = the distinct classes seen; n_ranked = the classes ranked in step 3;
+ *      weight_total = the sum of all candidate lengths; flags: OTG_UNITSET_NONE when no unit was selected (an empty group, no repeat
+ *      segment, everything under the thresholds), OTG_UNITSET_OVERFLOW (with OTG_UNITSET_NONE) when the group has more than
+ *      OTG_UNITSET_MAX_CLASSES distinct classes: no set, n_classes = OTG_UNITSET_MAX_CLASSES + 1, n_ranked = 0; the batch does not fail.
+ *   7. Per selected unit otg_unitset_unit {weight, segments, length} of its class.  The units of group g are set_first[g] ..
+ *      set_first[g + 1] of the unit list, their bytes unit_arena[unit_off[k] .. + unit_len[k]): the four arrays otg_unitparse_batch and
+ *      otg_locus_batch take.
+ * It follows that the result does not depend on the order in which segments are processed, that permuting the alleles of a group changes
+ * at most which of several equally long segments gives a representative, and that rotating every copy of a unit in every allele changes
+ * only the representatives.  No reverse-complement merging: all alleles of a region are on the reference strand.
+ *   otg_unitset_repeats         discovery over the latest otg_repeat_batch / otg_repeat_cohort on the context, whose alleles are read where
+ *                               that call read them (they must still lie there: the check of otg_unitalign_motifs).  sets: n_groups
+ *                               records; set_first: n_groups + 1 offsets into the unit list; *n_units, *unit_bytes: the sizes
+ *                               otg_unitset_collect needs.  Every output is nullable; params == NULL: the defaults.  The results stay in
+ *                               HBM.  No repeat results, a bad group_first or bad params: OTG_ERR_ARG; more than 2^24 groups:
+ *                               OTG_ERR_CAPACITY;
+ *   otg_unitset_collect         copies the unit records, unit_off, unit_len (unit_capacity entries each) and the unit bytes of the latest
+ *                               discovery to host arrays; a capacity too small is OTG_ERR_CAPACITY with the needs in the message;
+ *   otg_unitset_device_results  device pointers of all of it, valid until the next discovery on the context or otg_destroy; every output is
+ *                               nullable;
+ *   otg_unitset_last_ms         HIP-event times (ms) of the latest discovery: vote_ms = candidates and vote, select_ms = the pair
+ *                               lists, the pair alignments and the select;
+ *   otg_unitset_locus          the locus mode of allele i of that repeat call against the set of its group, for every allele, the alleles
+ *                               read in place.  No repeat call may lie between the discovery and this.  Tasks are the alleles whose group
+ *                               has a set; the record of any other allele is zero with flags = OTG_UNITSET_LOCUS_NO_SET, and it has no segments.
+ *                               out: n records, seg_off: n + 1 offsets; otg_locus_collect, otg_locus_device_results, otg_locus_last_ms and
+ *                               otg_locus_last_tiers work on the result as after otg_locus_batch (otg_unitparse_device_results gives the
+ *                               tasks of the second pass, which are fewer);
+ *   otg_unitset_emit            one catalogue line per VCF record r, whose group is r: chrom \t start \t end \t MOTIFS=CAG,CCG;BASES=120,48;
+ *                               SEGMENTS=3,2;ALLELES=2 \n, columns 1-3 those of the first BED record whose region string (chr:start-end)
+ *                               equals the record's ID; a record without one is OTG_ERR_ARG naming it.  A group without a set has "." in
+ *                               column 4, which otg_parse_bed_units reads as "no units".  Buffer protocol of otg_emit_alleles.
+ * The redundancy test runs the unit alignment's own kernels on the representatives where they lie in the alleles (a repeat segment holds at
+ * least two copies of its unit), so a discovery replaces what otg_unitalign_device_results and otg_unitalign_last_ms return.  The class
+ * table of a group lies in LDS and is keyed by (length, a 64-bit hash of the smallest rotation); a hash match is confirmed on the bases.
+ * OTG_UNITSET_HASH_BITS=<1..64> keeps only that many bits of the hash (read once per process), so that tests reach the
+ * compare.
+ * ------------------------------------------------------------------------------------------- */
+#define OTG_UNITSET_TOP          16
+#define OTG_UNITSET_MAX_CLASSES  2048
+#define OTG_UNITSET_NONE         1u   /* otg_unitset.flags */
+#define OTG_UNITSET_OVERFLOW     2u
+#define OTG_UNITSET_LOCUS_NO_SET         4u   /* otg_locus.flags after otg_unitset_locus: the allele's group has no set */
+typedef struct otg_unitset_params {
+  uint32_t min_bases;            /* 1..2^24: the least weight of a class                             */
+  uint32_t min_permille;         /* 0..1000: the least weight as a share of the group's largest      */
+  uint32_t redundant_permille;   /* 0..1000: edits per 1000 bases of u u that still count as explained */
+  uint32_t reserved;             /* 0                                                                */
+} otg_unitset_params;
+typedef struct otg_unitset {
+  uint32_t n_units;
+  uint32_t n_classes;
+  uint32_t n_ranked;
+  uint32_t flags;                /* OTG_UNITSET_NONE / _OVERFLOW                                     */
+  uint64_t weight_total;
+} otg_unitset;
+typedef struct otg_unitset_unit {
+  uint64_t weight;               /* bases in the class's segments                                    */
+  uint32_t segments;
+  uint32_t length;
+} otg_unitset_unit;
+void otg_unitset_params_default(otg_unitset_params* params);
+int otg_unitset_repeats(otg_ctx* ctx, const uint32_t* group_first, uint32_t n_groups, const otg_unitset_params* params, otg_unitset* sets,
+                        uint64_t* set_first, uint64_t* n_units, uint64_t* unit_bytes);
+int otg_unitset_collect(otg_ctx* ctx, otg_unitset_unit* units, uint64_t* unit_off, uint32_t* unit_len, uint64_t unit_capacity, uint8_t* unit_arena,
+                        uint64_t arena_capacity);
+int otg_unitset_device_results(otg_ctx* ctx, uint32_t* n_groups, const otg_unitset** sets, const uint64_t** set_first, uint64_t* n_units,
+                               const otg_unitset_unit** units, const uint64_t** unit_off, const uint32_t** unit_len, const uint8_t** unit_arena,
+                               uint64_t* unit_bytes);
+int otg_unitset_last_ms(otg_ctx* ctx, double* vote_ms, double* select_ms);
+int otg_unitset_locus(otg_ctx* ctx, const otg_tract_params* params, otg_locus* out, uint64_t* seg_off, uint64_t* n_segments);
+int otg_unitset_emit(const otg_vcf_record* records, uint32_t n_records, const char* region_arena, const otg_bed* beds, const char* chr_arena,
+                     uint32_t n_beds, const otg_unitset* sets, const uint64_t* set_first, const otg_unitset_unit* units, const uint8_t* unit_arena,
+                     const uint64_t* unit_off, const uint32_t* unit_len, char* out, uint64_t out_capacity, uint64_t* out_len);
+/* The unit sets of the regions of a VCF as a catalogue BED, in file order, built as otg_repeats_files is: per batch the repeat structure, the
+ * discovery with one group per VCF record, one otg_unitset_emit line per record.  A batch ends at a record boundary, so the alleles of a
+ * region are always in one discovery call; a record larger than batch_alleles runs alone.  The output is the input every catalogue tool
+ * reads (otter_copies, otter_tracts, otter_unitparse, otter_loci).  Out-of-range parameters are OTG_ERR_ARG with the message the tool prints;
+ * a VCF record without a BED record is OTG_ERR_ARG naming it.  stats as otg_vcf2mat_files. */
+typedef struct otg_units_job {
+  const char* vcf_path;          /* positional <VCF[.GZ]>                                            */
+  const char* bed_path;          /* -b: required, gives columns 1-3                                  */
+  uint32_t    max_period;        /* -p: 1..OTG_REPEAT_MAX_PERIOD (the tool's default: 256)           */
+  uint32_t    min_copies;        /* --min-copies: 2..1024 (the tool's default: 2)                    */
+  uint32_t    min_span;          /* --min-span: 2..65535 bases (the tool's default: 12)              */
+  uint32_t    min_bases;         /* --min-bases: 1..2^24 (the tool's default: 12)                    */
+  uint32_t    min_share;         /* --min-share: 0..1000 per mille (the tool's default: 50)          */
+  uint32_t    redundant;         /* --redundant: 0..1000 per mille (the tool's default: 100)         */
+  int32_t     threads;           /* -t: host threads of the emit                                     */
+  int32_t     device;            /* HIP device ordinal                                               */
+  uint32_t    batch_alleles;     /* alleles per batch, 0 = 65536                                     */
+  uint32_t    reserved;
+} otg_units_job;
+int otg_units_files(const otg_units_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
+/* otg_loci_files with the unit sets discovered where the catalogue has none, in one pass per batch: the repeat structure, the discovery (one
+ * group per VCF record; the parameters of `discover`, whose paths are ignored), the locus mode on the batch's alleles where the repeat call
+ * left them in HBM.  A region whose catalogue record has units keeps them; any other region gets the set discovered from its alleles.  Rows
+ * as otg_locus_emit, the units column holding the set that was used.  otg_loci_files itself is unchanged. */
+int otg_units_loci_files(const otg_loci_job* job, const otg_units_job* discover, otg_write_fn write, void* user, otg_job_stats* stats);
 
 /* ---------------------------------------------------------------------------------------------
  * Indexed allele BAMs from the product's own SAM text.  Every writer above emits SAM text and every reader wants a

@@ -15,3 +15,4 @@ from ._lib import parse_bed_units, unitalign_emit, copies_files  # noqa: F401
 from ._lib import tract_emit, tracts_files  # noqa: F401
 from ._lib import unitparse_emit, unitparse_files  # noqa: F401
 from ._lib import locus_emit, loci_files  # noqa: F401
+from ._lib import unitset_emit, units_files  # noqa: F401

@@ -37,6 +37,7 @@ EXPORTS = [
     "otg_tract_params_default", "otg_tract_batch", "otg_tract_motifs", "otg_tract_cohort", "otg_tract_device_results", "otg_tract_last_ms", "otg_tract_emit",
     "otg_tracts_files",
     "otg_locus_batch", "otg_locus_collect", "otg_locus_device_results", "otg_locus_last_ms", "otg_locus_last_tiers", "otg_locus_cohort", "otg_locus_emit", "otg_loci_files",
+    "otg_unitset_params_default", "otg_unitset_repeats", "otg_unitset_collect", "otg_unitset_device_results", "otg_unitset_last_ms", "otg_unitset_locus", "otg_unitset_emit", "otg_units_files", "otg_units_loci_files",
 ]
 
 _lib = None
@@ -474,6 +475,58 @@ class Context:
         self._check(self._L.otg_locus_last_tiers(self._h, C.byref(a), C.byref(b)), "otg_locus_last_tiers")
         return a.value, b.value
 
+    def unitset_repeats(self, group_first, min_bases=12, min_permille=50, redundant_permille=100, device_tensor=False):
+        """otg_unitset_repeats (and otg_unitset_collect): the unit set of every group of alleles of the latest repeat call on this context
+        (repeat_batch, cohort_repeats); group g is alleles group_first[g] .. group_first[g + 1] (include/otter_gpu.h states the rule) ->
+        (sets [n_groups] of abi.unitset_dt, units: per group the list of (unit bytes, weight, segments, length)); or with device_tensor=True
+        the torch tensors (sets int32 [n_groups, 6], set_first int64 [n_groups + 1], units int32 [n_units, 4], unit_off int64 [n_units],
+        unit_len int32 [n_units], unit_arena uint8 [bytes]) that wrap the results in HBM without a copy (valid until the next discovery on
+        this context).  The call counts as a unit alignment on the context."""
+        gf = np.ascontiguousarray(group_first, dtype=np.uint32)
+        if gf.ndim != 1 or len(gf) < 1:
+            raise ValueError("group_first needs n_groups + 1 entries")
+        G = len(gf) - 1
+        q = abi.UnitsetParams(min_bases, min_permille, redundant_permille, 0)
+        sets = np.zeros(G, dtype=abi.unitset_dt)
+        set_first = np.zeros(G + 1, dtype=np.uint64)
+        nu, nb = C.c_uint64(0), C.c_uint64(0)
+        rc = self._L.otg_unitset_repeats(self._h, abi.ptr(gf), C.c_uint32(G), C.byref(q), None if device_tensor else abi.ptr(sets),
+                                         None if device_tensor else abi.ptr(set_first), C.byref(nu), C.byref(nb))
+        self._check(rc, "otg_unitset_repeats")
+        U, B = nu.value, nb.value
+        if device_tensor:
+            m, u2, b2 = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+            p = [C.c_void_p() for _ in range(6)]
+            self._check(self._L.otg_unitset_device_results(self._h, C.byref(m), C.byref(p[0]), C.byref(p[1]), C.byref(u2), C.byref(p[2]), C.byref(p[3]), C.byref(p[4]),
+                                                           C.byref(p[5]), C.byref(b2)), "otg_unitset_device_results")
+            assert (m.value, u2.value, b2.value) == (G, U, B)
+            return (self._wrap_device(p[0].value, (G, 6), "<i4"), self._wrap_device(p[1].value, (G + 1,), "<i8"), self._wrap_device(p[2].value, (U, 4), "<i4"),
+                    self._wrap_device(p[3].value, (U,), "<i8"), self._wrap_device(p[4].value, (U,), "<i4"), self._wrap_device(p[5].value, (B,), "|u1"))
+        rec = np.zeros(U, dtype=abi.unitset_unit_dt)
+        uoff = np.zeros(U, dtype=np.uint64)
+        ulen = np.zeros(U, dtype=np.uint32)
+        arena = np.zeros(max(B, 1), dtype=np.uint8)
+        self._check(self._L.otg_unitset_collect(self._h, abi.ptr(rec), abi.ptr(uoff), abi.ptr(ulen), C.c_uint64(U), abi.ptr(arena), C.c_uint64(B)), "otg_unitset_collect")
+        raw = arena.tobytes()
+        units = [[(raw[int(uoff[k]):int(uoff[k]) + int(ulen[k])], int(rec["weight"][k]), int(rec["segments"][k]), int(rec["length"][k]))
+                  for k in range(int(set_first[g]), int(set_first[g + 1]))] for g in range(G)]
+        return sets, units
+
+    def unitset_last_ms(self):
+        """(candidates and vote ms, pair alignments and select ms) of the latest discovery on this context (HIP events)."""
+        return self._last_ms("otg_unitset_last_ms", 2)
+
+    def locus_unitsets(self, match=2, mismatch=7, indel=7, min_score=24, device_tensor=False):
+        """otg_unitset_locus: the locus mode of every allele of the latest repeat call against the unit set the latest discovery
+        (unitset_repeats) gave its group, the alleles read where they lie in HBM -> (records, seg_off, segs) as locus_batch returns them, one
+        record per allele; an allele whose group has no set has a zero record with flags = abi.UNITSET_LOCUS_NO_SET and no segments."""
+        m = C.c_uint32(0)
+        if self._L.otg_repeat_device_results(self._h, C.byref(m), None, None, None, None) != 0:
+            m.value = 0                                                     # (no repeat results: the entry below says what is missing)
+        q = abi.TractParams(match, mismatch, indel, min_score)
+        return self._seg_results("locus", m.value, device_tensor, lambda recs, seg_off, total: self._L.otg_unitset_locus(
+            self._h, C.byref(q), recs, seg_off, total), "otg_unitset_locus")
+
     def affine_align_batch(self, arena, tasks, x=4, o=6, e=2, want_cells=False):
         n = len(tasks)
         scores = np.zeros(n, dtype=np.int32)
@@ -900,6 +953,12 @@ class Context:
         q = abi.TractParams(match, mismatch, indel, min_score)
         return self._seg_results("locus", len(ts), device_tensor, lambda recs, seg_off, total: self._L.otg_locus_cohort(
             self._h, C.c_uint32(row_begin), C.c_uint32(n), *sets, abi.ptr(ts), abi.ptr(tq), C.c_uint32(len(ts)), C.byref(q), recs, seg_off, total), "otg_locus_cohort")
+
+    def cohort_unitsets(self, max_period=256, min_copies=2, min_span=12, min_bases=12, min_permille=50, redundant_permille=100, device_tensor=False):
+        """the unit set of every region of the open cohort batch: cohort_repeats over the whole row list, then the discovery with row_first as
+        the groups (one group per VCF line), the alleles read in the cohort arena in place -> as unitset_repeats returns it."""
+        self.cohort_repeats(0, None, max_period, min_copies, min_span, device_tensor=True)
+        return self.unitset_repeats(self.cohort_kmer_rows()["row_first"], min_bases, min_permille, redundant_permille, device_tensor)
 
     def cohort_end(self):
         self._check(self._L.otg_cohort_end(self._h), "otg_cohort_end")
@@ -1924,11 +1983,77 @@ def locus_emit(records, regions, seq_len, allele_sets, unit_sets, loci, seg_off,
     return out.raw[:need.value]
 
 
-def loci_files(vcf, bed, match=2, mismatch=7, indel=7, min_score=24, threads=1, device=0, batch_alleles=0):
+def loci_files(vcf, bed, match=2, mismatch=7, indel=7, min_score=24, threads=1, device=0, batch_alleles=0, discover=False, max_period=256, min_copies=2,
+               min_span=12, min_bases=12, min_share=50, redundant=100):
     """otg_loci_files: the joint parse of the repeat inside every allele of a VCF (plain, gzip or BGZF) against the unit set its region has in a
-    tandem-repeat catalogue, as text.  Returns (text bytes, stats dict)."""
+    tandem-repeat catalogue, as text.  Returns (text bytes, stats dict).  discover=True (otg_units_loci_files): a region without units in the
+    catalogue gets the set discovered from its alleles (the last six parameters, as units_files takes them)."""
     job = abi.LociJob()
     job.vcf_path = vcf.encode(); job.bed_path = bed.encode()
     job.match = match; job.mismatch = mismatch; job.indel = indel; job.min_score = min_score
     job.threads = threads; job.device = device; job.batch_alleles = batch_alleles
-    return _run_files_job("otg_loci_files", job, abi.LociJob)
+    if not discover:
+        return _run_files_job("otg_loci_files", job, abi.LociJob)
+    dj = abi.UnitsJob()
+    dj.max_period = max_period; dj.min_copies = min_copies; dj.min_span = min_span
+    dj.min_bases = min_bases; dj.min_share = min_share; dj.redundant = redundant
+    L = load()
+    chunks = []
+
+    def collect(_user, data, n):
+        chunks.append(C.string_at(data, n))
+        return 0
+    cb = abi.WRITE_FN(collect)
+    st = abi.JobStats()
+    L.otg_units_loci_files.argtypes = [C.POINTER(abi.LociJob), C.POINTER(abi.UnitsJob), abi.WRITE_FN, C.c_void_p, C.POINTER(abi.JobStats)]
+    rc = L.otg_units_loci_files(C.byref(job), C.byref(dj), cb, None, C.byref(st))
+    if rc != 0:
+        raise OtterGpuError("otg_units_loci_files failed (%d): %s" % (rc, _err(L)))
+    return b"".join(chunks), {k: getattr(st, k) for k, _ in abi.JobStats._fields_}
+
+
+def unitset_emit(records, regions, beds, sets, units):
+    """otg_unitset_emit: one catalogue line per VCF record (vcf_record_dt; record r is group r of the discovery) -> text bytes.  beds = a list
+    of (chrom bytes, start, end); sets (unitset_dt) and units (per group the list of (unit bytes, weight, segments, length)) as
+    Context.unitset_repeats returns them."""
+    L = load()
+    records = np.ascontiguousarray(records, dtype=abi.vcf_record_dt)
+    sets = np.ascontiguousarray(sets, dtype=abi.unitset_dt)
+    bed = np.zeros(max(len(beds), 1), dtype=abi.bed_dt)
+    chroms = b""
+    for i, (c, s, e) in enumerate(beds):
+        bed[i] = (len(chroms), len(c), s, e, 0)
+        chroms += c
+    chr_arena = np.frombuffer(chroms + b"\0", dtype=np.uint8)
+    flat = [u for g in units for u in g]
+    set_first = np.zeros(len(units) + 1, dtype=np.uint64)
+    set_first[1:] = np.cumsum([len(g) for g in units])
+    rec = np.zeros(max(len(flat), 1), dtype=abi.unitset_unit_dt)
+    for k, u in enumerate(flat):
+        rec[k] = (u[1], u[2], u[3])
+    uarena, uoff, ulen = _pack_units([u[0] for u in flat])
+    if not flat:
+        uoff, ulen = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint32)
+    reg = np.frombuffer(regions + b"\0", dtype=np.uint8)
+    need = C.c_uint64(0)
+    args = lambda out, cap: (abi.ptr(records), C.c_uint32(len(records)), abi.ptr(reg), abi.ptr(bed), abi.ptr(chr_arena), C.c_uint32(len(beds)), abi.ptr(sets),
+                             abi.ptr(set_first), abi.ptr(rec), abi.ptr(uarena), abi.ptr(uoff), abi.ptr(ulen), out, C.c_uint64(cap), C.byref(need))
+    rc = L.otg_unitset_emit(*args(None, 0))
+    if rc not in (0, abi.OTG_ERR_CAPACITY):
+        raise OtterGpuError("otg_unitset_emit failed (%d): %s" % (rc, _err(L)))
+    out = C.create_string_buffer(need.value + 1)
+    rc = L.otg_unitset_emit(*args(out, need.value))
+    if rc != 0:
+        raise OtterGpuError("otg_unitset_emit failed (%d): %s" % (rc, _err(L)))
+    return out.raw[:need.value]
+
+
+def units_files(vcf, bed, max_period=256, min_copies=2, min_span=12, min_bases=12, min_share=50, redundant=100, threads=1, device=0, batch_alleles=0):
+    """otg_units_files: the unit set of every region of a VCF (plain, gzip or BGZF), discovered from the repeat structure of its alleles, as a
+    catalogue BED (columns 1-3 from `bed`).  Returns (text bytes, stats dict)."""
+    job = abi.UnitsJob()
+    job.vcf_path = vcf.encode(); job.bed_path = bed.encode()
+    job.max_period = max_period; job.min_copies = min_copies; job.min_span = min_span
+    job.min_bases = min_bases; job.min_share = min_share; job.redundant = redundant
+    job.threads = threads; job.device = device; job.batch_alleles = batch_alleles
+    return _run_files_job("otg_units_files", job, abi.UnitsJob)

@@ -327,6 +327,29 @@ class LociJob(C.Structure):
                 ("min_score", C.c_uint32), ("threads", C.c_int32), ("device", C.c_int32), ("batch_alleles", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+# otg_unitset / otg_unitset_unit / otg_unitset_params (include/otter_gpu.h) and the bounds of the unit-set discovery
+unitset_dt = np.dtype([("n_units", np.uint32), ("n_classes", np.uint32), ("n_ranked", np.uint32), ("flags", np.uint32), ("weight_total", np.uint64)])
+unitset_unit_dt = np.dtype([("weight", np.uint64), ("segments", np.uint32), ("length", np.uint32)])
+assert unitset_dt.itemsize == 24 and unitset_unit_dt.itemsize == 16
+UNITSET_TOP = 16
+UNITSET_MAX_CLASSES = 2048
+UNITSET_NONE = 1
+UNITSET_OVERFLOW = 2
+UNITSET_LOCUS_NO_SET = 4
+
+
+class UnitsetParams(C.Structure):
+    """otg_unitset_params (include/otter_gpu.h)."""
+    _fields_ = [("min_bases", C.c_uint32), ("min_permille", C.c_uint32), ("redundant_permille", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class UnitsJob(C.Structure):
+    """otg_units_job (include/otter_gpu.h)."""
+    _fields_ = [("vcf_path", C.c_char_p), ("bed_path", C.c_char_p), ("max_period", C.c_uint32), ("min_copies", C.c_uint32), ("min_span", C.c_uint32),
+                ("min_bases", C.c_uint32), ("min_share", C.c_uint32), ("redundant", C.c_uint32), ("threads", C.c_int32), ("device", C.c_int32),
+                ("batch_alleles", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class JobStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("n_regions", "n_regions_ok", "n_regions_skipped", "n_reads", "n_alleles", "input_bytes", "output_bytes")] + \
                [("n_devices", C.c_uint32), ("reserved", C.c_uint32)] + [(k, C.c_double) for k in ("ms_total", "ms_ingest", "ms_hot_path", "ms_emit")]

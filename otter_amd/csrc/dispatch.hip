@@ -19,6 +19,7 @@
 #include "otg_repeat.hpp"
 #include "otg_unitalign.hpp"
 #include "otg_locus.hpp"
+#include "otg_unitset.hpp"
 #include "otg_tract.hpp"
 #include "otg_unitparse.hpp"
 #include "otg_unitparse_core.hpp"
@@ -1318,67 +1319,96 @@ int otg_tracts_files(const otg_tracts_job* job, otg_write_fn write, void* user, 
 // uses are uploaded; collect_fn brings its segments); the others get the row without units.  Rec = the operator's record (zero: an allele
 // that was not a task); rows_fn = its row text.
 extern "C++" {
+// The unit sets and tasks of one batch, as unit_sets_job and otg_units_loci_files build them: one set per record with units, one task per allele
+// of such a record, in allele order.  add() is the only place where a region's units are refused (more than eight, the lane budget, an empty
+// unit): these are the set refusals of otg_unitparse_check, which the resident entries called with these arrays do not repeat; the ranges of
+// the unit bytes hold by construction (every unit is copied into `units` here).
+struct BatchSets {
+  std::vector<uint64_t> set_first, uoff;
+  std::vector<uint32_t> ulen, allele_set, tseq, tset;
+  std::vector<uint8_t> units;
+  void begin(uint32_t na)
+  {
+    set_first.assign(1, 0); uoff.clear(); ulen.clear(); units.clear(); tseq.clear(); tset.clear();
+    allele_set.assign(na, OTG_UNITPARSE_NO_SET);
+  }
+  // units [u0, u1) of (arena, off, len) become the set of record R (region `name`); u0 == u1: the record has none
+  int add(otg_ctx* ctx, const std::string& name, const otg_vcf_record& R, const uint8_t* arena, const uint64_t* off, const uint32_t* len, uint64_t u0, uint64_t u1)
+  {
+    if (u1 == u0) return OTG_OK;
+    if (u1 - u0 > OTG_UNITPARSE_MAX_UNITS)
+      return otg_fail(ctx, OTG_ERR_ARG, "%s has %llu units in the catalogue, at most %d", name.c_str(), (unsigned long long)(u1 - u0),
+                      OTG_UNITPARSE_MAX_UNITS);
+    if (otg_unitparse_core::up_class(len + u0, (uint32_t)(u1 - u0)) == otg_unitparse_core::UP_NO_CLASS)
+      return otg_fail(ctx, OTG_ERR_ARG, "the units of %s do not fit one wave (%u lanes at four positions each, at most %d)", name.c_str(),
+                      otg_unitparse_core::up_lanes(len + u0, (uint32_t)(u1 - u0), 4u), OTG_UNITPARSE_MAX_LANES);
+    const uint32_t q = (uint32_t)set_first.size() - 1u;
+    for (uint64_t k = u0; k < u1; ++k) {
+      if (len[k] == 0u || len[k] > OTG_UNITALIGN_MAX_UNIT)
+        return otg_fail(ctx, OTG_ERR_ARG, "%s has a unit of %u bytes, 1 to %d are allowed", name.c_str(), len[k], OTG_UNITALIGN_MAX_UNIT);
+      uoff.push_back(units.size()); ulen.push_back(len[k]);
+      units.insert(units.end(), arena + off[k], arena + off[k] + len[k]);
+    }
+    set_first.push_back(ulen.size());
+    for (uint32_t i = 0; i < R.n_alleles; ++i) { allele_set[R.first_allele + i] = q; tseq.push_back(R.first_allele + i); tset.push_back(q); }
+    return OTG_OK;
+  }
+  void finish() { units.push_back(0); uoff.push_back(0); ulen.push_back(0); }      // (never empty: the emit takes their addresses)
+  uint32_t n_units() const { return (uint32_t)ulen.size() - 1u; }
+  uint32_t n_sets() const { return (uint32_t)set_first.size() - 1u; }
+  // the tasks are the alleles with units, in allele order: their records and segment offsets spread over all na alleles
+  template <typename Rec>
+  void spread(uint32_t na, const std::vector<Rec>& t_sums, const std::vector<uint64_t>& t_seg_off, uint64_t total, std::vector<Rec>& sums, std::vector<uint64_t>& seg_off) const
+  {
+    sums.assign(na, Rec{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}); seg_off.assign((size_t)na + 1, 0);
+    const uint32_t nt = (uint32_t)tseq.size();
+    uint32_t cur = 0;
+    for (uint32_t a = 0; a < na; ++a) {
+      seg_off[a] = t_seg_off[cur];
+      if (cur < nt && tseq[cur] == a) sums[a] = t_sums[cur++];
+    }
+    seg_off[na] = total;
+  }
+};
+
 template <typename Rec, typename BatchFn, typename CollectFn, typename RowsFn>
 int unit_sets_job(const char* who, const char* vcf_path, const char* bed_path, int32_t device, uint32_t batch_alleles, int32_t threads, otg_write_fn write, void* user,
                   otg_job_stats* stats, BatchFn batch_fn, CollectFn collect_fn, RowsFn rows_fn)
 {
   UnitCatalogue cat;
   if (int rc = cat.load(who, bed_path)) return rc;
-  // per batch: one set per record with units, one task per allele of such a record; the results per allele, in file order
-  std::vector<uint64_t> set_first, uoff, seg_off, t_seg_off;
-  std::vector<uint32_t> ulen, allele_set, tseq, tset;
-  std::vector<uint8_t> units;
+  // per batch: the sets and tasks (BatchSets); the results per allele, in file order
+  BatchSets S;
+  std::vector<uint64_t> seg_off, t_seg_off;
   std::vector<Rec> sums, t_sums;
   std::vector<otg_unitparse_seg> segs;
   return vcf_allele_job(who, vcf_path, bed_path, device, batch_alleles ? batch_alleles : 65536, threads, write, user, stats,
     [&](otg_ctx* ctx, const VcfBatch& B) {
-      set_first.assign(1, 0); uoff.clear(); ulen.clear(); units.clear(); tseq.clear(); tset.clear();
-      allele_set.assign(B.na, OTG_UNITPARSE_NO_SET);
+      S.begin(B.na);
       std::string name;
       for (uint32_t r = 0; r < B.nr; ++r) {
         const otg_vcf_record& R = B.rec[r];
         name.assign(B.regions.data() + R.region_off, R.region_len);
         uint64_t u0, u1;
         cat.units_of(name, &u0, &u1);
-        if (u1 == u0) continue;
-        if (u1 - u0 > OTG_UNITPARSE_MAX_UNITS)
-          return otg_fail(ctx, OTG_ERR_ARG, "%s has %llu units in the catalogue, at most %d", name.c_str(), (unsigned long long)(u1 - u0),
-                          OTG_UNITPARSE_MAX_UNITS);
-        if (otg_unitparse_core::up_class(cat.len.data() + u0, (uint32_t)(u1 - u0)) == otg_unitparse_core::UP_NO_CLASS)
-          return otg_fail(ctx, OTG_ERR_ARG, "the units of %s do not fit one wave (%u lanes at four positions each, at most %d)", name.c_str(),
-                          otg_unitparse_core::up_lanes(cat.len.data() + u0, (uint32_t)(u1 - u0), 4u), OTG_UNITPARSE_MAX_LANES);
-        const uint32_t q = (uint32_t)set_first.size() - 1u;
-        for (uint64_t k = u0; k < u1; ++k) {
-          uoff.push_back(units.size()); ulen.push_back(cat.len[k]);
-          units.insert(units.end(), cat.arena.begin() + cat.off[k], cat.arena.begin() + cat.off[k] + cat.len[k]);
-        }
-        set_first.push_back(ulen.size());
-        for (uint32_t i = 0; i < R.n_alleles; ++i) { allele_set[R.first_allele + i] = q; tseq.push_back(R.first_allele + i); tset.push_back(q); }
+        if (int rc = S.add(ctx, name, R, cat.arena.data(), cat.off.data(), cat.len.data(), u0, u1)) return rc;
       }
-      units.push_back(0); uoff.push_back(0); ulen.push_back(0);      // (never empty: the emit takes their addresses)
-      const uint32_t nt = (uint32_t)tseq.size();
+      S.finish();
+      const uint32_t nt = (uint32_t)S.tseq.size();
       t_sums.resize(nt); t_seg_off.assign((size_t)nt + 1, 0);
       uint64_t total = 0;
       if (nt) {
-        if (int rc = batch_fn(ctx, B.seqs.data(), B.au, B.off.data(), B.len.data(), B.na, units.data(), units.size() - 1, uoff.data(), ulen.data(),
-                              (uint32_t)ulen.size() - 1u, set_first.data(), (uint32_t)set_first.size() - 1u, tseq.data(), tset.data(), nt, t_sums.data(),
-                              t_seg_off.data(), &total)) return rc;
+        if (int rc = batch_fn(ctx, B.seqs.data(), B.au, B.off.data(), B.len.data(), B.na, S.units.data(), S.units.size() - 1, S.uoff.data(), S.ulen.data(), S.n_units(),
+                              S.set_first.data(), S.n_sets(), S.tseq.data(), S.tset.data(), nt, t_sums.data(), t_seg_off.data(), &total)) return rc;
       }
       segs.resize(total + 1);
       if (total)
         if (int rc = collect_fn(ctx, segs.data(), total)) return rc;
-      // the tasks are the alleles with units, in allele order: their segments lie in that order too
-      sums.assign(B.na, Rec{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}); seg_off.assign((size_t)B.na + 1, 0);
-      uint32_t cur = 0;
-      for (uint32_t a = 0; a < B.na; ++a) {
-        seg_off[a] = t_seg_off[cur];
-        if (cur < nt && tseq[cur] == a) sums[a] = t_sums[cur++];
-      }
-      seg_off[B.na] = total;
+      S.spread(B.na, t_sums, t_seg_off, total, sums, seg_off);
       return (int)OTG_OK;
     },
     [&](std::string& o, const VcfBatch& B, uint32_t r0, uint32_t nr) {
-      rows_fn(o, B.rec.data() + r0, nr, B.regions.data(), B.len.data(), allele_set.data(), set_first.data(), units.data(), uoff.data(), ulen.data(), sums.data(),
+      rows_fn(o, B.rec.data() + r0, nr, B.regions.data(), B.len.data(), S.allele_set.data(), S.set_first.data(), S.units.data(), S.uoff.data(), S.ulen.data(), sums.data(),
               seg_off.data(), segs.data());
     });
 }
@@ -1404,6 +1434,142 @@ int otg_loci_files(const otg_loci_job* job, otg_write_fn write, void* user, otg_
           const uint32_t* ulen, uint32_t nu, const uint64_t* sf, uint32_t ns, const uint32_t* ts, const uint32_t* tq, uint32_t nt, otg_locus* out, uint64_t* seg_off,
           uint64_t* total) { return otg_locus_batch(ctx, seqs, au, off, len, na, ua, ub, uoff, ulen, nu, sf, ns, ts, tq, nt, &q, out, seg_off, total); },
       otg_locus_collect, otg_locus_rows);
+}
+
+// the parameters of a discovery job, refused in the command line's words
+static int units_cli_args(const otg_units_job& J)
+{
+  if (J.max_period < 1 || J.max_period > OTG_REPEAT_MAX_PERIOD)
+    return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--max-period' (%u). Needs to be 1 <= x <= %d.", J.max_period, OTG_REPEAT_MAX_PERIOD);
+  if (J.min_copies < 2 || J.min_copies > 1024) return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--min-copies' (%u). Needs to be 2 <= x <= 1024.", J.min_copies);
+  if (J.min_span < 2 || J.min_span > 65535) return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--min-span' (%u). Needs to be 2 <= x <= 65535.", J.min_span);
+  if (J.min_bases < 1 || J.min_bases > (1u << 24))
+    return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--min-bases' (%u). Needs to be 1 <= x <= %u.", J.min_bases, 1u << 24);
+  if (J.min_share > 1000) return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--min-share' (%u). Needs to be 0 <= x <= 1000.", J.min_share);
+  if (J.redundant > 1000) return otg_fail(nullptr, OTG_ERR_ARG, "[ERROR] invalid '--redundant' (%u). Needs to be 0 <= x <= 1000.", J.redundant);
+  return OTG_OK;
+}
+
+// The unit sets of a VCF's regions as a catalogue BED: otg_repeat_batch and otg_unitset_repeats on vcf_allele_job, one group per VCF record.
+// A batch ends at a record boundary (otg_vcf_read_alleles delivers whole records; a record larger than the batch runs alone), so the alleles
+// of a region are always in one discovery call.
+int otg_units_files(const otg_units_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
+{
+  if (!job || !write || !job->vcf_path || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "otg_units_files: NULL job, writer, VCF or BED path");
+  if (int rc = units_cli_args(*job)) return rc;
+  const uint32_t max_period = job->max_period, min_copies = job->min_copies, min_span = job->min_span;
+  const otg_unitset_params q{job->min_bases, job->min_share, job->redundant, 0u};
+  Bed bed;
+  if (int rc = load_bed(job->bed_path, bed)) return rc;
+  std::map<std::string, uint32_t> by_region;                       // the first record of a region wins
+  {
+    std::string name;
+    for (uint32_t r = 0; r < bed.beds.size(); ++r) {
+      name.clear();
+      otg_region_name(name, bed.chr_arena.data() + bed.beds[r].chr_off, bed.beds[r].chr_len, bed.beds[r].start, bed.beds[r].end);
+      by_region.emplace(name, r);
+    }
+  }
+  std::vector<uint32_t> group_first, rec_bed, unit_len;
+  std::vector<otg_unitset> sets;
+  std::vector<uint64_t> set_first, unit_off;
+  std::vector<otg_unitset_unit> units;
+  std::vector<uint8_t> unit_arena;
+  return vcf_allele_job("otg_units_files", job->vcf_path, job->bed_path, job->device, job->batch_alleles ? job->batch_alleles : 65536, job->threads, write, user, stats,
+    [&](otg_ctx* ctx, const VcfBatch& B) {
+      rec_bed.resize(B.nr); group_first.resize((size_t)B.nr + 1); sets.resize(B.nr); set_first.assign((size_t)B.nr + 1, 0);
+      std::string name;
+      for (uint32_t r = 0; r < B.nr; ++r) {
+        name.assign(B.regions.data() + B.rec[r].region_off, B.rec[r].region_len);
+        const auto it = by_region.find(name);
+        if (it == by_region.end()) return otg_fail(ctx, OTG_ERR_ARG, "no BED record for the region %s", name.c_str());
+        rec_bed[r] = it->second;
+        group_first[r] = B.rec[r].first_allele;
+      }
+      group_first[B.nr] = B.na;
+      if (B.na == 0) return (int)OTG_OK;                            // (records always have a REF allele)
+      if (int rc = otg_repeat_batch(ctx, B.seqs.data(), B.au, B.off.data(), B.len.data(), B.na, max_period, min_copies, min_span, nullptr, nullptr, nullptr)) return rc;
+      uint64_t nu = 0, nb = 0;
+      if (int rc = otg_unitset_repeats(ctx, group_first.data(), B.nr, &q, sets.data(), set_first.data(), &nu, &nb)) return rc;
+      units.resize(nu + 1); unit_off.resize(nu + 1); unit_len.resize(nu + 1); unit_arena.resize(nb + 1);
+      return otg_unitset_collect(ctx, units.data(), unit_off.data(), unit_len.data(), nu, unit_arena.data(), nb);
+    },
+    [&](std::string& o, const VcfBatch& B, uint32_t r0, uint32_t nr) {
+      otg_unitset_lines(o, B.rec.data() + r0, nr, rec_bed.data() + r0, bed.beds.data(), bed.chr_arena.data(), set_first.data() + r0, units.data(), unit_arena.data(),
+                        unit_off.data(), unit_len.data());
+    });
+}
+
+// The locus mode over a VCF's alleles with the unit sets discovered where the catalogue has none, in one pass per batch: the repeat
+// structure, the discovery (one group per VCF record), then the locus mode on the batch's alleles where the repeat call left them in HBM.
+// A region whose catalogue record has units keeps them; any other region gets the set discovered from its alleles; rows as otg_loci_files.
+int otg_units_loci_files(const otg_loci_job* job, const otg_units_job* discover, otg_write_fn write, void* user, otg_job_stats* stats)
+{
+  if (!job || !discover || !write || !job->vcf_path || !job->bed_path)
+    return otg_fail(nullptr, OTG_ERR_ARG, "otg_units_loci_files: NULL job, discovery parameters, writer, VCF or BED path");
+  const otg_tract_params q{job->match, job->mismatch, job->indel, job->min_score};
+  if (int rc = tract_cli_args(q)) return rc;
+  if (int rc = units_cli_args(*discover)) return rc;
+  const otg_unitset_params dq{discover->min_bases, discover->min_share, discover->redundant, 0u};
+  const uint32_t max_period = discover->max_period, min_copies = discover->min_copies, min_span = discover->min_span;
+  const char* who = "otg_units_loci_files";
+  UnitCatalogue cat;
+  if (int rc = cat.load(who, job->bed_path)) return rc;
+  BatchSets S;
+  std::vector<uint64_t> seg_off, t_seg_off, d_set_first, d_uoff;
+  std::vector<uint32_t> group_first, d_ulen;
+  std::vector<uint8_t> d_arena;
+  std::vector<otg_unitset_unit> d_units;
+  std::vector<otg_locus> sums, t_sums;
+  std::vector<otg_unitparse_seg> segs;
+  return vcf_allele_job(who, job->vcf_path, job->bed_path, job->device, job->batch_alleles ? job->batch_alleles : 65536, job->threads, write, user, stats,
+    [&](otg_ctx* ctx, const VcfBatch& B) {
+      S.begin(B.na);
+      t_sums.clear(); t_seg_off.assign(1, 0); segs.resize(1);
+      if (B.na == 0) {
+        S.finish();
+        S.spread(0, t_sums, t_seg_off, 0, sums, seg_off);
+        return (int)OTG_OK;
+      }
+      group_first.resize((size_t)B.nr + 1);
+      for (uint32_t r = 0; r < B.nr; ++r) group_first[r] = B.rec[r].first_allele;
+      group_first[B.nr] = B.na;
+      d_set_first.assign((size_t)B.nr + 1, 0);
+      if (int rc = otg_repeat_batch(ctx, B.seqs.data(), B.au, B.off.data(), B.len.data(), B.na, max_period, min_copies, min_span, nullptr, nullptr, nullptr)) return rc;
+      uint64_t nu = 0, nb = 0;
+      if (int rc = otg_unitset_repeats(ctx, group_first.data(), B.nr, &dq, nullptr, d_set_first.data(), &nu, &nb)) return rc;
+      d_units.resize(nu + 1); d_uoff.resize(nu + 1); d_ulen.resize(nu + 1); d_arena.resize(nb + 1);
+      if (int rc = otg_unitset_collect(ctx, d_units.data(), d_uoff.data(), d_ulen.data(), nu, d_arena.data(), nb)) return rc;
+      std::string name;
+      for (uint32_t r = 0; r < B.nr; ++r) {
+        const otg_vcf_record& R = B.rec[r];
+        name.assign(B.regions.data() + R.region_off, R.region_len);
+        uint64_t u0, u1;
+        cat.units_of(name, &u0, &u1);
+        const int rc = u1 > u0 ? S.add(ctx, name, R, cat.arena.data(), cat.off.data(), cat.len.data(), u0, u1)
+                               : S.add(ctx, name, R, d_arena.data(), d_uoff.data(), d_ulen.data(), d_set_first[r], d_set_first[r + 1]);      // the discovered set
+        if (rc) return rc;
+      }
+      S.finish();
+      const uint32_t nt = (uint32_t)S.tseq.size();
+      t_sums.resize(nt); t_seg_off.assign((size_t)nt + 1, 0);
+      uint64_t total = 0;
+      if (nt) {
+        // the alleles lie where the repeat call read them: no second upload.  The sets have passed BatchSets::add, which stands in for
+        // otg_unitparse_check here
+        if (int rc = otg_locus_resident(ctx, who, ctx->last_repeat_rows, B.len.data(), B.na, S.units.data(), S.units.size() - 1, S.uoff.data(), S.ulen.data(), S.n_units(),
+                                        S.set_first.data(), S.n_sets(), S.tseq.data(), S.tset.data(), nt, q, t_sums.data(), t_seg_off.data(), &total)) return rc;
+      }
+      segs.resize(total + 1);
+      if (total)
+        if (int rc = otg_locus_collect(ctx, segs.data(), total)) return rc;
+      S.spread(B.na, t_sums, t_seg_off, total, sums, seg_off);
+      return (int)OTG_OK;
+    },
+    [&](std::string& o, const VcfBatch& B, uint32_t r0, uint32_t nr) {
+      otg_locus_rows(o, B.rec.data() + r0, nr, B.regions.data(), B.len.data(), S.allele_set.data(), S.set_first.data(), S.units.data(), S.uoff.data(), S.ulen.data(),
+                     sums.data(), seg_off.data(), segs.data());
+    });
 }
 
 // ---- `otter genotype` from files to text in one call: genotype() / genotype_process() (src/genotype.cpp:69-192).  Regions in bounded

@@ -59,6 +59,8 @@ struct otg_ctx {
   double last_motif_count_ms = 0.0, last_motif_reduce_ms = 0.0;   // HIP-event times of the latest otg_motif_batch / otg_motif_cohort (otg_motif_last_ms)
   uint32_t last_motif_n = 0, last_motif_stride = 0;               // the shape of the results in SLOT_MOTIF_OUT (otg_motif_device_results)
   OtgSegLast last_repeat;                                         // the latest otg_repeat_batch / otg_repeat_cohort: SLOT_REPEAT_RES / SLOT_REPEAT_SEGS, ms = runs, select
+  OtgRows last_repeat_rows = {nullptr, nullptr, nullptr};         // where that repeat call read its alleles (n = last_repeat.n): otg_unitset_repeats reads them in place
+  uint64_t repeat_serial = 0;                                     // counts the repeat calls on the context: a discovery remembers which one it read
   OtgRows last_motif_rows = {nullptr, nullptr, nullptr};                                  // where the latest motif call read its alleles (n = last_motif_n): otg_unitalign_motifs aligns them in place
   double last_unitalign_ms = 0.0;                                 // HIP-event time of the latest unit alignment (otg_unitalign_last_ms)
   uint32_t last_unitalign_n = 0;                                  // the records in SLOT_UNITALIGN_OUT (otg_unitalign_device_results); 0: none
@@ -66,6 +68,12 @@ struct otg_ctx {
   uint32_t last_tract_n = 0;                                      // the records in SLOT_TRACT_OUT (otg_tract_device_results); 0: none
   OtgSegLast last_unitparse;                                      // the latest unit parse: SLOT_UNITPARSE_RES / SLOT_UNITPARSE_SEGS, ms = forward, traceback
   OtgSegLast last_locus;                                          // the latest locus call: SLOT_LOCUS_OUT / SLOT_UNITPARSE_SEGS, ms = both passes, the local pass; a later unit parse ends it
+  // the latest otg_unitset_repeats: SLOT_UNITSET_RES (sets, set_first) / SLOT_UNITSET_UNITS (unit records, unit_off, unit_len, bytes)
+  struct UnitsetLast {
+    uint32_t n_groups = 0, n_alleles = 0; uint64_t n_units = 0, unit_bytes = 0, repeat_serial = 0; bool valid = false;
+    double ms[2] = {0.0, 0.0};                                    // candidates and vote, pair alignments and select
+    std::vector<uint32_t> group_first;                            // the caller's grouping (otg_unitset_locus maps alleles to sets by it)
+  } last_unitset;
   uint32_t last_locus_tiers[2] = {0u, 0u};                        // tasks the narrow / the wide tier of that call's local pass took (otg_locus_last_tiers)
   double last_kernel_ms = 0.0;                    // HIP-event time of the kernels of the latest operator-level call that reports one (otg_last_kernel_ms)
   // the latest genotype clustering with a metric (genotype_edit.hip): times of its two parts (otg_genotype_metric_last_ms), whether the edit
@@ -162,6 +170,9 @@ enum {
   SLOT_TRACT_OUT,                                                   // its records: they stay valid for the device results
   SLOT_LOCUS_SEQ, SLOT_LOCUS_META, SLOT_LOCUS_UNITS, SLOT_LOCUS_SUB,   // otg_locus_batch (locus.hip); SUB: the sub-rows of the second pass and the task order
   SLOT_LOCUS_OUT,                                                   // its records and segment offsets: they stay valid for the device results
+  SLOT_UNITSET_CAND, SLOT_UNITSET_WORK, SLOT_UNITSET_TASKS, SLOT_UNITSET_PAIRS,   // otg_unitset_repeats (unitset.hip): candidates, ranked classes and offsets, pair tasks, pair records
+  SLOT_UNITSET_RES, SLOT_UNITSET_UNITS,                             // its sets and offsets / its units: they stay valid for the device results
+  SLOT_UNITSET_LOCUS,                                               // otg_unitset_locus: the task records before they are spread over the alleles
   SLOT_COUNT
 };
 

@@ -241,6 +241,8 @@ int otg_repeat_resident(otg_ctx* ctx, const char* who, const OtgRows& rows, uint
                         otg_repeat_sum* sums, uint64_t* seg_off, uint64_t* n_segments)
 {
   ctx->last_repeat = OtgSegLast{};
+  ctx->last_repeat_rows = OtgRows{nullptr, nullptr, nullptr};
+  ++ctx->repeat_serial;
   if (n_segments) *n_segments = 0;
   if (n == 0) {
     if (seg_off) seg_off[0] = 0;
@@ -327,6 +329,7 @@ int otg_repeat_resident(otg_ctx* ctx, const char* who, const OtgRows& rows, uint
   HIP_TRY(ctx, hipEventElapsedTime(&r_ms, ctx->ev0, ctx->ev1));
   HIP_TRY(ctx, hipEventElapsedTime(&s_ms, ctx->ev1, ctx->ev2));
   ctx->last_repeat = OtgSegLast{n, total, true, {r_ms, s_ms}};
+  ctx->last_repeat_rows = rows;
   if (n_segments) *n_segments = total;
   return OTG_OK;
 }
