@@ -1399,7 +1399,8 @@ int otg_tracts_files(const otg_tracts_job* job, otg_write_fn write, void* user, 
  *                             otg_emit_alleles.
  * A locus call runs the joint parse as its second pass, on sub-rows of the same arena, so it counts as a unit parse on the context: afterwards
  * otg_unitparse_device_results and otg_unitparse_collect give, per task, the summary of the sub-row s[begin, end) (an empty row for a task
- * without a tract: zeros) and the segments already in allele coordinates; otg_unitparse_last_ms gives the second pass.  The local pass has
+ * without a tract: zeros) and the segments already in allele coordinates; otg_unitparse_last_ms gives the second pass.  otg_assemble_spread
+ * (below) runs two locus calls, the reads' one last: after it these entries hold the READS' records by otg_spread_read.task.  The local pass has
  * the lane layout of the joint parse (every unit at a lane boundary, 4 .. 64 lanes per task) and the key of the tract mode: score * 2^16 +
  * begin in 32 bits while the allele is no longer than the bound otg_locus_core.hpp derives from the call's scores and the largest unit of
  * the set, 32 / 32 in 64 bits above.  OTG_LOCUS_WIDE=1 sends every task through the 64-bit tier, OTG_LOCUS_SEG64=1 gives every task a
@@ -1578,6 +1579,109 @@ int otg_units_files(const otg_units_job* job, otg_write_fn write, void* user, ot
  * left them in HBM.  A region whose catalogue record has units keeps them; any other region gets the set discovered from its alleles.  Rows
  * as otg_locus_emit, the units column holding the set that was used.  otg_loci_files itself is unchanged. */
 int otg_units_loci_files(const otg_loci_job* job, const otg_units_job* discover, otg_write_fn write, void* user, otg_job_stats* stats);
+
+/* ---------------------------------------------------------------------------------------------
+ * Spread: the per-read copy numbers behind each consensus allele.  Every operator above reads consensus alleles, one sequence per haplotype;
+ * this one reads the READS of an assemble batch where otg_assemble_run left them in HBM and reports, per consensus allele, the distribution
+ * of the repeat length among the reads that voted for it (somatic expansion, mosaicism, a consensus off its reads' median).  No base and no
+ * segment comes back to the host.  The reference has no counterpart; this is the definition (all integers).  The inputs are
+ * the resident batch of the latest otg_assemble_run on the context, unit sets in the layout of otg_unitparse_batch, region_set[n_regions] (a
+ * set index, or OTG_SPREAD_NONE = 0xffffffff for "this region has no set") and an otg_tract_params (NULL: the defaults).
+ *   1. Read i of region r is COUNTED when the region's status is OTG_REGION_OK, the region has a set, the read's final label is >= 0 and both
+ *      spanning flags of its descriptor are set (a reassigned non-spanning read carries a cut tract).
+ *   2. A counted read's row is the bytes its device-side otg_read names as the run left them (a read rescued by local re-alignment is the
+ *      trimmed one).  Its record is, by definition, the otg_locus record and segments of otg_locus_batch on those bytes against the region's
+ *      set with those scores.  The read is CALLED when that record's flags are 0; its value is unit_bases, its value for unit k the sum of
+ *      unit_bases over its segments with unit == k (0 without one).
+ *   3. Every consensus allele (the n_alleles records of otg_assemble_result_sizes, in that order) is parsed the same way: ref_bases and the
+ *      per-unit ref_bases are its unit_bases and per-unit sums; without a tract they are zeros and OTG_SPREAD_REF_NONE is set.
+ *   4. The members of allele a are the called reads of its region whose label equals otg_allele.label.  With m members and their values
+ *      sorted v_0 <= .. <= v_{m-1}: q[j] = v[floor(j (m - 1) / 4)], j = 0..4 (min, lower quartile, lower median, upper quartile, max); the
+ *      same independently for every unit's series over the same members.  m = 0: q is zeros and OTG_SPREAD_NO_CALLS is set.
+ *   5. For the total series only: n_below / n_above = the members with a value < / > ref_bases, sum_below = the sum of ref_bases - v and
+ *      sum_above = the sum of v - ref_bases over them (64 bits); all four are 0 under OTG_SPREAD_REF_NONE.
+ *   6. n_reads = the counted reads carrying the allele's label, n_called = m.  An allele of a region without a set: zeros and
+ *      OTG_SPREAD_NO_SET.
+ * It follows that q[0] <= .. <= q[4], that n_below + n_above <= n_called <= n_reads <= the region's read count, that letter case changes
+ * nothing, that a single-unit set gives per-unit records equal to the total, and that with identical member reads every q[j] is their
+ * common unit_bases, with n_below = n_above = 0 when that also equals ref_bases.
+ *   otg_assemble_spread         out: n_alleles records (nullable); unit_off_out: n_alleles + 1 offsets into the unit records (nullable);
+ *                               *n_unit_records (nullable) = their number, the size otg_spread_collect needs.  OTG_ERR_ARG: no completed
+ *                               run on the context, n_regions not the batch's, a set index that is neither below n_sets nor
+ *                               OTG_SPREAD_NONE, the unit-set refusals of otg_unitparse_batch, scores out of range;
+ *   otg_spread_collect          the otg_spread_unit records of the latest call: allele a's are unit_off[a] .. unit_off[a + 1], one per unit
+ *                               of its region's set in set order; a capacity too small is OTG_ERR_CAPACITY;
+ *   otg_spread_collect_reads    one otg_spread_read per read of the batch: the row as the operator saw it, the label, counted, and task = the
+ *                               read's index among the records of the reads' locus call (OTG_SPREAD_NONE for an uncounted read);
+ *   otg_spread_device_results   device pointers of all of it, valid until the next spread call on the context or otg_destroy; every output
+ *                               is nullable;
+ *   otg_spread_last_ms          HIP-event times (ms) of the latest call: *ms = the device work of the call summed (the three parts that follow
+ *                               and the row, reference and read-record kernels; not the host's planning, copies and waits between them),
+ *                               the reads' locus call, the consensus locus call, the stats kernel; every output is nullable;
+ *   otg_spread_emit             per allele of region r the row region \t label \t allele length \t units \t n_reads \t n_called \t ref \t min \t
+ *                               q1 \t median \t q3 \t max \t n_below \t n_above \t sum_below \t sum_above \t per-unit \n, the totals in unit
+ *                               bases, the per-unit column UNIT:ref:min/q1/med/q3/max joined by `,`, in copies ("%.2f" of bases / unit
+ *                               length, as otg_unitparse_emit formats its counts column); a row without a set has "." as its units and
+ *                               per-unit columns.  Regions in batch order, alleles in record order.  Buffer protocol of otg_emit_alleles.
+ * The call runs the locus mode twice, the consensus alleles first and the reads last, so it counts as a locus call (and as a unit parse) on
+ * the context: afterwards otg_locus_device_results and otg_locus_collect hold the READS' records and segments, indexed by otg_spread_read.task.
+ * The statistics are found by selection on the value bits (otg_spread_core.hpp), one wave per allele, so the depth of a region is not capped;
+ * regions of up to 256 reads keep their values in registers, deeper ones re-read the records per pass.  OTG_SPREAD_REREAD=1 sends every
+ * allele through the second tier (read once per process).
+ * ------------------------------------------------------------------------------------------- */
+#define OTG_SPREAD_NONE     0xffffffffu   /* region_set: no set; otg_spread_read.task: not counted    */
+#define OTG_SPREAD_NO_SET   1u            /* otg_spread.flags                                         */
+#define OTG_SPREAD_NO_CALLS 2u
+#define OTG_SPREAD_REF_NONE 4u
+typedef struct otg_spread {
+  uint32_t n_reads;              /* counted reads with the allele's label                            */
+  uint32_t n_called;             /* of those, the members: their locus record has a tract            */
+  uint32_t ref_bases;            /* unit_bases of the consensus allele itself                        */
+  uint32_t q[5];                 /* min, lower quartile, lower median, upper quartile, max           */
+  uint32_t n_below;              /* members with a value < ref_bases                                 */
+  uint32_t n_above;
+  uint64_t sum_below;            /* sum of ref_bases - value over them                               */
+  uint64_t sum_above;
+  uint32_t flags;                /* OTG_SPREAD_NO_SET / _NO_CALLS / _REF_NONE                        */
+  uint32_t reserved;             /* 0                                                                */
+} otg_spread;
+typedef struct otg_spread_unit {
+  uint32_t ref_bases;
+  uint32_t q[5];
+} otg_spread_unit;
+typedef struct otg_spread_read {
+  uint64_t seq_off;              /* the read's row in the batch's arena as the run left it           */
+  uint32_t seq_len;
+  int32_t  label;
+  uint32_t counted;              /* 0 / 1                                                            */
+  uint32_t task;                 /* its record of the reads' locus call, OTG_SPREAD_NONE: none       */
+} otg_spread_read;
+int otg_assemble_spread(otg_ctx* ctx, const uint8_t* unit_arena, uint64_t unit_bytes, const uint64_t* unit_off, const uint32_t* unit_len,
+                        uint32_t n_units, const uint64_t* set_first, uint32_t n_sets, const uint32_t* region_set, uint32_t n_regions,
+                        const otg_tract_params* params, otg_spread* out, uint64_t* unit_off_out, uint64_t* n_unit_records);
+int otg_spread_collect(otg_ctx* ctx, otg_spread_unit* units, uint64_t capacity);
+int otg_spread_collect_reads(otg_ctx* ctx, otg_spread_read* reads, uint32_t capacity);
+int otg_spread_device_results(otg_ctx* ctx, uint32_t* n_alleles, const otg_spread** records, const uint64_t** unit_off, uint64_t* n_unit_records,
+                              const otg_spread_unit** units, uint32_t* n_reads, const otg_spread_read** reads);
+int otg_spread_last_ms(otg_ctx* ctx, double* ms, double* reads_ms, double* consensus_ms, double* stats_ms);
+int otg_spread_emit(const otg_bed* beds, const char* chr_arena, uint32_t n_regions, const otg_region_result* regions, const otg_allele* alleles,
+                    const uint32_t* region_set, const uint64_t* set_first, const uint8_t* unit_arena, const uint64_t* unit_off,
+                    const uint32_t* unit_len, const otg_spread* records, const uint64_t* spread_unit_off, const otg_spread_unit* units, char* out,
+                    uint64_t out_capacity, uint64_t* out_len);
+/* The spread from files to rows in one call: the batch loop of otg_assemble_files (ingest, hot path, emit; the same bounded batches and
+ * shards), with otg_assemble_spread on each batch right behind its run, on the same context, and one otg_spread_emit row per allele in BED
+ * order where otg_assemble_files writes allele records; no header.  The BED is a catalogue: the units of a region are column 4 as
+ * otg_parse_bed_units reads it, one set per record; a region without units gives OTG_SPREAD_NO_SET rows.  assemble.reads_only and
+ * assemble.is_fasta must be 0.  Out-of-range scores are OTG_ERR_ARG with the message the tool prints; a unit set the locus mode refuses is
+ * OTG_ERR_ARG.  otg_assemble_files itself writes what it wrote before.  stats as otg_assemble_files. */
+typedef struct otg_spread_job {
+  otg_assemble_job assemble;     /* BAM, catalogue BED, FASTA, assemble options, batches, devices    */
+  uint32_t    match;             /* --scores match,mismatch,indel (the tool's default: 2,7,7)        */
+  uint32_t    mismatch;
+  uint32_t    indel;
+  uint32_t    min_score;         /* --min-score: 0..2^24 (the tool's default: 24)                    */
+} otg_spread_job;
+int otg_spread_files(const otg_spread_job* job, otg_write_fn write, void* user, otg_job_stats* stats);
 
 /* ---------------------------------------------------------------------------------------------
  * Indexed allele BAMs from the product's own SAM text.  Every writer above emits SAM text and every reader wants a

@@ -16,3 +16,4 @@ from ._lib import tract_emit, tracts_files  # noqa: F401
 from ._lib import unitparse_emit, unitparse_files  # noqa: F401
 from ._lib import locus_emit, loci_files  # noqa: F401
 from ._lib import unitset_emit, units_files  # noqa: F401
+from ._lib import spread_emit, spread_files  # noqa: F401

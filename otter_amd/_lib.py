@@ -38,6 +38,7 @@ EXPORTS = [
     "otg_tracts_files",
     "otg_locus_batch", "otg_locus_collect", "otg_locus_device_results", "otg_locus_last_ms", "otg_locus_last_tiers", "otg_locus_cohort", "otg_locus_emit", "otg_loci_files",
     "otg_unitset_params_default", "otg_unitset_repeats", "otg_unitset_collect", "otg_unitset_device_results", "otg_unitset_last_ms", "otg_unitset_locus", "otg_unitset_emit", "otg_units_files", "otg_units_loci_files",
+    "otg_assemble_spread", "otg_spread_collect", "otg_spread_collect_reads", "otg_spread_device_results", "otg_spread_last_ms", "otg_spread_emit", "otg_spread_files",
 ]
 
 _lib = None
@@ -764,6 +765,59 @@ class Context:
         self.assemble_run()
         return self.assemble_collect()
 
+    def assemble_spread(self, unit_sets, region_set, match=2, mismatch=7, indel=7, min_score=24, device_tensor=False):
+        """otg_assemble_spread (and otg_spread_collect, otg_spread_collect_reads) after assemble_run on this context: per consensus allele the
+        order statistics of the repeat length among the reads that voted for it, the reads parsed where the run left them in HBM
+        (include/otter_gpu.h states the rule).  unit_sets: a list of lists of byte strings; region_set: per region an index into it, or None /
+        abi.SPREAD_NONE for a region without a set -> (records [n_alleles] of abi.spread_dt, unit_off [n_alleles + 1] uint64, unit_records of
+        abi.spread_unit_dt, reads [n_reads] of abi.spread_read_dt) as numpy arrays; or with device_tensor=True as torch tensors on this
+        context's device that wrap the results in HBM without a copy (int32 [n, 16], int64 [n + 1], int32 [units, 6], int32 [reads, 6]; valid
+        until the next spread call on this context).  Afterwards the locus results on the context are the reads' records, by reads["task"]."""
+        sets, _, _ = _pack_unit_sets(unit_sets, [], [])
+        rs = np.ascontiguousarray([abi.SPREAD_NONE if q is None else q for q in region_set], dtype=np.uint32)
+        q = abi.TractParams(match, mismatch, indel, min_score)
+        na, sb = C.c_uint32(0), C.c_uint64(0)
+        if self._L.otg_assemble_result_sizes(self._h, C.byref(na), C.byref(sb)) != 0:
+            na.value = 0                                                    # (no completed run: the entry below says what is missing)
+        rec = np.zeros(na.value, dtype=abi.spread_dt)
+        unit_off = np.zeros(na.value + 1, dtype=np.uint64)
+        nu = C.c_uint64(0)
+        rc = self._L.otg_assemble_spread(self._h, *sets, abi.ptr(rs) if len(rs) else None, C.c_uint32(len(rs)), C.byref(q), None if device_tensor else abi.ptr(rec),
+                                         None if device_tensor else abi.ptr(unit_off), C.byref(nu))
+        self._check(rc, "otg_assemble_spread")
+        if device_tensor:
+            m, u2, nr = C.c_uint32(0), C.c_uint64(0), C.c_uint32(0)
+            p = [C.c_void_p() for _ in range(4)]
+            self._check(self._L.otg_spread_device_results(self._h, C.byref(m), C.byref(p[0]), C.byref(p[1]), C.byref(u2), C.byref(p[2]), C.byref(nr), C.byref(p[3])),
+                        "otg_spread_device_results")
+            assert (m.value, u2.value) == (na.value, nu.value)
+            return (self._wrap_device(p[0].value, (m.value, 16), "<i4"), self._wrap_device(p[1].value, (m.value + 1,), "<i8"),
+                    self._wrap_device(p[2].value, (u2.value, 6), "<i4"), self._wrap_device(p[3].value, (nr.value, 6), "<i4"))
+        units = np.zeros(nu.value, dtype=abi.spread_unit_dt)
+        self._check(self._L.otg_spread_collect(self._h, abi.ptr(units) if nu.value else None, C.c_uint64(nu.value)), "otg_spread_collect")
+        nr = C.c_uint32(0)
+        self._check(self._L.otg_spread_device_results(self._h, None, None, None, None, None, C.byref(nr), None), "otg_spread_device_results")
+        reads = np.zeros(nr.value, dtype=abi.spread_read_dt)
+        self._check(self._L.otg_spread_collect_reads(self._h, abi.ptr(reads) if nr.value else None, C.c_uint32(nr.value)), "otg_spread_collect_reads")
+        return rec, unit_off, units, reads
+
+    def spread_last_ms(self):
+        """(the device work of the call summed, the reads' locus call, the consensus locus call, the stats kernel) ms of the latest assemble_spread (HIP events)."""
+        return self._last_ms("otg_spread_last_ms", 4)
+
+    def locus_last(self, device_tensor=False):
+        """the locus results that lie on this context (otg_locus_device_results / otg_locus_collect) -> (records, seg_off, segs) as locus_batch
+        returns them.  After assemble_spread they are the reads' records, indexed by the task of the read records."""
+        m, t, ps, po, pg = C.c_uint32(0), C.c_uint64(0), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._check(self._L.otg_locus_device_results(self._h, C.byref(m), C.byref(ps), C.byref(po), C.byref(pg), C.byref(t)), "otg_locus_device_results")
+        recs = self._wrap_device(ps.value, (m.value, 8), "<i4")
+        off = self._wrap_device(po.value, (m.value + 1,), "<i8")
+        segs = self._wrap_device(pg.value, (t.value, 6), "<i4")
+        if device_tensor:
+            return recs, off, segs
+        return (recs.cpu().numpy().view(np.uint32).reshape(-1, 8).copy().view(abi.locus_dt).reshape(-1), off.cpu().numpy().astype(np.uint64),
+                segs.cpu().numpy().view(np.uint32).reshape(-1, 6).copy().view(abi.unitparse_seg_dt).reshape(-1))
+
 
     # ------------------------------------------------------------------ cohort (assemble -> genotype without leaving the device)
     def cohort_begin(self, n_regions, n_samples):
@@ -1482,6 +1536,25 @@ def assemble_files(bam, bed, fasta=None, read_group="", is_fasta=False, reads_on
     return _into_sinks([bs], lambda: _run_files_job("otg_assemble_files", job, abi.AssembleJob, None, bs.writer))
 
 
+def spread_files(bam, bed, fasta=None, params=None, batch_regions=0, devices=None, offset_l=1, offset_r=0, mapq=0, nonprimary=False, omit_nonspanning=False,
+                 read_quality=0.0, threads=1, match=2, mismatch=7, indel=7, min_score=24):
+    """otg_spread_files: the spread from files to rows (include/otter_gpu.h): the batch loop of assemble_files over a catalogue BED (units in
+    column 4), the spread of every batch right behind its run, one spread_emit row per consensus allele in BED order.  Returns (text bytes,
+    stats dict)."""
+    job = abi.SpreadJob()
+    a = job.assemble
+    a.bam_path = bam.encode(); a.bed_path = bed.encode(); a.fasta_path = fasta.encode() if fasta else None
+    a.read_group = b""; a.is_fasta = 0; a.reads_only = 0
+    a.params = params if params is not None else abi.default_params()
+    a.ingest = abi.IngestOpts(offset_l, offset_r, mapq, int(nonprimary), int(omit_nonspanning), threads, read_quality)
+    a.batch_regions = batch_regions
+    devs = (C.c_int32 * len(devices))(*devices) if devices else None
+    a.n_devices = len(devices) if devices else 0
+    a.devices = devs
+    job.match, job.mismatch, job.indel, job.min_score = match, mismatch, indel, min_score
+    return _run_files_job("otg_spread_files", job, abi.SpreadJob)
+
+
 def assemble_batch_plan(n_regions, batch_regions=0):
     """Batch sizes otg_assemble_files cuts a shard of n_regions into (otg_assemble_batch_plan)."""
     L = load()
@@ -1980,6 +2053,33 @@ def locus_emit(records, regions, seq_len, allele_sets, unit_sets, loci, seg_off,
     rc = L.otg_locus_emit(*args(out, need.value))
     if rc != 0:
         raise OtterGpuError("otg_locus_emit failed (%d): %s" % (rc, _err(L)))
+    return out.raw[:need.value]
+
+
+def spread_emit(beds, chr_arena, res, region_set, unit_sets, records, unit_off, unit_records):
+    """otg_spread_emit: one row per consensus allele of a collected batch (res: Context.assemble_collect; beds, chr_arena: abi.make_beds) from
+    the results of Context.assemble_spread with the same unit_sets and region_set -> text bytes."""
+    L = load()
+    sets, _, _ = _pack_unit_sets(unit_sets, [], [])
+    rs = np.ascontiguousarray([abi.SPREAD_NONE if q is None else q for q in region_set] + [abi.SPREAD_NONE], dtype=np.uint32)
+    records = np.ascontiguousarray(records, dtype=abi.spread_dt)
+    unit_off = np.ascontiguousarray(unit_off, dtype=np.uint64)
+    unit_records = np.ascontiguousarray(unit_records, dtype=abi.spread_unit_dt)
+    if records.size == 0:
+        records = np.zeros(1, dtype=abi.spread_dt)
+    if unit_records.size == 0:
+        unit_records = np.zeros(1, dtype=abi.spread_unit_dt)
+    alleles = res["alleles"] if len(res["alleles"]) else np.zeros(1, dtype=abi.allele_dt)
+    need = C.c_uint64(0)
+    args = lambda out, cap: (abi.ptr(beds), abi.ptr(chr_arena, C.c_char_p), C.c_uint32(len(res["regions"])), abi.ptr(res["regions"]), abi.ptr(alleles), abi.ptr(rs),
+                             sets[5], sets[0], sets[2], sets[3], abi.ptr(records), abi.ptr(unit_off), abi.ptr(unit_records), out, C.c_uint64(cap), C.byref(need))
+    rc = L.otg_spread_emit(*args(None, 0))
+    if rc not in (0, abi.OTG_ERR_CAPACITY):
+        raise OtterGpuError("otg_spread_emit failed (%d): %s" % (rc, _err(L)))
+    out = C.create_string_buffer(need.value + 1)
+    rc = L.otg_spread_emit(*args(out, need.value))
+    if rc != 0:
+        raise OtterGpuError("otg_spread_emit failed (%d): %s" % (rc, _err(L)))
     return out.raw[:need.value]
 
 

@@ -188,6 +188,11 @@ class AssembleJob(C.Structure):
                 ("batch_regions", C.c_uint32), ("n_devices", C.c_int32), ("devices", C.POINTER(C.c_int32))]
 
 
+class SpreadJob(C.Structure):
+    """otg_spread_job (include/otter_gpu.h)."""
+    _fields_ = [("assemble", AssembleJob), ("match", C.c_uint32), ("mismatch", C.c_uint32), ("indel", C.c_uint32), ("min_score", C.c_uint32)]
+
+
 class GenotypeJob(C.Structure):
     """otg_genotype_job (include/otter_gpu.h)."""
     _fields_ = [("bam_path", C.c_char_p), ("bed_path", C.c_char_p), ("fasta_path", C.c_char_p), ("params", otg_params),
@@ -348,6 +353,18 @@ class UnitsJob(C.Structure):
     _fields_ = [("vcf_path", C.c_char_p), ("bed_path", C.c_char_p), ("max_period", C.c_uint32), ("min_copies", C.c_uint32), ("min_span", C.c_uint32),
                 ("min_bases", C.c_uint32), ("min_share", C.c_uint32), ("redundant", C.c_uint32), ("threads", C.c_int32), ("device", C.c_int32),
                 ("batch_alleles", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# otg_spread / otg_spread_unit / otg_spread_read (include/otter_gpu.h) and the flags of the spread operator
+spread_dt = np.dtype([("n_reads", np.uint32), ("n_called", np.uint32), ("ref_bases", np.uint32), ("q", np.uint32, (5,)), ("n_below", np.uint32), ("n_above", np.uint32),
+                      ("sum_below", np.uint64), ("sum_above", np.uint64), ("flags", np.uint32), ("reserved", np.uint32)])
+spread_unit_dt = np.dtype([("ref_bases", np.uint32), ("q", np.uint32, (5,))])
+spread_read_dt = np.dtype([("seq_off", np.uint64), ("seq_len", np.uint32), ("label", np.int32), ("counted", np.uint32), ("task", np.uint32)])
+assert spread_dt.itemsize == 64 and spread_unit_dt.itemsize == 24 and spread_read_dt.itemsize == 24
+SPREAD_NONE = 0xffffffff
+SPREAD_NO_SET = 1
+SPREAD_NO_CALLS = 2
+SPREAD_REF_NONE = 4
 
 
 class JobStats(C.Structure):

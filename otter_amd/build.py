@@ -7,7 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libotter_gpu.so")
-SOURCES = ["otg_api.hip", "wfa_edit.hip", "edit_align.hip", "myers_edit.hip", "wfa_affine.hip", "wfa_affine_reg.hip", "wfa_adaptive.hip", "cluster.hip", "poa.hip", "pipeline.hip", "emit.hip", "compare.hip", "kmer_usage.hip", "vcf2mat.hip", "ingest.hip", "bedfa.hip", "dispatch.hip", "gather.hip", "cohort.hip", "genotype_edit.hip", "motif.hip", "motif_emit.hip", "repeat.hip", "repeat_emit.hip", "unitalign.hip", "unitalign_emit.hip", "unitparse.hip", "unitparse_emit.hip", "tract.hip", "tract_emit.hip", "locus.hip", "locus_emit.hip", "unitset.hip", "unitset_emit.hip"]
+SOURCES = ["otg_api.hip", "wfa_edit.hip", "edit_align.hip", "myers_edit.hip", "wfa_affine.hip", "wfa_affine_reg.hip", "wfa_adaptive.hip", "cluster.hip", "poa.hip", "pipeline.hip", "emit.hip", "compare.hip", "kmer_usage.hip", "vcf2mat.hip", "ingest.hip", "bedfa.hip", "dispatch.hip", "gather.hip", "cohort.hip", "genotype_edit.hip", "motif.hip", "motif_emit.hip", "repeat.hip", "repeat_emit.hip", "unitalign.hip", "unitalign_emit.hip", "unitparse.hip", "unitparse_emit.hip", "tract.hip", "tract_emit.hip", "locus.hip", "locus_emit.hip", "unitset.hip", "unitset_emit.hip", "spread.hip", "spread_emit.hip"]
 # host-only sources (no device code; each also builds alone, without the rest of the library): the BAM + BAI writer and merge
 HOST_SOURCES = ["bam_sink.cpp"]
 # -ffp-contract=off: the reference's clustering decisions are FP64 comparisons made without FMA
@@ -43,7 +43,8 @@ TOOLS = [(TOOL_SRC, TOOL), (os.path.join(HERE, "..", "tools", "otter_compare.cpp
          (os.path.join(HERE, "..", "tools", "otter_unitparse.cpp"), os.path.join(HERE, "..", "tools", "otter_unitparse")),
          (os.path.join(HERE, "..", "tools", "otter_tracts.cpp"), os.path.join(HERE, "..", "tools", "otter_tracts")),
          (os.path.join(HERE, "..", "tools", "otter_loci.cpp"), os.path.join(HERE, "..", "tools", "otter_loci")),
-         (os.path.join(HERE, "..", "tools", "otter_units.cpp"), os.path.join(HERE, "..", "tools", "otter_units"))]
+         (os.path.join(HERE, "..", "tools", "otter_units.cpp"), os.path.join(HERE, "..", "tools", "otter_units")),
+         (os.path.join(HERE, "..", "tools", "otter_spread.cpp"), os.path.join(HERE, "..", "tools", "otter_spread"))]
 
 
 def build_tool(force=False):

@@ -20,6 +20,7 @@
 #include "otg_unitalign.hpp"
 #include "otg_locus.hpp"
 #include "otg_unitset.hpp"
+#include "otg_spread.hpp"
 #include "otg_tract.hpp"
 #include "otg_unitparse.hpp"
 #include "otg_unitparse_core.hpp"
@@ -291,9 +292,20 @@ int alleles_text(const Bed& bed, const Batch& b, const std::vector<otg_region_re
   });
 }
 
+// otg_spread_files: the unit sets of the catalogue (one per BED record with units, the records' contiguous stretches of the unit list), the
+// set of every BED record or OTG_SPREAD_NONE, and the scores
+struct SpreadSets {
+  std::vector<uint64_t> set_first, unit_off;
+  std::vector<uint32_t> unit_len, set_of;
+  std::vector<uint8_t> arena;
+  uint64_t unit_bytes = 0;
+  otg_tract_params q{};
+};
+
 // What otg_assemble_files' threads share besides the Job: the caller's options and the open inputs.
 struct AssembleShared {
   const otg_assemble_job* j = nullptr;
+  const SpreadSets* spread = nullptr;    // otg_spread_files: the emit stage writes spread rows, not allele records
   Job J;
   Bed bed;
   BamPtr bam;
@@ -329,9 +341,31 @@ int run_batch(AssembleShared& A, otg_ctx* ctx, Batch& b, std::vector<otg_region_
   int rc = hot_path_on(ctx, P, b, &na, &sb);
   if (rc == OTG_OK) rc = collect_on(ctx, b, na, sb, rr, al, seqs);
   if (rc != OTG_OK) return rc;
+  std::vector<otg_spread> sp_rec;
+  std::vector<uint64_t> sp_off;
+  std::vector<otg_spread_unit> sp_units;
+  std::vector<uint32_t> sp_set;
+  if (A.spread) {                        // the spread of the batch that has just run, on the same context; only its records come to the host
+    const SpreadSets& S = *A.spread;
+    sp_set.assign(S.set_of.begin() + b.first, S.set_of.begin() + b.first + b.n);
+    sp_set.push_back(OTG_SPREAD_NONE);
+    sp_rec.resize((size_t)na + 1); sp_off.resize((size_t)na + 2);
+    uint64_t nu = 0;
+    rc = otg_assemble_spread(ctx, S.arena.data(), S.unit_bytes, S.unit_off.data(), S.unit_len.data(), (uint32_t)(S.unit_off.size() - 1), S.set_first.data(),
+                             (uint32_t)(S.set_first.size() - 1), sp_set.data(), b.n, &S.q, sp_rec.data(), sp_off.data(), &nu);
+    if (rc != OTG_OK) return rc;
+    sp_units.resize((size_t)nu + 1);
+    if ((rc = otg_spread_collect(ctx, sp_units.data(), nu)) != OTG_OK) return rc;
+  }
   *ms_gpu += ms_since(t0);
   t0 = Clock::now();
-  rc = alleles_text(A.bed, b, rr, al, seqs, rg, j.is_fasta, b.text);
+  if (A.spread) {
+    const SpreadSets& S = *A.spread;
+    b.text.clear();
+    otg_spread_rows(b.text, A.bed.beds.data() + b.first, A.bed.chr_arena.data(), b.n, rr.data(), al.data(), sp_set.data(), S.set_first.data(), S.arena.data(),
+                    S.unit_off.data(), S.unit_len.data(), sp_rec.data(), sp_off.data(), sp_units.data());
+  } else
+    rc = alleles_text(A.bed, b, rr, al, seqs, rg, j.is_fasta, b.text);
   *ms_emit += ms_since(t0);
   trace("emit", b.index, b.n, t0);
   {
@@ -950,31 +984,35 @@ struct UnitCatalogue {
 
 extern "C" {
 
-int otg_assemble_files(const otg_assemble_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
+static int tract_cli_args(const otg_tract_params& q);
+// otg_assemble_files, and with `spread` otg_spread_files: the same batch loop, the spread call behind the hot path, spread rows for records
+static int assemble_files_impl(const char* who, const otg_assemble_job* job, const SpreadSets* spread, otg_write_fn write, void* user, otg_job_stats* stats)
 {
-  if (!job || !write || !job->bam_path || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "otg_assemble_files: NULL job, writer, BAM or BED path");
-  if (job->n_devices < 0 || (job->n_devices > 0 && !job->devices)) return otg_fail(nullptr, OTG_ERR_ARG, "otg_assemble_files: bad device list");
+  if (!job || !write || !job->bam_path || !job->bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "%s: NULL job, writer, BAM or BED path", who);
+  if (job->n_devices < 0 || (job->n_devices > 0 && !job->devices)) return otg_fail(nullptr, OTG_ERR_ARG, "%s: bad device list", who);
   const auto t_all = Clock::now();
   g_trace_t0 = t_all;
   AssembleShared A;
   A.j = job;
+  A.spread = spread;
   Job& J = A.J;
   int rc = load_bed(job->bed_path, A.bed);
   if (rc != OTG_OK) return rc;
   const uint32_t R = (uint32_t)A.bed.beds.size();
   J.st.n_regions = R;
+  if (spread && spread->set_of.size() != R) return otg_fail(nullptr, OTG_ERR_FATAL, "%s: the two BED readers disagree on %s", who, job->bed_path);
   rc = open_bam(job->bam_path, A.bam);
   if (rc != OTG_OK) return rc;
   if (job->fasta_path && job->fasta_path[0]) {
     rc = open_fasta(job->fasta_path, A.fasta);
     if (rc != OTG_OK) return rc;
   }
-  // SAM header; FASTA output has none
-  if (!job->is_fasta) {
+  // SAM header; FASTA output and spread rows have none
+  if (!job->is_fasta && !spread) {
     std::string hdr;
     rc = sam_header_text(A.bam.get(), job->read_group ? job->read_group : "", job->ingest.offset_l, job->ingest.offset_r, hdr);
     if (rc != OTG_OK) return rc;
-    if (write(user, hdr.data(), hdr.size()) != 0) return otg_fail(nullptr, OTG_ERR_ARG, "otg_assemble_files: the writer failed");
+    if (write(user, hdr.data(), hdr.size()) != 0) return otg_fail(nullptr, OTG_ERR_ARG, "%s: the writer failed", who);
     J.st.output_bytes += hdr.size();
   }
   J.st.n_devices = run_shards<std::string>(
@@ -990,8 +1028,35 @@ int otg_assemble_files(const otg_assemble_job* job, otg_write_fn write, void* us
   trace("job", 0, R, t_all);
   J.st.ms_total = ms_since(t_all);
   if (stats) *stats = J.st;
-  if (J.rc.load() != OTG_OK) return otg_fail(nullptr, J.rc.load(), "otg_assemble_files: %s", J.err.c_str());
+  if (J.rc.load() != OTG_OK) return otg_fail(nullptr, J.rc.load(), "%s: %s", who, J.err.c_str());
   return OTG_OK;
+}
+
+int otg_assemble_files(const otg_assemble_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
+{
+  return assemble_files_impl("otg_assemble_files", job, nullptr, write, user, stats);
+}
+
+int otg_spread_files(const otg_spread_job* job, otg_write_fn write, void* user, otg_job_stats* stats)
+{
+  const char* who = "otg_spread_files";
+  if (!job || !write || !job->assemble.bam_path || !job->assemble.bed_path) return otg_fail(nullptr, OTG_ERR_ARG, "%s: NULL job, writer, BAM or BED path", who);
+  if (job->assemble.reads_only || job->assemble.is_fasta) return otg_fail(nullptr, OTG_ERR_ARG, "%s: --reads-only and --fasta do not apply to spread rows", who);
+  SpreadSets S;
+  S.q = otg_tract_params{job->match, job->mismatch, job->indel, job->min_score};
+  if (int rc = tract_cli_args(S.q)) return rc;
+  UnitCatalogue cat;
+  if (int rc = cat.load(who, job->assemble.bed_path)) return rc;
+  // a set per record with units: the records' stretches of the unit list are contiguous, so the non-empty ones tile it
+  const size_t R = cat.first.size() - 1;
+  S.set_of.assign(R, OTG_SPREAD_NONE);
+  for (size_t r = 0; r < R; ++r)
+    if (cat.first[r + 1] > cat.first[r]) { S.set_of[r] = (uint32_t)S.set_first.size(); S.set_first.push_back(cat.first[r]); }
+  S.set_first.push_back(cat.first[R]);
+  S.unit_off = cat.off; S.unit_len = cat.len; S.arena = cat.arena;
+  S.unit_off.resize((size_t)cat.first[R] + 1); S.unit_len.resize((size_t)cat.first[R] + 1);
+  S.unit_bytes = S.arena.size() - 1;
+  return assemble_files_impl(who, &job->assemble, &S, write, user, stats);
 }
 
 // `otter compare` from files to text — compare() (src/compare.cpp:68-150).  Two batches in flight: while the pairs of one are aligned on the

@@ -74,6 +74,12 @@ struct otg_ctx {
     double ms[2] = {0.0, 0.0};                                    // candidates and vote, pair alignments and select
     std::vector<uint32_t> group_first;                            // the caller's grouping (otg_unitset_locus maps alleles to sets by it)
   } last_unitset;
+  // the latest otg_assemble_spread: SLOT_SPREAD_OUT (records, unit_off, unit records) / SLOT_SPREAD_READS; ms = total, the reads' locus call,
+  // the consensus locus call, the stats kernel
+  struct SpreadLast {
+    uint32_t n_alleles = 0, n_reads = 0; uint64_t n_units = 0; bool valid = false;
+    double ms[4] = {0.0, 0.0, 0.0, 0.0};
+  } last_spread;
   uint32_t last_locus_tiers[2] = {0u, 0u};                        // tasks the narrow / the wide tier of that call's local pass took (otg_locus_last_tiers)
   double last_kernel_ms = 0.0;                    // HIP-event time of the kernels of the latest operator-level call that reports one (otg_last_kernel_ms)
   // the latest genotype clustering with a metric (genotype_edit.hip): times of its two parts (otg_genotype_metric_last_ms), whether the edit
@@ -173,6 +179,8 @@ enum {
   SLOT_UNITSET_CAND, SLOT_UNITSET_WORK, SLOT_UNITSET_TASKS, SLOT_UNITSET_PAIRS,   // otg_unitset_repeats (unitset.hip): candidates, ranked classes and offsets, pair tasks, pair records
   SLOT_UNITSET_RES, SLOT_UNITSET_UNITS,                             // its sets and offsets / its units: they stay valid for the device results
   SLOT_UNITSET_LOCUS,                                               // otg_unitset_locus: the task records before they are spread over the alleles
+  SLOT_SPREAD_META,                                                 // otg_assemble_spread (spread.hip): the rows of the reads and of the consensus alleles, their task lists
+  SLOT_SPREAD_READS, SLOT_SPREAD_OUT,                               // its read records / its records, unit offsets and unit records: they stay valid for the device results
   SLOT_COUNT
 };
 
@@ -186,6 +194,18 @@ inline void otg_region_name(std::string& o, const char* chr, uint32_t chr_len, i
 
 void otg_pipeline_free(otg_ctx* ctx);
 int64_t otg_pipeline_run_regions(otg_ctx* ctx);
+// pipeline.hip: the batch of the latest completed otg_assemble_run where it lies on the device, valid until the next submit on the context:
+// the reads' arena (64 zero bytes behind it), the read descriptors as the run left them, the regions, the final labels, the region results,
+// the consensus records and their arena (16 bytes behind it, not zeroed: exactly what the sixteen-byte loads of the locus kernels need, which
+// read at most 15 bytes past a row and never use them; the 64 zero bytes of a caller's rows are not promised here); h_regions = the submitted regions on the host.  results is NULL for a batch
+// without regions or reads, alleles and seqs without alleles.
+struct OtgAssembleView {
+  uint32_t n_reads, n_regions, n_alleles;
+  const otg_region* h_regions;
+  const uint8_t* arena; const otg_read* reads; const otg_region* regions; const int32_t* labels;
+  const otg_region_result* results; const otg_allele* alleles; const uint8_t* seqs;
+};
+bool otg_pipeline_view(otg_ctx* ctx, OtgAssembleView* view);
 void otg_cohort_free(otg_ctx* ctx);
 // ingest.hip: gives a BAM handle the sample list of a cohort job (what otg_bam_sample_index reads from an allele BAM's header)
 void otg_bam_set_samples(otg_bam* b, const char* const* names, uint32_t n, int32_t offset_l, int32_t offset_r);

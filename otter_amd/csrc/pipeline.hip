@@ -93,6 +93,24 @@ void otg_pipeline_free(otg_ctx* ctx)
 // regions of the latest completed run (cohort.hip checks a staged run against its batch); -1 without one
 int64_t otg_pipeline_run_regions(otg_ctx* ctx) { return (ctx && ctx->pipe && ctx->pipe->ran) ? (int64_t)ctx->pipe->n_regions : -1; }
 
+// where the latest completed run left its batch (spread.hip reads the reads, the labels and the consensus records in place); false without one
+bool otg_pipeline_view(otg_ctx* ctx, OtgAssembleView* v)
+{
+  if (!ctx || !ctx->pipe || !ctx->pipe->ran) return false;
+  const Pipeline* pl = ctx->pipe;
+  const bool empty = pl->n_regions == 0 || pl->n_reads == 0;
+  v->n_reads = pl->n_reads; v->n_regions = pl->n_regions; v->n_alleles = pl->out_alleles;
+  v->h_regions = pl->h_regions.data();
+  v->arena = (const uint8_t*)pl->buf[B_ARENA].p;
+  v->reads = (const otg_read*)pl->buf[B_READS].p;
+  v->regions = (const otg_region*)pl->buf[B_REGIONS].p;
+  v->labels = (const int32_t*)pl->buf[B_LABELS].p;
+  v->results = empty ? nullptr : (const otg_region_result*)pl->buf[B_REGRES].p;
+  v->alleles = pl->out_alleles ? (const otg_allele*)pl->buf[B_OUTAL].p : nullptr;
+  v->seqs = pl->out_alleles ? (const uint8_t*)pl->buf[B_OUTSEQ].p : nullptr;
+  return true;
+}
+
 namespace {
 
 __device__ __forceinline__ size_t didx(int N, int r, int c) { return (size_t)((((long long)(2 * N - 3 - r)) * r) >> 1) + c - 1; }
