@@ -9,8 +9,9 @@
 //   * Window index x = k - kbase; lane l of pair-slot g owns the two ADJACENT diagonals x = 128 g + 2 l (even, E) and + 1 (odd, O).  Every
 //     quantity of the pair travels as ONE 32-bit word {lo16: E, hi16: O} of signed 16-bit offsets (null = -32768, creeping up by one per
 //     gap extension: still negative after 8 K scores).  Per slot six words stay in VGPRs for the whole alignment: M[s-4] and M[s-2] of the
-//     current score parity, the same two of the other parity (a score only reads M rows of its own parity; the two sets trade places
-//     after every score), I[s-1] and D[s-1].  The slot loop is unrolled at compile time: every register index is static, which slots a
+//     even scores (set 0), the same two of the odd scores (set 1), I[s-1] and D[s-1].  A score only reads M rows of its own parity, and the
+//     score loop runs two scores per trip, each in a body compiled for its parity: the sets never trade places, no word moves between
+//     registers from one score to the next.  The slot loop is unrolled at compile time: every register index is static, which slots a
 //     score touches is a wave-uniform branch per slot.
 //   * The recurrence runs on PACKED 16-bit operations (v_pk_max_i16 / v_pk_add_u16 / v_pk_sub_i16 clamp / v_pk_min_u16), two cells per
 //     instruction:  X_I = max(M[s-4], I[s-1]) and X_D = max(M[s-4], D[s-1]) are taken on the pair's own words; I[s] = X_I of the diagonal
@@ -78,7 +79,6 @@ __device__ __forceinline__ void opaque_v(uint32_t& x) { asm volatile("" : "+v"(x
 // and the allocator resolves part of them with copies at the loop header (dozens of v_mov per score) and spills; tied to its register, a word
 // never moves.
 __device__ __forceinline__ void vset(uint32_t& dst, uint32_t src) { asm("v_mov_b32 %0, %1" : "+v"(dst) : "v"(src)); }
-__device__ __forceinline__ void vswap(uint32_t& a, uint32_t& b) { asm("v_swap_b32 %0, %1" : "+v"(a), "+v"(b)); }   // (hipcc refuses asm operands that are lambda captures)
 __device__ __forceinline__ uint32_t umin3(uint32_t a, uint32_t b, uint32_t c) { const uint32_t m = a < b ? a : b; return m < c ? m : c; }
 __device__ __forceinline__ uint32_t pack16(int lo, int hi) { return __builtin_amdgcn_perm((uint32_t)hi, (uint32_t)lo, 0x05040100u); }   // {lo16: lo, hi16: hi}
 __device__ __forceinline__ uint64_t uniform64(uint64_t x)
@@ -257,11 +257,11 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
       return total < rem ? total : rem;
     };
 
-    uint32_t M4[2][S2], M2[2][S2];     // [parity set][pair-slot] = {lo16: even diagonal, hi16: odd diagonal}; set 0 = the parity of the current score: M[s-4], M[s-2]
+    uint32_t M4[2][S2], M2[2][S2];     // [parity set][pair-slot] = {lo16: even diagonal, hi16: odd diagonal}; set PS = the parity of the current score: M[s-4], M[s-2]
     uint32_t WI[S2], WD[S2];           // I[s-1], D[s-1]
     static_for<0, S2>([&](auto ic) __attribute__((always_inline)) { constexpr int i = decltype(ic)::value;
       M4[0][i] = NN; M2[0][i] = NN; M4[1][i] = NN; M2[1][i] = NN; WI[i] = NN; WD[i] = NN;
-      opaque_v(M4[0][i]); opaque_v(M2[0][i]); opaque_v(M4[1][i]); opaque_v(M2[1][i]); });     // vector registers from the start (the swaps at the loop top are tied to them)
+      opaque_v(M4[0][i]); opaque_v(M2[0][i]); opaque_v(M4[1][i]); opaque_v(M2[1][i]); });     // vector registers from the start
     uint32_t slab_top = 0;                       // (a slab is a few hundred megabytes at most: 32-bit bookkeeping on the scalar unit)
     const uint32_t slab_cap = ws.slab_bytes > 0xfff00000ull ? 0xfff00000u : (uint32_t)ws.slab_bytes;
     int s_end = -1, k_end = 0;
@@ -269,7 +269,7 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
     uint32_t xlv = NN, xrv = NN;                 // (NW > 1) lane g: X_I of slot g - 1 / X_D of slot g + 1 as exported at the end of the previous score
     const int xe = kend - kbase;                 // window index of the end diagonal (end-to-end termination)
 
-    int lane2 = 2 * lane, kb = __builtin_amdgcn_readfirstlane(kbase);
+    const int lane2_0 = 2 * lane, kb_0 = __builtin_amdgcn_readfirstlane(kbase);
     const int nul16v = NUL16;
 #ifdef OTG_REG_TIMING   // where a wave's cycles go, per section of a score (s_memtime; sums over all waves land behind the visited-cell counter)
     unsigned long long tm_pre = 0, tm_sweep = 0, tm_drain = 0, tm_exp = 0, tm_bar = 0, tm_n = 0, tm_vis = 0, tm_last = __builtin_amdgcn_s_memtime();
@@ -277,16 +277,23 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
 #else
 #define OTG_TM(acc)
 #endif
-    for (int s = 0; !fail; ++s) {
-      if (s >= ws.nrows) { fail = true; break; }
+    // One score.  PS, the score's parity, is a constant of the body: M rows of set PS are this score's M[s-4] and M[s-2], set 1 - PS rests.  The loop
+    // below calls the parity-0 body for s and the parity-1 body for s + 1, so the sets never trade places.  (One body for both parities swapped them
+    // after every score: 2 S2 v_swap_b32 of 8 cycles each, unconditional because control flow around them cost more than they did.)  Returns true
+    // when the alignment is over (s_end set, or fail).
+    auto step = [&](auto pc, const int s) __attribute__((always_inline)) -> bool {
+      constexpr int PS = decltype(pc)::value;
+      const bool first = PS == 0 && s == 0;      // (only the parity-0 body holds the code of score 0)
+      if (s >= ws.nrows) { fail = true; return true; }
       // opaque to the optimiser: per-slot expressions built on these are recomputed where they are used instead of being hoisted out of
-      // the score loop into S2 live registers each (loop-invariant code motion knows nothing about register pressure)
+      // the score loop into S2 live registers each (loop-invariant code motion knows nothing about register pressure).  Once per score, in
+      // both bodies, on copies local to the score (hipcc refuses asm operands that are lambda captures).
+      int lane2 = lane2_0, kb = kb_0, xes = xe;  // (xes: the end diagonal, tested per slot as hoisted S2 results, sat in lanes of a spill register)
       asm volatile("" : "+v"(lane2));
       asm volatile("" : "+s"(kb));
-      int xes = xe;                              // the same for the end diagonal: tested per slot as hoisted S2 results, it sat in lanes of a spill register
       asm volatile("" : "+s"(xes));
       int lo, hi;
-      if (s == 0) { lo = lo0; hi = hi0; }
+      if (first) { lo = lo0; hi = hi0; }
       else {
         lo = 1 << 30; hi = -(1 << 30);
         if (r2hi >= r2lo) { lo = imin(lo, r2lo); hi = imax(hi, r2hi); }
@@ -297,24 +304,28 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
         if (hi >= lo) {
           const int room = U - s;
           lo = imax(lo, elo - room); hi = imin(hi, ehi + room);
-          if (room < 0 || hi < lo) { fail = true; break; }
+          if (room < 0 || hi < lo) { fail = true; return true; }
         }
       }
       lo = __builtin_amdgcn_readfirstlane(lo); hi = __builtin_amdgcn_readfirstlane(hi);     // wave-uniform by construction: say so, the whole score loop stays scalar
       r4lo = r3lo; r4hi = r3hi; r3lo = r2lo; r3hi = r2hi; r2lo = r1lo; r2hi = r1hi;
       int cand = NOCAND;
       int j0 = 1, j1 = 0;                        // touched pair-slots of this score (none when the score is unreachable)
-      if (hi < lo) {   // unreachable score: nothing is written, the parity sets still trade places
+      if (hi < lo) {   // unreachable score: nothing is written
+        // Only an odd score can be (1 and 3: nothing costs 1, and 3 is a gap of no bases).  An even score s >= 2 has the range of score s - 2, which was
+        // reachable by induction and lies within [-pl, tl], and an empty clipped range has left above; score 0 has its start diagonals.  So the
+        // parity-0 body carries no path that skips every slot (should the impossible happen, the next tier takes the alignment).
+        if (PS == 0) { fail = true; return true; }
         r1lo = 1; r1hi = 0; idlo = 1; idhi = 0;
         rowtab[s] = -1;
-        if (s > 2 * (oes + es * (pl + tl)) + 8) { fail = true; break; }
+        if (s > 2 * (oes + es * (pl + tl)) + 8) { fail = true; return true; }
       } else {
       r1lo = lo; r1hi = hi;
       const int xlo = lo - kbase, xhi = hi - kbase;
-      if (xlo < 2 || xhi + 3 >= CAP) { fail = true; break; }
+      if (xlo < 2 || xhi + 3 >= CAP) { fail = true; return true; }
       j0 = (xlo - 1) >> 7; j1 = (xhi + 1) >> 7;  // one diagonal of margin on both sides: a cell's provenance byte carries its neighbours' gap choices
       const int width = (j1 - j0 + 1) * 128;
-      if (slab_top + (uint32_t)width > slab_cap) { fail = true; break; }
+      if (slab_top + (uint32_t)width > slab_cap) { fail = true; return true; }
       uint8_t* brow = slab + slab_top - 128 * j0;                  // provenance byte of window index x: brow[x]
       rowtab[s] = (int64_t)slab_top - (int64_t)(kbase + 128 * j0);  // wave-uniform store (same value from every lane and every wave)
       slab_top += (uint32_t)width;
@@ -393,7 +404,7 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
       auto fin_ef = [&](int h, int v) -> bool { return h >= 0 && ((h >= tl && pl - v <= pef) || (v >= pl && tl - h <= tef)); };
 
       OTG_TM(tm_pre);
-      if (s == 0) {
+      if (first) {
         // score 0: offset max(k, 0) on every start diagonal of the range, nothing elsewhere, no I / D wavefronts.  Written as "M[-2]" = that offset
         // minus one, so that the sweep below makes M[0] out of it like any other score (mismatch term M[s-2] + 1, then the probes): an ends-free
         // alignment can have thousands of start diagonals, and pushed through the queue one by one — as this branch once did — more than 384 of
@@ -404,7 +415,7 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
           const int xE = 128 * gi + lane2, kE = kb + xE, kO = kE + 1;
           const int hE = kE > 0 ? kE : 0, vE = hE - kE, hO = kO > 0 ? kO : 0, vO = hO - kO;
           const bool validE = kE >= lo && kE <= hi && hE <= tl && vE <= pl, validO = kO >= lo && kO <= hi && hO <= tl && vO <= pl;
-          M2[0][i] = pack16(validE ? hE - 1 : NUL16, validO ? hO - 1 : NUL16);
+          M2[PS][i] = pack16(validE ? hE - 1 : NUL16, validO ? hO - 1 : NUL16);
         });
       }
       {
@@ -414,10 +425,10 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
         static_for<0, S2>([&](auto ic) __attribute__((always_inline)) { constexpr int i = decltype(ic)::value;
           const int gi = NW == 1 ? i : i * NW + ww;
           if (NW == 1 && gi + 1 == j0)             // the slot left of the first touched one: its lane 63 is the left neighbour of the sweep
-            carryI = (uint32_t)__builtin_amdgcn_readlane((int)pk_max_i16(M4[0][i], WI[i]), 63);
+            carryI = (uint32_t)__builtin_amdgcn_readlane((int)pk_max_i16(M4[PS][i], WI[i]), 63);
           if (gi < j0 || gi > j1) return;
           opaque_v(lane2);                         // nothing derived from the lane's window index is computed ahead of its slot visit (one 64-bit store address per slot otherwise)
-          const uint32_t m4 = M4[0][i], m2 = M2[0][i], wi = WI[i], wd = WD[i];
+          const uint32_t m4 = M4[PS][i], m2 = M2[PS][i], wi = WI[i], wd = WD[i];
           // what the pair offers its neighbours, and which of the two it is (sign clear = the extension wins or ties)
           const uint32_t XI = pk_max_i16(m4, wi), fI = pk_sub_sat_i16(wi, m4);
           const uint32_t fD = pk_sub_sat_i16(wd, m4);
@@ -425,7 +436,7 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
           if (NW == 1) {
             XD = gi == j0 ? pk_max_i16(m4, wd) : XDc;
             lcar = carryI; rcar = NN;
-            if constexpr (i + 1 < S2) { XDc = pk_max_i16(M4[0][i + 1], WD[i + 1]); rcar = (uint32_t)__builtin_amdgcn_readlane((int)XDc, 0); }   // the next slot's lane 0, still old
+            if constexpr (i + 1 < S2) { XDc = pk_max_i16(M4[PS][i + 1], WD[i + 1]); rcar = (uint32_t)__builtin_amdgcn_readlane((int)XDc, 0); }   // the next slot's lane 0, still old
           } else {
             XD = pk_max_i16(m4, wd);
             lcar = (uint32_t)__builtin_amdgcn_readlane((int)xlv, gi);                       // slot gi - 1
@@ -501,8 +512,8 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
             hO += sel0(selO, m2nd); hE += sel0(mmE, m2nd);
             mmO &= mmE | m2m; mmE &= m2m;             // (the odd cell of a lane whose even cell took the probe stays as it was)
           }
-          M4[0][i] = m2;
-          M2[0][i] = pack16(sel(vmE, hE, nul16v), sel(vmO, hO, nul16v));
+          M4[PS][i] = m2;
+          M2[PS][i] = pack16(sel(vmE, hE, nul16v), sel(vmO, hO, nul16v));
           if (ef) {
             // a (valid) cell can end the alignment only where it has reached the end of a sequence: h == tl, or v == pl i.e. h == pl + k
             const int hp = pl + kE;
@@ -519,7 +530,7 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
           if ((mmE | mmO) != 0ull) push2(lane_in(mmE, lane), lane_in(mmO, lane), mmE, mmO, xE, hE, hO);
         });
       }
-      if (s == 0) static_for<0, S2>([&](auto ic) __attribute__((always_inline)) { constexpr int i = decltype(ic)::value; M4[0][i] = NN; opaque_v(M4[0][i]); });     // (what stood in for M[-2])
+      if (first) static_for<0, S2>([&](auto ic) __attribute__((always_inline)) { constexpr int i = decltype(ic)::value; M4[PS][i] = NN; opaque_v(M4[PS][i]); });     // (what stood in for M[-2])
       OTG_TM(tm_sweep);
 #ifdef OTG_REG_TIMING
       tm_n += 1; tm_vis += (unsigned long long)(NW == 1 ? (j1 - j0 + 1) : ((j1 - ww + NW) / NW - (j0 - ww + NW - 1) / NW));
@@ -534,12 +545,12 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
           const int pi = 64 * gi + (lane2 >> 1);   // (from the opaque lane index: an address per slot is not kept live across the score loop)
           const uint32_t pw = PT[pi];
           if (__ballot(pw != NN)) {
-            M2[0][i] = pk_max_i16(M2[0][i], pw);
+            M2[PS][i] = pk_max_i16(M2[PS][i], pw);
             PT[pi] = NN;
           }
         });
       }
-      idlo = s == 0 ? 1 : lo; idhi = s == 0 ? 0 : hi;
+      idlo = first ? 1 : lo; idhi = first ? 0 : hi;
       OTG_TM(tm_drain);
       }
       // ---- close the score: (NW > 1) publish what the neighbouring slots need for score s + 1 — X_I / X_D from the M[s-3] of the OTHER parity
@@ -550,11 +561,11 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
         // Every slot is exported, touched or not (a slot's X words change with the score parity even while it rests), by its two edge lanes under ONE
         // execution mask; after the barrier one row read per table serves all slot visits of the next score and one more the candidates.  (Written slot
         // by slot with a lane test and a range test each, and read back one word per slot visit, this section took a fifth of the four-wave tier's time.)
-        const int np = ((s + 1) & 1) * XROW;
+        constexpr int np = (1 - PS) * XROW;       // the row of the next score's parity
         if (lane == 0 || lane == 63) {
           volatile lds_u32* dst = XT + np + (lane == 63 ? 0 : GS + 2) + ww + 1;
           static_for<0, S2>([&](auto ic) __attribute__((always_inline)) { constexpr int i = decltype(ic)::value;
-            dst[i * NW] = pk_max_i16(M4[1][i], lane == 63 ? WI[i] : WD[i]); });
+            dst[i * NW] = pk_max_i16(M4[1 - PS][i], lane == 63 ? WI[i] : WD[i]); });
           if (lane == 0) XT[np + 2 * (GS + 2) + ww] = (uint32_t)cand;
         }
         OTG_TM(tm_exp);
@@ -570,12 +581,12 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
       }
       if (cand == FAILV) fail = true;
       else if (cand != NOCAND) { s_end = s; k_end = cand; }
-      // the other parity is next.  Unconditional, also in the last pass: with the two exits above in front of them the same sixteen swaps came
-      // wrapped in a copy of the whole state out of its registers and back (80 instructions per score)
-      static_for<0, S2>([&](auto ic) __attribute__((always_inline)) { constexpr int i = decltype(ic)::value;
-        vswap(M4[0][i], M4[1][i]);
-        vswap(M2[0][i], M2[1][i]); });
-      if (s_end >= 0) break;
+      return fail || s_end >= 0;
+    };
+    // Two scores per trip.  After the loop nothing reads the M registers, so leaving after either half is the same.
+    for (int s = 0; !fail; s += 2) {
+      if (step(std::integral_constant<int, 0>{}, s)) break;
+      if (step(std::integral_constant<int, 1>{}, s + 1)) break;
     }
 
 #ifdef OTG_REG_TIMING
@@ -605,18 +616,20 @@ void otg_affine_reg_geometry(int tier, int shape, int* aln_per_block, int* block
   int a = 4, b = 4;
   switch (tier * 10 + shape) {
     // shape, waves per CU; vector registers and how many of them are spilled, scalar registers spilled (the compiler's metadata; scripts/isa_reg_loop.py).
-    // Of the default shapes (x0) none reads private memory inside its score loop; the two alternatives that spill ~100 vector registers do.
-    case 0: a = 4; b = 4; break;        // <1,8>   16   128 (10 spilled), 47
-    case 1: a = 1; b = 10; break;       // <2,4>   20    96 (none), 59
-    case 10: a = 4; b = 3; break;       // <1,12>  12   168 (11 spilled), 57
-    case 11: a = 4; b = 4; break;       // <1,12>  16   128 (98 spilled), 57
-    case 12: a = 1; b = 8; break;       // <2,6>   16   124 (none), 65
-    case 20: a = 1; b = 8; break;       // <2,8>   16   128 (8 spilled), 75
-    case 21: a = 4; b = 3; break;       // <1,16>  12   168 (112 spilled), 67
-    case 22: a = 4; b = 2; break;       // <1,16>  8    220 (none), 67
-    case 30: a = 1; b = 4; break;       // <4,8>   16   128 (8 spilled), 75
-    case 31: a = 1; b = 3; break;       // <8,4>   24    80 (9 spilled), 57
-    case 40: a = 1; b = 2; break;       // <8,8>   16   128 (8 spilled), 75
+    // Every shape runs the two-body score loop (on one MI355X all four default shapes of configs[1] gained: 161.4 / 83.9 / 73.8 / 12.6 -> 151.2 / 78.8 /
+    // 69.5 / 11.8 ms per step).  Of the default shapes (x0) none reads private memory inside its score loop; <8,4> and the two alternatives that spill
+    // ~50 vector registers do.
+    case 0: a = 4; b = 4; break;        // <1,8>   16   128 (9 spilled), 47
+    case 1: a = 1; b = 10; break;       // <2,4>   20    96 (none), 60
+    case 10: a = 4; b = 3; break;       // <1,12>  12   162 (none), 60
+    case 11: a = 4; b = 4; break;       // <1,12>  16   128 (57 spilled), 60
+    case 12: a = 1; b = 8; break;       // <2,6>   16   123 (none), 68
+    case 20: a = 1; b = 8; break;       // <2,8>   16   128 (8 spilled), 81
+    case 21: a = 4; b = 3; break;       // <1,16>  12   168 (52 spilled), 70
+    case 22: a = 4; b = 2; break;       // <1,16>  8    202 (none), 70
+    case 30: a = 1; b = 4; break;       // <4,8>   16   128 (8 spilled), 81
+    case 31: a = 1; b = 3; break;       // <8,4>   24    80 (12 spilled), 55
+    case 40: a = 1; b = 2; break;       // <8,8>   16   128 (8 spilled), 79
     // (r04, measured and not kept: <2,16> for the 4096 window — half the exchange, an even split of ~10 live slots — at 2 waves per SIMD without spills
     //  or 3 with: affine stage of a 2 500-region slice of the 1-10 kb shard 364 ms with <4,8>, 436 / 392 ms with <2,16>: occupancy weighs more)
 

@@ -5,15 +5,16 @@
     python scripts/isa_reg_loop.py                                            (compiles the file itself)
 
 The score loop is found from the control flow, not from names: it is the smallest natural loop (header, and every block that reaches a back
-edge to it without passing the header) that holds at least S2 `global_store_short` — the provenance stores, one per slot visit.  Of that loop:
+edge to it without passing the header; a back edge is an edge to a block that dominates its source) that holds at least S2 `global_store_short` — the provenance stores, one per slot visit.  Of that loop:
   * `vmcnt` waits and private-memory (`scratch_*`) accesses: the sweep's provenance stores are never read back, so a score has no reason to wait
     for vector memory; a wait there (a flag or a spilled vector register read back) also waits for every store of the sweep, in order;
+  * `v_swap_b32` and `v_mov_b32`: words of the wavefront changing registers (the loop runs two scores per trip, a body per score parity, so that none has to);
   * `v_readlane_b32` / `v_writelane_b32`: SGPR spill traffic, lane reads of the recurrence included (2 to 4 per slot visit are the carries and
     the end cell);
   * one slot visit = the instructions between the provenance stores of the two middle slots, every path of the visit (second probe, both end
     tests, the queue push) counted once: fast-class / slow-class vector instructions as scripts/isa_mix.py classifies them, `v_swap_b32` apart,
     scalar, LDS, waits.
-Registers and spill counts are the compiler's metadata."""
+Registers, spill counts and the code size are the compiler's metadata."""
 import collections
 import importlib.util
 import os
@@ -43,6 +44,16 @@ def metadata(text):
         m = re.match(r"\s+\.(private_segment_fixed_size|sgpr_count|sgpr_spill_count|vgpr_count|vgpr_spill_count|agpr_count):\s+(\d+)", ln)
         if m and cur is not None:
             cur[m.group(1)] = int(m.group(2))
+    # the size of each kernel's code (`; codeLenInByte`, in the comment block behind the kernel's body)
+    cur = None
+    for ln in text.split("\n"):
+        m = re.match(r"(_Z\S+):", ln)
+        if m:
+            cur = m.group(1)
+            continue
+        m = re.match(r"; codeLenInByte = (\d+)", ln)
+        if m and cur in out:
+            out[cur].setdefault("code_bytes", int(m.group(1)))
     return {k: v for k, v in out.items() if KERNEL in k}
 
 
@@ -81,16 +92,45 @@ def blocks_of(L):
     return blocks, succ
 
 
-def natural_loops(succ):
-    """{header: set of blocks} for every back edge (an edge to a block at or above its source in the layout), loops of one header merged"""
+def dominators(succ):
+    """{block: set of the blocks that dominate it}, block 0 the entry (iterative; a few hundred blocks)"""
+    n = len(succ)
     pred = collections.defaultdict(list)
     for a, ss in enumerate(succ):
         for b in ss:
             pred[b].append(a)
+    seen, work = {0}, [0]
+    while work:
+        for b in succ[work.pop()]:
+            if b not in seen:
+                seen.add(b); work.append(b)
+    dom = {b: ({0} if b == 0 else set(seen)) for b in seen}
+    changed = True
+    while changed:
+        changed = False
+        for b in sorted(seen):
+            if b == 0:
+                continue
+            ps = [dom[p] for p in pred[b] if p in seen]
+            new = set.intersection(*ps) | {b} if ps else {b}
+            if new != dom[b]:
+                dom[b] = new; changed = True
+    return dom
+
+
+def natural_loops(succ):
+    """{header: set of blocks} for every back edge (an edge to a block that dominates its source), loops of one header merged.  (An edge to a block
+    above its source in the layout is not enough: with two score bodies per trip the exits of the first are laid out behind the second, and
+    the "loop" of such an edge is the whole kernel.)"""
+    pred = collections.defaultdict(list)
+    for a, ss in enumerate(succ):
+        for b in ss:
+            pred[b].append(a)
+    dom = dominators(succ)
     loops = {}
     for a, ss in enumerate(succ):
         for h in ss:
-            if h > a:
+            if a not in dom or h not in dom[a]:
                 continue
             body, work = {h, a}, [a] if a != h else []
             while work:
@@ -120,6 +160,7 @@ def loop_report(ins):
             "v_readlane": sum(x.startswith("v_readlane_b32") for x in ins),
             "v_writelane": sum(x.startswith("v_writelane_b32") for x in ins),
             "v_swap": sum(x.startswith("v_swap_b32") for x in ins),
+            "v_mov": sum(x.startswith("v_mov_b32") for x in ins),
             "prov_stores": sum(x.startswith("global_store_short") for x in ins)}
 
 
@@ -198,12 +239,12 @@ def main():
             continue
         m, lp, v = r["meta"], r["loop"], r["visit"]
         print("%s<%d,%d> seq %d, %d waves/SIMD, queue %d, LB %d" % ((KERNEL,) + shp))
-        print("  registers: %d VGPR (%d spilled), %d SGPR (%d spilled), private segment %d bytes" % (
-            m["vgpr_count"], m["vgpr_spill_count"], m["sgpr_count"], m["sgpr_spill_count"], m["private_segment_fixed_size"]))
+        print("  registers: %d VGPR (%d spilled), %d SGPR (%d spilled), private segment %d bytes, code %d bytes" % (
+            m["vgpr_count"], m["vgpr_spill_count"], m["sgpr_count"], m["sgpr_spill_count"], m["private_segment_fixed_size"], m.get("code_bytes", 0)))
         if lp is None:
             print("  score loop not found"); continue
-        print("  score loop: %d instructions, %d provenance stores, %d vmcnt waits, %d private-memory accesses, %d v_readlane, %d v_writelane, %d v_swap" % (
-            lp["instructions"], lp["prov_stores"], len(lp["vmcnt_waits"]), len(lp["scratch"]), lp["v_readlane"], lp["v_writelane"], lp["v_swap"]))
+        print("  score loop: %d instructions, %d provenance stores, %d vmcnt waits, %d private-memory accesses, %d v_readlane, %d v_writelane, %d v_swap, %d v_mov" % (
+            lp["instructions"], lp["prov_stores"], len(lp["vmcnt_waits"]), len(lp["scratch"]), lp["v_readlane"], lp["v_writelane"], lp["v_swap"], lp["v_mov"]))
         if v:
             print("  slot visit: " + ", ".join("%s %d" % (k, v.get(k, 0)) for k in ("slow", "fast", "lane", "v_swap", "scalar", "branch", "lds", "wait", "vmem", "scratch"))
                   + "; about %d SIMD cycles of vector issue" % v["cycles"])
