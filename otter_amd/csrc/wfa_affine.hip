@@ -974,6 +974,18 @@ int otg_launch_affine_todo(otg_ctx* ctx, const uint8_t* d_arena, const otg_align
       }
       if (ws.dbg) fprintf(stderr, "[otg] affine: register tiers keep %u / %u / %u / %u / %u alignments in flight, workspaces %.1f GB of a budget of %.1f GB, mask %d\n",
                           al[0], al[1], al[2], al[3], al[4], (double)total() / 1e9, (double)budget_r / 1e9, reg_mask);
+      if (ws.dbg) for (int t = 0; t < OTG_REG_TIERS; ++t) {
+        if (!((reg_mask >> t) & 1)) continue;
+        int apb = 1, bpc = 1, occ = 0, lds = 0, vg = 0;
+        otg_affine_reg_geometry(t, shape[t], &apb, &bpc);
+        if (otg_affine_reg_occupancy(ctx, t, shape[t], &occ, &lds, &vg) != OTG_OK) {      // (a debug print never fails the call)
+          (void)hipGetLastError();
+          fprintf(stderr, "[otg] affine: register tier %d shape %d: %d blocks per CU launched, the runtime's figure n/a\n", t, shape[t], bpc);
+          continue;
+        }
+        fprintf(stderr, "[otg] affine: register tier %d shape %d: %d blocks per CU launched, the runtime co-schedules %d (LDS %d bytes per block, %d vector registers)\n",
+                t, shape[t], bpc, occ, lds, vg);
+      }
       uint8_t* p = wsr;
       for (int t = 0; t < OTG_REG_TIERS; ++t) { wr[t].base = p; if (p) p += wr[t].stride * al[t]; }
     }

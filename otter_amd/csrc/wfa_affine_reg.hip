@@ -13,6 +13,12 @@
 //     score loop runs two scores per trip, each in a body compiled for its parity: the sets never trade places, no word moves between
 //     registers from one score to the next.  The slot loop is unrolled at compile time: every register index is static, which slots a
 //     score touches is a wave-uniform branch per slot.
+//   * Which diagonals a score covers is a closed form of the alignment's constants (affine_score_range.hpp): start range, one diagonal more
+//     per side and score from score 2 on, clamped to the matrix, clipped to the diamond of the bound.  Score 0 — start diagonals instead of
+//     a recurrence — is a third instantiation of the score body that runs once in front of the loop; score 1, which nothing reaches, is a
+//     row-table entry; the loop starts at score 2 and neither of its bodies has a path for an unreachable score.  (Carried as a five-deep
+//     history of ranges with such a path in the odd body, every wavefront word was a phi of the loop: 8-10 vector registers spilled at 128,
+//     twice the v_mov_b32.)
 //   * The recurrence runs on PACKED 16-bit operations (v_pk_max_i16 / v_pk_add_u16 / v_pk_sub_i16 clamp / v_pk_min_u16), two cells per
 //     instruction:  X_I = max(M[s-4], I[s-1]) and X_D = max(M[s-4], D[s-1]) are taken on the pair's own words; I[s] = X_I of the diagonal
 //     to the left + 1 and D[s] = X_D of the diagonal to the right are ONE DPP wave shift + ONE 16-bit funnel shift (v_alignbit) each (lane 0
@@ -32,6 +38,7 @@
 //     slot needs cross through double-buffered LDS export tables written at the END of a score for the next one — ONE barrier per score,
 //     which also publishes the waves' termination candidates.
 #include "wfa_affine_common.hpp"
+#include "affine_score_range.hpp"
 #include "wfa_affine_reg.hpp"
 #include <cstdlib>
 
@@ -86,6 +93,13 @@ __device__ __forceinline__ uint64_t uniform64(uint64_t x)
   return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(x >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
 }
 
+// N words of LDS, none for N = 0 (an array of no elements cannot be declared): what only the multi-wave shapes use takes no LDS from the others
+template <int ID, int N> __device__ __forceinline__ uint32_t* lds_words()
+{
+  if constexpr (N > 0) { __shared__ uint32_t w[N]; return &w[0]; }
+  else return nullptr;
+}
+
 // Scheduling fence: the two probes of a lane are independent, and left alone the scheduler interleaves them with each other and with the
 // recurrence of the slot — twice the live temporaries, which in the 12- and 16-slot bodies turn into spills of the wavefront words themselves.
 #ifndef OTG_SCHED_FENCE
@@ -117,8 +131,8 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
   // (NW > 1) what the waves hand each other at the end of a score, double-buffered by score parity: [0, GS + 2) entry g + 1 = X_I of slot g's lane 63,
   // [GS + 2, 2 GS + 4) entry g + 1 = X_D of slot g's lane 0, then one termination candidate per wave
   constexpr int XROW = 2 * (GS + 2) + WAVES;
-  __shared__ uint32_t s_x[2 * XROW + 64];       // (+ 64: a row is read back by all 64 lanes)
-  __shared__ int s_misc[4];
+  uint32_t* s_x = lds_words<0, (NW > 1 ? 2 * XROW + 64 : 0)>();       // (+ 64: a row is read back by all 64 lanes; one wave per alignment exchanges nothing)
+  uint32_t* s_misc = lds_words<1, (NW > 1 ? 4 : 0)>();
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int al = NW == 1 ? wv : 0;                  // which alignment of the block this wave works on
@@ -265,7 +279,6 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
     uint32_t slab_top = 0;                       // (a slab is a few hundred megabytes at most: 32-bit bookkeeping on the scalar unit)
     const uint32_t slab_cap = ws.slab_bytes > 0xfff00000ull ? 0xfff00000u : (uint32_t)ws.slab_bytes;
     int s_end = -1, k_end = 0;
-    int r1lo = 1, r1hi = 0, r2lo = 1, r2hi = 0, r3lo = 1, r3hi = 0, r4lo = 1, r4hi = 0, idlo = 1, idhi = 0;
     uint32_t xlv = NN, xrv = NN;                 // (NW > 1) lane g: X_I of slot g - 1 / X_D of slot g + 1 as exported at the end of the previous score
     const int xe = kend - kbase;                 // window index of the end diagonal (end-to-end termination)
 
@@ -279,11 +292,11 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
 #endif
     // One score.  PS, the score's parity, is a constant of the body: M rows of set PS are this score's M[s-4] and M[s-2], set 1 - PS rests.  The loop
     // below calls the parity-0 body for s and the parity-1 body for s + 1, so the sets never trade places.  (One body for both parities swapped them
-    // after every score: 2 S2 v_swap_b32 of 8 cycles each, unconditional because control flow around them cost more than they did.)  Returns true
-    // when the alignment is over (s_end set, or fail).
-    auto step = [&](auto pc, const int s) __attribute__((always_inline)) -> bool {
+    // after every score: 2 S2 v_swap_b32 of 8 cycles each, unconditional because control flow around them cost more than they did.)  `first`
+    // marks the third instantiation, score 0, which runs once in front of the loop.  Returns true when the alignment is over (s_end set, or fail).
+    auto step = [&](auto pc, auto fc, const int s) __attribute__((always_inline)) -> bool {
       constexpr int PS = decltype(pc)::value;
-      const bool first = PS == 0 && s == 0;      // (only the parity-0 body holds the code of score 0)
+      constexpr bool first = decltype(fc)::value;     // score 0: a body of its own in front of the loop, so the two loop bodies carry none of its code
       if (s >= ws.nrows) { fail = true; return true; }
       // opaque to the optimiser: per-slot expressions built on these are recomputed where they are used instead of being hoisted out of
       // the score loop into S2 live registers each (loop-invariant code motion knows nothing about register pressure).  Once per score, in
@@ -292,38 +305,17 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
       asm volatile("" : "+v"(lane2));
       asm volatile("" : "+s"(kb));
       asm volatile("" : "+s"(xes));
+      // The range of the score, in closed form from the alignment's constants (affine_score_range.hpp): no history of earlier ranges is carried
+      // from score to score.  Past score 1, which the loop never sees, no score is unreachable, so neither loop body has a path that skips
+      // every slot — such a path makes every wavefront word a phi of the loop, and the allocator pays for it with copies and spills on the
+      // paths that do run.  Should the impossible happen, the next tier takes the alignment.
       int lo, hi;
-      if (first) { lo = lo0; hi = hi0; }
-      else {
-        lo = 1 << 30; hi = -(1 << 30);
-        if (r2hi >= r2lo) { lo = imin(lo, r2lo); hi = imax(hi, r2hi); }
-        if (r4hi >= r4lo) { lo = imin(lo, r4lo - 1); hi = imax(hi, r4hi + 1); }
-        if (idhi >= idlo) { lo = imin(lo, idlo - 1); hi = imax(hi, idhi + 1); }
-        if (lo < -pl) lo = -pl;
-        if (hi > tl) hi = tl;
-        if (hi >= lo) {
-          const int room = U - s;
-          lo = imax(lo, elo - room); hi = imin(hi, ehi + room);
-          if (room < 0 || hi < lo) { fail = true; return true; }
-        }
-      }
+      if (affine_score_range(s, lo0, hi0, pl, tl, U, elo, ehi, &lo, &hi) != RANGE_OK) { fail = true; return true; }
       lo = __builtin_amdgcn_readfirstlane(lo); hi = __builtin_amdgcn_readfirstlane(hi);     // wave-uniform by construction: say so, the whole score loop stays scalar
-      r4lo = r3lo; r4hi = r3hi; r3lo = r2lo; r3hi = r2hi; r2lo = r1lo; r2hi = r1hi;
       int cand = NOCAND;
-      int j0 = 1, j1 = 0;                        // touched pair-slots of this score (none when the score is unreachable)
-      if (hi < lo) {   // unreachable score: nothing is written
-        // Only an odd score can be (1 and 3: nothing costs 1, and 3 is a gap of no bases).  An even score s >= 2 has the range of score s - 2, which was
-        // reachable by induction and lies within [-pl, tl], and an empty clipped range has left above; score 0 has its start diagonals.  So the
-        // parity-0 body carries no path that skips every slot (should the impossible happen, the next tier takes the alignment).
-        if (PS == 0) { fail = true; return true; }
-        r1lo = 1; r1hi = 0; idlo = 1; idhi = 0;
-        rowtab[s] = -1;
-        if (s > 2 * (oes + es * (pl + tl)) + 8) { fail = true; return true; }
-      } else {
-      r1lo = lo; r1hi = hi;
       const int xlo = lo - kbase, xhi = hi - kbase;
       if (xlo < 2 || xhi + 3 >= CAP) { fail = true; return true; }
-      j0 = (xlo - 1) >> 7; j1 = (xhi + 1) >> 7;  // one diagonal of margin on both sides: a cell's provenance byte carries its neighbours' gap choices
+      const int j0 = (xlo - 1) >> 7, j1 = (xhi + 1) >> 7;  // the touched pair-slots, one diagonal of margin on both sides: a cell's provenance byte carries its neighbours' gap choices
       const int width = (j1 - j0 + 1) * 128;
       if (slab_top + (uint32_t)width > slab_cap) { fail = true; return true; }
       uint8_t* brow = slab + slab_top - 128 * j0;                  // provenance byte of window index x: brow[x]
@@ -550,9 +542,7 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
           }
         });
       }
-      idlo = first ? 1 : lo; idhi = first ? 0 : hi;
       OTG_TM(tm_drain);
-      }
       // ---- close the score: (NW > 1) publish what the neighbouring slots need for score s + 1 — X_I / X_D from the M[s-3] of the OTHER parity
       // set, which is the current one of the next score, and the I / D words just written — and this wave's candidate; one barrier; then every
       // wave sees every candidate
@@ -561,11 +551,14 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
         // Every slot is exported, touched or not (a slot's X words change with the score parity even while it rests), by its two edge lanes under ONE
         // execution mask; after the barrier one row read per table serves all slot visits of the next score and one more the candidates.  (Written slot
         // by slot with a lane test and a range test each, and read back one word per slot visit, this section took a fifth of the four-wave tier's time.)
-        constexpr int np = (1 - PS) * XROW;       // the row of the next score's parity
+        // the row of the next score's parity; the score after score 0 is score 2, and score 0 writes the row score 1 would have, so that the rows
+        // still alternate from barrier to barrier (a wave ahead by a score never writes the row a wave behind is still reading)
+        constexpr int NP = first ? PS : 1 - PS;
+        constexpr int np = first ? 0 : (1 - PS) * XROW;
         if (lane == 0 || lane == 63) {
           volatile lds_u32* dst = XT + np + (lane == 63 ? 0 : GS + 2) + ww + 1;
           static_for<0, S2>([&](auto ic) __attribute__((always_inline)) { constexpr int i = decltype(ic)::value;
-            dst[i * NW] = pk_max_i16(M4[1 - PS][i], lane == 63 ? WI[i] : WD[i]); });
+            dst[i * NW] = pk_max_i16(M4[NP][i], lane == 63 ? WI[i] : WD[i]); });
           if (lane == 0) XT[np + 2 * (GS + 2) + ww] = (uint32_t)cand;
         }
         OTG_TM(tm_exp);
@@ -583,10 +576,17 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64, WPEU) void wfa_affine_reg_
       else if (cand != NOCAND) { s_end = s; k_end = cand; }
       return fail || s_end >= 0;
     };
-    // Two scores per trip.  After the loop nothing reads the M registers, so leaving after either half is the same.
-    for (int s = 0; !fail; s += 2) {
-      if (step(std::integral_constant<int, 0>{}, s)) break;
-      if (step(std::integral_constant<int, 1>{}, s + 1)) break;
+    // Score 0 once; score 1 is unreachable (nothing costs 1): its row-table entry says so, nothing else is written and no wave waits for another.
+    // Then two scores per trip.  After the loop nothing reads the M registers, so leaving after either half is the same.
+    if (!fail && !step(std::integral_constant<int, 0>{}, std::true_type{}, 0)) {
+      if (1 >= ws.nrows) fail = true;
+      else {
+        rowtab[1] = -1;
+        for (int s = 2;; s += 2) {
+          if (step(std::integral_constant<int, 0>{}, std::false_type{}, s)) break;
+          if (step(std::integral_constant<int, 1>{}, std::false_type{}, s + 1)) break;
+        }
+      }
     }
 
 #ifdef OTG_REG_TIMING
@@ -617,19 +617,21 @@ void otg_affine_reg_geometry(int tier, int shape, int* aln_per_block, int* block
   switch (tier * 10 + shape) {
     // shape, waves per CU; vector registers and how many of them are spilled, scalar registers spilled (the compiler's metadata; scripts/isa_reg_loop.py).
     // Every shape runs the two-body score loop (on one MI355X all four default shapes of configs[1] gained: 161.4 / 83.9 / 73.8 / 12.6 -> 151.2 / 78.8 /
-    // 69.5 / 11.8 ms per step).  Of the default shapes (x0) none reads private memory inside its score loop; <8,4> and the two alternatives that spill
-    // ~50 vector registers do.
-    case 0: a = 4; b = 4; break;        // <1,8>   16   128 (9 spilled), 47
-    case 1: a = 1; b = 10; break;       // <2,4>   20    96 (none), 60
-    case 10: a = 4; b = 3; break;       // <1,12>  12   162 (none), 60
-    case 11: a = 4; b = 4; break;       // <1,12>  16   128 (57 spilled), 60
-    case 12: a = 1; b = 8; break;       // <2,6>   16   123 (none), 68
-    case 20: a = 1; b = 8; break;       // <2,8>   16   128 (8 spilled), 81
-    case 21: a = 4; b = 3; break;       // <1,16>  12   168 (52 spilled), 70
-    case 22: a = 4; b = 2; break;       // <1,16>  8    202 (none), 70
-    case 30: a = 1; b = 4; break;       // <4,8>   16   128 (8 spilled), 81
-    case 31: a = 1; b = 3; break;       // <8,4>   24    80 (12 spilled), 55
-    case 40: a = 1; b = 2; break;       // <8,8>   16   128 (8 spilled), 79
+    // 69.5 / 11.8 ms per step).  With the score ranges in closed form and score 0 in front of the loop no shape spills a vector register or reads
+    // private memory, and the registers leave room for one more wave per SIMD in the default shapes.  Kept where the shape's own kernel time fell
+    // (configs[1], ms per step at the old -> the higher figure): <1,12> 3 -> 4 blocks per CU 143.4 -> 126.4, <2,8> 8 -> 10 65.0 -> 60.1, <4,8> 4 -> 5
+    // 10.8 -> 9.6; <1,8> at 5 (which the runtime does co-schedule: 5 x 32 768 bytes of LDS) 73.45 -> 73.44, so it stays at 4.
+    case 0: a = 4; b = 4; break;        // <1,8>    16   91 (none), 36
+    case 1: a = 1; b = 10; break;       // <2,4>   20    87 (none), 45
+    case 10: a = 4; b = 4; break;       // <1,12>   16   116 (none), 51
+    case 11: a = 4; b = 4; break;       // <1,12>  16   109 (none), 51
+    case 12: a = 1; b = 8; break;       // <2,6>   16    99 (none), 57
+    case 20: a = 1; b = 10; break;      // <2,8>    20   96 (none), 65
+    case 21: a = 4; b = 3; break;       // <1,16>  12   134 (none), 62
+    case 22: a = 4; b = 2; break;       // <1,16>  8    140 (none), 62
+    case 30: a = 1; b = 5; break;       // <4,8>    20   96 (none), 65
+    case 31: a = 1; b = 3; break;       // <8,4>   24    80 (none), 43
+    case 40: a = 1; b = 2; break;       // <8,8>   16    96 (none), 65
     // (r04, measured and not kept: <2,16> for the 4096 window — half the exchange, an even split of ~10 live slots — at 2 waves per SIMD without spills
     //  or 3 with: affine stage of a 2 500-region slice of the 1-10 kb shard 364 ms with <4,8>, 436 / 392 ms with <2,16>: occupancy weighs more)
 
@@ -638,30 +640,59 @@ void otg_affine_reg_geometry(int tier, int shape, int* aln_per_block, int* block
   *aln_per_block = a; *blocks_per_cu = b;
 }
 
+// The instantiations: X(case = tier * 10 + shape, NW, S2, SEQB, WPEU[, QCAP[, LB]]).  One list, expanded by the launch and by the occupancy query.
+// (Without the listed ones: a compile-time probe of the two main bodies, -DOTG_REG_PROBE.)
+#ifndef OTG_REG_PROBE
+#define OTG_REG_SHAPES(X)    \
+  X(0, 1, 8, 4096, 4)        \
+  X(30, 4, 8, 8192, 4)       \
+  X(1, 2, 4, 4096, 5, 256)   \
+  X(10, 1, 12, 4608, 3)      \
+  X(11, 1, 12, 4608, 4, 512, 0) \
+  X(12, 2, 6, 4608, 4)       \
+  X(20, 2, 8, 6144, 4)       \
+  X(21, 1, 16, 6144, 3, 512, 1) \
+  X(22, 1, 16, 6144, 2)      \
+  X(31, 8, 4, 8192, 6, 256)  \
+  X(40, 8, 8, 12288, 4)
+#else
+#define OTG_REG_SHAPES(X) X(0, 1, 8, 4096, 4) X(30, 4, 8, 8192, 4)
+#endif
+
+// What the runtime says about an instantiation (the debug line of the launch chain, OTG_DEBUG): the blocks it co-schedules on one CU, the
+// authority on occupancy — registers, LDS with its allocation granule and wave slots all enter — and the kernel's LDS bytes and registers.
+int otg_affine_reg_occupancy(otg_ctx* ctx, int tier, int shape, int* blocks_per_cu, int* lds_bytes, int* vgprs)
+{
+  hipFuncAttributes at{};
+  int nb = 0;
+#define OTG_REG_QUERY(CASE, NWV, S2V, SEQV, WPEUV, ...)                                                                                             \
+  case CASE: {                                                                                                                                       \
+    auto kern = wfa_affine_reg_kernel<NWV, S2V, SEQV, WPEUV, ##__VA_ARGS__>;                                                                         \
+    HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, NWV == 1 ? 256 : NWV * 64, 0));                                             \
+    HIP_TRY(ctx, hipFuncGetAttributes(&at, reinterpret_cast<const void*>(kern)));                                                                    \
+  } break;
+  switch (tier * 10 + shape) {
+    OTG_REG_SHAPES(OTG_REG_QUERY)
+    default: return otg_fail(ctx, OTG_ERR_ARG, "no register tier %d shape %d", tier, shape);
+  }
+#undef OTG_REG_QUERY
+  *blocks_per_cu = nb; *lds_bytes = (int)at.sharedSizeBytes; *vgprs = at.numRegs;
+  return OTG_OK;
+}
+
 // One tier launch: `shape` selects among the instantiations of a window (0 = the default of the chain).
 int otg_launch_affine_reg_tier(otg_ctx* ctx, int tier, int shape, uint32_t blocks, const uint8_t* d_arena, const otg_align_task* d_tasks,
                                const uint32_t* d_sorted, const uint32_t* d_seg, int g, int32_t* d_scores, const uint64_t* d_cig_off,
                                uint32_t* d_cig_len, uint8_t* d_cig_arena, uint64_t* d_cells, uint32_t* ticket, uint32_t* n_overflow,
                                uint32_t* overflow_list, const AffWs& ws, const int32_t* d_bound, unsigned long long* visited)
 {
-#define OTG_REG_LAUNCH(NWV, S2V, SEQV, WPEUV, ...)                                                                                              \
-  hipLaunchKernelGGL((wfa_affine_reg_kernel<NWV, S2V, SEQV, WPEUV, ##__VA_ARGS__>), dim3(blocks), dim3(NWV == 1 ? 256 : NWV * 64), 0, ctx->stream, d_arena, \
-                     d_tasks, d_sorted, d_seg, g, d_scores, d_cig_off, d_cig_len, d_cig_arena, d_cells, ticket, n_overflow, overflow_list, ws, d_bound, visited)
+#define OTG_REG_LAUNCH(CASE, NWV, S2V, SEQV, WPEUV, ...)                                                                                        \
+  case CASE:                                                                                                                                     \
+    hipLaunchKernelGGL((wfa_affine_reg_kernel<NWV, S2V, SEQV, WPEUV, ##__VA_ARGS__>), dim3(blocks), dim3(NWV == 1 ? 256 : NWV * 64), 0, ctx->stream, d_arena, \
+                       d_tasks, d_sorted, d_seg, g, d_scores, d_cig_off, d_cig_len, d_cig_arena, d_cells, ticket, n_overflow, overflow_list, ws, d_bound, visited); \
+    break;
   switch (tier * 10 + shape) {
-    case 0: OTG_REG_LAUNCH(1, 8, 4096, 4); break;
-    case 30: OTG_REG_LAUNCH(4, 8, 8192, 4); break;
-#ifndef OTG_REG_PROBE       // (a compile-time probe of the two main bodies: -DOTG_REG_PROBE)
-    case 1: OTG_REG_LAUNCH(2, 4, 4096, 5, 256); break;
-    case 10: OTG_REG_LAUNCH(1, 12, 4608, 3); break;
-    case 11: OTG_REG_LAUNCH(1, 12, 4608, 4, 512, 0); break;
-    case 12: OTG_REG_LAUNCH(2, 6, 4608, 4); break;
-    case 20: OTG_REG_LAUNCH(2, 8, 6144, 4); break;
-    case 21: OTG_REG_LAUNCH(1, 16, 6144, 3, 512, 1); break;
-    case 22: OTG_REG_LAUNCH(1, 16, 6144, 2); break;
-    case 31: OTG_REG_LAUNCH(8, 4, 8192, 6, 256); break;
-    case 40: OTG_REG_LAUNCH(8, 8, 12288, 4); break;
-
-#endif
+    OTG_REG_SHAPES(OTG_REG_LAUNCH)
     default: return otg_fail(ctx, OTG_ERR_ARG, "no register tier %d shape %d", tier, shape);
   }
 #undef OTG_REG_LAUNCH

@@ -1,5 +1,5 @@
 // wfa_affine_reg.hpp — host-side entry of the register-resident gap-affine tiers (wfa_affine_reg.hip), called by the launch chain in
-// wfa_affine.hip.  Tier = window: 0 = 1024 diagonals (one wave x 8 pair-slots), 1 = 1536 (1 x 12), 2 = 2048 (1 x 16), 3 = 4096 (4 waves x 8),
+// wfa_affine.hip.  Tier = window: 0 = 1024 diagonals (one wave x 8 pair-slots), 1 = 1536 (1 x 12), 2 = 2048 (2 waves x 8), 3 = 4096 (4 x 8),
 // 4 = 8192 (8 x 8).
 #pragma once
 #include "wfa_affine_common.hpp"
@@ -11,6 +11,8 @@ constexpr int OTG_REG_SEQB[OTG_REG_TIERS] = {4096, 4608, 6144, 8192, 12288};
 // multi-wave shapes: one alignment per block of NW waves).  `shape` selects among the instantiations of a window (0 = the chain's default;
 // the others are measurement switches, OTG_REG_SHAPE = one digit per tier).
 void otg_affine_reg_geometry(int tier, int shape, int* aln_per_block, int* blocks_per_cu);
+// what hipOccupancyMaxActiveBlocksPerMultiprocessor and hipFuncGetAttributes say about the instantiation (read by the chain's debug line)
+int otg_affine_reg_occupancy(otg_ctx* ctx, int tier, int shape, int* blocks_per_cu, int* lds_bytes, int* vgprs);
 
 int otg_launch_affine_reg_tier(otg_ctx* ctx, int tier, int shape, uint32_t blocks, const uint8_t* d_arena, const otg_align_task* d_tasks,
                                const uint32_t* d_sorted, const uint32_t* d_seg, int g, int32_t* d_scores, const uint64_t* d_cig_off,
